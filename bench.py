@@ -16,33 +16,88 @@ max-over-ranks time.  MP/s follows the reference's definition xsize*ysize*1e-6/e
 Prints ONE JSON line on rank 0.
 """
 import argparse
+import functools
 import json
 import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # the few streams in use (two frame sets x two, the copy stream, the shared pool) each on a hardware queue of their own
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured achievable rate
+DUMP_SAMPLES = 2048  # --dump-outputs: seeded sample positions per frame
+DUMP_CROP = 512      # --dump-outputs: side of the full-resolution crop of each distinct frame
+DUMP_CROP_FRAMES = 8
 
 
-def make_stream(xsize, ysize, distance, seed=177, max_clusters=0, ac_code_mode=0):
+@functools.lru_cache(maxsize=None)
+def _encoder_digest():
+    import hashlib
     import libjxl_amd as J
-    cache = "/tmp/libjxl_amd_bench_%dx%d_d%.2f_s%d_c%d_m%d.jxl" % (xsize, ysize, distance, seed, max_clusters, ac_code_mode)
+    with open(J.ENC_PATH, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()[:16]
+
+
+def cached_stream(name, encode):
+    """A synthetic benchmark stream, cached in the build directory under the digest of the encoder library that wrote it
+    (a rebuilt encoder never reads a stream another build wrote; the encoder is deterministic, so the bytes are the same
+    whether they come from the cache or not)."""
+    import libjxl_amd as J
+    cache = os.path.join(os.path.dirname(J.ENC_PATH), "bench_cache", "%s_%s.jxl" % (name, _encoder_digest()))
     if os.path.exists(cache):
         return open(cache, "rb").read()
-    img = J.synth_image(xsize, ysize, seed)
-    data = J.encode_rgb8(img, distance=distance, strategy_mode=1, max_clusters=max_clusters, ac_code_mode=ac_code_mode)
+    data = encode()
     try:
+        os.makedirs(os.path.dirname(cache), exist_ok=True)
         tmp = cache + ".%d" % os.getpid()
         open(tmp, "wb").write(data)
         os.replace(tmp, cache)
     except OSError:
         pass
     return data
+
+
+def make_stream(xsize, ysize, distance, seed=177, max_clusters=0, ac_code_mode=0):
+    import libjxl_amd as J
+    return cached_stream("%dx%d_d%.2f_s%d_c%d_m%d" % (xsize, ysize, distance, seed, max_clusters, ac_code_mode),
+                         lambda: J.encode_rgb8(J.synth_image(xsize, ysize, seed), distance=distance, strategy_mode=1,
+                                               max_clusters=max_clusters, ac_code_mode=ac_code_mode))
+
+
+def dump_positions(frames, h, w, nc):
+    """Where --dump-outputs looks in `frames` results of h x w x nc: per frame sample positions ys, xs ([frames, n], drawn
+    by a fixed seed; 24 MiB of float32 at most) and the crop (y, x, rows, columns) around the 256x256 group corner nearest
+    the middle of the frame."""
+    import numpy as np
+    n = max(1, min(DUMP_SAMPLES, (24 << 20) // (frames * nc * 4)))
+    rng = np.random.default_rng(177)
+    ys, xs = rng.integers(0, h, (frames, n)), rng.integers(0, w, (frames, n))
+    ch, cw = min(DUMP_CROP, h), min(DUMP_CROP, w)
+    cy = min(max(0, h // 2 // 256 * 256 - ch // 2), h - ch)
+    cx = min(max(0, w // 2 // 256 * 256 - cw // 2), w - cw)
+    return ys, xs, (cy, cx, ch, cw)
+
+
+def dump_outputs(path, ctxs, fetch, ndistinct):
+    """--dump-outputs: what the last timed step left in `ctxs`, the frames a caller of the timed path receives, as float32
+    .npy files under `path` (56 MiB at most): `pixels_sample` = every frame's samples at the positions of dump_positions
+    ([frames, positions, channels]), `pixels_crops` = its crop of each of the first DUMP_CROP_FRAMES frames, which hold
+    the distinct inputs ([frames, rows, columns, channels]). `fetch(ctx)` downloads one context's whole HxWxC result."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    first = fetch(ctxs[0])
+    h, w, nc = first.shape
+    ys, xs, (cy, cx, ch, cw) = dump_positions(len(ctxs), h, w, nc)
+    sample = np.empty((len(ctxs), ys.shape[1], nc), np.float32)
+    crops = []
+    for i, c in enumerate(ctxs):
+        img = first if i == 0 else fetch(c)
+        sample[i] = img[ys[i], xs[i]]
+        if i < min(ndistinct, DUMP_CROP_FRAMES):
+            crops.append(img[cy:cy + ch, cx:cx + cw].astype(np.float32))
+    np.save(os.path.join(path, "pixels_sample.npy"), sample)
+    np.save(os.path.join(path, "pixels_crops.npy"), np.stack(crops))
 
 
 def cpu_baseline(data, xsize, ysize, budget_s=20.0):
@@ -363,19 +418,8 @@ def lossless_main(args, J, sharding, torch, dist, rank, local_rank, world, xsize
     flags = J.LOSSLESS_RCT | J.LOSSLESS_SQUEEZE | J.LOSSLESS_WP
     if args.lossless_flags >= 0:  # measurement aid: other feature sets of the synthetic encoder
         flags = args.lossless_flags
-    datas = []
-    for i in range(ndistinct):
-        cache = "/tmp/libjxl_amd_bench_lossless_%dx%d_s%d_f%d.jxl" % (xsize, ysize, 177 + i, flags)
-        if os.path.exists(cache):
-            datas.append(open(cache, "rb").read())
-            continue
-        d = J.encode_lossless(J.synth_image(xsize, ysize, 177 + i), flags)
-        try:
-            open(cache + ".%d" % os.getpid(), "wb").write(d)
-            os.replace(cache + ".%d" % os.getpid(), cache)
-        except OSError:
-            pass
-        datas.append(d)
+    datas = [cached_stream("lossless_%dx%d_s%d_f%d" % (xsize, ysize, 177 + i, flags),
+                           lambda i=i: J.encode_lossless(J.synth_image(xsize, ysize, 177 + i), flags)) for i in range(ndistinct)]
     frames = [J.ModFrame(d) for d in datas]
     ctxs = [J.HipContext(local_rank) for _ in range(batch)]
     for i, c in enumerate(ctxs):
@@ -399,6 +443,8 @@ def lossless_main(args, J, sharding, torch, dist, rank, local_rank, world, xsize
     elapsed = time.perf_counter() - t0
     total_frames, max_elapsed = sharding.aggregate(batch * args.steps, elapsed, dist)
     launch_ms = ctxs[0].stage_ms(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctxs, lambda c: c.pixels(), ndistinct)
     if rank == 0:
         px = xsize * ysize
         comp = sum(len(d) for d in datas) / float(ndistinct)
@@ -462,6 +508,18 @@ def encode_main(args, J, sharding, torch, dist, rank, local_rank, world, xsize, 
     barrier()
     elapsed = time.perf_counter() - t0
     total_frames, max_elapsed = sharding.aggregate(batch * args.steps, elapsed, dist)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        # enc_rerun keeps its results on the device: the same forward call once more on the same input, with what a caller
+        # of jxlhip_enc_forward receives copied back (arrays over 2M entries as a sample at positions drawn by a fixed seed)
+        model = J.enc_forward_model(img, ctx, distance=args.distance, cfl_fit=1)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        rng = np.random.default_rng(177)
+        for name in ("acs", "qf", "dc", "coeffs"):
+            a = model[name]
+            if a.size > (2 << 20):
+                a = a.reshape(-1)[np.sort(rng.integers(0, a.size, 2 << 20))]
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float32))
     if rank == 0:
         px = xsize * ysize
         # forward transform kernel: reads the three f32 planes once, writes int32 coefficients once
@@ -559,7 +617,15 @@ def main():
                     help="--workload lossless: feature bits of the synthetic encoder (libjxl_amd.LOSSLESS_*) instead of RCT + Squeeze + WP")
     ap.add_argument("--launch-check", action="store_true",
                     help="only check the multi-rank launch (gloo, no GPU needed): every rank reports, rank 0 prints the ranks it saw")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed on rank 0 to DIR/<name>.npy (float32, a sample at "
+                         "positions drawn by a fixed seed where the whole would pass 56 MiB): the frames' pixels (vardct, "
+                         "lossless); for encode, the forward call once more on the same input")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.shard == "bands" and args.gpus > 1:
+        ap.error("--dump-outputs needs whole frames on rank 0: --shard frames")
     xsize, ysize = [int(v) for v in args.size.split("x")]
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -714,6 +780,7 @@ def main():
     step_no = [0]
 
     def step():
+        """Enqueues one step; returns the contexts whose pixels it writes."""
         k = step_no[0]
         step_no[0] += 1
         if free_running:
@@ -724,7 +791,7 @@ def main():
                 J.run_entropy_batch(cs)
                 J.run_transform_batch(cs)
                 J.run_filter_color_batch(cs)
-            return sets[0]
+            return [c for cs in sets for c in cs]
         ent = sets[k % nsets]
         down = sets[(k + 1) % nsets]
         if three:
@@ -750,7 +817,7 @@ def main():
         # No host synchronisation inside a step: all work of a set is ordered on that set's first stream (entropy ->
         # transform -> filter -> next entropy ...), the two sets' streams overlap on the device, and the host only
         # enqueues. The timed region is closed by the barrier's device synchronisation.
-        return ent
+        return down
 
     def barrier():
         if dist is not None:
@@ -768,9 +835,11 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (before the isolated launches below overwrite the pixels of sets[0])
+        dump_outputs(args.dump_outputs, last, lambda c: c.rgb8(), ndistinct)
     # duration of the entropy launches: HIP events on the stream each batch kernel was launched on; the events of the
     # last launch of every set are still in place after the region
     if free_running:  # frames-weighted mean of the sets' last entropy launches, expressed per whole batch like the other modes

@@ -1034,6 +1034,34 @@ def test_the_pipelined_bench_ends_when_the_runtime_runs_kernels_one_at_a_time(bu
     assert line["value"] > 0 and line["steps"] == 3
 
 
+@pytest.mark.parametrize("schedule", [[], ["--two-set"], ["--no-pipeline"], ["--sets", "3"]])
+def test_bench_dumps_the_pixels_of_its_last_step(built, tmp_path, schedule):
+    """bench.py --dump-outputs: float32 arrays of at most 64 MB holding the frames the last timed step decoded -- pixel for
+    pixel what a one-frame decode of the same stream gives -- whichever frame sets the schedule finished in that step."""
+    import os
+    import subprocess
+    import sys
+    J = built
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--size", "768x512", "--batch", "12", "--distinct", "2", "--steps", "3", "--warmup", "1",
+           "--no-cpu-baseline", "--e2e-frames", "0", "--no-libjxl-tables", "--dump-outputs", str(out)] + schedule
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(out)) == ["pixels_crops.npy", "pixels_sample.npy"]
+    crops, sample = np.load(out / "pixels_crops.npy"), np.load(out / "pixels_sample.npy")
+    assert crops.dtype == sample.dtype == np.float32 and crops.nbytes + sample.nbytes <= 64 << 20
+    refs = [J.decode_rgb8(bench.make_stream(768, 512, 1.0, 177 + k)).astype(np.float32) for k in range(2)]
+    ys, xs, (cy, cx, ch, cw) = bench.dump_positions(12, 512, 768, 3)
+    assert sample.shape == ys.shape + (3,) and crops.shape == (2, ch, cw, 3)
+    for i in range(12):  # (the frames of every set cycle through the distinct streams)
+        assert np.array_equal(sample[i], refs[i % 2][ys[i], xs[i]]), "frame %d" % i
+    for k in range(2):
+        assert np.array_equal(crops[k], refs[k][cy:cy + ch, cx:cx + cw])
+
+
 @pytest.mark.parametrize("filter_async", [0, 1])
 def test_band_halos_through_an_asynchronous_transport(built, filter_async):
     """The set forms jxlhip_halo_pack_batch / _unpack_batch with a transport that is what RCCL is to this library: work on
