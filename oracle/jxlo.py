@@ -89,6 +89,19 @@ class Decoded:
         v = [float(x) for x in a]
         return {"dc_step": v[0:3], "quant_scale": v[3], "epf_quant_mul": v[4], "epf_sharp_lut": v[5:13]}
 
+    @property
+    def quant_header(self):
+        """The quantiser fields of the VarDCT frame's headers as coded (Quantizer, DequantMatrices::DecodeDC, the frame
+        header's x_qm_scale / b_qm_scale, ColorCorrelation::DecodeDC)."""
+        a = (ctypes.c_float * 10)()
+        L = lib()
+        L.jxlo_quant_header.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+        L.jxlo_quant_header.restype = None
+        L.jxlo_quant_header(self._h, a)
+        v = [float(x) for x in a]
+        return {"global_scale": int(v[0]), "quant_dc": int(v[1]), "dc_quant": v[2:5], "x_qm_scale": int(v[5]),
+                "b_qm_scale": int(v[6]), "color_factor": int(v[7]), "base_corr_x": v[8], "base_corr_b": v[9]}
+
     def buffer(self, name):
         n = ctypes.c_size_t()
         p = lib().jxlo_buffer(self._h, name.encode(), ctypes.byref(n))

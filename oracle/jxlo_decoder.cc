@@ -49,6 +49,9 @@ struct Decoded {
   std::vector<float> dc_unsmoothed;  // the same before AdaptiveDCSmoothing (kept for the tests' third reading of it)
   float dc_step[3] = {0, 0, 0};      // DC quantisation step per channel (what the smoothing measures its gap in)
   float sigma_params[10] = {0};      // quant_scale, epf_quant_mul, epf_sharp_lut[8] (inputs of ComputeSigma)
+  // the quantiser fields of the (last) VarDCT frame's headers as coded: global_scale, quant_dc, dc_quant[3], x_qm_scale,
+  // b_qm_scale, color_factor, base_corr_x, base_corr_b
+  float quant_header[10] = {0};
   std::vector<uint8_t> acs;        // ysize_blocks x xsize_blocks: (strategy<<1)|is_first
   std::vector<int32_t> quant;      // raw quant field (valid at first blocks)
   std::vector<uint8_t> sharpness;
@@ -127,6 +130,15 @@ static void DecodeDcGlobal(BitReader& br, FrameState* s) {
       s->ytox_dc = int32_t(br.Read(8)) - 128;
       s->ytob_dc = int32_t(br.Read(8)) - 128;
     }
+    float* qh = s->out->quant_header;
+    qh[0] = float(s->global_scale);
+    qh[1] = float(s->quant_dc);
+    for (int c = 0; c < 3; c++) qh[2 + c] = s->dq.dc_quant[c];
+    qh[5] = float(fh.x_qm_scale);
+    qh[6] = float(fh.b_qm_scale);
+    qh[7] = float(s->color_factor);
+    qh[8] = s->base_corr_x;
+    qh[9] = s->base_corr_b;
   }
   // Modular global info
   if (br.ReadBool()) {
@@ -1172,6 +1184,10 @@ const void* jxlo_buffer(JxloHandle* h, const char* name, size_t* nbytes) {
 void jxlo_dc_params(JxloHandle* h, float* out) {
   for (int i = 0; i < 3; i++) out[i] = h->d.dc_step[i];
   for (int i = 0; i < 10; i++) out[3 + i] = h->d.sigma_params[i];
+}
+
+void jxlo_quant_header(JxloHandle* h, float* out) {
+  for (int i = 0; i < 10; i++) out[i] = h->d.quant_header[i];
 }
 
 // Known-answer hook for the colour stage: n XYB triples, planar [3][n], through XybToRgb (+ the sRGB transfer function
