@@ -107,6 +107,7 @@ typedef struct JxlHipPatches {
   const float* slot_alpha[4];
 } JxlHipPatches;
 
+typedef struct JxlHipColorTarget JxlHipColorTarget;
 typedef struct JxlHipFrameDesc {
   uint32_t xsize, ysize;
   uint32_t xsize_blocks, ysize_blocks;
@@ -214,6 +215,9 @@ typedef struct JxlHipFrameDesc {
    * (dec_frame.cc:206-212). The decoded channel is upsampled in front of the loop filters
    * (render_pipeline/stage_chroma_upsampling.cc:29-111, dec_cache.cc:138-150). */
   uint8_t chroma_hshift[3], chroma_vshift[3];
+  /* An XYB frame's output encoding when it is not (linear) sRGB or tone mapping applies (JxlHipColorTarget, below; copied by
+   * the upload): NULL = none. linear_output must then be 1 and opsin_inv the target's matrix. */
+  const struct JxlHipColorTarget* color_target;
 } JxlHipFrameDesc;
 
 int jxlhip_device_count(void);
@@ -346,6 +350,40 @@ int jxlhip_halo_unpack_batch(JxlHipContext* const* ctxs, size_t n, int side, con
  * For the reference's closed-form colour tests (lib/jxl/opsin_image_test.cc) against the kernel itself. */
 int jxlhip_debug_color(JxlHipContext* ctx, const float* xyb, size_t n, int linear_output, float* rgb);
 
+/* ---- Output colour encodings of XYB images other than (linear) sRGB (lib/jxl/dec_xyb.cc:127-250,
+ * render_pipeline/stage_tone_mapping.cc:30-120, stage_from_linear.cc:37-168). The host builds the description
+ * (jxlamd_color_output in jxl_amd.h); the primaries and white point live in `matrix`, which replaces the frame's
+ * opsin_inv. A target whose transfer function is sRGB or linear and that needs no tone mapping is the matrix alone
+ * (tf = JXLHIP_TF_NONE: the frame keeps the filter kernels' own colour stage); any other makes the filter leave the
+ * filtered XYB planes and the generic writer (k_color_out, k_upsample_color, k_modular_output) compute, per pixel:
+ * matrix -> tone mapping -> transfer function. */
+#define JXLHIP_TF_NONE 0   /* the frame's linear_output decides (sRGB curve or none) */
+#define JXLHIP_TF_LINEAR 1
+#define JXLHIP_TF_SRGB 2
+#define JXLHIP_TF_PQ 3     /* SMPTE ST 2084, 1.0 = pq_display_scale * 10000 cd/m2 */
+#define JXLHIP_TF_HLG 4    /* BT.2100 HLG, after the scene-light OOTF of hlg_exponent */
+#define JXLHIP_TF_709 5
+#define JXLHIP_TF_GAMMA 6  /* x^inv_gamma, values <= 1e-5 to 0 (DCI: inv_gamma = 1 / 2.6) */
+#define JXLHIP_TONE_NONE 0
+#define JXLHIP_TONE_REC2408 1  /* Rec2408ToneMapper, then GamutMap (cms/tone_mapping.h:23-113, tone_mapping-inl.h) */
+#define JXLHIP_TONE_HLG_OOTF 2 /* HlgOOTF from the image's intensity target to the desired one; GamutMap when gamut_map */
+struct JxlHipColorTarget {
+  float matrix[9];         /* the inverse opsin matrix towards the target primaries, scaled by 255 / intensity target */
+  uint32_t tf, tone, gamut_map;
+  float luminances[3];     /* Y row of the target primaries' RGB -> XYZ matrix (dec_xyb.cc:212) */
+  float pre_scale, post_scale; /* around the tone mapping: 10000 / orig and desired / 10000 for a PQ target, else 1 */
+  float pq_display_scale;  /* TF_PQ(orig_intensity_target): display intensity / 10000 */
+  float inv_gamma;         /* JXLHIP_TF_GAMMA */
+  float hlg_exponent;      /* JXLHIP_TF_HLG: HlgOOTF::ToSceneLight(desired) exponent; 0 = no OOTF */
+  float tone_exponent;     /* JXLHIP_TONE_HLG_OOTF exponent (gamma - 1) */
+  /* JXLHIP_TONE_REC2408: Rec2408ToneMapperBase's constants (cms/tone_mapping.h:87-111) */
+  float tm_source_peak, tm_target_peak, tm_pq_min, tm_pq_range, tm_inv_pq_range, tm_min_lum, tm_max_lum, tm_ks,
+      tm_inv_one_minus_ks, tm_normalizer, tm_inv_target_peak;
+};
+/* Test entry: the generic writer's colour stage alone on n XYB triples (planar [3][n]) with `target` (its matrix; the
+ * opsin biases of the frame the context last uploaded); interleaved f32 RGB out. */
+int jxlhip_debug_color_target(JxlHipContext* ctx, const float* xyb, size_t n, const JxlHipColorTarget* target, float* rgb);
+
 /* Debug aid: with JXLHIP_GUARD=1 in the environment every device buffer of a context is allocated with a 4 KiB guard
  * band either side, filled with a pattern. Waits for the device, then *touched = 0 when every band is intact, else
  * (1-based buffer index << 2) | (1 = band before, 2 = band after) of the first buffer a kernel wrote next to. */
@@ -440,6 +478,7 @@ typedef struct JxlHipModFrameDesc {
   float opsin_inv[9];
   float opsin_bias[3];
   int32_t linear_output;
+  const struct JxlHipColorTarget* color_target; /* as JxlHipFrameDesc::color_target (XYB frames only) */
 } JxlHipModFrameDesc;
 /* Copies a Modular frame's tables and sections to the device (the arrays may be released afterwards). */
 int jxlhip_modular_upload(JxlHipContext* ctx, const JxlHipModFrameDesc* desc);

@@ -521,6 +521,21 @@ def set_color_encoding(white_point=None, primaries=1, transfer_function=13, gamm
                                 intent, arr)
 
 
+def set_xyb_color_encoding(white_point=None, primaries=1, transfer_function=13, gamma=None, intent=1, xy=None, intensity_target=255.0):
+    """Test aid: the next VarDCT (XYB) streams declare this enum colour encoding (values as set_color_encoding) and, when it
+    is not 255, this intensity target (ToneMapping). The coded samples do not change: the tag only changes how a decoder
+    renders the same XYB body. white_point=None: untagged again (the streams are then byte-identical to before)."""
+    E = _enc_lib()
+    E.jxlenc_set_xyb_color_encoding.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 6 + [ctypes.POINTER(ctypes.c_int32), ctypes.c_float]
+    E.jxlenc_set_xyb_color_encoding.restype = None
+    if white_point is None:
+        E.jxlenc_set_xyb_color_encoding(0, 1, 1, 0, 0, 13, 1, None, 255.0)
+        return
+    arr = (ctypes.c_int32 * 8)(*[int(round(v * 1e6)) for v in (xy or [0] * 8)])
+    E.jxlenc_set_xyb_color_encoding(1, white_point, primaries, 1 if gamma is not None else 0, int(round((gamma or 0) * 1e7)),
+                                    transfer_function, intent, arr, float(intensity_target))
+
+
 def set_frame_name(name=""):
     """Test aid: the frames written from now on carry this name (empty: none again)."""
     E = _enc_lib()

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/jxl_amd.h"
+#include "../host/jxh_color.h"
 #include "../host/jxh_frame.h"
 #include "../host/jxh_modframe.h"
 
@@ -43,6 +44,7 @@ jxh::ParallelFor MakeParallelFor(JxlParallelRunner runner, void* opaque) {
 
 struct JxlAmdFrame {
   jxh::FramePlan plan;
+  jxh::ColorOutput color;  // the output encoding the decoder asks of an XYB frame (PrepareColorOutput)
   const uint8_t* data = nullptr;
   size_t size = 0;
   uint32_t coef_bits = 16;
@@ -410,9 +412,12 @@ int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t 
   d.epf_pass0_sigma_scale = lf.epf_pass0_sigma_scale;
   d.epf_pass2_sigma_scale = lf.epf_pass2_sigma_scale;
   d.epf_border_sad_mul = lf.epf_border_sad_mul;
-  for (int i = 0; i < 9; i++) d.opsin_inv[i] = P.ih.inv_opsin[i] * (255.0f / P.ih.intensity_target);
+  const jxh::ColorOutput& co = f->color;
+  for (int i = 0; i < 9; i++) d.opsin_inv[i] = co.active ? co.matrix[i] : P.ih.inv_opsin[i] * (255.0f / P.ih.intensity_target);
   // (frames of images that are not xyb_encoded: their own colour transform, frame_header.h:176-184, and no transfer function)
-  d.linear_output = P.ih.xyb_encoded ? (P.ih.linear_tf ? 1 : 0) : (P.fh.ycbcr ? 2 : 3);
+  const bool linear = co.active ? co.linear : P.ih.linear_tf;
+  d.linear_output = P.ih.xyb_encoded ? (linear ? 1 : 0) : (P.fh.ycbcr ? 2 : 3);
+  d.color_target = P.ih.xyb_encoded && co.active && co.target.tf ? &co.target : nullptr;
   d.band_group_row_begin = group_row_begin;
   d.band_group_row_end = group_row_end;
   d.has_noise = P.has_noise ? 1 : 0;
@@ -474,6 +479,7 @@ int jxlamd_icc_decode(const uint8_t* coded, size_t size, uint8_t* out, size_t ou
 }  // extern "C"
 struct JxlAmdModFrame {
   jxh::ModFramePlan plan;
+  jxh::ColorOutput color;  // as JxlAmdFrame::color
   const uint8_t* data = nullptr;
 };
 extern "C" {
@@ -717,8 +723,10 @@ int jxlamd_modframe_upload(const JxlAmdModFrame* f, JxlHipContext* ctx) {
     d.xyb_factor[c] = P.dc_quant[c];
     d.opsin_bias[c] = P.ih.opsin_bias[c];
   }
-  for (int i = 0; i < 9; i++) d.opsin_inv[i] = P.ih.inv_opsin[i] * (255.0f / P.ih.intensity_target);
-  d.linear_output = P.ih.linear_tf ? 1 : 0;
+  const jxh::ColorOutput& co = f->color;
+  for (int i = 0; i < 9; i++) d.opsin_inv[i] = co.active ? co.matrix[i] : P.ih.inv_opsin[i] * (255.0f / P.ih.intensity_target);
+  d.linear_output = (co.active ? co.linear : P.ih.linear_tf) ? 1 : 0;
+  d.color_target = P.xyb && co.active && co.target.tf ? &co.target : nullptr;
   const int r = jxlhip_modular_upload(ctx, &d);
   if (r) g_last_error = "jxlhip_modular_upload failed (" + std::to_string(r) + ")";
   return r;
@@ -854,6 +862,8 @@ struct JxlDecoderStruct {
   size_t downsampling_target = 8;  // decode.cc:788
   bool coalescing = true;  // JxlDecoderSetCoalescing: false = every regular frame is delivered by itself, unblended
   int want_linear = -1;  // JxlDecoderSetOutputColorProfile: -1 = as coded
+  int want_orig = 0;     // ... of an XYB image (want_linear -1): 1 = its original encoding, 2 = that with a linear transfer function
+  float desired_intensity = 0.0f;  // JxlDecoderSetDesiredIntensityTarget: > 0 replaces the image's intensity target
   JxlCmsInterface cms{};
   bool have_cms = false;
   JxlBitDepth bit_depth{JXL_BIT_DEPTH_FROM_PIXEL_FORMAT, 0, 0};
@@ -943,6 +953,8 @@ void ResetState(JxlDecoder* d) {
   d->mt_run = nullptr;
   d->extra_out.clear();
   d->want_linear = -1;
+  d->want_orig = 0;
+  d->desired_intensity = 0.0f;
   d->coalescing = true;  // decode.cc:834
   d->bit_depth = JxlBitDepth{JXL_BIT_DEPTH_FROM_PIXEL_FORMAT, 0, 0};
 }
@@ -1237,7 +1249,63 @@ bool WantsUnpremultiply(const JxlDecoder* d, const OutFormat& of) {
   return false;
 }
 
+// An XYB image in an enum colour encoding: its colour stage renders to RenderedEncoding (jxh_color.h, dec_xyb.cc:127-250).
+// (ICC-tagged XYB images render to (linear) sRGB; grey XYB images are refused with the headers.)
+static bool XybEnumImage(const JxlDecoder* d) { return d->ih.xyb_encoded && !d->ih.want_icc && !d->ih.gray; }
+// What the pixels of such an image are in: the original encoding (decode.cc / dec_xyb.cc:160-165: every enum transfer
+// function is one the stage can output), sRGB or linear sRGB (want_linear), or the original with a linear transfer function.
+static void RenderedEncoding(const JxlDecoder* d, JxlColorEncoding* ce) {
+  jxh::EncodingFromHeader(d->ih, ce);
+  if (d->want_linear >= 0) {
+    ce->white_point = JXL_WHITE_POINT_D65;
+    ce->white_point_xy[0] = 0.3127;
+    ce->white_point_xy[1] = 0.3290;
+    ce->primaries = JXL_PRIMARIES_SRGB;
+    ce->primaries_red_xy[0] = jxh::kSrgbPrimariesXy[0]; ce->primaries_red_xy[1] = jxh::kSrgbPrimariesXy[1];
+    ce->primaries_green_xy[0] = jxh::kSrgbPrimariesXy[2]; ce->primaries_green_xy[1] = jxh::kSrgbPrimariesXy[3];
+    ce->primaries_blue_xy[0] = jxh::kSrgbPrimariesXy[4]; ce->primaries_blue_xy[1] = jxh::kSrgbPrimariesXy[5];
+    ce->transfer_function = d->want_linear ? JXL_TRANSFER_FUNCTION_LINEAR : JXL_TRANSFER_FUNCTION_SRGB;
+    ce->gamma = 0;
+  } else if (d->want_orig == 2) {
+    ce->transfer_function = JXL_TRANSFER_FUNCTION_LINEAR;
+    ce->gamma = 0;
+  }
+}
+// dec_cache.cc:263-300: with coalescing, a regular frame that is blended (NeedsBlending: not a whole-canvas kReplace of
+// every channel) or kept for reference after the colour transform gets its transfer function BEFORE that, and the tone
+// mapping stage behind it; every other frame is tone-mapped in linear light, as the colour stage here does.
+static bool ToneMappedAfterBlending(const JxlDecoder* d, const jxh::FrameHeader& fh) {
+  if (!d->coalescing || (fh.frame_type != 0 && fh.frame_type != 3)) return false;
+  bool replace_all = fh.blend.mode == 0;
+  for (const jxh::BlendInfo& b : fh.ec_blend) replace_all = replace_all && b.mode == 0;
+  const bool can_ref = !fh.is_last && (fh.duration == 0 || fh.save_as_reference != 0);  // frame_header.h:373-379
+  return fh.custom_size || !replace_all || (can_ref && !fh.save_before_color_transform);
+}
+// The colour stage of a frame of the image (header `ih`, frame header `fh`): the matrix towards the rendered primaries,
+// and (transfer functions other than sRGB / linear, tone mapping) the generic writer's colour target.
+static JxlDecoderStatus PrepareColorOutput(JxlDecoder* d, const jxh::ImageHeader& ih, const jxh::FrameHeader& fh,
+                                           jxh::ColorOutput* out) {
+  *out = jxh::ColorOutput();
+  if (!XybEnumImage(d)) return JXL_DEC_SUCCESS;
+  JxlColorEncoding src, dst;
+  jxh::EncodingFromHeader(ih, &src);
+  RenderedEncoding(d, &dst);
+  JxlHipColorTarget t;
+  std::string err;
+  if (!jxh::MakeColorOutput(src, ih.intensity_target, dst, d->desired_intensity, ih.inv_opsin, &t, &err)) return Fail(d, err);
+  const bool generic = jxh::NeedsGenericWriter(t);
+  // (blending happens in the output encoding; the reference then tone-maps the blended, already encoded samples: not done here)
+  if (t.tone && ToneMappedAfterBlending(d, fh))
+    return Fail(d, "unsupported: tone mapping of a frame that is blended or kept for reference");
+  out->active = true;
+  out->linear = generic || t.tf == JXLHIP_TF_LINEAR;
+  memcpy(out->matrix, t.matrix, sizeof(out->matrix));
+  if (generic) out->target = t;
+  return JXL_DEC_SUCCESS;
+}
+
 JxlDecoderStatus DecodeModularPixels(JxlDecoder* d, bool to_canvas) {
+  if (PrepareColorOutput(d, d->mframe->plan.ih, d->mframe->plan.fh, &d->mframe->color) != JXL_DEC_SUCCESS) return JXL_DEC_ERROR;
   const OutFormat of = to_canvas ? kCanvasFormat : MapFormat(d, d->fmt);
   int r = jxlhip_set_output_format(d->ctx, of.type, of.nc, of.bits, of.big_endian);
   if (!r) r = jxlhip_set_output_orientation(d->ctx, to_canvas ? 1 : UndoOrientation(d));
@@ -1300,6 +1368,7 @@ JxlDecoderStatus DecodePixels(JxlDecoder* d, bool to_canvas) {
   jxlamd_frame_set_linear_output(d->frame, d->want_linear >= 0 ? d->want_linear : (P.ih.linear_tf ? 1 : 0));
   const uint32_t orientation = to_canvas ? 1 : UndoOrientation(d);
   if (to_canvas && d->want_linear >= 0 && d->want_linear != (P.ih.linear_tf ? 1 : 0)) return Fail(d, "unsupported: blending with a changed transfer function");
+  if (PrepareColorOutput(d, d->frame->plan.ih, d->frame->plan.fh, &d->frame->color) != JXL_DEC_SUCCESS) return JXL_DEC_ERROR;
   int r = jxlhip_set_output_format(d->ctx, of.type, of.nc, of.bits, of.big_endian);
   if (!r) r = jxlhip_set_output_orientation(d->ctx, orientation);
   if (!r) r = jxlhip_set_output_unpremultiply(d->ctx, !to_canvas && WantsUnpremultiply(d, of) ? 1 : 0);
@@ -1906,7 +1975,7 @@ JxlDecoderStatus JxlDecoderGetBasicInfo(const JxlDecoder* d, JxlBasicInfo* info)
     info->ysize = uint32_t(OrientedYsize(d));
     info->bits_per_sample = d->ih.bits;
     info->exponent_bits_per_sample = d->ih.exp_bits;
-    info->intensity_target = d->ih.intensity_target;
+    info->intensity_target = d->desired_intensity > 0 ? d->desired_intensity : d->ih.intensity_target;  // decode.cc:2243-2245
     info->uses_original_profile = !d->ih.xyb_encoded;
     info->orientation = d->keep_orientation ? JxlOrientation(d->ih.orientation) : JXL_ORIENT_IDENTITY;
     info->num_color_channels = d->ih.gray ? 1 : 3;
@@ -1978,36 +2047,16 @@ JxlDecoderStatus JxlDecoderGetColorAsEncodedProfile(const JxlDecoder* d, JxlColo
   if (EmbeddedIcc(d, target)) return JXL_DEC_ERROR;  // (decode.h:728-730: only the ICC form exists then)
   if (ce) {
     memset(ce, 0, sizeof(*ce));
-    // the fields as coded (color_encoding_internal.cc:144-200; enum xy values: color_encoding_cms.h); an XYB image is
-    // always (linear) sRGB here, anything else was refused with the headers
-    const jxh::ImageHeader& ih = d->ih;
-    ce->color_space = ih.gray ? JXL_COLOR_SPACE_GRAY : JXL_COLOR_SPACE_RGB;
-    ce->white_point = JxlWhitePoint(ih.white_point);
-    switch (ih.white_point) {
-      case 2: ce->white_point_xy[0] = ih.white_xy[0] * 1e-6; ce->white_point_xy[1] = ih.white_xy[1] * 1e-6; break;
-      case 10: ce->white_point_xy[0] = ce->white_point_xy[1] = 1.0 / 3; break;
-      case 11: ce->white_point_xy[0] = 0.314; ce->white_point_xy[1] = 0.351; break;
-      default: ce->white_point_xy[0] = 0.3127; ce->white_point_xy[1] = 0.3290; break;
-    }
-    ce->primaries = JxlPrimaries(ih.primaries);
-    static const double kSrgb[6] = {0.639998686, 0.330010138, 0.300003784, 0.600003357, 0.150002046, 0.059997204};
-    static const double k2100[6] = {0.708, 0.292, 0.170, 0.797, 0.131, 0.046};
-    static const double kP3[6] = {0.680, 0.320, 0.265, 0.690, 0.150, 0.060};
-    double xy[6];
-    for (int i = 0; i < 6; i++) xy[i] = ih.primaries == 2 ? ih.primaries_xy[i] * 1e-6 : (ih.primaries == 9 ? k2100[i] : (ih.primaries == 11 ? kP3[i] : kSrgb[i]));
-    ce->primaries_red_xy[0] = xy[0]; ce->primaries_red_xy[1] = xy[1];
-    ce->primaries_green_xy[0] = xy[2]; ce->primaries_green_xy[1] = xy[3];
-    ce->primaries_blue_xy[0] = xy[4]; ce->primaries_blue_xy[1] = xy[5];
-    // the pixels (target DATA) follow JxlDecoderSetOutputColorProfile; the original profile is what the stream says
-    if (target == JXL_COLOR_PROFILE_TARGET_DATA && d->want_linear >= 0) {
+    // the fields as coded (color_encoding_internal.cc:144-200; enum xy values: color_encoding_cms.h); the pixels (target
+    // DATA) of an XYB image are in the encoding its colour stage renders (primaries and white point included), those of
+    // other images follow JxlDecoderSetOutputColorProfile's transfer function
+    jxh::EncodingFromHeader(d->ih, ce);
+    if (target == JXL_COLOR_PROFILE_TARGET_DATA && XybEnumImage(d)) {
+      RenderedEncoding(d, ce);
+    } else if (target == JXL_COLOR_PROFILE_TARGET_DATA && d->want_linear >= 0) {
       ce->transfer_function = d->want_linear ? JXL_TRANSFER_FUNCTION_LINEAR : JXL_TRANSFER_FUNCTION_SRGB;
-    } else if (ih.have_gamma) {
-      ce->transfer_function = JXL_TRANSFER_FUNCTION_GAMMA;
-      ce->gamma = ih.gamma * 1e-7;
-    } else {
-      ce->transfer_function = JxlTransferFunction(ih.transfer_function);
+      ce->gamma = 0;
     }
-    ce->rendering_intent = JxlRenderingIntent(ih.rendering_intent);
   }
   return JXL_DEC_SUCCESS;
 }
@@ -2028,24 +2077,61 @@ JxlDecoderStatus JxlDecoderGetColorAsICCProfile(const JxlDecoder* d, JxlColorPro
 JxlDecoderStatus JxlDecoderSetPreferredColorProfile(JxlDecoder* d, const JxlColorEncoding* ce) {
   return JxlDecoderSetOutputColorProfile(d, ce, nullptr, 0);
 }
-JxlDecoderStatus JxlDecoderSetDesiredIntensityTarget(JxlDecoder*, float) { return JXL_DEC_SUCCESS; }
+// decode.cc:2876-2883: negative values are refused; > 0 becomes the intensity target XYB images are rendered (tone mapped) for
+JxlDecoderStatus JxlDecoderSetDesiredIntensityTarget(JxlDecoder* d, float desired_intensity_target) {
+  if (!d || !(desired_intensity_target >= 0)) return JXL_DEC_ERROR;
+  d->desired_intensity = desired_intensity_target;
+  return JXL_DEC_SUCCESS;
+}
 JxlDecoderStatus JxlDecoderSetCms(JxlDecoder* d, JxlCmsInterface cms) {
   d->cms = cms;
   d->have_cms = true;
   return JXL_DEC_SUCCESS;
 }
 JxlDecoderStatus JxlDecoderSetOutputColorProfile(JxlDecoder* d, const JxlColorEncoding* ce, const uint8_t* icc, size_t icc_size) {
-  // decode.cc:2810: after the colour-encoding event, before the pixels. Only (linear or non-linear) sRGB output exists
-  // here; anything else is refused so that the caller notices.
+  // decode.cc:2810: after the colour-encoding event, before the pixels. Without a CMS the outputs are (linear) sRGB and,
+  // for an XYB image in an enum encoding, its original encoding or that with a linear transfer function (the rendering
+  // intent has no effect then); anything else is refused so that the caller notices (the reference would render any
+  // enum target of an XYB image: a documented deviation).
   if (!d->have_ih || d->stage > 4) return JXL_DEC_ERROR;
   if (!ce || icc || icc_size) return JXL_DEC_ERROR;
   if (ce->color_space != (d->ih.gray ? JXL_COLOR_SPACE_GRAY : JXL_COLOR_SPACE_RGB)) return JXL_DEC_ERROR;
-  if (ce->white_point != JXL_WHITE_POINT_D65) return JXL_DEC_ERROR;
-  if (ce->color_space == JXL_COLOR_SPACE_RGB && ce->primaries != JXL_PRIMARIES_SRGB) return JXL_DEC_ERROR;
-  if (ce->transfer_function == JXL_TRANSFER_FUNCTION_LINEAR) d->want_linear = 1;
-  else if (ce->transfer_function == JXL_TRANSFER_FUNCTION_SRGB) d->want_linear = 0;
-  else return JXL_DEC_ERROR;
-  return JXL_DEC_SUCCESS;
+  const bool srgb = ce->white_point == JXL_WHITE_POINT_D65 && (ce->color_space != JXL_COLOR_SPACE_RGB || ce->primaries == JXL_PRIMARIES_SRGB);
+  if (srgb && (ce->transfer_function == JXL_TRANSFER_FUNCTION_LINEAR || ce->transfer_function == JXL_TRANSFER_FUNCTION_SRGB)) {
+    d->want_linear = ce->transfer_function == JXL_TRANSFER_FUNCTION_LINEAR ? 1 : 0;
+    d->want_orig = 0;
+    return JXL_DEC_SUCCESS;
+  }
+  if (XybEnumImage(d)) {
+    JxlColorEncoding orig, want = *ce;
+    jxh::EncodingFromHeader(d->ih, &orig);
+    want.rendering_intent = orig.rendering_intent;
+    for (int linear = 0; linear < 2; linear++) {
+      if (linear) {
+        orig.transfer_function = JXL_TRANSFER_FUNCTION_LINEAR;
+        orig.gamma = 0;
+      }
+      if (jxh::SameEncoding(want, orig)) {
+        d->want_linear = -1;
+        d->want_orig = 1 + linear;
+        return JXL_DEC_SUCCESS;
+      }
+    }
+  }
+  return JXL_DEC_ERROR;
+}
+// Test entry (jxl_amd.h): the colour stage's output description.
+int jxlamd_color_output(const JxlColorEncoding* source, float source_intensity, const JxlColorEncoding* target, float desired_intensity,
+                        const float* inv_opsin, JxlHipColorTarget* out) {
+  g_last_error.clear();
+  if (!source || !target || !out) return 1;
+  static const jxh::ImageHeader kDefault;
+  std::string err;
+  if (!jxh::MakeColorOutput(*source, source_intensity, *target, desired_intensity, inv_opsin ? inv_opsin : kDefault.inv_opsin, out, &err)) {
+    g_last_error = err;
+    return 1;
+  }
+  return 0;
 }
 static const std::string& FrameName(const JxlDecoder* d) { return d->frame ? d->frame->plan.fh.name : d->mframe->plan.fh.name; }
 JxlDecoderStatus JxlDecoderGetFrameHeader(const JxlDecoder* d, JxlFrameHeader* h) {

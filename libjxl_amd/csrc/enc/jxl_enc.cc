@@ -927,6 +927,12 @@ struct ColorState {
   int32_t xy[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // white, red, green, blue
 };
 static ColorState g_color;
+// jxlenc_set_xyb_color_encoding: the enum ColorEncoding (and ToneMapping intensity target) the next VarDCT streams of an
+// XYB image declare. The samples stay as the encoder makes them (sRGB in, XYB out): the tag only changes how a decoder
+// renders the same body.
+static ColorState g_xyb_color;
+static float g_xyb_intensity = 255.0f;
+static bool g_tone_mapping_fields = false;  // while a VarDCT header with a coded intensity target is written
 static void WriteEnum(BitWriter& bw, uint32_t v) {  // U32(Val(0), Val(1), BitsOffset(4, 2), BitsOffset(6, 18))
   static const uint32_t b[4] = {0, 0, 4, 6}, o[4] = {0, 1, 2, 18};
   WriteU32Sel(bw, v, b, o);
@@ -935,8 +941,7 @@ static void WriteCustomXy(BitWriter& bw, const int32_t* xy) {
   static const uint32_t b[4] = {19, 19, 20, 21}, o[4] = {0, 524288, 1048576, 2097152};
   for (int i = 0; i < 2; i++) WriteU32Sel(bw, xy[i] >= 0 ? uint32_t(xy[i]) * 2 : uint32_t(-(xy[i] + 1)) * 2 + 1, b, o);
 }
-static void WriteColorEncodingFields(BitWriter& bw, bool gray) {
-  const ColorState& C = g_color;
+static void WriteColorEncodingFields(BitWriter& bw, bool gray, const ColorState& C = g_color) {
   bw.Write(1, 0);  // not all_default
   bw.Write(1, 0);  // no ICC
   WriteEnum(bw, gray ? 1 : 0);
@@ -1009,7 +1014,7 @@ static struct {
   bool enabled = false;
   uint32_t xs = 0, ys = 0;
 } g_preview;  // jxlenc_set_preview: the image header announces a preview frame of this size (headers.cc:155-183 PreviewHeader)
-static bool ExtraFields() { return g_orientation != 1 || (g_anim.enabled && g_anim.timed) || g_preview.enabled; }
+static bool ExtraFields() { return g_orientation != 1 || (g_anim.enabled && g_anim.timed) || g_preview.enabled || g_tone_mapping_fields; }
 // image_metadata.cc:283-300: extra_fields = orientation, no intrinsic size, no preview, animation (:235-250).
 static void WriteExtraFields(BitWriter& bw) {
   if (!ExtraFields()) {
@@ -1040,9 +1045,19 @@ static void WriteExtraFields(BitWriter& bw) {
     bw.Write(1, 0);  // no timecodes
   }
 }
-// image_metadata.cc:340-344: with extra_fields a ToneMapping bundle follows the colour encoding (all_default here).
+// image_metadata.cc:340-344: with extra_fields a ToneMapping bundle follows the colour encoding (all_default unless a VarDCT
+// header carries jxlenc_set_xyb_color_encoding's intensity target: image_metadata.cc ToneMapping::VisitFields).
 static void WriteToneMapping(BitWriter& bw) {
-  if (ExtraFields()) bw.Write(1, 1);
+  if (!ExtraFields()) return;
+  if (!g_tone_mapping_fields) {
+    bw.Write(1, 1);
+    return;
+  }
+  bw.Write(1, 0);
+  WriteF16(bw, g_xyb_intensity);  // intensity_target
+  WriteF16(bw, 0.0f);             // min_nits
+  bw.Write(1, 0);                 // relative_to_max_display
+  WriteF16(bw, 0.0f);             // linear_below
 }
 // frame_header.cc:130-150, 372-399: the animation fields of a frame header, is_last, and (not last) save_as_reference 0.
 // A frame with a duration and no reference slot cannot be referenced: no save_before_color_transform bit follows.
@@ -1663,7 +1678,9 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
   bw.Write(3, 0);  // no aspect-ratio shortcut
   WriteSizeDim(bw, g_image_w ? g_image_w : uint32_t(ups == 1 ? f.xs : f.img_xs));
   const bool with_icc = !g_embedded_icc.empty();
-  if (!have_alpha && !with_icc && !ExtraFields() && !p.color_transform) {
+  const bool xyb_tag = g_xyb_color.enabled && !with_icc && !p.color_transform;
+  g_tone_mapping_fields = xyb_tag && g_xyb_intensity != 255.0f;
+  if (!have_alpha && !with_icc && !xyb_tag && !ExtraFields() && !p.color_transform) {
     bw.Write(1, 1);  // ImageMetadata all_default (8-bit sRGB, XYB encoded)
   } else {           // image_metadata.cc:283-356
     bw.Write(1, 0);  // not all_default
@@ -1674,7 +1691,9 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
     bw.Write(2, have_alpha ? 1 : 0);  // extra channels
     if (have_alpha) WriteAlphaChannelInfo(bw);
     bw.Write(1, p.color_transform ? 0 : 1);  // xyb_encoded
-    if (!with_icc) {
+    if (xyb_tag) {
+      WriteColorEncodingFields(bw, false, g_xyb_color);
+    } else if (!with_icc) {
       bw.Write(1, 1);  // ColorEncoding all_default (sRGB)
     } else {
       bw.Write(1, 0);  // ColorEncoding not all_default (color_encoding_internal.cc:144-158)
@@ -1684,6 +1703,7 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
     WriteToneMapping(bw);
     bw.Write(2, 0);  // no extensions
   }
+  g_tone_mapping_fields = false;
   if (!g_custom_ups_mask) {
     bw.Write(1, 1);  // CustomTransformData all_default
   } else {
@@ -2966,6 +2986,19 @@ void jxlenc_set_color_encoding(int enabled, uint32_t white_point, uint32_t prima
   jxe::g_color.transfer_function = transfer_function;
   jxe::g_color.intent = intent;
   for (int i = 0; i < 8; i++) jxe::g_color.xy[i] = xy8 ? xy8[i] : 0;
+}
+void jxlenc_set_xyb_color_encoding(int enabled, uint32_t white_point, uint32_t primaries, uint32_t have_gamma, uint32_t gamma,
+                                   uint32_t transfer_function, uint32_t intent, const int32_t* xy8, float intensity_target) {
+  jxe::ColorState& C = jxe::g_xyb_color;
+  C.enabled = enabled != 0;
+  C.white_point = white_point;
+  C.primaries = primaries;
+  C.have_gamma = have_gamma;
+  C.gamma = gamma;
+  C.transfer_function = transfer_function;
+  C.intent = intent;
+  for (int i = 0; i < 8; i++) C.xy[i] = xy8 ? xy8[i] : 0;
+  jxe::g_xyb_intensity = enabled && intensity_target > 0 ? intensity_target : 255.0f;
 }
 void jxlenc_set_reference_frame(int slot) { jxe::g_reference_slot = slot; }
 // The next frame is a kDCFrame of `level` (1..4; 0 = a regular frame again) / the next VarDCT frame takes its DC image from

@@ -202,6 +202,7 @@ struct JxlHipContext {
     bool xyb = false;  // XYB Modular frame: integer Y, X, B - Y channels, the colour stage's parameters in `xyb_color`
     float xyb_factor[3] = {0, 0, 0};
     jxlhip::FilterParams xyb_color;
+    JxlHipColorTarget xyb_target;
     std::vector<const JxlHipContext*> batch_ctxs;
     std::vector<uint64_t> batch_gens;
     uint32_t batch_n = 0, batch_tree_cap = 0, batch_table_cap = 0;
@@ -279,6 +280,7 @@ struct JxlHipContext {
   Buf alpha;                // f32 plane of the image size (jxlhip_set_alpha), used by 2- and 4-channel output
   bool have_alpha = false;
   bool color_out = false;   // the pixels come from k_color_out / k_upsample_color's generic writer (set at upload)
+  JxlHipColorTarget ct{};   // JxlHipFrameDesc::color_target of the frame: its output encoding (tf != 0: the generic writer)
   Buf kend, block_recs, dequant_scan;
   Buf trecs;     // the transform work lists as 16-byte varblock records (TransformParams::trecs)
   Buf ec_stage;  // jxlhip_upsample_plane: a coded extra channel, its kernels and (unless it becomes the alpha plane) the result
@@ -1135,6 +1137,13 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   // XybToRgb's other branches, which only the generic writers take
   if (d->linear_output < 0 || d->linear_output > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (d->linear_output >= 2) c->color_out = true;
+  // an output encoding other than (linear) sRGB (jxl_hip_color.h): the frame's matrix gives linear RGB, the generic writer the rest
+  c->ct = d->color_target ? *d->color_target : JxlHipColorTarget{};
+  if (c->ct.tf > JXLHIP_TF_GAMMA || c->ct.tone > JXLHIP_TONE_HLG_OOTF) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->ct.tf) {
+    if (d->linear_output != 1) return JXLHIP_ERR_INVALID_ARGUMENT;
+    c->color_out = true;
+  }
   // noise is added to the filtered planes between the filter launch and the colour conversion
   c->has_noise = d->has_noise != 0;
   if (c->has_noise) {
@@ -2684,6 +2693,9 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
     memcpy(M.xyb_color.opsin_inv, d->opsin_inv, sizeof(M.xyb_color.opsin_inv));
     M.xyb_color.linear_output = d->linear_output;
   }
+  M.xyb_target = d->color_target ? *d->color_target : JxlHipColorTarget{};
+  if (M.xyb_target.tf > JXLHIP_TF_GAMMA || M.xyb_target.tone > JXLHIP_TONE_HLG_OOTF) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (M.xyb_target.tf && (!M.xyb || d->linear_output != 1)) return JXLHIP_ERR_INVALID_ARGUMENT;
   if ((r = UploadSplines(c, d->splines, d->ysize))) return r;
   if (d->patches.num_positions && d->patches.uses_alpha) return JXLHIP_ERR_UNSUPPORTED;  // (the frame's alpha is an integer channel here)
   if ((r = UploadPatches(c, d->patches, d->ysize, d->xsize, d->ysize))) return r;
@@ -2860,6 +2872,7 @@ static void ModularBuildOps(JxlHipContext* const* ctxs, size_t n, std::vector<ui
     o.xyb = M.xyb ? 1 : 0;
     memcpy(o.xyb_factor, M.xyb_factor, sizeof(o.xyb_factor));
     o.color = M.xyb_color;
+    o.target = M.xyb_target;
     for (uint32_t j = 0; j < M.num_color + (M.has_alpha ? 1 : 0); j++) {
       o.ch[j] = pool + M.buf_off[M.out_buffer[j]];
       o.stride[j] = M.xs;
@@ -3172,6 +3185,7 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
       cp.f = c->fp;
       cp.f.in = c->plane[1].as<float>();
       cp.po = po;
+      cp.t = c->ct;
       hipLaunchKernelGGL(jxlhip::k_color_out, dim3((c->xs + 63) / 64, (c->band_y1 - c->band_y0 + 3) / 4), dim3(256), 0, ls, cp);
       HIP_TRY(hipGetLastError());
       continue;
@@ -3187,6 +3201,7 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
     up.po = po;
     up.xyb_out = nullptr;
     up.oxp = 0;
+    up.t = c->ct;
     if (c->has_noise) {  // upsample to planes, add the noise at the image's resolution, then the colour stage
       up.xyb_out = c->ups_planes.as<float>();
       up.oxp = (c->oxs + 7) & ~7u;
@@ -3223,6 +3238,7 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
       cp.f.y_begin = 0;
       cp.f.y_end = c->oys;
       cp.po = po;
+      cp.t = c->ct;
       hipLaunchKernelGGL(jxlhip::k_color_out, dim3((c->oxs + 63) / 64, (c->oys + 3) / 4), dim3(256), 0, ls, cp);
       HIP_TRY(hipGetLastError());
     }
@@ -3513,11 +3529,12 @@ int jxlhip_run_all(JxlHipContext* c) {
   return r;
 }
 
-// Test entry: the colour stage alone (k_color_out: XYB -> linear RGB -> transfer function) on `n` caller-supplied XYB
-// triples, planar [3][n], with the opsin parameters of the frame the context last uploaded; f32 RGB out, interleaved.
-// For the closed-form colour tests of the reference (opsin_image_test.cc) against the kernel itself.
-int jxlhip_debug_color(JxlHipContext* c, const float* xyb, size_t n, int linear_output, float* rgb) {
+// The colour stage alone (k_color_out: XYB -> linear RGB -> transfer function) on `n` caller-supplied XYB triples, planar
+// [3][n], with the opsin biases of the frame the context last uploaded; f32 RGB out, interleaved. t == NULL: the frame's
+// own matrix and linear_output; else t's matrix and the generic writer's colour target.
+static int DebugColor(JxlHipContext* c, const float* xyb, size_t n, int linear_output, const JxlHipColorTarget* t, float* rgb) {
   if (!c || !xyb || !rgb || !n || n > (1u << 24)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (t && (t->tf > JXLHIP_TF_GAMMA || t->tone > JXLHIP_TONE_HLG_OOTF)) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   HIP_TRY(hipSetDevice(c->device));
   Buf in, out;
@@ -3537,7 +3554,11 @@ int jxlhip_debug_color(JxlHipContext* c, const float* xyb, size_t n, int linear_
     cp.f.ys = cp.f.yp = 1;
     cp.f.y_begin = 0;
     cp.f.y_end = 1;
-    cp.f.linear_output = linear_output;
+    cp.f.linear_output = t ? 1 : linear_output;
+    if (t) {
+      memcpy(cp.f.opsin_inv, t->matrix, sizeof(cp.f.opsin_inv));
+      cp.t = *t;
+    }
     cp.po.dst = out.p;
     cp.po.xsize = uint32_t(n);
     cp.po.ysize = 1;
@@ -3552,6 +3573,15 @@ int jxlhip_debug_color(JxlHipContext* c, const float* xyb, size_t n, int linear_
   in.Free();
   out.Free();
   return e == hipSuccess ? 0 : -int(e);
+}
+// Test entries: for the closed-form colour tests of the reference (opsin_image_test.cc) against the kernel itself, and for
+// the output encodings of tagged XYB images (jxl_hip_color.h) against a float64 reading.
+int jxlhip_debug_color(JxlHipContext* c, const float* xyb, size_t n, int linear_output, float* rgb) {
+  return DebugColor(c, xyb, n, linear_output, nullptr, rgb);
+}
+int jxlhip_debug_color_target(JxlHipContext* c, const float* xyb, size_t n, const JxlHipColorTarget* t, float* rgb) {
+  if (!t) return JXLHIP_ERR_INVALID_ARGUMENT;
+  return DebugColor(c, xyb, n, 1, t, rgb);
 }
 
 int jxlhip_check_guards(JxlHipContext* c, uint32_t* touched) {

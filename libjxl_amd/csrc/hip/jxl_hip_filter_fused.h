@@ -18,6 +18,7 @@
 
 #include <type_traits>
 
+#include "jxl_hip_color.h"
 #include "jxl_hip_kernels.h"
 
 namespace jxlhip {
@@ -193,6 +194,7 @@ struct UpsampleParams {
   PixelOut po;          // po.dst != NULL: the image in this format instead of RGB8 in f.rgb
   float* xyb_out;       // != NULL: the upsampled X, Y, B as planes [3][oys][oxp] instead of pixels (the frame's noise is added
   uint32_t oxp;         // to them at the image's resolution before the colour stage: dec_cache.cc:206-216)
+  JxlHipColorTarget t;  // t.tf != JXLHIP_TF_NONE: the output encoding after f's matrix (jxl_hip_color.h); f.linear_output is 1
 };
 
 // XYB -> linear RGB -> (sRGB) for one pixel (stage_xyb.cc:80-92 + dec_xyb-inl.h:38-86, stage_from_linear.cc:114-144).
@@ -227,6 +229,7 @@ __device__ __forceinline__ void XybToRgb(const FilterParams& f, float X, float Y
 struct ColorOutParams {
   FilterParams f;  // f.in = filtered XYB planes; y_begin / y_end = rows to produce
   PixelOut po;
+  JxlHipColorTarget t;  // as UpsampleParams::t
 };
 __global__ __launch_bounds__(256) void k_color_out(ColorOutParams P) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = int(P.f.y_begin) + blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -234,6 +237,7 @@ __global__ __launch_bounds__(256) void k_color_out(ColorOutParams P) {
   const size_t plane = size_t(P.f.xp) * P.f.yp, gi = size_t(y) * P.f.xp + x;
   float r, g, b;
   XybToRgb(P.f, P.f.in[gi], P.f.in[plane + gi], P.f.in[2 * plane + gi], &r, &g, &b);
+  if (P.t.tf) ApplyColorTarget(P.t, &r, &g, &b);
   StorePixel(P.po, x, y, r, g, b);
 }
 
@@ -291,6 +295,7 @@ __global__ __launch_bounds__(256) void k_upsample_color(UpsampleParams P) {
       }
       float r, g, b;
       XybToRgb(P.f, Xc, Yc, Bc, &r, &g, &b);
+      if (P.t.tf) ApplyColorTarget(P.t, &r, &g, &b);
       if (P.po.dst) {
         StorePixel(P.po, X, Y, r, g, b);
         continue;

@@ -23,6 +23,7 @@
 #ifndef JXL_HIP_MODULAR_H_
 #define JXL_HIP_MODULAR_H_
 
+#include "jxl_hip_color.h"
 #include "jxl_hip_kernels.h"
 
 namespace jxlhip {
@@ -797,6 +798,7 @@ struct ModOutput {
   uint32_t xyb;
   float xyb_factor[3];
   FilterParams color;
+  JxlHipColorTarget target;  // tf != JXLHIP_TF_NONE: the output encoding after color's matrix (jxl_hip_color.h)
 };
 // One decoded integer -> the float the render pipeline starts from. `depth`: low byte = bits per sample, bits 8..15 = exponent
 // bits of a floating-point sample type (0 = integer samples).
@@ -849,7 +851,10 @@ __global__ __launch_bounds__(256) void k_modular_output(const ModOutput* ops) {
   }
   if (P.fmode == 2)
     for (uint32_t c = 0; c < 3; c++) v[c] = P.fplanes[(size_t(c) * P.h + y) * P.w + x];
-  if (P.xyb) XybToRgb(P.color, v[0], v[1], v[2], &v[0], &v[1], &v[2]);  // (after the splines, like every XYB frame)
+  if (P.xyb) {
+    XybToRgb(P.color, v[0], v[1], v[2], &v[0], &v[1], &v[2]);  // (after the splines, like every XYB frame)
+    if (P.target.tf) ApplyColorTarget(P.target, &v[0], &v[1], &v[2]);
+  }
   const float a = P.has_alpha ? ModSampleToFloat(P.ch[P.num_color][size_t(y) * P.stride[P.num_color] + x], P.alpha_bits) : 1.0f;
   const uint32_t nc = P.po.nc, ncol = nc < 3 ? 1u : 3u;
   float s[4];

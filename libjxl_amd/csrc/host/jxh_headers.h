@@ -4,7 +4,7 @@
 // lib/jxl/color_encoding_internal.cc:94-215, lib/jxl/frame_header.cc:30-439, lib/jxl/frame_header.h:35-50,
 // lib/jxl/loop_filter.cc:20-100, lib/jxl/toc.cc:29-115, lib/jxl/toc.h:31-41,
 // lib/jxl/frame_dimensions.h:34-59.
-// Unsupported features (ICC, preview, animation timing beyond parsing, non-sRGB colour) raise jxh::Error.
+// Unsupported features (grey XYB images other than (linear) sRGB) raise jxh::Error.
 #ifndef JXH_HEADERS_H_
 #define JXH_HEADERS_H_
 
@@ -127,11 +127,12 @@ static inline void ReadColorEncoding(BitReader& br, ImageHeader* h) {
   h->rendering_intent = ReadEnum(br);
   JXH_CHECK(h->rendering_intent <= 3, "invalid rendering intent");
   h->linear_tf = !h->have_gamma && h->transfer_function == 8;
-  // an XYB image is rendered by the colour stage here, which knows sRGB primaries with the sRGB curve or none
-  // (dec_xyb.cc:181-250 does the other enum spaces; no CMS here): anything else is refused rather than mis-rendered
-  if (h->xyb_encoded)
-    JXH_CHECK(h->white_point == 1 && (cs == 1 || h->primaries == 1) && !h->have_gamma && (h->transfer_function == 13 || h->transfer_function == 8),
-            "unsupported: XYB image in a colour space other than (linear) sRGB");
+  // an XYB image in any valid enum encoding of an RGB space is rendered to it by the colour stage (jxh_color.h after
+  // dec_xyb.cc:127-250, no CMS). Grey XYB images are not rendered here: those in (linear) sRGB get their header events and
+  // are refused at the pixels (the output format check, jxh_modframe.h), any other one is refused here.
+  if (h->xyb_encoded && cs == 1)
+    JXH_CHECK(h->white_point == 1 && !h->have_gamma && (h->transfer_function == 13 || h->transfer_function == 8),
+              "unsupported: XYB image in a colour space other than (linear) sRGB");
 }
 
 static inline void ReadImageHeader(BitReader& br, ImageHeader* h) {
