@@ -285,6 +285,7 @@ void jxlamd_frame_out_size(const JxlAmdFrame* f, uint32_t* wh) {
 // The N*N 5x5 upsampling kernels from the upper triangle of the symmetric weight matrix (stage_upsampling.cc:59-84):
 // the weights the image header codes (image_metadata.cc:87-214, CustomTransformData) or the default ones (:98-214).
 #include "../host/upsampling_weights.inc"
+#include "../host/dither.inc"
 static void UpsamplingKernels(uint32_t N, const jxh::ImageHeader& ih, std::vector<float>* kernel) {
   const std::vector<float>& coded = N == 2 ? ih.ups_weights2 : (N == 4 ? ih.ups_weights4 : ih.ups_weights8);
   const float* weights = !coded.empty() ? coded.data() : (N == 2 ? kUpsamplingWeights2 : (N == 4 ? kUpsamplingWeights4 : kUpsamplingWeights8));
@@ -1150,7 +1151,10 @@ OutFormat MapFormat(const JxlDecoder* d, const JxlPixelFormat& f) {
 
 // Host-side conversion of one Modular-coded extra channel (integer samples) to the caller's sample type
 // (dec_frame.cc:511-542 hands these channels to the same stage_write.cc conversions; they never touch the GPU stages).
-void StoreExtraRow(const int32_t* src, size_t xs, uint32_t ch_bits, const JxlPixelFormat& f, uint32_t out_bits, uint8_t* dst) {
+// Rows arrive oriented; 8-bit samples take the dither cell of channel 0 at the position before the transpose
+// (stage_write.cc:265-286 MakeUnsigned, :662-699): (x, row), or (row, x) when `transposed`.
+void StoreExtraRow(const int32_t* src, size_t xs, uint32_t ch_bits, const JxlPixelFormat& f, uint32_t out_bits, uint8_t* dst,
+                   size_t row, bool transposed) {
   const float inv = 1.0f / float((uint64_t(1) << ch_bits) - 1);
   for (size_t x = 0; x < xs; x++) {
     const float v = float(src[x]) * inv;
@@ -1165,7 +1169,9 @@ void StoreExtraRow(const int32_t* src, size_t xs, uint32_t ch_bits, const JxlPix
       memcpy(dst + x * 2, &h, 2);
     } else {
       const float mul = float((1u << out_bits) - 1u);
-      const float t = std::min(std::max(v * mul, 0.0f), mul);
+      float t = v * mul;
+      if (f.data_type == JXL_TYPE_UINT8) t += transposed ? kDither32[x & 31][row & 31] : kDither32[row & 31][x & 31];
+      t = std::min(std::max(t, 0.0f), mul);
       const uint32_t u = uint32_t(std::nearbyint(t));
       if (f.data_type == JXL_TYPE_UINT8) dst[x] = uint8_t(u);
       else {
@@ -1342,7 +1348,8 @@ JxlDecoderStatus DecodeModularPixels(JxlDecoder* d, bool to_canvas) {
     if (d->bit_depth.type == JXL_BIT_DEPTH_FROM_CODESTREAM) bits = std::min(bits, d->ih.extra[eo.first].bits);
     else if (d->bit_depth.type == JXL_BIT_DEPTH_CUSTOM) bits = d->bit_depth.bits_per_sample;
     for (size_t y = 0; y < ys; y++)
-      StoreExtraRow(plane.data() + y * xs, xs, d->ih.extra[eo.first].bits, f, bits, static_cast<uint8_t*>(eo.second.buf) + y * stride);
+      StoreExtraRow(plane.data() + y * xs, xs, d->ih.extra[eo.first].bits, f, bits, static_cast<uint8_t*>(eo.second.buf) + y * stride,
+                    y, orientation > 4);
   }
   return DeliverPixels(d, of, xs, ys);
 }
@@ -1465,7 +1472,8 @@ JxlDecoderStatus DecodePixels(JxlDecoder* d, bool to_canvas) {
     if (d->bit_depth.type == JXL_BIT_DEPTH_FROM_CODESTREAM) bits = std::min(bits, d->ih.extra[eo.first].bits);
     else if (d->bit_depth.type == JXL_BIT_DEPTH_CUSTOM) bits = d->bit_depth.bits_per_sample;
     for (size_t y = 0; y < ys; y++)
-      StoreExtraRow(p + y * xs, xs, d->ih.extra[eo.first].bits, f, bits, static_cast<uint8_t*>(eo.second.buf) + y * stride);
+      StoreExtraRow(p + y * xs, xs, d->ih.extra[eo.first].bits, f, bits, static_cast<uint8_t*>(eo.second.buf) + y * stride, y,
+                    orientation > 4);
   }
   return DeliverPixels(d, of, xs, ys);
 }
@@ -1540,7 +1548,7 @@ JxlDecoderStatus DeliverCanvas(JxlDecoder* d) {
     if (d->bit_depth.type == JXL_BIT_DEPTH_FROM_CODESTREAM) bits = std::min(bits, ch_bits);
     else if (d->bit_depth.type == JXL_BIT_DEPTH_CUSTOM) bits = d->bit_depth.bits_per_sample;
     const size_t stride = RowStride(f, xs);
-    for (size_t y = 0; y < ys; y++) StoreExtraRow(plane.data() + y * xs, xs, ch_bits, f, bits, static_cast<uint8_t*>(eo.second.buf) + y * stride);
+    for (size_t y = 0; y < ys; y++) StoreExtraRow(plane.data() + y * xs, xs, ch_bits, f, bits, static_cast<uint8_t*>(eo.second.buf) + y * stride, y, orientation > 4);
   }
   if (d->out_buf) {
     if (jxlhip_canvas_download(d->canvas, of.type, of.nc, of.bits, of.big_endian, orientation, d->out_buf, RowStride(d->fmt, xs)))

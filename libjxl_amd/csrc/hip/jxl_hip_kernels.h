@@ -1898,6 +1898,7 @@ __device__ __forceinline__ void StorePixel(const PixelOut& o, int x, int y, floa
   for (uint32_t c = 0; c < nc; c++) {
     const float f = v[c];
     if (o.type == 2) {
+#pragma clang fp contract(off)  // Mul, then Add the dither, each rounded (stage_write.cc MakeUnsigned): no FMA
       const float mul = float((1u << o.bits) - 1u);
       const float t = __builtin_amdgcn_fmed3f(f * mul + c_dither[((dy + int(c) * 13) & 31) * 32 + ((dx + int(c) * 23) & 31)], 0.0f, mul);
       static_cast<uint8_t*>(o.dst)[base + c] = uint8_t(__float2int_rn(t));

@@ -871,6 +871,7 @@ __global__ __launch_bounds__(256) void k_modular_output(const ModOutput* ops) {
   for (uint32_t c = 0; c < nc; c++) {
     const float f = s[c];
     if (P.po.type == 2) {
+#pragma clang fp contract(off)  // Mul, then Add the dither, each rounded (stage_write.cc MakeUnsigned): no FMA
       const float m = float((1u << P.po.bits) - 1u);
       const float t = __builtin_amdgcn_fmed3f(f * m + c_dither[((uint32_t(dy) + c * 13) & 31) * 32 + ((uint32_t(dx) + c * 23) & 31)], 0.0f, m);
       static_cast<uint8_t*>(P.po.dst)[base + c] = uint8_t(__float2int_rn(t));

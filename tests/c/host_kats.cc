@@ -6,7 +6,7 @@
 //   lehmer   random permutations -> Lehmer code -> DecodeLehmer (lehmer_code_test.cc)
 //   fjxl F.jxl F.raw W H C   a Modular (lossless) file written by the reference's enc_fast_lossless.cc decodes, through
 //            this front-end's bit reader / headers / TOC / prefix + LZ77 entropy coder / MA-tree channel decode / inverse
-//            transforms, to exactly the raw interleaved 8-bit samples it was made from.
+//            transforms, to exactly the raw interleaved samples it was made from (8-bit, or 16-bit little-endian above 8 bits).
 //   icc ENC ICC   (product only) the reference's own ICC codec vector (icc_codec_test.cc:52-211): the coded stream ENC must
 //            decode to the profile ICC byte for byte, and damaged copies of it must be rejected, not crash.
 //   fastmath the error bars of the reference's own fast_math_test.cc:46-111 on this front-end's FastLog2f / FastPow2f /
@@ -210,7 +210,7 @@ static int TestFjxl(const char* jxl_path, const char* raw_path, size_t W, size_t
   };
   std::vector<uint8_t> data, raw;
   REQUIRE(slurp(jxl_path, &data) && slurp(raw_path, &raw), "cannot read the fixture");
-  REQUIRE(raw.size() == W * Hh * C, "raw size");
+  size_t bps = 0;  // bytes per raw sample: 1 up to 8 bits, 2 (little-endian) above, as the image header says
   try {
     REQUIRE(data.size() > 2 && data[0] == 0xFF && data[1] == 0x0A, "not a bare codestream");
     H::BitReader br(data.data(), data.size());
@@ -220,7 +220,10 @@ static int TestFjxl(const char* jxl_path, const char* raw_path, size_t W, size_t
     REQUIRE(ih.xsize == W && ih.ysize == Hh, "image size %ux%u", ih.xsize, ih.ysize);
     const size_t ncolor = ih.gray ? 1 : 3;
     REQUIRE(ncolor + ih.extra.size() == C, "channel count %zu + %zu", ncolor, ih.extra.size());
-    REQUIRE(!ih.xyb_encoded && ih.bits == 8, "fjxl writes non-XYB 8-bit images");
+    REQUIRE(!ih.xyb_encoded && ih.exp_bits == 0 && ih.bits >= 1 && ih.bits <= 16, "fjxl writes non-XYB 1..16-bit integer images");
+    for (const auto& e : ih.extra) REQUIRE(e.bits == ih.bits, "fjxl's alpha has the colour's depth");
+    bps = ih.bits > 8 ? 2 : 1;
+    REQUIRE(raw.size() == W * Hh * C * bps, "raw size");
     H::FrameHeader fh;
     H::ReadFrameHeader(br, ih, &fh);
     REQUIRE(fh.modular && fh.is_last && fh.num_passes == 1 && fh.upsampling == 1, "frame header");
@@ -232,7 +235,7 @@ static int TestFjxl(const char* jxl_path, const char* raw_path, size_t W, size_t
     REQUIRE(base + toc.total == data.size(), "TOC: sections end at %zu, file has %zu bytes", size_t(base + toc.total), data.size());
     H::MGlobal mg;
     H::MImage full;
-    full.bitdepth = 8;
+    full.bitdepth = int(ih.bits);
     for (size_t c = 0; c < C; c++) full.ch.emplace_back(d.xsize, d.ysize);
     auto dc_global = [&](H::BitReader& r) {
       REQUIRE(r.ReadBool(), "DC dequant must be default in a Modular frame written by fjxl");
@@ -246,7 +249,7 @@ static int TestFjxl(const char* jxl_path, const char* raw_path, size_t W, size_t
     };
     auto group = [&](H::BitReader& r, size_t x0, size_t y0, size_t xs, size_t ys, int min_shift, int max_shift, int stream) {
       H::MImage part;
-      part.bitdepth = 8;
+      part.bitdepth = int(ih.bits);
       std::vector<size_t> which, px, py;
       size_t c = full.nb_meta;
       while (c < full.ch.size() && full.ch[c].w <= d.group_dim && full.ch[c].h <= d.group_dim) c++;
@@ -301,7 +304,10 @@ static int TestFjxl(const char* jxl_path, const char* raw_path, size_t W, size_t
     size_t bad = 0;
     for (size_t y = 0; y < Hh; y++)
       for (size_t x = 0; x < W; x++)
-        for (size_t c = 0; c < C; c++) bad += full.ch[c].Row(y)[x] != int32_t(raw[(y * W + x) * C + c]);
+        for (size_t c = 0; c < C; c++) {
+          const uint8_t* p = &raw[((y * W + x) * C + c) * bps];
+          bad += full.ch[c].Row(y)[x] != int32_t(bps == 2 ? p[0] | (p[1] << 8) : p[0]);
+        }
     REQUIRE(bad == 0, "%zu of %zu samples differ from the encoder's input", bad, W * Hh * C);
   } catch (const std::exception& e) {
     fprintf(stderr, "FAIL: %s\n", e.what());

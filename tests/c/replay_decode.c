@@ -63,6 +63,8 @@ int main(int argc, char** argv) {
   uint8_t* preview_pixels = NULL;
   size_t preview_bytes = 0;
   int unpremul = 0, progression = 0, detail = -1;
+  JxlBitDepthType depth_type = JXL_BIT_DEPTH_FROM_PIXEL_FORMAT; /* depth=stream / depth=<n>: FROM_CODESTREAM / CUSTOM */
+  uint32_t depth_bits = 0;
   int nopreview = 0; /* nopreview: do not subscribe to JXL_DEC_PREVIEW_IMAGE (the preview frame is stepped over) */
   int flush = 0, in_frame = 0, flushes = 0; /* flush: JxlDecoderFlushImage whenever the decoder runs out of input inside a frame */
   size_t skip = 0;
@@ -88,6 +90,8 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "unpremul")) unpremul = 1; /* JxlDecoderSetUnpremultiplyAlpha(true) */
     if (!strcmp(argv[i], "progression")) progression = 1; /* subscribe to JXL_DEC_FRAME_PROGRESSION and flush when it comes */
     if (!strncmp(argv[i], "detail=", 7)) detail = atoi(argv[i] + 7); /* JxlDecoderSetProgressiveDetail */
+    if (!strcmp(argv[i], "depth=stream")) depth_type = JXL_BIT_DEPTH_FROM_CODESTREAM; /* JxlDecoderSetImageOutBitDepth */
+    else if (!strncmp(argv[i], "depth=", 6)) { depth_type = JXL_BIT_DEPTH_CUSTOM; depth_bits = (uint32_t)atoi(argv[i] + 6); }
   }
   if (JxlSignatureCheck(bytes, size) == JXL_SIG_INVALID) return 2;
   JxlMemoryManager mm = {NULL, CountingAlloc, CountingFree};
@@ -264,7 +268,7 @@ int main(int argc, char** argv) {
       } else if (JxlDecoderSetImageOutBuffer(dec, &format, g_pixels, buffer_size) != JXL_DEC_SUCCESS) {
         return 2;
       }
-      JxlBitDepth depth = {JXL_BIT_DEPTH_FROM_PIXEL_FORMAT, 0, 0};
+      JxlBitDepth depth = {depth_type, depth_bits, 0};
       if (JxlDecoderSetImageOutBitDepth(dec, &depth) != JXL_DEC_SUCCESS) return 2; /* jxl.cc:567 */
       for (uint32_t i = 0; i < info.num_extra_channels; i++) {
         size_t ec_size = 0;

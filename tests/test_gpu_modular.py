@@ -22,9 +22,25 @@ def test_fjxl_fixture_bit_exact_on_gpu(built, name):
     J = built
     img = G.golden_image(name)
     data = open(os.path.join(ROOT, "tests", "golden", name + ".jxl"), "rb").read()
-    out = J.decode_lossless(data, num_channels=img.shape[2])
-    assert out.shape == img.shape
-    assert np.array_equal(out, img), "%d samples differ" % int((out != img).sum())
+    bits = MANIFEST[name]["bits"]
+    if bits == 8:
+        out = J.decode_lossless(data, num_channels=img.shape[2])
+        assert out.shape == img.shape
+        assert np.array_equal(out, img), "%d samples differ" % int((out != img).sum())
+    _exact_at_depth(J, data, img, bits)
+
+
+def _exact_at_depth(J, data, img, bits):
+    """f32 output bit-equal to the reference's int -> float of the encoder's input (np_sample_to_float, alpha included:
+    fjxl's alpha has the colour's depth), and back to the integers by round(f * (2^b - 1)); 16 bits also as u16."""
+    got = J.decode_lossless(data, num_channels=img.shape[2], data_type=0)
+    assert got.shape == img.shape and got.dtype == np.float32
+    want = np_sample_to_float(img, bits, 0)
+    bad = got.view(np.uint32) != want.view(np.uint32)
+    assert not bad.any(), "%d samples differ, first at %s" % (int(bad.sum()), np.argwhere(bad)[0].tolist())
+    assert np.array_equal(np.round(got.astype(np.float64) * ((1 << bits) - 1)).astype(np.int64), img.astype(np.int64))
+    if bits == 16:
+        assert np.array_equal(J.decode_lossless(data, num_channels=img.shape[2], data_type=3), img)
 
 
 def test_lossless_formats_and_channel_subsets(built):
@@ -63,6 +79,27 @@ def test_live_reference_encoder_output_on_gpu(built, tmp_path, size, channels, e
     subprocess.run([FJXL, raw, str(w), str(h), str(channels), "8", str(effort), out], check=True)
     got = J.decode_lossless(open(out, "rb").read(), channels)
     assert np.array_equal(got, img), "%d samples differ" % int((got != img).sum())
+
+
+_DEEP_LIVE = [(b, s, 1 + i % 4, i % 3) for i, (b, s) in enumerate((b, s) for b in (10, 12, 16) for s in ((257, 255), (1, 300), (2100, 40)))]
+
+
+@pytest.mark.skipif(not os.path.exists(FJXL), reason="the reference encoder binary (oracle/_ref/fjxl_enc) is not built here")
+@pytest.mark.parametrize("bits,size,channels,effort", _DEEP_LIVE + [(16, (3840, 2160), 4, 2), (12, (257, 255), 3, 1), (10, (2100, 40), 4, 0)])
+def test_live_reference_encoder_deep_noise_on_gpu(built, tmp_path, bits, size, channels, effort):
+    """Fresh deep output of the reference's encoder on full-range noise (16-bit residuals, wide hybrid-uint tokens, YCoCg
+    chroma one bit wider; 2100 wide: more than one DC group; 3840x2160 16-bit RGBA: configs[3] at depth): exact.
+    Not the full cross product: every depth meets every size once (_DEEP_LIVE), channels and effort cycling with it, so
+    each depth, size, channel count and effort occurs, but not each combination (16-bit x 2 channels, for one, is not
+    run); three extra cases add the 4K one."""
+    J = built
+    w, h = size
+    img = np.random.default_rng(bits * 7 + channels * 3 + effort + w).integers(0, 1 << bits, (h, w, channels)).astype(np.uint16)
+    raw = os.path.join(str(tmp_path), "in.raw")
+    out = os.path.join(str(tmp_path), "out.jxl")
+    img.astype("<u2").tofile(raw)
+    subprocess.run([FJXL, raw, str(w), str(h), str(channels), str(bits), str(effort), out], check=True)
+    _exact_at_depth(J, open(out, "rb").read(), img, bits)
 
 
 def test_lossless_through_the_decoder_api(built, tmp_path):
@@ -207,10 +244,13 @@ def test_reference_jni_wrapper_streams_on_gpu(built, tmp_path):
     Integer work: the samples equal the independent decoder's."""
     import jxlo
     import replay_util as R
+    import writer_np as W
     for name, dim in (("ref_jni_simple_1024.jxl", 1024), ("ref_jni_pixel_alpha_1x1.jxl", 1)):
         data = open(os.path.join(ROOT, "tests", "golden", name), "rb").read()
-        o = jxlo.Decoded(data, dumps=False)
+        o = jxlo.Decoded(data, dumps=True)
         want = o.rgb8.copy()
+        bits, ncol = o.info["bits"], 3  # (both are colour images; the 1x1 one's alpha has 8 bits like its colour)
+        ints = o.buffer("modular").reshape(-1, dim, dim).copy()
         o.close()
         for fmt, nc, bytes_per in (("u8", 4, 4), ("u8", 3, 3), ("f16", 4, 8), ("f16", 3, 6)):
             rc, events, out, px = R.run(data, tmp_path, fmt, nc)
@@ -218,7 +258,13 @@ def test_reference_jni_wrapper_streams_on_gpu(built, tmp_path):
             assert len(px) == dim * dim * bytes_per
             if fmt == "u8":
                 got = np.frombuffer(px, np.uint8).reshape(dim, dim, nc)
-                assert np.abs(got[..., :3].astype(int) - want[..., :3].astype(int)).max() <= 1  # (10-bit samples scaled to 8 bits in float)
+                # exact: the reference's writer (writer_np) applied to the oracle's integers at the stream's depth
+                planes = np.moveaxis(ints, 0, -1)
+                f = np_sample_to_float(planes[..., :ncol], bits, 0)
+                if nc == 4:
+                    a = np_sample_to_float(planes[..., ncol:], bits, 0) if planes.shape[2] > ncol else np.ones((dim, dim, 1), np.float32)
+                    f = np.dstack([f, a])
+                assert np.array_equal(got, W.write(f, "u8", 8)), name
                 if nc == 4:
                     assert np.array_equal(got[..., 3], want[..., 3] if want.shape[2] == 4 else np.full((dim, dim), 255, np.uint8))
     assert len(np.unique(want)) >= 1

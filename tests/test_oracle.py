@@ -35,10 +35,17 @@ def test_fjxl_golden_bit_exact(built, name):
     assert hashlib.sha256(img.tobytes()).hexdigest() == manifest[name]["pixels_sha256"], "fixture generator drifted"
     data = open(os.path.join(GOLDEN, name + ".jxl"), "rb").read()
     assert len(data) == manifest[name]["jxl_bytes"]
-    out = jxlo.Decoded(data, dumps=False).rgb8
-    exp = _expected(name)
-    assert out.shape == exp.shape
-    assert np.array_equal(out, exp)
+    assert manifest[name]["bits"] == CASES[name][5]
+    o = jxlo.Decoded(data, dumps=True)
+    h, w, nc = img.shape
+    assert o.info["bits"] == CASES[name][5]
+    assert np.array_equal(o.buffer("modular").reshape(nc, h, w), np.moveaxis(img, -1, 0).astype(np.int32))
+    out = o.rgb8.copy()
+    o.close()
+    if CASES[name][5] == 8:
+        exp = _expected(name)
+        assert out.shape == exp.shape
+        assert np.array_equal(out, exp)
 
 
 def test_fjxl_live_when_reference_encoder_present(built, tmp_path):
@@ -59,6 +66,43 @@ def test_fjxl_live_when_reference_encoder_present(built, tmp_path):
         dec = jxlo.Decoded(out.read_bytes(), dumps=False).rgb8
         exp = np.repeat(img, 3, -1) if nc == 1 else img
         assert np.array_equal(dec, exp), (w, h, nc, effort)
+    # deep samples, full-range noise: 16-bit residuals, wide hybrid-uint tokens, YCoCg chroma one bit wider
+    # (every depth meets every size once, channels and effort cycling with it; then configs[3] at depth: 4K 16-bit RGBA)
+    cases = [(b, s, 1 + i % 4, i % 3) for i, (b, s) in enumerate((b, s) for b in (10, 12, 16) for s in ((257, 255), (1, 300), (2100, 40)))]
+    for bits, (w, h), nc, effort in cases + [(16, (3840, 2160), 4, 2)]:
+        img = rng.integers(0, 1 << bits, (h, w, nc)).astype("<u2")
+        raw = tmp_path / "in.raw"
+        img.tofile(raw)
+        out = tmp_path / "o.jxl"
+        subprocess.run([enc, str(raw), str(w), str(h), str(nc), str(bits), str(effort), str(out)], check=True)
+        o = jxlo.Decoded(out.read_bytes(), dumps=True)
+        m = o.buffer("modular").reshape(nc, h, w)
+        o.close()
+        assert np.array_equal(m, np.moveaxis(img, -1, 0).astype(np.int32)), (bits, w, h, nc, effort)
+
+
+def test_fjxl_scalar_and_avx2_agree_on_full_range_noise(built, tmp_path):
+    """DESIGN.md "fjxl's AVX-512 path": the fixture generator (AVX2, FJXL_ENABLE_AVX512=0) and the scalar build write the
+    same bytes for full-range noise at efforts 0 and 1, and the oracle decodes them exactly. (Nothing is asserted about
+    the AVX-512 build's output.)"""
+    import jxlo
+    encs = [os.path.join(ROOT, "oracle", "_ref", n) for n in ("fjxl_enc", "fjxl_enc_scalar")]
+    if not all(os.path.exists(e) for e in encs):
+        pytest.skip("oracle/_ref/fjxl_enc{,_scalar} not built (reference sources absent)")
+    rng = np.random.default_rng(11)
+    for (w, h) in ((264, 40), (300, 280)):
+        for nc in (3, 4):
+            img = rng.integers(0, 256, (h, w, nc)).astype(np.uint8)
+            raw = tmp_path / "in.raw"
+            img.tofile(raw)
+            for effort in (0, 1):
+                streams = []
+                for e in encs:
+                    out = tmp_path / "o.jxl"
+                    subprocess.run([e, str(raw), str(w), str(h), str(nc), "8", str(effort), str(out)], check=True)
+                    streams.append(out.read_bytes())
+                assert streams[0] == streams[1], (w, h, nc, effort)
+                assert np.array_equal(jxlo.Decoded(streams[0], dumps=False).rgb8, img), (w, h, nc, effort)
 
 
 def test_reference_decode_test_1x1_stream(built):
