@@ -13,10 +13,15 @@ Multi-GPU (`--gpus N`, launched by torch.distributed.run, one rank per GPU): fra
 decodes its own batch (weak scaling) with no data-path collective; RCCL is only used for the barrier and the
 max-over-ranks time.  MP/s follows the reference's definition xsize*ysize*1e-6/elapsed (tools/speed_stats.cc:107).
 
+A plain run sets up (encodes its distinct frames, uploads them), warms up, times `--steps` steps, writes `--dump-outputs`
+and prints the line. `--full` adds, after the timed steps, what the headline does not need: the stage launches run alone
+(`roofline`, `stage_*`), the schedule over libjxl-sized entropy tables (`libjxl_tables`), the end-to-end rate (`e2e`) and
+the CPU baseline (`cpu_baseline`); `--workload encode`: the whole encode (`e2e`) and its CPU baseline; `--workload
+lossless`: its CPU baseline.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
-import functools
 import json
 import os
 import sys
@@ -31,38 +36,19 @@ DUMP_CROP = 512      # --dump-outputs: side of the full-resolution crop of each 
 DUMP_CROP_FRAMES = 8
 
 
-@functools.lru_cache(maxsize=None)
-def _encoder_digest():
-    import hashlib
-    import libjxl_amd as J
-    with open(J.ENC_PATH, "rb") as f:
-        return hashlib.sha256(f.read()).hexdigest()[:16]
-
-
-def cached_stream(name, encode):
-    """A synthetic benchmark stream, cached in the build directory under the digest of the encoder library that wrote it
-    (a rebuilt encoder never reads a stream another build wrote; the encoder is deterministic, so the bytes are the same
-    whether they come from the cache or not)."""
-    import libjxl_amd as J
-    cache = os.path.join(os.path.dirname(J.ENC_PATH), "bench_cache", "%s_%s.jxl" % (name, _encoder_digest()))
-    if os.path.exists(cache):
-        return open(cache, "rb").read()
-    data = encode()
-    try:
-        os.makedirs(os.path.dirname(cache), exist_ok=True)
-        tmp = cache + ".%d" % os.getpid()
-        open(tmp, "wb").write(data)
-        os.replace(tmp, cache)
-    except OSError:
-        pass
-    return data
-
-
 def make_stream(xsize, ysize, distance, seed=177, max_clusters=0, ac_code_mode=0):
     import libjxl_amd as J
-    return cached_stream("%dx%d_d%.2f_s%d_c%d_m%d" % (xsize, ysize, distance, seed, max_clusters, ac_code_mode),
-                         lambda: J.encode_rgb8(J.synth_image(xsize, ysize, seed), distance=distance, strategy_mode=1,
-                                               max_clusters=max_clusters, ac_code_mode=ac_code_mode))
+    return J.encode_rgb8(J.synth_image(xsize, ysize, seed), distance=distance, strategy_mode=1, max_clusters=max_clusters,
+                         ac_code_mode=ac_code_mode)
+
+
+def encode_all(encode, n):
+    """[encode(0), ..., encode(n - 1)]: the distinct synthetic streams of a run, encoded by every run itself (nothing is
+    read from an earlier one), several at a time -- the encoder is deterministic and releases the GIL, so the bytes are
+    those of one encode after the other in a fraction of the time."""
+    import concurrent.futures
+    with concurrent.futures.ThreadPoolExecutor(max(1, min(n, 4))) as pool:
+        return list(pool.map(encode, range(n)))
 
 
 def dump_positions(frames, h, w, nc):
@@ -418,8 +404,7 @@ def lossless_main(args, J, sharding, torch, dist, rank, local_rank, world, xsize
     flags = J.LOSSLESS_RCT | J.LOSSLESS_SQUEEZE | J.LOSSLESS_WP
     if args.lossless_flags >= 0:  # measurement aid: other feature sets of the synthetic encoder
         flags = args.lossless_flags
-    datas = [cached_stream("lossless_%dx%d_s%d_f%d" % (xsize, ysize, 177 + i, flags),
-                           lambda i=i: J.encode_lossless(J.synth_image(xsize, ysize, 177 + i), flags)) for i in range(ndistinct)]
+    datas = encode_all(lambda i: J.encode_lossless(J.synth_image(xsize, ysize, 177 + i), flags), ndistinct)
     frames = [J.ModFrame(d) for d in datas]
     ctxs = [J.HipContext(local_rank) for _ in range(batch)]
     for i, c in enumerate(ctxs):
@@ -465,7 +450,7 @@ def lossless_main(args, J, sharding, torch, dist, rank, local_rank, world, xsize
                             "frac": round(alg * batch / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), "traffic": None,
                             "frames_per_launch": batch, "launch_ms": round(launch_ms, 3),
                             "note": "a Modular stream is a pixel-serial adaptive decode (one lane per stream): latency-bound, not HBM-bound"}}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import jxlo
             t = []
@@ -537,7 +522,7 @@ def encode_main(args, J, sharding, torch, dist, rank, local_rank, world, xsize, 
                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(alg / (transform_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
                             "traffic": None, "launch_ms": round(transform_ms, 4), "algorithmic_bytes_per_launch": alg,
                             "kernels_ms_per_frame": round(span_ms / batch, 4)}}
-        if world == 1:
+        if args.full and world == 1:
             def best_of(device_tokens):
                 best = None
                 for _ in range(3):
@@ -585,9 +570,15 @@ def main():
                     help="--shard bands: every rank decodes ONLY its own rows of groups and the few rows its filters read beyond "
                          "them are exchanged with the neighbouring ranks after the transform stage (RCCL send / recv of dense "
                          "device blocks; jxlhip_halo_*), instead of decoding one group row of overlap either side")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, after it: the CPU baselines, the same schedule over "
+                         "streams with 128 histogram clusters (libjxl_tables), the stage launches run alone (roofline, "
+                         "stage_*), the end-to-end rate (e2e; encode: the whole encode); without it a run sets up, warms up, "
+                         "times the steps, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-libjxl-tables", action="store_true",
-                    help="skip the second measurement of the default line (the same schedule over streams with 128 histogram clusters)")
+                    help="--full: skip the second measurement of the default line (the same schedule over streams with 128 "
+                         "histogram clusters)")
     ap.add_argument("--no-pipeline", action="store_true", help="one frame set: entropy, then transform+filter, in sequence")
     ap.add_argument("--two-set", action="store_true",
                     help="the round-1 schedule: entropy(set A) beside transform(B) -> filter+colour(B), the sets' XYB planes shared")
@@ -605,8 +596,8 @@ def main():
                          "launches). 0 = the two-set schedule selected by the other flags")
     ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic frames (seeds 177, 178, ...) cycled through every frame set")
     ap.add_argument("--e2e-frames", type=int, default=2048,
-                    help="frames of the end-to-end measurement (compressed bytes in host memory -> RGB8 in host memory, host parse / "
-                         "upload / GPU stages / download pipelined over host threads); 0 = skip")
+                    help="--full: frames of the end-to-end measurement (compressed bytes in host memory -> RGB8 in host memory, "
+                         "host parse / upload / GPU stages / download pipelined over host threads); 0 = skip")
     ap.add_argument("--max-clusters", type=int, default=0, help="sensitivity runs: histogram clusters of the synthetic encoder (0 = its default 64)")
     ap.add_argument("--workload", choices=("vardct", "lossless", "encode"), default="vardct",
                     help="vardct: BASELINE.json configs[1] (the headline); lossless: configs[3], 3840x2160 Modular lossless "
@@ -679,7 +670,7 @@ def main():
     # set: sections, token counts and entropy tables differ from frame to frame, so the workgroups of a launch do not all
     # finish together
     ndistinct = max(1, min(args.distinct, args.batch))
-    datas = [make_stream(xsize, ysize, args.distance, 177 + i, args.max_clusters, args.ac_code_mode) for i in range(ndistinct)]
+    datas = encode_all(lambda i: make_stream(xsize, ysize, args.distance, 177 + i, args.max_clusters, args.ac_code_mode), ndistinct)
     frames = [J.Frame(d, threads=min(8, os.cpu_count() or 1)) for d in datas]
     data, frame = datas[0], frames[0]
     info = dict(frame.info)
@@ -840,39 +831,41 @@ def main():
     elapsed = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:  # (before the isolated launches below overwrite the pixels of sets[0])
         dump_outputs(args.dump_outputs, last, lambda c: c.rgb8(), ndistinct)
-    # duration of the entropy launches: HIP events on the stream each batch kernel was launched on; the events of the
-    # last launch of every set are still in place after the region
-    if free_running:  # frames-weighted mean of the sets' last entropy launches, expressed per whole batch like the other modes
-        entropy_ms = sum(cs[0].stage_ms(0) for cs in sets) * args.steps
-    else:
-        entropy_ms = sum(cs[0].stage_ms(0) for cs in sets) / float(nsets) * args.steps
     frames_local = args.batch * args.steps * share
     total_frames, max_elapsed = sharding.aggregate(frames_local, elapsed, dist)
-    # transform and filter+colour: the same batched launches over one set, run alone after the timed region (inside the
-    # region their kernels share the GPU with the concurrently running entropy kernel); per frame = launch time / frames
-    iso = [0.0, 0.0]
-    c = sets[0][0]
-    for which, fn in ((1, J.run_transform_batch), (2, J.run_filter_color_batch)):
-        best = 1e9
-        for _ in range(3):
-            fn(sets[0])
+    # (from here to the line, --full only: runs of their own after the timed region, none of which `value` needs)
+    if args.full:
+        # duration of the entropy launches: HIP events on the stream each batch kernel was launched on; the events of the
+        # last launch of every set are still in place after the region
+        if free_running:  # frames-weighted mean of the sets' last entropy launches, expressed per whole batch like the other modes
+            entropy_ms = sum(cs[0].stage_ms(0) for cs in sets) * args.steps
+        else:
+            entropy_ms = sum(cs[0].stage_ms(0) for cs in sets) / float(nsets) * args.steps
+        # transform and filter+colour: the same batched launches over one set, run alone after the timed region (inside the
+        # region their kernels share the GPU with the concurrently running entropy kernel); per frame = launch time / frames
+        iso = [0.0, 0.0]
+        c = sets[0][0]
+        for which, fn in ((1, J.run_transform_batch), (2, J.run_filter_color_batch)):
+            best = 1e9
+            for _ in range(3):
+                fn(sets[0])
+                c.sync()
+                best = min(best, c.stage_ms(which))
+            iso[which - 1] = best / len(sets[0])
+        # the entropy launch alone too (inside the region two of them overlap each other and the other stages)
+        ent_alone = 1e9
+        for _ in range(2):
+            J.run_entropy_batch(sets[0])
             c.sync()
-            best = min(best, c.stage_ms(which))
-        iso[which - 1] = best / len(sets[0])
-    # the entropy launch alone too (inside the region two of them overlap each other and the other stages)
-    ent_alone = 1e9
-    for _ in range(2):
-        J.run_entropy_batch(sets[0])
-        c.sync()
-        ent_alone = min(ent_alone, c.stage_ms(0))
-    stage_ms = [entropy_ms / args.steps / args.batch, iso[0], iso[1]]
+            ent_alone = min(ent_alone, c.stage_ms(0))
+        stage_ms = [entropy_ms / args.steps / args.batch, iso[0], iso[1]]
     # The same schedule over streams with libjxl-sized entropy tables: the synthetic encoder clusters
     # to at most 64 histograms by default, libjxl to kClustersLimit = 128 (lib/jxl/enc_ans.cc:931), whose alias tables
     # (128 x 2^6 entries x 8 B = 64 KB per frame) no longer leave every frame of the launch resident in LDS: the lane kernel
     # then reads them in place from global memory. Reported beside `value`, never instead of it.
     libjxl_tables = None
-    if world == 1 and args.max_clusters == 0 and args.ac_code_mode == 0 and not args.no_libjxl_tables and args.shard == "frames":
-        datas128 = [make_stream(xsize, ysize, args.distance, 177 + i, 128, 0) for i in range(ndistinct)]
+    if args.full and world == 1 and args.max_clusters == 0 and args.ac_code_mode == 0 and not args.no_libjxl_tables and args.shard == "frames":
+        datas128 = encode_all(lambda i: make_stream(xsize, ysize, args.distance, 177 + i, 128, 0), ndistinct)
         frames128 = [J.Frame(d, threads=min(8, os.cpu_count() or 1)) for d in datas128]
         # Frames per step: 512 (when `value` runs more). 64 KB of alias tables in the 8-byte form leave one workgroup per CU
         # (86 KB per frame: 256 frames per launch, 45.8 GP/s); the six-byte form of jxl_hip_entropy_lanes.h (70 KB per frame) keeps
@@ -921,35 +914,36 @@ def main():
         px = xsize * ysize
         mps = total_frames * px * 1e-6 / max_elapsed
         bpp = sum(len(d) for d in datas) / float(ndistinct) * 8.0 / px
-        # algorithmic bytes per launch (one frame) of each stage, SURVEY.md §8d / DESIGN.md:
-        alg = {
-            "entropy (k_entropy_lanes)": info["ac_bytes"] + 6.0 * px,          # bitstream read + int16 coefficients written
-            "transform (k_idct_fast/k_dct/k_special)": (6.0 + 0.4 + 12.0) * px,  # coefficients + side info read, f32 XYB written
-            "filter+colour (k_filter_rows2)": (12.0 + 0.06 + 3.0) * px,           # f32 XYB + sigma read, RGB8 written
-        }
-        names = list(alg)
-        dom = max(range(3), key=lambda s: stage_ms[s])
-        achieved = alg[names[dom]] / (stage_ms[dom] * 1e-3) / 1e9
-        frames_per_launch = args.batch if dom == 0 else 1
-        # HBM traffic of the dominant kernel: PMC counters from separate rocprofv3 passes of this command (committed
-        # summary; 2 x FETCH_SIZE + WRITE_SIZE per dispatch), only quoted when taken at the same frames per launch
-        traffic, traffic_source = None, None
-        try:
-            pmc_name = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_pmc_traffic.json"))[-1]  # the latest round's
-            pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_name)))
-            key = ["k_entropy_lanes", "k_idct_fast<short, 4, 4>", "k_filter_rows2"][dom]
-            # (several instantiations of a kernel may be in the summary -- the libjxl-tables leg runs others: the one this
-            # command dispatched most often is the default line's)
-            matches = sorted(((v.get("dispatches", 0), name) for name, v in pmc.items() if isinstance(v, dict) and key in name), reverse=True)[:1]
-            for _, name in matches:
-                v = pmc[name]
-                if pmc.get("_frames_per_launch") == args.batch:
-                    traffic = int(v["hbm_kib_per_dispatch"] * 1024)  # FETCH_SIZE doubled (gfx950: the guide's correction) + WRITE_SIZE
-                    # (PMC counters cannot be collected inside this run: the figure is the committed profile's, named with the
-                    # commit it was taken at, for a launch of the same frames per launch)
-                    traffic_source = "profiles/%s (separate rocprofv3 --pmc passes of this command at commit %s)" % (pmc_name, pmc.get("_commit", "unknown"))
-        except (OSError, ValueError, KeyError, TypeError):
-            pass
+        if args.full:
+            # algorithmic bytes per launch (one frame) of each stage, SURVEY.md §8d / DESIGN.md:
+            alg = {
+                "entropy (k_entropy_lanes)": info["ac_bytes"] + 6.0 * px,          # bitstream read + int16 coefficients written
+                "transform (k_idct_fast/k_dct/k_special)": (6.0 + 0.4 + 12.0) * px,  # coefficients + side info read, f32 XYB written
+                "filter+colour (k_filter_rows2)": (12.0 + 0.06 + 3.0) * px,           # f32 XYB + sigma read, RGB8 written
+            }
+            names = list(alg)
+            dom = max(range(3), key=lambda s: stage_ms[s])
+            achieved = alg[names[dom]] / (stage_ms[dom] * 1e-3) / 1e9
+            frames_per_launch = args.batch if dom == 0 else 1
+            # HBM traffic of the dominant kernel: PMC counters from separate rocprofv3 passes of this command (committed
+            # summary; 2 x FETCH_SIZE + WRITE_SIZE per dispatch), only quoted when taken at the same frames per launch
+            traffic, traffic_source = None, None
+            try:
+                pmc_name = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_pmc_traffic.json"))[-1]  # the latest round's
+                pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_name)))
+                key = ["k_entropy_lanes", "k_idct_fast<short, 4, 4>", "k_filter_rows2"][dom]
+                # (several instantiations of a kernel may be in the summary -- the libjxl-tables leg runs others: the one this
+                # command dispatched most often is the default line's)
+                matches = sorted(((v.get("dispatches", 0), name) for name, v in pmc.items() if isinstance(v, dict) and key in name), reverse=True)[:1]
+                for _, name in matches:
+                    v = pmc[name]
+                    if pmc.get("_frames_per_launch") == args.batch:
+                        traffic = int(v["hbm_kib_per_dispatch"] * 1024)  # FETCH_SIZE doubled (gfx950: the guide's correction) + WRITE_SIZE
+                        # (PMC counters cannot be collected inside this run: the figure is the committed profile's, named with the
+                        # commit it was taken at, for a launch of the same frames per launch)
+                        traffic_source = "profiles/%s (separate rocprofv3 --pmc passes of this command at commit %s)" % (pmc_name, pmc.get("_commit", "unknown"))
+            except (OSError, ValueError, KeyError, TypeError):
+                pass
         out = {
             "metric": "megapixels/sec decode, %dx%d VarDCT d%.1f" % (xsize, ysize, args.distance),
             "value": round(mps, 2),
@@ -979,31 +973,35 @@ def main():
                 "xyb_planes": "shared by the two sets" if nsets == 2 and not args.no_share_planes and not three and not free_running else "per frame", "parallelism": ("frames sharded over %d GPU(s), no data-path collective" % world) if args.shard == "frames" else
                 (("every frame split into %d bands of group rows, one per GPU; the rows a band's filters read beyond it are exchanged after the transform stage (RCCL send / recv)" % world) if args.halo else
                  ("every frame split into %d bands of group rows, one per GPU; each GPU also decodes the group row above and below its band, no exchange" % world))},
-            "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
-                         "frames_per_launch": frames_per_launch, "launch_ms": round(stage_ms[dom] * frames_per_launch, 4),
-                         "launch_ms_alone": round(ent_alone, 4) if dom == 0 else None,
-                         # > 1: consecutive steps' launches of this kernel (one per frame set, each on its own stream) overlap
-                         "launch_overlap_factor": round(stage_ms[dom] * frames_per_launch / (max_elapsed / args.steps * 1e3), 3) if dom == 0 else None,
-                         "frac_alone": round(alg[names[0]] * args.batch / (ent_alone * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if dom == 0 else None,
-                         "algorithmic_bytes_per_launch": int(alg[names[dom]] * frames_per_launch),
-                         "note": ("entropy decode is serial per 256x256 group (latency-bound, not HBM-bound); amortised over the frames of one "
-                                  "launch. launch_ms is the live average over the timed region, where consecutive steps' entropy launches "
-                                  "(one per frame set, each on its own stream) overlap each other and the other two stages, so it exceeds "
-                                  "ms_per_step; launch_ms_alone / frac_alone: the same launch with nothing beside it") if dom == 0 else ""},
-            # the whole path against HBM: B_alg = 39.4 + bpp / 8 bytes per pixel for the three-pass formulation
-            "path_roofline": {"algorithmic_bytes_per_px": round(39.4 + bpp / 8.0, 3),
-                              "achieved_gbs_per_gpu": round((39.4 + bpp / 8.0) * mps * 1e6 / world / 1e9, 1),
-                              "frac_of_hbm_peak": round((39.4 + bpp / 8.0) * mps * 1e6 / world / 1e9 / HBM_PEAK_GBS, 4)},
-            "stage_ms_per_frame": {names[s]: round(stage_ms[s], 4) for s in range(3)},  # entropy: live, launch / frames; others: isolated
-            "stage_gbs": {names[s]: round(alg[names[s]] / (stage_ms[s] * 1e-3) / 1e9, 2) for s in range(3)},
-            "stage_hbm_frac": {names[s]: round(alg[names[s]] / (stage_ms[s] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for s in range(3)},
         }
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
+                               "frames_per_launch": frames_per_launch, "launch_ms": round(stage_ms[dom] * frames_per_launch, 4),
+                               "launch_ms_alone": round(ent_alone, 4) if dom == 0 else None,
+                               # > 1: consecutive steps' launches of this kernel (one per frame set, each on its own stream) overlap
+                               "launch_overlap_factor": round(stage_ms[dom] * frames_per_launch / (max_elapsed / args.steps * 1e3), 3) if dom == 0 else None,
+                               "frac_alone": round(alg[names[0]] * args.batch / (ent_alone * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if dom == 0 else None,
+                               "algorithmic_bytes_per_launch": int(alg[names[dom]] * frames_per_launch),
+                               "note": ("entropy decode is serial per 256x256 group (latency-bound, not HBM-bound); amortised over the frames of one "
+                                        "launch. launch_ms is the live average over the timed region, where consecutive steps' entropy launches "
+                                        "(one per frame set, each on its own stream) overlap each other and the other two stages, so it exceeds "
+                                        "ms_per_step; launch_ms_alone / frac_alone: the same launch with nothing beside it") if dom == 0 else ""}
+        # the whole path against HBM: B_alg = 39.4 + bpp / 8 bytes per pixel for the three-pass formulation
+        out["path_roofline"] = {"algorithmic_bytes_per_px": round(39.4 + bpp / 8.0, 3),
+                                "achieved_gbs_per_gpu": round((39.4 + bpp / 8.0) * mps * 1e6 / world / 1e9, 1),
+                                "frac_of_hbm_peak": round((39.4 + bpp / 8.0) * mps * 1e6 / world / 1e9 / HBM_PEAK_GBS, 4)}
+        if args.full:
+            out.update({
+                "stage_ms_per_frame": {names[s]: round(stage_ms[s], 4) for s in range(3)},  # entropy: live, launch / frames; others: isolated
+                "stage_gbs": {names[s]: round(alg[names[s]] / (stage_ms[s] * 1e-3) / 1e9, 2) for s in range(3)},
+                "stage_hbm_frac": {names[s]: round(alg[names[s]] / (stage_ms[s] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for s in range(3)},
+            })
         # (the end-to-end and the CPU legs: one-GPU runs only, so that the ranks of a scaling run end together)
-        if args.e2e_frames > 0 and args.shard == "frames" and world == 1:
+        if args.full and args.e2e_frames > 0 and args.shard == "frames" and world == 1:
             out["e2e"] = end_to_end(J, datas, args.e2e_frames, local_rank, xsize, ysize)
             out["e2e"]["single_image"] = single_image_api(J, data, xsize, ysize)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             ref = system_libjxl_baseline(data, xsize, ysize, os.cpu_count() or 1)
             out["cpu_baseline"] = ref if ref else cpu_baseline(data, xsize, ysize)
         print(json.dumps(out))

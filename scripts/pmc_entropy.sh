@@ -16,7 +16,7 @@ P2="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACT
 P3="SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT SQ_ACTIVE_INST_MISC SQ_INSTS_BRANCH SQ_INSTS_VALU_TRANS SQ_IFETCH SQ_WAVES SQ_INSTS_VMEM_WR"
 i=1
 for P in "$P1" "$P2" "$P3"; do
-  rocprofv3 --output-format csv --pmc $P -d $RAW/p$i -o p$i -- python3 $R/bench.py --no-pipeline --steps 2 --warmup 1 --no-cpu-baseline "$@" > $RAW/p$i.log 2>&1 || echo "pass $i failed"
+  rocprofv3 --output-format csv --pmc $P -d $RAW/p$i -o p$i -- python3 $R/bench.py --no-pipeline --steps 2 --warmup 1 --full --no-cpu-baseline "$@" > $RAW/p$i.log 2>&1 || echo "pass $i failed"
   tail -3 $RAW/p$i.log | cut -c1-400 > $R/$OUT/p$i.tail.txt
   i=$((i+1))
 done

@@ -13,7 +13,7 @@ RAW=/tmp/prof_raw_$$
 mkdir -p $RAW
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --e2e-frames 0 $@"
+BENCH="python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --e2e-frames 0 $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/stats -o s -- $BENCH > $R/$OUT/${TAG}_bench.json 2> $RAW/stats.log
 cp $(find $RAW/stats -name "*kernel_stats.csv" | head -1) $R/$OUT/${TAG}_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/iso -o s -- $BENCH --no-pipeline > $R/$OUT/${TAG}_bench_isolated.json 2> $RAW/iso.log
@@ -23,7 +23,7 @@ cp $(find $RAW/iso -name "*kernel_stats.csv" | head -1) $R/$OUT/${TAG}_kernel_st
 ( while true; do date >> $R/$OUT/heartbeat.txt; sleep 45; done ) &
 HB=$!
 export JXLHIP_ENTROPY_GATE=0  # (counter collection serialises the kernels: a gated launch would wait for one that cannot start)
-PMCBENCH="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --e2e-frames 0 $@"
+PMCBENCH="python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --e2e-frames 0 $@"
 rocprofv3 --output-format csv --kernel-include-regex "k_entropy|k_idct|k_filter|k_dct|k_special|k_color" --pmc FETCH_SIZE -d $RAW/f -o f -- $PMCBENCH > /dev/null 2> $RAW/f.log
 rocprofv3 --output-format csv --kernel-include-regex "k_entropy|k_idct|k_filter|k_dct|k_special|k_color" --pmc WRITE_SIZE -d $RAW/w -o w -- $PMCBENCH > /dev/null 2> $RAW/w.log
 kill $HB

@@ -12,7 +12,7 @@ RAW=/tmp/pmc_traffic_$$
 mkdir -p $RAW
 export TMPDIR=/tmp JXLHIP_ENTROPY_GATE=0
 cd /tmp
-BENCH="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --e2e-frames 0"
+BENCH="python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --e2e-frames 0"
 RE="k_entropy|k_idct|k_filter|k_dct|k_special|k_color"
 timeout -k 10 ${PMC_TIMEOUT:-260} rocprofv3 --output-format csv --kernel-include-regex "$RE" --pmc FETCH_SIZE -d $RAW/f -o f -- $BENCH > $OUT/pmc_bench.json 2> $RAW/f.log; echo "fetch pass rc $?"
 timeout -k 10 ${PMC_TIMEOUT:-260} rocprofv3 --output-format csv --kernel-include-regex "$RE" --pmc WRITE_SIZE -d $RAW/w -o w -- $BENCH > /dev/null 2> $RAW/w.log; echo "write pass rc $?"

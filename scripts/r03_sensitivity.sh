@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 : > $OUT/r03_sensitivity.txt
 for spec in "--distance 0.5" "--max-clusters 128" "--max-clusters 128 --distance 0.5" "--ac-code-mode 1" "--distance 2.0"; do
-  timeout -k 10 300 python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --e2e-frames 0 $spec > $OUT/sens_last.json 2> $OUT/sens_last.err
+  timeout -k 10 300 python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --e2e-frames 0 $spec > $OUT/sens_last.json 2> $OUT/sens_last.err
   tail -1 $OUT/sens_last.json | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())

@@ -6,6 +6,6 @@ mkdir -p $R/$OUT
 cd $R
 for v in "256 4" "128 4" "192 4" "256 6" "128 6"; do
   set -- $v
-  JXLAMD_E2E_CHUNK=$1 JXLAMD_E2E_MOVERS=$2 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-libjxl-tables 2>/dev/null | tail -1 | \
+  JXLAMD_E2E_CHUNK=$1 JXLAMD_E2E_MOVERS=$2 python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-libjxl-tables 2>/dev/null | tail -1 | \
     python3 -c "import sys,json; d=json.loads(sys.stdin.read())['e2e']; print('chunk $1 movers $2:', d['value'], 'MP/s', d['ms_per_frame'], d['stage_busy_ms_per_frame'])" | tee -a $OUT/e2e_variants.txt
 done

@@ -13,7 +13,7 @@ for spec in "$@"; do
       *) args="$args $w" ;;
     esac
   done
-  line=$(env $envs timeout -k 10 400 python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --e2e-frames 0 $args 2>/dev/null | tail -1)
+  line=$(env $envs timeout -k 10 400 python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --e2e-frames 0 $args 2>/dev/null | tail -1)
   python3 - "$spec" "$line" >> $OUT <<'PY'
 import json, sys
 try:

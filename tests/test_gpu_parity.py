@@ -1020,18 +1020,40 @@ def test_the_pipelined_bench_ends_when_the_runtime_runs_kernels_one_at_a_time(bu
     one kernel at a time a launch gated on ANOTHER launch's workgroups being resident may wait for a kernel that is not
     allowed to start. The library therefore drops the gate in such processes (RuntimeMaySerialise) whatever the caller
     asked for: the default pipelined schedule of bench.py, which asks for the gate, must end under each of the
-    serialising switches. A child process under a timeout, small frames."""
+    serialising switches. A child process under a timeout, small frames; --full, so that the launches
+    after the timed steps (the stages alone, the libjxl-tables leg over the same schedule) must end too."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--size", "768x512", "--batch", "12", "--distinct", "2", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--e2e-frames", "0"]
+           "--full", "--no-cpu-baseline", "--e2e-frames", "0"]
     r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["value"] > 0 and line["steps"] == 3
+    assert line["libjxl_tables"]["value"] > 0 and line["roofline"]["achieved"] > 0 and len(line["stage_ms_per_frame"]) == 3
+
+
+def test_a_plain_bench_run_times_its_steps_and_nothing_else(built):
+    """bench.py without --full prints the headline line and none of the figures that take runs of their own after the
+    timed steps (the stages alone, the libjxl-tables leg, the end-to-end rate, the CPU baseline)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--size", "768x512", "--batch", "12", "--distinct", "2", "--steps", "3", "--warmup", "1"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "megapixels/sec decode, 768x512 VarDCT d1.0" and line["unit"] == "MP/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["steps"] == 3 and line["warmup"] == 1
+    assert line["value"] > 0 and abs(line["value"] - 12 * 768 * 512 * 1e-6 / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+    assert line["libjxl_tables"] is None and line["value_libjxl_tables"] is None
+    for key in ("roofline", "stage_ms_per_frame", "stage_gbs", "stage_hbm_frac", "e2e", "cpu_baseline"):
+        assert key not in line, key
 
 
 @pytest.mark.parametrize("schedule", [[], ["--two-set"], ["--no-pipeline"], ["--sets", "3"]])
