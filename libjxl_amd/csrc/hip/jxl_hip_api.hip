@@ -159,7 +159,9 @@ struct Stage {
 };
 
 constexpr int kEntropyWPG = 4;  // waves (= AC sections) per workgroup of the scalar-form entropy kernel
-constexpr int kLanesWPG = 4;    // waves per workgroup of the lane-parallel entropy kernel (one frame per workgroup)
+// The LDS a frame's lane-kernel workgroup may need at most, in waves of 64 lanes: the test that admits a frame to the lane
+// kernel (jxlhip_frame_upload) still budgets four, though every launch now runs one wave per workgroup.
+constexpr int kLanesAdmitWaves = 4;
 constexpr size_t kLdsBudget = 150 * 1024;
 
 }  // namespace
@@ -213,10 +215,9 @@ struct JxlHipContext {
   } mod;
   size_t plane_bytes = 0;  // bytes of plane[0] the current frame needs
   Buf ep_dev;                         // device copy of `ep` (the entropy kernel reads it through the scalar cache)
-  Buf batch_wave_ls;
   size_t batch_off_units = 0, batch_off_queue = 0, batch_off_wave_lanes = 0, batch_units = 0;  // layout of batch_lanes
   Buf batch_params, batch_map, batch_lanes;  // jxlhip_run_entropy_batch: parameter blocks, workgroup map, lane map
-  uint32_t batch_wait_shift = 2, batch_lanes_per_wave = 64, batch_wpg = 4;
+  uint32_t batch_wait_shift = 2;
   bool batch_galias = false;  // the lane kernel reads its alias tables from global memory (PrepareBatch)
   bool batch_a6 = false;      // ... or keeps them in LDS in the six-byte form (jxl_hip_entropy_lanes.h LanesLdsLayout)
   bool batch_prefix = false;  // ... decodes prefix codes
@@ -343,12 +344,12 @@ struct JxlHipContext {
   int final_plane = 0;  // which plane set holds the filtered XYB after jxlhip_run_filter_color
 };
 
-// Which entropy kernel: 2 (default) lane-parallel k_entropy_lanes, 1 wave-per-section scalar k_entropy_uni,
-// 0 the first k_entropy_ans. Environment override JXLHIP_ENTROPY is for A/B measurements only.
-static int EntropyKernelChoice() {
-  static const int v = [] {
+// JXLHIP_ENTROPY=1 (a test hook): no frame takes the lane-parallel k_entropy_lanes, every frame the wave-per-section
+// fallback (k_entropy_uni, or k_entropy_ans for tables beyond the LDS budget) that multi-pass frames and large tables take.
+static bool SectionEntropyForced() {
+  static const bool v = [] {
     const char* e = getenv("JXLHIP_ENTROPY");
-    return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 2;
+    return e && e[0] == '1';
   }();
   return v;
 }
@@ -382,10 +383,6 @@ static bool ValidPrefixTables(uint32_t offset_word, const uint32_t* table, size_
 static int EnvInt(const char* name, int def) {
   const char* e = getenv(name);
   return e && *e ? atoi(e) : def;
-}
-
-static size_t LanesLdsFor(const JxlHipContext* c, uint32_t lanes = 64) {
-  return jxlhip::LanesLdsLayout(1, c->ep.nctx, c->pass_clusters[0], c->pass_log_alpha[0], kLanesWPG, lanes).total;
 }
 
 extern "C" {
@@ -536,7 +533,7 @@ int jxlhip_ctx_create(int device, JxlHipContext** out) {
 static std::vector<Buf*> AllBufs(JxlHipContext* c) {
   std::vector<Buf*> all = {&c->basis, &c->sections, &c->sec_word, &c->sec_size, &c->blocks, &c->gbb, &c->bctx_lut, &c->dequant, &c->dc, &c->dc_raw, &c->dc_q, &c->dc_ep, &c->sharp,
                 &c->inv_sigma, &c->ytox, &c->ytob, &c->passes_dev, &c->coeffs, &c->errors, &c->plane[0], &c->plane[1],
-                &c->plane[2], &c->rgb, &c->tlist, &c->scratch, &c->ep_dev, &c->batch_params, &c->batch_map, &c->batch_lanes, &c->batch_wave_ls, &c->ups_kernel, &c->kend, &c->block_recs, &c->dequant_scan, &c->ec_stage, &c->alpha_patched, &c->trecs, &c->enc_tok_orders, &c->enc_tok_blk, &c->enc_tok_info,
+                &c->plane[2], &c->rgb, &c->tlist, &c->scratch, &c->ep_dev, &c->batch_params, &c->batch_map, &c->batch_lanes, &c->ups_kernel, &c->kend, &c->block_recs, &c->dequant_scan, &c->ec_stage, &c->alpha_patched, &c->trecs, &c->enc_tok_orders, &c->enc_tok_blk, &c->enc_tok_info,
                 &c->enc_tok_off, &c->enc_tok_nzmap, &c->enc_tok_small, &c->enc_tok_out, &c->enc_tok_base, &c->tb_params, &c->tb_desc, &c->fb_params, &c->alpha, &c->sec_end, &c->lz_window, &c->mod.pool, &c->mod.sections, &c->mod.blob, &c->mod.streams,
                 &c->mod.rects, &c->mod.status, &c->mod.end_bits, &c->mod.scratch, &c->mod.windows, &c->mod.batch_streams, &c->mod.batch_ops, &c->frame_blob, &c->noise, &c->spl_seg, &c->spl_row_start, &c->spl_row_seg, &c->spl_planes, &c->pat_rec, &c->pat_row_start, &c->pat_row_list,
                 &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes};
@@ -1130,8 +1127,7 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   if (!c->plane_lender && (r = c->plane[0].Ensure(plane_bytes))) return r;
   // pixels: RGB8 from every filter kernel, RGB f32 from the row-streaming one; any other format from the generic writer
   // (k_color_out on the filtered planes, or k_upsample_color)
-  c->color_out = !OutIsRgb8(c) && !(OutIsRgbF32(c) && c->ups == 1 && (c->epf_iters == 1 || c->epf_iters == 2) &&
-                                    !EnvInt("JXLHIP_FILTER_TILES", 0) && !EnvInt("JXLHIP_FILTER_ROWS1", 0));
+  c->color_out = !OutIsRgb8(c) && !(OutIsRgbF32(c) && c->ups == 1 && (c->epf_iters == 1 || c->epf_iters == 2));
   if (c->out_orient) c->color_out = true;  // (the oriented layout is written by the generic writer)
   // frames of images that are not XYB encoded (linear_output 2 = YCbCr, 3 = no colour transform): the colour stage is
   // XybToRgb's other branches, which only the generic writers take
@@ -1267,9 +1263,9 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   bool all_prefix = true;
   for (uint32_t p = 0; p < d->num_passes; p++) all_prefix = all_prefix && d->passes[p].use_prefix;
   c->lane_prefix = all_prefix && !any_lz77 && !EnvInt("JXLHIP_NO_LANE_PREFIX", 0);
-  c->lanes = EntropyKernelChoice() == 2 && ep.num_bctx <= 16 && d->num_passes <= 8 && (!generic || c->lane_prefix);
+  c->lanes = !SectionEntropyForced() && ep.num_bctx <= 16 && d->num_passes <= 8 && (!generic || c->lane_prefix);
   for (uint32_t p = 0; c->lanes && p < d->num_passes; p++)  // (alias tables that do not fit LDS are read in place)
-    c->lanes = jxlhip::LanesLdsLayout(1, ep.nctx, c->pass_clusters[p], c->pass_log_alpha[p], kLanesWPG, 64, false, c->lane_prefix).total <= kLdsBudget;
+    c->lanes = jxlhip::LanesLdsLayout(1, ep.nctx, c->pass_clusters[p], c->pass_log_alpha[p], kLanesAdmitWaves, 64, false, c->lane_prefix).total <= kLdsBudget;
   if (!c->lanes) c->lane_prefix = false;
   // (sections that have not arrived: the lane kernel takes a list of the ones that have; the section-per-workgroup kernels
   // step over a section of size 0 and leave the group's coefficients zeroed)
@@ -1445,10 +1441,9 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
 template <typename CoefT>
 static int LaunchEntropy(JxlHipContext* c) {
   const dim3 grid(c->ng), block(64);
-  const bool use_uni = EntropyKernelChoice() != 0;
   if (c->generic_codec) {
     hipLaunchKernelGGL(jxlhip::k_entropy_generic<CoefT>, grid, block, 3072, c->stream, c->ep);
-  } else if (c->alias_lds && use_uni) {
+  } else if (c->alias_lds) {
     // scalar-form kernel: alias tables, context map and uint configs shared in LDS by the waves of a workgroup
     const size_t shared = size_t(c->ep.lds_ctx_bytes) + c->ep.lds_alias_bytes + 1024;
     jxlhip::EntropyBatch b{c->ep_dev.as<jxlhip::EntropyParams>(), nullptr};
@@ -1466,14 +1461,8 @@ static int LaunchEntropy(JxlHipContext* c) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
       hipLaunchKernelGGL(k, grid, block, lds, c->stream, b);
     }
-  } else if (c->alias_lds) {
-    auto k = jxlhip::k_entropy_ans<CoefT, true>;
-    if (c->lds_entropy > 48 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_entropy)));
-    hipLaunchKernelGGL(k, grid, block, c->lds_entropy, c->stream, c->ep);
-  } else {
-    auto k = jxlhip::k_entropy_ans<CoefT, false>;
-    hipLaunchKernelGGL(k, grid, block, c->lds_entropy, c->stream, c->ep);
+  } else {  // alias tables beyond the LDS budget: read in place
+    hipLaunchKernelGGL(jxlhip::k_entropy_ans<CoefT>, grid, block, c->lds_entropy, c->stream, c->ep);
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1497,18 +1486,13 @@ static int RunEntropySingle(JxlHipContext* c) {
 }
 
 // ---- transform + filter launches, batched over the frames of a set ---------------------------------------------------
-// JXLHIP_IDCT_MATRIX=1 selects the matrix-form column kernel (k_idct_cols) instead of the fast in-register form.
-static bool IdctMatrixForm() { return EnvInt("JXLHIP_IDCT_MATRIX", 0) != 0; }
 // Varblocks a workgroup of the strategy's kernel handles.
 static uint32_t BlocksPerWG(int s) {
   static const uint8_t cx[27] = {1, 1, 1, 1, 2, 4, 1, 2, 1, 4, 2, 4, 1, 1, 1, 1, 1, 1, 8, 4, 8, 16, 8, 16, 32, 16, 32};
   static const uint8_t cy[27] = {1, 1, 1, 1, 2, 4, 2, 1, 4, 1, 4, 2, 1, 1, 1, 1, 1, 1, 8, 8, 4, 16, 16, 8, 32, 32, 16};
-  if (s == 0 || (s >= 4 && s <= 11)) {
-    if (IdctMatrixForm()) return jxlhip::kIdctColsThreads / (cx[s] * 8);  // k_idct_cols: 8 * covered_x threads per varblock
-    return jxlhip::IdctFastThreads(cx[s], cy[s]) / ((cx[s] > cy[s] ? cx[s] : cy[s]) * 8);  // k_idct_fast: max(rows, columns) threads
-  }
-  if (s >= 18 && s <= 20) return 1;                               // k_dct 64-class
-  return 4;                                                       // k_special
+  if (s == 0 || (s >= 4 && s <= 11) || (s >= 18 && s <= 20))  // k_idct_fast: max(rows, columns) threads per varblock
+    return jxlhip::IdctFastThreads(cx[s], cy[s]) / ((cx[s] > cy[s] ? cx[s] : cy[s]) * 8);
+  return 4;  // k_special
 }
 
 template <typename CoefT, int CX, int CY, bool CS = false>
@@ -1521,51 +1505,24 @@ static int LaunchIdctFast(JxlHipContext* c0, int s) {
   return 0;
 }
 
-template <typename CoefT, int CX, int CY>
-static int LaunchIdctCols(JxlHipContext* c0, int s) {
-  if (!IdctMatrixForm()) return LaunchIdctFast<CoefT, CX, CY>(c0, s);
-  constexpr int C = CX * 8, R = CY * 8, SIZE = CX * CY * 64, GROUPS = jxlhip::kIdctColsThreads / C;
-  constexpr size_t lds = (size_t(GROUPS) * (2 * SIZE + 4) + R * R) * sizeof(float);
-  auto k = jxlhip::k_idct_cols<CoefT, CX, CY>;
-  if (lds > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-  hipLaunchKernelGGL(k, dim3(c0->desc_count[s]), dim3(jxlhip::kIdctColsThreads), lds, c0->stream,
-                     c0->tb_params.as<jxlhip::TransformParams>(), c0->tb_desc.as<uint2>() + c0->desc_begin[s], uint32_t(s));
-  return 0;
-}
-
-template <typename CoefT, int CX, int CY>
-static int LaunchDct(JxlHipContext* c0, int s) {
-  constexpr int SIZE = CX * CY * 64;
-  constexpr size_t lds = size_t(3) * SIZE * sizeof(float);
-  auto k = jxlhip::k_dct<CoefT, CX, CY>;
-  if (lds > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-  hipLaunchKernelGGL(k, dim3(c0->desc_count[s]), dim3(256), lds, c0->stream, c0->tb_params.as<jxlhip::TransformParams>(),
-                     c0->tb_desc.as<uint2>() + c0->desc_begin[s], uint32_t(s));
-  return 0;
-}
-
 template <typename CoefT>
 static int LaunchTransforms(JxlHipContext* c0) {
   for (int s = 0; s < 21; s++) {
     if (!c0->desc_count[s]) continue;
     int e = 0;
     switch (s) {
-      case 0: e = LaunchIdctCols<CoefT, 1, 1>(c0, s); break;
-      case 4: e = LaunchIdctCols<CoefT, 2, 2>(c0, s); break;
-      case 5: e = LaunchIdctCols<CoefT, 4, 4>(c0, s); break;
-      case 6: e = LaunchIdctCols<CoefT, 1, 2>(c0, s); break;
-      case 7: e = LaunchIdctCols<CoefT, 2, 1>(c0, s); break;
-      case 8: e = LaunchIdctCols<CoefT, 1, 4>(c0, s); break;
-      case 9: e = LaunchIdctCols<CoefT, 4, 1>(c0, s); break;
-      case 10: e = LaunchIdctCols<CoefT, 2, 4>(c0, s); break;
-      case 11: e = LaunchIdctCols<CoefT, 4, 2>(c0, s); break;
-      // the 64-class: the fast (recursive even / odd) form too, one varblock per wave; JXLHIP_IDCT_MATRIX keeps the
-      // matrix-form kernel (the plain statement of the transform) reachable
-      case 18: e = IdctMatrixForm() ? LaunchDct<CoefT, 8, 8>(c0, s) : LaunchIdctFast<CoefT, 8, 8>(c0, s); break;
-      case 19: e = IdctMatrixForm() ? LaunchDct<CoefT, 4, 8>(c0, s) : LaunchIdctFast<CoefT, 4, 8>(c0, s); break;
-      case 20: e = IdctMatrixForm() ? LaunchDct<CoefT, 8, 4>(c0, s) : LaunchIdctFast<CoefT, 8, 4>(c0, s); break;
+      case 0: e = LaunchIdctFast<CoefT, 1, 1>(c0, s); break;
+      case 4: e = LaunchIdctFast<CoefT, 2, 2>(c0, s); break;
+      case 5: e = LaunchIdctFast<CoefT, 4, 4>(c0, s); break;
+      case 6: e = LaunchIdctFast<CoefT, 1, 2>(c0, s); break;
+      case 7: e = LaunchIdctFast<CoefT, 2, 1>(c0, s); break;
+      case 8: e = LaunchIdctFast<CoefT, 1, 4>(c0, s); break;
+      case 9: e = LaunchIdctFast<CoefT, 4, 1>(c0, s); break;
+      case 10: e = LaunchIdctFast<CoefT, 2, 4>(c0, s); break;
+      case 11: e = LaunchIdctFast<CoefT, 4, 2>(c0, s); break;
+      case 18: e = LaunchIdctFast<CoefT, 8, 8>(c0, s); break;  // (the 64-class: one varblock per wave)
+      case 19: e = LaunchIdctFast<CoefT, 4, 8>(c0, s); break;
+      case 20: e = LaunchIdctFast<CoefT, 8, 4>(c0, s); break;
       default:
         hipLaunchKernelGGL((jxlhip::k_special<CoefT>), dim3(c0->desc_count[s]), dim3(256), 0, c0->stream,
                            c0->tb_params.as<jxlhip::TransformParams>(), c0->tb_desc.as<uint2>() + c0->desc_begin[s], uint32_t(s));
@@ -1711,39 +1668,26 @@ static int LaunchFused(JxlHipContext* c0, const JxlHipContext::FilterGroup& g) {
   return 0;
 }
 
-// Gaborish + EPF1 (the d1.0 configuration) or + EPF1 + EPF2 (`epf` = 2): the row-streaming kernel, no LDS.
-static int LaunchFilterRows(JxlHipContext* c0, const JxlHipContext::FilterGroup& g, int epf = 1, bool gab = true) {
+// (Gaborish +) EPF1 (the d1.0 configuration) or EPF1 + EPF2 (`epf` = 2): the row-streaming kernel, no LDS.
+static int LaunchFilterRows(JxlHipContext* c0, const JxlHipContext::FilterGroup& g, int epf, bool gab) {
   const uint32_t cols = g.tiles_x * jxlhip::kFusedTW, rows = g.tiles_y * jxlhip::kFusedTH;  // upper bounds of the group
-  const bool one_px = epf == 1 && gab && EnvInt("JXLHIP_FILTER_ROWS1", 0) != 0;  // measurement aid: the one-column-per-lane form
-  const uint32_t per_wave = one_px ? jxlhip::kRowsLanes : jxlhip::kRows2Cols;
-  const uint32_t gx = ((cols + per_wave - 1) / per_wave + jxlhip::kRowsWaves - 1) / jxlhip::kRowsWaves;
+  const uint32_t gx = ((cols + jxlhip::kRows2Cols - 1) / jxlhip::kRows2Cols + jxlhip::kRowsWaves - 1) / jxlhip::kRowsWaves;
   // strip height: every strip re-reads and re-filters 6 halo rows, so the taller the better as long as the launch still
-  // has several waves for each of the chip's 1024 SIMDs
+  // has several waves for each of the chip's 1024 SIMDs (256 measured no better than 64: 0.0374 / 0.0361 / 0.0374 ms per 4K frame)
   uint32_t strip = jxlhip::kRowsStrip;
-  if (!one_px) {
-    const uint32_t want = uint32_t(EnvInt("JXLHIP_FILTER_STRIP", 0));
-    for (uint32_t s2 = want ? 256 : 128; s2 > strip; s2 >>= 1)  // (256 measured no better than 64: 0.0374 / 0.0361 / 0.0374 ms per 4K frame)
-      if (want ? s2 == want : uint64_t(gx) * jxlhip::kRowsWaves * ((rows + s2 - 1) / s2) * g.count >= 6 * 1024) {
-        strip = s2;
-        break;
-      }
-  }
+  if (uint64_t(gx) * jxlhip::kRowsWaves * ((rows + 2 * strip - 1) / (2 * strip)) * g.count >= 6 * 1024) strip *= 2;
   const uint32_t gy = (rows + strip - 1) / strip;
+  typedef void (*RowsKernel)(const jxlhip::FusedFilterParams*, int);
+  const RowsKernel k1t = jxlhip::k_filter_rows2<true, 1>, k1f = jxlhip::k_filter_rows2<false, 1>;
+  const RowsKernel k2t = jxlhip::k_filter_rows2<true, 2>, k2f = jxlhip::k_filter_rows2<false, 2>;
+  const RowsKernel n1t = jxlhip::k_filter_rows2<true, 1, false>, n1f = jxlhip::k_filter_rows2<false, 1, false>;
+  const RowsKernel n2t = jxlhip::k_filter_rows2<true, 2, false>, n2f = jxlhip::k_filter_rows2<false, 2, false>;
+  const RowsKernel k = gab ? (epf == 2 ? (g.u8srgb ? k2t : k2f) : (g.u8srgb ? k1t : k1f))
+                           : (epf == 2 ? (g.u8srgb ? n2t : n2f) : (g.u8srgb ? n1t : n1f));
   for (uint32_t z = 0; z < g.count; z += 65535) {  // grid z limit
     const uint32_t zn = g.count - z < 65535 ? g.count - z : 65535;
     const jxlhip::FusedFilterParams* fp = c0->fb_params.as<jxlhip::FusedFilterParams>() + g.first + z;
-    if (one_px)
-      hipLaunchKernelGGL(jxlhip::k_filter_rows, dim3(gx, gy, zn), dim3(64 * jxlhip::kRowsWaves), 0, c0->fstream, fp);
-    else {
-      typedef void (*RowsKernel)(const jxlhip::FusedFilterParams*, int);
-      const RowsKernel k1t = jxlhip::k_filter_rows2<true, 1>, k1f = jxlhip::k_filter_rows2<false, 1>;
-      const RowsKernel k2t = jxlhip::k_filter_rows2<true, 2>, k2f = jxlhip::k_filter_rows2<false, 2>;
-      const RowsKernel n1t = jxlhip::k_filter_rows2<true, 1, false>, n1f = jxlhip::k_filter_rows2<false, 1, false>;
-      const RowsKernel n2t = jxlhip::k_filter_rows2<true, 2, false>, n2f = jxlhip::k_filter_rows2<false, 2, false>;
-      const RowsKernel k = gab ? (epf == 2 ? (g.u8srgb ? k2t : k2f) : (g.u8srgb ? k1t : k1f))
-                               : (epf == 2 ? (g.u8srgb ? n2t : n2f) : (g.u8srgb ? n1t : n1f));
-      hipLaunchKernelGGL(k, dim3(gx, gy, zn), dim3(64 * jxlhip::kRowsWaves), 0, c0->fstream, fp, int(strip));
-    }
+    hipLaunchKernelGGL(k, dim3(gx, gy, zn), dim3(64 * jxlhip::kRowsWaves), 0, c0->fstream, fp, int(strip));
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1933,43 +1877,9 @@ static int EndDownstreamBatch(JxlHipContext* const* ctxs, size_t n, bool filter_
   return 0;
 }
 
-template <typename CoefT, int WPG, bool AIDS, bool GALIAS, bool PREFIX = false, bool ASMT = false, bool A6 = false>
-static int LaunchEntropyLanesW(JxlHipContext* c0);
-template <typename CoefT, bool GALIAS, bool ASMT>
-static int LaunchEntropyLanesA(JxlHipContext* c0) {
-  if (EnvInt("JXLHIP_LANES_DEBUG", 0) || EnvInt("JXLHIP_LANES_PROF", 0))  // measurement aids: instrumented build of the kernel
-    return c0->batch_wpg == 1 ? LaunchEntropyLanesW<CoefT, 1, true, GALIAS, false, ASMT>(c0)
-                              : (c0->batch_wpg == 2 ? LaunchEntropyLanesW<CoefT, 2, true, GALIAS, false, ASMT>(c0)
-                                                    : LaunchEntropyLanesW<CoefT, 4, true, GALIAS, false, ASMT>(c0));
-  return c0->batch_wpg == 1 ? LaunchEntropyLanesW<CoefT, 1, false, GALIAS, false, ASMT>(c0)
-                            : (c0->batch_wpg == 2 ? LaunchEntropyLanesW<CoefT, 2, false, GALIAS, false, ASMT>(c0)
-                                                  : LaunchEntropyLanesW<CoefT, 4, false, GALIAS, false, ASMT>(c0));
-}
-template <typename CoefT, bool GALIAS>
-static int LaunchEntropyLanesG(JxlHipContext* c0) {
-  // the hand-written trip (jxl_hip_lanes_trip.inc) serves LDS alias tables with int16 coefficients; JXLHIP_LANES_CPP=1 keeps
-  // the C++ trip for that form too (the two are held against each other by tests/test_gpu_parity.py)
-  if constexpr (!GALIAS && sizeof(CoefT) == 2) {
-    if (!EnvInt("JXLHIP_LANES_CPP", 0)) return LaunchEntropyLanesA<CoefT, GALIAS, true>(c0);
-  }
-  return LaunchEntropyLanesA<CoefT, GALIAS, false>(c0);
-}
-template <typename CoefT>
-static int LaunchEntropyLanes(JxlHipContext* c0) {
-  if (c0->batch_prefix)  // (no instrumented build of the prefix form)
-    return c0->batch_wpg == 1 ? LaunchEntropyLanesW<CoefT, 1, false, true, true>(c0)
-                              : (c0->batch_wpg == 2 ? LaunchEntropyLanesW<CoefT, 2, false, true, true>(c0)
-                                                    : LaunchEntropyLanesW<CoefT, 4, false, true, true>(c0));
-  if constexpr (sizeof(CoefT) == 2) {
-    if (c0->batch_a6)  // (PrepareBatch: one wave per workgroup, int16 coefficients; no instrumented build)
-      return EnvInt("JXLHIP_LANES_CPP", 0) ? LaunchEntropyLanesW<CoefT, 1, false, false, false, false, true>(c0)
-                                           : LaunchEntropyLanesW<CoefT, 1, false, false, false, true, true>(c0);
-  }
-  return c0->batch_galias ? LaunchEntropyLanesG<CoefT, true>(c0) : LaunchEntropyLanesG<CoefT, false>(c0);
-}
-template <typename CoefT, int WPG, bool AIDS, bool GALIAS, bool PREFIX, bool ASMT, bool A6>
+template <typename CoefT, bool AIDS, bool GALIAS, bool PREFIX = false, bool A6 = false>
 static int LaunchEntropyLanesW(JxlHipContext* c0) {
-  auto k = jxlhip::k_entropy_lanes<CoefT, WPG, AIDS, GALIAS, PREFIX, ASMT, A6>;
+  auto k = jxlhip::k_entropy_lanes<CoefT, AIDS, GALIAS, PREFIX, A6>;
   if (c0->batch_lds > 48 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(c0->batch_lds)));
   jxlhip::EntropyLaneBatch b;
@@ -1982,26 +1892,18 @@ static int LaunchEntropyLanesW(JxlHipContext* c0) {
   b.wave_lanes = blob + c0->batch_off_wave_lanes;
   HIP_TRY(hipMemsetAsync(b.queue, 0, c0->batch_units * 4, c0->stream));
   b.wait_shift = c0->batch_wait_shift;
-  {
-    // rounds (hot trips + transition pass) per refill round; the hand-written loop runs several groups of trips per round
-    int every = EnvInt("JXLHIP_REFILL_EVERY", ASMT ? 1 : int(jxlhip::kLanesRefillEvery));
-    if (every < 1 || (every & (every - 1))) every = int(jxlhip::kLanesRefillEvery);
-    b.refill_mask = uint32_t(every - 1);
-  }
-  b.prio = uint32_t(EnvInt("JXLHIP_LANES_PRIO", 0));
-  b.extra_pass_min = uint32_t(EnvInt("JXLHIP_EXTRA_PASS_MIN", 8));
-  if (b.extra_pass_min < 1) b.extra_pass_min = 1;
-  b.wave_log_ls = c0->batch_wave_ls.as<uint8_t>();
+  b.refill_mask = jxlhip::kLanesAsmTrip<CoefT, GALIAS, PREFIX> ? 0u : jxlhip::kLanesRefillEvery - 1;
+  b.extra_pass_min = jxlhip::kLanesExtraPassMin;
   b.debug = uint32_t(EnvInt("JXLHIP_LANES_DEBUG", 0));
   b.prof = nullptr;
   b.started = c0->batch_ctxs.size() > 1 ? GateCounter(c0) : nullptr;
   const bool prof = EnvInt("JXLHIP_LANES_PROF", 0) != 0;  // debugging aid: per-wave cycle split, printed to stderr
-  const size_t nwaves = size_t(c0->batch_wgs) * WPG;
+  const size_t nwaves = c0->batch_wgs;
   if (prof) {
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.prof), nwaves * 64));
     HIP_TRY(hipMemsetAsync(b.prof, 0, nwaves * 64, c0->stream));
   }
-  hipLaunchKernelGGL(k, dim3(c0->batch_wgs), dim3(64 * WPG), c0->batch_lds, c0->stream, b);
+  hipLaunchKernelGGL(k, dim3(c0->batch_wgs), dim3(64), c0->batch_lds, c0->stream, b);
   HIP_TRY(hipGetLastError());
   if (b.started) {
     // "resident" = as many of its workgroups as the chip's LDS holds at once, less a margin (the rest start as the first
@@ -2048,6 +1950,19 @@ static int LaunchEntropyLanesW(JxlHipContext* c0) {
   return 0;
 }
 
+// The lane kernel's forms: prefix codes, six-byte LDS tables (int16 coefficients), or alias tables in LDS / in global
+// memory; the last two also as the instrumented build (JXLHIP_LANES_DEBUG / JXLHIP_LANES_PROF, measurement aids).
+template <typename CoefT>
+static int LaunchEntropyLanes(JxlHipContext* c0) {
+  if (c0->batch_prefix) return LaunchEntropyLanesW<CoefT, false, true, true>(c0);
+  if constexpr (sizeof(CoefT) == 2) {
+    if (c0->batch_a6) return LaunchEntropyLanesW<CoefT, false, false, false, true>(c0);
+  }
+  if (EnvInt("JXLHIP_LANES_DEBUG", 0) || EnvInt("JXLHIP_LANES_PROF", 0))
+    return c0->batch_galias ? LaunchEntropyLanesW<CoefT, true, true>(c0) : LaunchEntropyLanesW<CoefT, true, false>(c0);
+  return c0->batch_galias ? LaunchEntropyLanesW<CoefT, false, true>(c0) : LaunchEntropyLanesW<CoefT, false, false>(c0);
+}
+
 template <typename CoefT>
 static int LaunchEntropyUniBatch(JxlHipContext* c0) {
   auto k = jxlhip::k_entropy_uni<CoefT, kEntropyWPG>;
@@ -2069,7 +1984,6 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
   std::vector<jxlhip::EntropyParams> params(n);
   std::vector<uint32_t> map, list, unit_desc;
   std::vector<uint8_t> wave_lanes;
-  std::vector<uint8_t> wave_ls;
   size_t lds = 0;
   for (size_t i = 0; i < n; i++) params[i] = ctxs[i]->ep;
   if (kernel == 2) {
@@ -2081,20 +1995,14 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
     //     sections of 12k-100k tokens, 60 lanes). The cost of a section is estimated as bytes + kSectionBytes (token
     //     counts are unknown before decoding; a constant term dominates in sparse sections);
     //   * small batches that leave SIMDs empty spread over up to one lane per section;
-    //   * the lanes of a unit are split evenly over the waves of its workgroups, and a wave's LDS rows are strided by
-    //     its lane count rounded up to a power of two.
-    const uint32_t kSectionBytes = uint32_t(EnvInt("JXLHIP_SECTION_BYTES", 4000));
-    const size_t target_waves = size_t(EnvInt("JXLHIP_TARGET_WAVES", 1024));
-    const int forced = EnvInt("JXLHIP_LANES", 0);  // measurement aid: lanes per wave
-    const int spread = EnvInt("JXLHIP_SPREAD", 100);  // percent of the minimum lane count (>= 100)
-    c0->batch_wait_shift = uint32_t(EnvInt("JXLHIP_WAIT_SHIFT", 1));
-    // waves per workgroup: ONE. The waves of a workgroup slow each other down (a lone 4K frame, one lane per wave: 832
+    //   * the lanes of a unit are split evenly over its waves.
+    // One wave per workgroup: the waves of a workgroup slow each other down (a lone 4K frame, one lane per wave: 832
     // cycles per trip with four waves per workgroup, 517 with two, 417 with one; 29.6 / 24.1 / 19.6 ms for the frame:
     // profiles/r04_single_frame.txt), and a workgroup of its own per wave costs only another copy of the tables in LDS.
-    // JXLHIP_WPG = 2 / 4 keeps the shared-table forms reachable.
-    uint32_t wpg = uint32_t(EnvInt("JXLHIP_WPG", 1));
-    if (wpg != 1 && wpg != 2) wpg = 4;
-    c0->batch_wpg = wpg;
+    constexpr uint32_t kSectionBytes = 4000;
+    constexpr size_t kTargetWaves = 1024;
+    const int forced = EnvInt("JXLHIP_LANES", 0);  // measurement aid: lanes per wave
+    c0->batch_wait_shift = uint32_t(EnvInt("JXLHIP_WAIT_SHIFT", 1));
     struct Unit {
       uint32_t frame, sel, pass, begin, count, min_lanes, lanes;
     };
@@ -2123,7 +2031,7 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
         u.pass = pass;
         u.begin = uint32_t(list.size());
         u.count = uint32_t(order.size());
-        u.min_lanes = uint32_t((total * uint64_t(spread < 100 ? 100 : spread) / 100 + longest - 1) / longest);
+        u.min_lanes = uint32_t((total + longest - 1) / longest);
         u.min_lanes = u.min_lanes > u.count ? u.count : (u.min_lanes ? u.min_lanes : 1);
         u.lanes = u.min_lanes;
         list.insert(list.end(), order.begin(), order.end());
@@ -2132,68 +2040,32 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
         units.push_back(u);
       }
     }
-    // lanes per wave: the fewest that fit all lanes into `target_waves` waves (a trip costs ~900 + 20 * lanes cycles)
+    // lanes per wave: the fewest that fit all lanes into kTargetWaves waves (a trip costs ~900 + 20 * lanes cycles)
     uint32_t lanes_per_wave = 1;
-    while (lanes_per_wave < 64 && (min_total + lanes_per_wave - 1) / lanes_per_wave > target_waves) lanes_per_wave *= 2;
+    while (lanes_per_wave < 64 && (min_total + lanes_per_wave - 1) / lanes_per_wave > kTargetWaves) lanes_per_wave *= 2;
     if (forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) lanes_per_wave = uint32_t(forced);
-    if (!EnvInt("JXLHIP_WPG", 0) && lanes_per_wave >= 32) {  // dense regime: one wave per workgroup, all of a unit's lanes
-      wpg = 1;                                                // in it (a trip costs about the same for 14 or 55 lanes)
+    if (lanes_per_wave >= 32) {  // dense regime: all of a unit's lanes in one wave (a trip costs about the same for 14 or 55 lanes)
       lanes_per_wave = 64;
       for (Unit& u : units)  // the wave's spare lanes are free: shorter lists per lane
         if (u.lanes < 64) u.lanes = u.count < 64 ? u.count : 64;
     }
-    c0->batch_wpg = wpg;
-    if (lanes_per_wave == 1 && min_total < target_waves) {  // room to spare: more lanes per unit, up to one per section
-      const double grow = double(target_waves) / double(min_total);
+    if (lanes_per_wave == 1 && min_total < kTargetWaves) {  // room to spare: more lanes per unit, up to one per section
+      const double grow = double(kTargetWaves) / double(min_total);
       for (Unit& u : units) {
         const uint32_t want = uint32_t(double(u.min_lanes) * grow);
         u.lanes = want > u.count ? u.count : (want < u.min_lanes ? u.min_lanes : want);
       }
     }
-    // Dense regime: a frame's few largest sections decide how long its launch lasts (the lane that decodes one of them
-    // runs one token per trip whatever the other lanes do, and every transition pass of the wave delays it), so they get a
-    // wave of their own with few lanes (few transitions to serve) beside the wave for all the other sections; the two
-    // share one set of LDS rows (EntropyLaneBatch::wave_log_ls).
-    const uint32_t split = (wpg == 1 && lanes_per_wave == 64) ? uint32_t(EnvInt("JXLHIP_SPLIT", 0)) : 0u;  // (0: measured slower on the benchmark frames)
-    std::vector<uint8_t> wg_shared;  // per workgroup: its waves share one row set
-    if (split && split < 64) {
-      wpg = 2;
-      c0->batch_wpg = 2;
-    }
     for (const Unit& u : units) {
-      if (split && split < 64) {
-        const uint32_t heavy = u.count >= 64 ? split : 0u;  // (a small unit: one wave)
-        const uint32_t first_index = uint32_t(unit_desc.size() / 4);
-        const uint32_t parts[2][2] = {{u.begin, heavy}, {u.begin + heavy, u.count - heavy}};
-        for (int part = 0; part < 2; part++) {
-          unit_desc.push_back(u.frame | u.sel << 16);
-          unit_desc.push_back(parts[part][0]);
-          unit_desc.push_back(parts[part][1]);
-          unit_desc.push_back(u.pass);
-        }
-        const uint32_t light_lanes = std::min<uint32_t>(64 - heavy, u.count - heavy);
-        map.push_back(first_index);
-        map.push_back(first_index + 1);
-        wave_lanes.push_back(uint8_t(heavy));
-        wave_lanes.push_back(uint8_t(light_lanes));
-        wave_ls.push_back(uint8_t(0x80 | (64 - heavy) % 64));  // the heavy wave's lanes use the top columns
-        wave_ls.push_back(uint8_t(0x80));
-        wg_shared.push_back(1);
-        continue;
-      }
-      const uint32_t per_wg = lanes_per_wave * wpg;
-      const uint32_t wgs = (u.lanes + per_wg - 1) / per_wg;
-      const uint32_t waves = wgs * wpg;
+      const uint32_t waves = (u.lanes + lanes_per_wave - 1) / lanes_per_wave;
       const uint32_t unit_index = uint32_t(unit_desc.size() / 4);
       unit_desc.push_back(u.frame | u.sel << 16);
       unit_desc.push_back(u.begin);
       unit_desc.push_back(u.count);
       unit_desc.push_back(u.pass);
-      for (uint32_t j = 0; j < wgs; j++) wg_shared.push_back(0);
       for (uint32_t w = 0; w < waves; w++) {  // even split of the unit's lanes over its waves
         const uint32_t cnt = u.lanes / waves + (w < u.lanes % waves ? 1u : 0u);
         map.push_back(unit_index);
-        wave_ls.push_back(uint8_t(0));  // (rows of its own, 64 lanes wide: jxl_hip_entropy_lanes.h)
         wave_lanes.push_back(uint8_t(cnt));
       }
     }
@@ -2204,18 +2076,18 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
     // Between the two, for tables of up to 128 clusters and 8192 slots (128 x 2^6: what libjxl writes for large frames): the six-byte
     // form of the tables in LDS (70 KB per frame: two frames per CU instead of one), when THAT leaves the launch resident.
     size_t lds_by_form[3] = {0, 0, 0};
-    const size_t num_wgs = map.size() / wpg;  // (`map` holds one unit per wave)
-    bool a6_ok = wpg == 1 && !c0->lane_prefix && c0->coef_bits == 16 && EnvInt("JXLHIP_A6", 1) != 0;
+    const size_t num_wgs = map.size();  // (`map` holds one unit per wave)
+    bool a6_ok = !c0->lane_prefix && c0->coef_bits == 16 && EnvInt("JXLHIP_A6", 1) != 0;
     for (int form = 0; form < 3; form++)
       for (size_t wg = 0; wg < num_wgs; wg++) {
-        const JxlHipContext* c = ctxs[unit_desc[size_t(map[wg * wpg]) * 4] & 0xFFFF];
-        const uint32_t up = unit_desc[size_t(map[wg * wpg]) * 4 + 3];  // the unit's pass
+        const JxlHipContext* c = ctxs[unit_desc[size_t(map[wg]) * 4] & 0xFFFF];
+        const uint32_t up = unit_desc[size_t(map[wg]) * 4 + 3];  // the unit's pass
         if (c->pass_log_alpha[up] > 7 || c->pass_clusters[up] > jxlhip::kLanesA6Clusters ||
             (size_t(c->pass_clusters[up]) << c->pass_log_alpha[up]) > jxlhip::kLanesA6Slots)
           a6_ok = false;
         size_t l = jxlhip::LanesLdsLayout(1, c->ep.nctx, c->pass_clusters[up], c->pass_log_alpha[up], 0, 0, form == 0 && !c0->lane_prefix,
                                           c0->lane_prefix, form == 2).wave0;
-        l += size_t(jxlhip::kLanesPerLaneBytes) * 64 * (wg_shared[wg] ? 1 : wpg);
+        l += size_t(jxlhip::kLanesPerLaneBytes) * 64;
         lds_by_form[form] = l > lds_by_form[form] ? l : lds_by_form[form];
       }
     int dev_cus = 256;
@@ -2233,10 +2105,10 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
     c0->batch_a6 = a6;
     c0->batch_galias = galias;
     c0->batch_prefix = c0->lane_prefix;
-    lds = lds_by_form[a6 ? 2 : (galias ? 1 : 0)] + size_t(EnvInt("JXLHIP_LDS_PAD", 0));  // (measurement aid: fewer workgroups per CU)
+    lds = lds_by_form[a6 ? 2 : (galias ? 1 : 0)];
     if (EnvInt("JXLHIP_PACK_DEBUG", 0))
-      fprintf(stderr, "[pack] units %zu sections %zu lanes(min) %zu lanes/wave %u waves/wg %u workgroups %zu lds %zu tables %s\n", units.size(),
-              total_sections, min_total, lanes_per_wave, wpg, map.size() / wpg, lds,
+      fprintf(stderr, "[pack] units %zu sections %zu lanes(min) %zu lanes/wave %u waves/wg 1 workgroups %zu lds %zu tables %s\n", units.size(),
+              total_sections, min_total, lanes_per_wave, map.size(), lds,
               c0->lane_prefix ? "prefix" : (a6 ? "lds6" : (galias ? "global" : "lds8")));
   } else {
     for (size_t i = 0; i < n; i++) {
@@ -2253,10 +2125,6 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
   if ((r = pc.Begin(c0))) return r;
   if ((r = pc.Add(c0->batch_params.p, params.data(), params.size() * sizeof(params[0])))) return r;
   if ((r = pc.Add(c0->batch_map.p, map.data(), map.size() * 4))) return r;
-  if (!wave_ls.empty()) {
-    if ((r = c0->batch_wave_ls.Ensure(wave_ls.size()))) return r;
-    if ((r = pc.Add(c0->batch_wave_ls.p, wave_ls.data(), wave_ls.size()))) return r;
-  }
   if (!list.empty()) {
     // one buffer: section list | unit descriptors (16-byte aligned) | queue counters | populated lanes per wave
     const size_t o_units = (list.size() * 4 + 15) & ~size_t(15), o_queue = o_units + unit_desc.size() * 4;
@@ -2276,7 +2144,7 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
   c0->batch_ctxs.assign(ctxs, ctxs + n);
   c0->batch_gens.resize(n);
   for (size_t i = 0; i < n; i++) c0->batch_gens[i] = ctxs[i]->generation;
-  c0->batch_wgs = uint32_t(kernel == 2 ? map.size() / c0->batch_wpg : map.size());
+  c0->batch_wgs = uint32_t(map.size());
   c0->batch_lds = lds;
   c0->batch_kernel = kernel;
   return 0;
@@ -2296,7 +2164,7 @@ extern "C" int jxlhip_run_entropy_batch(JxlHipContext* const* ctxs, size_t n) {
     if (n > 1 && !c->absent_groups.empty()) return JXLHIP_ERR_INVALID_ARGUMENT;  // (partial frames go one at a time: jxlhip_run_entropy)
     if (!c->lanes || c->coef_bits != c0->coef_bits || c->lane_prefix != c0->lane_prefix) all_scan = false;
     if (c->lanes || c->generic_codec || !c->alias_lds || c->ep.num_hist != 1 || c->np != 1 || c->coef_bits != c0->coef_bits ||
-        c->ng > 0xFFFF * kEntropyWPG || EntropyKernelChoice() == 0)
+        c->ng > 0xFFFF * kEntropyWPG)
       all_uni = false;
   }
   if (!all_scan && !all_uni) {
@@ -2337,21 +2205,6 @@ extern "C" int jxlhip_run_entropy_batch(JxlHipContext* const* ctxs, size_t n) {
       waited = ctxs[i]->pending_wait;
       ctxs[i]->pending_wait = nullptr;
     }
-  // Measurement aid (JXLHIP_SERIAL_ENTROPY=1): batched entropy launches of one device one after the other, whatever
-  // streams they are on.
-  static std::mutex serial_mu;
-  static hipEvent_t serial_tail[16] = {};
-  // MEASURED WORSE, hence off: alone beside the other sets' transform / filter launches for its whole length, a launch
-  // takes 112 - 126 ms (77 - 82 ms when two entropy launches overlap part of the time; 62 ms with nothing beside it):
-  // the lone waves lose far more to issue-bound neighbours on their SIMDs than to each other. s_setprio does not help.
-  const bool serial = n > 1 && c0->device >= 0 && c0->device < 16 && EnvInt("JXLHIP_SERIAL_ENTROPY", 0) != 0;
-  std::unique_lock<std::mutex> serial_lock(serial_mu, std::defer_lock);  // (held from the wait to the record: host threads)
-  if (serial) {
-    serial_lock.lock();
-    hipEvent_t& tail = serial_tail[c0->device];
-    if (!tail) HIP_TRY(hipEventCreateWithFlags(&tail, hipEventDisableTiming));
-    else HIP_TRY(hipStreamWaitEvent(c0->stream, tail, 0));
-  }
   lap("waits");
   HIP_TRY(hipEventRecord(c0->ev[0], c0->stream));
   for (size_t i = 0; i < n; i++)  // (the lane kernel writes every section's flag word itself, unless passes share it)
@@ -2382,7 +2235,6 @@ extern "C" int jxlhip_run_entropy_batch(JxlHipContext* const* ctxs, size_t n) {
   if (prof) fprintf(stderr, "[entropy batch] %s\n", prof_line.c_str());
   HIP_TRY(hipEventRecord(c0->ev[1], c0->stream));
   c0->ev_valid[0] = true;
-  if (serial) HIP_TRY(hipEventRecord(serial_tail[c0->device], c0->stream));
   if (n > 1) {
     HIP_TRY(hipEventRecord(c0->batch_done, c0->stream));
     for (size_t i = 1; i < n; i++) {
@@ -2966,10 +2818,9 @@ extern "C" int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n) {
       M0.batch_refs = M0.batch_refs || q.s->num_props > 16;
     }
     uint32_t tcap = 0;  // likewise for the largest set of symbol tables that fits
-    const uint32_t table_limit = uint32_t(EnvInt("JXLHIP_MOD_TABLE_WORDS", int(jxlhip::kModTableLdsWords)));  // (measurement aid)
     for (size_t i = 0; i < n; i++)
       for (uint32_t w : ctxs[i]->mod.code_table_words)
-        if (w <= table_limit && w > tcap) tcap = w;
+        if (w <= jxlhip::kModTableLdsWords && w > tcap) tcap = w;
     M0.batch_table_cap = tcap;
     std::vector<uint8_t> ops_blob;
     ModularBuildOps(ctxs, n, &ops_blob, &M0.batch_launches);
@@ -3078,12 +2929,12 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
   for (const JxlHipContext::FilterGroup& g : c0->fgroups) {
     switch (g.key) {
       case 0: r = LaunchFused<false, 0>(c0, g); break;
-      case 1: r = EnvInt("JXLHIP_FILTER_TILES", 0) ? LaunchFused<false, 1>(c0, g) : LaunchFilterRows(c0, g, 1, false); break;
-      case 2: r = EnvInt("JXLHIP_FILTER_TILES", 0) ? LaunchFused<false, 2>(c0, g) : LaunchFilterRows(c0, g, 2, false); break;
+      case 1: r = LaunchFilterRows(c0, g, 1, false); break;
+      case 2: r = LaunchFilterRows(c0, g, 2, false); break;
       case 3: r = LaunchFused<false, 3>(c0, g); break;
       case 4: r = LaunchFused<true, 0>(c0, g); break;
-      case 5: r = EnvInt("JXLHIP_FILTER_TILES", 0) ? LaunchFused<true, 1>(c0, g) : LaunchFilterRows(c0, g); break;
-      case 6: r = EnvInt("JXLHIP_FILTER_TILES", 0) ? LaunchFused<true, 2>(c0, g) : LaunchFilterRows(c0, g, 2); break;
+      case 5: r = LaunchFilterRows(c0, g, 1, true); break;
+      case 6: r = LaunchFilterRows(c0, g, 2, true); break;
       default: r = LaunchFused<true, 3>(c0, g); break;
     }
     if (r) return r;
@@ -3996,10 +3847,6 @@ static int EncLaunch(JxlHipContext* c, jxlhip::EncFwd& P, bool gaborish) {
         out = out == sets[0] ? sets[1] : sets[0];
       }
       P.planes = const_cast<float*>(in);
-    } else if (getenv("JXLHIP_ENC_SHARPEN_TILE")) {  // the LDS-tile form of the four rounds (the row form is held against it bit for bit)
-      hipLaunchKernelGGL(jxlhip::k_enc_sharpen4, dim3((P.xp + 63) / 64, (P.yp + 31) / 32, 3), dim3(256), 0, c->stream,
-                         static_cast<const float*>(sets[2]), sets[0], P.xp, P.yp);
-      P.planes = sets[0];
     } else {
       const uint32_t strips = (P.xp + jxlhip::kSharpenCols - 1) / jxlhip::kSharpenCols;
       hipLaunchKernelGGL(jxlhip::k_enc_sharpen_rows, dim3((strips + 3) / 4, (P.yp + jxlhip::kSharpenRows - 1) / jxlhip::kSharpenRows, 3), dim3(256), 0,

@@ -74,62 +74,6 @@ __global__ void k_enc_sharpen(const float* __restrict__ orig, const float* __res
   out[plane + size_t(yy) * xp + xx] = centre + (orig[plane + size_t(yy) * xp + xx] - blur);
 }
 
-// The four rounds in one launch: a 64x32 tile with a 4-sample apron in LDS; round k is computed on the tile grown by
-// 4 - k samples, so the last round has every neighbour it needs. Neighbour coordinates are clamped in IMAGE coordinates
-// exactly like the one-round kernel does, so positions outside the image are never read and each sample sees the same
-// operands in the same order as there.
-__global__ __launch_bounds__(256) void k_enc_sharpen4(const float* __restrict__ orig, float* __restrict__ out, uint32_t xp, uint32_t yp) {
-#pragma clang fp contract(off)
-  constexpr int TW = 64, TH = 32, H = 4, LW = TW + 2 * H, LH = TH + 2 * H;
-  __shared__ float s_o[LW * LH], s_a[LW * LH], s_b[LW * LH];
-  const int tx0 = int(blockIdx.x) * TW - H, ty0 = int(blockIdx.y) * TH - H, tid = threadIdx.x;
-  const size_t plane = size_t(xp) * yp * blockIdx.z;
-  for (int i = tid; i < LW * LH; i += 256) {
-    const int gx = tx0 + i % LW, gy = ty0 + i / LW;
-    if (gx < 0 || gy < 0 || gx >= int(xp) || gy >= int(yp)) continue;
-    const float v = orig[plane + size_t(gy) * xp + gx];
-    s_o[i] = v;
-    s_a[i] = v;
-  }
-  __syncthreads();
-  const float w1 = 1.1f * 0.104699568f, w2 = 1.1f * 0.055680538f, nrm = 1.0f / (1.0f + 4 * (w1 + w2));
-  float* y = s_a;
-  float* t = s_b;
-  // a tile whose apron lies inside the image needs no clamping: the neighbours are the LDS neighbours
-  const bool interior = tx0 >= 0 && ty0 >= 0 && tx0 + LW <= int(xp) && ty0 + LH <= int(yp);
-  for (int it = 1; it <= 4; it++) {
-    for (int i = tid; i < LW * LH; i += 256) {
-      const int lx = i % LW, ly = i / LW, gx = tx0 + lx, gy = ty0 + ly;  // (constant divisors)
-      if (lx < it || ly < it || lx >= LW - it || ly >= LH - it) continue;
-      int x0, x1, y0, y1;
-      const int yc = ly * LW;
-      if (interior) {
-        x0 = lx - 1;
-        x1 = lx + 1;
-        y0 = yc - LW;
-        y1 = yc + LW;
-      } else {
-        if (gx < 0 || gy < 0 || gx >= int(xp) || gy >= int(yp)) continue;
-        x0 = (gx ? gx - 1 : 0) - tx0;
-        x1 = (gx + 1 < int(xp) ? gx + 1 : int(xp) - 1) - tx0;
-        y0 = ((gy ? gy - 1 : 0) - ty0) * LW;
-        y1 = ((gy + 1 < int(yp) ? gy + 1 : int(yp) - 1) - ty0) * LW;
-      }
-      const float side = y[yc + x0] + y[yc + x1] + y[y0 + lx] + y[y1 + lx];
-      const float corner = y[y0 + x0] + y[y0 + x1] + y[y1 + x0] + y[y1 + x1];
-      const float centre = y[yc + lx];
-      const float blur = (centre + w1 * side + w2 * corner) * nrm;
-      const float v = centre + (s_o[yc + lx] - blur);
-      if (it == 4) out[plane + size_t(gy) * xp + gx] = v;
-      else t[yc + lx] = v;
-    }
-    __syncthreads();
-    float* sw = y;
-    y = t;
-    t = sw;
-  }
-}
-
 // The four rounds without LDS: a wave owns 64 adjacent columns (the middle 56 are written, four of halo either side) and
 // walks down a strip of rows. Round k of row r needs rows r - 1 .. r + 1 of round k - 1, so when source row s arrives
 // round 1 forms row s - 1, round 2 row s - 2, round 3 row s - 3 and round 4, the output, row s - 4: per round a window of

@@ -46,8 +46,7 @@ namespace jxlhip {
 
 struct EntropyLaneBatch {
   const EntropyParams* params;  // one per frame of the batch (device memory)
-  const uint32_t* wg_unit;      // per WAVE (workgroup * WPG + wave): its unit = sections of one frame that use one histogram set
-                                // (the waves of a workgroup serve the same frame, set and pass: they share its tables)
+  const uint32_t* wg_unit;      // per workgroup (one wave): its unit = sections of one frame that use one histogram set
   const uint4* units;           // per unit: {index into params | histogram selector << 16, first entry in `list`, entries, pass}
   const uint32_t* list;         // group (AC section) indices of every unit, largest compressed size first
   uint32_t* queue;              // per unit: next entry of its list to hand out (zeroed before the launch). A lane takes a
@@ -55,14 +54,9 @@ struct EntropyLaneBatch {
                                 // sections by actual decode time (a launch lasts as long as its busiest lane; sections
                                 // differ 8x in token count, which their byte size predicts poorly)
   const uint8_t* wave_lanes;    // per wave: populated lanes (the others idle)
-  uint32_t prio;                // non-zero: the waves raise their issue priority (s_setprio 3)
   uint32_t extra_pass_min;      // a service phase makes a further round of transitions only for at least this many lanes (>= 1)
   uint32_t wait_shift;          // the service phase runs once (waiting lanes << wait_shift) >= runnable lanes
   uint32_t refill_mask;         // a refill round every (refill_mask + 1) rounds (a power of two)
-  const uint8_t* wave_log_ls;   // per wave: where its lanes sit in the per-wave LDS rows (64 lanes wide): bit 7 set = the
-                                // workgroup's waves share ONE set of rows and this wave's lane l uses column (low 6 bits) + l
-                                // (a few lanes for the frame's largest sections beside a wave for all the others, at the LDS
-                                // cost of one wave); bit 7 clear = rows of its own, column l
   uint32_t debug;               // measurement aid: bit 0 = skip the coefficient stores (results are then invalid),
                                 // bit 1 = report every section's coefficient-token count in its error word
   unsigned long long* started;  // optional (may be NULL): every workgroup adds 1 when it begins (the host gates other launches on
@@ -81,7 +75,9 @@ constexpr uint32_t kLanesNzRows = 96;               // nzeros line buffer [chann
 constexpr uint32_t kLanesRingWords = 16;            // stream ring, u32; + 2 mirror rows (a 3-word read at slot 15 needs no wrap)
 constexpr uint32_t kLanesBlockRing = 8;             // packed block records, u32
 constexpr int kLanesTrips = 4;                      // hot trips per transition pass
-constexpr uint32_t kLanesRefillEvery = 4;           // rounds (trips + pass) per refill round; a power of two
+constexpr uint32_t kLanesRefillEvery = 4;           // rounds (trips + pass) per refill round of the C++ trip; a power of two
+                                                    // (the hand-written trip loops over groups itself: a refill round every round)
+constexpr uint32_t kLanesExtraPassMin = 8;          // EntropyLaneBatch::extra_pass_min
 constexpr uint32_t kLanesPerLaneBytes = kLanesNzRows + (kLanesRingWords + 2) * 4 + kLanesBlockRing * 4;
 // alias_lds = false: the alias tables stay in global memory (k_entropy_lanes<..., GALIAS = true>); prefix = true: prefix
 // codes (no alias tables at all; the per-cluster table offsets get a 1 KB region).
@@ -163,16 +159,18 @@ __device__ __forceinline__ uint32_t LaneHybrid(uint32_t tok, uint32_t cfg, uint3
   return (((((1u << msb) | (top & ((1u << msb) - 1))) << nb) | xb) << lsb) | low;
 }
 
-// AIDS = false compiles the measurement aids (B.prof, B.debug) out. GALIAS: the alias entries are read in place from
-// global memory (tables that would not leave every frame of the launch resident in LDS). PREFIX: prefix codes
-// (dec_huffman.h:28-41 in the two-level table form the host builds) instead of rANS.
-// ASMT: the hot trips are the hand-written group of jxl_hip_lanes_trip.inc (LDS alias tables, rANS, int16 coefficients only);
-// the C++ trip below is the statement of the algorithm, serves every other form and stays selectable for this one
-// (JXLHIP_LANES_CPP=1) so that the two can be held against each other bit for bit.
+// The hot trips are the hand-written group of jxl_hip_lanes_trip.inc for LDS alias tables, rANS and int16 coefficients;
+// the C++ trip below is the statement of the algorithm and serves every other form.
+template <typename CoefT, bool GALIAS, bool PREFIX>
+constexpr bool kLanesAsmTrip = sizeof(CoefT) == 2 && !GALIAS && !PREFIX;
+
+// One wave per workgroup. AIDS = false compiles the measurement aids (B.prof, B.debug) out. GALIAS: the alias entries are
+// read in place from global memory (tables that would not leave every frame of the launch resident in LDS). PREFIX: prefix
+// codes (dec_huffman.h:28-41 in the two-level table form the host builds) instead of rANS.
 // A6: the alias tables sit in LDS in the six-byte form (LanesLdsLayout): libjxl-sized tables, two frames per CU instead of one.
-template <typename CoefT, int WPG, bool AIDS, bool GALIAS = false, bool PREFIX = false, bool ASMT = false, bool A6 = false>
-__global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_) {
-  static_assert(!ASMT || (!GALIAS && !PREFIX && sizeof(CoefT) == 2), "the assembly trip: LDS alias tables, int16 coefficients");
+template <typename CoefT, bool AIDS, bool GALIAS = false, bool PREFIX = false, bool A6 = false>
+__global__ __launch_bounds__(64) void k_entropy_lanes(EntropyLaneBatch B_) {
+  constexpr bool ASMT = kLanesAsmTrip<CoefT, GALIAS, PREFIX>;
   static_assert(!A6 || (!GALIAS && !PREFIX), "the six-byte form is an LDS form of the rANS tables");
   EntropyLaneBatch B = B_;
   if (!AIDS) {
@@ -180,16 +178,12 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_)
     B.debug = 0;
   }
   extern __shared__ __align__(16) uint8_t lds_raw[];
-  if (B_.prio) __builtin_amdgcn_s_setprio(3);
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   if (B_.started && tid == 0) __hip_atomic_fetch_add(B_.started, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // ---- the launch description and the frame's parameter block, through the scalar cache into SGPRs
   typedef const uint32_t __attribute__((address_space(4)))* CU32;
-  const uint32_t wid = blockIdx.x * WPG + wave;
+  const uint32_t wid = blockIdx.x;
   const uint32_t unit = ((CU32)(uintptr_t)B.wg_unit)[wid];
-  const uint32_t wl = B.wave_log_ls[wid];
-  const uint32_t lane_off = __builtin_amdgcn_readfirstlane(wl & 63), region = __builtin_amdgcn_readfirstlane((wl & 0x80) ? 0u : wave);
   const CU32 ud = (CU32)(uintptr_t)(B.units + unit);
   const uint32_t wg_desc = ud[0], list_begin = ud[1], list_count = ud[2], pass = ud[3];
   const uint32_t wg_sel = wg_desc >> 16;  // the histogram set this workgroup's sections use
@@ -220,26 +214,26 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_)
   LdsU16* const l_nnz2 = (LdsU16*)(lds + L.ctx2);        // [ceil(nzeros left / covered)] -> 2 * kCoeffNumNonzeroContext
   LdsU16* const l_cfg = (LdsU16*)(lds + L.cfg);          // per cluster: split_exp | msb << 4 | lsb << 8
   LdsU32* const l_poff = (LdsU32*)(lds + L.poff);        // (PREFIX only)
-  const uint32_t wave_base = L.wave0 + region * (kLanesPerLaneBytes * 64);
-  const uint32_t col = lane_off + lane;  // this lane's column of the [row][64] arrays (lanes beyond the populated ones only read)
+  const uint32_t wave_base = L.wave0;
+  const uint32_t col = lane;  // this lane's column of the [row][64] arrays (lanes beyond the populated ones only read)
   LdsU8* const l_nz = lds + wave_base + col;                                          // nzeros line buffer [row][lane]
   const uint32_t ring_row0 = wave_base + kLanesNzRows * 64;                           // byte offset of stream-ring row 0
   const uint32_t bring_row0 = ring_row0 + (kLanesRingWords + 2) * 256;                // ... of block-record row 0
   LdsU32* const ring = (LdsU32*)(lds + ring_row0) + col;
   LdsU32* const bring = (LdsU32*)(lds + bring_row0) + col;
-  // LDS address of the dynamic segment + this wave's column offset (the DMA wants absolute addresses: row + 4 * lane)
-  const uint32_t lds_abs = uint32_t(uintptr_t(lds)) + lane_off * 4;
+  // LDS address of the dynamic segment (the DMA wants absolute addresses: row + 4 * lane)
+  const uint32_t lds_abs = uint32_t(uintptr_t(lds));
 
-  // ---- stage the frame's tables (whole workgroup)
+  // ---- stage the frame's tables
   {
     const uint32_t n_ctx = nctx + 16;  // the selected set's slice of the context map
     const uint8_t* ctx_slice = T.ctx_map + size_t(wg_sel) * nctx;
-    for (uint32_t i = tid; i < n_ctx; i += 64 * WPG) {
+    for (uint32_t i = tid; i < n_ctx; i += 64) {
       const uint32_t cl = ctx_slice[i];
       l_ctx[i] = uint8_t(cl < nclusters ? cl : nclusters - 1);
     }
     if (PREFIX)
-      for (uint32_t i = tid; i < nclusters; i += 64 * WPG) {
+      for (uint32_t i = tid; i < nclusters; i += 64) {
         const uint32_t cfg = T.cfg[i];
         l_cfg[i] = uint16_t((cfg & 15) | (((cfg >> 8) & 15) << 4) | (((cfg >> 16) & 15) << 8));
       }
@@ -249,7 +243,7 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_)
     // (repacked by jxlhip_frame_upload: PassDev::alias_packed; the uint config of the cluster rides in the spare bits
     // of x, so the trip needs no separate lookup for it)
     if (PREFIX)
-      for (uint32_t i = tid; i < nclusters; i += 64 * WPG) l_poff[i] = T.prefix_offset[i];
+      for (uint32_t i = tid; i < nclusters; i += 64) l_poff[i] = T.prefix_offset[i];
     const uint32_t n_alias = (GALIAS || PREFIX) ? 0u : nclusters << log_alpha;
     if constexpr (A6) {
       // the six-byte form (the host picks it for log_alpha <= 7, at most kLanesA6Clusters and kLanesA6Slots only): a cutoff of
@@ -258,7 +252,7 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_)
       LdsU16* const lb = (LdsU16*)(lds + kLanesA6B);
       LdsU32* const la = (LdsU32*)(lds + kLanesA6A);
       LdsU16* const lc = (LdsU16*)(lds + kLanesA6Cfg);
-      for (uint32_t i = tid; i < n_alias; i += 64 * WPG) {
+      for (uint32_t i = tid; i < n_alias; i += 64) {
         const uint2 e = galias[i];
         uint32_t cutoff = e.x >> 24, y = e.y & ((1u << (24 + log_alpha)) - 1);
         if (cutoff > entry_mask) {
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_)
       }
     } else {
       LdsU32x2* l_alias = (LdsU32x2*)(lds + L.alias);
-      for (uint32_t i = tid; i < n_alias; i += 64 * WPG) {
+      for (uint32_t i = tid; i < n_alias; i += 64) {
         const uint2 e = galias[i];
         l_alias[i] = LanesU32x2{e.x, e.y};
       }
@@ -280,7 +274,7 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_)
     if (tid < 64) l_nnz2[tid] = uint16_t(uint32_t(c_coeff_nnz_ctx[tid]) * 2);
     // 2 * kCoeffFreqContext(b) (ac_context.h:63-80), b = (k + 1) >> log2 covered: 1..63 in a valid stream; the entries
     // beyond continue the closed form (a corrupt stream may run a few positions past its block before it is stopped)
-    for (uint32_t b = tid; b < kLanesF2Bytes; b += 64 * WPG)
+    for (uint32_t b = tid; b < kLanesF2Bytes; b += 64)
       lds[L.f2 + b] = uint8_t(b < 64 ? uint32_t(c_coeff_freq_ctx[b]) * 2 : 2 * min(min(b - 1, 7 + (b >> 1)), 15 + (b >> 2)));
     LdsU32* z = (LdsU32*)(lds + wave_base);
     for (uint32_t i = lane; i < kLanesNzRows * 64 / 4; i += 64) z[i] = 0;
@@ -933,7 +927,7 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_)
     }
   }
   if (B.prof && lane == 0) {
-    unsigned long long* o = B.prof + size_t(blockIdx.x * WPG + wave) * 8;
+    unsigned long long* o = B.prof + size_t(blockIdx.x) * 8;
     o[0] = __builtin_readcyclecounter() - t_begin;
     o[1] = t_service;
     o[2] = n_service;
@@ -952,7 +946,7 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_lanes(EntropyLaneBatch B_)
   if (B.prof) {  // lane-trips of the wave (how full its trips were)
     unsigned long long total = n_lane_trips;
     for (int off = 32; off; off >>= 1) total += __shfl_down(total, off);
-    if (lane == 0) B.prof[size_t(blockIdx.x * WPG + wave) * 8 + 4] = total;
+    if (lane == 0) B.prof[size_t(blockIdx.x) * 8 + 4] = total;
   }
 }
 

@@ -4,11 +4,11 @@
 // Kernels and the reference code they replace:
 //   k_entropy_lanes (jxl_hip_entropy_lanes.h), k_entropy_uni, k_entropy_ans
 //                   lib/jxl/dec_group.cc:469-542,594-639 + dec_ans.h:170-257 + ans_common.h:102-142
-//   k_idct_cols<CX,CY>, k_dct<CX,CY>
+//   k_idct_fast<CX,CY>
 //                   lib/jxl/dec_group.cc:115-181 (dequant, CfL), dec_transforms-inl.h:691-818 (LLF from DC),
-//                   dct-inl.h:376-397 (scaled IDCT, evaluated here in its separable matrix form)
+//                   dct-inl.h:191-232,376-397 (scaled IDCT, recursive even / odd form)
 //   k_special       dec_transforms-inl.h:66-93,95-454,463-568 (IDENTITY, DCT2X2, DCT4X4, DCT4X8, DCT8X4, AFV0-3)
-//   k_dct_big       same as k_dct for 128/256-class transforms (global scratch instead of LDS)
+//   k_dct_big       128/256-class transforms, separable matrix form (global scratch instead of LDS)
 //   k_filter_fused (jxl_hip_filter_fused.h)
 //                   render_pipeline/stage_gaborish.cc:56-100, stage_epf.cc:82-494, stage_xyb.cc:80-92,
 //                   dec_xyb-inl.h:38-86, stage_from_linear.cc:114-144, cms/transfer_functions-inl.h:245-268,
@@ -130,14 +130,13 @@ __device__ __forceinline__ uint32_t BrRead(BitReader& b, uint32_t n) {  // n <= 
 }
 
 // One rANS symbol + hybrid-uint extra bits from `cluster`.
-template <bool ALIAS_LDS>
-__device__ __forceinline__ uint32_t ReadHybrid(BitReader& br, uint32_t& state, uint32_t cluster, const uint2* alias_g,
-                                               const uint2* alias_l, const uint32_t* cfg, uint32_t log_alpha) {
+__device__ __forceinline__ uint32_t ReadHybrid(BitReader& br, uint32_t& state, uint32_t cluster, const uint2* alias, const uint32_t* cfg,
+                                               uint32_t log_alpha) {
   const uint32_t log_entry = 12 - log_alpha;
   const uint32_t res = state & 0xFFFu;
   const uint32_t i = res >> log_entry;
   const uint32_t pos = res & ((1u << log_entry) - 1);
-  const uint2 e = ALIAS_LDS ? alias_l[(cluster << log_alpha) + i] : alias_g[(cluster << log_alpha) + i];
+  const uint2 e = alias[(cluster << log_alpha) + i];
   const uint32_t cutoff = e.x & 0xFF, right = (e.x >> 8) & 0xFF, freq0 = e.x >> 16;
   const uint32_t offsets1 = e.y & 0xFFFF, freq1 = e.y >> 16;
   const bool greater = pos >= cutoff;
@@ -160,15 +159,15 @@ __device__ __forceinline__ uint32_t ReadHybrid(BitReader& br, uint32_t& state, u
   return (((((1u << msb) | (hi & ((1u << msb) - 1))) << nbits) | bits) << lsb) | low;
 }
 
-// One 64-lane workgroup per 256x256 group. All lanes zero the group's coefficient planes and stage the entropy
-// tables in LDS; lane 0 then walks the (inherently serial) adaptive-context rANS stream.
-template <typename CoefT, bool ALIAS_LDS>
+// One 64-lane workgroup per 256x256 group, for alias tables beyond the LDS budget (read in place from global memory). All
+// lanes zero the group's coefficient planes and stage the context map in LDS; lane 0 then walks the (inherently serial)
+// adaptive-context rANS stream.
+template <typename CoefT>
 __global__ __launch_bounds__(64) void k_entropy_ans(EntropyParams P) {
   extern __shared__ __align__(16) uint8_t lds_raw[];
   const uint32_t g = blockIdx.x;
   const uint32_t lane = threadIdx.x;
   uint8_t* l_ctx = lds_raw;
-  uint2* l_alias = reinterpret_cast<uint2*>(lds_raw + P.lds_ctx_bytes);
   uint8_t* l_nz = lds_raw + P.lds_ctx_bytes + P.lds_alias_bytes;  // 3 * 1024
   const uint32_t b0 = P.gbb[g], b1 = P.gbb[g + 1];
   CoefT* gco = static_cast<CoefT*>(P.coeffs) + size_t(g) * 3 * 65536;
@@ -225,10 +224,6 @@ __global__ __launch_bounds__(64) void k_entropy_ans(EntropyParams P) {
     {
       const uint8_t* src = T.ctx_map + size_t(s_sel) * P.nctx;
       for (uint32_t i = lane; i < P.nctx + 16; i += 64) l_ctx[i] = src[i];
-      if (ALIAS_LDS) {
-        const uint32_t n = T.num_clusters << T.log_alpha;
-        for (uint32_t i = lane; i < n; i += 64) l_alias[i] = T.alias[i];
-      }
     }
     __threadfence_block();
     __syncthreads();
@@ -263,7 +258,7 @@ __global__ __launch_bounds__(64) void k_entropy_ans(EntropyParams P) {
         const uint32_t bctx = P.bctx_lut[((c * 13 + ord) * P.nq + qfi) * P.ndc + vb.quant_dc_ctx];
         uint32_t nzb = pred >= 64 ? 64 : pred;
         nzb = nzb < 8 ? nzb : 4 + nzb / 2;
-        uint32_t nzeros = ReadHybrid<ALIAS_LDS>(br, state, l_ctx[nzb * P.num_bctx + bctx], T.alias, l_alias, T.cfg, log_alpha);
+        uint32_t nzeros = ReadHybrid(br, state, l_ctx[nzb * P.num_bctx + bctx], T.alias, T.cfg, log_alpha);
         if (nzeros > size - covered) {
           err = kErrNzeros;
           break;
@@ -278,7 +273,7 @@ __global__ __launch_bounds__(64) void k_entropy_ans(EntropyParams P) {
         for (uint32_t k = covered; k < size && nzeros != 0; ++k) {
           const uint32_t nzl = (nzeros + covered - 1) >> log2c;
           const uint32_t ctx = hoff + (uint32_t(c_coeff_nnz_ctx[nzl & 63]) + c_coeff_freq_ctx[(k >> log2c) & 63]) * 2 + prev;
-          const uint32_t u = ReadHybrid<ALIAS_LDS>(br, state, l_ctx[ctx], T.alias, l_alias, T.cfg, log_alpha);
+          const uint32_t u = ReadHybrid(br, state, l_ctx[ctx], T.alias, T.cfg, log_alpha);
           const uint32_t mag = u >> 1, neg = (~u) & 1;
           const int32_t coeff = int32_t((mag ^ (neg - 1)) << shift);
           if (u) {
@@ -991,229 +986,6 @@ __device__ __forceinline__ float LlfFromDc(const PT& P, const float* dc, int ky,
   }
   s *= 1.0f / float(CX * CY);
   return s * c_resample[CY - 1 + ky] * c_resample[CX - 1 + kx];
-}
-
-// DCT-family strategies up to 64x64: per channel, dequantised coefficients are staged in LDS and the separable
-// inverse transform is evaluated as two matrix passes (LDS-resident tile, coalesced plane writes).
-template <typename CoefT, int CX, int CY>
-__global__ __launch_bounds__(256) void k_dct(const TransformParams* params, const uint2* desc, uint32_t strategy) {
-  JXL_TRANSFORM_PREAMBLE();
-  constexpr int R = CY * 8, C = CX * 8, SIZE = R * C;
-  constexpr int TPB = SIZE >= 256 ? 256 : SIZE;
-  constexpr int BPW = 256 / TPB;
-  extern __shared__ __align__(16) float lds_f[];
-  const int sub = threadIdx.x / TPB, t = threadIdx.x % TPB;
-  float* l_y = lds_f + sub * 3 * SIZE;  // dequantised Y stays resident for the chroma-from-luma of X and B
-  float* l_xb = l_y + SIZE;
-  float* l_tmp = l_xb + SIZE;
-  const uint32_t li = wgd.y + sub;
-  const bool active = li < n;
-  JxlHipVarBlock vb;
-  const CoefT* gq = nullptr;
-  const float* m = nullptr;
-  uint32_t msize = 0, bidx = 0;
-  float sc = 0, x_cc = 0, b_cc = 0;
-  if (active) {
-    bidx = list[li];
-    vb = P.blocks[bidx];
-    const uint32_t g = (vb.by >> 5) * P.xg + (vb.bx >> 5);
-    gq = static_cast<const CoefT*>(P.coeffs) + size_t(g) * 3 * 65536 + vb.coef_offset;
-    const uint32_t kind = c_strategy_qtable[strategy];
-    m = P.dequant + P.dq_offset[kind];
-    msize = P.dq_size[kind];
-    sc = P.inv_global_scale / float(vb.qf);
-    const uint32_t tiles_x = (P.xb + 7) / 8;
-    const uint32_t tile = (vb.by / 8) * tiles_x + vb.bx / 8;
-    x_cc = P.base_x + float(P.ytox[tile]) * P.color_scale;
-    b_cc = P.base_b + float(P.ytob[tile]) * P.color_scale;
-  }
-  const float* btc = P.basis_t + BasisOffset(C);
-  const float* btr = P.basis_t + BasisOffset(R);
-  for (int ci = 0; ci < 3; ci++) {
-    const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
-    float* l_coef = c == 1 ? l_y : l_xb;
-    if (active) {
-      const float mul = c == 1 ? sc : sc * (c == 0 ? P.x_dm : P.b_dm);
-      StageChannel<CoefT>(P, gq + size_t(c) * 65536, bidx, c, c_strategy_order[strategy], SIZE, CX * CY, m + size_t(c) * msize, mul,
-                          c == 0 ? x_cc : b_cc, l_y, l_coef, t, TPB);
-    }
-    __syncthreads();
-    if (active && t < CX * CY) {
-      const float* dc = P.dc + size_t(c) * P.xb * P.yb + size_t(vb.by) * P.xb + vb.bx;
-      // LLF corner: rows = short side
-      constexpr int LC = CX > CY ? CX : CY;  // long side
-      const int row = t / LC, col = t % LC;
-      int ky, kx;
-      if (CY < CX) { ky = row; kx = col; } else { kx = row; ky = col; }
-      l_coef[row * (LC * 8) + col] = LlfFromDc<CX, CY>(P, dc, ky, kx);
-    }
-    __syncthreads();
-    if (active) {
-      // pass A: tmp[ky][x] = sum_kx coef(ky,kx) * B_C[x][kx]
-      for (int i = t; i < SIZE; i += TPB) {
-        const int ky = i / C, x = i % C;
-        float s = 0.0f;
-        if (R < C) {
-#pragma unroll 8
-          for (int kx = 0; kx < C; kx++) s += l_coef[ky * C + kx] * btc[kx * C + x];
-        } else {
-#pragma unroll 8
-          for (int kx = 0; kx < C; kx++) s += l_coef[kx * R + ky] * btc[kx * C + x];
-        }
-        l_tmp[i] = s;
-      }
-    }
-    __syncthreads();
-    if (active) {
-      float* out = P.out + size_t(c) * P.xp * P.yp + size_t(vb.by) * 8 * P.xp + size_t(vb.bx) * 8;
-      for (int i = t; i < SIZE; i += TPB) {
-        const int y = i / C, x = i % C;
-        float s = 0.0f;
-#pragma unroll 8
-        for (int ky = 0; ky < R; ky++) s += l_tmp[ky * C + x] * btr[ky * R + y];
-        out[size_t(y) * P.xp + x] = s;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// DCT-family strategies up to 32x32, column-thread form. C = CX * 8 threads own one varblock, thread x owns column x:
-//   * dequantised coefficients are staged in LDS as [ky][kx] (zero / chroma-from-luma fill, then only the entropy
-//     stage's valid scan-order prefix is scattered through the coefficient order);
-//   * row pass:    tmp[ky] = sum_kx coef[ky][kx] * B_C[kx][x]   -- the thread keeps its basis column B_C[:][x] in
-//     registers and reads coefficient rows as LDS broadcasts (one ds_read_b128 per 4 FMAs, same address for the group);
-//   * column pass: out[y][x] = sum_ky tmp[ky] * B_R[ky][y]      -- tmp[] never leaves registers, the basis rows are LDS
-//     broadcasts as well (scalar-cache loads were measured to serialise on their latency), no second barrier;
-//   * row y of the block is written by the C threads of the group as one contiguous segment.
-typedef const float __attribute__((address_space(4)))* CF32;
-
-constexpr int kIdctColsThreads = 128;  // small workgroups: their LDS has to fit beside the resident entropy workgroups
-
-template <typename CoefT, int CX, int CY>
-__global__ __launch_bounds__(kIdctColsThreads) void k_idct_cols(const TransformParams* params, const uint2* desc, uint32_t strategy) {
-  JXL_TRANSFORM_PREAMBLE();
-  constexpr int R = CY * 8, C = CX * 8, SIZE = R * C, GSTRIDE = 2 * SIZE + 4;
-  extern __shared__ __align__(16) float lds_f[];
-  const int grp = threadIdx.x / C, x = threadIdx.x % C;
-  float* l_bn = lds_f;                          // column-pass basis [y][ky], read as broadcasts
-  float* l_y = lds_f + R * R + grp * GSTRIDE;  // dequantised Y stays resident for the chroma-from-luma of X and B
-  float* l_xb = l_y + SIZE;
-  const uint32_t li = wgd.y + grp;
-  const bool active = li < n;
-  JxlHipVarBlock vb;
-  const CoefT* gq = nullptr;
-  const float* m = nullptr;
-  uint32_t msize = 0, bidx = 0;
-  float sc = 0, x_cc = 0, b_cc = 0;
-  if (active) {
-    bidx = list[li];
-    vb = P.blocks[bidx];
-    const uint32_t g = (vb.by >> 5) * P.xg + (vb.bx >> 5);
-    gq = static_cast<const CoefT*>(P.coeffs) + size_t(g) * 3 * 65536 + vb.coef_offset;
-    const uint32_t kind = c_strategy_qtable[strategy];
-    m = P.dequant + P.dq_offset[kind];
-    msize = P.dq_size[kind];
-    sc = P.inv_global_scale / float(vb.qf);
-    const uint32_t tiles_x = (P.xb + 7) / 8;
-    const uint32_t tile = (vb.by / 8) * tiles_x + vb.bx / 8;
-    x_cc = P.base_x + float(P.ytox[tile]) * P.color_scale;
-    b_cc = P.base_b + float(P.ytob[tile]) * P.color_scale;
-  }
-  float breg[C];
-  {
-    const float* bt = P.basis_t + BasisOffset(C);
-#pragma unroll
-    for (int kx = 0; kx < C; kx++) breg[kx] = bt[kx * C + x];
-  }
-  {
-    const float* bn = P.basis_n + BasisOffset(R);  // [y * R + ky]
-    for (int i = threadIdx.x; i < R * R; i += kIdctColsThreads) l_bn[i] = bn[i];
-  }
-  const uint32_t ord = c_strategy_order[strategy];
-  for (int ci = 0; ci < 3; ci++) {
-    const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
-    float* l = c == 1 ? l_y : l_xb;
-    if (active) {
-      if (c == 1) {
-        for (int i = x * 4; i < SIZE; i += C * 4) *reinterpret_cast<float4*>(l + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-      } else {
-        const float cc = c == 0 ? x_cc : b_cc;
-        for (int i = x * 4; i < SIZE; i += C * 4) {
-          const float4 y4 = *reinterpret_cast<const float4*>(l_y + i);
-          *reinterpret_cast<float4*>(l + i) = make_float4(cc * y4.x, cc * y4.y, cc * y4.z, cc * y4.w);
-        }
-      }
-    }
-    __syncthreads();
-    if (active) {
-      const float mul = c == 1 ? sc : sc * (c == 0 ? P.x_dm : P.b_dm);
-      const CoefT* gqc = gq + size_t(c) * 65536;
-      const float* mc = m + size_t(c) * msize;
-      if (P.scan_order) {
-        // entry k: coefficient, its position and its dequant weight are three independent coalesced loads
-        const uint16_t* order = P.orders + P.order_offset[ord * 3 + c];
-        const float* ms = P.dequant_scan + (mc - P.dequant);
-        const uint32_t ke = P.kend[bidx * 3 + c];
-        const uint32_t k1 = ke < uint32_t(SIZE) ? ke : uint32_t(SIZE);
-#pragma unroll 4
-        for (uint32_t k = CX * CY + x; k < k1; k += C) {
-          const int q = int(gqc[k]);
-          const uint32_t pos = order[k];
-          const float w = ms[k];
-          if (q) {
-            const uint32_t idx = R < C ? pos : (pos % R) * C + pos / R;  // natural layout keeps the short side as rows
-            l[idx] += QuantBias(c, q, P.biases) * (w * mul);
-          }
-        }
-      } else {
-        for (uint32_t k = x; k < uint32_t(SIZE); k += C) {
-          const int q = int(gqc[k]);
-          if (q) {
-            const uint32_t idx = R < C ? k : (k % R) * C + k / R;
-            l[idx] += QuantBias(c, q, P.biases) * (mc[k] * mul);
-          }
-        }
-      }
-      if (x < CX * CY) {  // lowest frequencies from the DC image
-        const float* dc = P.dc + size_t(c) * P.xb * P.yb + size_t(vb.by) * P.xb + vb.bx;
-        const int ky = x / CX, kx = x % CX;
-        l[ky * C + kx] = LlfFromDc<CX, CY>(P, dc, ky, kx);
-      }
-    }
-    __syncthreads();
-    if (active) {
-      float tmp[R];
-#pragma unroll
-      for (int ky = 0; ky < R; ky++) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k4 = 0; k4 < C; k4 += 4) {
-          const float4 v = *reinterpret_cast<const float4*>(l + ky * C + k4);
-          acc += v.x * breg[k4];
-          acc += v.y * breg[k4 + 1];
-          acc += v.z * breg[k4 + 2];
-          acc += v.w * breg[k4 + 3];
-        }
-        tmp[ky] = acc;
-      }
-      float* out = P.out + size_t(c) * P.xp * P.yp + size_t(vb.by) * 8 * P.xp + size_t(vb.bx) * 8 + x;
-#pragma unroll
-      for (int y = 0; y < R; y++) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k4 = 0; k4 < R; k4 += 4) {
-          const float4 v = *reinterpret_cast<const float4*>(l_bn + y * R + k4);
-          acc += tmp[k4] * v.x;
-          acc += tmp[k4 + 1] * v.y;
-          acc += tmp[k4 + 2] * v.z;
-          acc += tmp[k4 + 3] * v.w;
-        }
-        out[size_t(y) * P.xp] = acc;
-      }
-    }
-    __syncthreads();
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

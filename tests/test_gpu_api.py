@@ -508,12 +508,10 @@ def test_frame_progression_steps_by_passes(built, tmp_path, detail, passes):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env,kw", [({}, dict(ac_code_mode=3)), ({}, dict(ac_code_mode=1)), ({}, dict(ac_code_mode=2)),
-                                    (dict(JXLHIP_ENTROPY="0"), {}), (dict(JXLHIP_ENTROPY="1"), {})])
+@pytest.mark.parametrize("env,kw", [({}, dict(ac_code_mode=3)), ({}, dict(ac_code_mode=1)), ({}, dict(ac_code_mode=2))])
 def test_partial_passes_on_the_other_entropy_kernels(built, tmp_path, monkeypatch, env, kw):
-    """The same steps for prefix / LZ77 coded streams (the generic kernel, or the lane kernel's prefix form) and with the
-    section-per-workgroup rANS kernels (JXLHIP_ENTROPY = 0 / 1): they step over sections that have not arrived (size 0) and
-    leave such a group, or such a pass of it, out."""
+    """The same steps for prefix / LZ77 coded streams (the generic kernel, or the lane kernel's prefix form): the kernels
+    step over sections that have not arrived (size 0) and leave such a group, or such a pass of it, out."""
     import os
     import jxlo
     J = built
@@ -537,6 +535,12 @@ def test_partial_passes_on_the_other_entropy_kernels(built, tmp_path, monkeypatc
         d = np.abs(got.astype(int) - want.rgb8.astype(int))
         want.close()
         assert d.max() <= 1 and (d > 0).mean() < 2e-3, line
+
+
+@pytest.mark.gpu
+def test_partial_passes_on_the_fallback_entropy_kernel(built, tmp_path, monkeypatch):
+    """The same steps with the section-per-workgroup rANS kernel (JXLHIP_ENTROPY = 1)."""
+    test_partial_passes_on_the_other_entropy_kernels(built, tmp_path, monkeypatch, dict(JXLHIP_ENTROPY="1"), {})
 
 
 @pytest.mark.gpu
