@@ -116,9 +116,15 @@ size_t jxlamd_modframe_end(const JxlAmdModFrame* frame, uint32_t* duration_last_
 void jxlamd_modframe_placement(const JxlAmdModFrame* frame, JxlAmdFramePlacement* placement);
 size_t jxlamd_modframe_placement_sized(const JxlAmdModFrame* frame, void* placement, size_t out_size);
 void jxlamd_modframe_free(JxlAmdModFrame* frame);
-/* info[0..9]: xsize, ysize, colour channels, has alpha, bits per sample, streams, channel buffers, transform operations,
- * extra channels, compressed bytes of all sections. */
+/* info[0..15]: xsize, ysize, colour channels, has alpha, bits per sample, streams, channel buffers, transform operations,
+ * extra channels, compressed bytes of all sections; [10..12] largest symbol-table set (words), LZ77 anywhere, largest
+ * tree; [13] launch levels of the inverse transforms (the deepest chain of group-local operations + the frame's own
+ * transforms: one launch per level and kind, whatever the number of groups), [14] group-local operations, [15] the deepest
+ * group-local chain. */
 void jxlamd_modframe_info(const JxlAmdModFrame* frame, uint32_t* info);
+/* TOC section `index` (0 = DC global, then the DC groups, then the AC groups; a one-group frame has section 0 only): where
+ * it starts in the buffer given to the parser and its size. Returns 0, or 1 when there is no such section. */
+int jxlamd_modframe_section(const JxlAmdModFrame* frame, uint32_t index, uint64_t* offset, uint32_t* size);
 /* Hands the plan to a context (jxlhip_modular_upload); then jxlhip_modular_run + jxlhip_download_pixels. */
 int jxlamd_modframe_upload(const JxlAmdModFrame* frame, JxlHipContext* ctx);
 /* Channel buffer of extra channel `index` after the run (jxlhip_modular_download_buffer), or 0xFFFFFFFF. */

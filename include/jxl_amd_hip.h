@@ -434,12 +434,22 @@ typedef struct JxlHipModStream {
 typedef struct JxlHipModBuffer {  /* a channel buffer: w x h int32 samples (the device pool is laid out by the library) */
   uint32_t w, h;
 } JxlHipModBuffer;
-typedef struct JxlHipModOp {  /* one inverse-transform step, in execution order */
-  uint32_t kind;          /* 0 = RCT on a rectangle, 1 = palette lookup, 2 = horizontal unsqueeze, 3 = vertical unsqueeze */
+typedef struct JxlHipModOp {  /* one inverse-transform step */
+  uint32_t kind;          /* 0 = RCT, 1 = palette lookup, 2 = horizontal unsqueeze, 3 = vertical unsqueeze */
   uint32_t buf[6];        /* RCT: 3 channels; palette: palette, index, outputs (buf[2..]); unsqueeze: averages, residuals, output */
-  uint32_t x0, y0, w, h;  /* RCT rectangle (whole channels: 0, 0, w, h) */
-  uint32_t param, nb, bit_depth;  /* RCT type; palette channels, sample depth */
-  uint32_t after_stream;  /* run after stream index + 1 streams' launch... 0xFFFFFFFF = after all streams (global transforms) */
+  uint32_t ox[6], oy[6];  /* per buffer: where its rectangle starts (whole channels: 0, 0; the palette itself is always whole) */
+  uint32_t w, h;          /* RCT, palette: the rectangle of every channel; unsqueeze: the OUTPUT rectangle, the averages are
+                             (n + 1) / 2 and the residuals n / 2 samples along the step's direction, n = w or h */
+  uint32_t param, nb, bit_depth;  /* RCT type / palette width; palette channels, sample depth */
+  /* Schedule. local = 1: the operation undoes a transform of one group stream (group-sized rectangles, private
+   * buffers); all local operations of a set of frames run before any other, those of one `level` and kind in ONE launch,
+   * so operations that share a level must not touch overlapping samples. local = 0: the frame's own transforms, one
+   * level per list entry, after the deepest local level.
+   * jxlhip_modular_upload checks that every rectangle lies inside its buffer and that an unsqueeze output is not one of its
+   * inputs, so no operation reads or writes outside the pool. It does NOT check the schedule: that operations sharing a
+   * level are disjoint, or that palette outputs 1.. do not alias the index rectangle. A description that breaks this
+   * decodes to wrong samples (a race), not to an error. */
+  uint32_t level, local;
 } JxlHipModOp;
 typedef struct JxlHipModFrameDesc {
   uint32_t xsize, ysize;

@@ -139,8 +139,10 @@ class Frame:
 class ModFrame:
     """Host-parsed Modular (lossless) frame: headers, trees, histograms, stream descriptors; samples stay compressed."""
 
+    # launch_levels: levels of inverse-transform launches (the deepest chain of group-local operations + the frame's own
+    # transforms; one launch per level and kind whatever the number of groups); num_local_ops / local_levels: the group part
     INFO = ("xsize", "ysize", "num_color", "has_alpha", "bits", "num_streams", "num_buffers", "num_ops", "num_extra", "section_bytes",
-            "max_table_words", "lz77", "max_tree_nodes")
+            "max_table_words", "lz77", "max_tree_nodes", "launch_levels", "num_local_ops", "local_levels")
 
     def __init__(self, data, frame_pos=0, frame_index=0):
         L = lib()
@@ -158,6 +160,15 @@ class ModFrame:
         t = (ctypes.c_uint32 * 3)()
         self.end = int(L.jxlamd_modframe_end(self._h, t))
         self.duration, self.is_last, self.timecode = int(t[0]), bool(t[1]), int(t[2])
+
+    def section(self, index):
+        """(offset, size) of TOC section `index` in the data: 0 = DC global, then the DC groups, then the AC groups."""
+        L = lib()
+        L.jxlamd_modframe_section.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+        off, size = ctypes.c_uint64(), ctypes.c_uint32()
+        if L.jxlamd_modframe_section(self._h, index, ctypes.byref(off), ctypes.byref(size)):
+            raise IndexError("no section %d" % index)
+        return int(off.value), int(size.value)
 
     def close(self):
         if self._h:
@@ -833,10 +844,22 @@ def encode_rgba8(img, **kw):
 
 LOSSLESS_PREFIX, LOSSLESS_LZ77, LOSSLESS_WP, LOSSLESS_SQUEEZE, LOSSLESS_RCT, LOSSLESS_ALL_PREDICTORS, LOSSLESS_PREV_CHANNEL = 1, 2, 4, 8, 16, 32, 64
 MODULAR_XYB = 128  # the frame codes XYB integers (Y, X, B - Y): "lossy Modular", not lossless any more
+# transforms in the group headers, each group on its own rectangle (frames of more than one group): an RCT (seed 0: YCoCg,
+# else types and permutations by seed and group); palettes (all colour channels when the group has at most `palette_colors`
+# colours, else one per colour channel with at most that many values); default Squeeze; a palette with ONE explicit entry
+# whose other colours must all be implicit ones (the call fails otherwise)
+LOSSLESS_LOCAL_RCT, LOSSLESS_LOCAL_PALETTE, LOSSLESS_LOCAL_SQUEEZE, LOSSLESS_LOCAL_IMPLICIT = 256, 512, 1024, 2048
 
 
-def encode_lossless(img, flags=LOSSLESS_RCT, seed=0):
+def _lossless_flags(flags, palette_colors):
+    if not 0 <= palette_colors < 65536:
+        raise ValueError("palette_colors: 0 (= 256) .. 65535")
+    return (flags & 0xFFFF) | (palette_colors << 16)
+
+
+def encode_lossless(img, flags=LOSSLESS_RCT, seed=0, palette_colors=0):
     """HxWxC uint8 image (C = 1..4: grey, grey + alpha, RGB, RGBA) -> lossless Modular codestream. flags: LOSSLESS_*."""
+    flags = _lossless_flags(flags, palette_colors)
     E = _enc_lib()
     img = np.ascontiguousarray(img, np.uint8)
     if img.ndim == 2:
@@ -847,11 +870,12 @@ def encode_lossless(img, flags=LOSSLESS_RCT, seed=0):
     return _finish(E, r, out, n, "jxlenc_encode_lossless")
 
 
-def encode_lossless_samples(samples, bits, exp_bits=0, flags=0, seed=0):
+def encode_lossless_samples(samples, bits, exp_bits=0, flags=0, seed=0, palette_colors=0):
     """HxWxC int32 samples (C = 1..4) -> lossless Modular codestream of an image with `bits`-bit integer samples, or
     (exp_bits != 0) float samples of `bits` bits whose bit patterns the integers are (32 / 8: float32 viewed as int32,
     16 / 5: float16 viewed as uint16). An alpha channel (C = 2 or 4) stays 8-bit."""
     E = _enc_lib()
+    flags = _lossless_flags(flags, palette_colors)
     a = np.ascontiguousarray(samples, np.int32)
     if a.ndim == 2:
         a = a[..., None]

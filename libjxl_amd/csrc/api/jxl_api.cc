@@ -601,6 +601,17 @@ void jxlamd_modframe_info(const JxlAmdModFrame* f, uint32_t* info) {
   info[10] = words;
   info[11] = lz;
   info[12] = nodes;
+  // the schedule of the inverse transforms: launch levels (the deepest group chain + the frame's own transforms, one launch
+  // per level and kind whatever the number of groups), operations that belong to group streams, the deepest group chain
+  info[13] = P.local_levels + P.global_levels;
+  info[14] = P.num_local_ops;
+  info[15] = P.local_levels;
+}
+int jxlamd_modframe_section(const JxlAmdModFrame* f, uint32_t index, uint64_t* offset, uint32_t* size) {
+  if (!f || index >= f->plan.section_size.size()) return 1;
+  if (offset) *offset = f->plan.section_offset[index];
+  if (size) *size = f->plan.section_size[index];
+  return 0;
 }
 uint32_t jxlamd_modframe_extra_buffer(const JxlAmdModFrame* f, uint32_t index) {
   return f && index < f->plan.extra_buffer.size() ? f->plan.extra_buffer[index] : 0xFFFFFFFFu;
@@ -688,14 +699,15 @@ int jxlamd_modframe_upload(const JxlAmdModFrame* f, JxlHipContext* ctx) {
     memset(&o, 0, sizeof(o));
     o.kind = q.kind;
     memcpy(o.buf, q.buf, sizeof(o.buf));
-    o.x0 = q.x0;
-    o.y0 = q.y0;
+    memcpy(o.ox, q.ox, sizeof(o.ox));
+    memcpy(o.oy, q.oy, sizeof(o.oy));
     o.w = q.w;
     o.h = q.h;
     o.param = q.param;
     o.nb = q.nb;
     o.bit_depth = q.bit_depth;
-    o.after_stream = 0xFFFFFFFFu;
+    o.level = q.level;
+    o.local = q.local;
     ops.push_back(o);
   }
   d.ops = ops.data();

@@ -2409,6 +2409,17 @@ static void EncodeRandom(size_t img_xs, size_t img_ys, const Params& p, std::vec
 // bit 2 = weighted-predictor leaves and a split on its error property, bit 3 = Squeeze (default steps), bit 4 = RCT
 // (YCoCg) over the colour channels, bit 5 = every leaf uses a different predictor (all 14 occur), bit 6 = a split on a
 // previous-channel property (16: |value| of the channel before). Lossless: whatever decodes it must return the input.
+// Transforms in the GROUP headers (what the reference encoder writes per group at its default effort, enc_modular.cc:
+// 1424-1521), each group on its own rectangle, in the order palette(s), RCT, squeeze:
+//   bit 8  = an RCT over the first three equally sized channels of every group stream (seed 0: YCoCg; otherwise the type
+//            follows from the seed and the group, permutations included);
+//   bit 9  = palettes: a group whose colour channels hold at most N distinct colours (N = flags >> 16, 0 = 256) gets ONE
+//            palette over all of them; any other group gets a single-channel palette for every colour channel with at
+//            most N distinct values (so one frame mixes chain depths);
+//   bit 10 = Squeeze with default parameters (from the group image's own shapes);
+//   bit 11 = "implicit colours only": a three-channel palette with ONE explicit entry per group; every other colour must be
+//            one of the implicit ones (palette.h:25-140: the 4x4x4 cube, the 5x5x5 cube, the negative-index deltas), else the
+//            call fails -- it never adds a second explicit entry.
 struct LosslessOptions {
   uint32_t flags;
   uint32_t seed;
@@ -2437,6 +2448,130 @@ static void FwdSqueezeLine(const int32_t* in, ptrdiff_t si, size_t n, int32_t* a
     res[ptrdiff_t(i) * sr] = int32_t((A - B) - jxh::SqueezeTendency(before, a, next));
   }
   if (na > nr) avg[ptrdiff_t(na - 1) * sa] = in[ptrdiff_t(n - 1) * si];
+}
+
+struct LocalTransform {  // one entry of a group header's transform list
+  uint32_t id, begin_c, rct_type, num_c, nb_colors;
+};
+static void FwdSqueeze(std::vector<LChannel>* chp, const std::vector<jxh::SqueezeStep>& steps) {
+  std::vector<LChannel>& ch = *chp;
+  for (const jxh::SqueezeStep& q : steps) {
+    const size_t b = q.begin_c, e = b + q.num_c;
+    size_t at = q.in_place ? e : ch.size();
+    for (size_t c = b; c < e; c++, at++) {
+      const LChannel src = ch[c];
+      LChannel a, r;
+      a.hshift = r.hshift = src.hshift + (q.horizontal ? 1 : 0);
+      a.vshift = r.vshift = src.vshift + (q.horizontal ? 0 : 1);
+      if (q.horizontal) {
+        a.w = (src.w + 1) / 2;
+        a.h = src.h;
+        r.w = src.w - a.w;
+        r.h = src.h;
+      } else {
+        a.w = src.w;
+        a.h = (src.h + 1) / 2;
+        r.w = src.w;
+        r.h = src.h - a.h;
+      }
+      a.d.assign(a.w * a.h, 0);
+      r.d.assign(r.w * r.h, 0);
+      if (q.horizontal) {
+        std::vector<int32_t> dummy(1);
+        for (size_t y = 0; y < src.h; y++) FwdSqueezeLine(src.Row(y), 1, src.w, a.Row(y), 1, r.w ? r.Row(y) : dummy.data(), 1);
+      } else {
+        std::vector<int32_t> dummy(1);
+        for (size_t x = 0; x < src.w; x++)
+          FwdSqueezeLine(src.d.data() + x, ptrdiff_t(src.w), src.h, a.d.data() + x, ptrdiff_t(a.w), r.h ? r.d.data() + x : dummy.data(), ptrdiff_t(r.w));
+      }
+      ch[c] = a;
+      ch.insert(ch.begin() + at, r);
+    }
+  }
+}
+static void DefaultSqueezeOf(const std::vector<LChannel>& ch, size_t nb_meta, std::vector<jxh::SqueezeStep>* steps) {
+  std::vector<jxh::MChannel> shapes(ch.size());
+  for (size_t c = 0; c < ch.size(); c++) {
+    shapes[c].w = ch[c].w;
+    shapes[c].h = ch[c].h;
+    shapes[c].hshift = ch[c].hshift;
+    shapes[c].vshift = ch[c].vshift;
+  }
+  jxh::DefaultSqueeze(shapes, nb_meta, steps);
+}
+// Forward RCT of any of the 42 types on three channels (the inverse: rct.cc:97-147).
+static void FwdRct(LChannel* c3[3], uint32_t type) {
+  const uint32_t perm = type / 7, custom = type % 7, second = custom >> 1, third = custom & 1;
+  const uint32_t slot[3] = {perm % 3, (perm + 1 + perm / 3) % 3, (perm + 2 - perm / 3) % 3};  // where the inverse puts its outputs
+  const size_t n = c3[0]->d.size();
+  for (size_t i = 0; i < n; i++) {
+    const int32_t o0 = c3[slot[0]]->d[i], o1 = c3[slot[1]]->d[i], o2 = c3[slot[2]]->d[i];
+    int32_t x0, x1, x2;
+    if (custom == 6) {  // YCoCg: the inverse computes tmp = Y - (Cg >> 1), G = Cg + tmp, B = tmp - (Co >> 1), R = B + Co
+      const int32_t Co = o0 - o2, tmp = o2 + (Co >> 1), Cg = o1 - tmp;
+      x0 = tmp + (Cg >> 1);
+      x1 = Co;
+      x2 = Cg;
+    } else {
+      x0 = o0;
+      x2 = third ? o2 - o0 : o2;
+      x1 = second == 1 ? o1 - o0 : (second == 2 ? o1 - ((o0 + o2) >> 1) : o1);
+    }
+    c3[0]->d[i] = x0;
+    c3[1]->d[i] = x1;
+    c3[2]->d[i] = x2;
+  }
+}
+// Forward palette over channels [begin, begin + num) of `ch` with the given colours (sorted, distinct, each num values):
+// the index channel replaces the first, the others leave, the palette ([num][colours], shifts -1) goes to the front.
+static void FwdPalette(std::vector<LChannel>* chp, size_t begin, size_t num, const std::vector<std::vector<int32_t>>& colors) {
+  std::vector<LChannel>& ch = *chp;
+  const size_t n = ch[begin].d.size();
+  std::vector<int32_t> key(num);
+  for (size_t i = 0; i < n; i++) {
+    for (size_t c = 0; c < num; c++) key[c] = ch[begin + c].d[i];
+    ch[begin].d[i] = int32_t(std::lower_bound(colors.begin(), colors.end(), key) - colors.begin());
+  }
+  ch.erase(ch.begin() + begin + 1, ch.begin() + begin + num);
+  LChannel pal;
+  pal.w = colors.size();
+  pal.h = num;
+  pal.hshift = pal.vshift = -1;
+  pal.d.resize(pal.w * pal.h);
+  for (size_t c = 0; c < num; c++)
+    for (size_t k = 0; k < colors.size(); k++) pal.d[c * pal.w + k] = colors[k][c];
+  ch.insert(ch.begin(), pal);
+}
+// The colours a three-channel palette of pal.w explicit entries gives the indices behind and before them (palette.h:25-140),
+// in the order a writer should prefer them: 1...189 past the explicit entries, then -1...-143.
+struct ImplicitColor {
+  int index;
+  int32_t v[3];
+};
+// (noinline: inlined into a caller whose palette is a local of three entries, GCC 11 follows PaletteValue's explicit-entry
+// branch, which these indices never take, and warns about its subscript: -Warray-bounds, a false positive)
+static __attribute__((noinline)) void ImplicitColors(const jxh::MChannel& pal, int bits, std::vector<ImplicitColor>* out) {
+  const int first = int(pal.w);
+  for (int k = 0; k < 64 + 125 + 143; k++) {
+    ImplicitColor q;
+    q.index = k < 64 + 125 ? first + k : -(k - (64 + 125) + 1);
+    for (size_t c = 0; c < 3; c++) q.v[c] = jxh::PaletteValue(pal, q.index, c, bits);
+    out->push_back(q);
+  }
+}
+static std::vector<std::vector<int32_t>> DistinctColors(const std::vector<LChannel>& ch, size_t begin, size_t num, size_t limit) {
+  std::vector<std::vector<int32_t>> all;
+  const size_t n = ch[begin].d.size();
+  std::vector<int32_t> key(num);
+  // (sorted insertion into a short list: the caller gives up beyond `limit` colours)
+  for (size_t i = 0; i < n; i++) {
+    for (size_t c = 0; c < num; c++) key[c] = ch[begin + c].d[i];
+    auto it = std::lower_bound(all.begin(), all.end(), key);
+    if (it != all.end() && *it == key) continue;
+    if (all.size() == limit) return {};
+    all.insert(it, key);
+  }
+  return all;
 }
 
 // `px`: interleaved samples as the integers the stream codes: `bits`-bit unsigned values, or (exp_bits != 0) the bit patterns
@@ -2484,45 +2619,8 @@ static void EncodeLossless(const int32_t* px, size_t xs, size_t ys, size_t nc, c
   const bool squeeze = (flags & 8) != 0;
   std::vector<jxh::SqueezeStep> steps;
   if (squeeze) {
-    std::vector<jxh::MChannel> shapes(nc);
-    for (size_t c = 0; c < nc; c++) {
-      shapes[c].w = xs;
-      shapes[c].h = ys;
-    }
-    jxh::DefaultSqueeze(shapes, 0, &steps);
-    for (const jxh::SqueezeStep& q : steps) {
-      const size_t b = q.begin_c, e = b + q.num_c;
-      size_t at = q.in_place ? e : ch.size();
-      for (size_t c = b; c < e; c++, at++) {
-        const LChannel src = ch[c];
-        LChannel a, r;
-        a.hshift = r.hshift = src.hshift + (q.horizontal ? 1 : 0);
-        a.vshift = r.vshift = src.vshift + (q.horizontal ? 0 : 1);
-        if (q.horizontal) {
-          a.w = (src.w + 1) / 2;
-          a.h = src.h;
-          r.w = src.w - a.w;
-          r.h = src.h;
-        } else {
-          a.w = src.w;
-          a.h = (src.h + 1) / 2;
-          r.w = src.w;
-          r.h = src.h - a.h;
-        }
-        a.d.assign(a.w * a.h, 0);
-        r.d.assign(r.w * r.h, 0);
-        if (q.horizontal) {
-          std::vector<int32_t> dummy(1);
-          for (size_t y = 0; y < src.h; y++) FwdSqueezeLine(src.Row(y), 1, src.w, a.Row(y), 1, r.w ? r.Row(y) : dummy.data(), 1);
-        } else {
-          std::vector<int32_t> dummy(1);
-          for (size_t x = 0; x < src.w; x++)
-            FwdSqueezeLine(src.d.data() + x, ptrdiff_t(src.w), src.h, a.d.data() + x, ptrdiff_t(a.w), r.h ? r.d.data() + x : dummy.data(), ptrdiff_t(r.w));
-        }
-        ch[c] = a;
-        ch.insert(ch.begin() + at, r);
-      }
-    }
+    DefaultSqueezeOf(ch, 0, &steps);
+    FwdSqueeze(&ch, steps);
   }
   // ---- the global tree: split on the channel index, optionally on the WP error / gradient property / previous channel
   struct Leaf {
@@ -2685,7 +2783,95 @@ static void EncodeLossless(const int32_t* px, size_t xs, size_t ys, size_t nc, c
     }
     tokenise(part, org, sz, 0, 0, &global_tokens);
   }
-  auto group_tokens = [&](size_t x0, size_t y0, size_t span, int min_shift, int max_shift, int stream_id, std::vector<Token>* toks) {
+  // A group's own transforms (flags bits 8-11), forward on a copy of the group image; `tr` receives the header's list.
+  const uint32_t local_flags = flags & 0xF00u;
+  const size_t palette_limit = (flags >> 16) ? (flags >> 16) : 256;
+  const size_t ncolor = gray ? 1 : 3;
+  std::vector<ImplicitColor> implicit;
+  if (local_flags & 0x800) {
+    const jxh::MChannel one_entry(1, 3, -1, -1);
+    ImplicitColors(one_entry, int(bits), &implicit);
+  }
+  auto local_transforms = [&](std::vector<LChannel>* gp, size_t group, std::vector<LocalTransform>* tr) {
+    std::vector<LChannel>& g = *gp;
+    size_t nb_meta = 0;
+    auto same_shape = [&](size_t b, size_t n) {
+      if (b + n > g.size()) return false;
+      for (size_t c = b + 1; c < b + n; c++)
+        if (g[c].w != g[b].w || g[c].h != g[b].h || g[c].hshift != g[b].hshift || g[c].vshift != g[b].vshift) return false;
+      return true;
+    };
+    if ((local_flags & 0x800) && ncolor == 3 && same_shape(0, 3)) {
+      // one explicit entry: the colour that is not implicit (else the first sample's); everything else by its implicit index
+      auto implicit_index = [&](const int32_t* v, int* index) {
+        for (const ImplicitColor& q : implicit)
+          if (q.v[0] == v[0] && q.v[1] == v[1] && q.v[2] == v[2]) {
+            *index = q.index;
+            return true;
+          }
+        return false;
+      };
+      const size_t n = g[0].d.size();
+      int32_t entry[3] = {g[0].d[0], g[1].d[0], g[2].d[0]};
+      bool have_entry = false;
+      std::vector<int32_t> idx(n);
+      for (size_t i = 0; i < n; i++) {
+        const int32_t v[3] = {g[0].d[i], g[1].d[i], g[2].d[i]};
+        int k = 0;
+        if (implicit_index(v, &k)) {
+          idx[i] = k;
+          continue;
+        }
+        if (have_entry && (v[0] != entry[0] || v[1] != entry[1] || v[2] != entry[2]))
+          throw std::runtime_error("implicit-only palette: a second colour that is not implicit");
+        have_entry = true;
+        memcpy(entry, v, sizeof(entry));
+        idx[i] = 0;
+      }
+      g[0].d = idx;
+      g.erase(g.begin() + 1, g.begin() + 3);
+      LChannel pc;
+      pc.w = 1;
+      pc.h = 3;
+      pc.hshift = pc.vshift = -1;
+      pc.d.assign(entry, entry + 3);
+      g.insert(g.begin(), pc);
+      nb_meta = 1;
+      tr->push_back({1, 0, 0, 3, 1});
+    } else if ((local_flags & 0x200) && same_shape(0, ncolor)) {
+      const auto all = DistinctColors(g, 0, ncolor, palette_limit);
+      if (!all.empty()) {
+        FwdPalette(&g, 0, ncolor, all);
+        nb_meta = 1;
+        tr->push_back({1, 0, 0, uint32_t(ncolor), uint32_t(all.size())});
+      } else if (ncolor == 3) {
+        for (size_t c = 0; c < 3; c++) {  // (every palette puts its meta channel in front: channel c has moved by nb_meta)
+          const auto one = DistinctColors(g, nb_meta + c, 1, palette_limit);
+          if (one.empty()) continue;
+          tr->push_back({1, uint32_t(nb_meta + c), 0, 1, uint32_t(one.size())});
+          FwdPalette(&g, nb_meta + c, 1, one);
+          nb_meta++;
+        }
+      }
+    }
+    if ((local_flags & 0x100) && !gray && same_shape(nb_meta, 3)) {
+      static const uint32_t kTypes[6] = {6, 13, 10, 33, 41, 2};  // YCoCg; YCoCg on a permutation; subtract-green forms with permutations
+      const uint32_t type = o.seed == 0 ? 6u : ((o.seed + group) % 7 == 0 ? uint32_t((o.seed * 5 + group * 11) % 42) : kTypes[(o.seed + group) % 6]);
+      if (type != 0) {
+        LChannel* c3[3] = {&g[nb_meta], &g[nb_meta + 1], &g[nb_meta + 2]};
+        FwdRct(c3, type);
+        tr->push_back({0, uint32_t(nb_meta), type, 0, 0});
+      }
+    }
+    if (local_flags & 0x400) {
+      std::vector<jxh::SqueezeStep> local_steps;
+      DefaultSqueezeOf(g, nb_meta, &local_steps);
+      FwdSqueeze(&g, local_steps);
+      tr->push_back({2, 0, 0, 0, 0});
+    }
+  };
+  auto group_tokens = [&](size_t x0, size_t y0, size_t span, int min_shift, int max_shift, int stream_id, std::vector<Token>* toks, size_t group,
+                          std::vector<LocalTransform>* tr) {
     std::vector<const LChannel*> part;
     std::vector<std::pair<size_t, size_t>> org, sz;
     for (size_t c = first_big; c < ch.size(); c++) {
@@ -2701,19 +2887,58 @@ static void EncodeLossless(const int32_t* px, size_t xs, size_t ys, size_t nc, c
       sz.push_back({rw, rh});
     }
     if (part.empty()) return false;
+    if (!local_flags) {
+      tokenise(part, org, sz, stream_id, 0, toks);
+      return true;
+    }
+    std::vector<LChannel> g(part.size());  // the group image on its own
+    for (size_t c = 0; c < part.size(); c++) {
+      g[c].w = sz[c].first;
+      g[c].h = sz[c].second;
+      g[c].hshift = part[c]->hshift;
+      g[c].vshift = part[c]->vshift;
+      g[c].d.resize(g[c].w * g[c].h);
+      for (size_t y = 0; y < g[c].h; y++) memcpy(g[c].Row(y), part[c]->Row(org[c].second + y) + org[c].first, g[c].w * sizeof(int32_t));
+    }
+    local_transforms(&g, group, tr);
+    part.clear();
+    org.clear();
+    sz.clear();
+    for (const LChannel& c : g) {
+      part.push_back(&c);
+      org.push_back({0, 0});
+      sz.push_back({c.w, c.h});
+    }
     tokenise(part, org, sz, stream_id, 0, toks);
     return true;
   };
   const bool multi = num_groups > 1;
   std::vector<std::vector<Token>> dc_tokens(multi ? ndc : 0), ac_tokens(multi ? num_groups : 0);
   std::vector<uint8_t> dc_present(dc_tokens.size(), 0), ac_present(ac_tokens.size(), 0);
+  std::vector<std::vector<LocalTransform>> dc_tr(dc_tokens.size()), ac_tr(ac_tokens.size());
   if (multi) {
+    bool failed = false;  // (nothing may leave a parallel region by exception)
 #pragma omp parallel for schedule(dynamic)
-    for (size_t g = 0; g < ndc; g++)
-      dc_present[g] = group_tokens((g % xdg) * gdim * 8, (g / xdg) * gdim * 8, gdim * 8, 3, 1000, int(1 + ndc + g), &dc_tokens[g]);
+    for (size_t g = 0; g < ndc; g++) {
+      try {
+        dc_present[g] = group_tokens((g % xdg) * gdim * 8, (g / xdg) * gdim * 8, gdim * 8, 3, 1000, int(1 + ndc + g), &dc_tokens[g], g, &dc_tr[g]);
+      } catch (...) {
+#pragma omp critical
+        failed = true;
+      }
+    }
 #pragma omp parallel for schedule(dynamic)
-    for (size_t g = 0; g < num_groups; g++)
-      ac_present[g] = group_tokens((g % xg) * gdim, (g / xg) * gdim, gdim, 0, 2, int(1 + 3 * ndc + 17 + g), &ac_tokens[g]);
+    for (size_t g = 0; g < num_groups; g++) {
+      try {
+        ac_present[g] = group_tokens((g % xg) * gdim, (g / xg) * gdim, gdim, 0, 2, int(1 + 3 * ndc + 17 + g), &ac_tokens[g], g, &ac_tr[g]);
+      } catch (...) {
+#pragma omp critical
+        failed = true;
+      }
+    }
+    if (failed) throw std::runtime_error("lossless: a group could not be coded with the transforms asked for");
+  } else if (local_flags) {
+    throw std::runtime_error("lossless: a single-group frame has no group streams to carry local transforms");
   }
   // ---- codes
   jxh::HybridCfg cfg420;
@@ -2732,11 +2957,42 @@ static void EncodeLossless(const int32_t* px, size_t xs, size_t ys, size_t nc, c
   std::vector<const std::vector<Token>*> all(streams.begin(), streams.end());
   BuildCode(all, size_t(num_leaves) + ((mode & 2) ? 1 : 0), 32, cfg420, &code, mode);
   // ---- sections
-  auto write_stream_header = [&](BitWriter& bw, bool global) {
+  auto write_begin_c = [&](BitWriter& bw, uint32_t v) {  // U32(Bits(3), BitsOffset(6, 8), ...)
+    bw.Write(2, v < 8 ? 0 : 1);
+    if (v < 8) bw.Write(3, v);
+    else bw.Write(6, v - 8);
+  };
+  auto write_stream_header = [&](BitWriter& bw, bool global, const std::vector<LocalTransform>* tr = nullptr) {
     bw.Write(1, 1);  // use the global tree
     bw.Write(1, 1);  // default weighted-predictor header
     if (!global) {
-      bw.Write(2, 0);  // no transforms
+      const uint32_t n = tr ? uint32_t(tr->size()) : 0;  // U32(Val(0), Val(1), BitsOffset(4, 2), ...)
+      bw.Write(2, n < 2 ? n : 2);
+      if (n >= 2) bw.Write(4, n - 2);
+      for (uint32_t i = 0; i < n; i++) {
+        const LocalTransform& t = (*tr)[i];
+        bw.Write(2, t.id);
+        if (t.id == 0) {
+          write_begin_c(bw, t.begin_c);
+          const uint32_t y = t.rct_type;  // U32(Val(6), Bits(2), BitsOffset(4, 2), BitsOffset(6, 10))
+          if (y == 6) bw.Write(2, 0);
+          else if (y < 4) bw.Write(2, 1), bw.Write(2, y);
+          else if (y < 18) bw.Write(2, 2), bw.Write(4, y - 2);
+          else bw.Write(2, 3), bw.Write(6, y - 10);
+        } else if (t.id == 1) {
+          write_begin_c(bw, t.begin_c);
+          bw.Write(2, t.num_c == 1 ? 0 : 1);  // U32(Val(1), Val(3), Val(4), ...): one channel or three
+          const uint32_t k = t.nb_colors;     // U32(BitsOffset(8, 0), BitsOffset(10, 256), BitsOffset(12, 1280), BitsOffset(16, 5376))
+          if (k < 256) bw.Write(2, 0), bw.Write(8, k);
+          else if (k < 1280) bw.Write(2, 1), bw.Write(10, k - 256);
+          else if (k < 5376) bw.Write(2, 2), bw.Write(12, k - 1280);
+          else bw.Write(2, 3), bw.Write(16, k - 5376);
+          bw.Write(2, 0);  // no delta entries
+          bw.Write(4, 0);  // predictor 0
+        } else {
+          bw.Write(2, 0);  // Squeeze with default parameters
+        }
+      }
       return;
     }
     const uint32_t nt = (rct ? 1 : 0) + (squeeze ? 1 : 0);
@@ -2781,7 +3037,7 @@ static void EncodeLossless(const int32_t* px, size_t xs, size_t ys, size_t nc, c
     for (size_t g = 0; g < ndc; g++) {
       BitWriter bw;
       if (dc_present[g]) {
-        write_stream_header(bw, false);
+        write_stream_header(bw, false, &dc_tr[g]);
         WriteTokens(bw, dc_tokens[g].data(), dc_tokens[g].size(), code);
       }
       bw.ZeroPad();
@@ -2791,7 +3047,7 @@ static void EncodeLossless(const int32_t* px, size_t xs, size_t ys, size_t nc, c
     for (size_t g = 0; g < num_groups; g++) {
       BitWriter bw;
       if (ac_present[g]) {
-        write_stream_header(bw, false);
+        write_stream_header(bw, false, &ac_tr[g]);
         WriteTokens(bw, ac_tokens[g].data(), ac_tokens[g].size(), code);
       }
       bw.ZeroPad();

@@ -143,7 +143,7 @@ struct PassBufs {
 
 // One launch of the Modular transform / output kernels over the frames of a set (ModularBuildOps).
 struct ModLaunch {
-  uint32_t kind;  // 0 RCT, 1 palette, 2 unsqueeze, 3 output
+  uint32_t kind;  // 0 RCT, 1 palette, 2 unsqueeze, 3 output, 4 / 5 / 6 float planes, splines, patches
   size_t offset;  // of the first parameter block in the blob
   uint32_t count, gx, gy;
 };
@@ -2489,23 +2489,28 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
   M.ops.assign(d->ops, d->ops + d->num_ops);
   for (const JxlHipModOp& op : M.ops) {
     const uint32_t nbuf = op.kind == 0 ? 3 : (op.kind == 1 ? 2 + op.nb : 3);
-    if (op.kind > 3 || nbuf > 6) return JXLHIP_ERR_INVALID_ARGUMENT;
+    if (op.kind > 3 || nbuf > 6 || op.local > 1 || op.level >= d->num_ops) return JXLHIP_ERR_INVALID_ARGUMENT;
     for (uint32_t j = 0; j < nbuf; j++)
       if (op.buf[j] >= d->num_buffers) return JXLHIP_ERR_INVALID_ARGUMENT;
+    // the w x h rectangle of buffer j at that buffer's origin lies inside it
+    auto inside = [&](uint32_t j, uint32_t w, uint32_t h) {
+      return uint64_t(op.ox[j]) + w <= M.buf_w[op.buf[j]] && uint64_t(op.oy[j]) + h <= M.buf_h[op.buf[j]];
+    };
     if (op.kind == 0) {
-      for (int j = 0; j < 3; j++)
-        if (uint64_t(op.x0) + op.w > M.buf_w[op.buf[j]] || uint64_t(op.y0) + op.h > M.buf_h[op.buf[j]]) return JXLHIP_ERR_INVALID_ARGUMENT;
+      for (uint32_t j = 0; j < 3; j++)
+        if (!inside(j, op.w, op.h)) return JXLHIP_ERR_INVALID_ARGUMENT;
       if (op.param >= 42) return JXLHIP_ERR_INVALID_ARGUMENT;
-    } else if (op.kind == 1) {
-      if (op.nb < 1 || op.nb > 4 || M.buf_h[op.buf[0]] < op.nb || op.param != M.buf_w[op.buf[0]]) return JXLHIP_ERR_INVALID_ARGUMENT;
+    } else if (op.kind == 1) {  // the palette is a whole buffer; index and outputs are rectangles
+      if (op.nb < 1 || op.nb > 4 || M.buf_h[op.buf[0]] < op.nb || op.param != M.buf_w[op.buf[0]] || op.ox[0] || op.oy[0])
+        return JXLHIP_ERR_INVALID_ARGUMENT;
       for (uint32_t j = 1; j < 2 + op.nb; j++)
-        if (M.buf_w[op.buf[j]] != op.w || M.buf_h[op.buf[j]] != op.h) return JXLHIP_ERR_INVALID_ARGUMENT;
-    } else {
-      const uint32_t a = op.buf[0], q = op.buf[1], o = op.buf[2];
+        if (!inside(j, op.w, op.h)) return JXLHIP_ERR_INVALID_ARGUMENT;
+    } else {  // averages and residuals follow from the output's size: they add up by construction, each must lie in its buffer
       const bool hz = op.kind == 2;
-      const uint32_t na = hz ? M.buf_w[a] : M.buf_h[a], nr = hz ? M.buf_w[q] : M.buf_h[q], no = hz ? M.buf_w[o] : M.buf_h[o];
-      const uint32_t la = hz ? M.buf_h[a] : M.buf_w[a], lr = hz ? M.buf_h[q] : M.buf_w[q], lo = hz ? M.buf_h[o] : M.buf_w[o];
-      if (na + nr != no || (nr != na && nr + 1 != na) || la != lr || la != lo) return JXLHIP_ERR_INVALID_ARGUMENT;
+      const uint32_t n = hz ? op.w : op.h, na = n - n / 2, nr = n / 2;
+      if (!inside(0, hz ? na : op.w, hz ? op.h : na) || !inside(1, hz ? nr : op.w, hz ? op.h : nr) || !inside(2, op.w, op.h))
+        return JXLHIP_ERR_INVALID_ARGUMENT;
+      if (op.buf[2] == op.buf[0] || op.buf[2] == op.buf[1]) return JXLHIP_ERR_INVALID_ARGUMENT;  // (a line is read while it is written)
     }
   }
   for (uint32_t j = 0; j < d->num_color + (d->has_alpha ? 1 : 0); j++) {
@@ -2560,89 +2565,108 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
   return 0;
 }
 
-// The inverse transforms and the pixel writer of a set of frames, as launches over parameter-block arrays: launch k does
-// the k-th transform of every frame that has one (one launch per kind), so a frame's steps stay in order on the stream
-// and a step of all frames shares the device. Built once per set (cached with the stream list), blocks in `out` (host),
+// The inverse transforms and the pixel writer of a set of frames, as launches over parameter-block arrays. First the
+// local phase: the operations that undo the transforms of single group streams. They are group-sized, those of different
+// groups touch disjoint rectangles and private buffers, and inside a group `level` orders them; so ALL operations of one
+// level and kind, of every group of every frame, are one launch (a frame with an RCT in each of its 135 groups: one RCT
+// launch). Then the frames' own transforms on whole channels, level k of every frame that has one in one launch per kind.
+// The two never share a launch: its grid is sized for its largest block, and one 4K channel beside thousands of group
+// blocks would start mostly empty workgroups. Built once per set (cached with the stream list), blocks in `blob` (host),
 // launches in `launches`.
 static void ModularBuildOps(JxlHipContext* const* ctxs, size_t n, std::vector<uint8_t>* blob, std::vector<ModLaunch>* launches) {
   blob->clear();
   launches->clear();
-  size_t levels = 0;
-  for (size_t i = 0; i < n; i++) levels = std::max(levels, ctxs[i]->mod.ops.size());
   auto append = [&](const void* p, size_t bytes) {
     const size_t at = blob->size();
     blob->resize(at + bytes);
     memcpy(blob->data() + at, p, bytes);
   };
   auto align = [&]() { blob->resize((blob->size() + 15) & ~size_t(15)); };
-  for (size_t level = 0; level < levels; level++) {
-    for (uint32_t kind = 0; kind < 3; kind++) {
-      align();
-      ModLaunch L{kind, blob->size(), 0, 0, 0};
-      for (size_t i = 0; i < n; i++) {
-        const JxlHipContext::Modular& M = ctxs[i]->mod;
-        if (level >= M.ops.size()) continue;
-        const JxlHipModOp& op = M.ops[level];
-        int32_t* pool = M.pool.as<int32_t>();
-        if (kind == 0 && op.kind == 0) {
-          jxlhip::ModRct p;
-          memset(&p, 0, sizeof(p));
-          for (int j = 0; j < 3; j++) {
-            p.stride[j] = M.buf_w[op.buf[j]];
-            p.c[j] = pool + M.buf_off[op.buf[j]] + size_t(op.y0) * p.stride[j] + op.x0;
-          }
-          p.w = op.w;
-          p.h = op.h;
-          p.type = op.param;
-          if (!op.w || !op.h) continue;
-          append(&p, sizeof(p));
-          L.count++;
-          L.gx = std::max(L.gx, (op.w + 255) / 256);
-          L.gy = std::max(L.gy, op.h);
-        } else if (kind == 1 && op.kind == 1) {
-          jxlhip::ModPalette p;
-          memset(&p, 0, sizeof(p));
-          p.palette = pool + M.buf_off[op.buf[0]];
-          p.index = pool + M.buf_off[op.buf[1]];
-          for (uint32_t j = 0; j < op.nb; j++) p.out[j] = pool + M.buf_off[op.buf[2 + j]];
-          p.palette_w = op.param;
-          p.nb = op.nb;
-          p.w = op.w;
-          p.h = op.h;
-          p.bit_depth = op.bit_depth;
-          p.index_stride = op.w;
-          p.out_stride = op.w;
-          if (!op.w || !op.h) continue;
-          append(&p, sizeof(p));
-          L.count++;
-          L.gx = std::max(L.gx, (op.w + 255) / 256);
-          L.gy = std::max(L.gy, op.h);
-        } else if (kind == 2 && op.kind >= 2) {
-          const uint32_t a = op.buf[0], q = op.buf[1], o = op.buf[2];
-          const bool hz = op.kind == 2;
-          jxlhip::ModUnsqueeze p;
-          memset(&p, 0, sizeof(p));
-          p.avg = pool + M.buf_off[a];
-          p.res = pool + M.buf_off[q];
-          p.out = pool + M.buf_off[o];
-          p.lines = hz ? M.buf_h[a] : M.buf_w[a];
-          p.na = hz ? M.buf_w[a] : M.buf_h[a];
-          p.nr = hz ? M.buf_w[q] : M.buf_h[q];
-          p.avg_line = hz ? M.buf_w[a] : 1;
-          p.avg_step = hz ? 1 : M.buf_w[a];
-          p.res_line = hz ? M.buf_w[q] : 1;
-          p.res_step = hz ? 1 : M.buf_w[q];
-          p.out_line = hz ? M.buf_w[o] : 1;
-          p.out_step = hz ? 1 : M.buf_w[o];
-          if (!p.lines) continue;
-          append(&p, sizeof(p));
-          L.count++;
-          L.gx = std::max(L.gx, (p.lines + 63) / 64);
-          L.gy = 1;
-        }
-      }
-      if (L.count) launches->push_back(L);
+  struct Ref {
+    uint32_t phase, level, kind;  // kind: the ModLaunch kind
+    uint32_t ctx, op;
+  };
+  std::vector<Ref> refs;
+  for (size_t i = 0; i < n; i++) {
+    const JxlHipContext::Modular& M = ctxs[i]->mod;
+    for (size_t k = 0; k < M.ops.size(); k++) {
+      const JxlHipModOp& op = M.ops[k];
+      const uint32_t kind = op.kind >= 2 ? 2 : op.kind;
+      refs.push_back({op.local ? 0u : 1u, op.level, kind, uint32_t(i), uint32_t(k)});
     }
+  }
+  std::stable_sort(refs.begin(), refs.end(), [](const Ref& a, const Ref& b) {
+    return a.phase != b.phase ? a.phase < b.phase : (a.level != b.level ? a.level < b.level : a.kind < b.kind);
+  });
+  for (size_t first = 0; first < refs.size();) {
+    size_t end = first;
+    while (end < refs.size() && refs[end].phase == refs[first].phase && refs[end].level == refs[first].level && refs[end].kind == refs[first].kind) end++;
+    const uint32_t kind = refs[first].kind;
+    align();
+    ModLaunch L{kind, blob->size(), 0, 0, 0};
+    for (size_t q = first; q < end; q++) {
+      const JxlHipContext::Modular& M = ctxs[refs[q].ctx]->mod;
+      const JxlHipModOp& op = M.ops[refs[q].op];
+      int32_t* pool = M.pool.as<int32_t>();
+      auto at = [&](uint32_t j) { return pool + M.buf_off[op.buf[j]] + size_t(op.oy[j]) * M.buf_w[op.buf[j]] + op.ox[j]; };
+      if (!op.w || !op.h) continue;
+      if (kind == 0) {
+        jxlhip::ModRct p;
+        memset(&p, 0, sizeof(p));
+        for (uint32_t j = 0; j < 3; j++) {
+          p.stride[j] = M.buf_w[op.buf[j]];
+          p.c[j] = at(j);
+        }
+        p.w = op.w;
+        p.h = op.h;
+        p.type = op.param;
+        append(&p, sizeof(p));
+        L.gx = std::max(L.gx, (op.w + 255) / 256);
+        L.gy = std::max(L.gy, op.h);
+      } else if (kind == 1) {
+        jxlhip::ModPalette p;
+        memset(&p, 0, sizeof(p));
+        p.palette = pool + M.buf_off[op.buf[0]];
+        p.index = at(1);
+        p.index_stride = M.buf_w[op.buf[1]];
+        for (uint32_t j = 0; j < op.nb; j++) {
+          p.out[j] = at(2 + j);
+          p.out_stride[j] = M.buf_w[op.buf[2 + j]];
+        }
+        p.palette_w = op.param;
+        p.nb = op.nb;
+        p.w = op.w;
+        p.h = op.h;
+        p.bit_depth = op.bit_depth;
+        append(&p, sizeof(p));
+        L.gx = std::max(L.gx, (op.w + 255) / 256);
+        L.gy = std::max(L.gy, op.h);
+      } else {
+        const bool hz = op.kind == 2;
+        const uint32_t len = hz ? op.w : op.h;
+        jxlhip::ModUnsqueeze p;
+        memset(&p, 0, sizeof(p));
+        p.avg = at(0);
+        p.res = at(1);
+        p.out = at(2);
+        p.lines = hz ? op.h : op.w;
+        p.na = len - len / 2;
+        p.nr = len / 2;
+        const uint32_t wa = M.buf_w[op.buf[0]], wr = M.buf_w[op.buf[1]], wo = M.buf_w[op.buf[2]];
+        p.avg_line = hz ? wa : 1;
+        p.avg_step = hz ? 1 : wa;
+        p.res_line = hz ? wr : 1;
+        p.res_step = hz ? 1 : wr;
+        p.out_line = hz ? wo : 1;
+        p.out_step = hz ? 1 : wo;
+        append(&p, sizeof(p));
+        L.gx = std::max(L.gx, (p.lines + 63) / 64);
+        L.gy = 1;
+      }
+      L.count++;
+    }
+    if (L.count) launches->push_back(L);
+    first = end;
   }
   // frames with patches / splines: colour samples to float planes (kind 4), the patches (kind 6), then the splines (kind 5)
   // over them (dec_cache.cc:193-201), then the output reads them

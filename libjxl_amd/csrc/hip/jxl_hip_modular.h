@@ -636,14 +636,16 @@ __global__ __launch_bounds__(64) void k_modular_streams(const ModStream* streams
   *S.end_bit = uint32_t(consumed);
 }
 
-// ---- inverse transforms on whole channels (one launch per transform step)
+// ---- inverse transforms on channel rectangles: whole channels for the frame's own transforms, a group's rectangle of the
+// frame's buffers (or a private buffer) for the transforms of a group stream. The blocks carry pointers to the first
+// sample of each rectangle and the strides of the buffers they lie in.
 struct ModRct {
   int32_t* c[3];  // the three channels in stored order
   uint32_t stride[3];
   uint32_t w, h, type;
 };
-// Every transform kernel takes an array of parameter blocks, one per blockIdx.z: a launch does the same step of many
-// frames (their k-th inverse transform), grid x / y sized for the largest.
+// Every transform kernel takes an array of parameter blocks, one per blockIdx.z: a launch does one level of many groups
+// and frames (jxl_hip_api.hip, ModularBuildOps), grid x / y sized for the largest.
 __global__ __launch_bounds__(256) void k_modular_rct(const ModRct* ops) {  // rct.cc:97-147
   const ModRct& P = ops[blockIdx.z];
   const uint32_t x = blockIdx.x * 256 + threadIdx.x;
@@ -730,9 +732,9 @@ __global__ __launch_bounds__(64) void k_modular_unsqueeze(const ModUnsqueeze* op
 
 struct ModPalette {  // palette.cc:26-202, the form without delta entries and predictor (nb_deltas == 0, predictor 0)
   const int32_t* palette;  // [nb_channels][palette_w]
-  const int32_t* index;    // the index channel
-  int32_t* out[4];
-  uint32_t palette_w, nb, w, h, bit_depth, index_stride, out_stride;
+  const int32_t* index;    // the index channel's rectangle
+  int32_t* out[4];         // the output rectangles; out[0] may be the index rectangle itself
+  uint32_t palette_w, nb, w, h, bit_depth, index_stride, out_stride[4];
 };
 __constant__ int16_t c_palette_delta[72][3] = {
     {0, 0, 0},       {4, 4, 4},       {11, 0, 0},      {0, 0, -13},     {0, -12, 0},     {-10, -10, -10},
@@ -779,7 +781,7 @@ __global__ __launch_bounds__(256) void k_modular_palette(const ModPalette* ops) 
     if (P.nb == 1) index = index < 0 ? 0 : (index >= int(P.palette_w) ? int(P.palette_w) - 1 : index);
     int32_t v[4];
     for (uint32_t c = 0; c < P.nb; c++) v[c] = ModPaletteValue(P, index, c);
-    for (uint32_t c = 0; c < P.nb; c++) P.out[c][size_t(y) * P.out_stride + x] = v[c];  // (out[0] may alias the index channel)
+    for (uint32_t c = 0; c < P.nb; c++) P.out[c][size_t(y) * P.out_stride[c] + x] = v[c];  // (out[0] may alias the index channel)
   }
 }
 

@@ -32,7 +32,13 @@ struct ModPlanStream {
 struct ModPlanOp {
   uint32_t kind;  // 0 RCT, 1 palette, 2 horizontal unsqueeze, 3 vertical unsqueeze
   uint32_t buf[6];
-  uint32_t x0, y0, w, h, param, nb, bit_depth;
+  uint32_t ox[6], oy[6];  // where each buffer's rectangle starts (whole channels: 0, 0)
+  uint32_t w, h;          // RCT / palette: the rectangle; unsqueeze: the OUTPUT (averages (n + 1) / 2, residuals n / 2 along the step)
+  uint32_t param, nb, bit_depth;
+  // local = 1: undoes a transform of ONE group stream, on that group's rectangles and private buffers. level: local
+  // operations count from 0 inside their group by data dependence (one more than the deepest earlier operation of the
+  // group that touches one of the same buffers); the frame's own inverse transforms count from 0 in list order.
+  uint32_t level, local;
 };
 
 struct ModFramePlan {
@@ -47,6 +53,7 @@ struct ModFramePlan {
   std::vector<ModPlanRect> rects;
   std::vector<ModPlanStream> streams;
   std::vector<ModPlanOp> ops;            // local (per group) operations first, then the frame's inverse transforms
+  uint32_t num_local_ops = 0, local_levels = 0, global_levels = 0;  // launch levels: local_levels + global_levels
   uint32_t out_buffer[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
   uint32_t num_color = 3, has_alpha = 0, alpha_bits = 8;
   std::vector<uint32_t> extra_buffer;    // per extra channel: the buffer that holds it after the inverse transforms
@@ -140,7 +147,7 @@ class ModFrameParser {
     {
       // stream 0: the channels no larger than a group (and every meta channel); the transforms stay pending
       std::vector<size_t> members;
-      ParseStreamHeader(g, &P, have_global, &full, &nb_meta, &transforms, /*local=*/false);
+      ParseStreamHeader(g, &P, have_global, &full, &nb_meta, &transforms, nullptr);
       for (size_t i = 0; i < full.size(); i++) {
         if (i >= nb_meta && (full[i].w > d.group_dim || full[i].h > d.group_dim)) break;
         members.push_back(i);
@@ -154,7 +161,6 @@ class ModFrameParser {
     while (first_big < full.size() && full[first_big].w <= d.group_dim && full[first_big].h <= d.group_dim) first_big++;
     auto group_stream = [&](size_t section, size_t x0, size_t y0, size_t span, int min_shift, int max_shift, uint32_t stream_id) {
       std::vector<VCh> part;
-      std::vector<ModPlanRect> rects;
       for (size_t c = first_big; c < full.size(); c++) {
         const VCh& fc = full[c];
         const int shift = std::min(fc.hshift, fc.vshift);
@@ -164,36 +170,54 @@ class ModFrameParser {
         const size_t rw = std::min(span >> fc.hshift, fc.w - rx), rh = std::min(span >> fc.vshift, fc.h - ry);
         if (!rw || !rh) continue;
         VCh v = fc;
+        v.x0 = rx;
+        v.y0 = ry;
         v.w = rw;
         v.h = rh;
         part.push_back(v);
-        rects.push_back({fc.buffer, uint32_t(rx), uint32_t(ry), uint32_t(rw), uint32_t(rh), Sig(v)});
       }
       if (part.empty()) return;
+      const std::vector<VCh> whole = part;  // the group image before its own transforms: rectangles of the frame's buffers
       BitReader r(data_ + P.section_offset[section], P.section_size[section]);
       size_t part_meta = 0;
       std::vector<MTransform> local;
-      ParseStreamHeader(r, &P, have_global, &part, &part_meta, &local, /*local=*/true);
+      std::vector<VCh> replaced;  // what the local transforms took out of the list, for the way back
+      ParseStreamHeader(r, &P, have_global, &part, &part_meta, &local, &replaced);
+      // the stream decodes the list the local transforms left: a channel they did not reshape is still a rectangle of the
+      // frame's buffer, one they made (palette, squeeze averages / residuals) is a whole buffer of its own
+      std::vector<ModPlanRect> rects;
+      for (const VCh& v : part) rects.push_back({v.buffer, uint32_t(v.x0), uint32_t(v.y0), uint32_t(v.w), uint32_t(v.h), Sig(v)});
       FinishStream(r, &P, uint32_t(section), stream_id, rects, have_global, 0);
-      for (size_t i = local.size(); i-- > 0;) {  // local transforms: only RCT (no channel-list change), on the group's rectangles
-        const MTransform& t = local[i];
-        JXH_CHECK(t.id == 0, "unsupported on the GPU path: group-local palette / squeeze");
-        JXH_CHECK(t.begin_c + 2 < rects.size(), "RCT: channel range");
-        const ModPlanRect &a = rects[t.begin_c], &b = rects[t.begin_c + 1], &c = rects[t.begin_c + 2];
-        JXH_CHECK(a.w == b.w && a.w == c.w && a.h == b.h && a.h == c.h && a.x0 == b.x0 && a.x0 == c.x0 && a.y0 == b.y0 && a.y0 == c.y0,
-                  "RCT: channel rectangles differ");
-        ModPlanOp op{};
-        op.kind = 0;
-        op.buf[0] = a.buffer;
-        op.buf[1] = b.buffer;
-        op.buf[2] = c.buffer;
-        op.x0 = a.x0;
-        op.y0 = a.y0;
-        op.w = a.w;
-        op.h = a.h;
-        op.param = t.rct_type;
-        P.ops.push_back(op);
+      // undone in reverse (encoding.cc:700-724 with undo_transforms), every last output into the group's rectangles
+      const size_t first_op = P.ops.size();
+      for (size_t i = local.size(); i-- > 0;) InverseOps(&P, local[i], &part, &part_meta, &replaced);
+      JXH_CHECK(part.size() == whole.size() && part_meta == 0 && replaced.empty(), "group stream: channel count after the inverse transforms");
+      for (size_t c = 0; c < part.size(); c++)
+        JXH_CHECK(part[c].buffer == whole[c].buffer && part[c].x0 == whole[c].x0 && part[c].y0 == whole[c].y0 && part[c].w == whole[c].w &&
+                      part[c].h == whole[c].h,
+                  "group stream: channel shapes after the inverse transforms");
+      std::vector<std::pair<uint32_t, uint32_t>> last;  // (buffer, level of the last operation of this group that touched it)
+      for (size_t k = first_op; k < P.ops.size(); k++) {
+        ModPlanOp& op = P.ops[k];
+        const uint32_t nbuf = op.kind == 1 ? 2 + op.nb : 3;
+        uint32_t level = 0;
+        for (uint32_t j = 0; j < nbuf; j++)
+          for (const auto& q : last)
+            if (q.first == op.buf[j]) level = std::max(level, q.second + 1);
+        for (uint32_t j = 0; j < nbuf; j++) {
+          bool seen = false;
+          for (auto& q : last)
+            if (q.first == op.buf[j]) {
+              q.second = level;
+              seen = true;
+            }
+          if (!seen) last.push_back({op.buf[j], level});
+        }
+        op.level = level;
+        op.local = 1;
+        P.local_levels = std::max(P.local_levels, level + 1);
       }
+      P.num_local_ops += uint32_t(P.ops.size() - first_op);
     };
     if (entries == 1) {
       // one section: every channel fits stream 0 (a frame this small has no channel larger than a group)
@@ -210,7 +234,10 @@ class ModFrameParser {
       }
     }
     // ---- the frame's inverse transforms as device operations on whole channel buffers
-    for (size_t i = transforms.size(); i-- > 0;) InverseOps(&P, transforms[i], &full, &nb_meta);
+    const size_t first_global = P.ops.size();
+    for (size_t i = transforms.size(); i-- > 0;) InverseOps(&P, transforms[i], &full, &nb_meta, nullptr);
+    for (size_t k = first_global; k < P.ops.size(); k++) P.ops[k].level = uint32_t(k - first_global);
+    P.global_levels = uint32_t(P.ops.size() - first_global);
     JXH_CHECK(full.size() == P.num_color + ih.extra.size() && nb_meta == 0, "channel count after the inverse transforms");
     for (size_t c = 0; c < P.num_color; c++) {
       JXH_CHECK(full[c].w == d.xsize && full[c].h == d.ysize, "colour channel size");
@@ -233,19 +260,20 @@ class ModFrameParser {
     uint32_t buffer;
     size_t w, h;
     int hshift, vshift;
+    size_t x0 = 0, y0 = 0;  // a group's channel: where its rectangle starts in the frame's buffer
   };
   static uint32_t Sig(const VCh& v) { return uint32_t((v.hshift + 2) * 64 + (v.vshift + 2)); }
   static VCh NewChannel(ModFramePlan* P, size_t w, size_t h, int hs, int vs) {
     JXH_CHECK(w < (size_t(1) << 30) && h < (size_t(1) << 30), "channel too large");
     P->buffers.push_back({uint32_t(w), uint32_t(h)});
-    return VCh{uint32_t(P->buffers.size() - 1), w, h, hs, vs};
+    return VCh{uint32_t(P->buffers.size() - 1), w, h, hs, vs, 0, 0};
   }
 
   // GroupHeader (encoding.cc:554-600) + the shape effect of its transforms on the channel list + an optional local tree
   // and code. On return `br` stands at the first bit of the stream's sample data (unless the stream has no samples).
+  // `replaced` (group streams): receives the channels the transforms take out of the list, see MetaShape.
   void ParseStreamHeader(BitReader& br, ModFramePlan* P, bool have_global, std::vector<VCh>* ch, size_t* nb_meta, std::vector<MTransform>* transforms,
-                         bool local) {
-    (void)local;
+                         std::vector<VCh>* replaced) {
     use_global_ = br.ReadBool();
     wp_ = WpHeader();
     if (!br.ReadBool()) {
@@ -261,7 +289,7 @@ class ModFrameParser {
     const uint32_t nt = ReadU32(br, Val(0), Val(1), BitsOffset(4, 2), BitsOffset(8, 18));
     transforms->resize(nt);
     for (auto& t : *transforms) ReadTransform(br, &t);
-    for (auto& t : *transforms) MetaShape(P, &t, ch, nb_meta);
+    for (auto& t : *transforms) MetaShape(P, &t, ch, nb_meta, replaced);
     (void)have_global;
   }
 
@@ -317,8 +345,10 @@ class ModFrameParser {
   }
 
   // Effect of a transform on the channel list (MetaApply: transform.cc:102-131, palette.cc:26-60, squeeze.cc:456-517);
-  // every channel whose shape changes gets a fresh buffer of its coded size.
-  static void MetaShape(ModFramePlan* P, MTransform* t, std::vector<VCh>* ch, size_t* nb_meta) {
+  // every channel whose shape changes gets a fresh buffer of its coded size. `replaced` (group streams, else null) keeps the
+  // channels that leave the list, in order: the inverse puts its outputs back into exactly those, so that a group's
+  // samples end in the frame's buffers.
+  static void MetaShape(ModFramePlan* P, MTransform* t, std::vector<VCh>* ch, size_t* nb_meta, std::vector<VCh>* replaced) {
     auto check_equal = [&](size_t c1, size_t c2) {
       JXH_CHECK(c1 <= c2 && c2 < ch->size(), "transform: invalid channel range");
       JXH_CHECK(!(c1 < *nb_meta && c2 >= *nb_meta), "transform: range spans meta and non-meta channels");
@@ -337,6 +367,7 @@ class ModFrameParser {
         JXH_CHECK(e < *nb_meta, "palette: bad meta channel range");
         *nb_meta += 2 - t->num_c;
       }
+      if (replaced) replaced->insert(replaced->end(), ch->begin() + b + 1, ch->begin() + e + 1);
       ch->erase(ch->begin() + b + 1, ch->begin() + e + 1);
       ch->insert(ch->begin(), NewChannel(P, t->nb_colors + t->nb_deltas, t->num_c, -1, -1));
     } else {
@@ -364,6 +395,7 @@ class ModFrameParser {
           VCh src = (*ch)[c];
           JXH_CHECK(src.w && src.h, "squeeze of an empty channel");
           JXH_CHECK(src.hshift <= 30 && src.vshift <= 30, "squeeze: too many steps");
+          if (replaced) replaced->push_back(src);
           size_t rw = src.w, rh = src.h;
           if (q.horizontal) {
             src.w = (src.w + 1) / 2;
@@ -381,8 +413,15 @@ class ModFrameParser {
     }
   }
 
-  // Inverse of a transform as device operations (rct.cc:97-147, palette.cc:62-202, squeeze.cc:128-385).
-  static void InverseOps(ModFramePlan* P, const MTransform& t, std::vector<VCh>* ch, size_t* nb_meta) {
+  // Inverse of a transform as device operations (rct.cc:97-147, palette.cc:62-202, squeeze.cc:128-385). The frame's own
+  // transforms (`replaced` null) give every channel they bring back a fresh buffer; a group's put it into the channel the
+  // forward transform replaced (MetaShape kept them, last in first out).
+  static void SetBuf(ModPlanOp* op, int j, const VCh& v) {
+    op->buf[j] = v.buffer;
+    op->ox[j] = uint32_t(v.x0);
+    op->oy[j] = uint32_t(v.y0);
+  }
+  static void InverseOps(ModFramePlan* P, const MTransform& t, std::vector<VCh>* ch, size_t* nb_meta, std::vector<VCh>* replaced) {
     if (t.id == 0) {
       const size_t m = t.begin_c;
       JXH_CHECK(m + 2 < ch->size(), "RCT: channel range");
@@ -391,13 +430,13 @@ class ModFrameParser {
       if (t.rct_type == 0) return;
       ModPlanOp op{};
       op.kind = 0;
-      op.buf[0] = a.buffer;
-      op.buf[1] = b.buffer;
-      op.buf[2] = c.buffer;
+      SetBuf(&op, 0, a);
+      SetBuf(&op, 1, b);
+      SetBuf(&op, 2, c);
       op.w = uint32_t(a.w);
       op.h = uint32_t(a.h);
       op.param = t.rct_type;
-      P->ops.push_back(op);
+      if (!replaced || (a.w && a.h)) P->ops.push_back(op);
     } else if (t.id == 1) {
       JXH_CHECK(*nb_meta >= 1, "palette transform without palette");
       JXH_CHECK(t.nb_deltas == 0 && t.predictor == 0, "unsupported on the GPU path: palette with delta entries / predictor");
@@ -407,14 +446,17 @@ class ModFrameParser {
       const VCh idx = (*ch)[c0];
       ModPlanOp op{};
       op.kind = 1;
-      op.buf[0] = pal.buffer;
-      op.buf[1] = idx.buffer;
-      op.buf[2] = idx.buffer;  // the first output replaces the index channel
+      SetBuf(&op, 0, pal);
+      SetBuf(&op, 1, idx);
+      SetBuf(&op, 2, idx);  // the first output replaces the index channel
+      if (replaced) JXH_CHECK(replaced->size() >= nb - 1, "palette: channel bookkeeping");
       for (size_t i = 1; i < nb; i++) {
-        const VCh v = NewChannel(P, idx.w, idx.h, idx.hshift, idx.vshift);
+        const VCh v = replaced ? (*replaced)[replaced->size() - (nb - 1) + (i - 1)] : NewChannel(P, idx.w, idx.h, idx.hshift, idx.vshift);
+        JXH_CHECK(v.w == idx.w && v.h == idx.h, "palette: channel sizes differ");
         ch->insert(ch->begin() + c0 + i, v);
-        op.buf[2 + i] = v.buffer;
+        SetBuf(&op, int(2 + i), v);
       }
+      if (replaced) replaced->resize(replaced->size() - (nb - 1));
       op.w = uint32_t(idx.w);
       op.h = uint32_t(idx.h);
       op.nb = uint32_t(nb);
@@ -435,38 +477,33 @@ class ModFrameParser {
           JXH_CHECK(*nb_meta >= q.num_c, "squeeze: meta channel bookkeeping");
           *nb_meta -= q.num_c;
         }
+        if (replaced) JXH_CHECK(replaced->size() >= q.num_c, "squeeze: channel bookkeeping");
         for (size_t c = b; c < e; c++) {
           const VCh a = (*ch)[c], r = (*ch)[first_res + (c - b)];
-          if (q.horizontal) {
-            JXH_CHECK(a.w == (a.w + r.w + 1) / 2 && a.h == r.h, "squeeze: channel sizes do not match");
-            if (r.w == 0) {
-              (*ch)[c].hshift--;
-              continue;
-            }
-            const VCh out = NewChannel(P, a.w + r.w, a.h, a.hshift - 1, a.vshift);
-            ModPlanOp op{};
-            op.kind = 2;
-            op.buf[0] = a.buffer;
-            op.buf[1] = r.buffer;
-            op.buf[2] = out.buffer;
-            if (a.h) P->ops.push_back(op);
-            (*ch)[c] = out;
-          } else {
-            JXH_CHECK(a.h == (a.h + r.h + 1) / 2 && a.w == r.w, "squeeze: channel sizes do not match");
-            if (r.h == 0) {
-              (*ch)[c].vshift--;
-              continue;
-            }
-            const VCh out = NewChannel(P, a.w, a.h + r.h, a.hshift, a.vshift - 1);
-            ModPlanOp op{};
-            op.kind = 3;
-            op.buf[0] = a.buffer;
-            op.buf[1] = r.buffer;
-            op.buf[2] = out.buffer;
-            if (a.w) P->ops.push_back(op);
-            (*ch)[c] = out;
+          const bool hz = q.horizontal;
+          if (hz) JXH_CHECK(a.w == (a.w + r.w + 1) / 2 && a.h == r.h, "squeeze: channel sizes do not match");
+          else JXH_CHECK(a.h == (a.h + r.h + 1) / 2 && a.w == r.w, "squeeze: channel sizes do not match");
+          if (!replaced && (hz ? r.w : r.h) == 0) {  // nothing to interleave: the averages are the channel
+            if (hz) (*ch)[c].hshift--;
+            else (*ch)[c].vshift--;
+            continue;
           }
+          // (a group's channel goes back into the buffer it came from even then: the operation copies the lone average)
+          const size_t ow = hz ? a.w + r.w : a.w, oh = hz ? a.h : a.h + r.h;
+          const VCh out = replaced ? (*replaced)[replaced->size() - q.num_c + (c - b)]
+                                   : NewChannel(P, ow, oh, a.hshift - (hz ? 1 : 0), a.vshift - (hz ? 0 : 1));
+          JXH_CHECK(out.w == ow && out.h == oh, "squeeze: channel sizes do not match");
+          ModPlanOp op{};
+          op.kind = hz ? 2 : 3;
+          SetBuf(&op, 0, a);
+          SetBuf(&op, 1, r);
+          SetBuf(&op, 2, out);
+          op.w = uint32_t(ow);
+          op.h = uint32_t(oh);
+          if (hz ? a.h : a.w) P->ops.push_back(op);
+          (*ch)[c] = out;
         }
+        if (replaced) replaced->resize(replaced->size() - q.num_c);
         ch->erase(ch->begin() + first_res, ch->begin() + first_res + q.num_c);
       }
     }
