@@ -137,7 +137,8 @@ const char* jxlamd_last_error(void);
 int jxlamd_icc_decode(const uint8_t* coded, size_t size, uint8_t* out, size_t out_size, size_t* profile_size, size_t* coded_bits);
 /* Test entry: the output description of the XYB colour stage (lib/jxl/dec_xyb.cc:127-250, stage_tone_mapping.cc:30-76,
  * stage_from_linear.cc:146-168) for an image coded in `source` with intensity target `source_intensity`, rendered to the
- * RGB encoding `target` for `desired_intensity` (0 = the image's). inv_opsin: the image's OpsinInverseMatrix, row-major
+ * RGB encoding `target` (or, source and target both D65 grey, to grey: three equal luminance rows) for `desired_intensity`
+ * (0 = the image's). inv_opsin: the image's OpsinInverseMatrix, row-major
  * (NULL = the default one). out->tf is the target's transfer function; the decoder hands frames whose target is sRGB or
  * linear without tone mapping the matrix alone. Returns 0, or 1 (see jxlamd_last_error). */
 int jxlamd_color_output(const JxlColorEncoding* source, float source_intensity, const JxlColorEncoding* target, float desired_intensity,

@@ -255,7 +255,8 @@ int jxlhip_download_rgb8(JxlHipContext* ctx, uint8_t* dst, size_t stride);
  * call before jxlhip_frame_upload; default RGB8). data_type uses the JxlDataType values (0 = f32, 2 = u8, 3 = u16,
  * 5 = f16), num_channels 1..4 (2 and 4 carry alpha: jxlhip_set_alpha, else opaque), bits_per_sample the depth of the
  * unsigned types (0 = full width), big_endian swaps the bytes of multi-byte samples. RGB8 is written by every filter
- * kernel and RGB f32 by the row-streaming one (the d1.0 configuration); other formats cost one more pass over the planes. */
+ * kernel, RGB f32 and one 8-bit sRGB channel (channel 0: the pixel of a grey image) by the row-streaming one (the d1.0
+ * configuration); other formats cost one more pass over the planes. */
 int jxlhip_set_output_format(JxlHipContext* ctx, uint32_t data_type, uint32_t num_channels, uint32_t bits_per_sample, int big_endian);
 /* The pixels are written with the image's orientation undone (JxlOrientation / EXIF numbering 1..8; 1 = as coded), the
  * way the reference's write stage does it (render_pipeline/stage_write.cc:292-306,441-458,664-699): for 5..8 the rows
@@ -305,7 +306,9 @@ int jxlhip_get_section_end_bits(JxlHipContext* ctx, uint32_t* bits, size_t n);
 int jxlhip_download(JxlHipContext* ctx, const char* name, void* dst, size_t dst_size, size_t* needed);
 
 /* Options (set before jxlhip_frame_upload): "keep_filtered" = 1 makes jxlhip_run_filter_color also store the filtered
- * XYB planes for jxlhip_download("xyb_filtered") (test aid; costs one extra plane set and 12 B/pixel of writes).
+ * XYB planes for jxlhip_download("xyb_filtered") (test aid; costs one extra plane set and 12 B/pixel of writes). Switched
+ * on only after the upload of a frame that writes one 8-bit channel from the filter kernel (rows of 1 byte per pixel,
+ * which no other writer may fill), it makes the filter launch fail with JXLHIP_ERR_INVALID_ARGUMENT: upload again.
  * "filter_async" = 1 (on the FIRST context of a set; may be changed at any time): jxlhip_run_filter_color_batch launches
  * on that context's second stream, ordered after the work its first stream holds. The call sequence entropy_batch,
  * transform_batch, filter_color_batch, entropy_batch, ... on one frame set then overlaps every filter + colour launch
@@ -383,6 +386,11 @@ struct JxlHipColorTarget {
 /* Test entry: the generic writer's colour stage alone on n XYB triples (planar [3][n]) with `target` (its matrix; the
  * opsin biases of the frame the context last uploaded); interleaved f32 RGB out. */
 int jxlhip_debug_color_target(JxlHipContext* ctx, const float* xyb, size_t n, const JxlHipColorTarget* target, float* rgb);
+
+/* Test access: who writes the pixels of the VarDCT frame the context last uploaded. *route = 0: the generic writer behind
+ * the filter kernel (k_color_out / k_upsample_color), 1: the filter kernel itself (RGB8, RGB f32), 2: the one-channel
+ * 8-bit form of the row-streaming filter kernel (k_filter_rows2<true, EPF, GAB, true>). */
+int jxlhip_debug_pixel_route(JxlHipContext* ctx, uint32_t* route);
 
 /* Debug aid: with JXLHIP_GUARD=1 in the environment every device buffer of a context is allocated with a 4 KiB guard
  * band either side, filled with a pattern. Waits for the device, then *touched = 0 when every band is intact, else

@@ -214,6 +214,15 @@ class HipContext:
         _check(L.jxlhip_debug_color(self._h, xyb.ctypes.data, n, 1 if linear else 0, out.ctypes.data), "jxlhip_debug_color")
         return out
 
+    def pixel_route(self):
+        """Test access: 0 = the generic writer makes the pixels of the uploaded frame, 1 = the filter kernel, 2 = the filter
+        kernel's one-channel 8-bit form."""
+        L = lib()
+        L.jxlhip_debug_pixel_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        r = ctypes.c_uint32()
+        _check(L.jxlhip_debug_pixel_route(self._h, ctypes.byref(r)), "jxlhip_debug_pixel_route")
+        return int(r.value)
+
     def check_guards(self):
         """JXLHIP_GUARD=1 debug aid: 0 when no kernel wrote next to one of this context's device buffers."""
         t = ctypes.c_uint32()
@@ -532,11 +541,24 @@ def set_color_encoding(white_point=None, primaries=1, transfer_function=13, gamm
                                 intent, arr)
 
 
-def set_xyb_color_encoding(white_point=None, primaries=1, transfer_function=13, gamma=None, intent=1, xy=None, intensity_target=255.0):
+def set_xyb_gray(on=True):
+    """Test aid: the next streams of an XYB image (VarDCT, or encode_lossless with MODULAR_XYB) declare colour space Gray
+    (with set_xyb_color_encoding's / set_color_encoding's white point and transfer function, D65 sRGB without). The body is
+    the same three-channel XYB frame: a decoder renders its luminance."""
+    E = _enc_lib()
+    E.jxlenc_set_xyb_gray.argtypes = [ctypes.c_int]
+    E.jxlenc_set_xyb_gray.restype = None
+    E.jxlenc_set_xyb_gray(1 if on else 0)
+
+
+def set_xyb_color_encoding(white_point=None, primaries=1, transfer_function=13, gamma=None, intent=1, xy=None, intensity_target=255.0,
+                           gray=False):
     """Test aid: the next VarDCT (XYB) streams declare this enum colour encoding (values as set_color_encoding) and, when it
     is not 255, this intensity target (ToneMapping). The coded samples do not change: the tag only changes how a decoder
-    renders the same XYB body. white_point=None: untagged again (the streams are then byte-identical to before)."""
+    renders the same XYB body. gray: colour space Gray (no primaries) instead of RGB (set_xyb_gray). white_point=None:
+    untagged again (the streams are then byte-identical to before)."""
     E = _enc_lib()
+    set_xyb_gray(gray and white_point is not None)
     E.jxlenc_set_xyb_color_encoding.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 6 + [ctypes.POINTER(ctypes.c_int32), ctypes.c_float]
     E.jxlenc_set_xyb_color_encoding.restype = None
     if white_point is None:

@@ -414,7 +414,9 @@ int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t 
   d.epf_pass2_sigma_scale = lf.epf_pass2_sigma_scale;
   d.epf_border_sad_mul = lf.epf_border_sad_mul;
   const jxh::ColorOutput& co = f->color;
-  for (int i = 0; i < 9; i++) d.opsin_inv[i] = co.active ? co.matrix[i] : P.ih.inv_opsin[i] * (255.0f / P.ih.intensity_target);
+  float own_matrix[9];
+  jxh::OwnMatrix(P.ih, own_matrix);
+  for (int i = 0; i < 9; i++) d.opsin_inv[i] = co.active ? co.matrix[i] : own_matrix[i];
   // (frames of images that are not xyb_encoded: their own colour transform, frame_header.h:176-184, and no transfer function)
   const bool linear = co.active ? co.linear : P.ih.linear_tf;
   d.linear_output = P.ih.xyb_encoded ? (linear ? 1 : 0) : (P.fh.ycbcr ? 2 : 3);
@@ -737,7 +739,9 @@ int jxlamd_modframe_upload(const JxlAmdModFrame* f, JxlHipContext* ctx) {
     d.opsin_bias[c] = P.ih.opsin_bias[c];
   }
   const jxh::ColorOutput& co = f->color;
-  for (int i = 0; i < 9; i++) d.opsin_inv[i] = co.active ? co.matrix[i] : P.ih.inv_opsin[i] * (255.0f / P.ih.intensity_target);
+  float own_matrix[9];
+  jxh::OwnMatrix(P.ih, own_matrix);
+  for (int i = 0; i < 9; i++) d.opsin_inv[i] = co.active ? co.matrix[i] : own_matrix[i];
   d.linear_output = (co.active ? co.linear : P.ih.linear_tf) ? 1 : 0;
   d.color_target = P.xyb && co.active && co.target.tf ? &co.target : nullptr;
   const int r = jxlhip_modular_upload(ctx, &d);
@@ -1268,8 +1272,8 @@ bool WantsUnpremultiply(const JxlDecoder* d, const OutFormat& of) {
 }
 
 // An XYB image in an enum colour encoding: its colour stage renders to RenderedEncoding (jxh_color.h, dec_xyb.cc:127-250).
-// (ICC-tagged XYB images render to (linear) sRGB; grey XYB images are refused with the headers.)
-static bool XybEnumImage(const JxlDecoder* d) { return d->ih.xyb_encoded && !d->ih.want_icc && !d->ih.gray; }
+// (ICC-tagged XYB images render to (linear) sRGB, grey ones to (linear) sRGB grey.)
+static bool XybEnumImage(const JxlDecoder* d) { return d->ih.xyb_encoded && !d->ih.want_icc; }
 // What the pixels of such an image are in: the original encoding (decode.cc / dec_xyb.cc:160-165: every enum transfer
 // function is one the stage can output), sRGB or linear sRGB (want_linear), or the original with a linear transfer function.
 static void RenderedEncoding(const JxlDecoder* d, JxlColorEncoding* ce) {
@@ -1304,7 +1308,9 @@ static bool ToneMappedAfterBlending(const JxlDecoder* d, const jxh::FrameHeader&
 static JxlDecoderStatus PrepareColorOutput(JxlDecoder* d, const jxh::ImageHeader& ih, const jxh::FrameHeader& fh,
                                            jxh::ColorOutput* out) {
   *out = jxh::ColorOutput();
-  if (!XybEnumImage(d)) return JXL_DEC_SUCCESS;
+  // (an ICC-tagged grey XYB image takes the stage too, towards D65 grey with the sRGB or linear curve, for its luminance rows:
+  // the header's enum fields are the defaults then)
+  if (!XybEnumImage(d) && !(d->ih.xyb_encoded && d->ih.gray)) return JXL_DEC_SUCCESS;
   JxlColorEncoding src, dst;
   jxh::EncodingFromHeader(ih, &src);
   RenderedEncoding(d, &dst);
@@ -2230,7 +2236,7 @@ static JxlDecoderStatus CheckFormat(const JxlDecoder* d, const JxlPixelFormat* f
   if (!d->have_ih || !f) return JXL_DEC_ERROR;
   if (f->num_channels < 1 || f->num_channels > 4 || !KnownType(f->data_type)) return JXL_DEC_ERROR;
   if (f->num_channels < 3 && !d->ih.gray) return JXL_DEC_ERROR;  // decode.cc:2512-2520: grayscale output of a colour image
-  if (d->ih.gray && !d->mframe) return JXL_DEC_ERROR;            // (grey images: Modular frames only on this path)
+  if (d->ih.gray && !d->ih.xyb_encoded && !d->mframe) return JXL_DEC_ERROR;  // (grey images that are not XYB: Modular frames only)
   return JXL_DEC_SUCCESS;
 }
 JxlDecoderStatus JxlDecoderImageOutBufferSize(const JxlDecoder* d, const JxlPixelFormat* f, size_t* size) {

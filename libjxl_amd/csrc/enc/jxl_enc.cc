@@ -932,6 +932,9 @@ static ColorState g_color;
 // renders the same body.
 static ColorState g_xyb_color;
 static float g_xyb_intensity = 255.0f;
+// jxlenc_set_xyb_gray: the next streams of an XYB image (VarDCT, or Modular with the XYB flag) declare colour space Gray.
+// The body stays the three-channel XYB frame it was: a decoder renders its luminance (dec_xyb.cc:228-232).
+static bool g_xyb_gray = false;
 static bool g_tone_mapping_fields = false;  // while a VarDCT header with a coded intensity target is written
 static void WriteEnum(BitWriter& bw, uint32_t v) {  // U32(Val(0), Val(1), BitsOffset(4, 2), BitsOffset(6, 18))
   static const uint32_t b[4] = {0, 0, 4, 6}, o[4] = {0, 1, 2, 18};
@@ -1678,7 +1681,7 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
   bw.Write(3, 0);  // no aspect-ratio shortcut
   WriteSizeDim(bw, g_image_w ? g_image_w : uint32_t(ups == 1 ? f.xs : f.img_xs));
   const bool with_icc = !g_embedded_icc.empty();
-  const bool xyb_tag = g_xyb_color.enabled && !with_icc && !p.color_transform;
+  const bool xyb_tag = (g_xyb_color.enabled || g_xyb_gray) && !with_icc && !p.color_transform;
   g_tone_mapping_fields = xyb_tag && g_xyb_intensity != 255.0f;
   if (!have_alpha && !with_icc && !xyb_tag && !ExtraFields() && !p.color_transform) {
     bw.Write(1, 1);  // ImageMetadata all_default (8-bit sRGB, XYB encoded)
@@ -1692,13 +1695,13 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
     if (have_alpha) WriteAlphaChannelInfo(bw);
     bw.Write(1, p.color_transform ? 0 : 1);  // xyb_encoded
     if (xyb_tag) {
-      WriteColorEncodingFields(bw, false, g_xyb_color);
+      WriteColorEncodingFields(bw, g_xyb_gray, g_xyb_color.enabled ? g_xyb_color : ColorState());
     } else if (!with_icc) {
       bw.Write(1, 1);  // ColorEncoding all_default (sRGB)
     } else {
       bw.Write(1, 0);  // ColorEncoding not all_default (color_encoding_internal.cc:144-158)
       bw.Write(1, 1);  //   want_icc
-      bw.Write(2, 0);  //   colour space RGB
+      bw.Write(2, g_xyb_gray && !p.color_transform ? 1 : 0);  //   colour space RGB, or Gray (jxlenc_set_xyb_gray)
     }
     WriteToneMapping(bw);
     bw.Write(2, 0);  // no extensions
@@ -3092,8 +3095,8 @@ static void EncodeLossless(const int32_t* px, size_t xs, size_t ys, size_t nc, c
     bw.Write(1, 1);  //   want_icc
     bw.Write(2, 0);  //   colour space RGB
   } else if (g_color.enabled) {
-    WriteColorEncodingFields(bw, gray);
-  } else if (!gray) {
+    WriteColorEncodingFields(bw, gray || (xyb_frame && g_xyb_gray));
+  } else if (!gray && !(xyb_frame && g_xyb_gray)) {
     bw.Write(1, 1);  // ColorEncoding all_default (sRGB)
   } else {
     bw.Write(1, 0);  // not all_default
@@ -3256,6 +3259,7 @@ void jxlenc_set_xyb_color_encoding(int enabled, uint32_t white_point, uint32_t p
   for (int i = 0; i < 8; i++) C.xy[i] = xy8 ? xy8[i] : 0;
   jxe::g_xyb_intensity = enabled && intensity_target > 0 ? intensity_target : 255.0f;
 }
+void jxlenc_set_xyb_gray(int on) { jxe::g_xyb_gray = on != 0; }
 void jxlenc_set_reference_frame(int slot) { jxe::g_reference_slot = slot; }
 // The next frame is a kDCFrame of `level` (1..4; 0 = a regular frame again) / the next VarDCT frame takes its DC image from
 // the DC frame before it (kUseDcFrame). Test aids, not thread-safe.

@@ -281,6 +281,7 @@ struct JxlHipContext {
   Buf alpha;                // f32 plane of the image size (jxlhip_set_alpha), used by 2- and 4-channel output
   bool have_alpha = false;
   bool color_out = false;   // the pixels come from k_color_out / k_upsample_color's generic writer (set at upload)
+  bool gray8_fast = false;  // one 8-bit sRGB channel from k_filter_rows2's one-channel form: fp.rgb has 1 byte per pixel (set at upload)
   JxlHipColorTarget ct{};   // JxlHipFrameDesc::color_target of the frame: its output encoding (tf != 0: the generic writer)
   Buf kend, block_recs, dequant_scan;
   Buf trecs;     // the transform work lists as 16-byte varblock records (TransformParams::trecs)
@@ -322,7 +323,7 @@ struct JxlHipContext {
   hipStream_t planes_stream = nullptr;
   // jxlhip_run_transform_batch / jxlhip_run_filter_color_batch: description of the frame set launched from this context
   struct FilterGroup {
-    int key;  // gaborish * 4 + epf iterations
+    int key;  // gaborish * 4 + epf iterations, + 8: frames of the one-channel 8-bit form (JxlHipContext::gray8_fast)
     uint32_t first, count, tiles_x, tiles_y;
     bool u8srgb;  // every frame of the group writes 8-bit sRGB only (k_filter_rows2<true>)
   };
@@ -359,6 +360,7 @@ static const JxlHipContext* PlaneHolder(const JxlHipContext* c) { return c->plan
 static size_t OutSampleBytes(const JxlHipContext* c) { return c->out_type == 2 ? 1 : (c->out_type == 0 ? 4 : 2); }
 static size_t OutPixelBytes(const JxlHipContext* c) { return OutSampleBytes(c) * c->out_nc; }
 static bool OutIsRgb8(const JxlHipContext* c) { return c->out_type == 2 && c->out_nc == 3 && c->out_bits == 8; }
+static bool OutIsGray8(const JxlHipContext* c) { return c->out_type == 2 && c->out_nc == 1 && c->out_bits == 8; }
 static bool OutIsRgbF32(const JxlHipContext* c) { return c->out_type == 0 && c->out_nc == 3 && !c->out_swap; }
 
 // Every index PrefixLookup (jxl_hip_kernels.h) can form from a cluster's two-level tables stays inside `table`, and
@@ -1127,7 +1129,15 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   if (!c->plane_lender && (r = c->plane[0].Ensure(plane_bytes))) return r;
   // pixels: RGB8 from every filter kernel, RGB f32 from the row-streaming one; any other format from the generic writer
   // (k_color_out on the filtered planes, or k_upsample_color)
-  c->color_out = !OutIsRgb8(c) && !(OutIsRgbF32(c) && c->ups == 1 && (c->epf_iters == 1 || c->epf_iters == 2));
+  // (one 8-bit channel: from the row-streaming kernel's one-channel form when the frame ends in sRGB; the filtered planes
+  // are not kept beside it)
+  const bool rows_kernel = c->ups == 1 && (c->epf_iters == 1 || c->epf_iters == 2);
+#ifdef JXLHIP_NO_GRAY8_ROWS  // (scripts/measure_grey_xyb.py: the comparison build, one 8-bit channel from the generic writer)
+  const bool gray8 = false;
+#else
+  const bool gray8 = OutIsGray8(c) && rows_kernel && d->linear_output == 0 && !c->keep_filtered;
+#endif
+  c->color_out = !OutIsRgb8(c) && !gray8 && !(OutIsRgbF32(c) && rows_kernel);
   if (c->out_orient) c->color_out = true;  // (the oriented layout is written by the generic writer)
   // frames of images that are not XYB encoded (linear_output 2 = YCbCr, 3 = no colour transform): the colour stage is
   // XybToRgb's other branches, which only the generic writers take
@@ -1418,8 +1428,9 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   }
   memcpy(fp.opsin_inv, d->opsin_inv, sizeof(fp.opsin_inv));
   fp.linear_output = d->linear_output;
-  fp.rgb = OutIsRgb8(c) ? c->rgb.as<uint8_t>() : nullptr;
-  fp.rgbf = !OutIsRgb8(c) && !c->color_out ? c->rgb.as<float>() : nullptr;
+  c->gray8_fast = OutIsGray8(c) && !c->color_out;
+  fp.rgb = OutIsRgb8(c) || c->gray8_fast ? c->rgb.as<uint8_t>() : nullptr;
+  fp.rgbf = !OutIsRgb8(c) && !c->gray8_fast && !c->color_out ? c->rgb.as<float>() : nullptr;
   c->epf_pass0 = d->epf_pass0_sigma_scale;
   c->epf_pass2 = d->epf_pass2_sigma_scale;
   c->epf_border = d->epf_border_sad_mul;
@@ -1589,7 +1600,7 @@ static void FillFusedParams(const JxlHipContext* c, jxlhip::FusedFilterParams* p
 }
 static int FilterKey(const JxlHipContext* c) {
   const int epf = c->epf_iters < 0 ? 0 : (c->epf_iters > 3 ? 3 : c->epf_iters);
-  return (c->gab ? 4 : 0) + epf;
+  return (c->gray8_fast ? 8 : 0) + (c->gab ? 4 : 0) + epf;
 }
 // Builds (or re-uses) the description of a set of frames for the batched transform and filter launches.
 static int PrepareDownstream(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n) {
@@ -1632,6 +1643,8 @@ static int PrepareDownstream(JxlHipContext* c0, JxlHipContext* const* ctxs, size
     JxlHipContext::FilterGroup& g = c0->fgroups.back();
     g.count++;
     g.u8srgb = g.u8srgb && fparams[j].f.rgb && !fparams[j].f.rgbf && !fparams[j].filtered && !fparams[j].f.linear_output;
+    // (a one-channel frame has no other form to fall back to: every other writer would put three bytes per pixel into its rows)
+    if (c->gray8_fast && !g.u8srgb) return JXLHIP_ERR_INVALID_ARGUMENT;
     g.tiles_x = tx > g.tiles_x ? tx : g.tiles_x;
     g.tiles_y = ty > g.tiles_y ? ty : g.tiles_y;
   }
@@ -1669,7 +1682,7 @@ static int LaunchFused(JxlHipContext* c0, const JxlHipContext::FilterGroup& g) {
 }
 
 // (Gaborish +) EPF1 (the d1.0 configuration) or EPF1 + EPF2 (`epf` = 2): the row-streaming kernel, no LDS.
-static int LaunchFilterRows(JxlHipContext* c0, const JxlHipContext::FilterGroup& g, int epf, bool gab) {
+static int LaunchFilterRows(JxlHipContext* c0, const JxlHipContext::FilterGroup& g, int epf, bool gab, bool gray = false) {
   const uint32_t cols = g.tiles_x * jxlhip::kFusedTW, rows = g.tiles_y * jxlhip::kFusedTH;  // upper bounds of the group
   const uint32_t gx = ((cols + jxlhip::kRows2Cols - 1) / jxlhip::kRows2Cols + jxlhip::kRowsWaves - 1) / jxlhip::kRowsWaves;
   // strip height: every strip re-reads and re-filters 6 halo rows, so the taller the better as long as the launch still
@@ -1682,8 +1695,12 @@ static int LaunchFilterRows(JxlHipContext* c0, const JxlHipContext::FilterGroup&
   const RowsKernel k2t = jxlhip::k_filter_rows2<true, 2>, k2f = jxlhip::k_filter_rows2<false, 2>;
   const RowsKernel n1t = jxlhip::k_filter_rows2<true, 1, false>, n1f = jxlhip::k_filter_rows2<false, 1, false>;
   const RowsKernel n2t = jxlhip::k_filter_rows2<true, 2, false>, n2f = jxlhip::k_filter_rows2<false, 2, false>;
-  const RowsKernel k = gab ? (epf == 2 ? (g.u8srgb ? k2t : k2f) : (g.u8srgb ? k1t : k1f))
-                           : (epf == 2 ? (g.u8srgb ? n2t : n2f) : (g.u8srgb ? n1t : n1f));
+  const RowsKernel k1g = jxlhip::k_filter_rows2<true, 1, true, true>, k2g = jxlhip::k_filter_rows2<true, 2, true, true>;
+  const RowsKernel n1g = jxlhip::k_filter_rows2<true, 1, false, true>, n2g = jxlhip::k_filter_rows2<true, 2, false, true>;
+  if (gray && !g.u8srgb) return JXLHIP_ERR_INVALID_ARGUMENT;
+  const RowsKernel k = gray ? (gab ? (epf == 2 ? k2g : k1g) : (epf == 2 ? n2g : n1g))
+                       : gab ? (epf == 2 ? (g.u8srgb ? k2t : k2f) : (g.u8srgb ? k1t : k1f))
+                             : (epf == 2 ? (g.u8srgb ? n2t : n2f) : (g.u8srgb ? n1t : n1f));
   for (uint32_t z = 0; z < g.count; z += 65535) {  // grid z limit
     const uint32_t zn = g.count - z < 65535 ? g.count - z : 65535;
     const jxlhip::FusedFilterParams* fp = c0->fb_params.as<jxlhip::FusedFilterParams>() + g.first + z;
@@ -2951,15 +2968,16 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
   const hipStream_t ls = c0->fstream;
   HIP_TRY(hipEventRecord(c0->ev[4], ls));
   for (const JxlHipContext::FilterGroup& g : c0->fgroups) {
-    switch (g.key) {
-      case 0: r = LaunchFused<false, 0>(c0, g); break;
-      case 1: r = LaunchFilterRows(c0, g, 1, false); break;
-      case 2: r = LaunchFilterRows(c0, g, 2, false); break;
-      case 3: r = LaunchFused<false, 3>(c0, g); break;
-      case 4: r = LaunchFused<true, 0>(c0, g); break;
-      case 5: r = LaunchFilterRows(c0, g, 1, true); break;
-      case 6: r = LaunchFilterRows(c0, g, 2, true); break;
-      default: r = LaunchFused<true, 3>(c0, g); break;
+    const bool gray = (g.key & 8) != 0;  // (only frames of the row-streaming kernel: set at upload)
+    switch (g.key & 7) {
+      case 0: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<false, 0>(c0, g); break;
+      case 1: r = LaunchFilterRows(c0, g, 1, false, gray); break;
+      case 2: r = LaunchFilterRows(c0, g, 2, false, gray); break;
+      case 3: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<false, 3>(c0, g); break;
+      case 4: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<true, 0>(c0, g); break;
+      case 5: r = LaunchFilterRows(c0, g, 1, true, gray); break;
+      case 6: r = LaunchFilterRows(c0, g, 2, true, gray); break;
+      default: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<true, 3>(c0, g); break;
     }
     if (r) return r;
   }
@@ -3457,6 +3475,13 @@ int jxlhip_debug_color(JxlHipContext* c, const float* xyb, size_t n, int linear_
 int jxlhip_debug_color_target(JxlHipContext* c, const float* xyb, size_t n, const JxlHipColorTarget* t, float* rgb) {
   if (!t) return JXLHIP_ERR_INVALID_ARGUMENT;
   return DebugColor(c, xyb, n, 1, t, rgb);
+}
+
+int jxlhip_debug_pixel_route(JxlHipContext* c, uint32_t* route) {
+  if (!c || !route) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
+  *route = c->color_out || c->ups != 1 ? 0u : (c->gray8_fast ? 2u : 1u);
+  return 0;
 }
 
 int jxlhip_check_guards(JxlHipContext* c, uint32_t* touched) {

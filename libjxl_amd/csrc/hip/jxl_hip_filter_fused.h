@@ -489,9 +489,14 @@ __device__ __forceinline__ P2 BufP2(__amdgpu_buffer_rsrc_t r, uint32_t voff, uin
 // GAB = false (what the reference's encoder writes at its fast efforts, Gaborish off: enc_frame.cc:316-322): the
 // "Gaborish output" ring is fed with the input row itself, one row behind like the filtered one would be; nothing else
 // changes (the halo stays the same, one row and column more than needed).
-template <bool U8SRGB, int EPF = 1, bool GAB = true>
+// GREY (with U8SRGB): the launch's frames all write one 8-bit sRGB channel, f.rgb being rows of xs bytes: channel 0 of the
+// colour stage alone (for a grey image, whose matrix has three equal rows, the pixel: dec_xyb.cc:228-232, stage_write.cc
+// num_color_ = 1). The filters are the same, all three XYB channels feed their sums; of the colour stage one matrix row, one
+// curve and one dither cell are left, spelled as in the RGB form, so the samples equal the RGB form's red channel bit for bit.
+template <bool U8SRGB, int EPF = 1, bool GAB = true, bool GREY = false>
 __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFilterParams* params, int strip_rows) {
   static_assert(EPF == 1 || EPF == 2, "(Gaborish +) one or two EPF iterations");
+  static_assert(U8SRGB || !GREY, "the one-channel writer exists for 8-bit sRGB only");
   constexpr int HALO = kRowsHalo + (EPF == 2 ? 1 : 0);
   FusedFilterParams P;
   LoadParams(P, params + blockIdx.z);
@@ -516,7 +521,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFil
   // loop-invariant lane offsets in bytes; the per-step part of every address is a scalar
   const uint32_t vo0 = uint32_t(mx0) * 4u, vo1 = uint32_t(mx1) * 4u;  // input columns
   const uint32_t vsig = uint32_t(mx0 >> 3) * 4u;                      // x is even: the pair shares its 8x8 block
-  const uint32_t vout = uint32_t(x) * 3u;                             // interleaved RGB column (lanes with x < 0 never store)
+  const uint32_t vout = uint32_t(x) * (GREY ? 1u : 3u);               // interleaved RGB column (lanes with x < 0 never store)
   const uint32_t vd0 = uint32_t(x & 31) * 4u;                         // dither columns: channel 0 (even: pair contiguous)
   const uint32_t vd1a = uint32_t((x + 23) & 31) * 4u, vd1b = uint32_t((x + 24) & 31) * 4u;  // channel 1 (odd: may wrap)
   const uint32_t vd2 = uint32_t((x + 46) & 31) * 4u;                  // channel 2 (even)
@@ -578,6 +583,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFil
     is = BufF32(sig_buf, vsig, uint32_t(rc >> 3) * uint32_t(P.f.xb) * 4u);
     if (!has_rgb) return;
     di[0] = BufP2(dither_buf, vd0, uint32_t(r & 31) * 128u);
+    if constexpr (GREY) return;
     di[1] = P2{BufF32(dither_buf, vd1a, uint32_t((r + 13) & 31) * 128u), BufF32(dither_buf, vd1b, uint32_t((r + 13) & 31) * 128u)};
     di[2] = BufP2(dither_buf, vd2, uint32_t((r + 26) & 31) * 128u);
   };
@@ -732,6 +738,22 @@ __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFil
           const P2 gr = (Y + X) - P.f.opsin_bias_cbrt[0], gg = (Y - X) - P.f.opsin_bias_cbrt[1], gb = Bc - P.f.opsin_bias_cbrt[2];
           const P2 mr = (gr * gr) * gr + P.f.opsin_bias[0], mg = (gg * gg) * gg + P.f.opsin_bias[1], mb = (gb * gb) * gb + P.f.opsin_bias[2];
           P2 cr = P.f.opsin_inv[2] * mb + (P.f.opsin_inv[1] * mg + P.f.opsin_inv[0] * mr);
+          if constexpr (GREY) {
+            cr = Srgb2ForU8(cr);
+            const bool even = ((r & xs) & 1) == 0;  // r * xs + x with x even: the row's parity decides the alignment
+            uint32_t w = __builtin_amdgcn_cvt_pk_u8_f32(cr.x * 255.0f + di[0].x, 0, 0u);
+            w = __builtin_amdgcn_cvt_pk_u8_f32(cr.y * 255.0f + di[0].y, 1, w);
+            const uint32_t orow = uint32_t(r) * uint32_t(xs);
+            asm volatile("" : "+v"(w));  // (as below: the packed bytes exist for every lane before the masked stores)
+            if (!emit0) {
+              // (a lane of the halo columns, or beyond the frame: nothing to store)
+            } else if (even && emit1) {  // two bytes at r * xs + x, even: one 16-bit store
+              __builtin_amdgcn_raw_buffer_store_b16(uint16_t(w), rgb_buf, vout, orow, 0);
+            } else {
+              __builtin_amdgcn_raw_buffer_store_b8(uint8_t(w), rgb_buf, vout, orow, 0);
+              if (emit1) __builtin_amdgcn_raw_buffer_store_b8(uint8_t(w >> 8), rgb_buf, vout + 1, orow, 0);
+            }
+          } else {
           P2 cg = P.f.opsin_inv[5] * mb + (P.f.opsin_inv[4] * mg + P.f.opsin_inv[3] * mr);
           P2 cb = P.f.opsin_inv[8] * mb + (P.f.opsin_inv[7] * mg + P.f.opsin_inv[6] * mr);
           const bool even = ((r & xs) & 1) == 0;  // (r * xs + x) * 3 with x even: the row's parity decides the alignment
@@ -799,6 +821,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFil
                 __builtin_amdgcn_raw_buffer_store_b8(uint8_t(w2 >> 8), rgb_buf, vout + 5, orow, 0);
               }
             }
+          }
           }
         }
       }

@@ -1595,7 +1595,7 @@ struct FilterParams {
   // colour
   float opsin_inv[9], opsin_bias[3], opsin_bias_cbrt[3];
   int32_t linear_output;
-  uint8_t* rgb;  // interleaved RGB8 (xs * 3 bytes per row), or NULL
+  uint8_t* rgb;  // interleaved RGB8 (xs * 3 bytes per row), or NULL; k_filter_rows2's one-channel form: rows of xs bytes
   float* rgbf;   // interleaved RGB f32 (stage_write.cc:334-370 StoreFloatRow), or NULL; honoured by k_filter_rows2 only
 };
 

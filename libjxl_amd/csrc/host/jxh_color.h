@@ -135,8 +135,11 @@ static inline double PqEncodeNits(double nits) {
 static inline bool MakeColorOutput(const JxlColorEncoding& src, float src_intensity, const JxlColorEncoding& dst, float desired,
                                    const float* inv_opsin, JxlHipColorTarget* t, std::string* err) {
   memset(t, 0, sizeof(*t));
-  if (dst.color_space != JXL_COLOR_SPACE_RGB || src.color_space != JXL_COLOR_SPACE_RGB) {
-    *err = "unsupported: XYB output to a colour space other than RGB";
+  // dec_xyb.cc:127-135,228-232: a grey image renders to grey (D65 here, see ReadColorEncoding), a colour image to RGB
+  const bool grey = src.color_space == JXL_COLOR_SPACE_GRAY;
+  if (grey ? (dst.color_space != JXL_COLOR_SPACE_GRAY || src.white_point != JXL_WHITE_POINT_D65 || dst.white_point != JXL_WHITE_POINT_D65)
+           : (dst.color_space != JXL_COLOR_SPACE_RGB || src.color_space != JXL_COLOR_SPACE_RGB)) {
+    *err = grey ? "unsupported: grey XYB output to a colour space other than D65 grey" : "unsupported: XYB output to a colour space other than RGB";
     return false;
   }
   if (!(src_intensity > 0)) {
@@ -147,7 +150,7 @@ static inline bool MakeColorOutput(const JxlColorEncoding& src, float src_intens
   Mat3 m;
   for (int i = 0; i < 9; i++) m[i / 3][i % 3] = inv_opsin[i];
   double lum[3] = {0.2126, 0.7152, 0.0722};
-  if (dst.primaries != JXL_PRIMARIES_SRGB || dst.white_point != JXL_WHITE_POINT_D65) {  // dec_xyb.cc:195-226
+  if (!grey && (dst.primaries != JXL_PRIMARIES_SRGB || dst.white_point != JXL_WHITE_POINT_D65)) {  // dec_xyb.cc:195-226
     Mat3 srgb_to_xyz, adapt, to_xyz, xyzd50_to_dst;
     const double p[6] = {dst.primaries_red_xy[0], dst.primaries_red_xy[1], dst.primaries_green_xy[0],
                          dst.primaries_green_xy[1], dst.primaries_blue_xy[0], dst.primaries_blue_xy[1]};
@@ -169,6 +172,12 @@ static inline bool MakeColorOutput(const JxlColorEncoding& src, float src_intens
     }
     Mul3(xyzd50_to_dst, srgb_to_xyz, xyzd50_to_dst);
     Mul3(xyzd50_to_dst, m, m);
+  }
+  if (grey) {  // dec_xyb.cc:228-232: [lum; lum; lum] * inverse matrix: three equal channels, the writer hands out the first
+    Mat3 l;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) l[i][j] = lum[j];
+    Mul3(l, m, m);
   }
   // InitSIMDInverseMatrix: relative luminance, 1.0 = the image's intensity target (as the sRGB path: jxl_api.cc)
   for (int i = 0; i < 9; i++) t->matrix[i] = float(m[i / 3][i % 3]) * (255.0f / src_intensity);
@@ -228,6 +237,18 @@ static inline bool MakeColorOutput(const JxlColorEncoding& src, float src_intens
     }
   }
   return true;
+}
+// The matrix of a frame whose colour stage nobody described (ColorOutput inactive): the image's own inverse opsin matrix
+// scaled to relative luminance, for a grey image behind the luminance rows of MakeColorOutput.
+static inline void OwnMatrix(const ImageHeader& ih, float* out) {
+  const float scale = 255.0f / ih.intensity_target;
+  for (int i = 0; i < 9; i++) out[i] = ih.inv_opsin[i] * scale;
+  if (!ih.gray || !ih.xyb_encoded) return;
+  const double lum[3] = {0.2126, 0.7152, 0.0722};
+  for (int j = 0; j < 3; j++) {
+    const double v = lum[0] * ih.inv_opsin[j] + lum[1] * ih.inv_opsin[3 + j] + lum[2] * ih.inv_opsin[6 + j];
+    out[j] = out[3 + j] = out[6 + j] = float(v) * scale;
+  }
 }
 // What the decoder hands a frame's upload: the matrix towards the output primaries (scaled by 255 / intensity target),
 // whether the filter kernels end linear, and the generic writer's target (target.tf != 0) when they cannot render it.

@@ -4,7 +4,7 @@
 // lib/jxl/color_encoding_internal.cc:94-215, lib/jxl/frame_header.cc:30-439, lib/jxl/frame_header.h:35-50,
 // lib/jxl/loop_filter.cc:20-100, lib/jxl/toc.cc:29-115, lib/jxl/toc.h:31-41,
 // lib/jxl/frame_dimensions.h:34-59.
-// Unsupported features (grey XYB images other than (linear) sRGB) raise jxh::Error.
+// Unsupported features (grey XYB images that are not D65, or PQ) raise jxh::Error.
 #ifndef JXH_HEADERS_H_
 #define JXH_HEADERS_H_
 
@@ -128,11 +128,13 @@ static inline void ReadColorEncoding(BitReader& br, ImageHeader* h) {
   JXH_CHECK(h->rendering_intent <= 3, "invalid rendering intent");
   h->linear_tf = !h->have_gamma && h->transfer_function == 8;
   // an XYB image in any valid enum encoding of an RGB space is rendered to it by the colour stage (jxh_color.h after
-  // dec_xyb.cc:127-250, no CMS). Grey XYB images are not rendered here: those in (linear) sRGB get their header events and
-  // are refused at the pixels (the output format check, jxh_modframe.h), any other one is refused here.
+  // dec_xyb.cc:127-250, no CMS). A grey XYB image is rendered likewise (its luminance: jxh_color.h) when its white point is
+  // D65, with the sRGB, linear, 709, HLG or DCI curve or a gamma. Refused here: another white point (the reference falls
+  // back to linear grey there, dec_xyb.cc:137-140,160-164), and grey PQ, which the colour stage could render as well: its
+  // refusal with the headers is what tests/test_color_encoding_host.py holds this reader to, so it stays until that changes.
   if (h->xyb_encoded && cs == 1)
-    JXH_CHECK(h->white_point == 1 && !h->have_gamma && (h->transfer_function == 13 || h->transfer_function == 8),
-              "unsupported: XYB image in a colour space other than (linear) sRGB");
+    JXH_CHECK(h->white_point == 1 && (h->have_gamma || h->transfer_function != 16),
+              "unsupported: grey XYB image in a colour space other than D65 grey with an sRGB / linear / 709 / HLG / DCI / gamma curve");
 }
 
 static inline void ReadImageHeader(BitReader& br, ImageHeader* h) {

@@ -86,7 +86,6 @@ class ModFrameParser {
     // (1 = kDCFrame: kept before the colour transform as a later frame's DC image; 2 = kReferenceOnly; 3 = kSkipProgressive)
     // (where the frame sits on the canvas and how it blends: the caller's business, as for FrameParser::ParseFrame)
     JXH_CHECK(!fh.ycbcr, "unsupported: YCbCr Modular frames");
-    JXH_CHECK(!(ih.xyb_encoded && ih.gray), "unsupported: grey XYB Modular frames");
     JXH_CHECK(fh.upsampling == 1 && fh.num_passes == 1, "unsupported: upsampled / multi-pass Modular frames");
     for (uint32_t u : fh.ec_upsampling) JXH_CHECK(u == 1, "unsupported: upsampled extra channels");
     JXH_CHECK(!(fh.flags & (FrameHeader::kNoise | FrameHeader::kUseDcFrame)), "unsupported: noise / kUseDcFrame on Modular frames");
@@ -134,12 +133,12 @@ class ModFrameParser {
       }
     bool have_global = false;
     if (g.ReadBool()) {
-      const size_t nb = (ih.gray ? 1 : 3) + ih.extra.size();
+      const size_t nb = (ih.gray && !ih.xyb_encoded ? 1 : 3) + ih.extra.size();
       DecodeTree(g, &P.trees[0], std::min<size_t>(size_t(1) << 22, 1024 + d.xsize * d.ysize * nb / 16));
       DecodeHistograms(g, (P.trees[0].size() + 1) / 2, &P.codes[0]);
       have_global = true;
     }
-    P.num_color = ih.gray ? 1 : 3;
+    P.num_color = ih.gray && !ih.xyb_encoded ? 1 : 3;  // (dec_modular.cc: one colour channel only without a colour transform)
     std::vector<VCh> full;
     for (size_t c = 0; c < P.num_color + ih.extra.size(); c++) full.push_back(NewChannel(&P, d.xsize, d.ysize, 0, 0));
     size_t nb_meta = 0;
