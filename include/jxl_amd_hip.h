@@ -302,6 +302,9 @@ int jxlhip_get_section_end_bits(JxlHipContext* ctx, uint32_t* bits, size_t n);
  *   "xyb_idct"     float [3][ysize_padded][xsize_padded] after the inverse transforms
  *   "xyb_filtered" float [3][ysize_padded][xsize_padded] after Gaborish/EPF (rows < ysize, columns < xsize valid;
  *                  only with option "keep_filtered")
+ *   "kend"         uint32 [num_blocks][3]: scan position after the last non-zero coefficient of a (varblock, channel);
+ *                  frames decoded in scan order only (after the entropy stage)
+ *   "transform_lists" uint32 [entries][2] = {strategy, varblock index}: the transform work lists in launch order
  * Returns the number of bytes the buffer needs through *needed when dst is NULL. */
 int jxlhip_download(JxlHipContext* ctx, const char* name, void* dst, size_t dst_size, size_t* needed);
 
@@ -309,6 +312,8 @@ int jxlhip_download(JxlHipContext* ctx, const char* name, void* dst, size_t dst_
  * XYB planes for jxlhip_download("xyb_filtered") (test aid; costs one extra plane set and 12 B/pixel of writes). Switched
  * on only after the upload of a frame that writes one 8-bit channel from the filter kernel (rows of 1 byte per pixel,
  * which no other writer may fill), it makes the filter launch fail with JXLHIP_ERR_INVALID_ARGUMENT: upload again.
+ * "transform_dense" = 1 (test aid): the transform kernels treat every coefficient extent as full, i.e. take none of the
+ * shortcuts they decide from the coefficient counts. The same kernels, the same results.
  * "filter_async" = 1 (on the FIRST context of a set; may be changed at any time): jxlhip_run_filter_color_batch launches
  * on that context's second stream, ordered after the work its first stream holds. The call sequence entropy_batch,
  * transform_batch, filter_color_batch, entropy_batch, ... on one frame set then overlaps every filter + colour launch

@@ -241,6 +241,7 @@ struct JxlHipContext {
   bool lanes = false, lane_multi = false;
   uint32_t nblocks = 0;
   bool keep_filtered = false;  // jxlhip_set_option("keep_filtered"): also write the filtered XYB planes (tests)
+  bool transform_dense = false;  // jxlhip_set_option("transform_dense"): TransformParams::dense at the next upload (tests)
   bool band_halo = false;      // jxlhip_set_option("band_halo"): a band decodes ONLY its own group rows; the rows of the
                                // neighbouring bands that its filters read arrive through jxlhip_halo_unpack
   // output pixel format (jxlhip_set_output_format; JxlDataType numbering): RGB8 by default
@@ -1361,6 +1362,7 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
     if (d->dequant_size[k] != 64u * areas[s] || size_t(d->dequant_offset[k]) + 3 * size_t(d->dequant_size[k]) > d->dequant_floats)
       return JXLHIP_ERR_INVALID_ARGUMENT;
   }
+  tp.dense = c->transform_dense ? 1 : 0;
   tp.cs = cs;
   tp.cs_out = c->plane[1].as<float>();  // (a YCbCr frame's colour stage is the generic writer: the second plane set exists)
   tp.dc = c->dc.as<float>();
@@ -3272,6 +3274,10 @@ int jxlhip_set_option(JxlHipContext* c, const char* name, int value) {
     c->keep_filtered = value != 0;
     return 0;
   }
+  if (std::string(name) == "transform_dense") {  // (takes effect at the next upload)
+    c->transform_dense = value != 0;
+    return 0;
+  }
   if (std::string(name) == "band_halo") {  // (takes effect at the next upload of a band)
     c->band_halo = value != 0;
     return 0;
@@ -3590,6 +3596,13 @@ int jxlhip_download(JxlHipContext* c, const char* name, void* dst, size_t dst_si
   } else if (n == "inv_sigma") {
     src = c->inv_sigma.p;
     bytes = size_t(c->xb) * c->yb * 4;
+  } else if (n == "kend") {  // uint32 [varblock][3]: scan position after the last non-zero coefficient (scan-order frames)
+    if (!c->scan_order) return JXLHIP_ERR_INVALID_ARGUMENT;
+    src = c->kend.p;
+    bytes = c->blocks_host.size() * 12;
+  } else if (n == "transform_lists") {  // uint32 [entry][2] = {strategy, varblock}: the transform work lists in launch order
+    if (!c->scan_order) return JXLHIP_ERR_INVALID_ARGUMENT;
+    bytes = size_t(c->list_begin[26] + c->list_count[26]) * 8;
   } else if (n == "xyb_filtered") {
     if (!c->keep_filtered || !c->plane[1].p) return JXLHIP_ERR_INVALID_ARGUMENT;  // needs jxlhip_set_option("keep_filtered", 1)
     src = c->plane[1].p;
@@ -3604,6 +3617,18 @@ int jxlhip_download(JxlHipContext* c, const char* name, void* dst, size_t dst_si
   {
     int pw = ApplyPendingWait(c);
     if (pw) return pw;
+  }
+  if (n == "transform_lists") {
+    uint32_t* out = static_cast<uint32_t*>(dst);
+    std::vector<uint32_t> list(bytes / 8);
+    HIP_TRY(hipMemcpyAsync(list.data(), c->tlist.p, list.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int s = 0; s < 27; s++)
+      for (uint32_t j = 0; j < c->list_count[s]; j++) {
+        out[2 * size_t(c->list_begin[s] + j)] = uint32_t(s);
+        out[2 * size_t(c->list_begin[s] + j) + 1] = list[c->list_begin[s] + j];
+      }
+    return 0;
   }
   HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

@@ -912,6 +912,10 @@ struct TransformParams {
   // The lowest frequencies come from the channel's own DC sample, at the same shifted position of its DC plane.
   uint32_t cs;
   float* cs_out;
+  // jxlhip_set_option("transform_dense") (tests): k_idct_fast treats every coefficient extent as full, i.e. takes none of
+  // its wave-uniform shortcuts (the channel from its lowest frequencies alone, staging rounds left out). Same kernel,
+  // same results.
+  uint32_t dense;
 };
 
 // Batched launches: one workgroup descriptor per workgroup = {frame index into the parameter array, index of the
@@ -1031,32 +1035,10 @@ struct WcTable<64> {  // 1 / (2 cos((n + 1/2) pi / 64)), n = 0..31 (dct_scales.h
   static constexpr float v[32] = {5.001506360e-01f, 5.013584524e-01f, 5.037887257e-01f, 5.074711721e-01f, 5.124514794e-01f, 5.187927131e-01f, 5.265773152e-01f, 5.359098169e-01f, 5.469204380e-01f, 5.597698129e-01f, 5.746551840e-01f, 5.918185359e-01f, 6.115573479e-01f, 6.342389367e-01f, 6.603198078e-01f, 6.903721282e-01f, 7.251205224e-01f, 7.654941650e-01f, 8.127020908e-01f, 8.683447152e-01f, 9.345835970e-01f, 1.014408265e+00f, 1.112071621e+00f, 1.233832738e+00f, 1.389293959e+00f, 1.593972283e+00f, 1.874675980e+00f, 2.282050068e+00f, 2.924628428e+00f, 4.084611078e+00f, 6.796750712e+00f, 2.037387817e+01f};
 };
 
-template <int N>
-__device__ __forceinline__ void FastIdct(float (&v)[N]) {
-  if constexpr (N == 2) {
-    const float a = v[0] + v[1], b = v[0] - v[1];
-    v[0] = a;
-    v[1] = b;
-  } else if constexpr (N > 2) {
-    float e[N / 2], o[N / 2];
-#pragma unroll
-    for (int j = 0; j < N / 2; j++) {
-      e[j] = v[2 * j];
-      o[j] = v[2 * j + 1];
-    }
-#pragma unroll
-    for (int j = N / 2 - 1; j > 0; j--) o[j] += o[j - 1];
-    o[0] *= 1.41421356237309504880f;
-    FastIdct<N / 2>(e);
-    FastIdct<N / 2>(o);
-#pragma unroll
-    for (int n = 0; n < N / 2; n++) {
-      const float t = o[n] * WcTable<N>::v[n];
-      v[n] = e[n] + t;
-      v[N - 1 - n] = e[n] - t;
-    }
-  }
-}
+// FastIdct<N> and the pruned FastIdctPruned<N, K> over these tables: plain C++ a host compiler can read too (tests)
+}  // namespace jxlhip
+#include "jxl_idct_butterfly.h"
+namespace jxlhip {
 
 // Tile hand-over inside a ONE-WAVE workgroup: the LDS operations of a wave execute in order, so a later read sees an
 // earlier write of any lane without a wait; only the compiler must not reorder them. __syncthreads() here would be a
@@ -1138,24 +1120,44 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
   ushort4 pp[PR];
   float4 pw[PR];
   uint32_t ke3[3] = {0, 0, 0};
-  auto prefetch = [&](int c) {
+  // Coefficient extents. kend is the scan position after a (varblock, channel)'s last non-zero coefficient; at d1.0 the sum
+  // of them is a quarter of all positions and chroma of the large classes has none beyond the lowest-frequency corner
+  // (DESIGN.md 8.3). Everything below that depends on them is decided for the WAVE, from the largest kend of its
+  // varblocks (inactive groups count 0): scalar branches, no new EXEC regions (per-lane predication was measured worse, see
+  // the staging loop). `rounds(c)`: how many of the PR staging rounds reach a coefficient of channel c; 0 = no varblock of
+  // the wave has anything beyond the corner, which comes from the DC image.
+  const bool sparse = P.scan_order != 0 && P.dense == 0;
+  auto rounds = [&](int c) -> int {
+    if (!sparse) return PR;
+    int n = __any(ke3[c] > uint32_t(CX * CY)) ? 1 : 0;
+    if constexpr (PF) {
+#pragma unroll
+      for (int r = 1; r < PR; r++) n += __any(ke3[c] > uint32_t(r * TB * 4)) ? 1 : 0;
+    }
+    return n;
+  };
+  auto prefetch = [&](int c, int nr) {
     const CoefT* gqc = gq + size_t(c) * 65536;
     const uint16_t* order = P.orders + P.order_offset[ord * 3 + c];
     const float* ms = P.dequant_scan + ((m + size_t(c) * msize) - P.dequant);
 #pragma unroll
     for (int r = 0; r < PR; r++) {
-      const uint32_t k4 = uint32_t(t) * 4 + uint32_t(r) * TB * 4;
-      pq[r] = load_coef4(gqc + k4);
-      pp[r] = *reinterpret_cast<const ushort4*>(order + k4);
-      pw[r] = *reinterpret_cast<const float4*>(ms + k4);
+      if (r < nr) {
+        const uint32_t k4 = uint32_t(t) * 4 + uint32_t(r) * TB * 4;
+        pq[r] = load_coef4(gqc + k4);
+        pp[r] = *reinterpret_cast<const ushort4*>(order + k4);
+        pw[r] = *reinterpret_cast<const float4*>(ms + k4);
+      }
     }
   };
   const bool pf = PF && P.scan_order != 0;
-  if (pf && active) {
+  if (P.scan_order != 0 && active) {
 #pragma unroll
     for (int c = 0; c < 3; c++) ke3[c] = P.kend[bidx * 3 + c];
-    prefetch(1);
+    // (Y has coefficients in practically every wave: its loads do not wait for the counts)
+    if (pf) prefetch(1, PR);
   }
+  const int nr3[3] = {rounds(0), rounds(1), rounds(2)};
 #pragma unroll
   for (int ci = 0; ci < 3; ci++) {
     const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
@@ -1164,7 +1166,13 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
     const uint32_t hs = CS ? (P.cs >> (2 * c)) & 1u : 0u, vs = CS ? (P.cs >> (2 * c + 1)) & 1u : 0u;
     const bool act_c = active && (!CS || ((uint32_t(vb.bx) & hs) | (uint32_t(vb.by) & vs)) == 0);
     const uint32_t obx = active ? uint32_t(vb.bx) >> hs : 0u, oby = active ? uint32_t(vb.by) >> vs : 0u;
-    if (!pf) {
+    // nr == 0: the channel is its lowest-frequency corner alone. Nothing is loaded, zeroed or staged, and the two passes
+    // below run the pruned butterfly on the corner: the bits of the full path on the zero-padded tile.
+    const int nr = nr3[c];
+    const bool llf_only = sparse && nr == 0;
+    // the tile's zeros: every position is written by the rounds of the prefetching classes when all of them run; rounds left
+    // out leave theirs to a wide fill first (the wave's LDS operations execute in order)
+    if (!llf_only && (!pf || nr < PR)) {
       if (active)
         for (int i = t * 4; i < TILE; i += TB * 4) *reinterpret_cast<float4*>(l + i) = make_float4(0.f, 0.f, 0.f, 0.f);
       WaveLdsSync();
@@ -1174,7 +1182,7 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
       const CoefT* gqc = gq + size_t(c) * 65536;
       const float* mc = m + size_t(c) * msize;
       if (pf) {
-        // this channel's rounds are in registers; the next channel's leave now
+        // this channel's rounds are in registers; the next channel's leave now (those that reach a coefficient)
         Coef4 cq[PR];
         ushort4 cp[PR];
         float4 cw[PR];
@@ -1184,11 +1192,12 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
           cp[r] = pp[r];
           cw[r] = pw[r];
         }
-        if (ci < 2) prefetch(ci == 0 ? 0 : 2);
+        if (ci < 2) prefetch(ci == 0 ? 0 : 2, nr3[ci == 0 ? 0 : 2]);
         const uint32_t ke = ke3[c];
         const uint32_t k1 = ke < uint32_t(SIZE) ? ke : uint32_t(SIZE);
 #pragma unroll
         for (int r = 0; r < PR; r++) {
+          if (r >= nr) break;  // (wave-uniform; the rounds that run stay unpredicated)
           const uint32_t k4 = uint32_t(t) * 4 + uint32_t(r) * TB * 4;
           const uint32_t pos4[4] = {cp[r].x, cp[r].y, cp[r].z, cp[r].w};
           const float wv[4] = {cw[r].x, cw[r].y, cw[r].z, cw[r].w};
@@ -1199,18 +1208,20 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
             const uint32_t pos = pos4[j];
             const uint32_t idx = R < C ? pos : (pos % R) * C + pos / R;  // natural layout keeps the short side as rows
             const float val = QuantBiasNoBranch(c, q, P.biases) * (wv[j] * mul);
-            // every position of the tile is written exactly once by these rounds, so nothing zeroes it first and no store
-            // is predicated (24 EXEC regions with their branches per thread otherwise): zero where there is no coefficient
+            // every position of the tile is written exactly once by these rounds (when all run), so nothing zeroes it first
+            // and no store is predicated (24 EXEC regions with their branches per thread otherwise): zero where there is no coefficient
             // (beyond the count, or a zero), and at the lowest-frequency corner, which the wave overwrites below (its LDS
             // operations execute in order)
             l[(idx >> LOGC) * S + (idx & (C - 1))] = (k >= uint32_t(CX * CY) && k < k1 && q) ? val : 0.0f;
           }
         }
+      } else if (llf_only) {
+        // (nothing to stage)
       } else if (P.scan_order) {
         // entry k: coefficient, its position and its dequant weight are three independent coalesced loads
         const uint16_t* order = P.orders + P.order_offset[ord * 3 + c];
         const float* ms = P.dequant_scan + (mc - P.dequant);
-        const uint32_t ke = P.kend[bidx * 3 + c];
+        const uint32_t ke = ke3[c];
         const uint32_t k1 = ke < uint32_t(SIZE) ? ke : uint32_t(SIZE);
         // four scan positions per thread and round: one 8-byte (int16) coefficient load, one 8-byte load of their positions
         // and one 16-byte load of their weights instead of four rounds of 2 + 2 + 4 bytes (the kernel is bound by the number
@@ -1253,7 +1264,16 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
       }
     }
     WaveLdsSync();
-    if (act_c && t < R) {  // pass 1: row ky = t
+    if (llf_only) {
+      if (act_c && t < CY) {  // pass 1 on the corner's rows: CX inputs each (rows ky >= CY are zero and stay zero)
+        float v[C];
+#pragma unroll
+        for (int kx = 0; kx < C; kx++) v[kx] = kx < CX ? l[t * S + kx] : 0.0f;
+        FastIdctPruned<C, CX>(v);
+#pragma unroll
+        for (int x = 0; x < C; x++) l[t * S + x] = v[x];
+      }
+    } else if (act_c && t < R) {  // pass 1: row ky = t
       float v[C];
 #pragma unroll
       for (int kx = 0; kx < C; kx++) v[kx] = l[t * S + kx];
@@ -1264,9 +1284,15 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
     WaveLdsSync();
     if (act_c && t < C) {  // pass 2: column x = t
       float v[R];
+      if (llf_only) {  // CY inputs
 #pragma unroll
-      for (int ky = 0; ky < R; ky++) v[ky] = l[ky * S + t];
-      FastIdct<R>(v);
+        for (int ky = 0; ky < R; ky++) v[ky] = ky < CY ? l[ky * S + t] : 0.0f;
+        FastIdctPruned<R, CY>(v);
+      } else {
+#pragma unroll
+        for (int ky = 0; ky < R; ky++) v[ky] = l[ky * S + t];
+        FastIdct<R>(v);
+      }
       // rows through a raw buffer: one 32-bit lane offset for the column, the row's offset in a scalar register (24 64-bit
       // address computations per thread otherwise); three planes of at most 1 GiB: the offsets fit 32 bits.
       // (Measured and not kept, round 4: rows in the last pass, so that a thread stores C adjacent pixels as 16-byte pieces
