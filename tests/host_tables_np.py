@@ -83,32 +83,54 @@ def interpolate(pos, mx, array):
     return F(a * fast_powf(F(b / a), F(scaled - F(idx))))
 
 
+def _fast_powf_arrays(base, exponent):
+    """fast_powf on float32 arrays: the steps of fast_log2f / fast_pow2f above, one rounding per operation."""
+    p = [-1.8503833400518310E-06, 1.4287160470083755E+00, 7.4245873327820566E-01]
+    q = [9.9032814277590719E-01, 1.0096718572241148E+00, 1.7409343003366853E-01]
+    bits = np.ascontiguousarray(base, F).view(np.int32)
+    exp_shifted = (bits - np.int32(0x3f2aaaab)) >> 23
+    mantissa = (bits - (exp_shifted << 23)).view(F)
+    x = _eval_rational(mantissa - F(1.0), p, q) + exp_shifted.astype(F)
+    x = x * np.asarray(exponent, F)
+    floorx = np.floor(x)
+    exp = ((floorx.astype(np.int32) + np.int32(127)) << 23).view(F)
+    frac = x - floorx
+    num = frac + F(1.01749063e+01)
+    num = num * frac + F(4.88687798e+01)
+    num = num * frac + F(9.85506591e+01)
+    num = num * exp
+    den = frac * F(2.10242958e-01) + F(-2.22328856e-02)
+    den = den * frac + F(-1.94414990e+01)
+    den = den * frac + F(9.85506633e+01)
+    return num / den
+
+
 def get_quant_weights(rows, cols, distance_bands, num_bands):
-    """quant_weights.cc:129-160: out[c][y][x] for a cols x rows transform from per-channel distance bands."""
+    """quant_weights.cc:129-160: out[c][y][x] for a cols x rows transform from per-channel distance bands (all positions of
+    a channel at once: the 256x256 table has 65536)."""
     out = np.zeros((3, rows, cols), F)
+    scale = F(F(num_bands - 1) / F(F(1.41421356237309504880) + F(1e-6)))
+    rcpcol = F(scale / F(cols - 1))
+    rcprow = F(scale / F(rows - 1))
+    dy = np.arange(rows, dtype=F) * rcprow
+    dx = np.arange(cols, dtype=F) * rcpcol
+    dist = np.sqrt((dx * dx)[None, :] + (dy * dy)[:, None])  # (MulAdd in the reference: one rounding less, far below the bar)
+    assert dist.dtype == F
+    idx = dist.astype(np.int64)
+    frac = dist - idx.astype(F)
     for c in range(3):
         bands = [F(distance_bands[c][0])]
         assert bands[0] >= 1e-8
         for i in range(1, num_bands):
             bands.append(F(bands[-1] * mult(distance_bands[c][i])))
             assert bands[-1] >= 1e-8
-        scale = F(F(num_bands - 1) / F(F(1.41421356237309504880) + F(1e-6)))
-        rcpcol = F(scale / F(cols - 1))
-        rcprow = F(scale / F(rows - 1))
-        for y in range(rows):
-            dy = F(F(y) * rcprow)
-            dy2 = F(dy * dy)
-            for x in range(cols):
-                dx = F(F(x) * rcpcol)
-                dist = F(np.sqrt(F(F(dx * dx) + dy2)))  # (MulAdd in the reference: one rounding less, far below the bar)
-                if num_bands == 1:
-                    w = bands[0]
-                else:
-                    idx = int(dist)
-                    frac = F(dist - F(idx))
-                    a, b = bands[idx], bands[idx + 1]
-                    w = F(a * fast_powf(F(b / a), frac))
-                out[c, y, x] = w
+        if num_bands == 1:
+            out[c] = bands[0]
+        else:
+            assert idx.max() + 1 < num_bands
+            b = np.asarray(bands, F)
+            lo, hi = b[idx], b[idx + 1]
+            out[c] = lo * _fast_powf_arrays(hi / lo, frac)
     return out
 
 

@@ -838,7 +838,8 @@ def test_idct_basis_functions_gpu(built, strategy):
     """Every coefficient position of every DCT-family strategy, one per varblock: the block the transform kernels produce
     must be that position's float64 basis function (lib/jxl/dct_for_test.h:23-94) within the reference's per-basis-vector
     bar 1e-7 * N (dct_test.cc:191-216). Covers k_idct_fast (8..64) and k_dct_big (128 / 256 class),
-    the scan-order coefficient layout and the coefficient orders, against a closed form instead of the oracle."""
+    the scan-order coefficient layout and the coefficient orders, against a closed form instead of the oracle.
+    k_special, dequantisation, the bias, chroma from luma and the corner from DC are held by test_gpu_inverse_f64.py."""
     from test_oracle import basis_stream, check_basis_planes
     J = built
     data, blocks, shape = basis_stream(J, strategy)
