@@ -609,6 +609,51 @@ typedef struct {
 } JxlHipEncTokDesc;
 int jxlhip_enc_token_counts(JxlHipContext* ctx, const JxlHipEncTokDesc* desc, uint32_t* totals);
 int jxlhip_enc_tokens(JxlHipContext* ctx, const uint32_t* bases, uint32_t* tokens, size_t capacity);
+/* Entropy coding of the resident tokens (those of the last jxlhip_enc_tokens, which stay on the device: with tokens = NULL
+ * that call copies nothing to the host and `capacity` only bounds the ranges) - csrc/hip/jxl_hip_enc.h, "entropy coding".
+ * The host keeps what is small and serial (clustering, normalisation, alias tables, headers); the device counts and writes.
+ *
+ * jxlhip_enc_histograms: counts[num_ctx][256] receives how often every hybrid-uint symbol (split_exp / msb_in_token /
+ * lsb_in_token as in a coded HybridUintConfig, dec_ans.h:64-98) occurs in every context, *max_token the largest symbol.
+ * A symbol >= 256 is not counted and makes the call return JXLHIP_ERR_INVALID_ARGUMENT (*max_token then still says which),
+ * a token context >= num_ctx likewise.
+ *
+ * jxlhip_enc_ans_sizes rANS-codes every group's tokens backwards from the final state (ans_params.h: 0x13 << 16) with the
+ * caller's code and returns each group's exact length in bits, bit_counts[groups]; jxlhip_enc_ans_write then places group g's
+ * bit string (LSB first; the unused bits of its last byte zero) at out[byte_bases[g]], ceil(bit_counts[g] / 8) bytes:
+ *   prefix_count[g] (<= 8) bits of prefix_value[g], the 32-bit state, then per token in order the 16-bit chunk it flushed
+ *   (if any) and its extra bits: what follows an AC group's histogram selector in the stream (dec_group.cc:594-610).
+ * The code: ctx_map[num_ctx] < num_clusters (<= 256); per cluster the frequencies freq[cluster][256] (summing to 4096; 0 =
+ * the symbol has no code: a token that needs it makes the call fail, nothing is written for it), rev_start[cluster][256]
+ * (the running sum of the frequencies) and rev[cluster][4096], the slot of (symbol, offset) at rev_start + offset: the
+ * inverse of the decoder's alias table (ans_common.h:102-142). Every entry is validated at the call.
+ * All three synchronous, on the context's stream. */
+typedef struct {
+  uint32_t split_exp, msb_in_token, lsb_in_token;
+  uint32_t num_ctx;
+} JxlHipEncHistDesc;
+typedef struct {
+  uint32_t split_exp, msb_in_token, lsb_in_token;
+  uint32_t num_ctx;
+  const uint8_t* ctx_map;
+  uint32_t num_clusters, log_alpha;
+  const uint16_t* freq;
+  const uint16_t* rev_start;
+  const uint16_t* rev;
+  const uint8_t* prefix_count;
+  const uint8_t* prefix_value;
+} JxlHipEncAnsDesc;
+int jxlhip_enc_histograms(JxlHipContext* ctx, const JxlHipEncHistDesc* desc, uint32_t* counts, uint32_t* max_token);
+int jxlhip_enc_ans_sizes(JxlHipContext* ctx, const JxlHipEncAnsDesc* desc, uint32_t* bit_counts);
+int jxlhip_enc_ans_write(JxlHipContext* ctx, const uint64_t* byte_bases, uint8_t* out, size_t capacity);
+/* Test access: makes tokens[2 * n] ({context, value} pairs) the resident tokens, as one group, and runs the two calls above
+ * on them (prefix_count / prefix_value: one entry); out receives ceil(*bits / 8) bytes. jxlhip_enc_histograms then counts
+ * the same tokens. */
+int jxlhip_debug_ans_write(JxlHipContext* ctx, const uint32_t* tokens, size_t n, const JxlHipEncAnsDesc* desc, uint8_t* out, size_t capacity,
+                           uint64_t* bits);
+/* Kernel time of the last jxlhip_enc_histograms (ms[0]) and of the last jxlhip_enc_ans_sizes + jxlhip_enc_ans_write (ms[1]),
+ * milliseconds (HIP events around the launches, copies excluded); 0 for a pass that has not run. */
+int jxlhip_enc_entropy_last_ms(JxlHipContext* ctx, float* ms);
 /* Measurement: runs the kernel sequence of the last jxlhip_enc_forward `times` more times on its input, which is still
  * resident on the device (no copies); jxlhip_enc_last_ms then gives the time of all `times` passes. Synchronous. */
 int jxlhip_enc_forward_rerun(JxlHipContext* ctx, uint32_t times);

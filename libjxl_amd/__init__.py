@@ -293,6 +293,41 @@ class HipContext:
         _check(L.jxlhip_enc_last_transform_ms(self._h, ctypes.byref(b)), "jxlhip_enc_last_transform_ms")
         return a.value, b.value
 
+    def debug_ans_write(self, tokens, tables, capacity=None):
+        """Test access: rANS-codes `tokens` ((n, 2) uint32 {context, value} pairs) as one section with the device's entropy
+        kernels and the code `tables` (an AnsTables). Returns (the bit string as bytes, its length in bits); `capacity`
+        bytes of room for it (default: enough)."""
+        L = lib()
+        L.jxlhip_debug_ans_write.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(EncAnsDesc), ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
+        tokens = np.ascontiguousarray(tokens, np.uint32).reshape(-1, 2)
+        cap = 16 + 8 * len(tokens) if capacity is None else int(capacity)
+        out = np.zeros(max(1, cap), np.uint8)
+        bits = ctypes.c_uint64()
+        d = tables.desc()
+        _check(L.jxlhip_debug_ans_write(self._h, tokens.ctypes.data, len(tokens), ctypes.byref(d), out.ctypes.data, cap, ctypes.byref(bits)),
+               "jxlhip_debug_ans_write")
+        return out[:(bits.value + 7) // 8].tobytes(), int(bits.value)
+
+    def enc_histograms(self, num_ctx, cfg=(4, 2, 0)):
+        """Symbol counts of the resident tokens (the last device tokenisation, or debug_ans_write's): ((num_ctx, 256) uint32,
+        the largest symbol)."""
+        L = lib()
+        L.jxlhip_enc_histograms.argtypes = [ctypes.c_void_p, ctypes.POINTER(EncHistDesc), ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        counts = np.zeros((num_ctx, 256), np.uint32)
+        mx = ctypes.c_uint32()
+        d = EncHistDesc(cfg[0], cfg[1], cfg[2], num_ctx)
+        _check(L.jxlhip_enc_histograms(self._h, ctypes.byref(d), counts.ctypes.data, ctypes.byref(mx)), "jxlhip_enc_histograms")
+        return counts, int(mx.value)
+
+    def enc_entropy_ms(self):
+        """Kernel milliseconds of the last histogram pass and of the last rANS sizes + write passes on this context."""
+        L = lib()
+        L.jxlhip_enc_entropy_last_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+        ms = (ctypes.c_float * 2)()
+        _check(L.jxlhip_enc_entropy_last_ms(self._h, ms), "jxlhip_enc_entropy_last_ms")
+        return float(ms[0]), float(ms[1])
+
     def upload_modular(self, mframe):
         _check(lib().jxlamd_modframe_upload(mframe._h, self._h), "jxlamd_modframe_upload")
         self.frame_info = dict(mframe.info)
@@ -464,6 +499,52 @@ class EncParams(ctypes.Structure):
                 ("custom_cmap", ctypes.c_int32), ("custom_lf", ctypes.c_int32), ("ac_code_mode", ctypes.c_int32),
                 ("noise", ctypes.c_int32), ("cfl_fit", ctypes.c_int32), ("color_transform", ctypes.c_int32), ("raw_quant", ctypes.c_int32),
                 ("chroma_subsampling", ctypes.c_int32), ("ec_upsampling", ctypes.c_int32)]
+
+
+class EncHistDesc(ctypes.Structure):  # JxlHipEncHistDesc
+    _fields_ = [("split_exp", ctypes.c_uint32), ("msb_in_token", ctypes.c_uint32), ("lsb_in_token", ctypes.c_uint32), ("num_ctx", ctypes.c_uint32)]
+
+
+class EncAnsDesc(ctypes.Structure):  # JxlHipEncAnsDesc
+    _fields_ = [("split_exp", ctypes.c_uint32), ("msb_in_token", ctypes.c_uint32), ("lsb_in_token", ctypes.c_uint32), ("num_ctx", ctypes.c_uint32),
+                ("ctx_map", ctypes.c_void_p), ("num_clusters", ctypes.c_uint32), ("log_alpha", ctypes.c_uint32), ("freq", ctypes.c_void_p),
+                ("rev_start", ctypes.c_void_p), ("rev", ctypes.c_void_p), ("prefix_count", ctypes.c_void_p), ("prefix_value", ctypes.c_void_p)]
+
+
+class AnsTables:
+    """An ANS code in the flat form the entropy entry points take: ctx_map (num_ctx,) uint8, freq and rev_start
+    (clusters, 256) uint16, rev (clusters, 4096) uint16, log_alpha, the hybrid-uint configuration (split_exp, msb, lsb) and
+    the prefix (bit count, value) written ahead of the coder state."""
+
+    def __init__(self, ctx_map, freq, rev_start, rev, log_alpha, cfg=(4, 2, 0), prefix=(0, 0)):
+        self.ctx_map = np.ascontiguousarray(ctx_map, np.uint8)
+        self.freq = np.ascontiguousarray(freq, np.uint16).reshape(-1, 256)
+        self.rev_start = np.ascontiguousarray(rev_start, np.uint16).reshape(-1, 256)
+        self.rev = np.ascontiguousarray(rev, np.uint16).reshape(-1, 4096)
+        self.log_alpha, self.cfg = int(log_alpha), tuple(cfg)
+        self.prefix = (np.array([prefix[0]], np.uint8), np.array([prefix[1]], np.uint8))
+
+    def desc(self):
+        return EncAnsDesc(self.cfg[0], self.cfg[1], self.cfg[2], len(self.ctx_map), self.ctx_map.ctypes.data, len(self.freq), self.log_alpha,
+                          self.freq.ctypes.data, self.rev_start.ctypes.data, self.rev.ctypes.data, self.prefix[0].ctypes.data,
+                          self.prefix[1].ctypes.data)
+
+
+def ans_write_tokens(tokens, tables, capacity=None):
+    """The host rANS writer (jxlenc_ans_write_tokens) on (n, 2) uint32 {context, value} pairs and an AnsTables code:
+    (the bit string as bytes, its length in bits)."""
+    E = _enc_lib()
+    E.jxlenc_ans_write_tokens.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(EncAnsDesc), ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_uint64)]
+    tokens = np.ascontiguousarray(tokens, np.uint32).reshape(-1, 2)
+    cap = 16 + 8 * len(tokens) if capacity is None else int(capacity)
+    out = np.zeros(max(1, cap), np.uint8)
+    bits = ctypes.c_uint64()
+    d = tables.desc()
+    r = E.jxlenc_ans_write_tokens(tokens.ctypes.data, len(tokens), ctypes.byref(d), out.ctypes.data, cap, ctypes.byref(bits))
+    if r:
+        raise JxlAmdError("jxlenc_ans_write_tokens failed: %d" % r)
+    return out[:(bits.value + 7) // 8].tobytes(), int(bits.value)
 
 
 def _enc_lib():
@@ -803,11 +884,47 @@ def encode_rgb8(img, **kw):
     return _finish(E, r, out, n, "jxlenc_encode_rgb8")
 
 
-def encode_rgb8_gpu(img, ctx, timings=None, device_tokens=False, **kw):
+def _forward_entropy(E, img, p, fns, handle, secs):
+    pp = ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))
+    E.jxlenc_encode_rgb8_forward_entropy.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams)] + \
+        [ctypes.c_void_p] * 7 + [pp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_double)]
+    out, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_size_t()
+    r = E.jxlenc_encode_rgb8_forward_entropy(img.tobytes(), img.shape[1], img.shape[0], ctypes.byref(p),
+                                             *([ctypes.cast(f, ctypes.c_void_p) for f in fns] + [handle, ctypes.byref(out), ctypes.byref(n), secs]))
+    return _finish(E, r, out, n, "jxlenc_encode_rgb8_forward_entropy")
+
+
+def encode_rgb8_hooks_cpu(img, timings=None, **kw):
+    """The route of encode_rgb8_gpu(device_entropy=True) with CPU doubles behind every hook (forward, tokens, histograms,
+    rANS sizes / write): the plumbing of that route on a machine without a GPU. `timings` receives device_tokens and
+    device_entropy as there."""
+    E = _enc_lib()
+    E.jxlenc_cpu_ctx_new.restype = ctypes.c_void_p
+    E.jxlenc_cpu_ctx_free.argtypes = [ctypes.c_void_p]
+    img = np.ascontiguousarray(img, np.uint8)
+    p = _params(**kw)
+    secs = (ctypes.c_double * 4)()
+    h = E.jxlenc_cpu_ctx_new()
+    try:
+        data = _forward_entropy(E, img, p, [E.jxlenc_cpu_forward, E.jxlenc_cpu_token_counts, E.jxlenc_cpu_tokens, E.jxlenc_cpu_histograms,
+                                            E.jxlenc_cpu_ans_sizes, E.jxlenc_cpu_ans_write], h, secs)
+    finally:
+        E.jxlenc_cpu_ctx_free(h)
+    if timings is not None:
+        timings.update(forward_s=secs[0], assemble_s=secs[1], device_tokens=int(secs[2]), device_entropy=int(secs[3]))
+    return data
+
+
+def encode_rgb8_gpu(img, ctx, timings=None, device_tokens=False, device_entropy=False, **kw):
     """VarDCT-encodes an RGB8 image with the pixel-domain half (colour, sharpening, transform selection, forward DCT,
     quantisation) on the GPU (jxlhip_enc_forward on `ctx`) and entropy coding / headers on the host. `timings` (a dict)
     receives forward_s (the call, copies included), assemble_s and kernels_ms (HIP events around the launches).
-    device_tokens: the coefficients are tokenised on the device too (jxlhip_enc_tokens) and never copied to the host."""
+    device_tokens: the coefficients are tokenised on the device too (jxlhip_enc_tokens) and never copied to the host.
+    device_entropy (implies device_tokens): the tokens are counted and rANS-coded there as well (jxlhip_enc_histograms,
+    jxlhip_enc_ans_sizes / _write): only the counts and the coded AC sections come to the host, which clusters, normalises
+    and writes the headers. Prefix codes, LZ77, several passes and coded orders / block contexts fall back to the host
+    coder. `timings` then also receives device_entropy (tokens coded on the device, 0 after that fallback) and
+    entropy_kernels_ms (the histogram, sizes and write kernels). The stream is the same bytes in all three forms."""
     E, L = _enc_lib(), lib()
     pp = ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))
     E.jxlenc_encode_rgb8_forward.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams), ctypes.c_void_p,
@@ -816,8 +933,17 @@ def encode_rgb8_gpu(img, ctx, timings=None, device_tokens=False, **kw):
     img = np.ascontiguousarray(img, np.uint8)
     p = _params(**kw)
     out, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_size_t()
-    secs = (ctypes.c_double * 3)()
+    secs = (ctypes.c_double * 4)()
     fn = ctypes.cast(L.jxlhip_enc_forward, ctypes.c_void_p)
+    if device_entropy:
+        data = _forward_entropy(E, img, p, [L.jxlhip_enc_forward, L.jxlhip_enc_token_counts, L.jxlhip_enc_tokens, L.jxlhip_enc_histograms,
+                                            L.jxlhip_enc_ans_sizes, L.jxlhip_enc_ans_write], ctx._h, secs)
+        if timings is not None:
+            ms = ctypes.c_float()
+            _check(L.jxlhip_enc_last_ms(ctx._h, ctypes.byref(ms)), "jxlhip_enc_last_ms")
+            timings.update(forward_s=secs[0], assemble_s=secs[1], kernels_ms=ms.value, device_tokens=int(secs[2]), device_entropy=int(secs[3]),
+                           entropy_kernels_ms=sum(ctx.enc_entropy_ms()) if secs[3] else 0.0)
+        return data
     if device_tokens:
         E.jxlenc_encode_rgb8_forward_tokens.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams)] + \
             [ctypes.c_void_p] * 4 + [pp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_double)]

@@ -271,8 +271,7 @@ static double NowSeconds() {
 static void BuildPrefixCodes(EncCode* code, const std::vector<std::vector<double>>& csum);
 
 // mode: bit 0 = prefix codes instead of ANS, bit 1 = the streams carry LZ77 tokens (num_ctx then includes the distance context)
-static void BuildCode(const std::vector<const std::vector<Token>*>& streams, size_t num_ctx, size_t max_clusters,
-                      jxh::HybridCfg cfg, EncCode* code, int mode = 0) {
+static void InitCode(size_t num_ctx, jxh::HybridCfg cfg, int mode, EncCode* code) {
   code->num_ctx = num_ctx;
   code->cfg = cfg;
   code->use_prefix = (mode & 1) != 0;
@@ -280,6 +279,14 @@ static void BuildCode(const std::vector<const std::vector<Token>*>& streams, siz
   code->lz_len_cfg.split_exp = 4;
   code->lz_len_cfg.split_token = 16;
   code->lz_len_cfg.msb = code->lz_len_cfg.lsb = 0;
+}
+
+// The first half of BuildCode: how often every symbol occurs in every context (hist[ctx] reaches as far as the context's
+// largest symbol), and the largest symbol of all.
+static void CountSymbols(const std::vector<const std::vector<Token>*>& streams, size_t num_ctx, const EncCode& cfgs,
+                         std::vector<std::vector<uint32_t>>* hist_out, uint32_t* max_tok_out) {
+  const jxh::HybridCfg cfg = cfgs.cfg;
+  const EncCode* const code = &cfgs;
   uint32_t max_tok = 0;
   std::vector<std::vector<uint32_t>> hist(num_ctx);
   auto count = [&](const std::vector<Token>& st, std::vector<std::vector<uint32_t>>& into, uint32_t* mx) {
@@ -313,6 +320,14 @@ static void BuildCode(const std::vector<const std::vector<Token>*>& streams, siz
   } else {
     for (const auto* st : streams) count(*st, hist, &max_tok);
   }
+  hist_out->swap(hist);
+  *max_tok_out = max_tok;
+}
+
+// The second half: clustering, normalisation and the reverse maps (or prefix codes) from the counts. A count that is zero
+// contributes nothing anywhere below, so counts that reach further than a context's largest symbol give the same code.
+static void BuildCodeFromCounts(const std::vector<std::vector<uint32_t>>& hist, uint32_t max_tok, size_t max_clusters, EncCode* code) {
+  const size_t num_ctx = code->num_ctx;
   code->log_alpha = code->use_prefix ? 15 : std::max(5, CeilLog2(max_tok + 1));
   if (!code->use_prefix && code->log_alpha > 8) abort();
   const size_t A = max_tok + 1;
@@ -373,6 +388,15 @@ static void BuildCode(const std::vector<const std::vector<Token>*>& streams, siz
     code->norm[k] = Normalize(h);
   }
   BuildReverseMaps(code);
+}
+
+static void BuildCode(const std::vector<const std::vector<Token>*>& streams, size_t num_ctx, size_t max_clusters,
+                      jxh::HybridCfg cfg, EncCode* code, int mode = 0) {
+  InitCode(num_ctx, cfg, mode, code);
+  std::vector<std::vector<uint32_t>> hist;
+  uint32_t max_tok = 0;
+  CountSymbols(streams, num_ctx, *code, &hist, &max_tok);
+  BuildCodeFromCounts(hist, max_tok, max_clusters, code);
 }
 
 // rANS-encodes tokens (all contexts via code->ctx_map); writes the 32-bit initial state first.
@@ -834,6 +858,14 @@ struct FrameModel {
   // (context, value) pairs in bitstream order, group g at dev_tokens[dev_token_base[g] .. + dev_token_count[g])
   std::vector<uint64_t> dev_tokens;  // {context, value} pairs of uint32
   std::vector<uint32_t> dev_token_base, dev_token_count;
+  // ... or the tokens never came either: the device counted and rANS-coded them (ForwardHook::histograms / ans_sizes /
+  // ans_write). Then `dev_tokens` is empty, dev_ac_code is the AC code the host built from the device's counts, and group
+  // g's part of its section (histogram selector, coder state, chunks and extra bits) is the dev_ac_nbits[g] bits at
+  // dev_ac_bits[dev_ac_base[g]].
+  std::shared_ptr<EncCode> dev_ac_code;
+  std::vector<uint8_t> dev_ac_bits;
+  std::vector<uint64_t> dev_ac_base;
+  std::vector<uint32_t> dev_ac_nbits;
   uint32_t global_scale, quant_dc;
   int epf_iters, gab;
   uint64_t flags;
@@ -1256,6 +1288,65 @@ static void WriteSizeDim(BitWriter& bw, uint32_t v) {
   WriteU32Sel(bw, v, bits, offs);
 }
 
+// The AC tokens of one group in one pass (enc_entropy_coder.cc:153-255 TokenizeCoefficients): per varblock in raster order
+// and channel Y, X, B the non-zero count, then the coefficients up to the last non-zero one. scan: [(pass * 13 + order
+// bucket) * 3 + c] coefficient orders; dc_bucket(block index): the block's DC context.
+template <typename DcBucket>
+static void TokenizeAcGroup(const FrameModel& f, size_t g, size_t xg, size_t pass, size_t num_passes, const jxh::BlockCtxMap& bctx,
+                            const DcBucket& dc_bucket, size_t num_hist, size_t nctx, const std::vector<std::vector<uint32_t>>& scan,
+                            std::vector<Token>* tokens) {
+  // the part of a coefficient this pass carries (the decoder adds value << shift over the passes, dec_group.cc:335-338)
+  auto part = [&](int32_t v) -> int32_t {
+    const int sh = int(num_passes - 1 - pass);  // this pass's shift; the passes before carried v >> (sh + 1)
+    return pass == 0 ? (v >> sh) : (v >> sh) - ((v >> (sh + 1)) << 1);
+  };
+  const size_t bx0 = (g % xg) * 32, by0 = (g / xg) * 32;
+  const size_t gw = std::min<size_t>(32, f.xb - bx0), gh = std::min<size_t>(32, f.yb - by0);
+  std::vector<int32_t> nzmap(3 * 1024, 0);
+  std::vector<Token>& out_t = *tokens;
+  size_t offset = 0;
+  for (size_t by_ = 0; by_ < gh; by_++)
+    for (size_t bx_ = 0; bx_ < gw; bx_++) {
+      const size_t bx = bx_, by = by_;
+      uint8_t a = f.acs[(by0 + by) * f.xb + bx0 + bx];
+      if (!(a & 1)) continue;
+      const int st = a >> 1;
+      const size_t cx = jxh::kCoveredX[st], cy = jxh::kCoveredY[st], log2c = jxh::kLog2Covered[st];
+      const size_t covered = size_t(1) << log2c, size = covered * 64;
+      const int ord = jxh::kStrategyOrder[st];
+      const uint32_t qf = uint32_t(f.qf[(by0 + by) * f.xb + bx0 + bx]);
+      static const int kOrder[3] = {1, 0, 2};
+      for (int ci = 0; ci < 3; ci++) {
+        const int c = kOrder[ci];
+        if (!f.Present(c, bx0 + bx, by0 + by)) continue;  // (dec_group.cc:572-578: only the blocks a subsampled channel has)
+        const int32_t* q = f.GroupCoeffs(g) + size_t(c) * 65536 + offset;
+        int32_t* nzc = nzmap.data() + c * 1024;
+        const size_t bx = bx_ >> f.hs[c], by = by_ >> f.vs[c];
+        const int32_t* top = by ? nzc + (by - 1) * 32 : nullptr;
+        int32_t* cur = nzc + by * 32;
+        int32_t pred = bx == 0 ? (top ? top[0] : 32) : (!top ? cur[bx - 1] : (top[bx] + cur[bx - 1] + 1) / 2);
+        const uint32_t* order = scan[(pass * 13 + ord) * 3 + c].data();
+        size_t nz = 0;
+        for (size_t k = covered; k < size; k++) nz += part(q[order[k]]) != 0;
+        size_t bc = bctx.Context(dc_bucket((by0 + by_) * f.xb + bx0 + bx_), qf, ord, c);
+        const size_t hist_off = (g % num_hist) * nctx;  // this group's histogram set
+        out_t.push_back({uint32_t(hist_off + bctx.NonZeroContext(uint32_t(pred), bc)), uint32_t(nz)});
+        for (size_t y = 0; y < cy; y++)
+          for (size_t x = 0; x < cx; x++) cur[bx + x + y * 32] = int32_t((nz + covered - 1) >> log2c);
+        const size_t hoff = bctx.ZeroDensityOffset(bc);
+        size_t prev = nz > size / 16 ? 0 : 1, left = nz;
+        for (size_t k = covered; k < size && left != 0; k++) {
+          size_t ctx = hist_off + hoff + jxh::ZeroDensityContext(left, k, covered, log2c, prev);
+          int32_t v = part(q[order[k]]);
+          out_t.push_back({uint32_t(ctx), PackSigned(v)});
+          prev = v != 0;
+          left -= prev;
+        }
+      }
+      offset += size;
+    }
+}
+
 static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>* out) {
   const size_t xg = DivCeil(f.xs, 256), yg = DivCeil(f.ys, 256), num_groups = xg * yg;
   const size_t xdg = DivCeil(f.xb, 256), ydg = DivCeil(f.yb, 256), ndc = xdg * ydg;
@@ -1454,64 +1545,20 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
 #pragma omp parallel for schedule(dynamic)
   for (size_t pg = 0; pg < num_groups * num_passes; pg++) {
     const size_t g = pg % num_groups, pass = pg / num_groups;
+    if (f.dev_ac_code) continue;  // counted and coded on the device: no tokens here
     if (!f.dev_tokens.empty()) {  // tokenised on the device: the same pairs, already in order
       const Token* t = reinterpret_cast<const Token*>(f.dev_tokens.data()) + f.dev_token_base[g];
       ac_tokens[pg].assign(t, t + f.dev_token_count[g]);
       continue;
     }
-    // the part of a coefficient this pass carries (the decoder adds value << shift over the passes, dec_group.cc:335-338)
-    auto part = [&](int32_t v) -> int32_t {
-      const int sh = int(num_passes - 1 - pass);  // this pass's shift; the passes before carried v >> (sh + 1)
-      return pass == 0 ? (v >> sh) : (v >> sh) - ((v >> (sh + 1)) << 1);
-    };
-    const size_t bx0 = (g % xg) * 32, by0 = (g / xg) * 32;
-    const size_t gw = std::min<size_t>(32, f.xb - bx0), gh = std::min<size_t>(32, f.yb - by0);
-    std::vector<int32_t> nzmap(3 * 1024, 0);
-    std::vector<Token>& out_t = ac_tokens[pg];
-    size_t offset = 0;
-    for (size_t by_ = 0; by_ < gh; by_++)
-      for (size_t bx_ = 0; bx_ < gw; bx_++) {
-        const size_t bx = bx_, by = by_;
-        uint8_t a = f.acs[(by0 + by) * f.xb + bx0 + bx];
-        if (!(a & 1)) continue;
-        const int st = a >> 1;
-        const size_t cx = jxh::kCoveredX[st], cy = jxh::kCoveredY[st], log2c = jxh::kLog2Covered[st];
-        const size_t covered = size_t(1) << log2c, size = covered * 64;
-        const int ord = jxh::kStrategyOrder[st];
-        const uint32_t qf = uint32_t(f.qf[(by0 + by) * f.xb + bx0 + bx]);
-        static const int kOrder[3] = {1, 0, 2};
-        for (int ci = 0; ci < 3; ci++) {
-          const int c = kOrder[ci];
-          if (!f.Present(c, bx0 + bx, by0 + by)) continue;  // (dec_group.cc:572-578: only the blocks a subsampled channel has)
-          const int32_t* q = f.GroupCoeffs(g) + size_t(c) * 65536 + offset;
-          int32_t* nzc = nzmap.data() + c * 1024;
-          const size_t bx = bx_ >> f.hs[c], by = by_ >> f.vs[c];
-          const int32_t* top = by ? nzc + (by - 1) * 32 : nullptr;
-          int32_t* cur = nzc + by * 32;
-          int32_t pred = bx == 0 ? (top ? top[0] : 32) : (!top ? cur[bx - 1] : (top[bx] + cur[bx - 1] + 1) / 2);
-          const uint32_t* order = scan[(pass * 13 + ord) * 3 + c].data();
-          size_t nz = 0;
-          for (size_t k = covered; k < size; k++) nz += part(q[order[k]]) != 0;
-          size_t bc = bctx.Context(dc_bucket((by0 + by_) * f.xb + bx0 + bx_), qf, ord, c);
-          const size_t hist_off = (g % num_hist) * nctx;  // this group's histogram set
-          out_t.push_back({uint32_t(hist_off + bctx.NonZeroContext(uint32_t(pred), bc)), uint32_t(nz)});
-          for (size_t y = 0; y < cy; y++)
-            for (size_t x = 0; x < cx; x++) cur[bx + x + y * 32] = int32_t((nz + covered - 1) >> log2c);
-          const size_t hoff = bctx.ZeroDensityOffset(bc);
-          size_t prev = nz > size / 16 ? 0 : 1, left = nz;
-          for (size_t k = covered; k < size && left != 0; k++) {
-            size_t ctx = hist_off + hoff + jxh::ZeroDensityContext(left, k, covered, log2c, prev);
-            int32_t v = part(q[order[k]]);
-            out_t.push_back({uint32_t(ctx), PackSigned(v)});
-            prev = v != 0;
-            left -= prev;
-          }
-        }
-        offset += size;
-      }
+    TokenizeAcGroup(f, g, xg, pass, num_passes, bctx, dc_bucket, num_hist, nctx, scan, &ac_tokens[pg]);
   }
   std::vector<EncCode> ac_codes(num_passes);
   for (size_t pass = 0; pass < num_passes; pass++) {
+    if (f.dev_ac_code) {  // (one pass, plain ANS: EncodeImage) built there from the device's counts
+      ac_codes[pass] = *f.dev_ac_code;
+      continue;
+    }
     std::vector<const std::vector<Token>*> all;
     for (size_t g = 0; g < num_groups; g++) all.push_back(&ac_tokens[pass * num_groups + g]);
     const int mode = p.ac_code_mode & 3;  // bit 0: prefix codes, bit 1: LZ77
@@ -1625,6 +1672,10 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
   };
   auto write_ac_group = [&](BitWriter& bw, size_t pg) {
     const size_t g = pg % num_groups;
+    if (f.dev_ac_code) {  // the device's bit string: selector, coder state, chunks and extra bits
+      bw.AppendBits(f.dev_ac_bits.data() + f.dev_ac_base[g], f.dev_ac_nbits[g]);
+      return;
+    }
     bw.Write(CeilLog2(num_hist), uint32_t(g % num_hist));  // histogram selector (dec_group.cc:594-610)
     WriteTokens(bw, ac_tokens[pg].data(), ac_tokens[pg].size(), ac_codes[pg / num_groups]);
     if (!alpha_group_tokens.empty() && alpha_group_present[g] && pg / num_groups == num_passes - 1) {  // Modular data of the group, behind the coefficients
@@ -1823,6 +1874,98 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
 }
 
 // ---------------------------------------------------------------- image mode
+// An ANS code's tables in the flat form the entropy hooks take (JxlHipEncAnsDesc), and back.
+struct AnsTables {
+  std::vector<uint8_t> ctx_map;
+  std::vector<uint16_t> freq, rev_start, rev;
+  uint32_t num_clusters, log_alpha, num_ctx;
+  jxh::HybridCfg cfg;
+  explicit AnsTables(const EncCode& c)
+      : ctx_map(c.ctx_map), freq(c.num_clusters * 256, 0), rev_start(c.num_clusters * 256, 0), rev(c.num_clusters * 4096, 0),
+        num_clusters(uint32_t(c.num_clusters)), log_alpha(uint32_t(c.log_alpha)), num_ctx(uint32_t(c.num_ctx)), cfg(c.cfg) {
+    for (size_t k = 0; k < c.num_clusters; k++) {
+      // (an empty cluster: all of the mass on symbol 0, as BuildReverseMaps has it)
+      if (c.norm[k].empty()) freq[k * 256] = 4096;
+      for (size_t s2 = 0; s2 < c.norm[k].size() && s2 < 256; s2++) {
+        freq[k * 256 + s2] = uint16_t(c.norm[k][s2]);
+        rev_start[k * 256 + s2] = uint16_t(c.rev_start[k][s2]);
+      }
+      std::copy(c.rev[k].begin(), c.rev[k].end(), rev.begin() + k * 4096);
+    }
+  }
+  JxlHipEncAnsDesc Desc(const uint8_t* prefix_count, const uint8_t* prefix_value) const {
+    JxlHipEncAnsDesc d;
+    memset(&d, 0, sizeof(d));
+    d.split_exp = cfg.split_exp;
+    d.msb_in_token = cfg.msb;
+    d.lsb_in_token = cfg.lsb;
+    d.num_ctx = num_ctx;
+    d.ctx_map = ctx_map.data();
+    d.num_clusters = num_clusters;
+    d.log_alpha = log_alpha;
+    d.freq = freq.data();
+    d.rev_start = rev_start.data();
+    d.rev = rev.data();
+    d.prefix_count = prefix_count;
+    d.prefix_value = prefix_value;
+    return d;
+  }
+};
+// The checks every implementation of the entropy hooks makes on a descriptor before it forms an index from it.
+static bool ValidAnsDesc(const JxlHipEncAnsDesc* d) {
+  if (!d || !d->ctx_map || !d->freq || !d->rev_start || !d->rev || !d->num_ctx || !d->num_clusters || d->num_clusters > 256) return false;
+  if (d->log_alpha < 5 || d->log_alpha > 8 || d->split_exp > d->log_alpha || d->msb_in_token + d->lsb_in_token > d->split_exp) return false;
+  for (uint32_t i = 0; i < d->num_ctx; i++)
+    if (d->ctx_map[i] >= d->num_clusters) return false;
+  for (uint32_t k = 0; k < d->num_clusters; k++) {
+    uint32_t sum = 0;
+    for (uint32_t s2 = 0; s2 < 256; s2++) {
+      const uint32_t fr = d->freq[k * 256 + s2];
+      if (fr && (s2 >> d->log_alpha)) return false;
+      if (fr && d->rev_start[k * 256 + s2] != sum) return false;
+      sum += fr;
+      if (sum > 4096) return false;
+    }
+    if (sum != 4096) return false;
+    for (uint32_t i = 0; i < 4096; i++)
+      if (d->rev[k * 4096 + i] >= 4096) return false;
+  }
+  return true;
+}
+// ... and the code WriteTokens takes, from such a descriptor (valid)
+static void CodeFromDesc(const JxlHipEncAnsDesc& d, EncCode* code) {
+  jxh::HybridCfg cfg;
+  cfg.split_exp = d.split_exp;
+  cfg.split_token = 1u << d.split_exp;
+  cfg.msb = d.msb_in_token;
+  cfg.lsb = d.lsb_in_token;
+  InitCode(d.num_ctx, cfg, 0, code);
+  code->ctx_map.assign(d.ctx_map, d.ctx_map + d.num_ctx);
+  code->num_clusters = d.num_clusters;
+  code->log_alpha = int(d.log_alpha);
+  code->norm.assign(d.num_clusters, std::vector<int32_t>(256));
+  code->rev_start.assign(d.num_clusters, std::vector<uint32_t>(257, 0));
+  code->rev.assign(d.num_clusters, std::vector<uint16_t>(4096));
+  for (uint32_t k = 0; k < d.num_clusters; k++) {
+    for (uint32_t s2 = 0; s2 < 256; s2++) {
+      code->norm[k][s2] = d.freq[k * 256 + s2];
+      code->rev_start[k][s2] = d.rev_start[k * 256 + s2];
+    }
+    std::copy(d.rev + k * 4096, d.rev + (k + 1) * 4096, code->rev[k].begin());
+  }
+}
+// Whether WriteTokens can code these tokens with this code: contexts in range, every symbol with probability mass.
+static bool TokensCodable(const Token* tk, size_t n, const EncCode& code) {
+  for (size_t i = 0; i < n; i++) {
+    if (tk[i].ctx >= code.num_ctx) return false;
+    uint32_t tok, nb, bits;
+    HybridEncode(code.cfg, tk[i].value, &tok, &nb, &bits);
+    const auto& norm = code.norm[code.ctx_map[tk[i].ctx]];
+    if (tok >= norm.size() || norm[tok] <= 0) return false;
+  }
+  return true;
+}
+
 static void QuantParams(float distance, FrameModel* f, float* quant_ac) {
   const float kAcQuant = 0.765f, kDcQuant = 1.095924047623553f, kDcMul = 0.3f, kDcQuantPow = 0.83f;
   float target_dc = std::max(0.5f * distance, std::min(distance, kDcMul * std::pow((1.0f / kDcMul) * distance, kDcQuantPow)));
@@ -1848,6 +1991,12 @@ typedef int (*ForwardFn)(void* ctx, const uint8_t* rgb, size_t stride, const Jxl
 // coefficients stay on the device and the host entropy coder starts from the tokens.
 typedef int (*TokenCountsFn)(void* ctx, const JxlHipEncTokDesc* desc, uint32_t* totals);
 typedef int (*TokensFn)(void* ctx, const uint32_t* bases, uint32_t* tokens, size_t capacity);
+// ... and the entropy coding of those tokens (jxlhip_enc_histograms, jxlhip_enc_ans_sizes / jxlhip_enc_ans_write): when all
+// are given the tokens stay on the device too: its counts come up, the host builds the code from them and hands the tables
+// down, and the coded sections come up.
+typedef int (*HistogramsFn)(void* ctx, const JxlHipEncHistDesc* desc, uint32_t* counts, uint32_t* max_token);
+typedef int (*AnsSizesFn)(void* ctx, const JxlHipEncAnsDesc* desc, uint32_t* bit_counts);
+typedef int (*AnsWriteFn)(void* ctx, const uint64_t* byte_bases, uint8_t* out, size_t capacity);
 struct ForwardHook {
   ForwardFn fn;
   void* ctx;
@@ -1855,6 +2004,10 @@ struct ForwardHook {
   TokenCountsFn tok_counts = nullptr;
   TokensFn tok_emit = nullptr;
   uint64_t device_tokens = 0;  // out: how many tokens came from the device (0: the host tokenised)
+  HistogramsFn histograms = nullptr;
+  AnsSizesFn ans_sizes = nullptr;
+  AnsWriteFn ans_write = nullptr;
+  uint64_t device_coded = 0;  // out: how many tokens the device entropy-coded (0: the host coder wrote them)
   // test access: when set, the raw outputs of the forward call are copied here and nothing is assembled
   uint8_t* cap_acs = nullptr;
   int32_t *cap_qf = nullptr, *cap_dc = nullptr, *cap_coeffs = nullptr;
@@ -1968,10 +2121,52 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
         total += f.dev_token_count[g];
       }
       if (total >= (uint64_t(1) << 32)) throw std::runtime_error("token hook: too many tokens");
-      f.dev_tokens.assign(size_t(total) + 1, 0);
-      tr = hook->tok_emit(hook->ctx, f.dev_token_base.data(), reinterpret_cast<uint32_t*>(f.dev_tokens.data()), size_t(total));
+      // device entropy coding: plain ANS only (prefix codes and LZ77 stay with the host coder)
+      const bool dev_ans = hook->histograms && hook->ans_sizes && hook->ans_write && (p.ac_code_mode & 3) == 0 && !alpha;
+      if (!dev_ans) f.dev_tokens.assign(size_t(total) + 1, 0);
+      tr = hook->tok_emit(hook->ctx, f.dev_token_base.data(), dev_ans ? nullptr : reinterpret_cast<uint32_t*>(f.dev_tokens.data()), size_t(total));
       if (tr) throw std::runtime_error("token hook failed (" + std::to_string(tr) + ")");
       hook->device_tokens = total;
+      if (dev_ans) {
+        jxh::HybridCfg cfg420;
+        cfg420.split_exp = 4; cfg420.split_token = 16; cfg420.msb = 2; cfg420.lsb = 0;
+        const size_t num_ctx = size_t(td.num_ctxs) * 495 * td.num_hist;
+        JxlHipEncHistDesc hd = {cfg420.split_exp, cfg420.msb, cfg420.lsb, uint32_t(num_ctx)};
+        std::unique_ptr<uint32_t[]> counts(new uint32_t[num_ctx * 256]);
+        uint32_t max_tok = 0;
+        int er = hook->histograms(hook->ctx, &hd, counts.get(), &max_tok);
+        if (er) throw std::runtime_error("histogram hook failed (" + std::to_string(er) + ")");
+        std::vector<std::vector<uint32_t>> hist(num_ctx);
+        for (size_t c = 0; c < num_ctx; c++) {
+          const uint32_t* row = counts.get() + c * 256;
+          size_t used = 0;
+          for (size_t k = 0; k <= max_tok; k++)
+            if (row[k]) used = k + 1;
+          hist[c].assign(row, row + used);
+        }
+        counts.reset();
+        f.dev_ac_code.reset(new EncCode);
+        EncCode& code = *f.dev_ac_code;
+        InitCode(num_ctx, cfg420, 0, &code);
+        BuildCodeFromCounts(hist, max_tok, p.max_clusters > 0 ? size_t(p.max_clusters) : 64, &code);
+        AnsTables tab(code);
+        std::vector<uint8_t> pc(ng, uint8_t(CeilLog2(td.num_hist))), pv(ng);
+        for (size_t g = 0; g < ng; g++) pv[g] = uint8_t(g % td.num_hist);  // the histogram selector of write_ac_group
+        JxlHipEncAnsDesc ad = tab.Desc(pc.data(), pv.data());
+        f.dev_ac_nbits.assign(ng, 0);
+        er = hook->ans_sizes(hook->ctx, &ad, f.dev_ac_nbits.data());
+        if (er) throw std::runtime_error("ANS hook failed (" + std::to_string(er) + ")");
+        f.dev_ac_base.assign(ng, 0);
+        uint64_t bytes = 0;
+        for (size_t g = 0; g < ng; g++) {
+          f.dev_ac_base[g] = bytes;
+          bytes += (uint64_t(f.dev_ac_nbits[g]) + 7) / 8;
+        }
+        f.dev_ac_bits.assign(size_t(bytes) + 1, 0);
+        er = hook->ans_write(hook->ctx, f.dev_ac_base.data(), f.dev_ac_bits.data(), size_t(bytes));
+        if (er) throw std::runtime_error("ANS hook failed (" + std::to_string(er) + ")");
+        hook->device_coded = total;
+      }
     }
     if (hook->cap_acs) {
       memcpy(hook->cap_acs, f.acs.data(), nb);
@@ -3364,6 +3559,213 @@ int jxlenc_encode_rgb8_forward_tokens(const uint8_t* rgb, uint32_t xs, uint32_t 
     seconds[2] = double(hook.device_tokens);
   }
   return Finish(v, out, n);
+}
+
+// The same with the tokens counted and rANS-coded on the device as well (jxlhip_enc_histograms, jxlhip_enc_ans_sizes,
+// jxlhip_enc_ans_write on the same context): no token comes to the host, only the counts and the coded AC sections do; the host
+// clusters, normalises and writes the headers. Plain ANS in one pass with the default orders and block contexts; anything
+// else takes the route of jxlenc_encode_rgb8_forward_tokens (or _forward). seconds[2]: tokens the device produced,
+// seconds[3]: tokens the device coded (0 after a fallback).
+int jxlenc_encode_rgb8_forward_entropy(const uint8_t* rgb, uint32_t xs, uint32_t ys, const JxlEncParams* p, jxe::ForwardFn forward,
+                                       jxe::TokenCountsFn tok_counts, jxe::TokensFn tok_emit, jxe::HistogramsFn histograms,
+                                       jxe::AnsSizesFn ans_sizes, jxe::AnsWriteFn ans_write, void* ctx, uint8_t** out, size_t* n,
+                                       double* seconds) {
+  jxe::UseThreads();
+  if (!rgb || !xs || !ys || !p || p->distance <= 0 || !forward || !tok_counts || !tok_emit || !histograms || !ans_sizes || !ans_write) return -1;
+  jxe::Params q;
+  memcpy(&q, p, sizeof(q));
+  if (q.upsampling > 1) return -1;
+  std::vector<uint8_t> v;
+  jxe::ForwardHook hook = {forward, ctx, {0, 0}};
+  hook.tok_counts = tok_counts;
+  hook.tok_emit = tok_emit;
+  hook.histograms = histograms;
+  hook.ans_sizes = ans_sizes;
+  hook.ans_write = ans_write;
+  try {
+    jxe::EncodeImage(rgb, xs, ys, q, &v, 0, 0, nullptr, &hook);
+  } catch (...) {
+    return -2;
+  }
+  if (seconds) {
+    seconds[0] = hook.seconds[0];
+    seconds[1] = hook.seconds[1];
+    seconds[2] = double(hook.device_tokens);
+    seconds[3] = double(hook.device_coded);
+  }
+  return Finish(v, out, n);
+}
+
+// The host rANS writer on a caller's tokens ({context, value} pairs) and code (a JxlHipEncAnsDesc, validated like the device
+// entry validates it): prefix bits, the 32-bit state, chunks and extra bits, as one LSB-first bit string of *bits bits in
+// out[capacity]. What jxlhip_debug_ans_write is held to. -1: bad arguments, -3: a token the code cannot code, -4: capacity.
+int jxlenc_ans_write_tokens(const uint32_t* tokens, size_t n, const JxlHipEncAnsDesc* desc, uint8_t* out, size_t capacity, uint64_t* bits) {
+  if ((!tokens && n) || !out || !bits || !jxe::ValidAnsDesc(desc)) return -1;
+  if (desc->prefix_count && (desc->prefix_count[0] > 8 || !desc->prefix_value)) return -1;
+  jxe::EncCode code;
+  jxe::CodeFromDesc(*desc, &code);
+  const jxe::Token* tk = reinterpret_cast<const jxe::Token*>(tokens);
+  if (!jxe::TokensCodable(tk, n, code)) return -3;
+  jxe::BitWriter bw;
+  if (desc->prefix_count) bw.Write(desc->prefix_count[0], desc->prefix_value[0] & ((1u << desc->prefix_count[0]) - 1));
+  jxe::WriteTokens(bw, tk, n, code);
+  *bits = bw.BitPos();
+  if (bw.bytes().size() > capacity) return -4;
+  memcpy(out, bw.bytes().data(), bw.bytes().size());
+  return 0;
+}
+
+// CPU doubles of the token and entropy hooks, so that the whole hook route runs without a GPU: a small context keeps the
+// last forward call's model; the token calls run the host tokeniser on it, the entropy calls CountSymbols' arithmetic and
+// WriteTokens. They test the plumbing (counts -> code, the selector prefix, BitWriter::AppendBits), not a second coder.
+struct JxlEncCpuCtx {
+  jxe::FrameModel f;
+  bool have_model = false, have_tokens = false, resident = false;
+  uint32_t num_hist = 1;
+  std::vector<std::vector<jxe::Token>> tokens;  // per group
+  std::vector<std::vector<uint8_t>> coded;      // per group (jxlenc_cpu_ans_sizes)
+  std::vector<uint32_t> coded_bits;
+};
+JxlEncCpuCtx* jxlenc_cpu_ctx_new(void) { return new JxlEncCpuCtx; }
+void jxlenc_cpu_ctx_free(JxlEncCpuCtx* c) { delete c; }
+
+int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHipEncDesc* d, uint8_t* acs, int32_t* qf, int32_t* dc,
+                       int32_t* coeffs) {
+  JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
+  jxe::UseThreads();
+  if (!c || !rgb || !d || !acs || !qf || !dc || stride < size_t(d->xsize) * 3) return -1;
+  c->have_model = c->have_tokens = c->resident = false;
+  jxe::Params q;
+  memset(&q, 0, sizeof(q));
+  q.distance = d->distance;
+  q.epf_iters = -1;
+  q.gab = int32_t(d->gaborish);
+  q.strategy_mode = int32_t(d->strategy_mode);
+  q.cfl_fit = int32_t(d->cfl_fit);
+  q.seed = 1;
+  std::vector<uint8_t> tight;
+  if (stride != size_t(d->xsize) * 3) {
+    tight.resize(size_t(d->xsize) * d->ysize * 3);
+    for (uint32_t y = 0; y < d->ysize; y++) memcpy(tight.data() + size_t(y) * d->xsize * 3, rgb + y * stride, size_t(d->xsize) * 3);
+    rgb = tight.data();
+  }
+  jxe::FrameModel& f = c->f;
+  try {
+    jxe::EncodeImage(rgb, d->xsize, d->ysize, q, nullptr, 0, 0, nullptr, nullptr, &f);
+  } catch (...) {
+    return -2;
+  }
+  if (f.global_scale != d->global_scale || f.quant_dc != d->quant_dc) return -3;  // the descriptor is not this distance's
+  const size_t nb = f.xb * f.yb;
+  memcpy(acs, f.acs.data(), nb);
+  if (d->ytox) memcpy(d->ytox, f.ytox.data(), f.ytox.size());
+  if (d->ytob) memcpy(d->ytob, f.ytob.data(), f.ytob.size());
+  memcpy(qf, f.qf.data(), nb * 4);
+  for (int ch = 0; ch < 3; ch++) memcpy(dc + ch * nb, f.dc[ch].data(), nb * 4);
+  if (coeffs)
+    for (size_t g = 0; g < f.coeffs.size(); g++) memcpy(coeffs + g * 3 * 65536, f.coeffs[g].data(), size_t(3) * 65536 * 4);
+  c->have_model = true;
+  return 0;
+}
+
+int jxlenc_cpu_token_counts(void* ctx, const JxlHipEncTokDesc* d, uint32_t* totals) {
+  JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
+  if (!c || !d || !totals || !d->num_ctxs || !d->num_hist) return -1;
+  if (!c->have_model) return -5;
+  const jxe::FrameModel& f = c->f;
+  const jxh::BlockCtxMap bctx;  // the default map, the one the descriptor's callers pass
+  if (d->num_ctxs != bctx.num_ctxs || memcmp(d->ctx_map, bctx.ctx_map.data(), sizeof(d->ctx_map)) != 0) return -1;
+  std::vector<std::vector<uint32_t>> scan(13 * 3);
+  for (int s2 = 0; s2 < 27; s2++) {
+    const int ord = jxh::kStrategyOrder[s2];
+    if (!scan[ord * 3].empty()) continue;
+    jxh::NaturalOrder(s2, &scan[ord * 3]);
+    scan[ord * 3 + 1] = scan[ord * 3 + 2] = scan[ord * 3];
+  }
+  const size_t xg = jxe::DivCeil(f.xs, 256), ng = xg * jxe::DivCeil(f.ys, 256);
+  c->tokens.assign(ng, {});
+  c->num_hist = d->num_hist;
+  const auto no_dc_bucket = [](size_t) { return 0; };
+  for (size_t g = 0; g < ng; g++) {
+    jxe::TokenizeAcGroup(f, g, xg, 0, 1, bctx, no_dc_bucket, d->num_hist, bctx.NumACContexts(), scan, &c->tokens[g]);
+    totals[g] = uint32_t(c->tokens[g].size());
+  }
+  c->have_tokens = true;
+  c->resident = false;
+  return 0;
+}
+
+int jxlenc_cpu_tokens(void* ctx, const uint32_t* bases, uint32_t* tokens, size_t capacity) {
+  JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
+  if (!c || !bases) return -1;
+  if (!c->have_tokens) return -5;
+  for (size_t g = 0; g < c->tokens.size(); g++)
+    if (uint64_t(bases[g]) + c->tokens[g].size() > capacity) return -1;
+  if (tokens)
+    for (size_t g = 0; g < c->tokens.size(); g++)
+      if (!c->tokens[g].empty()) memcpy(tokens + size_t(bases[g]) * 2, c->tokens[g].data(), c->tokens[g].size() * sizeof(jxe::Token));
+  c->resident = true;
+  c->coded.clear();
+  return 0;
+}
+
+int jxlenc_cpu_histograms(void* ctx, const JxlHipEncHistDesc* d, uint32_t* counts, uint32_t* max_token) {
+  JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
+  if (!c || !d || !counts || !max_token || !d->num_ctx || d->msb_in_token + d->lsb_in_token > d->split_exp) return -1;
+  if (!c->resident) return -5;
+  jxh::HybridCfg cfg;
+  cfg.split_exp = d->split_exp;
+  cfg.split_token = 1u << d->split_exp;
+  cfg.msb = d->msb_in_token;
+  cfg.lsb = d->lsb_in_token;
+  memset(counts, 0, size_t(d->num_ctx) * 256 * 4);
+  uint32_t mx = 0;
+  bool bad = false;
+  for (const auto& st : c->tokens)
+    for (const jxe::Token& t : st) {
+      uint32_t tok, nb, bits;
+      jxe::HybridEncode(cfg, t.value, &tok, &nb, &bits);
+      mx = std::max(mx, tok);
+      if (t.ctx >= d->num_ctx || tok >= 256) {
+        bad = true;
+        continue;
+      }
+      counts[size_t(t.ctx) * 256 + tok]++;
+    }
+  *max_token = mx;
+  return bad ? -1 : 0;
+}
+
+int jxlenc_cpu_ans_sizes(void* ctx, const JxlHipEncAnsDesc* d, uint32_t* bit_counts) {
+  JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
+  if (!c || !bit_counts || !jxe::ValidAnsDesc(d) || !d->prefix_count || !d->prefix_value) return -1;
+  if (!c->resident) return -5;
+  jxe::EncCode code;
+  jxe::CodeFromDesc(*d, &code);
+  const size_t ng = c->tokens.size();
+  c->coded.assign(ng, {});
+  c->coded_bits.assign(ng, 0);
+  for (size_t g = 0; g < ng; g++) {
+    if (d->prefix_count[g] > 8) return -1;
+    if (!jxe::TokensCodable(c->tokens[g].data(), c->tokens[g].size(), code)) return -3;
+    jxe::BitWriter bw;
+    bw.Write(d->prefix_count[g], d->prefix_value[g] & ((1u << d->prefix_count[g]) - 1));
+    jxe::WriteTokens(bw, c->tokens[g].data(), c->tokens[g].size(), code);
+    c->coded_bits[g] = bit_counts[g] = uint32_t(bw.BitPos());
+    c->coded[g] = bw.bytes();
+  }
+  return 0;
+}
+
+int jxlenc_cpu_ans_write(void* ctx, const uint64_t* byte_bases, uint8_t* out, size_t capacity) {
+  JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
+  if (!c || !byte_bases || !out) return -1;
+  if (c->coded.empty()) return -5;
+  for (size_t g = 0; g < c->coded.size(); g++)
+    if (byte_bases[g] + c->coded[g].size() > capacity) return -1;
+  for (size_t g = 0; g < c->coded.size(); g++)
+    if (!c->coded[g].empty()) memcpy(out + byte_bases[g], c->coded[g].data(), c->coded[g].size());
+  return 0;
 }
 
 // The CPU form of the forward path, with jxlhip_enc_forward's signature (ctx unused): what the GPU tests compare the

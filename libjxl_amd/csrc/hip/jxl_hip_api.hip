@@ -254,6 +254,13 @@ struct JxlHipContext {
   bool enc_tok_ready = false;
   std::vector<uint32_t> enc_tok_totals;
   Buf enc_tok_orders, enc_tok_blk, enc_tok_info, enc_tok_off, enc_tok_nzmap, enc_tok_small, enc_tok_out, enc_tok_base;
+  // entropy coding of the resident tokens (jxlhip_enc_histograms, jxlhip_enc_ans_sizes -> jxlhip_enc_ans_write): the groups
+  // the tokens in enc_tok_out belong to, the bit lengths of the last sizes call, kernel times
+  std::vector<uint32_t> ent_base, ent_count, ent_bits;
+  bool ent_resident = false, ent_sized = false, ent_timed[3] = {false, false, false};
+  jxlhip::EncAns ent;
+  Buf ent_counts, ent_status, ent_grp, ent_tab, ent_rec, ent_fl, ent_small, ent_out, ent_obase;
+  hipEvent_t ent_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // histograms; records + chain; scatter
   jxlhip::EncFwd enc_last;     // the parameters of the last jxlhip_enc_forward (its input stays resident): jxlhip_enc_forward_rerun
   bool enc_last_gaborish = false;
   uint32_t out_orient = 0;  // jxlhip_set_output_orientation: PixelOut::orient bits (0 = the image as coded)
@@ -467,6 +474,7 @@ static JxlHipContext* RecycleContext(int device) {
   o->pass_bufs.clear();
   for (size_t i = 0; i < sizeof(c->ev) / sizeof(c->ev[0]); i++) std::swap(c->ev[i], o->ev[i]);
   for (size_t i = 0; i < sizeof(c->enc_ev) / sizeof(c->enc_ev[0]); i++) std::swap(c->enc_ev[i], o->enc_ev[i]);
+  for (size_t i = 0; i < sizeof(c->ent_ev) / sizeof(c->ent_ev[0]); i++) std::swap(c->ent_ev[i], o->ent_ev[i]);
   std::swap(c->stage, o->stage);
   jxlhip_ctx_destroy(o);  // (what is left of it: lazily created events, a stream of its own)
   return c;
@@ -539,7 +547,8 @@ static std::vector<Buf*> AllBufs(JxlHipContext* c) {
                 &c->plane[2], &c->rgb, &c->tlist, &c->scratch, &c->ep_dev, &c->batch_params, &c->batch_map, &c->batch_lanes, &c->ups_kernel, &c->kend, &c->block_recs, &c->dequant_scan, &c->ec_stage, &c->alpha_patched, &c->trecs, &c->enc_tok_orders, &c->enc_tok_blk, &c->enc_tok_info,
                 &c->enc_tok_off, &c->enc_tok_nzmap, &c->enc_tok_small, &c->enc_tok_out, &c->enc_tok_base, &c->tb_params, &c->tb_desc, &c->fb_params, &c->alpha, &c->sec_end, &c->lz_window, &c->mod.pool, &c->mod.sections, &c->mod.blob, &c->mod.streams,
                 &c->mod.rects, &c->mod.status, &c->mod.end_bits, &c->mod.scratch, &c->mod.windows, &c->mod.batch_streams, &c->mod.batch_ops, &c->frame_blob, &c->noise, &c->spl_seg, &c->spl_row_start, &c->spl_row_seg, &c->spl_planes, &c->pat_rec, &c->pat_row_start, &c->pat_row_list,
-                &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes};
+                &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes,
+                &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
   for (auto& pb : c->pass_bufs)
     for (Buf* b : {&pb.ctx_map, &pb.alias, &pb.cfg, &pb.orders, &pb.ptable, &pb.poffset, &pb.alias_packed}) all.push_back(b);
   return all;
@@ -566,6 +575,8 @@ void jxlhip_ctx_destroy(JxlHipContext* c) {
   for (auto& ev : c->ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : c->enc_ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : c->ent_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (c->stage.done) (void)hipEventDestroy(c->stage.done);
   if (c->stage.p) (void)hipHostFree(c->stage.p);
@@ -4026,6 +4037,7 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
   if (coeffs) HIP_TRY(hipMemcpyAsync(coeffs, c->enc_coef.p, ng * 3 * 65536 * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->enc_tok_ready = false;
+  c->ent_resident = c->ent_sized = false;
   return 0;
 }
 
@@ -4083,7 +4095,7 @@ int jxlhip_enc_token_counts(JxlHipContext* c, const JxlHipEncTokDesc* d, uint32_
 }
 
 int jxlhip_enc_tokens(JxlHipContext* c, const uint32_t* bases, uint32_t* tokens, size_t capacity) {
-  if (!c || !bases || !tokens) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c || !bases) return JXLHIP_ERR_INVALID_ARGUMENT;  // (tokens == NULL: they stay on the device, for the entropy calls)
   if (!c->enc_tok_ready) return JXLHIP_ERR_NO_FRAME;
   const size_t ng = c->enc_tok_totals.size();
   uint64_t need = 0;
@@ -4100,8 +4112,213 @@ int jxlhip_enc_tokens(JxlHipContext* c, const uint32_t* bases, uint32_t* tokens,
   T.tokens = c->enc_tok_out.as<uint2>();
   hipLaunchKernelGGL(jxlhip::k_enc_tok_emit, dim3(uint32_t(ng)), dim3(jxlhip::kTokThreads), 0, c->stream, T);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(tokens, c->enc_tok_out.p, size_t(need) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (tokens) HIP_TRY(hipMemcpyAsync(tokens, c->enc_tok_out.p, size_t(need) * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  c->ent_base.assign(bases, bases + ng);
+  c->ent_count = c->enc_tok_totals;
+  c->ent_resident = true;
+  c->ent_sized = false;
+  return 0;
+}
+
+// ---- entropy coding of the resident tokens (jxl_hip_enc.h)
+namespace {
+// What both passes start with: the groups' token counts on the device, the events, the token side of the parameters.
+int EntBegin(JxlHipContext* c, jxlhip::EncAns* A, uint32_t* blocks) {
+  const size_t ng = c->ent_base.size();
+  int r;
+  if ((r = c->ent_grp.Ensure(ng * 4))) return r;
+  for (auto& ev : c->ent_ev)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  HIP_TRY(hipMemcpyAsync(c->ent_grp.p, c->ent_count.data(), ng * 4, hipMemcpyHostToDevice, c->stream));
+  memset(A, 0, sizeof(*A));
+  A->tokens = c->enc_tok_out.as<uint2>();
+  A->base = c->enc_tok_base.as<uint32_t>();
+  A->count = c->ent_grp.as<uint32_t>();
+  uint32_t most = 0;
+  for (uint32_t n : c->ent_count) most = std::max(most, n);
+  // (per-token kernels: blocks per group so that a thread takes about sixteen tokens)
+  *blocks = std::max(1u, std::min(32u, (most + jxlhip::kAnsThreads * 16 - 1) / (jxlhip::kAnsThreads * 16)));
+  return 0;
+}
+bool HybridOk(uint32_t split_exp, uint32_t msb, uint32_t lsb) { return split_exp <= 8 && msb + lsb <= split_exp; }
+}  // namespace
+
+int jxlhip_enc_histograms(JxlHipContext* c, const JxlHipEncHistDesc* d, uint32_t* counts, uint32_t* max_token) {
+  if (!c || !d || !counts || !max_token || !d->num_ctx || d->num_ctx > (1u << 20) || !HybridOk(d->split_exp, d->msb_in_token, d->lsb_in_token))
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->ent_resident) return JXLHIP_ERR_NO_FRAME;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t ng = c->ent_base.size(), bytes = size_t(d->num_ctx) * 256 * 4;
+  jxlhip::EncAns A;
+  uint32_t blocks;
+  int r;
+  if ((r = EntBegin(c, &A, &blocks)) || (r = c->ent_counts.Ensure(bytes)) || (r = c->ent_status.Ensure(8))) return r;
+  HIP_TRY(hipMemsetAsync(c->ent_counts.p, 0, bytes, c->stream));
+  HIP_TRY(hipMemsetAsync(c->ent_status.p, 0, 8, c->stream));
+  A.split_exp = d->split_exp;
+  A.msb = d->msb_in_token;
+  A.lsb = d->lsb_in_token;
+  A.num_ctx = d->num_ctx;
+  A.counts = c->ent_counts.as<uint32_t>();
+  A.status = c->ent_status.as<uint32_t>();
+  HIP_TRY(hipEventRecord(c->ent_ev[0], c->stream));
+  hipLaunchKernelGGL(jxlhip::k_enc_hist, dim3(blocks, uint32_t(ng)), dim3(jxlhip::kAnsThreads), 0, c->stream, A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ent_ev[1], c->stream));
+  c->ent_timed[0] = true;
+  uint32_t status[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(counts, c->ent_counts.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(status, c->ent_status.p, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *max_token = status[0];
+  return (status[1] || status[0] >= 256) ? JXLHIP_ERR_INVALID_ARGUMENT : 0;
+}
+
+int jxlhip_enc_ans_sizes(JxlHipContext* c, const JxlHipEncAnsDesc* d, uint32_t* bit_counts) {
+  if (!c || !d || !bit_counts || !d->ctx_map || !d->freq || !d->rev_start || !d->rev || !d->prefix_count || !d->prefix_value || !d->num_ctx ||
+      d->num_ctx > (1u << 20) || !d->num_clusters || d->num_clusters > 256 || d->log_alpha < 5 || d->log_alpha > 8 ||
+      !HybridOk(d->split_exp, d->msb_in_token, d->lsb_in_token))
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->ent_resident) return JXLHIP_ERR_NO_FRAME;
+  c->ent_sized = false;
+  // every index the kernels form from the tables stays inside them: clusters below num_clusters; per cluster the
+  // frequencies sum to 4096 with rev_start their running sum (so rev_start + freq <= 4096) and no symbol beyond the
+  // alphabet; reverse-map entries below 4096
+  const size_t ng = c->ent_base.size(), K = d->num_clusters;
+  for (uint32_t i = 0; i < d->num_ctx; i++)
+    if (d->ctx_map[i] >= K) return JXLHIP_ERR_INVALID_ARGUMENT;
+  for (size_t k = 0; k < K; k++) {
+    uint32_t sum = 0;
+    for (uint32_t s = 0; s < 256; s++) {
+      const uint32_t f = d->freq[k * 256 + s];
+      if (f && ((s >> d->log_alpha) || d->rev_start[k * 256 + s] != sum)) return JXLHIP_ERR_INVALID_ARGUMENT;
+      sum += f;
+      if (sum > 4096) return JXLHIP_ERR_INVALID_ARGUMENT;
+    }
+    if (sum != 4096) return JXLHIP_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < 4096; i++)
+      if (d->rev[k * 4096 + i] >= 4096) return JXLHIP_ERR_INVALID_ARGUMENT;
+  }
+  uint64_t need = 0;
+  for (size_t g = 0; g < ng; g++) {
+    if (d->prefix_count[g] > 8) return JXLHIP_ERR_INVALID_ARGUMENT;
+    need = std::max<uint64_t>(need, uint64_t(c->ent_base[g]) + c->ent_count[g]);
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  // the tables in one block: ctx_map | freq | rev_start | rev | prefix_count | prefix_value, each 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+  const size_t o_freq = up16(d->num_ctx), o_start = o_freq + K * 512, o_rev = o_start + K * 512, o_pc = o_rev + K * 8192, o_pv = o_pc + up16(ng),
+               tab_bytes = o_pv + up16(ng);
+  jxlhip::EncAns& A = c->ent;
+  uint32_t blocks;
+  int r;
+  if ((r = EntBegin(c, &A, &blocks)) || (r = c->ent_tab.Ensure(tab_bytes)) || (r = c->ent_rec.Ensure(size_t(need ? need : 1) * 4)) ||
+      (r = c->ent_fl.Ensure(size_t(need ? need : 1) * 4)) || (r = c->ent_small.Ensure(ng * 12)))
+    return r;
+  uint8_t* tab = c->ent_tab.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(tab, d->ctx_map, d->num_ctx, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(tab + o_freq, d->freq, K * 512, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(tab + o_start, d->rev_start, K * 512, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(tab + o_rev, d->rev, K * 8192, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(tab + o_pc, d->prefix_count, ng, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(tab + o_pv, d->prefix_value, ng, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->ent_small.p, 0, ng * 12, c->stream));
+  A.split_exp = d->split_exp;
+  A.msb = d->msb_in_token;
+  A.lsb = d->lsb_in_token;
+  A.num_ctx = d->num_ctx;
+  A.ctx_map = tab;
+  A.freq = reinterpret_cast<const uint16_t*>(tab + o_freq);
+  A.rev_start = reinterpret_cast<const uint16_t*>(tab + o_start);
+  A.rev = reinterpret_cast<const uint16_t*>(tab + o_rev);
+  A.prefix_count = tab + o_pc;
+  A.prefix_value = tab + o_pv;
+  A.rec = c->ent_rec.as<uint32_t>();
+  A.fl = c->ent_fl.as<uint32_t>();
+  A.state = c->ent_small.as<uint32_t>();
+  A.bits = A.state + ng;
+  A.err = A.state + 2 * ng;
+  HIP_TRY(hipEventRecord(c->ent_ev[2], c->stream));
+  hipLaunchKernelGGL(jxlhip::k_enc_ans_records, dim3(blocks, uint32_t(ng)), dim3(jxlhip::kAnsThreads), 0, c->stream, A);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(jxlhip::k_enc_ans_chain, dim3(uint32_t(ng)), dim3(64), 0, c->stream, A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ent_ev[3], c->stream));
+  c->ent_timed[1] = true;
+  c->ent_timed[2] = false;
+  std::vector<uint32_t> back(2 * ng);
+  HIP_TRY(hipMemcpyAsync(back.data(), A.bits, ng * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t g = 0; g < ng; g++)
+    if (back[ng + g]) return JXLHIP_ERR_INVALID_ARGUMENT;  // a token this code cannot code (context, alphabet or a zero frequency)
+  c->ent_bits.assign(back.begin(), back.begin() + ng);
+  memcpy(bit_counts, back.data(), ng * 4);
+  c->ent_sized = true;
+  return 0;
+}
+
+int jxlhip_enc_ans_write(JxlHipContext* c, const uint64_t* byte_bases, uint8_t* out, size_t capacity) {
+  if (!c || !byte_bases || !out) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->ent_resident || !c->ent_sized) return JXLHIP_ERR_NO_FRAME;
+  const size_t ng = c->ent_base.size();
+  uint64_t end = 0;
+  for (size_t g = 0; g < ng; g++) {  // every group's range inside the caller's buffer (they may not overlap: a prefix sum)
+    const uint64_t bytes = (uint64_t(c->ent_bits[g]) + 7) / 8;
+    if (byte_bases[g] > capacity || bytes > capacity - byte_bases[g]) return JXLHIP_ERR_INVALID_ARGUMENT;
+    end = std::max(end, byte_bases[g] + bytes);
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t words = size_t((end + 3) / 4) + 2;  // (a token's bits reach into at most the word its last bit is in)
+  int r;
+  if ((r = c->ent_out.Ensure(words * 4)) || (r = c->ent_obase.Ensure(ng * 8))) return r;
+  HIP_TRY(hipMemsetAsync(c->ent_out.p, 0, words * 4, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->ent_obase.p, byte_bases, ng * 8, hipMemcpyHostToDevice, c->stream));
+  jxlhip::EncAns A = c->ent;
+  A.out_base = c->ent_obase.as<uint64_t>();
+  A.out = c->ent_out.as<uint32_t>();
+  HIP_TRY(hipEventRecord(c->ent_ev[4], c->stream));
+  hipLaunchKernelGGL(jxlhip::k_enc_ans_scatter, dim3(uint32_t(ng)), dim3(jxlhip::kAnsThreads), 0, c->stream, A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ent_ev[5], c->stream));
+  c->ent_timed[2] = true;
+  if (end) HIP_TRY(hipMemcpyAsync(out, c->ent_out.p, size_t(end), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int jxlhip_debug_ans_write(JxlHipContext* c, const uint32_t* tokens, size_t n, const JxlHipEncAnsDesc* d, uint8_t* out, size_t capacity,
+                           uint64_t* bits) {
+  if (!c || (!tokens && n) || !d || !out || !bits || n >= (size_t(1) << 28)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  int r;
+  if ((r = c->enc_tok_out.Ensure((n ? n : 1) * 8)) || (r = c->enc_tok_base.Ensure(4))) return r;
+  if (n) HIP_TRY(hipMemcpyAsync(c->enc_tok_out.p, tokens, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->enc_tok_base.p, 0, 4, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->enc_tok_ready = false;  // (the resident tokens are no longer those of the last jxlhip_enc_token_counts)
+  c->ent_base.assign(1, 0);
+  c->ent_count.assign(1, uint32_t(n));
+  c->ent_resident = true;
+  c->ent_sized = false;
+  uint32_t nbits = 0;
+  if ((r = jxlhip_enc_ans_sizes(c, d, &nbits))) return r;
+  *bits = nbits;
+  const uint64_t base = 0;
+  return jxlhip_enc_ans_write(c, &base, out, capacity);
+}
+
+int jxlhip_enc_entropy_last_ms(JxlHipContext* c, float* ms) {
+  if (!c || !ms) return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  float t[3] = {0, 0, 0};
+  for (int i = 0; i < 3; i++)
+    if (c->ent_timed[i]) {
+      HIP_TRY(hipEventSynchronize(c->ent_ev[2 * i + 1]));
+      HIP_TRY(hipEventElapsedTime(&t[i], c->ent_ev[2 * i], c->ent_ev[2 * i + 1]));
+    }
+  ms[0] = t[0];
+  ms[1] = t[1] + t[2];
   return 0;
 }
 

@@ -799,5 +799,196 @@ __global__ __launch_bounds__(kTokThreads) void k_enc_tok_emit(EncTok P) {
   }
 }
 
+// ---------------------------------------------------------------- entropy coding of the tokens
+// What the host coder does behind the tokens (csrc/enc/jxl_enc.cc CountSymbols and WriteTokens), on the tokens where they
+// are: symbol counts per context go up, the host clusters and normalises them and sends the code's tables down, and every
+// group's coded bit string goes up. The tokens themselves never leave the device.
+//   k_enc_hist         per token: its hybrid-uint symbol, counted in counts[context][symbol] (integer sums: any order)
+//   k_enc_ans_records  per token: the frequency of its symbol in its context's cluster and where the symbol's slots start
+//                      in the cluster's reverse map, as one word; the number of extra bits
+//   k_enc_ans_chain    per group, one wave: the coder state, backwards from the final state 0x13 << 16 (a token's state
+//                      depends on the state behind it: this is the serial part). Per token whether it flushed 16 bits, and
+//                      which; per group the state the stream starts with and the exact length in bits
+//   k_enc_ans_scatter  per group, one workgroup: prefix sum of the bit lengths, every token's chunk and extra bits OR-ed
+//                      into the words of the (zeroed) output it falls into
+// Every index formed from a table is bounded by the checks jxlhip_enc_ans_sizes makes on the tables; a token the code cannot
+// code (context out of range, symbol beyond the alphabet or without frequency) is coded as a symbol of frequency 1 at slot
+// 0 - in bounds - and raises its group's error flag, which fails the call.
+struct EncAns {
+  const uint2* tokens;         // {context, value}; group g at tokens[base[g] .. base[g] + count[g])
+  const uint32_t* base;        // [groups]
+  const uint32_t* count;       // [groups]
+  uint32_t split_exp, msb, lsb, num_ctx;
+  uint32_t* counts;            // (hist) [num_ctx][256]
+  uint32_t* status;            // (hist) [0] largest symbol, [1] non-zero: a token outside the table
+  const uint8_t* ctx_map;      // [num_ctx], entries < clusters
+  const uint16_t* freq;        // [clusters][256]
+  const uint16_t* rev_start;   // [clusters][256]; rev_start + freq <= 4096
+  const uint16_t* rev;         // [clusters][4096], entries < 4096
+  const uint8_t* prefix_count; // [groups], <= 8
+  const uint8_t* prefix_value; // [groups]
+  uint32_t* rec;               // per token: frequency - 1 | (cluster * 4096 + rev_start) << 12
+  uint32_t* fl;                // per token: chunk | flushed << 16 | extra bits << 17
+  uint32_t* state;             // [groups] the state the stream starts with
+  uint32_t* bits;              // [groups] length of the bit string
+  uint32_t* err;               // [groups]
+  const uint64_t* out_base;    // (scatter) [groups] first byte in out
+  uint32_t* out;               // (scatter) words, zeroed
+};
+constexpr uint32_t kAnsThreads = 256, kAnsBlocksPerGroup = 8;
+
+// (jxl_enc.cc HybridEncode; split_exp >= msb + lsb, so n - msb >= 0 for every value that gets here)
+__device__ __forceinline__ void EncHybrid(uint32_t v, uint32_t split_exp, uint32_t msb, uint32_t lsb, uint32_t& tok, uint32_t& nbits, uint32_t& bits) {
+  if (v < (1u << split_exp)) {
+    tok = v;
+    nbits = 0;
+    bits = 0;
+    return;
+  }
+  const uint32_t n = 31u - uint32_t(__clz(int(v))), m = v - (1u << n);
+  tok = (1u << split_exp) + ((n - split_exp) << (msb + lsb)) + ((m >> (n - msb)) << lsb) + (m & ((1u << lsb) - 1u));
+  nbits = n - msb - lsb;
+  bits = (v >> lsb) & ((1u << nbits) - 1u);
+}
+
+__global__ __launch_bounds__(kAnsThreads) void k_enc_hist(EncAns P) {
+  const uint32_t g = blockIdx.y, n = P.count[g];
+  const uint2* tk = P.tokens + P.base[g];
+  uint32_t mx = 0, bad = 0;
+  for (uint32_t i = blockIdx.x * kAnsThreads + threadIdx.x; i < n; i += gridDim.x * kAnsThreads) {
+    const uint2 t = tk[i];
+    uint32_t tok, nb, bits;
+    EncHybrid(t.y, P.split_exp, P.msb, P.lsb, tok, nb, bits);
+    mx = max(mx, tok);
+    if (t.x >= P.num_ctx || tok >= 256u) bad = 1;
+    else atomicAdd(&P.counts[size_t(t.x) * 256 + tok], 1u);
+  }
+  for (int o = 32; o; o >>= 1) {
+    mx = max(mx, uint32_t(__shfl_xor(int(mx), o)));
+    bad |= uint32_t(__shfl_xor(int(bad), o));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (mx) atomicMax(&P.status[0], mx);
+    if (bad) atomicOr(&P.status[1], 1u);
+  }
+}
+
+__global__ __launch_bounds__(kAnsThreads) void k_enc_ans_records(EncAns P) {
+  const uint32_t g = blockIdx.y, n = P.count[g], base = P.base[g];
+  uint32_t bad = 0;
+  for (uint32_t i = blockIdx.x * kAnsThreads + threadIdx.x; i < n; i += gridDim.x * kAnsThreads) {
+    const uint2 t = P.tokens[base + i];
+    uint32_t tok, nb, bits, rec = 0;
+    EncHybrid(t.y, P.split_exp, P.msb, P.lsb, tok, nb, bits);
+    if (t.x >= P.num_ctx || tok >= 256u) {
+      bad |= 1;
+    } else {
+      const uint32_t k = P.ctx_map[t.x], f = P.freq[k * 256 + tok];
+      if (!f) bad |= 2;
+      else rec = (f - 1u) | (k * 4096u + P.rev_start[k * 256 + tok]) << 12;
+    }
+    P.rec[base + i] = rec;
+    P.fl[base + i] = nb << 17;
+  }
+  if (bad) atomicOr(&P.err[g], bad);
+}
+
+// The state chain of one group on one wave. The wave loads 64 records at a time, coalesced, and every lane turns its own
+// record's frequency into a double reciprocal; the 64 steps then run on wave-uniform values (a record comes out of its lane
+// by v_readlane): state / freq as trunc(state * (1 / freq)) with one correction step - the product is within 2^-20 of the
+// quotient, a non-integer quotient is at least 2^-12 from the next integer, so only an exact multiple can come out one low,
+// and the remainder test catches it. The only load that depends on the state is rev[...].
+__global__ __launch_bounds__(64) void k_enc_ans_chain(EncAns P) {
+  const uint32_t g = blockIdx.x, lane = threadIdx.x, n = P.count[g], base = P.base[g];
+  const uint16_t* __restrict__ rev = P.rev;
+  uint32_t state = 0x13u << 16, total = 0;
+  for (uint32_t t0 = ((n + 63u) & ~63u); t0 >= 64u;) {
+    t0 -= 64u;
+    const uint32_t i = t0 + lane;
+    const bool in = i < n;
+    const uint32_t rec = in ? P.rec[base + i] : 0u;
+    uint32_t f = in ? P.fl[base + i] : 0u;
+    const double rcp = 1.0 / double((rec & 0xFFFu) + 1u);
+    const int rcp_lo = __double2loint(rcp), rcp_hi = __double2hiint(rcp);
+    uint32_t mine = 0;
+    for (int j = int(min(64u, n - t0)) - 1; j >= 0; j--) {
+      const uint32_t r = uint32_t(__builtin_amdgcn_readlane(int(rec), j));
+      const double rc = __hiloint2double(__builtin_amdgcn_readlane(rcp_hi, j), __builtin_amdgcn_readlane(rcp_lo, j));
+      const uint32_t freq = (r & 0xFFFu) + 1u;
+      const bool flush = (state >> 20) >= freq;
+      const uint32_t chunk = state & 0xFFFFu;
+      if (flush) state >>= 16;
+      uint32_t q = uint32_t(double(state) * rc), rem = state - q * freq;
+      if (rem >= freq) {
+        q++;
+        rem -= freq;
+      }
+      state = (q << 12) + rev[(r >> 12) + rem];
+      if (int(lane) == j) mine = chunk | (flush ? 0x10000u : 0u);
+    }
+    if (in) {
+      f |= mine;
+      P.fl[base + i] = f;
+      total += (f >> 17) + ((f >> 16) & 1u) * 16u;
+    }
+  }
+  for (int o = 32; o; o >>= 1) total += uint32_t(__shfl_xor(int(total), o));
+  if (lane == 0) {
+    P.state[g] = state;
+    P.bits[g] = uint32_t(P.prefix_count[g]) + 32u + total;
+  }
+}
+
+// `len` (<= 47) bits of v at absolute bit position `pos` of the zeroed word array
+__device__ __forceinline__ void AnsPut(uint32_t* out, uint64_t pos, uint64_t v, uint32_t len) {
+  if (!len) return;
+  const uint64_t w = pos >> 5;
+  const uint32_t sh = uint32_t(pos & 31);
+  const uint64_t lo = v << sh;
+  const uint32_t w0 = uint32_t(lo), w1 = uint32_t(lo >> 32), w2 = sh ? uint32_t(v >> (64 - sh)) : 0u;
+  if (w0) atomicOr(&out[w], w0);
+  if (w1) atomicOr(&out[w + 1], w1);
+  if (w2) atomicOr(&out[w + 2], w2);
+}
+
+__global__ __launch_bounds__(kAnsThreads) void k_enc_ans_scatter(EncAns P) {
+  __shared__ uint32_t l_wave[kAnsThreads / 64];
+  const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = P.count[g], base = P.base[g];
+  if (P.err[g]) return;  // (uniform) nothing is written for a group the code cannot code
+  const uint64_t bit0 = P.out_base[g] * 8;
+  const uint32_t pc = P.prefix_count[g];
+  if (tid == 0) {
+    AnsPut(P.out, bit0, uint64_t(P.prefix_value[g]) & ((1u << pc) - 1u), pc);
+    AnsPut(P.out, bit0 + pc, P.state[g], 32);
+  }
+  uint64_t running = pc + 32u;
+  for (uint32_t t0 = 0; t0 < n; t0 += kAnsThreads) {
+    const uint32_t i = t0 + tid;
+    const bool in = i < n;
+    const uint32_t f = in ? P.fl[base + i] : 0u;
+    const uint32_t nb = (f >> 17) & 31u, flushed = (f >> 16) & 1u, len = nb + 16u * flushed;
+    uint32_t incl = len;  // inclusive scan over the wave, then over the workgroup's four waves
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t v = uint32_t(__shfl_up(int(incl), o));
+      if (int(lane) >= o) incl += v;
+    }
+    __syncthreads();  // (l_wave of the round before has been read)
+    if (lane == 63) l_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (uint32_t w = 0; w < kAnsThreads / 64; w++) {
+      if (w < wave) before += l_wave[w];
+      all += l_wave[w];
+    }
+    if (len) {
+      const uint32_t value = P.tokens[base + i].y;
+      const uint64_t extra = (value >> P.lsb) & ((1u << nb) - 1u);
+      const uint64_t v = flushed ? (uint64_t(f & 0xFFFFu) | extra << 16) : extra;
+      AnsPut(P.out, bit0 + running + before + incl - len, v, len);
+    }
+    running += all;
+  }
+}
+
 }  // namespace jxlhip
 #endif  // JXL_HIP_ENC_H_

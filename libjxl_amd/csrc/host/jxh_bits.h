@@ -91,6 +91,16 @@ class BitWriter {
       Write(n, o.buf_[i >> 3]);
     }
   }
+  // The first `nbits` bits of an LSB-first bit string, at any bit position (bits of b's last byte beyond nbits are ignored).
+  void AppendBits(const uint8_t* b, size_t nbits) {
+    size_t i = 0;
+    if ((pos_ & 7) == 0 && nbits >= 8) {  // byte aligned: the whole bytes go in as they are
+      buf_.insert(buf_.end(), b, b + nbits / 8);
+      i = nbits & ~size_t(7);
+      pos_ += i;
+    }
+    for (; i < nbits; i += 8) Write(unsigned(nbits - i < 8 ? nbits - i : 8), b[i >> 3]);
+  }
   void AppendBytes(const std::vector<uint8_t>& b) {
     ZeroPad();
     buf_.insert(buf_.end(), b.begin(), b.end());
