@@ -302,6 +302,8 @@ int jxlhip_get_section_end_bits(JxlHipContext* ctx, uint32_t* bits, size_t n);
  *   "xyb_idct"     float [3][ysize_padded][xsize_padded] after the inverse transforms
  *   "xyb_filtered" float [3][ysize_padded][xsize_padded] after Gaborish/EPF (rows < ysize, columns < xsize valid;
  *                  only with option "keep_filtered")
+ *   "xyb_upsampled" float [3][out_ysize][out_xsize padded to 8] of an upsampled frame, behind the upsampling and the noise
+ *                  (only with option "keep_upsampled")
  *   "kend"         uint32 [num_blocks][3]: scan position after the last non-zero coefficient of a (varblock, channel);
  *                  frames decoded in scan order only (after the entropy stage)
  *   "transform_lists" uint32 [entries][2] = {strategy, varblock index}: the transform work lists in launch order
@@ -312,6 +314,9 @@ int jxlhip_download(JxlHipContext* ctx, const char* name, void* dst, size_t dst_
  * XYB planes for jxlhip_download("xyb_filtered") (test aid; costs one extra plane set and 12 B/pixel of writes). Switched
  * on only after the upload of a frame that writes one 8-bit channel from the filter kernel (rows of 1 byte per pixel,
  * which no other writer may fill), it makes the filter launch fail with JXLHIP_ERR_INVALID_ARGUMENT: upload again.
+ * "keep_upsampled" = 1 (test aid): an upsampled frame takes the route a noisy upsampled frame takes (k_upsample_color
+ * writes X, Y, B at the image's size, then k_color_out makes the pixels) and keeps those planes for
+ * jxlhip_download("xyb_upsampled"). Off: launches and jxlhip_debug_pixel_route are as they were.
  * "transform_dense" = 1 (test aid): the transform kernels treat every coefficient extent as full, i.e. take none of the
  * shortcuts they decide from the coefficient counts. The same kernels, the same results.
  * "filter_async" = 1 (on the FIRST context of a set; may be changed at any time): jxlhip_run_filter_color_batch launches
@@ -391,6 +396,14 @@ struct JxlHipColorTarget {
 /* Test entry: the generic writer's colour stage alone on n XYB triples (planar [3][n]) with `target` (its matrix; the
  * opsin biases of the frame the context last uploaded); interleaved f32 RGB out. */
 int jxlhip_debug_color_target(JxlHipContext* ctx, const float* xyb, size_t n, const JxlHipColorTarget* target, float* rgb);
+
+/* Test entry: noise synthesis alone (k_noise_random, then k_noise_add on rows [y_begin, y_end)) on caller-supplied planes:
+ * xyb / xyb_out = [3][ysize][xsize] floats, dense, in host memory (rows outside the band come back as they went in);
+ * seed0 / seed1 = the visible / non-visible frame index; lut = the 8 strengths; ytox / ytob = the base colour
+ * correlation; raw_out (may be NULL) = the three random planes in front of the high-pass, same layout. Refuses empty or
+ * oversized planes (more than 2^24 samples), an empty or outlying band and values that are not finite. */
+int jxlhip_debug_noise(JxlHipContext* ctx, const float* xyb, uint32_t xsize, uint32_t ysize, uint32_t seed0, uint32_t seed1,
+                       const float* lut, float ytox, float ytob, uint32_t y_begin, uint32_t y_end, float* raw_out, float* xyb_out);
 
 /* Test access: who writes the pixels of the VarDCT frame the context last uploaded. *route = 0: the generic writer behind
  * the filter kernel (k_color_out / k_upsample_color), 1: the filter kernel itself (RGB8, RGB f32), 2: the one-channel

@@ -124,6 +124,14 @@ class Frame:
         self.end = int(L.jxlamd_frame_end(self._h, t))  # byte offset behind the frame
         self.duration, self.is_last, self.timecode = int(t[0]), bool(t[1]), int(t[2])
 
+    def upsampling_kernels(self, factor):
+        """The factor x factor 5x5 upsampling kernels the host builds from the image's coded or default weights."""
+        L = lib()
+        L.jxlamd_upsampling_kernels.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        k = np.zeros((factor, factor, 5, 5), np.float32)
+        _check(L.jxlamd_upsampling_kernels(self._h, factor, k.ctypes.data), "jxlamd_upsampling_kernels")
+        return k
+
     def close(self):
         if self._h:
             lib().jxlamd_frame_free(self._h)
@@ -212,6 +220,44 @@ class HipContext:
         L = lib()
         L.jxlhip_debug_color.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
         _check(L.jxlhip_debug_color(self._h, xyb.ctypes.data, n, 1 if linear else 0, out.ctypes.data), "jxlhip_debug_color")
+        return out
+
+    def debug_noise(self, xyb, seed0, seed1, lut, ytox, ytob, band=None, want_raw=True):
+        """Test entry: the noise kernels alone on planes xyb [3, ys, xs] -> (planes with the noise, raw random planes or None);
+        band = (y_begin, y_end): only those rows get noise."""
+        xyb = np.ascontiguousarray(xyb, np.float32)
+        _, ys, xs = xyb.shape
+        y0, y1 = band if band is not None else (0, ys)
+        lut = np.ascontiguousarray(lut, np.float32)
+        assert lut.shape == (8,)
+        out = np.empty_like(xyb)
+        raw = np.empty_like(xyb) if want_raw else None
+        L = lib()
+        L.jxlhip_debug_noise.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.jxlhip_debug_noise(self._h, xyb.ctypes.data, xs, ys, seed0, seed1, lut.ctypes.data, ytox, ytob, y0, y1,
+                                    raw.ctypes.data if want_raw else None, out.ctypes.data), "jxlhip_debug_noise")
+        return out, raw
+
+    def upsample_plane(self, plane, factor, kernels, out_xs, out_ys, as_alpha=False):
+        """jxlhip_upsample_plane on plane [ys, xs] with kernels [factor, factor, 5, 5]: the result [out_ys, out_xs], or (as_alpha)
+        None, the result being the context's alpha plane (download_alpha)."""
+        plane = np.ascontiguousarray(plane, np.float32)
+        kernels = np.ascontiguousarray(kernels, np.float32)
+        assert kernels.size == factor * factor * 25
+        out = None if as_alpha else np.empty((out_ys, out_xs), np.float32)
+        L = lib()
+        L.jxlhip_upsample_plane.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
+        _check(L.jxlhip_upsample_plane(self._h, plane.ctypes.data, plane.shape[1], plane.shape[0], factor, kernels.ctypes.data, out_xs, out_ys,
+                                       1 if as_alpha else 0, None if as_alpha else out.ctypes.data), "jxlhip_upsample_plane")
+        return out
+
+    def download_alpha(self, out_xs, out_ys):
+        L = lib()
+        L.jxlhip_download_alpha.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        out = np.empty((out_ys, out_xs), np.float32)
+        _check(L.jxlhip_download_alpha(self._h, out.ctypes.data), "jxlhip_download_alpha")
         return out
 
     def pixel_route(self):
@@ -412,6 +458,8 @@ class HipContext:
             return buf.view(np.uint32).reshape(-1, 3)
         if name == "transform_lists":  # [entry] = (strategy, varblock), launch order
             return buf.view(np.uint32).reshape(-1, 2)
+        if name == "xyb_upsampled":  # the image's size, rows padded to 8
+            return buf.view(np.float32).reshape(3, fi["out_ysize"], (fi["out_xsize"] + 7) // 8 * 8)
         if name in ("dc", "inv_sigma"):  # block-resolution planes as the transform / filter stages read them
             return buf.view(np.float32)
         return buf.view(np.float32).reshape(3, fi["ysize_blocks"] * 8, fi["xsize_blocks"] * 8)

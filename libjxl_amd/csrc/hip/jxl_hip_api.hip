@@ -241,6 +241,8 @@ struct JxlHipContext {
   bool lanes = false, lane_multi = false;
   uint32_t nblocks = 0;
   bool keep_filtered = false;  // jxlhip_set_option("keep_filtered"): also write the filtered XYB planes (tests)
+  bool keep_upsampled = false;  // jxlhip_set_option("keep_upsampled"): an upsampled frame's X, Y, B at the image's size stay (tests)
+  bool ups_kept = false;        // ... and the uploaded frame was set up for it (ups_planes holds them after the filter launch)
   bool transform_dense = false;  // jxlhip_set_option("transform_dense"): TransformParams::dense at the next upload (tests)
   bool band_halo = false;      // jxlhip_set_option("band_halo"): a band decodes ONLY its own group rows; the rows of the
                                // neighbouring bands that its filters read arrive through jxlhip_halo_unpack
@@ -1176,6 +1178,12 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
     const size_t nxs = c->ups == 1 ? c->xs : c->oxs, nys = c->ups == 1 ? c->ys : c->oys;
     if ((r = c->noise.Ensure(nxs * nys * 3 * 4))) return r;
     if (c->ups != 1 && (r = c->ups_planes.Ensure(size_t((c->oxs + 7) & ~7u) * c->oys * 3 * 4))) return r;
+  }
+  // (tests: the upsampled planes are kept, so the frame takes the route of a noisy upsampled frame without the noise)
+  c->ups_kept = c->keep_upsampled && c->ups != 1;
+  if (c->ups_kept) {
+    c->color_out = true;
+    if ((r = c->ups_planes.Ensure(size_t((c->oxs + 7) & ~7u) * c->oys * 3 * 4))) return r;
   }
   // splines are drawn over the filtered planes before noise and the colour conversion
   // (an upsampled frame's splines and patches are drawn at its own resolution, on the planes the upsampling kernel reads:
@@ -3108,7 +3116,8 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
     up.xyb_out = nullptr;
     up.oxp = 0;
     up.t = c->ct;
-    if (c->has_noise) {  // upsample to planes, add the noise at the image's resolution, then the colour stage
+    const bool to_planes = c->has_noise || c->ups_kept;
+    if (to_planes) {  // upsample to planes, add the noise at the image's resolution, then the colour stage
       up.xyb_out = c->ups_planes.as<float>();
       up.oxp = (c->oxs + 7) & ~7u;
     }
@@ -3134,6 +3143,8 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
       np.y_end = c->oys;
       hipLaunchKernelGGL(jxlhip::k_noise_random, dim3((np.ngroups * 8 + 63) / 64), dim3(64), 0, ls, np);
       hipLaunchKernelGGL(jxlhip::k_noise_add, dim3((c->oxs + 63) / 64, (c->oys + 3) / 4), dim3(256), 0, ls, np);
+    }
+    if (to_planes) {
       jxlhip::ColorOutParams cp;
       cp.f = c->fp;
       cp.f.in = up.xyb_out;
@@ -3283,6 +3294,10 @@ int jxlhip_set_option(JxlHipContext* c, const char* name, int value) {
   if (!c || !name) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (std::string(name) == "keep_filtered") {
     c->keep_filtered = value != 0;
+    return 0;
+  }
+  if (std::string(name) == "keep_upsampled") {  // (takes effect at the next upload)
+    c->keep_upsampled = value != 0;
     return 0;
   }
   if (std::string(name) == "transform_dense") {  // (takes effect at the next upload)
@@ -3494,6 +3509,57 @@ int jxlhip_debug_color_target(JxlHipContext* c, const float* xyb, size_t n, cons
   return DebugColor(c, xyb, n, 1, t, rgb);
 }
 
+// Test entry: noise synthesis alone (k_noise_random, k_noise_add) on caller-supplied dense planes, for a float64 reading.
+int jxlhip_debug_noise(JxlHipContext* c, const float* xyb, uint32_t xsize, uint32_t ysize, uint32_t seed0, uint32_t seed1, const float* lut,
+                       float ytox, float ytob, uint32_t y_begin, uint32_t y_end, float* raw_out, float* xyb_out) {
+  if (!c || !xyb || !lut || !xyb_out || !xsize || !ysize || xsize > (1u << 16) || ysize > (1u << 16)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (uint64_t(xsize) * ysize > (1u << 24) || y_begin >= y_end || y_end > ysize) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!std::isfinite(ytox) || !std::isfinite(ytob)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < 8; i++)
+    if (!std::isfinite(lut[i])) return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  {
+    int pw = ApplyPendingWait(c);
+    if (pw) return pw;
+  }
+  const size_t bytes = size_t(xsize) * ysize * 12;
+  Buf raw, planes;
+  int r;
+  if ((r = raw.Ensure(bytes)) || (r = planes.Ensure(bytes))) {
+    raw.Free();
+    planes.Free();
+    return r;
+  }
+  hipError_t e = hipMemcpyAsync(planes.p, xyb, bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    jxlhip::NoiseParams np;
+    memset(&np, 0, sizeof(np));
+    np.raw = raw.as<float>();
+    np.planes = planes.as<float>();
+    np.xsize = np.xp = xsize;
+    np.ysize = np.yp = ysize;
+    np.xgroups = (xsize + 255) / 256;
+    np.ngroups = np.xgroups * ((ysize + 255) / 256);
+    np.seed[0] = seed0;
+    np.seed[1] = seed1;
+    memcpy(np.lut, lut, sizeof(np.lut));
+    np.ytox = ytox;
+    np.ytob = ytob;
+    np.y_begin = y_begin;
+    np.y_end = y_end;
+    hipLaunchKernelGGL(jxlhip::k_noise_random, dim3((np.ngroups * 8 + 63) / 64), dim3(64), 0, c->stream, np);
+    hipLaunchKernelGGL(jxlhip::k_noise_add, dim3((xsize + 63) / 64, (y_end - y_begin + 3) / 4), dim3(256), 0, c->stream, np);
+    e = hipGetLastError();
+    if (e == hipSuccess && raw_out) e = hipMemcpyAsync(raw_out, raw.p, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(xyb_out, planes.p, bytes, hipMemcpyDeviceToHost, c->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(c->stream);  // (before the buffers go, whatever was enqueued)
+  raw.Free();
+  planes.Free();
+  if (e == hipSuccess) e = es;
+  return e == hipSuccess ? 0 : -int(e);
+}
+
 int jxlhip_debug_pixel_route(JxlHipContext* c, uint32_t* route) {
   if (!c || !route) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
@@ -3618,6 +3684,10 @@ int jxlhip_download(JxlHipContext* c, const char* name, void* dst, size_t dst_si
     if (!c->keep_filtered || !c->plane[1].p) return JXLHIP_ERR_INVALID_ARGUMENT;  // needs jxlhip_set_option("keep_filtered", 1)
     src = c->plane[1].p;
     bytes = plane_bytes;
+  } else if (n == "xyb_upsampled") {  // [3][out_ysize][out_xsize padded to 8]: behind the upsampling (and the noise, if any)
+    if (!c->ups_kept || !c->ups_planes.p) return JXLHIP_ERR_INVALID_ARGUMENT;  // needs jxlhip_set_option("keep_upsampled", 1)
+    src = c->ups_planes.p;
+    bytes = size_t((c->oxs + 7) & ~7u) * c->oys * 3 * 4;
   } else {
     return JXLHIP_ERR_INVALID_ARGUMENT;
   }

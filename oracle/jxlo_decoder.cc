@@ -1245,6 +1245,36 @@ void jxlo_chroma_upsample_kat(float* plane, size_t stride, size_t xsize, size_t 
   memcpy(plane, p.data(), p.size() * sizeof(float));
 }
 
+// Known-answer hook for the upsampling stage on ONE caller plane (tests/features_f64.py holds it to a float64 reading):
+// `plane` = xsize * ysize floats, dense; `weights` = the coded upper triangle (NULL: the default weights of the factor);
+// `out` = out_xsize * out_ysize floats, dense. `kernels` (may be NULL) receives the factor * factor 5x5 kernels.
+void jxlo_upsample_kat(const float* plane, size_t xsize, size_t ysize, uint32_t factor, const float* weights, size_t out_xsize,
+                       size_t out_ysize, float* out, float* kernels) {
+  jxlo::Planes3 in, up;
+  in.Alloc(xsize, ysize, xsize);
+  in.p[0].assign(plane, plane + xsize * ysize);
+  jxlo::Upsample(in, factor, weights, out_xsize, out_ysize, &up, 1);
+  memcpy(out, up.p[0].data(), out_xsize * out_ysize * sizeof(float));
+  if (kernels) jxlo::UpsamplingKernels(factor, weights, kernels);
+}
+
+// Known-answer hook for noise synthesis on caller planes: `xyb` = [3][ysize][xsize] floats, dense, modified in place;
+// `raw` (may be NULL) receives the three random planes before the high-pass, same layout.
+void jxlo_noise_kat(float* xyb, size_t xsize, size_t ysize, uint32_t seed0, uint32_t seed1, const float* lut, float ytox, float ytob,
+                    float* raw) {
+  const size_t n = xsize * ysize;
+  jxlo::Planes3 img;
+  img.Alloc(xsize, ysize, xsize);
+  for (int c = 0; c < 3; c++) img.p[c].assign(xyb + c * n, xyb + (c + 1) * n);
+  jxlo::AddNoise(&img, xsize, ysize, lut, ytox, ytob, seed0, seed1);
+  for (int c = 0; c < 3; c++) memcpy(xyb + c * n, img.p[c].data(), n * sizeof(float));
+  if (raw) {
+    std::vector<float> r[3];
+    jxlo::NoiseRandom(xsize, ysize, seed0, seed1, r);
+    for (int c = 0; c < 3; c++) memcpy(raw + c * n, r[c].data(), n * sizeof(float));
+  }
+}
+
 // Known-answer hook for the noise generator: `vectors` steps of the single-seed generator, 8 values each
 // (lib/jxl/xorshift128plus_test.cc:60-257 holds the expected values for seed 12345).
 void jxlo_xorshift_fill(uint64_t seed, uint64_t* out, size_t vectors) {

@@ -40,6 +40,10 @@ int jxlhip_upsample_plane(JxlHipContext*, const float*, uint32_t, uint32_t, uint
   return JXLHIP_ERR_INVALID_ARGUMENT;
 }
 int jxlhip_set_option(JxlHipContext*, const char*, int) { return JXLHIP_ERR_INVALID_ARGUMENT; }
+int jxlhip_debug_noise(JxlHipContext*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, const float*, float, float, uint32_t, uint32_t,
+                       float*, float*) {
+  return JXLHIP_ERR_INVALID_ARGUMENT;
+}
 }
 
 static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
