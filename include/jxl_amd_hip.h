@@ -574,9 +574,11 @@ int jxlhip_debug_blend(int device, const float* bg, const float* fg, size_t n, c
  * Replaces, behind lib/jxl/enc_frame.cc:1135-1166's per-group loop: SRGBToXYB (enc_xyb.cc:152-174), the Gaborish
  * sharpening (enc_gaborish.cc:21-70) and ComputeCoefficients (enc_group.cc:380-533: forward transform, DC from the
  * lowest frequencies, AC quantisation with chroma-from-luma from the dequantised Y). Transform selection and the quant
- * field are this library's own simple activity heuristics, not the reference's search (enc_ac_strategy.cc,
- * enc_adaptive_quantization.cc): the output is a valid model of a frame, not libjxl's choice of one. Entropy coding
- * and the headers stay on the host (csrc/enc). */
+ * field are this library's own simple activity heuristics by default, not the reference's search (enc_ac_strategy.cc,
+ * enc_adaptive_quantization.cc): the output is a valid model of a frame, not libjxl's choice of one. With
+ * quant_field_mode 1 the quant field is the reference's initial one (what libjxl writes at its default effort before any
+ * Butteraugli iteration), under this library's transform choices. Entropy coding and the headers stay on the host
+ * (csrc/enc). */
 typedef struct {
   uint32_t xsize, ysize;
   float distance;         /* Butteraugli-style target: scales the thresholds of the transform selection */
@@ -594,6 +596,13 @@ typedef struct {
   const float* dequant;
   uint32_t dequant_floats;
   uint32_t dequant_offset[17], dequant_size[17];
+  /* 0: the quant field is this library's activity rule around quant_ac. 1: the reference's initial adaptive quant field
+   * (InitialQuantField with butteraugli_distance_for_iqf = distance, or 0.62 * distance without Gaborish, rescale 1, over
+   * the XYB planes before the sharpening: enc_heuristics.cc:1118-1129), aggregated per transform by AdjustQuantField and
+   * made integer by SetQuantFieldRect under global_scale; quant_ac is not read. The caller passes the global_scale /
+   * quant_dc of ComputeGlobalScaleAndQuant(InitialQuantDC(distance), 0.39 / distance, 0). Anything else is
+   * JXLHIP_ERR_INVALID_ARGUMENT. */
+  uint32_t quant_field_mode;
 } JxlHipEncDesc;
 /* rgb: interleaved sRGB8 in host memory, `stride` bytes per row. Outputs (host memory): acs[yb * xb] = (strategy << 1) |
  * first-block bit, qf[yb * xb] (quant field at first blocks), dc[3][yb * xb] quantised DC stored X, Y, B, and
@@ -667,6 +676,18 @@ int jxlhip_debug_ans_write(JxlHipContext* ctx, const uint32_t* tokens, size_t n,
 /* Kernel time of the last jxlhip_enc_histograms (ms[0]) and of the last jxlhip_enc_ans_sizes + jxlhip_enc_ans_write (ms[1]),
  * milliseconds (HIP events around the launches, copies excluded); 0 for a pass that has not run. */
 int jxlhip_enc_entropy_last_ms(JxlHipContext* ctx, float* ms);
+/* The reference's initial adaptive quant field alone (lib/jxl/enc_adaptive_quantization.cc InitialQuantField :1264-1271 ->
+ * AdaptiveQuantizationMap :664-705, without mask1x1 and its blur): xyb = the X, Y, B planes [3][ysize][xsize] in host
+ * memory, xsize and ysize multiples of 8 (the image padded to whole blocks; a neighbour outside is the nearest sample);
+ * butteraugli_target = the distance the field is built for (enc_heuristics.cc:1119-1122), rescale as there (1).
+ * Outputs, host memory: aq_map[ysize / 8][xsize / 8] the field per block, before AdjustQuantField; mask (may be NULL)
+ * the masking image the AC-strategy search reads. log2 / exp2 are exact where the reference approximates them
+ * (relative 3e-7). Synchronous; leaves the last jxlhip_enc_forward's state as it was. */
+int jxlhip_enc_initial_quant_field(JxlHipContext* ctx, const float* xyb, uint32_t xsize, uint32_t ysize, float butteraugli_target,
+                                   float rescale, float* aq_map, float* mask);
+/* Kernel time of the two quant-field kernels in the last pass of the last jxlhip_enc_forward / _rerun made with
+ * quant_field_mode 1 (they are part of jxlhip_enc_last_ms too), milliseconds. */
+int jxlhip_enc_aq_last_ms(JxlHipContext* ctx, float* ms);
 /* Measurement: runs the kernel sequence of the last jxlhip_enc_forward `times` more times on its input, which is still
  * resident on the device (no copies); jxlhip_enc_last_ms then gives the time of all `times` passes. Synchronous. */
 int jxlhip_enc_forward_rerun(JxlHipContext* ctx, uint32_t times);

@@ -339,6 +339,14 @@ class HipContext:
         _check(L.jxlhip_enc_last_transform_ms(self._h, ctypes.byref(b)), "jxlhip_enc_last_transform_ms")
         return a.value, b.value
 
+    def enc_aq_ms(self):
+        """Measurement: ms of the two adaptive-quant kernels in the last forward pass made with adaptive_quant=1."""
+        L = lib()
+        L.jxlhip_enc_aq_last_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+        a = ctypes.c_float()
+        _check(L.jxlhip_enc_aq_last_ms(self._h, ctypes.byref(a)), "jxlhip_enc_aq_last_ms")
+        return a.value
+
     def debug_ans_write(self, tokens, tables, capacity=None):
         """Test access: rANS-codes `tokens` ((n, 2) uint32 {context, value} pairs) as one section with the device's entropy
         kernels and the code `tables` (an AnsTables). Returns (the bit string as bytes, its length in bits); `capacity`
@@ -546,7 +554,7 @@ class EncParams(ctypes.Structure):
                 ("zero_ac", ctypes.c_int32), ("num_histograms", ctypes.c_int32), ("big_coeffs", ctypes.c_int32), ("num_passes", ctypes.c_int32), ("upsampling", ctypes.c_int32), ("custom_orders", ctypes.c_int32), ("custom_bctx", ctypes.c_int32),
                 ("custom_cmap", ctypes.c_int32), ("custom_lf", ctypes.c_int32), ("ac_code_mode", ctypes.c_int32),
                 ("noise", ctypes.c_int32), ("cfl_fit", ctypes.c_int32), ("color_transform", ctypes.c_int32), ("raw_quant", ctypes.c_int32),
-                ("chroma_subsampling", ctypes.c_int32), ("ec_upsampling", ctypes.c_int32)]
+                ("chroma_subsampling", ctypes.c_int32), ("ec_upsampling", ctypes.c_int32), ("adaptive_quant", ctypes.c_int32)]
 
 
 class EncHistDesc(ctypes.Structure):  # JxlHipEncHistDesc
@@ -1028,6 +1036,30 @@ def enc_forward_model(img, ctx=None, **kw):
     if r:
         raise JxlAmdError("jxlenc_forward_model failed (%d)" % r)
     return dict(acs=acs, qf=qf, dc=dc, coeffs=co)
+
+
+def initial_quant_field(xyb, distance, ctx=None, rescale=1.0):
+    """The reference's initial adaptive quant field of X, Y, B planes [3][ysize][xsize] (float32, sizes multiples of 8) built
+    for `distance` (the frame's, or 0.62 of it for a frame without Gaborish): (aq_map, mask), both [ysize / 8][xsize / 8].
+    On the GPU (jxlhip_enc_initial_quant_field on `ctx`), or from the CPU stream writer's own code when ctx is None."""
+    xyb = np.ascontiguousarray(xyb, np.float32)
+    if xyb.ndim != 3 or xyb.shape[0] != 3:
+        raise ValueError("xyb: [3][ysize][xsize]")
+    ys, xs = xyb.shape[1:]
+    aq, mask = np.zeros((ys // 8, xs // 8), np.float32), np.zeros((ys // 8, xs // 8), np.float32)
+    tail = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
+    args = (xyb.ctypes.data, xs, ys, float(distance), float(rescale), aq.ctypes.data, mask.ctypes.data)
+    if ctx is not None:
+        L = lib()
+        L.jxlhip_enc_initial_quant_field.argtypes = [ctypes.c_void_p] + tail
+        _check(L.jxlhip_enc_initial_quant_field(ctx._h, *args), "jxlhip_enc_initial_quant_field")
+    else:
+        E = _enc_lib()
+        E.jxlenc_cpu_initial_quant_field.argtypes = tail
+        r = E.jxlenc_cpu_initial_quant_field(*args)
+        if r:
+            raise JxlAmdError("jxlenc_cpu_initial_quant_field failed (%d)" % r)
+    return aq, mask
 
 
 def encode_rgba8(img, **kw):

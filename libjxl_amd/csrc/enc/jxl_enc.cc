@@ -1265,6 +1265,9 @@ struct Params {
                            //     4:2:2 = 8, 4:4:0 = 12. Only transforms that cover one block; no adaptive DC smoothing.
   int32_t ec_upsampling;   // jxlenc_encode_rgba8: the alpha channel is coded at ceil(size / this) (0/1, 2, 4, 8; at least `upsampling`,
                            //     at most four times it) and flagged for upsampling (frame_header.cc:265-283)
+  int32_t adaptive_quant;  // 1 = image mode writes the reference's initial adaptive quant field (InitialQuantField below) in
+                           //     place of the activity rule, and the global scale the reference derives for it; XYB frames
+                           //     without subsampling, strategy_mode 0 or 1
 };
 
 static bool Fits(const FrameModel& f, size_t bx, size_t by, int st) {
@@ -1966,12 +1969,14 @@ static bool TokensCodable(const Token* tk, size_t n, const EncCode& code) {
   return true;
 }
 
-static void QuantParams(float distance, FrameModel* f, float* quant_ac) {
+// adaptive: the global scale comes from the median the reference assumes for its initial quant field, 0.39 / distance
+// (enc_heuristics.cc:1128-1129 -> quantizer.cc:45-76 ComputeGlobalScaleAndQuant), instead of from the AC target.
+static void QuantParams(float distance, FrameModel* f, float* quant_ac, bool adaptive = false) {
   const float kAcQuant = 0.765f, kDcQuant = 1.095924047623553f, kDcMul = 0.3f, kDcQuantPow = 0.83f;
   float target_dc = std::max(0.5f * distance, std::min(distance, kDcMul * std::pow((1.0f / kDcMul) * distance, kDcQuantPow)));
   float qdc = std::min(kDcQuant / target_dc, 50.0f);
   float qac = kAcQuant / distance;
-  float scale = 65536.0f * qac / 5.0f;
+  float scale = 65536.0f * (adaptive ? float(0.39 / distance) : qac) / 5.0f;
   scale = std::max(1.0f, std::min(32768.0f, scale));
   int gs = int(scale);
   int scaled_qdc = int(qdc * 4096 * 1.6);
@@ -1981,6 +1986,135 @@ static void QuantParams(float distance, FrameModel* f, float* quant_ac) {
   f->quant_dc = uint32_t(std::min<float>(65536.0f, qdc * inv_gs + 0.5f));
   if (f->quant_dc < 1) f->quant_dc = 1;
   *quant_ac = qac;
+}
+
+// ---- the reference's initial adaptive quant field (lib/jxl/enc_adaptive_quantization.cc: ComputeTile :528-628, FuzzyErosion
+// :389-449, PerBlockModulations :315-348, ComputeMask :95-117, the gamma / high-frequency / blue modulations :127-313),
+// float32 with every expression written once and not contracted; csrc/hip/jxl_hip_enc.h restates it operation by operation.
+// The order of every sum:
+//   cell (4x4 pixels)   per column the four rows top to bottom, then (c0 + c1 + c2 + c3) * 0.25 left to right
+//   erosion             w0 * m0 + w1 * m1 + w2 * m2 + w3 * m3 left to right, m ascending; the block's cells in raster order
+//   64-sample sums      per row left to right (a sample's two terms in the order written), then the row sums as
+//                       ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7))
+//   aggregation         AdjustQuantField's: the covered blocks in raster order
+// log2f / exp2f are the exact functions where the reference has FastLog2f / FastPow2f (rational approximations, relative
+// error 3e-7: base/fast_math-inl.h). The reference's 64x64 tiles carry one border cell of their neighbours
+// (:534-537, from_rect :614), so its result is that of one cell image over the whole plane: what is computed here.
+struct AqParams {
+  float w[4];      // erosion weights of the four smallest of a 3x3 neighbourhood
+  float mul, add;  // scale * dampen, (1 - dampen) * 0.48 * scale
+};
+static AqParams MakeAqParams(float target, float rescale) {
+  AqParams a;
+  const float scale = 0.765f / target * rescale;
+  const float base_level = 0.48f * scale;
+  float dampen = 1.0f;
+  if (target >= 2.0f) {
+    dampen = 1.0f - ((target - 2.0f) / (14.0f - 2.0f));
+    if (dampen < 0) dampen = 0;
+  }
+  a.mul = scale * dampen;
+  a.add = (1.0f - dampen) * base_level;
+  const float kMulBase[4] = {0.125f, 0.1f, 0.09f, 0.06f}, kMulAdd[4] = {0.0f, -0.1f, -0.09f, -0.06f};
+  const float mul = target < 2.0f ? (2.0f - target) * (1.0f / 2.0f) : 0.0f;
+  float norm_sum = 0.0f;
+  for (int i = 0; i < 4; i++) {
+    a.w[i] = kMulBase[i] + mul * kMulAdd[i];
+    norm_sum += a.w[i];
+  }
+  for (int i = 0; i < 4; i++) a.w[i] *= 0.29959705784054957f / norm_sum;
+  return a;
+}
+template <bool kInvert>
+static inline float AqGammaRatio(float v) {
+  const float kInvLog2e = 0.6931471805599453f, kSGmul = 226.77216153508914f, kSGmul2 = 1.0f / 73.377132366608819f;
+  const float kSGRetMul = kSGmul2 * 18.6580932135f * kInvLog2e, kSGVOffset = 7.7825991679894591f, kEpsilon = 1e-2f;
+  const float kNumMul = kSGRetMul * 3 * kSGmul, kVOffset = kSGVOffset * kInvLog2e + kEpsilon, kDenMul = kInvLog2e * kSGmul;
+  v = v < 0.0f ? 0.0f : v;
+  const float v2 = v * v;
+  const float num = kNumMul * v2 + kEpsilon, den = (kDenMul * v) * v2 + kVOffset;
+  return kInvert ? num / den : den / num;
+}
+// planes X, Y, B of xp x yp samples (multiples of 8); aq [yp / 8][xp / 8]; mask the same, may be NULL
+static void InitialQuantField(const float* px, const float* py, const float* pb, size_t xp, size_t yp, float target, float rescale,
+                              float* aq, float* mask) {
+  const AqParams A = MakeAqParams(target, rescale);
+  const size_t cw = xp / 4, ch = yp / 4, xb = xp / 8, yb = yp / 8;
+  std::vector<float> cells(cw * ch);
+  const float kSqrtMul = std::sqrt(float(211.66567973503678f * 1e8)), kLogOffset = 27.505837037000106f;
+#pragma omp parallel for
+  for (size_t cy = 0; cy < ch; cy++) {
+    std::vector<float> col(xp);
+    for (size_t y = cy * 4; y < cy * 4 + 4; y++) {
+      const float* row = py + y * xp;
+      const float* up = py + (y ? y - 1 : y) * xp;
+      const float* down = py + (y + 1 < yp ? y + 1 : y) * xp;
+      for (size_t x = 0; x < xp; x++) {
+        const float left = row[x ? x - 1 : x], right = row[x + 1 < xp ? x + 1 : x];
+        const float base = 0.25f * (down[x] + up[x] + left + right);
+        float d = AqGammaRatio<false>(row[x] + 0.019f) * (row[x] - base);
+        d *= d;
+        d = d >= 0.2f ? 0.2f : d;
+        const float p = 0.25f * std::sqrt(d * kSqrtMul + kLogOffset);
+        col[x] = (y & 3) ? col[x] + p : p;
+      }
+    }
+    for (size_t cx = 0; cx < cw; cx++) cells[cy * cw + cx] = (col[cx * 4] + col[cx * 4 + 1] + col[cx * 4 + 2] + col[cx * 4 + 3]) * 0.25f;
+  }
+  auto tree = [](const float (&r)[8]) { return ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7])); };
+#pragma omp parallel for
+  for (size_t by = 0; by < yb; by++)
+    for (size_t bx = 0; bx < xb; bx++) {
+      float e = 0.0f;
+      for (size_t k = 0; k < 4; k++) {
+        const size_t cy = by * 2 + (k >> 1), cx = bx * 2 + (k & 1);
+        const size_t ya = cy ? cy - 1 : cy, yc = cy + 1 < ch ? cy + 1 : cy, xa = cx ? cx - 1 : cx, xc = cx + 1 < cw ? cx + 1 : cx;
+        float nb[9] = {cells[ya * cw + xa], cells[ya * cw + cx], cells[ya * cw + xc], cells[cy * cw + xa], cells[cy * cw + cx],
+                       cells[cy * cw + xc], cells[yc * cw + xa], cells[yc * cw + cx], cells[yc * cw + xc]};
+        std::partial_sort(nb, nb + 4, nb + 9);
+        const float v = A.w[0] * nb[0] + A.w[1] * nb[1] + A.w[2] * nb[2] + A.w[3] * nb[3];
+        e = k ? e + v : v;
+      }
+      if (mask) mask[by * xb + bx] = 1.0f / (e + 0.001f);
+      float m;
+      {
+        const float kOffset3 = 3.7179635626140772f, kOffset4 = 0.25f * kOffset3;
+        const float v1 = std::max(e * 0.80061762862741759f, 1e-3f);
+        const float v2 = 1.0f / (v1 + 302.59587815579727f);
+        const float v3 = 1.0f / (v1 * v1 + kOffset3);
+        const float v4 = 1.0f / (v1 * v1 + kOffset4);
+        m = -0.7647f + (9.4708735624378946f * v4 + (17.35036561631863f * v2 + 6.7943250517376494f * v3));
+      }
+      float rg[8], rh[8], rb[8];
+      for (size_t r = 0; r < 8; r++) {
+        const size_t o = (by * 8 + r) * xp + bx * 8;
+        const float *X = px + o, *Y = py + o, *B = pb + o;
+        const float* N = r == 7 ? Y : Y + xp;  // the row below; row 7 pairs with itself
+        float sg = 0.0f, sh = 0.0f, sb = 0.0f;
+        for (size_t x = 0; x < 8; x++) {
+          const float iny = Y[x] + 0.16f;
+          sg += AqGammaRatio<true>(iny - X[x]);
+          sg += AqGammaRatio<true>(iny + X[x]);
+          if (x < 7) sh += std::min(0.0206f, std::fabs(Y[x] - Y[x + 1]));
+          sh += std::min(0.0206f, std::fabs(Y[x] - N[x]));
+          const float pye = (Y[x] + 0.0031994768654636393f) + std::fabs(X[x]);
+          sb += B[x] > pye ? std::min(B[x] - pye, 0.010474084867598155f) : 0.0f;
+        }
+        rg[r] = sg;
+        rh[r] = sh;
+        rb[r] = sb;
+      }
+      const float sg = tree(rg), sh = tree(rh);
+      float sb = tree(rb);
+      m = 0.1005613337192697f * std::log2(sg * (0.5f / 64)) + m;
+      const float hf = (sh * -0.38f + 0.42f) + m;
+      const float kLimit = 0.010474084867598155f, kMaxLimit = 15.463398341612438f;
+      if (sb >= 32 * kLimit) sb = 64 * kLimit - sb;
+      if (sb >= kMaxLimit * kLimit) sb = kMaxLimit * kLimit;
+      sb *= 0.90590804735610064f;
+      const float blue = sb + m;
+      aq[by * xb + bx] = std::exp2(std::min(hf, blue) * 1.442695041f) * A.mul + A.add;
+    }
 }
 
 // The pixel-domain half of the encode done elsewhere (the HIP forward path, jxlhip_enc_forward of include/jxl_amd_hip.h,
@@ -2035,8 +2169,12 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
   f.img_xs = img_xs ? img_xs : xs;
   f.img_ys = img_ys ? img_ys : ys;
   const size_t xp = f.xb * 8, yp = f.yb * 8;
+  if (p.adaptive_quant != 0 && p.adaptive_quant != 1) throw std::runtime_error("adaptive_quant: 0 or 1");
+  const bool adaptive = p.adaptive_quant == 1;
+  // (the field is defined over XYB planes at full resolution, under this writer's own transform choices)
+  if (adaptive && (p.color_transform || f.Subsampled() || p.strategy_mode > 1)) throw std::runtime_error("adaptive_quant: unsupported parameters");
   float quant_ac;
-  QuantParams(p.distance, &f, &quant_ac);
+  QuantParams(p.distance, &f, &quant_ac, adaptive);
   f.gab = p.gab < 0 ? 1 : p.gab;
   if (hook) {
     // image mode with the default colour correlation only: what the device path implements
@@ -2077,6 +2215,7 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
     d.quant_dc = f.quant_dc;
     d.quant_ac = quant_ac;
     d.cfl_fit = p.cfl_fit ? 1 : 0;
+    d.quant_field_mode = adaptive ? 1 : 0;
     d.ytox = f.ytox.data();
     d.ytob = f.ytob.data();
     const size_t nb = f.xb * f.yb, ng = DivCeil(xs, 256) * DivCeil(ys, 256);
@@ -2185,6 +2324,12 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
   std::vector<float> xyb[3];
   if (p.color_transform) RgbToPlain(rgb, xs, ys, xp, yp, p.color_transform == 2, xyb);
   else RgbToXyb(rgb, xs, ys, xp, yp, xyb);
+  std::vector<float> aq_map;
+  if (adaptive) {
+    // before the sharpening, at 0.62 of the distance when the frame has no Gaborish (enc_heuristics.cc:1118-1143)
+    aq_map.resize(f.xb * f.yb);
+    InitialQuantField(xyb[0].data(), xyb[1].data(), xyb[2].data(), xp, yp, f.gab ? p.distance : p.distance * 0.62f, 1.0f, aq_map.data(), nullptr);
+  }
   if (f.gab) {
     // Approximate inverse of the decoder's Gaborish blur K (3x3, default weights): y <- y + (x - K*y), 4 rounds.
     const float w1 = 1.1f * 0.104699568f, w2 = 1.1f * 0.055680538f, nrm = 1.0f / (1.0f + 4 * (w1 + w2));
@@ -2299,11 +2444,33 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
       Place(f, bx, by, st);
     }
   // adaptive quant field
+  // (adaptive_quant: AdjustQuantField, enc_adaptive_quantization.cc:1198-1247, with the frame's own distance: the largest
+  // value under the transform, mixed with the mean from four blocks on; then Quantizer::SetQuantFieldRect, quantizer.cc:78-88)
+  float mean_max_mixer = 1.0f;
+  if (p.distance > 1.54138f) mean_max_mixer = std::max(0.0f, 1.0f - (p.distance - 1.54138f) * 0.56391f);
   for (size_t by = 0; by < f.yb; by++)
     for (size_t bx = 0; bx < f.xb; bx++) {
       uint8_t a = f.acs[by * f.xb + bx];
       if (!(a & 1)) continue;
       int st = a >> 1;
+      if (adaptive) {
+        const size_t cx = jxh::kCoveredX[st], cy = jxh::kCoveredY[st];
+        float mx = aq_map[by * f.xb + bx], mean = 0.0f;
+        for (size_t yy = 0; yy < cy; yy++)
+          for (size_t xx = 0; xx < cx; xx++) {
+            const float v = aq_map[(by + yy) * f.xb + bx + xx];
+            mean += v;
+            mx = std::max(v, mx);
+          }
+        mean /= float(cy * cx);
+        if (cy * cx >= 4) {
+          mx *= mean_max_mixer;
+          mx += (1.0f - mean_max_mixer) * mean;
+        }
+        const float inv_gs = 65536.0f / float(f.global_scale);
+        f.qf[by * f.xb + bx] = int(std::max(1.0f, std::min(mx * inv_gs + 0.5f, 256.0f)));
+        continue;
+      }
       float m = region_max(bx, by, jxh::kCoveredX[st], jxh::kCoveredY[st]);
       float mul = 1.35f - 0.12f * std::log2(1.0f + m * 400.0f);
       mul = std::max(0.8f, std::min(1.4f, mul));
@@ -3375,6 +3542,7 @@ struct JxlEncParams {
   int32_t raw_quant;       // 1 = RAW dequantisation table for the 8x8 DCT, see jxe::Params
   int32_t chroma_subsampling;  // YCbCr frames: channel modes of Cb, Y, Cr (4 = 4:2:0, 8 = 4:2:2, 12 = 4:4:0), see jxe::Params
   int32_t ec_upsampling;   // jxlenc_encode_rgba8: upsampling factor of the alpha channel, see jxe::Params
+  int32_t adaptive_quant;  // 1 = the reference's initial adaptive quant field, see jxe::Params
 };
 
 // The next VarDCT streams code their own upsampling weights (mask bit k: the 2^(k+1)-fold matrix; 0: default weights again).
@@ -3642,6 +3810,7 @@ int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHi
   q.gab = int32_t(d->gaborish);
   q.strategy_mode = int32_t(d->strategy_mode);
   q.cfl_fit = int32_t(d->cfl_fit);
+  q.adaptive_quant = int32_t(d->quant_field_mode);
   q.seed = 1;
   std::vector<uint8_t> tight;
   if (stride != size_t(d->xsize) * 3) {
@@ -3655,7 +3824,7 @@ int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHi
   } catch (...) {
     return -2;
   }
-  if (f.global_scale != d->global_scale || f.quant_dc != d->quant_dc) return -3;  // the descriptor is not this distance's
+  if (f.global_scale != d->global_scale || f.quant_dc != d->quant_dc) return -3;  // the descriptor is not this distance's and quant field mode's
   const size_t nb = f.xb * f.yb;
   memcpy(acs, f.acs.data(), nb);
   if (d->ytox) memcpy(d->ytox, f.ytox.data(), f.ytox.size());
@@ -3781,6 +3950,7 @@ int jxlenc_forward_cpu(void*, const uint8_t* rgb, size_t stride, const JxlHipEnc
   q.gab = int32_t(d->gaborish);
   q.strategy_mode = int32_t(d->strategy_mode);
   q.cfl_fit = int32_t(d->cfl_fit);
+  q.adaptive_quant = int32_t(d->quant_field_mode);
   q.seed = 1;
   std::vector<uint8_t> tight;
   if (stride != size_t(d->xsize) * 3) {
@@ -3794,7 +3964,7 @@ int jxlenc_forward_cpu(void*, const uint8_t* rgb, size_t stride, const JxlHipEnc
   } catch (...) {
     return -2;
   }
-  if (f.global_scale != d->global_scale || f.quant_dc != d->quant_dc) return -3;  // the descriptor is not this distance's
+  if (f.global_scale != d->global_scale || f.quant_dc != d->quant_dc) return -3;  // the descriptor is not this distance's and quant field mode's
   const size_t nb = f.xb * f.yb;
   memcpy(acs, f.acs.data(), nb);
   if (d->ytox) memcpy(d->ytox, f.ytox.data(), f.ytox.size());
@@ -3802,6 +3972,21 @@ int jxlenc_forward_cpu(void*, const uint8_t* rgb, size_t stride, const JxlHipEnc
   memcpy(qf, f.qf.data(), nb * 4);
   for (int c = 0; c < 3; c++) memcpy(dc + c * nb, f.dc[c].data(), nb * 4);
   for (size_t g = 0; g < f.coeffs.size(); g++) memcpy(coeffs + g * 3 * 65536, f.coeffs[g].data(), size_t(3) * 65536 * 4);
+  return 0;
+}
+
+// The CPU double of jxlhip_enc_initial_quant_field (include/jxl_amd_hip.h): the same arguments without the context.
+int jxlenc_cpu_initial_quant_field(const float* xyb, uint32_t xsize, uint32_t ysize, float butteraugli_target, float rescale, float* aq_map,
+                                   float* mask) {
+  jxe::UseThreads();
+  if (!xyb || !aq_map || !xsize || !ysize || (xsize & 7) || (ysize & 7) || xsize > (1u << 18) || ysize > (1u << 18)) return -1;
+  if (!(butteraugli_target > 0) || !(rescale > 0) || !std::isfinite(butteraugli_target) || !std::isfinite(rescale)) return -1;
+  const size_t plane = size_t(xsize) * ysize;
+  try {
+    jxe::InitialQuantField(xyb, xyb + plane, xyb + 2 * plane, xsize, ysize, butteraugli_target, rescale, aq_map, mask);
+  } catch (...) {
+    return -2;
+  }
   return 0;
 }
 

@@ -250,7 +250,7 @@ struct JxlHipContext {
   uint32_t out_type = 2, out_nc = 3, out_bits = 8, out_swap = 0;
   // forward (encoder) path, jxlhip_enc_forward: device buffers and the kernel time of the last call
   Buf enc_rgb, enc_planes[3], enc_act, enc_acs, enc_qf, enc_off, enc_dc, enc_coef, enc_lut, enc_dq, enc_ytox, enc_ytob;
-  hipEvent_t enc_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // whole sequence; the transform kernel of its last pass
+  hipEvent_t enc_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // whole sequence; the transform kernel of its last pass; the two adaptive-quant kernels of its last pass (quant_field_mode 1)
   bool enc_timed = false;
   jxlhip::EncTok enc_tok;      // jxlhip_enc_token_counts -> jxlhip_enc_tokens
   bool enc_tok_ready = false;
@@ -264,6 +264,8 @@ struct JxlHipContext {
   Buf ent_counts, ent_status, ent_grp, ent_tab, ent_rec, ent_fl, ent_small, ent_out, ent_obase;
   hipEvent_t ent_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // histograms; records + chain; scatter
   jxlhip::EncFwd enc_last;     // the parameters of the last jxlhip_enc_forward (its input stays resident): jxlhip_enc_forward_rerun
+  jxlhip::EncAq enc_last_aq;   // ... and of its adaptive quant field (quant_field_mode 1)
+  Buf enc_aq_cells, enc_aq_map, enc_aq_mask, enc_aq_in;  // cell image, field, masking; the planes of jxlhip_enc_initial_quant_field
   bool enc_last_gaborish = false;
   uint32_t out_orient = 0;  // jxlhip_set_output_orientation: PixelOut::orient bits (0 = the image as coded)
   bool out_unpremul = false;  // jxlhip_set_output_unpremultiply (PixelOut::orient bit 3 for outputs that carry alpha)
@@ -549,7 +551,7 @@ static std::vector<Buf*> AllBufs(JxlHipContext* c) {
                 &c->plane[2], &c->rgb, &c->tlist, &c->scratch, &c->ep_dev, &c->batch_params, &c->batch_map, &c->batch_lanes, &c->ups_kernel, &c->kend, &c->block_recs, &c->dequant_scan, &c->ec_stage, &c->alpha_patched, &c->trecs, &c->enc_tok_orders, &c->enc_tok_blk, &c->enc_tok_info,
                 &c->enc_tok_off, &c->enc_tok_nzmap, &c->enc_tok_small, &c->enc_tok_out, &c->enc_tok_base, &c->tb_params, &c->tb_desc, &c->fb_params, &c->alpha, &c->sec_end, &c->lz_window, &c->mod.pool, &c->mod.sections, &c->mod.blob, &c->mod.streams,
                 &c->mod.rects, &c->mod.status, &c->mod.end_bits, &c->mod.scratch, &c->mod.windows, &c->mod.batch_streams, &c->mod.batch_ops, &c->frame_blob, &c->noise, &c->spl_seg, &c->spl_row_start, &c->spl_row_seg, &c->spl_planes, &c->pat_rec, &c->pat_row_start, &c->pat_row_list,
-                &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes,
+                &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in,
                 &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
   for (auto& pb : c->pass_bufs)
     for (Buf* b : {&pb.ctx_map, &pb.alias, &pb.cfg, &pb.orders, &pb.ptable, &pb.poffset, &pb.alias_packed}) all.push_back(b);
@@ -3983,6 +3985,47 @@ int jxlhip_canvas_download_alpha(JxlHipCanvas* v, float* dst, size_t n) {
 }
 
 // ---- forward path: see jxl_hip_enc.h
+// The two kernels of the adaptive quant field (jxl_hip_enc.h) on the context's stream.
+static void EncAqLaunch(JxlHipContext* c, const jxlhip::EncAq& A) {
+  const uint32_t strips = (A.xp + jxlhip::kAqCols - 1) / jxlhip::kAqCols;
+  hipLaunchKernelGGL(jxlhip::k_enc_aq_cells, dim3((strips + 3) / 4, (A.yp + jxlhip::kAqRows - 1) / jxlhip::kAqRows), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(jxlhip::k_enc_aq_blocks, dim3((A.xb + 7) / 8, A.yb), dim3(64), 0, c->stream, A);
+}
+// The parameters of the field that depend on the distance alone (enc_adaptive_quantization.cc:319-331 dampen, :397-412
+// erosion weights, :1268-1270 scale): float32, as csrc/enc/jxl_enc.cc AqParams states them.
+static void EncAqParams(float target, float rescale, jxlhip::EncAq* A) {
+  const float scale = 0.765f / target * rescale;
+  const float base_level = 0.48f * scale;
+  float dampen = 1.0f;
+  if (target >= 2.0f) {
+    dampen = 1.0f - ((target - 2.0f) / (14.0f - 2.0f));
+    if (dampen < 0) dampen = 0;
+  }
+  A->mul = scale * dampen;
+  A->add = (1.0f - dampen) * base_level;
+  const float kMulBase[4] = {0.125f, 0.1f, 0.09f, 0.06f}, kMulAdd[4] = {0.0f, -0.1f, -0.09f, -0.06f};
+  const float mul = target < 2.0f ? (2.0f - target) * (1.0f / 2.0f) : 0.0f;
+  float norm_sum = 0.0f;
+  for (int i = 0; i < 4; i++) {
+    A->w[i] = kMulBase[i] + mul * kMulAdd[i];
+    norm_sum += A->w[i];
+  }
+  for (int i = 0; i < 4; i++) A->w[i] *= 0.29959705784054957f / norm_sum;
+}
+static int EncAqEnsure(JxlHipContext* c, uint32_t xp, uint32_t yp, jxlhip::EncAq* A) {
+  const size_t nb = size_t(xp / 8) * (yp / 8);
+  int r;
+  if ((r = c->enc_aq_cells.Ensure(nb * 4 * 4)) || (r = c->enc_aq_map.Ensure(nb * 4)) || (r = c->enc_aq_mask.Ensure(nb * 4))) return r;
+  A->cells = c->enc_aq_cells.as<float>();
+  A->aq = c->enc_aq_map.as<float>();
+  A->mask = c->enc_aq_mask.as<float>();
+  A->xp = xp;
+  A->yp = yp;
+  A->xb = xp / 8;
+  A->yb = yp / 8;
+  return 0;
+}
+
 // The kernel sequence of the forward path on the context's stream (P.planes is set on the way).
 static int EncLaunch(JxlHipContext* c, jxlhip::EncFwd& P, bool gaborish) {
   const size_t nb = size_t(P.xb) * P.yb, ng = size_t(P.xg) * P.yg;
@@ -3991,6 +4034,16 @@ static int EncLaunch(JxlHipContext* c, jxlhip::EncFwd& P, bool gaborish) {
   const dim3 px_grid((P.xp + 255) / 256, P.yp);
   P.planes = gaborish ? sets[2] : sets[0];
   hipLaunchKernelGGL(jxlhip::k_enc_xyb, px_grid, dim3(256), 0, c->stream, P);
+  if (P.quant_field_mode) {  // the adaptive quant field, from the planes before the sharpening (enc_heuristics.cc:1118-1143)
+    jxlhip::EncAq& A = c->enc_last_aq;
+    int r = EncAqEnsure(c, P.xp, P.yp, &A);  // (jxlhip_enc_initial_quant_field shares the buffers and may have grown them since)
+    if (r) return r;
+    P.aq_map = A.aq;
+    A.planes = P.planes;
+    HIP_TRY(hipEventRecord(c->enc_ev[4], c->stream));
+    EncAqLaunch(c, A);
+    HIP_TRY(hipEventRecord(c->enc_ev[5], c->stream));
+  }
   if (gaborish) {
     if (getenv("JXLHIP_ENC_SHARPEN_ROUNDS")) {  // the one-round-per-launch form: orig = sets[2]; 2 -> 0 -> 1 -> 0 -> 1
       const dim3 g3(px_grid.x, px_grid.y, 3);
@@ -4011,7 +4064,8 @@ static int EncLaunch(JxlHipContext* c, jxlhip::EncFwd& P, bool gaborish) {
   }
   hipLaunchKernelGGL(jxlhip::k_enc_activity, dim3((P.xb + 7) / 8, P.yb), dim3(64), 0, c->stream, P);
   const uint32_t tiles = ((P.xb + 7) / 8) * ((P.yb + 7) / 8);
-  hipLaunchKernelGGL(jxlhip::k_enc_select, dim3(tiles), dim3(64), 0, c->stream, P);
+  if (P.quant_field_mode) hipLaunchKernelGGL(jxlhip::k_enc_select<true>, dim3(tiles), dim3(64), 0, c->stream, P);
+  else hipLaunchKernelGGL(jxlhip::k_enc_select<false>, dim3(tiles), dim3(64), 0, c->stream, P);
   hipLaunchKernelGGL(jxlhip::k_enc_offsets, dim3(uint32_t(ng)), dim3(64), 0, c->stream, P);
   HIP_TRY(hipMemsetAsync(c->enc_coef.p, 0, ng * 3 * 65536 * 4, c->stream));
   HIP_TRY(hipEventRecord(c->enc_ev[2], c->stream));
@@ -4028,7 +4082,8 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
                        int32_t* coeffs) {
   if (!c || !rgb || !d || !acs || !qf || !dc) return JXLHIP_ERR_INVALID_ARGUMENT;  // (coeffs may be NULL: they stay on the device)
   if (!d->xsize || !d->ysize || d->xsize > (1u << 18) || d->ysize > (1u << 18) || stride < size_t(d->xsize) * 3) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!(d->distance > 0) || !d->global_scale || !d->quant_dc || !d->dequant || d->strategy_mode > 1) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!(d->distance > 0) || !d->global_scale || !d->quant_dc || !d->dequant || d->strategy_mode > 1 || d->quant_field_mode > 1)
+    return JXLHIP_ERR_INVALID_ARGUMENT;
   for (int k = 0; k < 17; k++)
     if (size_t(d->dequant_offset[k]) + 3 * size_t(d->dequant_size[k]) > d->dequant_floats) return JXLHIP_ERR_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
@@ -4091,6 +4146,15 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
   P.scale = float(d->global_scale) / 65536.0f;
   P.ytox = c->enc_ytox.as<int8_t>();
   P.ytob = c->enc_ytob.as<int8_t>();
+  P.quant_field_mode = d->quant_field_mode;
+  if (P.quant_field_mode) {
+    jxlhip::EncAq& A = c->enc_last_aq;
+    // enc_heuristics.cc:1119-1122: the field's distance is 0.62 of the frame's without Gaborish; rescale 1
+    EncAqParams(d->gaborish ? d->distance : d->distance * 0.62f, 1.0f, &A);
+    // enc_adaptive_quantization.cc:1207-1218, with the frame's own distance
+    P.mean_max_mixer = 1.0f;
+    if (d->distance > 1.54138f) P.mean_max_mixer = std::max(0.0f, 1.0f - (d->distance - 1.54138f) * 0.56391f);
+  }
   HIP_TRY(hipMemsetAsync(c->enc_ytox.p, 0, ntiles, c->stream));
   HIP_TRY(hipMemsetAsync(c->enc_ytob.p, 0, ntiles, c->stream));
   HIP_TRY(hipEventRecord(c->enc_ev[0], c->stream));
@@ -4389,6 +4453,37 @@ int jxlhip_enc_entropy_last_ms(JxlHipContext* c, float* ms) {
     }
   ms[0] = t[0];
   ms[1] = t[1] + t[2];
+  return 0;
+}
+
+int jxlhip_enc_initial_quant_field(JxlHipContext* c, const float* xyb, uint32_t xsize, uint32_t ysize, float butteraugli_target, float rescale,
+                                   float* aq_map, float* mask) {
+  if (!c || !xyb || !aq_map || !xsize || !ysize || (xsize & 7) || (ysize & 7) || xsize > (1u << 18) || ysize > (1u << 18))
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!(butteraugli_target > 0) || !(rescale > 0) || !std::isfinite(butteraugli_target) || !std::isfinite(rescale)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  jxlhip::EncAq A;  // (its own planes and parameters: the last forward call's stay what jxlhip_enc_forward_rerun replays)
+  memset(&A, 0, sizeof(A));
+  const size_t plane = size_t(xsize) * ysize, nb = plane / 64;
+  int r;
+  if ((r = c->enc_aq_in.Ensure(3 * plane * 4)) || (r = EncAqEnsure(c, xsize, ysize, &A))) return r;
+  EncAqParams(butteraugli_target, rescale, &A);
+  A.planes = c->enc_aq_in.as<float>();
+  HIP_TRY(hipMemcpyAsync(c->enc_aq_in.p, xyb, 3 * plane * 4, hipMemcpyHostToDevice, c->stream));
+  EncAqLaunch(c, A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(aq_map, A.aq, nb * 4, hipMemcpyDeviceToHost, c->stream));
+  if (mask) HIP_TRY(hipMemcpyAsync(mask, A.mask, nb * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int jxlhip_enc_aq_last_ms(JxlHipContext* c, float* ms) {
+  if (!c || !ms) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->enc_timed || !c->enc_last.quant_field_mode) return JXLHIP_ERR_NO_FRAME;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->enc_ev[5]));
+  HIP_TRY(hipEventElapsedTime(ms, c->enc_ev[4], c->enc_ev[5]));
   return 0;
 }
 

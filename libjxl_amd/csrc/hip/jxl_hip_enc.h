@@ -2,10 +2,13 @@
 // activity, transform selection + quant field, forward DCT + DC extraction + quantisation with chroma-from-luma.
 // What the reference does in enc_xyb.cc:83-174 (SRGBToXYB), enc_gaborish.cc:21-70, enc_group.cc:380-533
 // (ComputeCoefficients: TransformFromPixels, DCFromLowestFrequencies, QuantizeBlockAC / QuantizeRoundtripYBlockAC) and
-// enc_transforms-inl.h. The selection heuristics are the ones of this repo's CPU stream writer (csrc/enc), NOT the
-// reference's AC-strategy search / adaptive quantisation / Butteraugli loop (enc_ac_strategy.cc:827-1068,
-// enc_adaptive_quantization.cc:664-1115): those stay out of this slice. Every float expression keeps the operation order
-// of the CPU writer with contraction off, so that the two agree except where cbrtf / log2f differ in the last place.
+// enc_transforms-inl.h. The transform selection is the one of this repo's CPU stream writer (csrc/enc), NOT the
+// reference's AC-strategy search (enc_ac_strategy.cc:827-1068), and there is no Butteraugli loop
+// (enc_adaptive_quantization.cc:707-1115): those stay out. The quant field is the writer's own activity rule by default;
+// with quant_field_mode 1 it is the reference's initial adaptive quant field (enc_adaptive_quantization.cc:88-449,
+// 466-628, 1198-1247: k_enc_aq_cells, k_enc_aq_blocks and the tail of k_enc_select<true>). Every float expression keeps the
+// operation order of the CPU writer with contraction off, so that the two agree except where cbrtf / log2f / exp2f differ
+// in the last place.
 #ifndef JXL_HIP_ENC_H_
 #define JXL_HIP_ENC_H_
 
@@ -36,6 +39,11 @@ struct EncFwd {
   float scale;  // Quantizer::Scale() = global_scale / 65536
   int8_t* ytox;
   int8_t* ytob;
+  // quant_field_mode 1 (k_enc_select<true>): the adaptive quant field per block before aggregation (k_enc_aq_blocks, from
+  // an EncAq over the planes before the sharpening) and the max / mean mix of AdjustQuantField
+  uint32_t quant_field_mode;
+  const float* aq_map;  // [yb][xb]
+  float mean_max_mixer;
 };
 
 // enc_xyb.cc:50-104: opsin absorbance matrix + bias, cube root, X = (L - M) / 2, Y = (L + M) / 2, B = S.
@@ -177,9 +185,182 @@ __global__ void k_enc_activity(EncFwd P) {
   if (live && row == 0) P.act[size_t(by) * P.xb + bx] = a / 64;
 }
 
+// ---------------------------------------------------------------- adaptive quant field (quant_field_mode 1)
+// The reference's initial quant field (lib/jxl/enc_adaptive_quantization.cc: ComputeTile :528-628, FuzzyErosion :389-449,
+// PerBlockModulations :315-348 with ComputeMask :95-117, GammaModulation :179-211, HfModulation :260-313, BlueModulation
+// :221-256) over the XYB planes before the sharpening, as csrc/enc/jxl_enc.cc InitialQuantField states it in float32:
+//   k_enc_aq_cells   per 4x4 pixels: the masked, gamma-weighted Laplacian of Y, summed down the four rows of each column
+//                    (row 0 first) and averaged over the four columns (c0 + c1 + c2 + c3, left to right, times 0.25)
+//   k_enc_aq_blocks  per 8x8 block: the four smallest of each cell's 3x3 neighbourhood weighted and summed over the
+//                    block's 2x2 cells (raster order), the masking output 1 / (e + 0.001), and the modulations
+// Sums over the 64 samples of a block: per row left to right (where a sample adds two terms, in the order written), then
+// the eight row sums as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)). log2f / exp2f are the exact functions where the
+// reference has rational approximations (base/fast_math-inl.h). One global cell image: the reference's 64x64 tiles carry
+// a border cell of their neighbours, so its tiling leaves no seam either.
+struct EncAq {
+  const float* planes;  // [3][yp][xp] X, Y, B; a neighbour outside the plane is the nearest sample of the plane
+  float* cells;         // [yp / 4][xp / 4]
+  float* aq;            // [yb][xb] the field, before the aggregation over transforms
+  float* mask;          // [yb][xb] masking for the AC-strategy search (ComputeMaskForAcStrategyUse)
+  uint32_t xp, yp, xb, yb;
+  float w[4];           // erosion weights of the four smallest, normalised (they depend on the distance below 2)
+  float mul, add;       // scale * dampen, (1 - dampen) * 0.48 * scale
+};
+
+// RatioOfDerivativesOfCubicRootToSimpleGamma (:127-145): den / num, or num / den when INVERT
+template <bool INVERT>
+__device__ __forceinline__ float EncGammaRatio(float v) {
+#pragma clang fp contract(off)
+  const float kInvLog2e = 0.6931471805599453f, kSGmul = 226.77216153508914f, kSGmul2 = 1.0f / 73.377132366608819f;
+  const float kSGRetMul = kSGmul2 * 18.6580932135f * kInvLog2e, kSGVOffset = 7.7825991679894591f, kEpsilon = 1e-2f;
+  const float kNumMul = kSGRetMul * 3 * kSGmul, kVOffset = kSGVOffset * kInvLog2e + kEpsilon, kDenMul = kInvLog2e * kSGmul;
+  v = v < 0.0f ? 0.0f : v;
+  const float v2 = v * v;
+  const float num = kNumMul * v2 + kEpsilon, den = (kDenMul * v) * v2 + kVOffset;
+  return INVERT ? num / den : den / num;
+}
+
+constexpr int kAqCols = 56, kAqRows = 32;
+template <int CTRL>
+__device__ __forceinline__ float EncDpp(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+// A wave owns 64 adjacent columns (the middle 56 = 14 cells are written, four of halo either side so that cells start at a
+// multiple of four lanes) and walks down a strip of rows, a cell row (four rows) per step, with the rows above and at in
+// registers; the horizontal neighbours come from the adjacent lanes, the four column sums of a cell from the lanes of its quad.
+__global__ __launch_bounds__(256) void k_enc_aq_cells(EncAq P) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int strip_x0 = (int(blockIdx.x) * 4 + wave) * kAqCols - 4, gx = strip_x0 + lane;
+  if (strip_x0 + 4 >= int(P.xp)) return;  // (a wave beyond the last column strip)
+  const int Y0 = int(blockIdx.y) * kAqRows, Y1 = min(Y0 + kAqRows, int(P.yp)), last = int(P.yp) - 1;
+  const bool in_x = gx >= 0 && gx < int(P.xp), left_edge = gx == 0, right_edge = gx == int(P.xp) - 1;
+  const bool writes = lane >= 4 && lane < 4 + kAqCols && in_x && (lane & 3) == 0;
+  const float* src = P.planes + size_t(P.xp) * P.yp + (in_x ? gx : 0);
+  float* dst = P.cells + (in_x ? gx >> 2 : 0);
+  const float kSqrtMul = sqrtf(float(211.66567973503678f * 1e8)), kLogOffset = 27.505837037000106f;
+  float up = src[size_t(max(Y0 - 1, 0)) * P.xp], cur = src[size_t(Y0) * P.xp];
+  for (int y = Y0; y < Y1; y += 4) {  // (Y0 and Y1 are multiples of four: a cell row per step)
+    // the four rows below in flight together: with one load per step the kernel waits out a memory latency per row
+    float next[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) next[k] = src[size_t(min(y + 1 + k, last)) * P.xp];
+    float col = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const float down = next[k];
+      const float l = EncFromLeft(cur), r = EncFromRight(cur);
+      const float left = left_edge ? cur : l, right = right_edge ? cur : r;
+      const float base = 0.25f * (down + up + left + right);
+      float d = EncGammaRatio<false>(cur + 0.019f) * (cur - base);
+      d *= d;
+      d = d >= 0.2f ? 0.2f : d;
+      const float p = 0.25f * sqrtf(d * kSqrtMul + kLogOffset);  // MaskingSqrt
+      col = k ? col + p : p;
+      up = cur;
+      cur = down;
+    }
+    const float c0 = EncDpp<0x00>(col), c1 = EncDpp<0x55>(col), c2 = EncDpp<0xAA>(col), c3 = EncDpp<0xFF>(col);  // quad_perm broadcasts
+    if (writes) dst[size_t(y >> 2) * (P.xp >> 2)] = (c0 + c1 + c2 + c3) * 0.25f;
+  }
+}
+
+// A wave per 8 blocks (lane = block * 8 + row), each lane holding its row of X, Y and B; the row below comes from the next
+// lane. Lanes 0..3 of a block erode its four cells, reading the 3x3 neighbourhoods from the cell image.
+__global__ __launch_bounds__(64) void k_enc_aq_blocks(EncAq P) {
+#pragma clang fp contract(off)
+  const uint32_t lane = threadIdx.x, row = lane & 7, first = lane & ~7u;
+  const uint32_t bx = blockIdx.x * 8 + (lane >> 3), by = blockIdx.y;
+  const bool live = bx < P.xb;
+  const uint32_t lbx = live ? bx : 0;
+  const size_t plane = size_t(P.xp) * P.yp;
+  const float* s = P.planes + size_t(by * 8 + row) * P.xp + size_t(lbx) * 8;
+  float X[8], Y[8], B[8], N[8];
+  {
+    const float4 x0 = *reinterpret_cast<const float4*>(s), x1 = *reinterpret_cast<const float4*>(s + 4);
+    const float4 y0 = *reinterpret_cast<const float4*>(s + plane), y1 = *reinterpret_cast<const float4*>(s + plane + 4);
+    const float4 b0 = *reinterpret_cast<const float4*>(s + 2 * plane), b1 = *reinterpret_cast<const float4*>(s + 2 * plane + 4);
+    X[0] = x0.x; X[1] = x0.y; X[2] = x0.z; X[3] = x0.w; X[4] = x1.x; X[5] = x1.y; X[6] = x1.z; X[7] = x1.w;
+    Y[0] = y0.x; Y[1] = y0.y; Y[2] = y0.z; Y[3] = y0.w; Y[4] = y1.x; Y[5] = y1.y; Y[6] = y1.z; Y[7] = y1.w;
+    B[0] = b0.x; B[1] = b0.y; B[2] = b0.z; B[3] = b0.w; B[4] = b1.x; B[5] = b1.y; B[6] = b1.z; B[7] = b1.w;
+  }
+#pragma unroll
+  for (int x = 0; x < 8; x++) {
+    const float n = EncFromRight(Y[x]);  // the next lane: the row below
+    N[x] = row == 7 ? Y[x] : n;          // (row 7 pairs with itself)
+  }
+  // ---- fuzzy erosion: cell (row >> 1, row & 1) of the block in lanes 0..3 (the other four repeat them)
+  float v;
+  {
+    const uint32_t cw = P.xp >> 2, ch = P.yp >> 2;
+    const uint32_t cy = by * 2 + ((row >> 1) & 1), cx = lbx * 2 + (row & 1);
+    const uint32_t ya = cy ? cy - 1 : cy, yc = cy + 1 < ch ? cy + 1 : cy, xa = cx ? cx - 1 : cx, xc = cx + 1 < cw ? cx + 1 : cx;
+    const float* ra = P.cells + size_t(ya) * cw;
+    const float* rb = P.cells + size_t(cy) * cw;
+    const float* rc = P.cells + size_t(yc) * cw;
+    const float nb[9] = {ra[xa], ra[cx], ra[xc], rb[xa], rb[cx], rb[xc], rc[xa], rc[cx], rc[xc]};
+    float m0 = nb[0], m1 = INFINITY, m2 = INFINITY, m3 = INFINITY;  // the four smallest, ascending
+#pragma unroll
+    for (int i = 1; i < 9; i++) {
+      const float a0 = fminf(m0, nb[i]), b0 = fmaxf(m0, nb[i]);
+      const float a1 = fminf(m1, b0), b1 = fmaxf(m1, b0);
+      const float a2 = fminf(m2, b1), b2 = fmaxf(m2, b1);
+      m3 = fminf(m3, b2);
+      m0 = a0; m1 = a1; m2 = a2;
+    }
+    v = P.w[0] * m0 + P.w[1] * m1 + P.w[2] * m2 + P.w[3] * m3;
+  }
+  const float e = ((__shfl(v, first, 64) + __shfl(v, first + 1, 64)) + __shfl(v, first + 2, 64)) + __shfl(v, first + 3, 64);
+  // ---- ComputeMask
+  float m;
+  {
+    const float kOffset3 = 3.7179635626140772f, kOffset4 = 0.25f * kOffset3;
+    const float v1 = fmaxf(e * 0.80061762862741759f, 1e-3f);
+    const float v2 = 1.0f / (v1 + 302.59587815579727f);
+    const float v3 = 1.0f / (v1 * v1 + kOffset3);
+    const float v4 = 1.0f / (v1 * v1 + kOffset4);
+    m = -0.7647f + (9.4708735624378946f * v4 + (17.35036561631863f * v2 + 6.7943250517376494f * v3));
+  }
+  // ---- the row's terms of the three sums
+  float sg = 0.0f, sh = 0.0f, sb = 0.0f;
+#pragma unroll
+  for (int x = 0; x < 8; x++) {
+    const float iny = Y[x] + 0.16f;
+    sg += EncGammaRatio<true>(iny - X[x]);
+    sg += EncGammaRatio<true>(iny + X[x]);
+    if (x < 7) sh += fminf(0.0206f, fabsf(Y[x] - Y[x + 1]));
+    sh += fminf(0.0206f, fabsf(Y[x] - N[x]));
+    const float pye = (Y[x] + 0.0031994768654636393f) + fabsf(X[x]);
+    sb += B[x] > pye ? fminf(B[x] - pye, 0.010474084867598155f) : 0.0f;
+  }
+#pragma unroll
+  for (int d = 1; d < 8; d <<= 1) {  // (r0 + r1) + (r2 + r3) ... : addition commutes, every lane of the block holds the same sum
+    sg += __shfl_xor(sg, d, 64);
+    sh += __shfl_xor(sh, d, 64);
+    sb += __shfl_xor(sb, d, 64);
+  }
+  m = 0.1005613337192697f * log2f(sg * (0.5f / 64)) + m;  // GammaModulation
+  const float hf = (sh * -0.38f + 0.42f) + m;              // HfModulation
+  const float kLimit = 0.010474084867598155f, kMaxLimit = 15.463398341612438f;
+  if (sb >= 32 * kLimit) sb = 64 * kLimit - sb;            // BlueModulation: all blue is no reason to spend bits
+  if (sb >= kMaxLimit * kLimit) sb = kMaxLimit * kLimit;
+  sb *= 0.90590804735610064f;
+  const float blue = sb + m;
+  const float out = fminf(hf, blue);
+  if (live && row == 0) {
+    const size_t bi = size_t(by) * P.xb + bx;
+    P.aq[bi] = exp2f(out * 1.442695041f) * P.mul + P.add;
+    P.mask[bi] = 1.0f / (e + 0.001f);
+  }
+}
+
 // Transform selection and quant field of one 64x64 tile (8x8 blocks) per wave: every candidate is aligned to its own
 // size, so the greedy raster scan of the CPU writer never looks outside the tile it is in. The activity tests of every
 // (position, candidate) pair are evaluated by the lanes in parallel; only the occupancy bookkeeping of the scan is serial.
+// AQ = true (quant_field_mode 1): the quant field is the aggregation of the adaptive field P.aq_map over each transform
+// (AdjustQuantField, enc_adaptive_quantization.cc:1198-1247, and Quantizer::SetQuantFieldRect, quantizer.cc:78-88);
+// AQ = false is the writer's activity rule, compiled as it was before the other form existed.
+template <bool AQ>
 __global__ __launch_bounds__(64) void k_enc_select(EncFwd P) {
 #pragma clang fp contract(off)
   const uint32_t tiles_x = (P.xb + 7) / 8;
@@ -191,6 +372,8 @@ __global__ __launch_bounds__(64) void k_enc_select(EncFwd P) {
   const uint32_t w = min(8u, P.xb - bx0), h = min(8u, P.yb - by0);
   const bool inside = x < w && y < h;
   s_act[lane] = inside ? P.act[size_t(by0 + y) * P.xb + bx0 + x] : 0.0f;
+  __shared__ float s_aq[64];  // (AQ only: the other form never names it and carries no LDS for it)
+  if (AQ) s_aq[lane] = inside ? P.aq_map[size_t(by0 + y) * P.xb + bx0 + x] : 0.0f;
   s_acs[lane] = 0xFF;
   __syncthreads();
   const float T64 = 0.004f * P.distance, T32 = 0.008f * P.distance, T16 = 0.016f * P.distance, TR = 0.011f * P.distance;
@@ -241,7 +424,26 @@ __global__ __launch_bounds__(64) void k_enc_select(EncFwd P) {
   const size_t bi = size_t(by0 + y) * P.xb + bx0 + x;
   P.acs[bi] = a;
   int32_t q = 0;
-  if (a & 1) {
+  if (AQ) {
+    if (a & 1) {
+      // the covered blocks in raster order: the largest, and the mean mixed in from four blocks on
+      const int st = a >> 1;
+      const uint32_t cx = c_covered_x[st], cy = c_covered_y[st];
+      float mx = s_aq[lane], mean = 0.0f;
+      for (uint32_t yy = 0; yy < cy; yy++)
+        for (uint32_t xx = 0; xx < cx; xx++) {
+          const float v = s_aq[(y + yy) * 8 + x + xx];
+          mean += v;
+          mx = fmaxf(v, mx);
+        }
+      mean /= float(cy * cx);
+      if (cy * cx >= 4) {
+        mx *= P.mean_max_mixer;
+        mx += (1.0f - P.mean_max_mixer) * mean;
+      }
+      q = int(fmaxf(1.0f, fminf(mx * P.inv_gs + 0.5f, 256.0f)));
+    }
+  } else if (a & 1) {
     const int st = a >> 1;
     const float m = region_max(x, y, c_covered_x[st], c_covered_y[st]);
     float mul = 1.35f - 0.12f * log2f(1.0f + m * 400.0f);
