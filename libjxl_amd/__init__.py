@@ -567,6 +567,15 @@ class EncAnsDesc(ctypes.Structure):  # JxlHipEncAnsDesc
                 ("rev_start", ctypes.c_void_p), ("rev", ctypes.c_void_p), ("prefix_count", ctypes.c_void_p), ("prefix_value", ctypes.c_void_p)]
 
 
+class EncHooks(ctypes.Structure):  # JxlEncHooks: forward; token_counts + tokens; histograms + ans_sizes + ans_write
+    _fields_ = [(k, ctypes.c_void_p) for k in ("forward", "token_counts", "tokens", "histograms", "ans_sizes", "ans_write")]
+
+
+class EncHookStats(ctypes.Structure):  # JxlEncHookStats
+    _fields_ = [("forward_s", ctypes.c_double), ("assemble_s", ctypes.c_double), ("device_tokens", ctypes.c_uint64),
+                ("device_coded", ctypes.c_uint64)]
+
+
 class AnsTables:
     """An ANS code in the flat form the entropy entry points take: ctx_map (num_ctx,) uint8, freq and rev_start
     (clusters, 256) uint16, rev (clusters, 4096) uint16, log_alpha, the hybrid-uint configuration (split_exp, msb, lsb) and
@@ -590,8 +599,6 @@ def ans_write_tokens(tokens, tables, capacity=None):
     """The host rANS writer (jxlenc_ans_write_tokens) on (n, 2) uint32 {context, value} pairs and an AnsTables code:
     (the bit string as bytes, its length in bits)."""
     E = _enc_lib()
-    E.jxlenc_ans_write_tokens.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(EncAnsDesc), ctypes.c_void_p, ctypes.c_size_t,
-                                          ctypes.POINTER(ctypes.c_uint64)]
     tokens = np.ascontiguousarray(tokens, np.uint32).reshape(-1, 2)
     cap = 16 + 8 * len(tokens) if capacity is None else int(capacity)
     out = np.zeros(max(1, cap), np.uint8)
@@ -604,23 +611,60 @@ def ans_write_tokens(tokens, tables, capacity=None):
 
 
 def _enc_lib():
+    """libjxlenc.so with the signature of every jxlenc_* entry declared, here and nowhere else."""
     global _enc
     if _enc is None:
         if not os.path.exists(ENC_PATH):
             raise JxlAmdError("%s is missing: run libjxl_amd.build()" % ENC_PATH)
         E = ctypes.CDLL(ENC_PATH)
-        pp = ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))
-        E.jxlenc_encode_rgb8.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams), pp,
-                                         ctypes.POINTER(ctypes.c_size_t)]
-        E.jxlenc_encode_rgba8.argtypes = E.jxlenc_encode_rgb8.argtypes
-        E.jxlenc_encode_lossless.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
-                                             ctypes.c_uint32, pp, ctypes.POINTER(ctypes.c_size_t)]
-        E.jxlenc_encode_lossless_samples.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
-                                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, pp, ctypes.POINTER(ctypes.c_size_t)]
-        E.jxlenc_encode_random.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams), pp,
-                                           ctypes.POINTER(ctypes.c_size_t)]
-        E.jxlenc_synth_image.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
-        E.jxlenc_free.argtypes = [ctypes.POINTER(ctypes.c_uint8)]
+        c_int, u32, vp, sz, cp = ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p
+        i32p, szp, pp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(sz), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))
+        image = [cp, u32, u32, ctypes.POINTER(EncParams)]
+        color = [c_int] + [u32] * 6 + [i32p]
+        sigs = {  # name: (restype, argtypes)
+            "encode_rgb8": (c_int, image + [pp, szp]),
+            "encode_rgba8": (c_int, image + [pp, szp]),
+            "encode_rgb8_hooks": (c_int, image + [ctypes.POINTER(EncHooks), vp, pp, szp, ctypes.POINTER(EncHookStats)]),
+            "encode_lossless": (c_int, [cp] + [u32] * 5 + [pp, szp]),
+            "encode_lossless_samples": (c_int, [vp] + [u32] * 7 + [pp, szp]),
+            "encode_random": (c_int, image[1:] + [pp, szp]),
+            "forward_model": (c_int, image + [vp] * 6),
+            "ans_write_tokens": (c_int, [vp, sz, ctypes.POINTER(EncAnsDesc), vp, sz, ctypes.POINTER(ctypes.c_uint64)]),
+            "synth_image": (None, [u32, u32, u32, vp]),
+            "free": (None, [ctypes.POINTER(ctypes.c_uint8)]),
+            "last_header_bytes": (sz, []),
+            # the CPU doubles of the hooks (jxlhip_enc_* signatures, a JxlEncCpuCtx or NULL where those take the context)
+            "cpu_ctx_new": (vp, []),
+            "cpu_ctx_free": (None, [vp]),
+            "cpu_forward": (c_int, [vp, vp, sz] + [vp] * 5),
+            "cpu_token_counts": (c_int, [vp] * 3),
+            "cpu_tokens": (c_int, [vp] * 3 + [sz]),
+            "cpu_histograms": (c_int, [vp] * 4),
+            "cpu_ans_sizes": (c_int, [vp] * 3),
+            "cpu_ans_write": (c_int, [vp] * 3 + [sz]),
+            "cpu_initial_quant_field": (c_int, [vp, u32, u32, ctypes.c_float, ctypes.c_float, vp, vp]),
+            # what the next streams carry (test aids)
+            "set_custom_upsampling": (None, [u32, u32]),
+            "set_embedded_icc": (None, [cp, sz, sz]),
+            "set_color_encoding": (None, color),
+            "set_xyb_color_encoding": (None, color + [ctypes.c_float]),
+            "set_xyb_gray": (None, [c_int]),
+            "set_frame_name": (None, [cp]),
+            "set_orientation": (None, [u32]),
+            "set_splines": (None, [i32p, sz]),
+            "set_patches": (None, [i32p, sz]),
+            "set_animation": (None, [c_int] + [u32] * 4 + [c_int]),
+            "set_layer": (None, [c_int, ctypes.c_int32, ctypes.c_int32] + [u32] * 8 + [c_int]),
+            "set_preview": (None, [c_int, u32, u32]),
+            "set_alpha_premultiplied": (None, [c_int]),
+            "set_reference_frame": (None, [c_int]),
+            "set_image_size": (None, [u32, u32]),
+            "set_dc_frame": (None, [c_int]),
+            "set_use_dc_frame": (None, [c_int]),
+        }
+        for name, (restype, argtypes) in sigs.items():
+            fn = getattr(E, "jxlenc_" + name)
+            fn.restype, fn.argtypes = restype, argtypes
         _enc = E
     return _enc
 
@@ -649,8 +693,6 @@ def set_custom_upsampling(mask=0, seed=1):
     """Test aid: the next VarDCT streams code their own upsampling weights (CustomTransformData, image_metadata.cc:87-214):
     bit k of `mask` = the 2^(k+1)-fold weight matrix is coded (seeded variations of the default weights); 0 = default again."""
     E = _enc_lib()
-    E.jxlenc_set_custom_upsampling.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-    E.jxlenc_set_custom_upsampling.restype = None
     E.jxlenc_set_custom_upsampling(mask, seed)
 
 
@@ -658,7 +700,6 @@ def set_embedded_icc(coded=None):
     """Test aid: the synthetic encoders embed this coded ICC profile (want_icc) in the streams they write from now on
     (None: no profile again)."""
     E = _enc_lib()
-    E.jxlenc_set_embedded_icc.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t]
     if not coded:
         E.jxlenc_set_embedded_icc(b"", 0, 0)
         return
@@ -672,8 +713,6 @@ def set_color_encoding(white_point=None, primaries=1, transfer_function=13, gamm
     13 sRGB / 16 PQ / 17 DCI / 18 HLG, or gamma as a float; xy = 8 custom chromaticities white, red, green, blue).
     white_point=None: sRGB again."""
     E = _enc_lib()
-    E.jxlenc_set_color_encoding.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 6 + [ctypes.POINTER(ctypes.c_int32)]
-    E.jxlenc_set_color_encoding.restype = None
     if white_point is None:
         E.jxlenc_set_color_encoding(0, 1, 1, 0, 0, 13, 1, None)
         return
@@ -687,8 +726,6 @@ def set_xyb_gray(on=True):
     (with set_xyb_color_encoding's / set_color_encoding's white point and transfer function, D65 sRGB without). The body is
     the same three-channel XYB frame: a decoder renders its luminance."""
     E = _enc_lib()
-    E.jxlenc_set_xyb_gray.argtypes = [ctypes.c_int]
-    E.jxlenc_set_xyb_gray.restype = None
     E.jxlenc_set_xyb_gray(1 if on else 0)
 
 
@@ -700,8 +737,6 @@ def set_xyb_color_encoding(white_point=None, primaries=1, transfer_function=13, 
     untagged again (the streams are then byte-identical to before)."""
     E = _enc_lib()
     set_xyb_gray(gray and white_point is not None)
-    E.jxlenc_set_xyb_color_encoding.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 6 + [ctypes.POINTER(ctypes.c_int32), ctypes.c_float]
-    E.jxlenc_set_xyb_color_encoding.restype = None
     if white_point is None:
         E.jxlenc_set_xyb_color_encoding(0, 1, 1, 0, 0, 13, 1, None, 255.0)
         return
@@ -713,8 +748,6 @@ def set_xyb_color_encoding(white_point=None, primaries=1, transfer_function=13, 
 def set_frame_name(name=""):
     """Test aid: the frames written from now on carry this name (empty: none again)."""
     E = _enc_lib()
-    E.jxlenc_set_frame_name.argtypes = [ctypes.c_char_p]
-    E.jxlenc_set_frame_name.restype = None
     E.jxlenc_set_frame_name(name.encode())
 
 
@@ -722,8 +755,6 @@ def set_orientation(orientation=1):
     """Test aid: the synthetic encoders declare this image orientation (1..8, EXIF numbering) in the streams they write
     from now on (1: none again)."""
     E = _enc_lib()
-    E.jxlenc_set_orientation.argtypes = [ctypes.c_uint32]
-    E.jxlenc_set_orientation.restype = None
     E.jxlenc_set_orientation(int(orientation))
 
 
@@ -731,8 +762,6 @@ def set_splines(splines=None, quantization_adjustment=0):
     """Test aid: the next streams carry these quantised splines (None: none again). Each spline is a dict: points (list of
     integer (x, y) control points), color ([3][32] integer DCT coefficients of X, Y, B along the arc) and sigma ([32])."""
     E = _enc_lib()
-    E.jxlenc_set_splines.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t]
-    E.jxlenc_set_splines.restype = None
     if not splines:
         E.jxlenc_set_splines(None, 0)
         return
@@ -756,9 +785,6 @@ def encode_animation(frames, durations, tps=(10, 1), num_loops=0, lossless=False
     """Test aid: an animation of full-size frames that replace each other (no layers, blending, crops or references):
     frames[i] (HxWx3 or HxWx4 uint8, all of one size) is shown for durations[i] ticks of tps[0] / tps[1] per second."""
     E = _enc_lib()
-    E.jxlenc_set_animation.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 4 + [ctypes.c_int]
-    E.jxlenc_set_animation.restype = None
-    E.jxlenc_last_header_bytes.restype = ctypes.c_size_t
     out = b""
     try:
         for i, (img, dur) in enumerate(zip(frames, durations)):
@@ -783,15 +809,8 @@ def encode_layers(layers, tps=None, num_loops=0, lossless=False, premultiplied=F
     denominator) makes it an animation (frames with duration > 0 are shown); tps = None a layered still (only the last
     frame is shown)."""
     E = _enc_lib()
-    E.jxlenc_set_animation.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 4 + [ctypes.c_int]
-    E.jxlenc_set_animation.restype = None
-    E.jxlenc_set_layer.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_uint32] * 8 + [ctypes.c_int]
-    E.jxlenc_set_layer.restype = None
-    E.jxlenc_last_header_bytes.restype = ctypes.c_size_t
     ch, cw = layers[0]["img"].shape[:2]
     out = b""
-    E.jxlenc_set_alpha_premultiplied.argtypes = [ctypes.c_int]
-    E.jxlenc_set_alpha_premultiplied.restype = None
     E.jxlenc_set_alpha_premultiplied(1 if premultiplied else 0)  # (the alpha channel is declared associated; samples as given)
     try:
         for i, L in enumerate(layers):
@@ -819,13 +838,6 @@ def encode_with_preview(img, preview, **kw):
     the image header announces the preview's size (headers.cc:155-183) and the preview is the codestream's first frame, a
     regular frame that is not the last (decode.cc:1266-1268)."""
     E = _enc_lib()
-    E.jxlenc_set_animation.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 4 + [ctypes.c_int]
-    E.jxlenc_set_animation.restype = None
-    E.jxlenc_set_preview.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
-    E.jxlenc_set_preview.restype = None
-    E.jxlenc_last_header_bytes.restype = ctypes.c_size_t
-    E.jxlenc_set_layer.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_uint32] * 8 + [ctypes.c_int]
-    E.jxlenc_set_layer.restype = None
     try:
         E.jxlenc_set_animation(1, 10, 1, 0, 0, 0)  # (multi-frame ...
         E.jxlenc_set_layer(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)  # ... untimed: a frame header with is_last = false, no duration)
@@ -850,22 +862,11 @@ def encode_patched(img, atlas, patches, slot=1, atlas_vardct=False, lossless=Fal
     (dec_patch_dictionary.h:32-58); the last two apply to the image's alpha channel (RGBA `img` and `atlas`, VarDCT atlas).
     The patches are drawn over the decoded frame; nothing is subtracted when encoding."""
     E = _enc_lib()
-    E.jxlenc_set_reference_frame.argtypes = [ctypes.c_int]
-    E.jxlenc_set_reference_frame.restype = None
-    E.jxlenc_set_image_size.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-    E.jxlenc_set_image_size.restype = None
-    E.jxlenc_set_patches.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t]
-    E.jxlenc_set_patches.restype = None
-    E.jxlenc_set_animation.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 4 + [ctypes.c_int]
-    E.jxlenc_set_animation.restype = None
-    E.jxlenc_last_header_bytes.restype = ctypes.c_size_t
     flat = [len(patches)]
     for p in patches:
         flat += [slot, p["x0"], p["y0"], p["xsize"], p["ysize"], len(p["positions"])]
         for pos in p["positions"]:
             flat += list(pos) + [0] * (6 - len(pos))
-    E.jxlenc_set_alpha_premultiplied.argtypes = [ctypes.c_int]
-    E.jxlenc_set_alpha_premultiplied.restype = None
     try:
         E.jxlenc_set_alpha_premultiplied(1 if premultiplied else 0)  # (the alpha channel is declared associated; samples as given)
         E.jxlenc_set_image_size(img.shape[1], img.shape[0])
@@ -889,13 +890,6 @@ def encode_with_dc_frame(img, dc_vardct=False, **kw):
     an XYB Modular frame like libjxl's DC frames, or as a VarDCT frame), then `img` as a VarDCT frame with kUseDcFrame, whose
     DC groups carry no DC stream: its DC image is the DC frame's output (frame_header.h:348, passes_state.cc:62-77)."""
     E = _enc_lib()
-    E.jxlenc_set_image_size.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-    E.jxlenc_set_image_size.restype = None
-    E.jxlenc_set_dc_frame.argtypes = [ctypes.c_int]
-    E.jxlenc_set_dc_frame.restype = None
-    E.jxlenc_set_use_dc_frame.argtypes = [ctypes.c_int]
-    E.jxlenc_set_use_dc_frame.restype = None
-    E.jxlenc_last_header_bytes.restype = ctypes.c_size_t
     h, w = img.shape[:2]
     xb, yb = (w + 7) // 8, (h + 7) // 8
     pad = np.pad(img, ((0, yb * 8 - h), (0, xb * 8 - w), (0, 0)), mode="edge")
@@ -940,14 +934,16 @@ def encode_rgb8(img, **kw):
     return _finish(E, r, out, n, "jxlenc_encode_rgb8")
 
 
-def _forward_entropy(E, img, p, fns, handle, secs):
-    pp = ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))
-    E.jxlenc_encode_rgb8_forward_entropy.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams)] + \
-        [ctypes.c_void_p] * 7 + [pp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_double)]
-    out, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_size_t()
-    r = E.jxlenc_encode_rgb8_forward_entropy(img.tobytes(), img.shape[1], img.shape[0], ctypes.byref(p),
-                                             *([ctypes.cast(f, ctypes.c_void_p) for f in fns] + [handle, ctypes.byref(out), ctypes.byref(n), secs]))
-    return _finish(E, r, out, n, "jxlenc_encode_rgb8_forward_entropy")
+def _encode_hooks(img, p, fns, handle):
+    """jxlenc_encode_rgb8_hooks with the functions `fns` (forward[, token_counts, tokens[, histograms, ans_sizes,
+    ans_write]]) on the context `handle`: (the stream, its JxlEncHookStats)."""
+    E = _enc_lib()
+    img = np.ascontiguousarray(img, np.uint8)
+    hooks = EncHooks(*[ctypes.cast(f, ctypes.c_void_p).value for f in fns])
+    out, n, st = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_size_t(), EncHookStats()
+    r = E.jxlenc_encode_rgb8_hooks(img.tobytes(), img.shape[1], img.shape[0], ctypes.byref(p), ctypes.byref(hooks), handle, ctypes.byref(out),
+                                   ctypes.byref(n), ctypes.byref(st))
+    return _finish(E, r, out, n, "jxlenc_encode_rgb8_hooks"), st
 
 
 def encode_rgb8_hooks_cpu(img, timings=None, **kw):
@@ -955,19 +951,14 @@ def encode_rgb8_hooks_cpu(img, timings=None, **kw):
     rANS sizes / write): the plumbing of that route on a machine without a GPU. `timings` receives device_tokens and
     device_entropy as there."""
     E = _enc_lib()
-    E.jxlenc_cpu_ctx_new.restype = ctypes.c_void_p
-    E.jxlenc_cpu_ctx_free.argtypes = [ctypes.c_void_p]
-    img = np.ascontiguousarray(img, np.uint8)
-    p = _params(**kw)
-    secs = (ctypes.c_double * 4)()
     h = E.jxlenc_cpu_ctx_new()
     try:
-        data = _forward_entropy(E, img, p, [E.jxlenc_cpu_forward, E.jxlenc_cpu_token_counts, E.jxlenc_cpu_tokens, E.jxlenc_cpu_histograms,
-                                            E.jxlenc_cpu_ans_sizes, E.jxlenc_cpu_ans_write], h, secs)
+        data, st = _encode_hooks(img, _params(**kw), [E.jxlenc_cpu_forward, E.jxlenc_cpu_token_counts, E.jxlenc_cpu_tokens,
+                                                      E.jxlenc_cpu_histograms, E.jxlenc_cpu_ans_sizes, E.jxlenc_cpu_ans_write], h)
     finally:
         E.jxlenc_cpu_ctx_free(h)
     if timings is not None:
-        timings.update(forward_s=secs[0], assemble_s=secs[1], device_tokens=int(secs[2]), device_entropy=int(secs[3]))
+        timings.update(forward_s=st.forward_s, assemble_s=st.assemble_s, device_tokens=st.device_tokens, device_entropy=st.device_coded)
     return data
 
 
@@ -981,39 +972,20 @@ def encode_rgb8_gpu(img, ctx, timings=None, device_tokens=False, device_entropy=
     and writes the headers. Prefix codes, LZ77, several passes and coded orders / block contexts fall back to the host
     coder. `timings` then also receives device_entropy (tokens coded on the device, 0 after that fallback) and
     entropy_kernels_ms (the histogram, sizes and write kernels). The stream is the same bytes in all three forms."""
-    E, L = _enc_lib(), lib()
-    pp = ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))
-    E.jxlenc_encode_rgb8_forward.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams), ctypes.c_void_p,
-                                             ctypes.c_void_p, pp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_double)]
+    L = lib()
     L.jxlhip_enc_last_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
-    img = np.ascontiguousarray(img, np.uint8)
-    p = _params(**kw)
-    out, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_size_t()
-    secs = (ctypes.c_double * 4)()
-    fn = ctypes.cast(L.jxlhip_enc_forward, ctypes.c_void_p)
+    fns = [L.jxlhip_enc_forward]
+    if device_tokens or device_entropy:
+        fns += [L.jxlhip_enc_token_counts, L.jxlhip_enc_tokens]
     if device_entropy:
-        data = _forward_entropy(E, img, p, [L.jxlhip_enc_forward, L.jxlhip_enc_token_counts, L.jxlhip_enc_tokens, L.jxlhip_enc_histograms,
-                                            L.jxlhip_enc_ans_sizes, L.jxlhip_enc_ans_write], ctx._h, secs)
-        if timings is not None:
-            ms = ctypes.c_float()
-            _check(L.jxlhip_enc_last_ms(ctx._h, ctypes.byref(ms)), "jxlhip_enc_last_ms")
-            timings.update(forward_s=secs[0], assemble_s=secs[1], kernels_ms=ms.value, device_tokens=int(secs[2]), device_entropy=int(secs[3]),
-                           entropy_kernels_ms=sum(ctx.enc_entropy_ms()) if secs[3] else 0.0)
-        return data
-    if device_tokens:
-        E.jxlenc_encode_rgb8_forward_tokens.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams)] + \
-            [ctypes.c_void_p] * 4 + [pp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_double)]
-        r = E.jxlenc_encode_rgb8_forward_tokens(img.tobytes(), img.shape[1], img.shape[0], ctypes.byref(p), fn,
-                                                ctypes.cast(L.jxlhip_enc_token_counts, ctypes.c_void_p),
-                                                ctypes.cast(L.jxlhip_enc_tokens, ctypes.c_void_p), ctx._h, ctypes.byref(out), ctypes.byref(n), secs)
-    else:
-        r = E.jxlenc_encode_rgb8_forward(img.tobytes(), img.shape[1], img.shape[0], ctypes.byref(p), fn, ctx._h, ctypes.byref(out),
-                                         ctypes.byref(n), secs)
-    data = _finish(E, r, out, n, "jxlenc_encode_rgb8_forward")
+        fns += [L.jxlhip_enc_histograms, L.jxlhip_enc_ans_sizes, L.jxlhip_enc_ans_write]
+    data, st = _encode_hooks(img, _params(**kw), fns, ctx._h)
     if timings is not None:
         ms = ctypes.c_float()
         _check(L.jxlhip_enc_last_ms(ctx._h, ctypes.byref(ms)), "jxlhip_enc_last_ms")
-        timings.update(forward_s=secs[0], assemble_s=secs[1], kernels_ms=ms.value, device_tokens=int(secs[2]))
+        timings.update(forward_s=st.forward_s, assemble_s=st.assemble_s, kernels_ms=ms.value, device_tokens=st.device_tokens)
+        if device_entropy:
+            timings.update(device_entropy=st.device_coded, entropy_kernels_ms=sum(ctx.enc_entropy_ms()) if st.device_coded else 0.0)
     return data
 
 
@@ -1021,16 +993,13 @@ def enc_forward_model(img, ctx=None, **kw):
     """Test access: the raw outputs of one forward call (acs, qf, dc, coeffs) from the GPU path on `ctx`, or from the
     CPU stream writer's own model code when ctx is None."""
     E = _enc_lib()
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    E.jxlenc_forward_model.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(EncParams), ctypes.c_void_p,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     img = np.ascontiguousarray(img, np.uint8)
     ys, xs = img.shape[:2]
     xb, yb, ng = (xs + 7) // 8, (ys + 7) // 8, ((xs + 255) // 256) * ((ys + 255) // 256)
     acs, qf = np.zeros((yb, xb), np.uint8), np.zeros((yb, xb), np.int32)
     dc, co = np.zeros((3, yb, xb), np.int32), np.zeros((ng, 3, 65536), np.int32)
     p = _params(**kw)
-    fn = ctypes.cast(lib().jxlhip_enc_forward if ctx is not None else E.jxlenc_forward_cpu, ctypes.c_void_p)
+    fn = ctypes.cast(lib().jxlhip_enc_forward if ctx is not None else E.jxlenc_cpu_forward, ctypes.c_void_p)
     r = E.jxlenc_forward_model(img.tobytes(), xs, ys, ctypes.byref(p), fn, ctx._h if ctx is not None else None, acs.ctypes.data,
                                qf.ctypes.data, dc.ctypes.data, co.ctypes.data)
     if r:
@@ -1055,7 +1024,6 @@ def initial_quant_field(xyb, distance, ctx=None, rescale=1.0):
         _check(L.jxlhip_enc_initial_quant_field(ctx._h, *args), "jxlhip_enc_initial_quant_field")
     else:
         E = _enc_lib()
-        E.jxlenc_cpu_initial_quant_field.argtypes = tail
         r = E.jxlenc_cpu_initial_quant_field(*args)
         if r:
             raise JxlAmdError("jxlenc_cpu_initial_quant_field failed (%d)" % r)

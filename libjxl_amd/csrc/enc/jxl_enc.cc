@@ -30,6 +30,7 @@
 #include "../../../include/jxl_amd_hip.h"  // JxlHipEncDesc: the forward path's descriptor (no link dependency)
 
 #include "../host/jxh_bits.h"
+#include "../host/jxh_enc_shared.h"
 #include "../host/jxh_entropy.h"
 #include "../host/jxh_modular.h"
 #include "../host/jxh_vardct.h"
@@ -737,15 +738,12 @@ static void ModularTokens(const TreeSpec& tree, const int32_t* px, size_t w, siz
 }
 
 // ---------------------------------------------------------------- colour + transforms
-static inline float SrgbToLinear(float v) {
-  return v <= 0.04045f ? v / 12.92f : std::pow((v + 0.055f) / 1.055f, 2.4f);
-}
 static void RgbToXyb(const uint8_t* rgb, size_t xs, size_t ys, size_t xp, size_t yp, std::vector<float> planes[3]) {
   static const float kM[9] = {0.30f, 1.0f - 0.078f - 0.30f, 0.078f, 0.23f, 1.0f - 0.078f - 0.23f, 0.078f,
                               0.24342268924547819f, 0.20476744424496821f, 1.0f - 0.24342268924547819f - 0.20476744424496821f};
   const float bias = 0.0037930732552754493f, cb = std::cbrt(bias);
   float lut[256];
-  for (int i = 0; i < 256; i++) lut[i] = SrgbToLinear(i / 255.0f);
+  for (int i = 0; i < 256; i++) lut[i] = jxh::SrgbEotf8(i);
   for (int c = 0; c < 3; c++) planes[c].assign(xp * yp, 0.0f);
   for (size_t y = 0; y < yp; y++) {
     size_t sy = std::min(y, ys - 1);
@@ -858,7 +856,7 @@ struct FrameModel {
   // (context, value) pairs in bitstream order, group g at dev_tokens[dev_token_base[g] .. + dev_token_count[g])
   std::vector<uint64_t> dev_tokens;  // {context, value} pairs of uint32
   std::vector<uint32_t> dev_token_base, dev_token_count;
-  // ... or the tokens never came either: the device counted and rANS-coded them (ForwardHook::histograms / ans_sizes /
+  // ... or the tokens never came either: the device counted and rANS-coded them (Hooks::histograms / ans_sizes /
   // ans_write). Then `dev_tokens` is empty, dev_ac_code is the AC code the host built from the device's counts, and group
   // g's part of its section (histogram selector, coder state, chunks and extra bits) is the dev_ac_nbits[g] bits at
   // dev_ac_bits[dev_ac_base[g]].
@@ -1918,22 +1916,7 @@ struct AnsTables {
 static bool ValidAnsDesc(const JxlHipEncAnsDesc* d) {
   if (!d || !d->ctx_map || !d->freq || !d->rev_start || !d->rev || !d->num_ctx || !d->num_clusters || d->num_clusters > 256) return false;
   if (d->log_alpha < 5 || d->log_alpha > 8 || d->split_exp > d->log_alpha || d->msb_in_token + d->lsb_in_token > d->split_exp) return false;
-  for (uint32_t i = 0; i < d->num_ctx; i++)
-    if (d->ctx_map[i] >= d->num_clusters) return false;
-  for (uint32_t k = 0; k < d->num_clusters; k++) {
-    uint32_t sum = 0;
-    for (uint32_t s2 = 0; s2 < 256; s2++) {
-      const uint32_t fr = d->freq[k * 256 + s2];
-      if (fr && (s2 >> d->log_alpha)) return false;
-      if (fr && d->rev_start[k * 256 + s2] != sum) return false;
-      sum += fr;
-      if (sum > 4096) return false;
-    }
-    if (sum != 4096) return false;
-    for (uint32_t i = 0; i < 4096; i++)
-      if (d->rev[k * 4096 + i] >= 4096) return false;
-  }
-  return true;
+  return jxh::AnsTablesInBounds(*d);
 }
 // ... and the code WriteTokens takes, from such a descriptor (valid)
 static void CodeFromDesc(const JxlHipEncAnsDesc& d, EncCode* code) {
@@ -2004,27 +1987,6 @@ struct AqParams {
   float w[4];      // erosion weights of the four smallest of a 3x3 neighbourhood
   float mul, add;  // scale * dampen, (1 - dampen) * 0.48 * scale
 };
-static AqParams MakeAqParams(float target, float rescale) {
-  AqParams a;
-  const float scale = 0.765f / target * rescale;
-  const float base_level = 0.48f * scale;
-  float dampen = 1.0f;
-  if (target >= 2.0f) {
-    dampen = 1.0f - ((target - 2.0f) / (14.0f - 2.0f));
-    if (dampen < 0) dampen = 0;
-  }
-  a.mul = scale * dampen;
-  a.add = (1.0f - dampen) * base_level;
-  const float kMulBase[4] = {0.125f, 0.1f, 0.09f, 0.06f}, kMulAdd[4] = {0.0f, -0.1f, -0.09f, -0.06f};
-  const float mul = target < 2.0f ? (2.0f - target) * (1.0f / 2.0f) : 0.0f;
-  float norm_sum = 0.0f;
-  for (int i = 0; i < 4; i++) {
-    a.w[i] = kMulBase[i] + mul * kMulAdd[i];
-    norm_sum += a.w[i];
-  }
-  for (int i = 0; i < 4; i++) a.w[i] *= 0.29959705784054957f / norm_sum;
-  return a;
-}
 template <bool kInvert>
 static inline float AqGammaRatio(float v) {
   const float kInvLog2e = 0.6931471805599453f, kSGmul = 226.77216153508914f, kSGmul2 = 1.0f / 73.377132366608819f;
@@ -2038,7 +2000,8 @@ static inline float AqGammaRatio(float v) {
 // planes X, Y, B of xp x yp samples (multiples of 8); aq [yp / 8][xp / 8]; mask the same, may be NULL
 static void InitialQuantField(const float* px, const float* py, const float* pb, size_t xp, size_t yp, float target, float rescale,
                               float* aq, float* mask) {
-  const AqParams A = MakeAqParams(target, rescale);
+  AqParams A;
+  jxh::EncAqDistanceParams(target, rescale, &A);
   const size_t cw = xp / 4, ch = yp / 4, xb = xp / 8, yb = yp / 8;
   std::vector<float> cells(cw * ch);
   const float kSqrtMul = std::sqrt(float(211.66567973503678f * 1e8)), kLogOffset = 27.505837037000106f;
@@ -2117,8 +2080,47 @@ static void InitialQuantField(const float* px, const float* py, const float* pb,
     }
 }
 
-// The pixel-domain half of the encode done elsewhere (the HIP forward path, jxlhip_enc_forward of include/jxl_amd_hip.h,
-// whose signature this is): the caller hands the function and its context over, this library does not link against it.
+// The alpha plane of jxlenc_encode_rgba8 with its geometry: w x h samples (w = 0: frame sized), the extra channel's upsampling
+// factor and its shift against the frame.
+struct AlphaPlane {
+  const std::vector<uint8_t>* samples;
+  uint32_t w, h, ups, shift;
+};
+// What every image-mode frame starts from, on either route: sizes, the quantiser's scales, loop filter and flags, the
+// per-block and per-tile fields at their defaults. Returns the AC quantisation target.
+static float BeginFrame(FrameModel* fp, size_t xs, size_t ys, const Params& p, size_t img_xs, size_t img_ys, const AlphaPlane* alpha) {
+  FrameModel& f = *fp;
+  if (alpha) {
+    f.alpha = *alpha->samples;
+    if (alpha->w) {
+      f.alpha_w = alpha->w;
+      f.alpha_h = alpha->h;
+      f.alpha_ups = alpha->ups;
+      f.alpha_shift = alpha->shift;
+    }
+  }
+  f.SetSubsampling(p.color_transform == 2 ? uint32_t(p.chroma_subsampling) : 0u);
+  f.SetSize(xs, ys);
+  f.img_xs = img_xs ? img_xs : xs;
+  f.img_ys = img_ys ? img_ys : ys;
+  if (p.adaptive_quant != 0 && p.adaptive_quant != 1) throw std::runtime_error("adaptive_quant: 0 or 1");
+  const bool adaptive = p.adaptive_quant == 1;
+  // (the field is defined over XYB planes at full resolution, under this writer's own transform choices)
+  if (adaptive && (p.color_transform || f.Subsampled() || p.strategy_mode > 1)) throw std::runtime_error("adaptive_quant: unsupported parameters");
+  float quant_ac;
+  QuantParams(p.distance, &f, &quant_ac, adaptive);
+  f.gab = p.gab < 0 ? 1 : p.gab;
+  f.epf_iters = p.epf_iters >= 0 ? p.epf_iters : (p.distance >= 4.0f ? 3 : p.distance >= 1.5f ? 2 : p.distance >= 0.7f ? 1 : 0);
+  f.flags = (p.skip_dc_smoothing ? 128 : 0) | (p.noise > 0 ? 1 : 0) | (g_splines.empty() ? 0 : 16) | (g_patches.empty() ? 0 : 2);
+  f.sharp.assign(f.xb * f.yb, 4);
+  f.ytox.assign(DivCeil(f.xb, 8) * DivCeil(f.yb, 8), 0);
+  f.ytob.assign(f.ytox.size(), 0);
+  return quant_ac;
+}
+
+// ---- the hook route: parts of the encode done elsewhere, by functions and a context the caller hands over (this library
+// does not link against them).
+// The pixel-domain half (the HIP forward path, jxlhip_enc_forward of include/jxl_amd_hip.h, whose signature this is)
 typedef int (*ForwardFn)(void* ctx, const uint8_t* rgb, size_t stride, const JxlHipEncDesc* desc, uint8_t* acs, int32_t* qf, int32_t* dc,
                          int32_t* coeffs);
 // ... and the tokenisation of its coefficients (jxlhip_enc_token_counts / jxlhip_enc_tokens): when both are given the
@@ -2131,196 +2133,201 @@ typedef int (*TokensFn)(void* ctx, const uint32_t* bases, uint32_t* tokens, size
 typedef int (*HistogramsFn)(void* ctx, const JxlHipEncHistDesc* desc, uint32_t* counts, uint32_t* max_token);
 typedef int (*AnsSizesFn)(void* ctx, const JxlHipEncAnsDesc* desc, uint32_t* bit_counts);
 typedef int (*AnsWriteFn)(void* ctx, const uint64_t* byte_bases, uint8_t* out, size_t capacity);
-struct ForwardHook {
-  ForwardFn fn;
-  void* ctx;
-  double seconds[2];  // out: forward call, assembly (entropy coding + headers)
-  TokenCountsFn tok_counts = nullptr;
-  TokensFn tok_emit = nullptr;
-  uint64_t device_tokens = 0;  // out: how many tokens came from the device (0: the host tokenised)
-  HistogramsFn histograms = nullptr;
-  AnsSizesFn ans_sizes = nullptr;
-  AnsWriteFn ans_write = nullptr;
-  uint64_t device_coded = 0;  // out: how many tokens the device entropy-coded (0: the host coder wrote them)
-  // test access: when set, the raw outputs of the forward call are copied here and nothing is assembled
-  uint8_t* cap_acs = nullptr;
-  int32_t *cap_qf = nullptr, *cap_dc = nullptr, *cap_coeffs = nullptr;
+// in (JxlEncHooks of jxlenc_encode_rgb8_hooks)
+struct Hooks {
+  ForwardFn forward;            // required
+  TokenCountsFn token_counts;   // both or neither
+  TokensFn tokens;
+  HistogramsFn histograms;      // all or none; need the token pair
+  AnsSizesFn ans_sizes;
+  AnsWriteFn ans_write;
 };
+// out (JxlEncHookStats)
+struct HookStats {
+  double forward_s, assemble_s;  // forward call (device tokenisation and coding included), assembly (entropy coding + headers)
+  uint64_t device_tokens;        // how many tokens came from the device (0: the host tokenised)
+  uint64_t device_coded;         // how many tokens the device entropy-coded (0: the host coder wrote them)
+};
+// test access (jxlenc_forward_model): the raw outputs of the forward call are copied here and nothing is assembled
+struct ForwardCapture {
+  uint8_t* acs;
+  int32_t *qf, *dc, *coeffs;
+};
+static void HookCheck(int r, const char* which) {
+  if (r) throw std::runtime_error(std::string(which) + " hook failed (" + std::to_string(r) + ")");
+}
 
-// (jxlenc_encode_rgba8 -> EncodeImage: width, height, upsampling factor and shift of a subsampled alpha plane; 0 = frame sized)
-static thread_local uint32_t g_alpha_dims[4] = {0, 0, 0, 0};
-// model_only: stop before the bitstream assembly and hand the frame model out (the CPU form of the forward path).
-static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& p, std::vector<uint8_t>* out, size_t img_xs = 0,
-                        size_t img_ys = 0, const std::vector<uint8_t>* alpha = nullptr, ForwardHook* hook = nullptr,
-                        FrameModel* model_only = nullptr) {
-  FrameModel f;
-  if (alpha) {
-    f.alpha = *alpha;
-    if (g_alpha_dims[0]) {
-      f.alpha_w = g_alpha_dims[0];
-      f.alpha_h = g_alpha_dims[1];
-      f.alpha_ups = g_alpha_dims[2];
-      f.alpha_shift = g_alpha_dims[3];
+// The forward path's descriptor of a frame BeginFrame has set up (ytox / ytob: the frame's own, written by the call).
+static JxlHipEncDesc ForwardDesc(FrameModel& f, const Params& p, float quant_ac) {
+  // the default dequantisation tables, flat, built once (they do not depend on the image)
+  static std::vector<float> flat;
+  static uint32_t flat_offset[17], flat_size[17];
+  static std::once_flag flat_once;
+  std::call_once(flat_once, [] {
+    jxh::DequantTables dq;
+    for (int k = 0; k < 17; k++) {
+      flat_offset[k] = flat_size[k] = 0;
+      if (k >= 13) continue;  // 128 / 256 point tables: never selected here, not built
+      dq.Compute(k);
+      flat_offset[k] = uint32_t(flat.size());
+      flat_size[k] = uint32_t(dq.table[k].size() / 3);
+      flat.insert(flat.end(), dq.table[k].begin(), dq.table[k].end());
     }
+  });
+  JxlHipEncDesc d;
+  memset(&d, 0, sizeof(d));
+  memcpy(d.dequant_offset, flat_offset, sizeof(flat_offset));
+  memcpy(d.dequant_size, flat_size, sizeof(flat_size));
+  d.dequant = flat.data();
+  d.dequant_floats = uint32_t(flat.size());
+  d.xsize = uint32_t(f.xs);
+  d.ysize = uint32_t(f.ys);
+  d.distance = p.distance;
+  d.gaborish = f.gab ? 1 : 0;
+  d.strategy_mode = uint32_t(p.strategy_mode);
+  d.global_scale = f.global_scale;
+  d.quant_dc = f.quant_dc;
+  d.quant_ac = quant_ac;
+  d.cfl_fit = p.cfl_fit ? 1 : 0;
+  d.quant_field_mode = p.adaptive_quant == 1 ? 1 : 0;
+  d.ytox = f.ytox.data();
+  d.ytob = f.ytob.data();
+  return d;
+}
+
+// Device tokenisation of the last forward call's coefficients: one pass, natural orders, the default block context map
+// (what it is written for). The counts and bases go to the model; the tokens too unless they `stay` on the device for
+// DeviceEntropy. Returns how many there are.
+struct TokenShape {
+  uint32_t num_ctxs, num_hist;
+};
+static uint64_t DeviceTokens(const Hooks& h, void* ctx, const Params& p, size_t ng, bool stay, FrameModel* fp, TokenShape* shape) {
+  FrameModel& f = *fp;
+  JxlHipEncTokDesc td;
+  memset(&td, 0, sizeof(td));
+  std::vector<uint16_t> orders;
+  bool have[13] = {};
+  for (int s2 = 0; s2 < 27; s2++) {
+    const int ord = jxh::kStrategyOrder[s2];
+    if (have[ord]) continue;
+    have[ord] = true;
+    td.order_offset[ord] = uint32_t(orders.size());
+    if (size_t(jxh::kCoveredX[s2]) * jxh::kCoveredY[s2] > 64) continue;  // (the forward path selects up to 64x64)
+    std::vector<uint32_t> nat;
+    jxh::NaturalOrder(s2, &nat);
+    for (uint32_t v : nat) orders.push_back(uint16_t(v));
   }
-  f.SetSubsampling(p.color_transform == 2 ? uint32_t(p.chroma_subsampling) : 0u);
-  f.SetSize(xs, ys);
-  if (hook && f.Subsampled()) throw std::runtime_error("forward hook: unsupported parameters");
-  f.img_xs = img_xs ? img_xs : xs;
-  f.img_ys = img_ys ? img_ys : ys;
-  const size_t xp = f.xb * 8, yp = f.yb * 8;
-  if (p.adaptive_quant != 0 && p.adaptive_quant != 1) throw std::runtime_error("adaptive_quant: 0 or 1");
-  const bool adaptive = p.adaptive_quant == 1;
-  // (the field is defined over XYB planes at full resolution, under this writer's own transform choices)
-  if (adaptive && (p.color_transform || f.Subsampled() || p.strategy_mode > 1)) throw std::runtime_error("adaptive_quant: unsupported parameters");
-  float quant_ac;
-  QuantParams(p.distance, &f, &quant_ac, adaptive);
-  f.gab = p.gab < 0 ? 1 : p.gab;
-  if (hook) {
-    // image mode with the default colour correlation only: what the device path implements
-    if (p.strategy_mode > 1 || p.random_cmap || p.custom_cmap) throw std::runtime_error("forward hook: unsupported parameters");
-    const double t0 = NowSeconds();
-    f.epf_iters = p.epf_iters >= 0 ? p.epf_iters : (p.distance >= 4.0f ? 3 : p.distance >= 1.5f ? 2 : p.distance >= 0.7f ? 1 : 0);
-    f.flags = (p.skip_dc_smoothing ? 128 : 0) | (p.noise > 0 ? 1 : 0) | (g_splines.empty() ? 0 : 16) | (g_patches.empty() ? 0 : 2);
-    f.sharp.assign(f.xb * f.yb, 4);
-    f.ytox.assign(DivCeil(f.xb, 8) * DivCeil(f.yb, 8), 0);
-    f.ytob.assign(f.ytox.size(), 0);
-    // the default dequantisation tables, flat, built once (they do not depend on the image)
-    static std::vector<float> flat;
-    static uint32_t flat_offset[17], flat_size[17];
-    static std::once_flag flat_once;
-    std::call_once(flat_once, [] {
-      jxh::DequantTables dq;
-      for (int k = 0; k < 17; k++) {
-        flat_offset[k] = flat_size[k] = 0;
-        if (k >= 13) continue;  // 128 / 256 point tables: never selected here, not built
-        dq.Compute(k);
-        flat_offset[k] = uint32_t(flat.size());
-        flat_size[k] = uint32_t(dq.table[k].size() / 3);
-        flat.insert(flat.end(), dq.table[k].begin(), dq.table[k].end());
-      }
-    });
-    JxlHipEncDesc d;
-    memset(&d, 0, sizeof(d));
-    memcpy(d.dequant_offset, flat_offset, sizeof(flat_offset));
-    memcpy(d.dequant_size, flat_size, sizeof(flat_size));
-    d.dequant = flat.data();
-    d.dequant_floats = uint32_t(flat.size());
-    d.xsize = uint32_t(xs);
-    d.ysize = uint32_t(ys);
-    d.distance = p.distance;
-    d.gaborish = f.gab ? 1 : 0;
-    d.strategy_mode = uint32_t(p.strategy_mode);
-    d.global_scale = f.global_scale;
-    d.quant_dc = f.quant_dc;
-    d.quant_ac = quant_ac;
-    d.cfl_fit = p.cfl_fit ? 1 : 0;
-    d.quant_field_mode = adaptive ? 1 : 0;
-    d.ytox = f.ytox.data();
-    d.ytob = f.ytob.data();
-    const size_t nb = f.xb * f.yb, ng = DivCeil(xs, 256) * DivCeil(ys, 256);
-    f.acs.assign(nb, 0);
-    f.qf.assign(nb, 0);
-    // (no zero fill and no second copy of the coefficients: 100 MB at 4K)
-    std::vector<int32_t> dc(3 * nb);
-    // device tokenisation: one pass, natural orders, the default block context map (what it is written for)
-    const bool dev_tok = hook->tok_counts && hook->tok_emit && !hook->cap_acs && !(p.num_passes >= 2 && p.num_passes <= 3) && !p.custom_orders && !p.custom_bctx;
-    if (!dev_tok) f.flat_coeffs.reset(new int32_t[ng * 3 * 65536]);
-    int32_t* const co = f.flat_coeffs.get();
-    const int r = hook->fn(hook->ctx, rgb, xs * 3, &d, f.acs.data(), f.qf.data(), dc.data(), co);
-    if (r) throw std::runtime_error("forward hook failed (" + std::to_string(r) + ")");
-    if (dev_tok) {
-      JxlHipEncTokDesc td;
-      memset(&td, 0, sizeof(td));
-      std::vector<uint16_t> orders;
-      bool have[13] = {};
-      for (int s2 = 0; s2 < 27; s2++) {
-        const int ord = jxh::kStrategyOrder[s2];
-        if (have[ord]) continue;
-        have[ord] = true;
-        td.order_offset[ord] = uint32_t(orders.size());
-        if (size_t(jxh::kCoveredX[s2]) * jxh::kCoveredY[s2] > 64) continue;  // (the forward path selects up to 64x64)
-        std::vector<uint32_t> nat;
-        jxh::NaturalOrder(s2, &nat);
-        for (uint32_t v : nat) orders.push_back(uint16_t(v));
-      }
-      td.orders = orders.data();
-      td.orders_size = uint32_t(orders.size());
-      const jxh::BlockCtxMap bctx;
-      memcpy(td.ctx_map, bctx.ctx_map.data(), sizeof(td.ctx_map));
-      td.num_ctxs = uint32_t(bctx.num_ctxs);
-      td.num_hist = uint32_t((p.num_histograms > 1 && ng > 1) ? std::min<size_t>(size_t(p.num_histograms), ng) : 1);
-      f.dev_token_count.assign(ng, 0);
-      int tr = hook->tok_counts(hook->ctx, &td, f.dev_token_count.data());
-      if (tr) throw std::runtime_error("token hook failed (" + std::to_string(tr) + ")");
-      f.dev_token_base.assign(ng, 0);
-      uint64_t total = 0;
-      for (size_t g = 0; g < ng; g++) {
-        f.dev_token_base[g] = uint32_t(total);
-        total += f.dev_token_count[g];
-      }
-      if (total >= (uint64_t(1) << 32)) throw std::runtime_error("token hook: too many tokens");
-      // device entropy coding: plain ANS only (prefix codes and LZ77 stay with the host coder)
-      const bool dev_ans = hook->histograms && hook->ans_sizes && hook->ans_write && (p.ac_code_mode & 3) == 0 && !alpha;
-      if (!dev_ans) f.dev_tokens.assign(size_t(total) + 1, 0);
-      tr = hook->tok_emit(hook->ctx, f.dev_token_base.data(), dev_ans ? nullptr : reinterpret_cast<uint32_t*>(f.dev_tokens.data()), size_t(total));
-      if (tr) throw std::runtime_error("token hook failed (" + std::to_string(tr) + ")");
-      hook->device_tokens = total;
-      if (dev_ans) {
-        jxh::HybridCfg cfg420;
-        cfg420.split_exp = 4; cfg420.split_token = 16; cfg420.msb = 2; cfg420.lsb = 0;
-        const size_t num_ctx = size_t(td.num_ctxs) * 495 * td.num_hist;
-        JxlHipEncHistDesc hd = {cfg420.split_exp, cfg420.msb, cfg420.lsb, uint32_t(num_ctx)};
-        std::unique_ptr<uint32_t[]> counts(new uint32_t[num_ctx * 256]);
-        uint32_t max_tok = 0;
-        int er = hook->histograms(hook->ctx, &hd, counts.get(), &max_tok);
-        if (er) throw std::runtime_error("histogram hook failed (" + std::to_string(er) + ")");
-        std::vector<std::vector<uint32_t>> hist(num_ctx);
-        for (size_t c = 0; c < num_ctx; c++) {
-          const uint32_t* row = counts.get() + c * 256;
-          size_t used = 0;
-          for (size_t k = 0; k <= max_tok; k++)
-            if (row[k]) used = k + 1;
-          hist[c].assign(row, row + used);
-        }
-        counts.reset();
-        f.dev_ac_code.reset(new EncCode);
-        EncCode& code = *f.dev_ac_code;
-        InitCode(num_ctx, cfg420, 0, &code);
-        BuildCodeFromCounts(hist, max_tok, p.max_clusters > 0 ? size_t(p.max_clusters) : 64, &code);
-        AnsTables tab(code);
-        std::vector<uint8_t> pc(ng, uint8_t(CeilLog2(td.num_hist))), pv(ng);
-        for (size_t g = 0; g < ng; g++) pv[g] = uint8_t(g % td.num_hist);  // the histogram selector of write_ac_group
-        JxlHipEncAnsDesc ad = tab.Desc(pc.data(), pv.data());
-        f.dev_ac_nbits.assign(ng, 0);
-        er = hook->ans_sizes(hook->ctx, &ad, f.dev_ac_nbits.data());
-        if (er) throw std::runtime_error("ANS hook failed (" + std::to_string(er) + ")");
-        f.dev_ac_base.assign(ng, 0);
-        uint64_t bytes = 0;
-        for (size_t g = 0; g < ng; g++) {
-          f.dev_ac_base[g] = bytes;
-          bytes += (uint64_t(f.dev_ac_nbits[g]) + 7) / 8;
-        }
-        f.dev_ac_bits.assign(size_t(bytes) + 1, 0);
-        er = hook->ans_write(hook->ctx, f.dev_ac_base.data(), f.dev_ac_bits.data(), size_t(bytes));
-        if (er) throw std::runtime_error("ANS hook failed (" + std::to_string(er) + ")");
-        hook->device_coded = total;
-      }
-    }
-    if (hook->cap_acs) {
-      memcpy(hook->cap_acs, f.acs.data(), nb);
-      memcpy(hook->cap_qf, f.qf.data(), nb * 4);
-      memcpy(hook->cap_dc, dc.data(), dc.size() * 4);
-      memcpy(hook->cap_coeffs, co, ng * 3 * 65536 * 4);
-      return;
-    }
-    for (int c = 0; c < 3; c++) f.dc[c].assign(dc.begin() + c * nb, dc.begin() + (c + 1) * nb);
-    const double t1 = NowSeconds();
-    Assemble(f, p, out);
-    hook->seconds[0] = t1 - t0;
-    hook->seconds[1] = NowSeconds() - t1;
+  td.orders = orders.data();
+  td.orders_size = uint32_t(orders.size());
+  const jxh::BlockCtxMap bctx;
+  memcpy(td.ctx_map, bctx.ctx_map.data(), sizeof(td.ctx_map));
+  td.num_ctxs = uint32_t(bctx.num_ctxs);
+  td.num_hist = uint32_t((p.num_histograms > 1 && ng > 1) ? std::min<size_t>(size_t(p.num_histograms), ng) : 1);
+  f.dev_token_count.assign(ng, 0);
+  HookCheck(h.token_counts(ctx, &td, f.dev_token_count.data()), "token");
+  f.dev_token_base.assign(ng, 0);
+  uint64_t total = 0;
+  for (size_t g = 0; g < ng; g++) {
+    f.dev_token_base[g] = uint32_t(total);
+    total += f.dev_token_count[g];
+  }
+  if (total >= (uint64_t(1) << 32)) throw std::runtime_error("token hook: too many tokens");
+  if (!stay) f.dev_tokens.assign(size_t(total) + 1, 0);
+  HookCheck(h.tokens(ctx, f.dev_token_base.data(), stay ? nullptr : reinterpret_cast<uint32_t*>(f.dev_tokens.data()), size_t(total)), "token");
+  shape->num_ctxs = td.num_ctxs;
+  shape->num_hist = td.num_hist;
+  return total;
+}
+
+// Device entropy coding of the tokens DeviceTokens left there: the counts come up, the host builds the code from them and
+// hands its tables down, the sizes come up, and then the coded sections, each at its byte base.
+static void DeviceEntropy(const Hooks& h, void* ctx, const Params& p, size_t ng, const TokenShape& shape, FrameModel* fp) {
+  FrameModel& f = *fp;
+  jxh::HybridCfg cfg420;
+  cfg420.split_exp = 4; cfg420.split_token = 16; cfg420.msb = 2; cfg420.lsb = 0;
+  const size_t num_ctx = size_t(shape.num_ctxs) * 495 * shape.num_hist;
+  JxlHipEncHistDesc hd = {cfg420.split_exp, cfg420.msb, cfg420.lsb, uint32_t(num_ctx)};
+  std::unique_ptr<uint32_t[]> counts(new uint32_t[num_ctx * 256]);
+  uint32_t max_tok = 0;
+  HookCheck(h.histograms(ctx, &hd, counts.get(), &max_tok), "histogram");
+  std::vector<std::vector<uint32_t>> hist(num_ctx);
+  for (size_t c = 0; c < num_ctx; c++) {
+    const uint32_t* row = counts.get() + c * 256;
+    size_t used = 0;
+    for (size_t k = 0; k <= max_tok; k++)
+      if (row[k]) used = k + 1;
+    hist[c].assign(row, row + used);
+  }
+  counts.reset();
+  f.dev_ac_code.reset(new EncCode);
+  EncCode& code = *f.dev_ac_code;
+  InitCode(num_ctx, cfg420, 0, &code);
+  BuildCodeFromCounts(hist, max_tok, p.max_clusters > 0 ? size_t(p.max_clusters) : 64, &code);
+  AnsTables tab(code);
+  std::vector<uint8_t> pc(ng, uint8_t(CeilLog2(shape.num_hist))), pv(ng);
+  for (size_t g = 0; g < ng; g++) pv[g] = uint8_t(g % shape.num_hist);  // the histogram selector of write_ac_group
+  JxlHipEncAnsDesc ad = tab.Desc(pc.data(), pv.data());
+  f.dev_ac_nbits.assign(ng, 0);
+  HookCheck(h.ans_sizes(ctx, &ad, f.dev_ac_nbits.data()), "ANS");
+  f.dev_ac_base.assign(ng, 0);
+  uint64_t bytes = 0;
+  for (size_t g = 0; g < ng; g++) {
+    f.dev_ac_base[g] = bytes;
+    bytes += (uint64_t(f.dev_ac_nbits[g]) + 7) / 8;
+  }
+  f.dev_ac_bits.assign(size_t(bytes) + 1, 0);
+  HookCheck(h.ans_write(ctx, f.dev_ac_base.data(), f.dev_ac_bits.data(), size_t(bytes)), "ANS");
+}
+
+// EncodeImage with the model made by the hooks (image mode with the default colour correlation only: what the device path
+// implements). cap: the forward call's raw outputs go there and nothing else happens.
+static void EncodeImageHooks(const uint8_t* rgb, size_t xs, size_t ys, const Params& p, const Hooks& h, void* ctx, std::vector<uint8_t>* out,
+                             HookStats* stats, const ForwardCapture* cap) {
+  const double t0 = NowSeconds();
+  FrameModel f;
+  const float quant_ac = BeginFrame(&f, xs, ys, p, 0, 0, nullptr);
+  if (f.Subsampled() || p.strategy_mode > 1 || p.random_cmap || p.custom_cmap) throw std::runtime_error("forward hook: unsupported parameters");
+  const JxlHipEncDesc d = ForwardDesc(f, p, quant_ac);
+  const size_t nb = f.xb * f.yb, ng = DivCeil(xs, 256) * DivCeil(ys, 256);
+  f.acs.assign(nb, 0);
+  f.qf.assign(nb, 0);
+  // (no zero fill and no second copy of the coefficients: 100 MB at 4K)
+  std::vector<int32_t> dc(3 * nb);
+  const bool dev_tok = h.token_counts && h.tokens && !cap && !(p.num_passes >= 2 && p.num_passes <= 3) && !p.custom_orders && !p.custom_bctx;
+  if (!dev_tok) f.flat_coeffs.reset(new int32_t[ng * 3 * 65536]);
+  int32_t* const co = f.flat_coeffs.get();
+  HookCheck(h.forward(ctx, rgb, xs * 3, &d, f.acs.data(), f.qf.data(), dc.data(), co), "forward");
+  if (cap) {
+    memcpy(cap->acs, f.acs.data(), nb);
+    memcpy(cap->qf, f.qf.data(), nb * 4);
+    memcpy(cap->dc, dc.data(), dc.size() * 4);
+    memcpy(cap->coeffs, co, ng * 3 * 65536 * 4);
     return;
   }
+  if (dev_tok) {
+    // plain ANS only on the device (prefix codes and LZ77 stay with the host coder)
+    const bool dev_ans = h.histograms && h.ans_sizes && h.ans_write && (p.ac_code_mode & 3) == 0;
+    TokenShape shape;
+    stats->device_tokens = DeviceTokens(h, ctx, p, ng, dev_ans, &f, &shape);
+    if (dev_ans) {
+      DeviceEntropy(h, ctx, p, ng, shape, &f);
+      stats->device_coded = stats->device_tokens;
+    }
+  }
+  for (int c = 0; c < 3; c++) f.dc[c].assign(dc.begin() + c * nb, dc.begin() + (c + 1) * nb);
+  const double t1 = NowSeconds();
+  Assemble(f, p, out);
+  stats->forward_s = t1 - t0;
+  stats->assemble_s = NowSeconds() - t1;
+}
+
+// model_only: stop before the bitstream assembly and hand the frame model out (the CPU form of the forward path).
+static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& p, std::vector<uint8_t>* out, size_t img_xs = 0,
+                        size_t img_ys = 0, const AlphaPlane* alpha = nullptr, FrameModel* model_only = nullptr) {
+  FrameModel f;
+  const float quant_ac = BeginFrame(&f, xs, ys, p, img_xs, img_ys, alpha);
+  const bool adaptive = p.adaptive_quant == 1;
+  const size_t xp = f.xb * 8, yp = f.yb * 8;
   std::vector<float> xyb[3];
   if (p.color_transform) RgbToPlain(rgb, xs, ys, xp, yp, p.color_transform == 2, xyb);
   else RgbToXyb(rgb, xs, ys, xp, yp, xyb);
@@ -2368,13 +2375,8 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
       xyb[c].swap(sub);
     }
   }
-  f.epf_iters = p.epf_iters >= 0 ? p.epf_iters : (p.distance >= 4.0f ? 3 : p.distance >= 1.5f ? 2 : p.distance >= 0.7f ? 1 : 0);
-  f.flags = (p.skip_dc_smoothing ? 128 : 0) | (p.noise > 0 ? 1 : 0) | (g_splines.empty() ? 0 : 16) | (g_patches.empty() ? 0 : 2);
   f.acs.assign(f.xb * f.yb, 0xFF);
   f.qf.assign(f.xb * f.yb, 0);
-  f.sharp.assign(f.xb * f.yb, 4);
-  f.ytox.assign(DivCeil(f.xb, 8) * DivCeil(f.yb, 8), 0);
-  f.ytob.assign(f.ytox.size(), 0);
   Rng rng(p.seed + 12345);
   if (p.random_cmap)
     for (size_t i = 0; i < f.ytox.size(); i++) {
@@ -2446,8 +2448,7 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
   // adaptive quant field
   // (adaptive_quant: AdjustQuantField, enc_adaptive_quantization.cc:1198-1247, with the frame's own distance: the largest
   // value under the transform, mixed with the mean from four blocks on; then Quantizer::SetQuantFieldRect, quantizer.cc:78-88)
-  float mean_max_mixer = 1.0f;
-  if (p.distance > 1.54138f) mean_max_mixer = std::max(0.0f, 1.0f - (p.distance - 1.54138f) * 0.56391f);
+  const float mean_max_mixer = jxh::EncMeanMaxMixer(p.distance);
   for (size_t by = 0; by < f.yb; by++)
     for (size_t bx = 0; bx < f.xb; bx++) {
       uint8_t a = f.acs[by * f.xb + bx];
@@ -2536,7 +2537,7 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
   for (int s = 0; s < 27; s++) dq.Matrix(s, 0);  // precompute (not thread-safe lazily)
   const float inv_gs = 65536.0f / float(f.global_scale);
   // (x_qm_scale 3, b_qm_scale 2 in the frame header; an image that is not xyb_encoded codes neither: both are 2)
-  const float x_dm = p.color_transform ? 1.0f : std::pow(1.25f, 2.0f - 3.0f), b_dm = std::pow(1.25f, 2.0f - 2.0f);
+  const float x_dm = p.color_transform ? 1.0f : jxh::EncXDm(), b_dm = jxh::EncBDm();
   const float inv_quant_dc = inv_gs / float(f.quant_dc);
   const float dc_step[3] = {inv_quant_dc / 4096.0f, inv_quant_dc / 512.0f, inv_quant_dc / 256.0f};
   const size_t tiles_x = DivCeil(f.xb, 8);
@@ -3678,89 +3679,38 @@ int jxlenc_encode_rgb8(const uint8_t* rgb, uint32_t xs, uint32_t ys, const JxlEn
   return Finish(v, out, n);
 }
 
-// jxlenc_encode_rgb8 with the pixel-domain half (colour, sharpening, transform selection, forward DCT, quantisation) done
-// by `forward` (jxlhip_enc_forward and its context); entropy coding and headers here. seconds (may be NULL): forward
-// call, assembly.
-int jxlenc_encode_rgb8_forward(const uint8_t* rgb, uint32_t xs, uint32_t ys, const JxlEncParams* p, jxe::ForwardFn forward, void* ctx,
-                               uint8_t** out, size_t* n, double* seconds) {
+// jxlenc_encode_rgb8 with parts of the work done by the caller's functions on the caller's `ctx` (the device route:
+// jxlhip_enc_* of include/jxl_amd_hip.h on a JxlHipContext; this library does not link against them).
+//   forward                     the pixel-domain half (colour, sharpening, transform selection, forward DCT, quantisation);
+//                               entropy coding and headers here
+//   token_counts, tokens        the coefficients are tokenised there too and never come to the host, which starts from the
+//                               tokens. Progressive passes, coded orders or a coded block context map: the host tokenises.
+//   histograms, ans_sizes,      the tokens are counted and rANS-coded there as well: only the counts and the coded AC
+//   ans_write                   sections come to the host, which clusters, normalises and writes the headers. Plain ANS only;
+//                               prefix codes and LZ77 take the route above.
+// -1: bad arguments (upsampling > 1, a half-given pair or triple, the triple without the pair), -2: the writer threw.
+typedef jxe::Hooks JxlEncHooks;
+// forward call (copies included), assembly (entropy coding + headers); tokens the device produced / entropy-coded (0: the host did)
+typedef jxe::HookStats JxlEncHookStats;
+int jxlenc_encode_rgb8_hooks(const uint8_t* rgb, uint32_t xs, uint32_t ys, const JxlEncParams* p, const JxlEncHooks* hooks, void* ctx,
+                             uint8_t** out, size_t* n, JxlEncHookStats* stats) {
   jxe::UseThreads();
-  if (!rgb || !xs || !ys || !p || p->distance <= 0 || !forward) return -1;
+  if (!rgb || !xs || !ys || !p || p->distance <= 0 || !hooks || !hooks->forward) return -1;
+  const bool pair = hooks->token_counts && hooks->tokens, triple = hooks->histograms && hooks->ans_sizes && hooks->ans_write;
+  if (!pair && (hooks->token_counts || hooks->tokens)) return -1;
+  if (!triple && (hooks->histograms || hooks->ans_sizes || hooks->ans_write)) return -1;
+  if (triple && !pair) return -1;
   jxe::Params q;
   memcpy(&q, p, sizeof(q));
   if (q.upsampling > 1) return -1;
   std::vector<uint8_t> v;
-  jxe::ForwardHook hook = {forward, ctx, {0, 0}};
+  jxe::HookStats st = {0, 0, 0, 0};
   try {
-    jxe::EncodeImage(rgb, xs, ys, q, &v, 0, 0, nullptr, &hook);
+    jxe::EncodeImageHooks(rgb, xs, ys, q, *hooks, ctx, &v, &st, nullptr);
   } catch (...) {
     return -2;
   }
-  if (seconds) {
-    seconds[0] = hook.seconds[0];
-    seconds[1] = hook.seconds[1];
-  }
-  return Finish(v, out, n);
-}
-
-// The same with the coefficients tokenised on the device too (jxlhip_enc_token_counts / jxlhip_enc_tokens on the same context):
-// the host starts from the tokens. Falls back to host tokenisation for progressive passes, coded orders or a coded block
-// context map; seconds[2] receives the number of tokens the device produced (0 after that fallback).
-int jxlenc_encode_rgb8_forward_tokens(const uint8_t* rgb, uint32_t xs, uint32_t ys, const JxlEncParams* p, jxe::ForwardFn forward,
-                                      jxe::TokenCountsFn tok_counts, jxe::TokensFn tok_emit, void* ctx, uint8_t** out, size_t* n, double* seconds) {
-  jxe::UseThreads();
-  if (!rgb || !xs || !ys || !p || p->distance <= 0 || !forward || !tok_counts || !tok_emit) return -1;
-  jxe::Params q;
-  memcpy(&q, p, sizeof(q));
-  if (q.upsampling > 1) return -1;
-  std::vector<uint8_t> v;
-  jxe::ForwardHook hook = {forward, ctx, {0, 0}};
-  hook.tok_counts = tok_counts;
-  hook.tok_emit = tok_emit;
-  try {
-    jxe::EncodeImage(rgb, xs, ys, q, &v, 0, 0, nullptr, &hook);
-  } catch (...) {
-    return -2;
-  }
-  if (seconds) {
-    seconds[0] = hook.seconds[0];
-    seconds[1] = hook.seconds[1];
-    seconds[2] = double(hook.device_tokens);
-  }
-  return Finish(v, out, n);
-}
-
-// The same with the tokens counted and rANS-coded on the device as well (jxlhip_enc_histograms, jxlhip_enc_ans_sizes,
-// jxlhip_enc_ans_write on the same context): no token comes to the host, only the counts and the coded AC sections do; the host
-// clusters, normalises and writes the headers. Plain ANS in one pass with the default orders and block contexts; anything
-// else takes the route of jxlenc_encode_rgb8_forward_tokens (or _forward). seconds[2]: tokens the device produced,
-// seconds[3]: tokens the device coded (0 after a fallback).
-int jxlenc_encode_rgb8_forward_entropy(const uint8_t* rgb, uint32_t xs, uint32_t ys, const JxlEncParams* p, jxe::ForwardFn forward,
-                                       jxe::TokenCountsFn tok_counts, jxe::TokensFn tok_emit, jxe::HistogramsFn histograms,
-                                       jxe::AnsSizesFn ans_sizes, jxe::AnsWriteFn ans_write, void* ctx, uint8_t** out, size_t* n,
-                                       double* seconds) {
-  jxe::UseThreads();
-  if (!rgb || !xs || !ys || !p || p->distance <= 0 || !forward || !tok_counts || !tok_emit || !histograms || !ans_sizes || !ans_write) return -1;
-  jxe::Params q;
-  memcpy(&q, p, sizeof(q));
-  if (q.upsampling > 1) return -1;
-  std::vector<uint8_t> v;
-  jxe::ForwardHook hook = {forward, ctx, {0, 0}};
-  hook.tok_counts = tok_counts;
-  hook.tok_emit = tok_emit;
-  hook.histograms = histograms;
-  hook.ans_sizes = ans_sizes;
-  hook.ans_write = ans_write;
-  try {
-    jxe::EncodeImage(rgb, xs, ys, q, &v, 0, 0, nullptr, &hook);
-  } catch (...) {
-    return -2;
-  }
-  if (seconds) {
-    seconds[0] = hook.seconds[0];
-    seconds[1] = hook.seconds[1];
-    seconds[2] = double(hook.device_tokens);
-    seconds[3] = double(hook.device_coded);
-  }
+  if (stats) *stats = st;
   return Finish(v, out, n);
 }
 
@@ -3797,12 +3747,15 @@ struct JxlEncCpuCtx {
 JxlEncCpuCtx* jxlenc_cpu_ctx_new(void) { return new JxlEncCpuCtx; }
 void jxlenc_cpu_ctx_free(JxlEncCpuCtx* c) { delete c; }
 
+// The CPU form of the forward path, with jxlhip_enc_forward's signature: what the GPU tests compare the device path with,
+// array by array, and what lets the hook plumbing be tested without a GPU. ctx: a JxlEncCpuCtx, which keeps the model for
+// the token and entropy doubles below, or NULL (the model is then a local one). coeffs may be NULL.
 int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHipEncDesc* d, uint8_t* acs, int32_t* qf, int32_t* dc,
                        int32_t* coeffs) {
   JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
   jxe::UseThreads();
-  if (!c || !rgb || !d || !acs || !qf || !dc || stride < size_t(d->xsize) * 3) return -1;
-  c->have_model = c->have_tokens = c->resident = false;
+  if (!rgb || !d || !acs || !qf || !dc || stride < size_t(d->xsize) * 3) return -1;
+  if (c) c->have_model = c->have_tokens = c->resident = false;
   jxe::Params q;
   memset(&q, 0, sizeof(q));
   q.distance = d->distance;
@@ -3818,9 +3771,10 @@ int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHi
     for (uint32_t y = 0; y < d->ysize; y++) memcpy(tight.data() + size_t(y) * d->xsize * 3, rgb + y * stride, size_t(d->xsize) * 3);
     rgb = tight.data();
   }
-  jxe::FrameModel& f = c->f;
+  jxe::FrameModel local;
+  jxe::FrameModel& f = c ? c->f : local;
   try {
-    jxe::EncodeImage(rgb, d->xsize, d->ysize, q, nullptr, 0, 0, nullptr, nullptr, &f);
+    jxe::EncodeImage(rgb, d->xsize, d->ysize, q, nullptr, 0, 0, nullptr, &f);
   } catch (...) {
     return -2;
   }
@@ -3833,7 +3787,7 @@ int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHi
   for (int ch = 0; ch < 3; ch++) memcpy(dc + ch * nb, f.dc[ch].data(), nb * 4);
   if (coeffs)
     for (size_t g = 0; g < f.coeffs.size(); g++) memcpy(coeffs + g * 3 * 65536, f.coeffs[g].data(), size_t(3) * 65536 * 4);
-  c->have_model = true;
+  if (c) c->have_model = true;
   return 0;
 }
 
@@ -3937,44 +3891,6 @@ int jxlenc_cpu_ans_write(void* ctx, const uint64_t* byte_bases, uint8_t* out, si
   return 0;
 }
 
-// The CPU form of the forward path, with jxlhip_enc_forward's signature (ctx unused): what the GPU tests compare the
-// device path with, array by array, and what lets the hook plumbing be tested without a GPU.
-int jxlenc_forward_cpu(void*, const uint8_t* rgb, size_t stride, const JxlHipEncDesc* d, uint8_t* acs, int32_t* qf, int32_t* dc,
-                       int32_t* coeffs) {
-  jxe::UseThreads();
-  if (!rgb || !d || !acs || !qf || !dc || !coeffs || stride < size_t(d->xsize) * 3) return -1;
-  jxe::Params q;
-  memset(&q, 0, sizeof(q));
-  q.distance = d->distance;
-  q.epf_iters = -1;
-  q.gab = int32_t(d->gaborish);
-  q.strategy_mode = int32_t(d->strategy_mode);
-  q.cfl_fit = int32_t(d->cfl_fit);
-  q.adaptive_quant = int32_t(d->quant_field_mode);
-  q.seed = 1;
-  std::vector<uint8_t> tight;
-  if (stride != size_t(d->xsize) * 3) {
-    tight.resize(size_t(d->xsize) * d->ysize * 3);
-    for (uint32_t y = 0; y < d->ysize; y++) memcpy(tight.data() + size_t(y) * d->xsize * 3, rgb + y * stride, size_t(d->xsize) * 3);
-    rgb = tight.data();
-  }
-  jxe::FrameModel f;
-  try {
-    jxe::EncodeImage(rgb, d->xsize, d->ysize, q, nullptr, 0, 0, nullptr, nullptr, &f);
-  } catch (...) {
-    return -2;
-  }
-  if (f.global_scale != d->global_scale || f.quant_dc != d->quant_dc) return -3;  // the descriptor is not this distance's and quant field mode's
-  const size_t nb = f.xb * f.yb;
-  memcpy(acs, f.acs.data(), nb);
-  if (d->ytox) memcpy(d->ytox, f.ytox.data(), f.ytox.size());
-  if (d->ytob) memcpy(d->ytob, f.ytob.data(), f.ytob.size());
-  memcpy(qf, f.qf.data(), nb * 4);
-  for (int c = 0; c < 3; c++) memcpy(dc + c * nb, f.dc[c].data(), nb * 4);
-  for (size_t g = 0; g < f.coeffs.size(); g++) memcpy(coeffs + g * 3 * 65536, f.coeffs[g].data(), size_t(3) * 65536 * 4);
-  return 0;
-}
-
 // The CPU double of jxlhip_enc_initial_quant_field (include/jxl_amd_hip.h): the same arguments without the context.
 int jxlenc_cpu_initial_quant_field(const float* xyb, uint32_t xsize, uint32_t ysize, float butteraugli_target, float rescale, float* aq_map,
                                    float* mask) {
@@ -3990,7 +3906,7 @@ int jxlenc_cpu_initial_quant_field(const float* xyb, uint32_t xsize, uint32_t ys
   return 0;
 }
 
-// Test access: the raw outputs of one forward call made with the descriptor jxlenc_encode_rgb8_forward builds
+// Test access: the raw outputs of one forward call made with the descriptor jxlenc_encode_rgb8_hooks builds
 // (acs / qf: yb * xb, dc: 3 * yb * xb, coeffs: groups * 3 * 65536).
 int jxlenc_forward_model(const uint8_t* rgb, uint32_t xs, uint32_t ys, const JxlEncParams* p, jxe::ForwardFn forward, void* ctx,
                          uint8_t* acs, int32_t* qf, int32_t* dc, int32_t* coeffs) {
@@ -3998,14 +3914,11 @@ int jxlenc_forward_model(const uint8_t* rgb, uint32_t xs, uint32_t ys, const Jxl
   if (!rgb || !xs || !ys || !p || p->distance <= 0 || !forward || !acs || !qf || !dc || !coeffs) return -1;
   jxe::Params q;
   memcpy(&q, p, sizeof(q));
-  jxe::ForwardHook hook = {forward, ctx, {0, 0}};
-  hook.cap_acs = acs;
-  hook.cap_qf = qf;
-  hook.cap_dc = dc;
-  hook.cap_coeffs = coeffs;
-  std::vector<uint8_t> v;
+  JxlEncHooks hooks = {};
+  hooks.forward = forward;
+  const jxe::ForwardCapture cap = {acs, qf, dc, coeffs};
   try {
-    jxe::EncodeImage(rgb, xs, ys, q, &v, 0, 0, nullptr, &hook);
+    jxe::EncodeImageHooks(rgb, xs, ys, q, hooks, ctx, nullptr, nullptr, &cap);
   } catch (...) {
     return -2;
   }
@@ -4047,14 +3960,9 @@ int jxlenc_encode_rgba8(const uint8_t* rgba, uint32_t xs, uint32_t ys, const Jxl
   while ((ups << shift) < ecu) shift++;
   std::vector<uint8_t> v;
   try {
-    jxe::g_alpha_dims[0] = ecu == 1 ? 0 : aw;
-    jxe::g_alpha_dims[1] = ah;
-    jxe::g_alpha_dims[2] = ecu;
-    jxe::g_alpha_dims[3] = shift;
-    jxe::EncodeImage(rgb.data(), sx, sy, q, &v, ups == 1 ? 0 : xs, ups == 1 ? 0 : ys, &alpha);
-    jxe::g_alpha_dims[0] = 0;
+    const jxe::AlphaPlane a = {&alpha, ecu == 1 ? 0 : aw, ah, ecu, shift};
+    jxe::EncodeImage(rgb.data(), sx, sy, q, &v, ups == 1 ? 0 : xs, ups == 1 ? 0 : ys, &a);
   } catch (...) {
-    jxe::g_alpha_dims[0] = 0;
     return -2;
   }
   return Finish(v, out, n);

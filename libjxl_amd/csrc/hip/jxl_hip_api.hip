@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../../include/jxl_amd_hip.h"
+#include "../host/jxh_enc_shared.h"
 #include "jxl_hip_kernels.h"
 #include "jxl_hip_entropy_lanes.h"
 #include "jxl_hip_filter_fused.h"
@@ -3991,27 +3992,6 @@ static void EncAqLaunch(JxlHipContext* c, const jxlhip::EncAq& A) {
   hipLaunchKernelGGL(jxlhip::k_enc_aq_cells, dim3((strips + 3) / 4, (A.yp + jxlhip::kAqRows - 1) / jxlhip::kAqRows), dim3(256), 0, c->stream, A);
   hipLaunchKernelGGL(jxlhip::k_enc_aq_blocks, dim3((A.xb + 7) / 8, A.yb), dim3(64), 0, c->stream, A);
 }
-// The parameters of the field that depend on the distance alone (enc_adaptive_quantization.cc:319-331 dampen, :397-412
-// erosion weights, :1268-1270 scale): float32, as csrc/enc/jxl_enc.cc AqParams states them.
-static void EncAqParams(float target, float rescale, jxlhip::EncAq* A) {
-  const float scale = 0.765f / target * rescale;
-  const float base_level = 0.48f * scale;
-  float dampen = 1.0f;
-  if (target >= 2.0f) {
-    dampen = 1.0f - ((target - 2.0f) / (14.0f - 2.0f));
-    if (dampen < 0) dampen = 0;
-  }
-  A->mul = scale * dampen;
-  A->add = (1.0f - dampen) * base_level;
-  const float kMulBase[4] = {0.125f, 0.1f, 0.09f, 0.06f}, kMulAdd[4] = {0.0f, -0.1f, -0.09f, -0.06f};
-  const float mul = target < 2.0f ? (2.0f - target) * (1.0f / 2.0f) : 0.0f;
-  float norm_sum = 0.0f;
-  for (int i = 0; i < 4; i++) {
-    A->w[i] = kMulBase[i] + mul * kMulAdd[i];
-    norm_sum += A->w[i];
-  }
-  for (int i = 0; i < 4; i++) A->w[i] *= 0.29959705784054957f / norm_sum;
-}
 static int EncAqEnsure(JxlHipContext* c, uint32_t xp, uint32_t yp, jxlhip::EncAq* A) {
   const size_t nb = size_t(xp / 8) * (yp / 8);
   int r;
@@ -4111,10 +4091,7 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
   for (auto& ev : c->enc_ev)
     if (!ev) HIP_TRY(hipEventCreate(&ev));
   float lut[256];
-  for (int i = 0; i < 256; i++) {
-    const float v = float(i) / 255.0f;
-    lut[i] = v <= 0.04045f ? v / 12.92f : std::pow((v + 0.055f) / 1.055f, 2.4f);  // sRGB EOTF (transfer_functions-inl.h TF_SRGB)
-  }
+  for (int i = 0; i < 256; i++) lut[i] = jxh::SrgbEotf8(i);
   HIP_TRY(hipMemcpyAsync(c->enc_lut.p, lut, sizeof(lut), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->enc_dq.p, d->dequant, size_t(d->dequant_floats) * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->enc_rgb.p, rgb, stride * P.ys, hipMemcpyHostToDevice, c->stream));
@@ -4135,8 +4112,8 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
   P.distance = d->distance;
   P.quant_ac = d->quant_ac;
   P.inv_gs = 65536.0f / float(d->global_scale);
-  P.x_dm = std::pow(1.25f, 2.0f - 3.0f);  // x_qm_scale 3, b_qm_scale 2 (dec_cache.h:161-162)
-  P.b_dm = std::pow(1.25f, 2.0f - 2.0f);
+  P.x_dm = jxh::EncXDm();
+  P.b_dm = jxh::EncBDm();
   const float inv_quant_dc = P.inv_gs / float(d->quant_dc);
   P.dc_step[0] = inv_quant_dc / 4096.0f;
   P.dc_step[1] = inv_quant_dc / 512.0f;
@@ -4150,10 +4127,8 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
   if (P.quant_field_mode) {
     jxlhip::EncAq& A = c->enc_last_aq;
     // enc_heuristics.cc:1119-1122: the field's distance is 0.62 of the frame's without Gaborish; rescale 1
-    EncAqParams(d->gaborish ? d->distance : d->distance * 0.62f, 1.0f, &A);
-    // enc_adaptive_quantization.cc:1207-1218, with the frame's own distance
-    P.mean_max_mixer = 1.0f;
-    if (d->distance > 1.54138f) P.mean_max_mixer = std::max(0.0f, 1.0f - (d->distance - 1.54138f) * 0.56391f);
+    jxh::EncAqDistanceParams(d->gaborish ? d->distance : d->distance * 0.62f, 1.0f, &A);
+    P.mean_max_mixer = jxh::EncMeanMaxMixer(d->distance);
   }
   HIP_TRY(hipMemsetAsync(c->enc_ytox.p, 0, ntiles, c->stream));
   HIP_TRY(hipMemsetAsync(c->enc_ytob.p, 0, ntiles, c->stream));
@@ -4316,24 +4291,9 @@ int jxlhip_enc_ans_sizes(JxlHipContext* c, const JxlHipEncAnsDesc* d, uint32_t* 
     return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->ent_resident) return JXLHIP_ERR_NO_FRAME;
   c->ent_sized = false;
-  // every index the kernels form from the tables stays inside them: clusters below num_clusters; per cluster the
-  // frequencies sum to 4096 with rev_start their running sum (so rev_start + freq <= 4096) and no symbol beyond the
-  // alphabet; reverse-map entries below 4096
+  // (every index the kernels form from the tables stays inside them)
+  if (!jxh::AnsTablesInBounds(*d)) return JXLHIP_ERR_INVALID_ARGUMENT;
   const size_t ng = c->ent_base.size(), K = d->num_clusters;
-  for (uint32_t i = 0; i < d->num_ctx; i++)
-    if (d->ctx_map[i] >= K) return JXLHIP_ERR_INVALID_ARGUMENT;
-  for (size_t k = 0; k < K; k++) {
-    uint32_t sum = 0;
-    for (uint32_t s = 0; s < 256; s++) {
-      const uint32_t f = d->freq[k * 256 + s];
-      if (f && ((s >> d->log_alpha) || d->rev_start[k * 256 + s] != sum)) return JXLHIP_ERR_INVALID_ARGUMENT;
-      sum += f;
-      if (sum > 4096) return JXLHIP_ERR_INVALID_ARGUMENT;
-    }
-    if (sum != 4096) return JXLHIP_ERR_INVALID_ARGUMENT;
-    for (uint32_t i = 0; i < 4096; i++)
-      if (d->rev[k * 4096 + i] >= 4096) return JXLHIP_ERR_INVALID_ARGUMENT;
-  }
   uint64_t need = 0;
   for (size_t g = 0; g < ng; g++) {
     if (d->prefix_count[g] > 8) return JXLHIP_ERR_INVALID_ARGUMENT;
@@ -4467,7 +4427,7 @@ int jxlhip_enc_initial_quant_field(JxlHipContext* c, const float* xyb, uint32_t 
   const size_t plane = size_t(xsize) * ysize, nb = plane / 64;
   int r;
   if ((r = c->enc_aq_in.Ensure(3 * plane * 4)) || (r = EncAqEnsure(c, xsize, ysize, &A))) return r;
-  EncAqParams(butteraugli_target, rescale, &A);
+  jxh::EncAqDistanceParams(butteraugli_target, rescale, &A);
   A.planes = c->enc_aq_in.as<float>();
   HIP_TRY(hipMemcpyAsync(c->enc_aq_in.p, xyb, 3 * plane * 4, hipMemcpyHostToDevice, c->stream));
   EncAqLaunch(c, A);

@@ -1,4 +1,4 @@
-"""The CPU stream writer's model of the forward VarDCT path (jxlenc_forward_cpu through enc_forward_model with no
+"""The CPU stream writer's model of the forward VarDCT path (jxlenc_cpu_forward through enc_forward_model with no
 context) against the float64 reading of tests/enc_fwd_f64.py, which shares no code or tables with it. The CPU model is
 what the GPU kernels are held to array by array; this holds the pair's shared tables and conventions (resample scales,
 coefficient layout, quantisation bias, sharpening edges, dead zone) to an independent reading, and is where the
