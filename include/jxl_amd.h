@@ -83,6 +83,10 @@ size_t jxlamd_frame_section_sizes(const JxlAmdFrame* frame, uint32_t* sizes, siz
 /* Size of the decoded image: the frame size, times the upsampling factor of an upsampled frame (cropped to the image). */
 void jxlamd_frame_out_size(const JxlAmdFrame* frame, uint32_t* width_height);
 int jxlamd_frame_upload(const JxlAmdFrame* frame, JxlHipContext* ctx);
+/* Test aid: exchanges what varblocks i and j of the parsed frame say about themselves (position, strategy, quant field, DC
+ * context), leaving their coefficient offsets in place: a descriptor whose varblocks are not in raster order, for the
+ * upload's validation. Returns 0, or 1 when an index is out of range. */
+int jxlamd_frame_debug_swap_blocks(JxlAmdFrame* frame, uint32_t i, uint32_t j);
 /* Same, for a band of rows of 256x256 groups [group_row_begin, group_row_end) (see JxlHipFrameDesc); 0, 0 = whole frame. */
 int jxlamd_frame_upload_band(const JxlAmdFrame* frame, JxlHipContext* ctx, uint32_t group_row_begin, uint32_t group_row_end);
 /* Output transfer function of the frame's pixels: 0 = sRGB, 1 = linear (JxlDecoderSetOutputColorProfile); before upload. */

@@ -211,7 +211,8 @@ typedef struct JxlHipFrameDesc {
    * Its block at (sx, sy) is coded with the varblock at (sx << hshift, sy << vshift) (dec_group.cc:568-578: the other
    * varblocks carry nothing for it), its DC samples (`dc_quantised` / `dc`) sit in the top-left part of its plane with the
    * plane's row stride, and DequantDC applies no chroma from luma (compressed_dc.cc:232-250). xsize_blocks / ysize_blocks
-   * are then whole MCUs (multiples of 1 << the largest shift); only varblocks of one block; dc_smoothing must be 0
+   * are then whole MCUs (multiples of 1 << the largest shift); only varblocks of one block, every group's in raster order
+   * (the block context of a channel takes the quant field at the channel's own column, dec_group.cc:492); dc_smoothing must be 0
    * (dec_frame.cc:206-212). The decoded channel is upsampled in front of the loop filters
    * (render_pipeline/stage_chroma_upsampling.cc:29-111, dec_cache.cc:138-150). */
   uint8_t chroma_hshift[3], chroma_vshift[3];
@@ -409,6 +410,10 @@ int jxlhip_debug_noise(JxlHipContext* ctx, const float* xyb, uint32_t xsize, uin
  * the filter kernel (k_color_out / k_upsample_color), 1: the filter kernel itself (RGB8, RGB f32), 2: the one-channel
  * 8-bit form of the row-streaming filter kernel (k_filter_rows2<true, EPF, GAB, true>). */
 int jxlhip_debug_pixel_route(JxlHipContext* ctx, uint32_t* route);
+/* Test access: which kernel jxlhip_run_entropy launches for the VarDCT frame the context last uploaded. *route = 0:
+ * k_entropy_lanes (the frame is kept in scan order when it has one pass), 1: k_entropy_uni, 2: k_entropy_ans (alias tables
+ * beyond the LDS budget, read in place), 3: k_entropy_generic (prefix codes and / or LZ77). */
+int jxlhip_debug_entropy_route(JxlHipContext* ctx, uint32_t* route);
 
 /* Debug aid: with JXLHIP_GUARD=1 in the environment every device buffer of a context is allocated with a 4 KiB guard
  * band either side, filled with a pattern. Waits for the device, then *touched = 0 when every band is intact, else

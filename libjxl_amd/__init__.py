@@ -442,6 +442,25 @@ class HipContext:
         r = lib().jxlhip_get_errors(self._h, flags, n)
         return r, list(flags)
 
+    def entropy_route(self):
+        """Test access: the kernel run_entropy launches for the uploaded frame: 0 k_entropy_lanes, 1 k_entropy_uni,
+        2 k_entropy_ans, 3 k_entropy_generic."""
+        L = lib()
+        L.jxlhip_debug_entropy_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        r = ctypes.c_uint32()
+        _check(L.jxlhip_debug_entropy_route(self._h, ctypes.byref(r)), "jxlhip_debug_entropy_route")
+        return int(r.value)
+
+    def section_end_bits(self):
+        """jxlhip_get_section_end_bits: [pass][group], the bit (from the section's first byte) where the entropy stage's
+        coefficient walk ended."""
+        L = lib()
+        L.jxlhip_get_section_end_bits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        n = self.frame_info["num_groups"]
+        bits = np.zeros(n * self.frame_info.get("num_passes", 1), np.uint32)
+        _check(L.jxlhip_get_section_end_bits(self._h, bits.ctypes.data, bits.size), "jxlhip_get_section_end_bits")
+        return bits.reshape(-1, n)
+
     def stage_ms(self, which):
         ms = ctypes.c_float()
         _check(lib().jxlhip_last_stage_ms(self._h, which, ctypes.byref(ms)), "jxlhip_last_stage_ms")
@@ -565,6 +584,53 @@ class EncAnsDesc(ctypes.Structure):  # JxlHipEncAnsDesc
     _fields_ = [("split_exp", ctypes.c_uint32), ("msb_in_token", ctypes.c_uint32), ("lsb_in_token", ctypes.c_uint32), ("num_ctx", ctypes.c_uint32),
                 ("ctx_map", ctypes.c_void_p), ("num_clusters", ctypes.c_uint32), ("log_alpha", ctypes.c_uint32), ("freq", ctypes.c_void_p),
                 ("rev_start", ctypes.c_void_p), ("rev", ctypes.c_void_p), ("prefix_count", ctypes.c_void_p), ("prefix_value", ctypes.c_void_p)]
+
+
+class EncTokDesc(ctypes.Structure):  # JxlHipEncTokDesc
+    _fields_ = [("orders", ctypes.c_void_p), ("orders_size", ctypes.c_uint32), ("order_offset", ctypes.c_uint32 * 13),
+                ("ctx_map", ctypes.c_uint8 * 39), ("num_ctxs", ctypes.c_uint32), ("num_hist", ctypes.c_uint32)]
+
+
+class CpuEncContext:
+    """Test access: a JxlEncCpuCtx, the context of the jxlenc_cpu_* doubles of the encoder hooks. It keeps the model of
+    the last enc_forward_model(img, this) for enc_tokens."""
+
+    def __init__(self):
+        self._h = _enc_lib().jxlenc_cpu_ctx_new()
+
+    def close(self):
+        if self._h:
+            _enc_lib().jxlenc_cpu_ctx_free(self._h)
+            self._h = None
+
+
+def enc_tokens(ctx, orders, order_offset, ctx_map, num_ctxs, num_hist=1, guard=4):
+    """Test access: the AC tokens of the last forward call on `ctx`, from jxlhip_enc_token_counts / jxlhip_enc_tokens (a
+    HipContext) or the jxlenc_cpu_* pair (a CpuEncContext), under one JxlHipEncTokDesc: orders (uint16, bucket b at
+    order_offset[b]), ctx_map[39], num_ctxs, num_hist. Returns (totals, per group an (n, 2) uint32 array of {context,
+    value}, the `guard` pairs behind `capacity`, which were set to 0xA5A5A5A5 before the call)."""
+    orders = np.ascontiguousarray(orders, np.uint16)
+    d = EncTokDesc(orders.ctypes.data, orders.size, (ctypes.c_uint32 * 13)(*[int(v) for v in order_offset]),
+                   (ctypes.c_uint8 * 39)(*[int(v) for v in ctx_map]), int(num_ctxs), int(num_hist))
+    if isinstance(ctx, CpuEncContext):
+        E = _enc_lib()
+        counts, emit, what = E.jxlenc_cpu_token_counts, E.jxlenc_cpu_tokens, "jxlenc_cpu_token"
+    else:
+        L = lib()
+        counts, emit, what = L.jxlhip_enc_token_counts, L.jxlhip_enc_tokens, "jxlhip_enc_token"
+        counts.argtypes, emit.argtypes = [ctypes.c_void_p] * 3, [ctypes.c_void_p] * 3 + [ctypes.c_size_t]
+    ng = ((ctx.enc_size[0] + 255) // 256) * ((ctx.enc_size[1] + 255) // 256)
+    totals = np.zeros(ng, np.uint32)
+    r = counts(ctx._h, ctypes.byref(d), totals.ctypes.data)
+    if r:
+        raise JxlAmdError("%s_counts failed: %d" % (what, r))
+    bases = np.concatenate([[0], np.cumsum(totals)]).astype(np.uint32)
+    total = int(totals.sum())
+    buf = np.full((total + guard, 2), 0xA5A5A5A5, np.uint32)
+    r = emit(ctx._h, bases.ctypes.data, buf.ctypes.data, total)
+    if r:
+        raise JxlAmdError("%ss failed: %d" % (what, r))
+    return totals, [buf[int(bases[g]):int(bases[g + 1])].copy() for g in range(ng)], buf[total:].copy()
 
 
 class EncHooks(ctypes.Structure):  # JxlEncHooks: forward; token_counts + tokens; histograms + ans_sizes + ans_write
@@ -991,7 +1057,7 @@ def encode_rgb8_gpu(img, ctx, timings=None, device_tokens=False, device_entropy=
 
 def enc_forward_model(img, ctx=None, **kw):
     """Test access: the raw outputs of one forward call (acs, qf, dc, coeffs) from the GPU path on `ctx`, or from the
-    CPU stream writer's own model code when ctx is None."""
+    CPU stream writer's own model code when ctx is None or a CpuEncContext (which keeps the model, for enc_tokens)."""
     E = _enc_lib()
     img = np.ascontiguousarray(img, np.uint8)
     ys, xs = img.shape[:2]
@@ -999,11 +1065,14 @@ def enc_forward_model(img, ctx=None, **kw):
     acs, qf = np.zeros((yb, xb), np.uint8), np.zeros((yb, xb), np.int32)
     dc, co = np.zeros((3, yb, xb), np.int32), np.zeros((ng, 3, 65536), np.int32)
     p = _params(**kw)
-    fn = ctypes.cast(lib().jxlhip_enc_forward if ctx is not None else E.jxlenc_cpu_forward, ctypes.c_void_p)
+    cpu = ctx is None or isinstance(ctx, CpuEncContext)
+    fn = ctypes.cast(E.jxlenc_cpu_forward if cpu else lib().jxlhip_enc_forward, ctypes.c_void_p)
     r = E.jxlenc_forward_model(img.tobytes(), xs, ys, ctypes.byref(p), fn, ctx._h if ctx is not None else None, acs.ctypes.data,
                                qf.ctypes.data, dc.ctypes.data, co.ctypes.data)
     if r:
         raise JxlAmdError("jxlenc_forward_model failed (%d)" % r)
+    if ctx is not None:
+        ctx.enc_size = (xs, ys)
     return dict(acs=acs, qf=qf, dc=dc, coeffs=co)
 
 

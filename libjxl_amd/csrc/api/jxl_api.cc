@@ -309,6 +309,13 @@ static void UpsamplingKernels(uint32_t N, const jxh::ImageHeader& ih, std::vecto
 
 int jxlamd_frame_upload(const JxlAmdFrame* f, JxlHipContext* ctx) { return jxlamd_frame_upload_band(f, ctx, 0, 0); }
 
+int jxlamd_frame_debug_swap_blocks(JxlAmdFrame* f, uint32_t i, uint32_t j) {
+  if (!f || i >= f->plan.blocks.size() || j >= f->plan.blocks.size()) return 1;
+  std::swap(f->plan.blocks[i], f->plan.blocks[j]);
+  std::swap(f->plan.blocks[i].coef_offset, f->plan.blocks[j].coef_offset);
+  return 0;
+}
+
 int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t group_row_begin, uint32_t group_row_end) {
   g_last_error.clear();
   if (!f || !ctx) {

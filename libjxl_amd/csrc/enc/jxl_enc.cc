@@ -327,7 +327,11 @@ static void CountSymbols(const std::vector<const std::vector<Token>*>& streams, 
 
 // The second half: clustering, normalisation and the reverse maps (or prefix codes) from the counts. A count that is zero
 // contributes nothing anywhere below, so counts that reach further than a context's largest symbol give the same code.
-static void BuildCodeFromCounts(const std::vector<std::vector<uint32_t>>& hist, uint32_t max_tok, size_t max_clusters, EncCode* code) {
+// max_clusters (Params::max_clusters): 0 = 64; below 0 = up to that many (at most 256) with no merging by cost, so that a
+// small frame gets as many histograms as it has contexts in use (test streams with large alias tables).
+static void BuildCodeFromCounts(const std::vector<std::vector<uint32_t>>& hist, uint32_t max_tok, int32_t max_clusters_param, EncCode* code) {
+  const bool by_cost = max_clusters_param >= 0;
+  const size_t max_clusters = max_clusters_param > 0 ? size_t(max_clusters_param) : (by_cost ? 64 : std::min<size_t>(256, size_t(-int64_t(max_clusters_param))));
   const size_t num_ctx = code->num_ctx;
   code->log_alpha = code->use_prefix ? 15 : std::max(5, CeilLog2(max_tok + 1));
   if (!code->use_prefix && code->log_alpha > 8) abort();
@@ -362,7 +366,7 @@ static void BuildCodeFromCounts(const std::vector<std::vector<uint32_t>>& hist, 
         best = int(k);
       }
     }
-    bool merge = best >= 0 && (csum.size() >= max_clusters || best_cost < self_cost * 1.08 + 64.0);
+    bool merge = best >= 0 && (csum.size() >= max_clusters || (by_cost && best_cost < self_cost * 1.08 + 64.0));
     if (!merge) {
       csum.push_back(self);
       ctot.push_back(double(total[c]));
@@ -391,7 +395,7 @@ static void BuildCodeFromCounts(const std::vector<std::vector<uint32_t>>& hist, 
   BuildReverseMaps(code);
 }
 
-static void BuildCode(const std::vector<const std::vector<Token>*>& streams, size_t num_ctx, size_t max_clusters,
+static void BuildCode(const std::vector<const std::vector<Token>*>& streams, size_t num_ctx, int32_t max_clusters,
                       jxh::HybridCfg cfg, EncCode* code, int mode = 0) {
   InitCode(num_ctx, cfg, mode, code);
   std::vector<std::vector<uint32_t>> hist;
@@ -1234,7 +1238,7 @@ struct Params {
   int32_t strategy_mode;   // 0 = DCT8 only, 1 = heuristic mix (8..64), 2 = uniform random over `strategy_mask`
   uint32_t strategy_mask;  // bit per strategy for mode 2 (0 = all 27)
   uint32_t seed;
-  int32_t max_clusters;    // 0 = default (64)
+  int32_t max_clusters;    // 0 = default (64); < 0: up to -max_clusters, never merged by cost (BuildCodeFromCounts)
   int32_t skip_dc_smoothing;
   int32_t random_cmap;     // random chroma-from-luma factors (always on in random mode)
   int32_t zero_ac;         // random mode: leave every AC coefficient zero (DC-only stream)
@@ -1315,7 +1319,6 @@ static void TokenizeAcGroup(const FrameModel& f, size_t g, size_t xg, size_t pas
       const size_t cx = jxh::kCoveredX[st], cy = jxh::kCoveredY[st], log2c = jxh::kLog2Covered[st];
       const size_t covered = size_t(1) << log2c, size = covered * 64;
       const int ord = jxh::kStrategyOrder[st];
-      const uint32_t qf = uint32_t(f.qf[(by0 + by) * f.xb + bx0 + bx]);
       static const int kOrder[3] = {1, 0, 2};
       for (int ci = 0; ci < 3; ci++) {
         const int c = kOrder[ci];
@@ -1329,6 +1332,9 @@ static void TokenizeAcGroup(const FrameModel& f, size_t g, size_t xg, size_t pas
         const uint32_t* order = scan[(pass * 13 + ord) * 3 + c].data();
         size_t nz = 0;
         for (size_t k = covered; k < size; k++) nz += part(q[order[k]]) != 0;
+        // (the quant field at the channel's own column of the frame's row, the DC bucket at the frame's:
+        // enc_entropy_coder.cc:220 row_qf[sbx[c]] beside row_qdc[bx])
+        const uint32_t qf = uint32_t(f.qf[(by0 + by_) * f.xb + bx0 + bx]);
         size_t bc = bctx.Context(dc_bucket((by0 + by_) * f.xb + bx0 + bx_), qf, ord, c);
         const size_t hist_off = (g % num_hist) * nctx;  // this group's histogram set
         out_t.push_back({uint32_t(hist_off + bctx.NonZeroContext(uint32_t(pred), bc)), uint32_t(nz)});
@@ -1565,7 +1571,7 @@ static void Assemble(const FrameModel& f, const Params& p, std::vector<uint8_t>*
     const int mode = p.ac_code_mode & 3;  // bit 0: prefix codes, bit 1: LZ77
     if (mode & 2)
       for (size_t g = 0; g < num_groups; g++) Lz77Pass(&ac_tokens[pass * num_groups + g], uint32_t(nctx * num_hist));
-    BuildCode(all, nctx * num_hist + ((mode & 2) ? 1 : 0), p.max_clusters > 0 ? size_t(p.max_clusters) : 64, cfg420, &ac_codes[pass], mode);
+    BuildCode(all, nctx * num_hist + ((mode & 2) ? 1 : 0), p.max_clusters, cfg420, &ac_codes[pass], mode);
   }
   // ---- sections
   auto write_dc_global = [&](BitWriter& bw) {
@@ -2262,7 +2268,7 @@ static void DeviceEntropy(const Hooks& h, void* ctx, const Params& p, size_t ng,
   f.dev_ac_code.reset(new EncCode);
   EncCode& code = *f.dev_ac_code;
   InitCode(num_ctx, cfg420, 0, &code);
-  BuildCodeFromCounts(hist, max_tok, p.max_clusters > 0 ? size_t(p.max_clusters) : 64, &code);
+  BuildCodeFromCounts(hist, max_tok, p.max_clusters, &code);
   AnsTables tab(code);
   std::vector<uint8_t> pc(ng, uint8_t(CeilLog2(shape.num_hist))), pv(ng);
   for (size_t g = 0; g < ng; g++) pv[g] = uint8_t(g % shape.num_hist);  // the histogram selector of write_ac_group
@@ -3796,13 +3802,22 @@ int jxlenc_cpu_token_counts(void* ctx, const JxlHipEncTokDesc* d, uint32_t* tota
   if (!c || !d || !totals || !d->num_ctxs || !d->num_hist) return -1;
   if (!c->have_model) return -5;
   const jxe::FrameModel& f = c->f;
-  const jxh::BlockCtxMap bctx;  // the default map, the one the descriptor's callers pass
-  if (d->num_ctxs != bctx.num_ctxs || memcmp(d->ctx_map, bctx.ctx_map.data(), sizeof(d->ctx_map)) != 0) return -1;
+  // the descriptor's block context map (no thresholds) and orders, under jxlhip_enc_token_counts' own checks: the nine order
+  // buckets of the transforms the forward path selects, complete and with entries below their size
+  if (!d->orders || d->num_ctxs > 16) return -1;
+  jxh::BlockCtxMap bctx;
+  bctx.ctx_map.assign(d->ctx_map, d->ctx_map + 39);
+  bctx.num_ctxs = d->num_ctxs;
+  for (uint8_t v : bctx.ctx_map)
+    if (v >= d->num_ctxs) return -1;
+  static const uint32_t kBucketSize[9] = {64, 64, 256, 1024, 128, 256, 512, 4096, 2048};
   std::vector<std::vector<uint32_t>> scan(13 * 3);
-  for (int s2 = 0; s2 < 27; s2++) {
-    const int ord = jxh::kStrategyOrder[s2];
-    if (!scan[ord * 3].empty()) continue;
-    jxh::NaturalOrder(s2, &scan[ord * 3]);
+  for (int ord = 0; ord < 9; ord++) {
+    if (uint64_t(d->order_offset[ord]) + kBucketSize[ord] > d->orders_size) return -1;
+    const uint16_t* o = d->orders + d->order_offset[ord];
+    for (uint32_t k = 0; k < kBucketSize[ord]; k++)
+      if (o[k] >= kBucketSize[ord]) return -1;
+    scan[ord * 3].assign(o, o + kBucketSize[ord]);
     scan[ord * 3 + 1] = scan[ord * 3 + 2] = scan[ord * 3];
   }
   const size_t xg = jxe::DivCeil(f.xs, 256), ng = xg * jxe::DivCeil(f.ys, 256);

@@ -905,6 +905,12 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
           return JXLHIP_ERR_INVALID_ARGUMENT;
         if (v.coef_offset != off) return JXLHIP_ERR_INVALID_ARGUMENT;
         if (cs && cx[v.strategy] * cy[v.strategy] != 1) return JXLHIP_ERR_INVALID_ARGUMENT;  // (dec_modular.cc:534-538)
+        // (so a subsampled group's varblocks are its blocks in raster order: the entropy stage finds the block at a
+        // channel's own column, whose quant field its block context takes, that many entries back in the row)
+        if (cs) {
+          const uint32_t gw = std::min<uint32_t>(32, d->xsize_blocks - gx0);
+          if (v.bx != gx0 + (i - b0) % gw || v.by != gy0 + (i - b0) / gw) return JXLHIP_ERR_INVALID_ARGUMENT;
+        }
         off += 64u * cx[v.strategy] * cy[v.strategy];
         if (off > 65536) return JXLHIP_ERR_INVALID_ARGUMENT;
       }
@@ -1340,11 +1346,19 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
       for (uint32_t t = 0; t < d->num_qf_thresholds; t++) qfi += v.qf > d->qf_thresholds[t];
       uint32_t rec = (v.bx & 31u) | ((v.by & 31u) ? 32u : 0u) | uint32_t(kLog2Cx[v.strategy]) << 6 | uint32_t(kLog2Cy[v.strategy]) << 9;
       for (uint32_t ch = 0; ch < 3; ch++) {
-        const uint32_t bctx = d->block_ctx_lut[((ch * 13 + kOrderBucket[v.strategy]) * ep.nq + qfi) * ep.ndc + v.quant_dc_ctx];
-        rec |= (bctx & 15u) << (12 + 4 * ch);
         // (chroma-subsampled frames: bit 24 + channel = the block is off the channel's grid and carries nothing for it,
         // bit 27 + channel = the channel's columns are half the frame's)
         const uint32_t hs = (cs >> (2 * ch)) & 1u, vs = (cs >> (2 * ch + 1)) & 1u;
+        // the quant field at the channel's own column (dec_group.cc:492, 583-588: qf_row[sbx]); a subsampled group's
+        // varblocks are its blocks in raster order (validated above), so that block is fbx - (fbx >> hs) entries back
+        uint32_t qfc = qfi;
+        if (hs) {
+          const uint32_t fbx = v.bx & 31u;
+          qfc = 0;
+          for (uint32_t t = 0; t < d->num_qf_thresholds; t++) qfc += d->blocks[i - (fbx - (fbx >> 1))].qf > d->qf_thresholds[t];
+        }
+        const uint32_t bctx = d->block_ctx_lut[((ch * 13 + kOrderBucket[v.strategy]) * ep.nq + qfc) * ep.ndc + v.quant_dc_ctx];
+        rec |= (bctx & 15u) << (12 + 4 * ch);
         if ((v.bx & hs) | (v.by & vs)) rec |= 1u << (24 + ch);
         rec |= hs << (27 + ch);
       }
@@ -3567,6 +3581,13 @@ int jxlhip_debug_pixel_route(JxlHipContext* c, uint32_t* route) {
   if (!c || !route) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   *route = c->color_out || c->ups != 1 ? 0u : (c->gray8_fast ? 2u : 1u);
+  return 0;
+}
+
+int jxlhip_debug_entropy_route(JxlHipContext* c, uint32_t* route) {
+  if (!c || !route) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
+  *route = c->lanes ? 0u : (c->generic_codec ? 3u : (c->alias_lds ? 1u : 2u));  // (LaunchEntropy's own order of choices)
   return 0;
 }
 

@@ -255,7 +255,16 @@ __global__ __launch_bounds__(64) void k_entropy_ans(EntropyParams P) {
         if (lbx == 0) pred = lby ? nzc[(lby - 1) * 32] : 32;
         else if (lby == 0) pred = nzc[lbx - 1];
         else pred = (uint32_t(nzc[(lby - 1) * 32 + lbx]) + nzc[lby * 32 + lbx - 1] + 1) >> 1;
-        const uint32_t bctx = P.bctx_lut[((c * 13 + ord) * P.nq + qfi) * P.ndc + vb.quant_dc_ctx];
+        // The quant field of the block context is read at the channel's own column of the frame's row (dec_group.cc:492,
+        // 583-588: qf_row[sbx]). A subsampled frame has one block per varblock in raster order (jxlhip_frame_upload checks
+        // it), so that block is fbx - lbx entries back in this row.
+        uint32_t qfc = qfi;
+        if (P.cs != 0 && hs) {
+          const uint32_t q = P.blocks[bi - (fbx - lbx)].qf;
+          qfc = 0;
+          for (uint32_t t = 0; t + 1 < P.nq; t++) qfc += q > P.qf_thr[t];
+        }
+        const uint32_t bctx = P.bctx_lut[((c * 13 + ord) * P.nq + qfc) * P.ndc + vb.quant_dc_ctx];
         uint32_t nzb = pred >= 64 ? 64 : pred;
         nzb = nzb < 8 ? nzb : 4 + nzb / 2;
         uint32_t nzeros = ReadHybrid(br, state, l_ctx[nzb * P.num_bctx + bctx], T.alias, T.cfg, log_alpha);
@@ -455,7 +464,13 @@ __global__ __launch_bounds__(64) void k_entropy_generic(EntropyParams P) {
         if (lbx == 0) pred = lby ? nzc[(lby - 1) * 32] : 32;
         else if (lby == 0) pred = nzc[lbx - 1];
         else pred = (uint32_t(nzc[(lby - 1) * 32 + lbx]) + nzc[lby * 32 + lbx - 1] + 1) >> 1;
-        const uint32_t bctx = P.bctx_lut[((c * 13 + ord) * P.nq + qfi) * P.ndc + vb.quant_dc_ctx];
+        uint32_t qfc = qfi;  // (the quant field at the channel's own column: see k_entropy_ans)
+        if (P.cs != 0 && hs) {
+          const uint32_t q = P.blocks[bi - (fbx - lbx)].qf;
+          qfc = 0;
+          for (uint32_t t = 0; t + 1 < P.nq; t++) qfc += q > P.qf_thr[t];
+        }
+        const uint32_t bctx = P.bctx_lut[((c * 13 + ord) * P.nq + qfc) * P.ndc + vb.quant_dc_ctx];
         uint32_t nzb = pred >= 64 ? 64 : pred;
         nzb = nzb < 8 ? nzb : 4 + nzb / 2;
         uint32_t nzeros = GenericRead(r, ctx_map[nzb * P.num_bctx + bctx]);
@@ -741,7 +756,13 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_uni(EntropyBatch B) {
         if (lbx == 0) pred = lby ? Uni(nzc[(lby - 1) * 32]) : 32;
         else if (lby == 0) pred = Uni(nzc[lbx - 1]);
         else pred = (Uni(nzc[(lby - 1) * 32 + lbx]) + Uni(nzc[lby * 32 + lbx - 1]) + 1) >> 1;
-        const uint32_t li = ((c * 13 + ord) * P.nq + qfi) * P.ndc + dcctx;
+        uint32_t qfc = qfi;  // (the quant field at the channel's own column: see k_entropy_ans)
+        if (P.cs != 0 && hs) {
+          const uint32_t q = blk[(bi - (fbx - lbx)) * 3 + 1] >> 16;
+          qfc = 0;
+          for (uint32_t t = 0; t + 1 < P.nq; t++) qfc += q > P.qf_thr[t];
+        }
+        const uint32_t li = ((c * 13 + ord) * P.nq + qfc) * P.ndc + dcctx;
         const uint32_t bctx = (lut[li >> 2] >> ((li & 3) * 8)) & 0xFF;
         uint32_t nzb = pred >= 64 ? 64 : pred;
         nzb = nzb < 8 ? nzb : 4 + nzb / 2;

@@ -48,22 +48,27 @@ INFO = ("xsize", "ysize", "channels", "modular", "xsize_blocks", "ysize_blocks",
 _DTYPES = {"rgb8": np.uint8, "rgbf": np.float32, "coeffs": np.int32, "nzeros": np.int32, "xyb_idct": np.float32,
            "xyb_filtered": np.float32, "dc": np.float32, "acs": np.uint8, "quant": np.int32, "sharpness": np.uint8,
            "ytox": np.int8, "ytob": np.int8, "inv_sigma": np.float32, "quant_dc": np.uint8, "modular": np.int32,
-           "dc_unsmoothed": np.float32, "alphaf": np.float32}
+           "dc_unsmoothed": np.float32, "alphaf": np.float32, "ac_walk": np.int64}
 
 
 class Decoded:
-    def __init__(self, data, dumps=True, frame=0, prefix=0, preview=False):
+    def __init__(self, data, dumps=True, frame=0, prefix=0, preview=False, ac_export=False):
         """prefix: draw the frame from the first `prefix` bytes of the codestream alone (FrameDecoder::Flush: AC groups
-        whose sections are not whole inside the prefix keep all-zero coefficients); 0 = the whole stream."""
+        whose sections are not whole inside the prefix keep all-zero coefficients); 0 = the whole stream.
+        ac_export: keep what the AC coefficient walk was given as parsed (ac_tables; off by default)."""
         L = lib()
         data = bytes(data)
         L.jxlo_set_flush_prefix.argtypes = [ctypes.c_size_t]
         L.jxlo_set_flush_prefix.restype = None
+        L.jxlo_set_ac_export.argtypes = [ctypes.c_int]
+        L.jxlo_set_ac_export.restype = None
         L.jxlo_set_flush_prefix(prefix)
+        L.jxlo_set_ac_export(1 if ac_export else 0)
         try:
             self._h = L.jxlo_decode(data, len(data), (1 if dumps else 0) | (2 if preview else 0) | frame << 8)  # preview: the preview frame
         finally:
             L.jxlo_set_flush_prefix(0)
+            L.jxlo_set_ac_export(0)
         err = L.jxlo_error(self._h)
         if err:
             msg = err.decode()
@@ -101,6 +106,48 @@ class Decoded:
         v = [float(x) for x in a]
         return {"global_scale": int(v[0]), "quant_dc": int(v[1]), "dc_quant": v[2:5], "x_qm_scale": int(v[5]),
                 "b_qm_scale": int(v[6]), "color_factor": int(v[7]), "base_corr_x": v[8], "base_corr_b": v[9]}
+
+    @property
+    def ac_tables(self):
+        """What the oracle's AC coefficient walk was given, as parsed from a bare codestream (Decoded(..., ac_export=True); the
+        layout is ExportAcWalk's in jxlo_decoder.cc). A dict: num_passes, num_groups, num_histograms, hshift[3], vshift[3],
+        bctx = {num_ctxs, num_dc_ctxs, qf_thresholds, ctx_map}, passes = [{shift, use_prefix, log_alpha, lz77 = None or
+        {min_symbol, min_length, length_cfg, dist_ctx}, ctx_map, clusters = [{cfg = (split_exponent, msb, lsb), table = symbol
+        frequencies or prefix code lengths}], orders}], sections[pass][group] = (first bit of the walk in the codestream, byte
+        offset and byte size of the section that holds it, the bit behind the walk as the oracle read it)."""
+        a = self.buffer("ac_walk")
+        if a is None:
+            raise RuntimeError("no AC tables: decode a VarDCT frame with ac_export=True")
+        a = [int(v) for v in a]
+        pos = [0]
+
+        def take(n=None):
+            if n is None:
+                pos[0] += 1
+                return a[pos[0] - 1]
+            pos[0] += n
+            return a[pos[0] - n:pos[0]]
+
+        t = dict(num_passes=take(), num_groups=take(), num_histograms=take(), hshift=take(3), vshift=take(3))
+        b = dict(num_ctxs=take(), num_dc_ctxs=take())
+        b["qf_thresholds"] = take(take())
+        b["ctx_map"] = take(take())
+        t["bctx"] = b
+        t["passes"] = []
+        for _ in range(t["num_passes"]):
+            p = dict(shift=take(), use_prefix=bool(take()), log_alpha=take())
+            lz, min_symbol, min_length, length_cfg, dist_ctx = take(), take(), take(), tuple(take(3)), take()
+            p["lz77"] = dict(min_symbol=min_symbol, min_length=min_length, length_cfg=length_cfg, dist_ctx=dist_ctx) if lz else None
+            p["ctx_map"] = take(take())
+            p["clusters"] = []
+            for _ in range(take()):
+                cfg = tuple(take(3))
+                p["clusters"].append(dict(cfg=cfg, table=take(take())))
+            p["orders"] = np.array(take(take()), np.int64)
+            t["passes"].append(p)
+        t["sections"] = [[tuple(take(4)) for _ in range(t["num_groups"])] for _ in range(t["num_passes"])]
+        assert pos[0] == len(a)
+        return t
 
     def buffer(self, name):
         n = ctypes.c_size_t()

@@ -29,6 +29,7 @@
 
 namespace jxlo {
 static size_t g_flush_prefix = 0;  // jxlo_set_flush_prefix: bytes of the codestream that "have arrived" (0 = all)
+static bool g_ac_export = false;   // jxlo_set_ac_export: keep what DecodeAcGroupPass is given (Decoded::ac_walk), for the tests
 
 struct Decoded {
   ImageHeader ih;
@@ -61,6 +62,8 @@ struct Decoded {
   std::vector<int32_t> modular;    // planar decoded integer channels for Modular frames
   uint32_t used_acs = 0;
   uint64_t ac_symbols = 0;
+  // What DecodeAcGroupPass was given, as one list of integers (only under jxlo_set_ac_export; ExportAcWalk has the layout).
+  std::vector<int64_t> ac_walk;
 };
 
 struct FrameState {
@@ -91,6 +94,10 @@ struct FrameState {
   size_t num_histograms = 1;
   std::vector<std::vector<uint32_t>> orders;  // per pass
   std::vector<EntropyCode> ac_codes;          // per pass
+  // per (pass, group) under g_ac_export: first bit of the AC walk in the codestream, byte offset and size of the section
+  // that holds it, the bit behind the walk as this decoder read it
+  const uint8_t* cs_data = nullptr;
+  std::vector<int64_t> ac_sections;
   // planes
   size_t xb, yb;
   Planes3 idct;  // padded
@@ -428,6 +435,12 @@ static void DecodeAcGroupPass(BitReader& br, FrameState* s, size_t g, uint32_t p
   const size_t gx = g % d.xsize_groups, gy = g / d.xsize_groups;
   const size_t bx0 = gx * 32, by0 = gy * 32;
   const size_t bw = std::min<size_t>(32, d.xsize_blocks - bx0), bh = std::min<size_t>(32, d.ysize_blocks - by0);
+  int64_t* sect = s->ac_sections.empty() ? nullptr : &s->ac_sections[(size_t(pass) * d.num_groups + g) * 4];
+  if (sect) {
+    sect[0] = int64_t((br.data() - s->cs_data) * 8 + br.BitPos());
+    sect[1] = int64_t(br.data() - s->cs_data);
+    sect[2] = int64_t(br.size());
+  }
   size_t hbits = CeilLog2(s->num_histograms);
   size_t sel = hbits ? size_t(br.Read(hbits)) : 0;
   JXLO_CHECK(sel < s->num_histograms, "invalid histogram selector");
@@ -447,7 +460,6 @@ static void DecodeAcGroupPass(BitReader& br, FrameState* s, size_t g, uint32_t p
       const size_t cx = kCoveredX[st], cy = kCoveredY[st];
       const size_t log2c = kLog2Covered[st], covered = size_t(1) << log2c, size = covered * 64;
       const int ord = kStrategyOrder[st];
-      const uint32_t qf = uint32_t(o->quant[(by0 + by) * d.xsize_blocks + bx0 + bx]);
       const uint8_t qdc = o->quant_dc[(by0 + by) * d.xsize_blocks + bx0 + bx];
       static const int kChanOrder[3] = {1, 0, 2};
       for (int ci = 0; ci < 3; ci++) {
@@ -461,6 +473,8 @@ static void DecodeAcGroupPass(BitReader& br, FrameState* s, size_t g, uint32_t p
         const int32_t* top = by ? nzc + (by - 1) * 32 : nullptr;
         int32_t* cur = nzc + by * 32;
         int32_t predicted = PredictNz(top, cur, bx);
+        // (dec_group.cc:492 with the call at :583-588: the quant field at the channel's own column of the frame's row)
+        const uint32_t qf = uint32_t(o->quant[(by0 + fby) * d.xsize_blocks + bx0 + bx]);
         size_t block_ctx = s->bctx.Context(qdc, qf, ord, c);
         size_t nzctx = s->bctx.NonZeroContext(uint32_t(predicted), block_ctx) + ctx_offset;
         size_t nzeros = rd.Read(nzctx);
@@ -487,8 +501,49 @@ static void DecodeAcGroupPass(BitReader& br, FrameState* s, size_t g, uint32_t p
     }
   }
   JXLO_CHECK(rd.FinalStateOk(), "AC group: bad ANS final state");
+  if (sect) sect[3] = int64_t((br.data() - s->cs_data) * 8 + br.BitPos());
 #pragma omp atomic
   o->ac_symbols += symbols;
+}
+
+// The tables of the AC walk as parsed, for a reading of the walk that shares no code with this one (tests/ac_walk_np.py).
+// One list of integers:
+//   num_passes, num_groups, num_histograms, hshift[3], vshift[3],
+//   block context map: num_ctxs, num_dc_ctxs, n, qf_thresholds[n], m, ctx_map[m],
+//   per pass: pass shift, use_prefix, log_alpha, lz77, min_symbol, min_length, length config (split_exponent, msb, lsb),
+//             clustered distance context, n, context map[n] (num_histograms * NumACContexts entries, one more with LZ77),
+//             num_clusters, per cluster: split_exponent, msb, lsb, n, n symbol frequencies (rANS) or code lengths (prefix),
+//             n, coefficient orders[n],
+//   per (pass, group): the four numbers of FrameState::ac_sections.
+static void ExportAcWalk(const FrameState* s, std::vector<int64_t>* o) {
+  o->clear();
+  auto put = [o](int64_t v) { o->push_back(v); };
+  put(s->fh.num_passes); put(int64_t(s->dim.num_groups)); put(int64_t(s->num_histograms));
+  for (int c = 0; c < 3; c++) put(s->fh.hshift[c]);
+  for (int c = 0; c < 3; c++) put(s->fh.vshift[c]);
+  put(int64_t(s->bctx.num_ctxs)); put(int64_t(s->bctx.num_dc_ctxs));
+  put(int64_t(s->bctx.qf_thresholds.size()));
+  for (uint32_t t : s->bctx.qf_thresholds) put(t);
+  put(int64_t(s->bctx.ctx_map.size()));
+  for (uint8_t v : s->bctx.ctx_map) put(v);
+  for (uint32_t p = 0; p < s->fh.num_passes; p++) {
+    const EntropyCode& c = s->ac_codes[p];
+    put(s->fh.pass_shift[p]); put(c.use_prefix); put(c.log_alpha); put(c.lz77); put(c.lz_min_symbol); put(c.lz_min_length);
+    put(c.lz_len_cfg.split_exp); put(c.lz_len_cfg.msb); put(c.lz_len_cfg.lsb); put(c.lz_dist_ctx);
+    const size_t nmap = s->num_histograms * s->bctx.NumACContexts() + (c.lz77 ? 1 : 0);
+    put(int64_t(nmap));
+    for (size_t i = 0; i < nmap; i++) put(c.ctx_map[i]);
+    put(int64_t(c.num_clusters));
+    for (size_t k = 0; k < c.num_clusters; k++) {
+      put(c.cfg[k].split_exp); put(c.cfg[k].msb); put(c.cfg[k].lsb);
+      const std::vector<int32_t>& v = c.parsed[k];
+      put(int64_t(v.size()));
+      for (int32_t x : v) put(x);
+    }
+    put(int64_t(s->orders[p].size()));
+    for (uint32_t x : s->orders[p]) put(x);
+  }
+  for (int64_t v : s->ac_sections) put(v);
 }
 
 // Dequantise + CfL + LLF + inverse transform for all varblocks of a group (dec_group.cc:115-181, 433-450).
@@ -589,6 +644,8 @@ static void DecodeFrame(BitReader& br, const ImageHeader& ih, Decoded* out, bool
   const size_t base = br.BitPos() / 8;
   JXLO_CHECK(base + toc.total <= br.size(), "truncated frame");
   const uint8_t* data = br.data();
+  s->cs_data = data;
+  if (g_ac_export && !fh.modular) s->ac_sections.assign(np * d.num_groups * 4, -1);
   const size_t xb = d.xsize_blocks, yb = d.ysize_blocks;
   if (!fh.modular) {
     out->dc.assign(3 * xb * yb, 0.0f);
@@ -684,6 +741,7 @@ static void DecodeFrame(BitReader& br, const ImageHeader& ih, Decoded* out, bool
     }
   }
   br.Skip(base * 8 + toc.total * 8 - br.BitPos());
+  if (!s->ac_sections.empty()) ExportAcWalk(s, &out->ac_walk);
   // Undo the global modular transforms
   for (size_t i = s->full.transforms.size(); i-- > 0;) InverseTransform(&s->full, s->full.transforms[i]);
   s->full.transforms.clear();
@@ -1108,6 +1166,8 @@ struct JxloHandle {
 // flags: bit0 = keep intermediate dumps, bits 8.. = index of the frame to decode (animations). Returns a handle (never NULL);
 // check jxlo_error().
 void jxlo_set_flush_prefix(size_t nbytes) { jxlo::g_flush_prefix = nbytes; }
+// Off by default; on, a VarDCT frame's Decoded keeps the "ac_walk" buffer (ExportAcWalk).
+void jxlo_set_ac_export(int on) { jxlo::g_ac_export = on != 0; }
 JxloHandle* jxlo_decode(const uint8_t* data, size_t size, int flags) {
   JxloHandle* h = new JxloHandle;
   try {
@@ -1173,7 +1233,7 @@ const void* jxlo_buffer(JxloHandle* h, const char* name, size_t* nbytes) {
   }
   JXLO_BUF(rgb8) JXLO_BUF(rgbf) JXLO_BUF(coeffs) JXLO_BUF(nzeros) JXLO_BUF(xyb_idct) JXLO_BUF(xyb_filtered) JXLO_BUF(dc)
   JXLO_BUF(acs) JXLO_BUF(quant) JXLO_BUF(sharpness) JXLO_BUF(ytox) JXLO_BUF(ytob) JXLO_BUF(inv_sigma) JXLO_BUF(quant_dc) JXLO_BUF(dc_unsmoothed)
-  JXLO_BUF(modular) JXLO_BUF(alphaf)
+  JXLO_BUF(modular) JXLO_BUF(alphaf) JXLO_BUF(ac_walk)
 #undef JXLO_BUF
   *nbytes = 0;
   return nullptr;

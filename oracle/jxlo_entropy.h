@@ -49,6 +49,9 @@ struct EntropyCode {
   std::vector<AliasEntry> alias;        // cluster << log_alpha
   std::vector<PrefixCode> prefix;       // per cluster
   std::vector<int> degenerate;          // per cluster (-1 if not single-symbol)
+  // per cluster as parsed, kept for the tests' export of the tables: symbol frequencies (rANS) or code lengths (prefix; a
+  // single non-zero length is the zero-bit code of that symbol)
+  std::vector<std::vector<int32_t>> parsed;
   bool lz77 = false;
   uint32_t lz_min_symbol = 224, lz_min_length = 3;
   HybridCfg lz_len_cfg;
@@ -161,9 +164,11 @@ static inline void BuildPrefixFromLengths(const std::vector<uint8_t>& lens, Pref
   JXLO_CHECK(filled == pc->sym.size(), "prefix code is not complete");
 }
 
-static inline void ReadPrefixCode(BitReader& br, size_t alphabet_size, PrefixCode* pc) {
+static inline void ReadPrefixCode(BitReader& br, size_t alphabet_size, PrefixCode* pc, std::vector<uint8_t>* lens_out = nullptr) {
   JXLO_CHECK(alphabet_size <= (1u << 15), "prefix alphabet too large");
-  std::vector<uint8_t> lens(alphabet_size, 0);
+  std::vector<uint8_t> lens_local(alphabet_size, 0);
+  if (lens_out) lens_out->assign(alphabet_size, 0);
+  std::vector<uint8_t>& lens = lens_out ? *lens_out : lens_local;
   uint32_t hskip = uint32_t(br.Read(2));
   if (hskip == 1) {  // simple code: 1..4 explicit symbols
     int max_bits = alphabet_size > 1 ? FloorLog2(alphabet_size - 1) + 1 : 0;
@@ -577,6 +582,7 @@ static inline void DecodeHistograms(BitReader& br, size_t num_contexts, EntropyC
   for (auto& c : code->cfg) ReadHybridCfg(br, code->log_alpha, &c);
   const size_t max_alpha = size_t(1) << code->log_alpha;
   code->degenerate.assign(code->num_clusters, -1);
+  code->parsed.assign(code->num_clusters, std::vector<int32_t>());
   if (code->use_prefix) {
     code->prefix.resize(code->num_clusters);
     std::vector<uint32_t> sizes(code->num_clusters);
@@ -586,8 +592,11 @@ static inline void DecodeHistograms(BitReader& br, size_t num_contexts, EntropyC
     }
     for (size_t c = 0; c < code->num_clusters; c++) {
       if (sizes[c] > 1) {
-        ReadPrefixCode(br, sizes[c], &code->prefix[c]);
+        std::vector<uint8_t> lens;
+        ReadPrefixCode(br, sizes[c], &code->prefix[c], &lens);
+        code->parsed[c].assign(lens.begin(), lens.end());
       } else {
+        code->parsed[c].assign(1, 1);
         code->prefix[c].max_len = 0;
         code->prefix[c].sym.assign(1, 0);
         code->prefix[c].len.assign(1, 0);
@@ -602,6 +611,7 @@ static inline void DecodeHistograms(BitReader& br, size_t num_contexts, EntropyC
       ReadHistogram(br, &counts);
       JXLO_CHECK(counts.size() <= max_alpha, "ANS alphabet too large");
       while (!counts.empty() && counts.back() == 0) counts.pop_back();
+      code->parsed[c] = counts;
       for (size_t s = 0; s < counts.size(); s++)
         if (counts[s]) UpdateMaxBits(code, c, s);
       int deg = counts.empty() ? 0 : int(counts.size()) - 1;

@@ -1,7 +1,11 @@
 """A plain reading of the rANS *decoder* for the entropy tests: alias tables (lib/jxl/ans_common.cc InitAliasTable,
 ans_common.h:102-142 Lookup), the symbol read (dec_ans.h:170-197) and the hybrid-uint read (dec_ans.h:226-257), on an
 LSB-first bit string. It shares nothing with the encoder under test: what that writes must come back through here token
-for token, and the coder must end in its start state (dec_ans.h:222)."""
+for token, and the coder must end in its start state (dec_ans.h:222).
+
+For the AC coefficient walk (tests/ac_walk_np.py) there is also a streaming reader, Reader.read(context), over a Code as a
+decoder parsed it: a hybrid-uint configuration per cluster, rANS or prefix codes rebuilt canonically from their code
+lengths (huffman_table.cc:64-146, dec_huffman.cc), and the LZ77 layer of dec_ans.h:287-353."""
 import numpy as np
 
 ANS_LOG_TAB_SIZE = 12
@@ -112,3 +116,134 @@ def decode(data, nbits, contexts, ctx_map, freqs, log_alpha, cfg=(4, 2, 0), pref
     if br.pos != nbits:
         raise ValueError("%d bits left" % (nbits - br.pos))
     return prefix, values
+
+
+# ---------------------------------------------------------------- the streaming reader (dec_ans.h:162-353, dec_ans.cc:334-377)
+LZ_WINDOW = 1 << 20  # dec_ans.h:105 kWindowSize
+
+
+class ByteBits:
+    """LSB-first bits [begin, end) of `data`; reading past `end` is an error (the reference zero-fills and fails at Close)."""
+
+    def __init__(self, data, begin, end):
+        self.d = bytes(data)
+        self.pos, self.end = int(begin), int(end)
+
+    def read(self, k):
+        p = self.pos
+        if p + k > self.end:
+            raise ValueError("read past the end of the section (%d + %d > %d)" % (p, k, self.end))
+        self.pos = p + k
+        return (int.from_bytes(self.d[p >> 3:(p >> 3) + 8], "little") >> (p & 7)) & ((1 << k) - 1)
+
+
+def canonical_prefix_code(lengths):
+    """{(length, code read first bit first): symbol} of the canonical code with these lengths: codes are handed out by
+    length, then by symbol (huffman_table.cc:64-146 sorts the symbols so; its table is indexed by the bit-reversed code,
+    which is the same as reading the code's bits first to last). A code with one used symbol has no bits."""
+    used = [i for i, n in enumerate(lengths) if n]
+    if len(used) <= 1:
+        return {(0, 0): used[0] if used else 0}
+    out, code = {}, 0
+    for n in range(1, max(lengths) + 1):
+        for sym in used:
+            if lengths[sym] == n:
+                out[(n, code)] = sym
+                code += 1
+        code <<= 1
+    if code != 1 << (max(lengths) + 1):
+        raise ValueError("the code lengths do not fill the code space")
+    return out
+
+
+class Code:
+    """An entropy code as a decoder parsed it: use_prefix, log_alpha, ctx_map (context -> cluster), per cluster cfg =
+    (split_exponent, msb_in_token, lsb_in_token) and table = symbol frequencies (rANS) or code lengths (prefix), lz77 = None
+    or dict(min_symbol, min_length, length_cfg, dist_ctx (clustered))."""
+
+    def __init__(self, use_prefix, log_alpha, ctx_map, clusters, lz77=None):
+        self.use_prefix, self.log_alpha, self.ctx_map, self.lz77 = bool(use_prefix), int(log_alpha), list(ctx_map), lz77
+        self.cfg = [tuple(c["cfg"]) for c in clusters]
+        if self.use_prefix:
+            self.prefix = [canonical_prefix_code(c["table"]) for c in clusters]
+        else:
+            log_entry = ANS_LOG_TAB_SIZE - self.log_alpha
+            self.lookup = []  # per cluster, per state residue: (symbol, offset, frequency) (ans_common.h:102-142 Lookup)
+            for c in clusters:
+                table = alias_table(c["table"], self.log_alpha)
+                rows = []
+                for res in range(ANS_TAB_SIZE):
+                    idx, pos = res >> log_entry, res & ((1 << log_entry) - 1)
+                    cut, rv, f0, o1, f1 = table[idx]
+                    rows.append((rv, o1 + pos, f1) if pos >= cut else (idx, pos, f0))
+                self.lookup.append(rows)
+
+
+class Reader:
+    """ANSSymbolReader on bits [begin, end) of `data`: Create reads the 32-bit state of a rANS code (dec_ans.cc:351-355);
+    read(context) is ReadHybridUintClusteredInlined behind the context map. `copies` counts LZ77 copy commands."""
+
+    def __init__(self, code, data, begin, end, distance_multiplier=0):
+        assert distance_multiplier == 0, "special distances (dec_ans.h:141-145) are not read here: AC streams have none"
+        self.c, self.br = code, ByteBits(data, begin, end)
+        self.state = ANS_SIGNATURE << 16 if code.use_prefix else self.br.read(32)
+        self.window = {} if code.lz77 else None  # position & mask -> value
+        self.num_decoded = self.num_to_copy = self.copy_pos = self.copies = 0
+
+    @property
+    def pos(self):
+        return self.br.pos
+
+    def final_state_ok(self):
+        return self.state == ANS_SIGNATURE << 16
+
+    def _symbol(self, cluster):
+        if self.c.use_prefix:
+            table = self.c.prefix[cluster]
+            if (0, 0) in table:
+                return table[(0, 0)]
+            n = code = 0
+            while True:
+                code, n = (code << 1) | self.br.read(1), n + 1
+                if (n, code) in table:
+                    return table[(n, code)]
+                if n > 15:
+                    raise ValueError("no such prefix code")
+        sym, off, freq = self.c.lookup[cluster][self.state & (ANS_TAB_SIZE - 1)]
+        state = freq * (self.state >> ANS_LOG_TAB_SIZE) + off
+        if state < (1 << 16):
+            state = (state << 16) | self.br.read(16)
+        self.state = state
+        return sym
+
+    def _copy(self):
+        r = self.window.get(self.copy_pos & (LZ_WINDOW - 1), 0)
+        self.copy_pos += 1
+        self.num_to_copy -= 1
+        self.window[self.num_decoded & (LZ_WINDOW - 1)] = r
+        self.num_decoded += 1
+        return r
+
+    def read(self, ctx):
+        if not 0 <= ctx < len(self.c.ctx_map) - (1 if self.c.lz77 else 0):
+            raise ValueError("context %d is beyond the context map" % ctx)
+        cluster = self.c.ctx_map[ctx]
+        lz = self.c.lz77
+        if lz is None:
+            return read_hybrid(self.br, self._symbol(cluster), *self.c.cfg[cluster])
+        if self.num_to_copy > 0:
+            return self._copy()
+        token = self._symbol(cluster)
+        if token >= lz["min_symbol"]:
+            self.num_to_copy = read_hybrid(self.br, token - lz["min_symbol"], *lz["length_cfg"]) + lz["min_length"]
+            distance = read_hybrid(self.br, self._symbol(lz["dist_ctx"]), *self.c.cfg[lz["dist_ctx"]]) + 1  # no special distances
+            distance = min(distance, self.num_decoded, LZ_WINDOW)
+            self.copy_pos = self.num_decoded - distance
+            if distance == 0:  # nothing decoded yet: the copy reads zeros (dec_ans.h:323-328)
+                self.window = {}
+            self.copies += 1
+            return self._copy()
+        r = read_hybrid(self.br, token, *self.c.cfg[cluster])
+        self.window[self.num_decoded & (LZ_WINDOW - 1)] = r
+        self.num_decoded += 1
+        return r
