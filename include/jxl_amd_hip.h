@@ -690,6 +690,14 @@ int jxlhip_enc_entropy_last_ms(JxlHipContext* ctx, float* ms);
  * (relative 3e-7). Synchronous; leaves the last jxlhip_enc_forward's state as it was. */
 int jxlhip_enc_initial_quant_field(JxlHipContext* ctx, const float* xyb, uint32_t xsize, uint32_t ysize, float butteraugli_target,
                                    float rescale, float* aq_map, float* mask);
+/* The per-pixel masking the reference's AC-strategy search reads (mask1x1: enc_adaptive_quantization.cc ComputeTile :498-526
+ * and Blur1x1Masking :634-662, borders as convolve_symmetric5.cc has them), alone: xyb as above (only the Y plane is read),
+ * taken BEFORE any sharpening, like the quant field; out[ysize][xsize] in host memory. log1p is the exact function, as in the
+ * reference. Synchronous; leaves the last jxlhip_enc_forward's state as it was. jxlenc_cpu_masking_1x1 (libjxlenc) is the
+ * CPU double with the same arguments less the context. */
+int jxlhip_enc_masking_1x1(JxlHipContext* ctx, const float* xyb, uint32_t xsize, uint32_t ysize, float* out);
+/* Kernel time of the last jxlhip_enc_masking_1x1 (copies excluded), milliseconds. */
+int jxlhip_enc_masking_last_ms(JxlHipContext* ctx, float* ms);
 /* Kernel time of the two quant-field kernels in the last pass of the last jxlhip_enc_forward / _rerun made with
  * quant_field_mode 1 (they are part of jxlhip_enc_last_ms too), milliseconds. */
 int jxlhip_enc_aq_last_ms(JxlHipContext* ctx, float* ms);

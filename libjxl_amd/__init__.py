@@ -347,6 +347,14 @@ class HipContext:
         _check(L.jxlhip_enc_aq_last_ms(self._h, ctypes.byref(a)), "jxlhip_enc_aq_last_ms")
         return a.value
 
+    def enc_masking_ms(self):
+        """Measurement: ms of the kernel of the last masking_1x1 on this context."""
+        L = lib()
+        L.jxlhip_enc_masking_last_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+        a = ctypes.c_float()
+        _check(L.jxlhip_enc_masking_last_ms(self._h, ctypes.byref(a)), "jxlhip_enc_masking_last_ms")
+        return a.value
+
     def debug_ans_write(self, tokens, tables, capacity=None):
         """Test access: rANS-codes `tokens` ((n, 2) uint32 {context, value} pairs) as one section with the device's entropy
         kernels and the code `tables` (an AnsTables). Returns (the bit string as bytes, its length in bits); `capacity`
@@ -709,6 +717,7 @@ def _enc_lib():
             "cpu_ans_sizes": (c_int, [vp] * 3),
             "cpu_ans_write": (c_int, [vp] * 3 + [sz]),
             "cpu_initial_quant_field": (c_int, [vp, u32, u32, ctypes.c_float, ctypes.c_float, vp, vp]),
+            "cpu_masking_1x1": (c_int, [vp, u32, u32, vp]),
             # what the next streams carry (test aids)
             "set_custom_upsampling": (None, [u32, u32]),
             "set_embedded_icc": (None, [cp, sz, sz]),
@@ -1097,6 +1106,27 @@ def initial_quant_field(xyb, distance, ctx=None, rescale=1.0):
         if r:
             raise JxlAmdError("jxlenc_cpu_initial_quant_field failed (%d)" % r)
     return aq, mask
+
+
+def masking_1x1(xyb, ctx=None):
+    """The per-pixel masking the reference's AC-strategy search reads (mask1x1) of X, Y, B planes [3][ysize][xsize] (float32,
+    sizes multiples of 8, before any sharpening): [ysize][xsize] float32. On the GPU (jxlhip_enc_masking_1x1 on `ctx`), or
+    from the CPU stream writer's own code when ctx is None."""
+    xyb = np.ascontiguousarray(xyb, np.float32)
+    if xyb.ndim != 3 or xyb.shape[0] != 3:
+        raise ValueError("xyb: [3][ysize][xsize]")
+    ys, xs = xyb.shape[1:]
+    out = np.zeros((ys, xs), np.float32)
+    args = (xyb.ctypes.data, xs, ys, out.ctypes.data)
+    if ctx is not None:
+        L = lib()
+        L.jxlhip_enc_masking_1x1.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+        _check(L.jxlhip_enc_masking_1x1(ctx._h, *args), "jxlhip_enc_masking_1x1")
+    else:
+        r = _enc_lib().jxlenc_cpu_masking_1x1(*args)
+        if r:
+            raise JxlAmdError("jxlenc_cpu_masking_1x1 failed (%d)" % r)
+    return out
 
 
 def encode_rgba8(img, **kw):

@@ -2086,6 +2086,57 @@ static void InitialQuantField(const float* px, const float* py, const float* pb,
     }
 }
 
+// ---- the reference's per-pixel masking (mask1x1: enc_adaptive_quantization.cc ComputeTile :498-526, Blur1x1Masking :634-662
+// with Symmetric5Border / WeightedSumBorder of convolve_symmetric5.cc:35-97), which its AC-strategy search reads. From the Y
+// plane before the sharpening, like the quant field. float32, every expression written once and not contracted;
+// k_enc_mask1x1 (csrc/hip/jxl_hip_enc.h) restates it operation by operation:
+//   laplacian  base = 0.25 * (((down + up) + left) + right), a neighbour outside the plane being the sample itself;
+//              v = 1 / (log1p(|ratio<false>(Y + 0.019) * (Y - base)|) + 0.01)
+//   blur       rows and columns outside the plane MIRRORED (-1 -> 0, -2 -> 1; n -> n - 1, n + 1 -> n - 2); a row's sum is
+//              w2 * (m2 + p2) + (w1 * (m1 + p1) + w0 * centre); the five rows as
+//              ((row(y) + row(y - 2)) + row(y - 1)) + (row(y + 2) + row(y + 1))
+// log1p is the exact function, as in the reference.
+static inline size_t MirrorIndex(int64_t x, int64_t n) {
+  while (x < 0 || x >= n) x = x < 0 ? -x - 1 : 2 * n - 1 - x;
+  return size_t(x);
+}
+// py: the Y plane of xp x yp samples; out the same size
+static void Masking1x1(const float* py, size_t xp, size_t yp, float* out) {
+  float w[6];
+  jxh::EncMask1x1Weights(w);
+  std::vector<float> lap(xp * yp);
+#pragma omp parallel for
+  for (size_t y = 0; y < yp; y++) {
+    const float* row = py + y * xp;
+    const float* up = py + (y ? y - 1 : y) * xp;
+    const float* down = py + (y + 1 < yp ? y + 1 : y) * xp;
+    for (size_t x = 0; x < xp; x++) {
+      const float left = row[x ? x - 1 : x], right = row[x + 1 < xp ? x + 1 : x];
+      const float base = 0.25f * (down[x] + up[x] + left + right);
+      const float d = std::fabs(AqGammaRatio<false>(row[x] + 0.019f) * (row[x] - base));
+      lap[y * xp + x] = 1.0f / (std::log1p(d) + 0.01f);
+    }
+  }
+  auto row_sum = [&](int64_t y, size_t x, float w0, float w1, float w2) {
+    const float* r = lap.data() + MirrorIndex(y, int64_t(yp)) * xp;
+    const float m2 = r[MirrorIndex(int64_t(x) - 2, int64_t(xp))], p2 = r[MirrorIndex(int64_t(x) + 2, int64_t(xp))];
+    const float m1 = r[MirrorIndex(int64_t(x) - 1, int64_t(xp))], p1 = r[MirrorIndex(int64_t(x) + 1, int64_t(xp))];
+    const float s2 = w2 * (m2 + p2), s1 = w1 * (m1 + p1), s0 = w0 * r[x];
+    return s2 + (s1 + s0);
+  };
+#pragma omp parallel for
+  for (size_t y = 0; y < yp; y++)
+    for (size_t x = 0; x < xp; x++) {
+      const int64_t iy = int64_t(y);
+      float sum0 = row_sum(iy, x, w[0], w[1], w[2]);
+      sum0 += row_sum(iy - 2, x, w[2], w[4], w[5]);
+      float sum1 = row_sum(iy + 2, x, w[2], w[4], w[5]);
+      sum0 += row_sum(iy - 1, x, w[1], w[3], w[4]);
+      sum1 += row_sum(iy + 1, x, w[1], w[3], w[4]);
+      out[y * xp + x] = sum0 + sum1;
+    }
+}
+
 // The alpha plane of jxlenc_encode_rgba8 with its geometry: w x h samples (w = 0: frame sized), the extra channel's upsampling
 // factor and its shift against the frame.
 struct AlphaPlane {
@@ -3915,6 +3966,18 @@ int jxlenc_cpu_initial_quant_field(const float* xyb, uint32_t xsize, uint32_t ys
   const size_t plane = size_t(xsize) * ysize;
   try {
     jxe::InitialQuantField(xyb, xyb + plane, xyb + 2 * plane, xsize, ysize, butteraugli_target, rescale, aq_map, mask);
+  } catch (...) {
+    return -2;
+  }
+  return 0;
+}
+
+// The CPU double of jxlhip_enc_masking_1x1 (include/jxl_amd_hip.h): the same arguments without the context.
+int jxlenc_cpu_masking_1x1(const float* xyb, uint32_t xsize, uint32_t ysize, float* out) {
+  jxe::UseThreads();
+  if (!xyb || !out || !xsize || !ysize || (xsize & 7) || (ysize & 7) || xsize > (1u << 18) || ysize > (1u << 18)) return -1;
+  try {
+    jxe::Masking1x1(xyb + size_t(xsize) * ysize, xsize, ysize, out);
   } catch (...) {
     return -2;
   }

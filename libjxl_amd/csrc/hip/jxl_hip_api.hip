@@ -267,6 +267,9 @@ struct JxlHipContext {
   jxlhip::EncFwd enc_last;     // the parameters of the last jxlhip_enc_forward (its input stays resident): jxlhip_enc_forward_rerun
   jxlhip::EncAq enc_last_aq;   // ... and of its adaptive quant field (quant_field_mode 1)
   Buf enc_aq_cells, enc_aq_map, enc_aq_mask, enc_aq_in;  // cell image, field, masking; the planes of jxlhip_enc_initial_quant_field
+  Buf enc_mask1x1;                                        // the per-pixel masking of jxlhip_enc_masking_1x1 (its Y plane goes through enc_aq_in)
+  hipEvent_t mask_ev[2] = {nullptr, nullptr};             // ... and its kernel's time
+  bool mask_timed = false;
   bool enc_last_gaborish = false;
   uint32_t out_orient = 0;  // jxlhip_set_output_orientation: PixelOut::orient bits (0 = the image as coded)
   bool out_unpremul = false;  // jxlhip_set_output_unpremultiply (PixelOut::orient bit 3 for outputs that carry alpha)
@@ -480,6 +483,7 @@ static JxlHipContext* RecycleContext(int device) {
   for (size_t i = 0; i < sizeof(c->ev) / sizeof(c->ev[0]); i++) std::swap(c->ev[i], o->ev[i]);
   for (size_t i = 0; i < sizeof(c->enc_ev) / sizeof(c->enc_ev[0]); i++) std::swap(c->enc_ev[i], o->enc_ev[i]);
   for (size_t i = 0; i < sizeof(c->ent_ev) / sizeof(c->ent_ev[0]); i++) std::swap(c->ent_ev[i], o->ent_ev[i]);
+  for (size_t i = 0; i < sizeof(c->mask_ev) / sizeof(c->mask_ev[0]); i++) std::swap(c->mask_ev[i], o->mask_ev[i]);
   std::swap(c->stage, o->stage);
   jxlhip_ctx_destroy(o);  // (what is left of it: lazily created events, a stream of its own)
   return c;
@@ -552,7 +556,7 @@ static std::vector<Buf*> AllBufs(JxlHipContext* c) {
                 &c->plane[2], &c->rgb, &c->tlist, &c->scratch, &c->ep_dev, &c->batch_params, &c->batch_map, &c->batch_lanes, &c->ups_kernel, &c->kend, &c->block_recs, &c->dequant_scan, &c->ec_stage, &c->alpha_patched, &c->trecs, &c->enc_tok_orders, &c->enc_tok_blk, &c->enc_tok_info,
                 &c->enc_tok_off, &c->enc_tok_nzmap, &c->enc_tok_small, &c->enc_tok_out, &c->enc_tok_base, &c->tb_params, &c->tb_desc, &c->fb_params, &c->alpha, &c->sec_end, &c->lz_window, &c->mod.pool, &c->mod.sections, &c->mod.blob, &c->mod.streams,
                 &c->mod.rects, &c->mod.status, &c->mod.end_bits, &c->mod.scratch, &c->mod.windows, &c->mod.batch_streams, &c->mod.batch_ops, &c->frame_blob, &c->noise, &c->spl_seg, &c->spl_row_start, &c->spl_row_seg, &c->spl_planes, &c->pat_rec, &c->pat_row_start, &c->pat_row_list,
-                &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in,
+                &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in, &c->enc_mask1x1,
                 &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
   for (auto& pb : c->pass_bufs)
     for (Buf* b : {&pb.ctx_map, &pb.alias, &pb.cfg, &pb.orders, &pb.ptable, &pb.poffset, &pb.alias_packed}) all.push_back(b);
@@ -582,6 +586,8 @@ void jxlhip_ctx_destroy(JxlHipContext* c) {
   for (auto& ev : c->enc_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : c->ent_ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : c->mask_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (c->stage.done) (void)hipEventDestroy(c->stage.done);
   if (c->stage.p) (void)hipHostFree(c->stage.p);
@@ -4456,6 +4462,42 @@ int jxlhip_enc_initial_quant_field(JxlHipContext* c, const float* xyb, uint32_t 
   HIP_TRY(hipMemcpyAsync(aq_map, A.aq, nb * 4, hipMemcpyDeviceToHost, c->stream));
   if (mask) HIP_TRY(hipMemcpyAsync(mask, A.mask, nb * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int jxlhip_enc_masking_1x1(JxlHipContext* c, const float* xyb, uint32_t xsize, uint32_t ysize, float* out) {
+  if (!c || !xyb || !out || !xsize || !ysize || (xsize & 7) || (ysize & 7) || xsize > (1u << 18) || ysize > (1u << 18))
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t plane = size_t(xsize) * ysize;
+  int r;
+  if ((r = c->enc_aq_in.Ensure(plane * 4)) || (r = c->enc_mask1x1.Ensure(plane * 4))) return r;
+  for (auto& ev : c->mask_ev)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  jxlhip::EncMask1x1 M;
+  M.y = c->enc_aq_in.as<float>();
+  M.out = c->enc_mask1x1.as<float>();
+  M.xp = xsize;
+  M.yp = ysize;
+  jxh::EncMask1x1Weights(M.w);
+  HIP_TRY(hipMemcpyAsync(c->enc_aq_in.p, xyb + plane, plane * 4, hipMemcpyHostToDevice, c->stream));  // (the Y plane is all it reads)
+  HIP_TRY(hipEventRecord(c->mask_ev[0], c->stream));
+  hipLaunchKernelGGL(jxlhip::k_enc_mask1x1, dim3((xsize + jxlhip::kMaskCols - 1) / jxlhip::kMaskCols, (ysize + jxlhip::kMaskRows - 1) / jxlhip::kMaskRows),
+                     dim3(256), 0, c->stream, M);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->mask_ev[1], c->stream));
+  c->mask_timed = true;
+  HIP_TRY(hipMemcpyAsync(out, M.out, plane * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int jxlhip_enc_masking_last_ms(JxlHipContext* c, float* ms) {
+  if (!c || !ms) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->mask_timed) return JXLHIP_ERR_NO_FRAME;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->mask_ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, c->mask_ev[0], c->mask_ev[1]));
   return 0;
 }
 

@@ -354,6 +354,70 @@ __global__ __launch_bounds__(64) void k_enc_aq_blocks(EncAq P) {
   }
 }
 
+// ---------------------------------------------------------------- per-pixel masking (mask1x1)
+// What the reference's AC-strategy search reads per pixel (enc_adaptive_quantization.cc ComputeTile :498-526, Blur1x1Masking
+// :634-662 with the border rule of convolve_symmetric5.cc:35-97), from the Y plane before the sharpening, as csrc/enc/jxl_enc.cc
+// Masking1x1 states it in float32: v = 1 / (log1p(|ratio<false>(Y + 0.019) (Y - base)|) + 0.01) with the Laplacian's
+// neighbours clamped to the plane, then the symmetric 5x5 blur of v with rows and columns outside the plane mirrored.
+// A workgroup owns kMaskCols x kMaskRows outputs: it forms v over them and two samples of halo either side in LDS (a halo
+// sample outside the plane is v at its mirror image, formed from Y like any other), then every lane blurs four rows of one
+// column out of a register window of 8 x 5 samples.
+struct EncMask1x1 {
+  const float* y;  // [yp][xp] the Y plane
+  float* out;      // [yp][xp]
+  uint32_t xp, yp;
+  float w[6];      // c, r, R, d, L, D of the blur: jxh::EncMask1x1Weights
+};
+constexpr int kMaskCols = 64, kMaskRows = 16;
+__global__ __launch_bounds__(256) void k_enc_mask1x1(EncMask1x1 P) {
+#pragma clang fp contract(off)
+  constexpr int W = kMaskCols + 4, H = kMaskRows + 4;
+  __shared__ float s[H][W];
+  const int xp = int(P.xp), yp = int(P.yp);
+  const int X0 = int(blockIdx.x) * kMaskCols, Y0 = int(blockIdx.y) * kMaskRows;
+  for (int i = threadIdx.x; i < W * H; i += 256) {
+    const int ly = i / W, lx = i - ly * W;
+    const int gx = X0 - 2 + lx, gy = Y0 - 2 + ly;  // -2 .. : at most two beyond either edge where an output reads it
+    float v = 0.0f;
+    if (gx <= xp + 1 && gy <= yp + 1) {  // (further out only the dead outputs of a partial tile would read)
+      // Mirror (image_ops.h:184-196); xp, yp >= 8, so one reflection brings -2 .. n + 1 inside
+      const int x = gx < 0 ? -gx - 1 : gx >= xp ? 2 * xp - 1 - gx : gx;
+      const int y = gy < 0 ? -gy - 1 : gy >= yp ? 2 * yp - 1 - gy : gy;
+      const float* row = P.y + size_t(y) * xp;
+      const float cur = row[x];
+      const float up = P.y[size_t(y ? y - 1 : y) * xp + x], down = P.y[size_t(y + 1 < yp ? y + 1 : y) * xp + x];
+      const float left = row[x ? x - 1 : x], right = row[x + 1 < xp ? x + 1 : x];
+      const float base = 0.25f * (down + up + left + right);
+      const float d = fabsf(EncGammaRatio<false>(cur + 0.019f) * (cur - base));
+      v = 1.0f / (log1pf(d) + 0.01f);
+    }
+    s[ly][lx] = v;
+  }
+  __syncthreads();
+  const int lx = threadIdx.x & 63, r0 = int(threadIdx.x >> 6) * 4;  // rows r0 .. r0 + 3 of column lx
+  float win[8][5];
+#pragma unroll
+  for (int j = 0; j < 8; j++)
+#pragma unroll
+    for (int k = 0; k < 5; k++) win[j][k] = s[r0 + j][lx + k];
+  const int gx = X0 + lx;
+  if (gx >= xp) return;
+  auto row_sum = [](const float (&r)[5], float w0, float w1, float w2) {
+    const float s2 = w2 * (r[0] + r[4]), s1 = w1 * (r[1] + r[3]), s0 = w0 * r[2];
+    return s2 + (s1 + s0);
+  };
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int gy = Y0 + r0 + j;
+    float sum0 = row_sum(win[j + 2], P.w[0], P.w[1], P.w[2]);
+    sum0 += row_sum(win[j], P.w[2], P.w[4], P.w[5]);
+    float sum1 = row_sum(win[j + 4], P.w[2], P.w[4], P.w[5]);
+    sum0 += row_sum(win[j + 1], P.w[1], P.w[3], P.w[4]);
+    sum1 += row_sum(win[j + 3], P.w[1], P.w[3], P.w[4]);
+    if (gy < yp) P.out[size_t(gy) * xp + gx] = sum0 + sum1;
+  }
+}
+
 // Transform selection and quant field of one 64x64 tile (8x8 blocks) per wave: every candidate is aligned to its own
 // size, so the greedy raster scan of the CPU writer never looks outside the tile it is in. The activity tests of every
 // (position, candidate) pair are evaluated by the lanes in parallel; only the occupancy bookkeeping of the scan is serial.

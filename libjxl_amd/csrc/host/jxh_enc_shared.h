@@ -36,6 +36,25 @@ inline void EncAqDistanceParams(float target, float rescale, A* a) {
   for (int i = 0; i < 4; i++) a->w[i] *= 0.29959705784054957f / norm_sum;
 }
 
+// The six distinct weights of the 5x5 blur of the per-pixel masking (Blur1x1Masking, enc_adaptive_quantization.cc:639-655,
+// with the member order of WeightsSymmetric5, convolve.h:30-40), the lower-right quadrant of the kernel being
+//   c r R
+//   r d L
+//   R L D
+// into w = {c, r, R, d, L, D}. The sum of the filter is float arithmetic up to the factor 4, double from the 1.0 on.
+inline void EncMask1x1Weights(float w[6]) {
+  const float k[5] = {0.364911248f, 0.05f, 0.1688888021f, 0.221069183f, 0.306563504f};
+  double sum = 1.0 + 4 * (k[0] + k[1] + k[2] + k[4] + 2 * k[3]);
+  if (sum < 1e-5) sum = 1e-5;
+  const float normalize = static_cast<float>(1.0 / sum);
+  w[0] = normalize;
+  w[1] = normalize * k[0];
+  w[2] = normalize * k[2];
+  w[3] = normalize * k[1];
+  w[4] = normalize * k[3];
+  w[5] = normalize * k[4];
+}
+
 // AdjustQuantField (enc_adaptive_quantization.cc:1207-1218) with the frame's own distance: how much of the largest field
 // value under a transform of four blocks or more is kept, the rest being the mean.
 inline float EncMeanMaxMixer(float distance) {
