@@ -904,20 +904,18 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
       for (uint32_t i = b0; i < b1; i++) {
         const JxlHipVarBlock& v = d->blocks[i];
         if (v.strategy >= 27 || v.qf == 0 || v.qf > 256 || v.quant_dc_ctx >= d->num_dc_ctxs) return JXLHIP_ERR_INVALID_ARGUMENT;
-        static const uint8_t cx[27] = {1, 1, 1, 1, 2, 4, 1, 2, 1, 4, 2, 4, 1, 1, 1, 1, 1, 1, 8, 4, 8, 16, 8, 16, 32, 16, 32};
-        static const uint8_t cy[27] = {1, 1, 1, 1, 2, 4, 2, 1, 4, 1, 4, 2, 1, 1, 1, 1, 1, 1, 8, 8, 4, 16, 16, 8, 32, 32, 16};
-        if (v.bx < gx0 || v.by < gy0 || v.bx + cx[v.strategy] > gx0 + 32 || v.by + cy[v.strategy] > gy0 + 32 ||
-            v.bx + cx[v.strategy] > d->xsize_blocks || v.by + cy[v.strategy] > d->ysize_blocks)
+        const uint32_t cx = jxlhip::kCoveredX[v.strategy], cy = jxlhip::kCoveredY[v.strategy];
+        if (v.bx < gx0 || v.by < gy0 || v.bx + cx > gx0 + 32 || v.by + cy > gy0 + 32 || v.bx + cx > d->xsize_blocks || v.by + cy > d->ysize_blocks)
           return JXLHIP_ERR_INVALID_ARGUMENT;
         if (v.coef_offset != off) return JXLHIP_ERR_INVALID_ARGUMENT;
-        if (cs && cx[v.strategy] * cy[v.strategy] != 1) return JXLHIP_ERR_INVALID_ARGUMENT;  // (dec_modular.cc:534-538)
+        if (cs && cx * cy != 1) return JXLHIP_ERR_INVALID_ARGUMENT;  // (dec_modular.cc:534-538)
         // (so a subsampled group's varblocks are its blocks in raster order: the entropy stage finds the block at a
         // channel's own column, whose quant field its block context takes, that many entries back in the row)
         if (cs) {
           const uint32_t gw = std::min<uint32_t>(32, d->xsize_blocks - gx0);
           if (v.bx != gx0 + (i - b0) % gw || v.by != gy0 + (i - b0) / gw) return JXLHIP_ERR_INVALID_ARGUMENT;
         }
-        off += 64u * cx[v.strategy] * cy[v.strategy];
+        off += 64u * cx * cy;
         if (off > 65536) return JXLHIP_ERR_INVALID_ARGUMENT;
       }
     }
@@ -1323,14 +1321,12 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   ep.coef_pass_stride = uint64_t(d->num_groups) * 3 * 65536;
   ep.kend_pass_stride = uint32_t(kend_per_pass);
   if (c->lane_multi) {  // k_merge_passes scatters through every pass's orders: validate them here
-    static const uint8_t kind_of[27] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
-    static const uint8_t bucket_of[27] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
     for (uint32_t p = 0; p < d->num_passes; p++)
       for (int st = 0; st < 27; st++) {
         if (!c->list_count[st]) continue;
-        const uint32_t size = d->dequant_size[kind_of[st]];
+        const uint32_t size = d->dequant_size[jxlhip::kStrategyQuantTable[st]];
         for (int ch = 0; ch < 3; ch++) {
-          const uint32_t oo = d->passes[p].order_offset[bucket_of[st] * 3 + ch];
+          const uint32_t oo = d->passes[p].order_offset[jxlhip::kStrategyOrder[st] * 3 + ch];
           if (size_t(oo) + size > d->passes[p].orders_size) return JXLHIP_ERR_INVALID_ARGUMENT;
           for (uint32_t k = 0; k < size; k++)
             if (d->passes[p].orders[oo + k] >= size) return JXLHIP_ERR_INVALID_ARGUMENT;
@@ -1342,30 +1338,23 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
     // table lookups: column in the group (5 bits) | not in the group's first row (1) | log2 covered_x (3) |
     // log2 covered_y (3) | block context of X, Y, B (4 bits each: ac_context.h:101-143 BlockCtxMap::Context, from the
     // strategy's order bucket, the quant-field bucket and the DC bucket).
-    static const uint8_t kOrderBucket[27] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
-    static const uint8_t kLog2Cx[27] = {0, 0, 0, 0, 1, 2, 0, 1, 0, 2, 1, 2, 0, 0, 0, 0, 0, 0, 3, 2, 3, 4, 3, 4, 5, 4, 5};
-    static const uint8_t kLog2Cy[27] = {0, 0, 0, 0, 1, 2, 1, 0, 2, 0, 2, 1, 0, 0, 0, 0, 0, 0, 3, 3, 2, 4, 4, 3, 5, 5, 4};
     std::vector<uint32_t> recs(size_t(d->num_blocks) + 16, 0);
     for (uint32_t i = 0; i < d->num_blocks; i++) {
       const JxlHipVarBlock& v = d->blocks[i];
-      uint32_t qfi = 0;
-      for (uint32_t t = 0; t < d->num_qf_thresholds; t++) qfi += v.qf > d->qf_thresholds[t];
-      uint32_t rec = (v.bx & 31u) | ((v.by & 31u) ? 32u : 0u) | uint32_t(kLog2Cx[v.strategy]) << 6 | uint32_t(kLog2Cy[v.strategy]) << 9;
+      const uint32_t qfi = jxlhip::QfBucket(v.qf, ep.qf_thr, ep.nq);
+      const uint32_t fbx = v.bx & 31u, fby = v.by & 31u;
+      uint32_t rec = fbx | (fby ? 32u : 0u) | jxlhip::Log2CoveredX(v.strategy) << 6 | jxlhip::Log2CoveredY(v.strategy) << 9;
       for (uint32_t ch = 0; ch < 3; ch++) {
         // (chroma-subsampled frames: bit 24 + channel = the block is off the channel's grid and carries nothing for it,
         // bit 27 + channel = the channel's columns are half the frame's)
-        const uint32_t hs = (cs >> (2 * ch)) & 1u, vs = (cs >> (2 * ch + 1)) & 1u;
-        // the quant field at the channel's own column (dec_group.cc:492, 583-588: qf_row[sbx]); a subsampled group's
-        // varblocks are its blocks in raster order (validated above), so that block is fbx - (fbx >> hs) entries back
-        uint32_t qfc = qfi;
-        if (hs) {
-          const uint32_t fbx = v.bx & 31u;
-          qfc = 0;
-          for (uint32_t t = 0; t < d->num_qf_thresholds; t++) qfc += d->blocks[i - (fbx - (fbx >> 1))].qf > d->qf_thresholds[t];
-        }
-        const uint32_t bctx = d->block_ctx_lut[((ch * 13 + kOrderBucket[v.strategy]) * ep.nq + qfc) * ep.ndc + v.quant_dc_ctx];
+        const uint32_t hs = jxlhip::ChannelHShift(cs, ch);
+        uint32_t lbx, lby;
+        const bool carried = jxlhip::ChannelCell(cs, ch, fbx, fby, lbx, lby);
+        // (the quant field at the channel's own column: a subsampled group's varblocks are its blocks in raster order, validated above)
+        const uint32_t qfc = hs ? jxlhip::QfBucket(d->blocks[i - jxlhip::QfColumnBack(fbx, lbx)].qf, ep.qf_thr, ep.nq) : qfi;
+        const uint32_t bctx = d->block_ctx_lut[jxlhip::BctxLutIndex(ch, jxlhip::kStrategyOrder[v.strategy], ep.nq, qfc, ep.ndc, v.quant_dc_ctx)];
         rec |= (bctx & 15u) << (12 + 4 * ch);
-        if ((v.bx & hs) | (v.by & vs)) rec |= 1u << (24 + ch);
+        if (!carried) rec |= 1u << (24 + ch);
         rec |= hs << (27 + ch);
       }
       recs[i] = rec;
@@ -1397,11 +1386,9 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   memcpy(tp.dq_offset, d->dequant_offset, sizeof(tp.dq_offset));
   memcpy(tp.dq_size, d->dequant_size, sizeof(tp.dq_size));
   for (int s = 0; s < 27; s++) {
-    static const uint8_t qt[27] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
-    static const uint16_t areas[27] = {1, 1, 1, 1, 4, 16, 2, 2, 4, 4, 8, 8, 1, 1, 1, 1, 1, 1, 64, 32, 32, 256, 128, 128, 1024, 512, 512};
     if (c->list_count[s] == 0) continue;
-    const uint32_t k = qt[s];
-    if (d->dequant_size[k] != 64u * areas[s] || size_t(d->dequant_offset[k]) + 3 * size_t(d->dequant_size[k]) > d->dequant_floats)
+    const uint32_t k = jxlhip::kStrategyQuantTable[s];
+    if (d->dequant_size[k] != 64u * jxlhip::CoveredBlocks(s) || size_t(d->dequant_offset[k]) + 3 * size_t(d->dequant_size[k]) > d->dequant_floats)
       return JXLHIP_ERR_INVALID_ARGUMENT;
   }
   tp.dense = c->transform_dense ? 1 : 0;
@@ -1432,14 +1419,12 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   tp.dequant_scan = nullptr;
   if (c->scan_order) {
     // dequant tables in scan order for the kinds in use
-    static const uint8_t kind_of[27] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
-    static const uint8_t bucket_of[27] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
     std::vector<float> scan(d->dequant_floats, 0.0f);
     for (int st = 0; st < 27; st++) {
       if (!c->list_count[st]) continue;
-      const uint32_t kind = kind_of[st], size = d->dequant_size[kind];
+      const uint32_t kind = jxlhip::kStrategyQuantTable[st], size = d->dequant_size[kind];
       for (int ch = 0; ch < 3; ch++) {
-        const uint32_t oo = d->passes[0].order_offset[bucket_of[st] * 3 + ch];
+        const uint32_t oo = d->passes[0].order_offset[jxlhip::kStrategyOrder[st] * 3 + ch];
         if (size_t(oo) + size > d->passes[0].orders_size) return JXLHIP_ERR_INVALID_ARGUMENT;
         const uint16_t* order = d->passes[0].orders + oo;
         const float* m = d->dequant + d->dequant_offset[kind] + size_t(ch) * size;
@@ -1543,10 +1528,9 @@ static int RunEntropySingle(JxlHipContext* c) {
 // ---- transform + filter launches, batched over the frames of a set ---------------------------------------------------
 // Varblocks a workgroup of the strategy's kernel handles.
 static uint32_t BlocksPerWG(int s) {
-  static const uint8_t cx[27] = {1, 1, 1, 1, 2, 4, 1, 2, 1, 4, 2, 4, 1, 1, 1, 1, 1, 1, 8, 4, 8, 16, 8, 16, 32, 16, 32};
-  static const uint8_t cy[27] = {1, 1, 1, 1, 2, 4, 2, 1, 4, 1, 4, 2, 1, 1, 1, 1, 1, 1, 8, 8, 4, 16, 16, 8, 32, 32, 16};
+  const uint32_t cx = jxlhip::kCoveredX[s], cy = jxlhip::kCoveredY[s];
   if (s == 0 || (s >= 4 && s <= 11) || (s >= 18 && s <= 20))  // k_idct_fast: max(rows, columns) threads per varblock
-    return jxlhip::IdctFastThreads(cx[s], cy[s]) / ((cx[s] > cy[s] ? cx[s] : cy[s]) * 8);
+    return jxlhip::IdctFastThreads(cx, cy) / ((cx > cy ? cx : cy) * 8);
   return 4;  // k_special
 }
 
@@ -3747,17 +3731,15 @@ int jxlhip_download(JxlHipContext* c, const char* name, void* dst, size_t dst_si
     // the device holds scan-order entries [covered, kend) per (block, channel): present them in the natural layout
     std::vector<uint32_t> kend(c->blocks_host.size() * 3);
     HIP_TRY(hipMemcpy(kend.data(), c->kend.p, kend.size() * 4, hipMemcpyDeviceToHost));
-    static const uint8_t log2c[27] = {0, 0, 0, 0, 2, 4, 1, 1, 2, 2, 3, 3, 0, 0, 0, 0, 0, 0, 6, 5, 5, 8, 7, 7, 10, 9, 9};
-    static const uint8_t bucket[27] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
     const size_t esz = c->coef_bits / 8;
     std::vector<uint8_t> tmp(65536 * esz);
     for (uint32_t g = 0; g < c->ng; g++)
       for (uint32_t b = c->gbb_host[g]; b < c->gbb_host[g + 1]; b++) {
         const JxlHipVarBlock& v = c->blocks_host[b];
-        const uint32_t covered = 1u << log2c[v.strategy], size = covered * 64;
+        const uint32_t covered = jxlhip::CoveredBlocks(v.strategy), size = covered * 64;
         for (int ch = 0; ch < 3; ch++) {
           uint8_t* base = static_cast<uint8_t*>(dst) + ((size_t(g) * 3 + ch) * 65536 + v.coef_offset) * esz;
-          const uint16_t* order = c->orders_host.data() + c->order_offset_host[bucket[v.strategy] * 3 + ch];
+          const uint16_t* order = c->orders_host.data() + c->order_offset_host[jxlhip::kStrategyOrder[v.strategy] * 3 + ch];
           uint32_t ke = kend[size_t(b) * 3 + ch];
           ke = ke > size ? size : ke;
           memcpy(tmp.data(), base, size * esz);

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../../include/jxl_amd_hip.h"
+#include "jxl_hip_block_ctx.h"
 
 namespace jxlhip {
 
@@ -109,10 +110,7 @@ __global__ __launch_bounds__(256) void k_epf_sigma(SigmaParams P) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P.num_blocks) return;
   const JxlHipVarBlock v = P.blocks[i];
-  // blocks covered per strategy (ac_strategy.h:130-167; the same table jxlhip_frame_upload validates the varblocks with)
-  const uint8_t kCx[27] = {1, 1, 1, 1, 2, 4, 1, 2, 1, 4, 2, 4, 1, 1, 1, 1, 1, 1, 8, 4, 8, 16, 8, 16, 32, 16, 32};
-  const uint8_t kCy[27] = {1, 1, 1, 1, 2, 4, 2, 1, 4, 1, 4, 2, 1, 1, 1, 1, 1, 1, 8, 8, 4, 16, 16, 8, 32, 32, 16};
-  const uint32_t st = v.strategy < 27 ? v.strategy : 0, cx = kCx[st], cy = kCy[st];
+  const uint32_t st = v.strategy < 27 ? v.strategy : 0, cx = kCoveredX[st], cy = kCoveredY[st];  // (the constant objects, as the local tables here were: the compiler knows no entry is 0)
   const float kInvSigmaNum = -1.1715728752538099024f;
   const float sigma_quant = P.epf_quant_mul / (P.quant_scale * float(v.qf) * kInvSigmaNum);
   for (uint32_t iy = 0; iy < cy; iy++)

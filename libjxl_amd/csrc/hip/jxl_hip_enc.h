@@ -1033,17 +1033,12 @@ __global__ __launch_bounds__(kTokThreads) void k_enc_tok_emit(EncTok P) {
       // entropy_coder.h:25-35 PredictFromTopAndLeft over the map of counts (every cell read here belongs to a varblock
       // that comes earlier in raster order), ac_context.h:131-143 NonZeroContext
       const uint8_t* m = P.nzmap + (size_t(g) * 3 + c) * 1024;
-      uint32_t pred;
-      if (lbx == 0) pred = lby ? m[(lby - 1) * 32] : 32u;
-      else if (lby == 0) pred = m[lbx - 1];
-      else pred = (uint32_t(m[(lby - 1) * 32 + lbx]) + m[lby * 32 + lbx - 1] + 1) >> 1;
-      uint32_t nzb = pred >= 64 ? 64 : pred;
-      nzb = nzb < 8 ? nzb : 4 + nzb / 2;
-      out[o] = make_uint2(hist_off + nzb * P.num_ctxs + bc, nz);
+      const uint32_t pred = PredictNonZeros([m](uint32_t i) { return uint32_t(m[i]); }, lbx, lby);
+      out[o] = make_uint2(hist_off + NonZeroBucket(pred) * P.num_ctxs + bc, nz);
     }
     if (!nz) continue;
     // ac_context.h:63-83 ZeroDensityContext for scan positions covered .. last - 1: non-zeros left = count - non-zeros before k
-    const uint32_t hoff = hist_off + P.num_ctxs * 37 + 458 * bc;
+    const uint32_t hoff = hist_off + ZeroDensityBase(P.num_ctxs, bc);
     uint32_t before = 0;                            // non-zeros at scan positions [covered, k0)
     uint32_t carry = nz > size / 16 ? 0u : 1u;      // "previous coefficient was non-zero" for the chunk's first lane
     for (uint32_t k0 = covered & ~63u; k0 < last; k0 += 64) {
@@ -1055,7 +1050,7 @@ __global__ __launch_bounds__(kTokThreads) void k_enc_tok_emit(EncTok P) {
         const uint32_t left = nz - before - uint32_t(__popcll(mz & ((1ull << lane) - 1)));
         const uint32_t prev = (lane == 0 || k == covered) ? carry : uint32_t((mz >> (lane - 1)) & 1);
         const uint32_t nzl = (left + covered - 1) >> log2c;
-        const uint32_t ctx = hoff + (uint32_t(c_coeff_nnz_ctx[nzl & 63]) + c_coeff_freq_ctx[(k >> log2c) & 63]) * 2 + prev;
+        const uint32_t ctx = ZeroDensityContext(hoff, c_coeff_nnz_ctx[nzl & 63], c_coeff_freq_ctx[(k >> log2c) & 63], prev);
         const uint32_t val = v >= 0 ? uint32_t(v) * 2 : uint32_t(-(v + 1)) * 2 + 1;
         out[o + 1 + (k - covered)] = make_uint2(ctx, val);
       }

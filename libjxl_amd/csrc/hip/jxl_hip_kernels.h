@@ -2,8 +2,9 @@
 // launches it is in jxl_hip_api.hip. No CPU implementation of these stages exists in the product.
 //
 // Kernels and the reference code they replace:
-//   k_entropy_lanes (jxl_hip_entropy_lanes.h), k_entropy_uni, k_entropy_ans
-//                   lib/jxl/dec_group.cc:469-542,594-639 + dec_ans.h:170-257 + ans_common.h:102-142
+//   k_entropy_lanes (jxl_hip_entropy_lanes.h), k_entropy_uni, k_entropy_ans / k_entropy_generic (one walk: WalkSection)
+//                   lib/jxl/dec_group.cc:469-542,594-639 + dec_ans.h:170-257 + ans_common.h:102-142; the block-context
+//                   rules and the per-strategy tables are stated once, in jxl_hip_block_ctx.h
 //   k_idct_fast<CX,CY>
 //                   lib/jxl/dec_group.cc:115-181 (dequant, CfL), dec_transforms-inl.h:691-818 (LLF from DC),
 //                   dct-inl.h:191-232,376-397 (scaled IDCT, recursive even / odd form)
@@ -21,15 +22,12 @@
 #include <stdint.h>
 
 #include "../../../include/jxl_amd_hip.h"
+#include "jxl_hip_block_ctx.h"
 
 namespace jxlhip {
 
 // ---------------------------------------------------------------------------------------------- constants
-__constant__ uint8_t c_covered_x[27] = {1, 1, 1, 1, 2, 4, 1, 2, 1, 4, 2, 4, 1, 1, 1, 1, 1, 1, 8, 4, 8, 16, 8, 16, 32, 16, 32};
-__constant__ uint8_t c_covered_y[27] = {1, 1, 1, 1, 2, 4, 2, 1, 4, 1, 4, 2, 1, 1, 1, 1, 1, 1, 8, 8, 4, 16, 16, 8, 32, 32, 16};
-__constant__ uint8_t c_log2_covered[27] = {0, 0, 0, 0, 2, 4, 1, 1, 2, 2, 3, 3, 0, 0, 0, 0, 0, 0, 6, 5, 5, 8, 7, 7, 10, 9, 9};
-__constant__ uint8_t c_strategy_order[27] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
-__constant__ uint8_t c_strategy_qtable[27] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
+// (c_covered_x, c_covered_y, c_log2_covered, c_strategy_order, c_strategy_qtable, c_strategy_info: jxl_hip_block_ctx.h)
 __constant__ uint16_t c_coeff_freq_ctx[64] = {
     0,  0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 15, 16, 16, 17, 17,
     18, 18, 19, 19, 20, 20, 21, 21, 22, 22, 23, 23, 23, 23, 24, 24, 24, 24, 25, 25, 25, 25,
@@ -137,6 +135,7 @@ __device__ __forceinline__ uint32_t ReadHybrid(BitReader& br, uint32_t& state, u
   const uint32_t i = res >> log_entry;
   const uint32_t pos = res & ((1u << log_entry) - 1);
   const uint2 e = alias[(cluster << log_alpha) + i];
+  const uint32_t c = cfg[cluster];  // (issued beside the alias entry: both are global reads, one latency on the serial chain)
   const uint32_t cutoff = e.x & 0xFF, right = (e.x >> 8) & 0xFF, freq0 = e.x >> 16;
   const uint32_t offsets1 = e.y & 0xFFFF, freq1 = e.y >> 16;
   const bool greater = pos >= cutoff;
@@ -146,7 +145,6 @@ __device__ __forceinline__ uint32_t ReadHybrid(BitReader& br, uint32_t& state, u
   state = freq * (state >> 12) + off;
   BrRefill(br);
   if (state < (1u << 16)) state = (state << 16) | BrRead(br, 16);
-  const uint32_t c = cfg[cluster];
   const uint32_t split_exp = c & 0xFF, msb = (c >> 8) & 0xFF, lsb = (c >> 16) & 0xFF;
   const uint32_t split_token = 1u << split_exp;
   if (token < split_token) return token;
@@ -159,157 +157,9 @@ __device__ __forceinline__ uint32_t ReadHybrid(BitReader& br, uint32_t& state, u
   return (((((1u << msb) | (hi & ((1u << msb) - 1))) << nbits) | bits) << lsb) | low;
 }
 
-// One 64-lane workgroup per 256x256 group, for alias tables beyond the LDS budget (read in place from global memory). All
-// lanes zero the group's coefficient planes and stage the context map in LDS; lane 0 then walks the (inherently serial)
-// adaptive-context rANS stream.
-template <typename CoefT>
-__global__ __launch_bounds__(64) void k_entropy_ans(EntropyParams P) {
-  extern __shared__ __align__(16) uint8_t lds_raw[];
-  const uint32_t g = blockIdx.x;
-  const uint32_t lane = threadIdx.x;
-  uint8_t* l_ctx = lds_raw;
-  uint8_t* l_nz = lds_raw + P.lds_ctx_bytes + P.lds_alias_bytes;  // 3 * 1024
-  const uint32_t b0 = P.gbb[g], b1 = P.gbb[g + 1];
-  CoefT* gco = static_cast<CoefT*>(P.coeffs) + size_t(g) * 3 * 65536;
-  // total coefficients per channel in this group
-  uint32_t total = 0;
-  if (b1 > b0) {
-    const JxlHipVarBlock last = P.blocks[b1 - 1];
-    total = last.coef_offset + (64u << c_log2_covered[last.strategy]);
-  }
-  for (uint32_t pass = 0; pass < P.num_passes; pass++) {
-    const PassDev& T = P.passes[pass];
-    const uint32_t sec = pass * P.num_groups + g;
-    if (pass && P.sec_size[sec] == 0) break;  // (a frame drawn from a prefix of its bytes: this pass of the group has not arrived)
-    __syncthreads();
-    if (pass == 0) {
-      // zero fill (16-byte stores)
-      const uint32_t n16 = (total * uint32_t(sizeof(CoefT))) / 16;
-      for (int c = 0; c < 3; c++) {
-        uint4* dst = reinterpret_cast<uint4*>(gco + size_t(c) * 65536);
-        for (uint32_t i = lane; i < n16; i += 64) dst[i] = make_uint4(0, 0, 0, 0);
-      }
-      if (P.sec_size[sec] == 0) break;  // (none of the group's passes has arrived: the DC image alone)
-    }
-    for (uint32_t i = lane; i < 3 * 1024; i += 64) l_nz[i] = 0;
-    // histogram selector is read by lane 0 first; all lanes then stage that slice of the context map
-    __shared__ uint32_t s_sel, s_state;
-    __shared__ BitReader s_br;
-    if (lane == 0) {
-      BitReader br;
-      br.p = P.sections + P.sec_word[sec];
-      br.nwords = (P.sec_size[sec] + 3) / 4;
-      br.idx = 0;
-      br.buf = 0;
-      br.bits = 0;
-      BrRefill(br);
-      if (sec == 0 && P.first_bit_offset) BrRead(br, P.first_bit_offset);
-      uint32_t hb = 0;
-      while ((1u << hb) < P.num_hist) hb++;
-      BrRefill(br);
-      uint32_t sel = hb ? BrRead(br, hb) : 0;
-      if (sel >= P.num_hist) {
-        atomicOr(&P.errors[g], kErrSelector);
-        sel = 0;
-      }
-      BrRefill(br);
-      uint32_t st = BrRead(br, 16);
-      BrRefill(br);
-      st |= BrRead(br, 16) << 16;
-      s_sel = sel;
-      s_state = st;
-      s_br = br;
-    }
-    __syncthreads();
-    {
-      const uint8_t* src = T.ctx_map + size_t(s_sel) * P.nctx;
-      for (uint32_t i = lane; i < P.nctx + 16; i += 64) l_ctx[i] = src[i];
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (lane != 0) continue;
-
-    BitReader br = s_br;
-    uint32_t state = s_state;
-    const uint32_t log_alpha = T.log_alpha;
-    const uint32_t shift = T.shift;
-    uint32_t err = 0;
-    for (uint32_t bi = b0; bi < b1 && !err; bi++) {
-      const JxlHipVarBlock vb = P.blocks[bi];
-      const uint32_t st = vb.strategy;
-      const uint32_t cx = c_covered_x[st], cy = c_covered_y[st], log2c = c_log2_covered[st];
-      const uint32_t covered = 1u << log2c, size = covered * 64;
-      const uint32_t ord = c_strategy_order[st];
-      uint32_t qfi = 0;
-      for (uint32_t t = 0; t + 1 < P.nq; t++) qfi += vb.qf > P.qf_thr[t];
-      const uint32_t fbx = vb.bx & 31, fby = vb.by & 31;
-#pragma unroll 1
-      for (int ci = 0; ci < 3 && !err; ci++) {
-        const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
-        // (a subsampled channel, EntropyParams::cs: only the blocks on its own grid carry it, and its counts live there)
-        const uint32_t hs = (P.cs >> (2 * c)) & 1u, vs = (P.cs >> (2 * c + 1)) & 1u;
-        if ((fbx & hs) | (fby & vs)) continue;
-        const uint32_t lbx = fbx >> hs, lby = fby >> vs;
-        uint8_t* nzc = l_nz + c * 1024;
-        uint32_t pred;
-        if (lbx == 0) pred = lby ? nzc[(lby - 1) * 32] : 32;
-        else if (lby == 0) pred = nzc[lbx - 1];
-        else pred = (uint32_t(nzc[(lby - 1) * 32 + lbx]) + nzc[lby * 32 + lbx - 1] + 1) >> 1;
-        // The quant field of the block context is read at the channel's own column of the frame's row (dec_group.cc:492,
-        // 583-588: qf_row[sbx]). A subsampled frame has one block per varblock in raster order (jxlhip_frame_upload checks
-        // it), so that block is fbx - lbx entries back in this row.
-        uint32_t qfc = qfi;
-        if (P.cs != 0 && hs) {
-          const uint32_t q = P.blocks[bi - (fbx - lbx)].qf;
-          qfc = 0;
-          for (uint32_t t = 0; t + 1 < P.nq; t++) qfc += q > P.qf_thr[t];
-        }
-        const uint32_t bctx = P.bctx_lut[((c * 13 + ord) * P.nq + qfc) * P.ndc + vb.quant_dc_ctx];
-        uint32_t nzb = pred >= 64 ? 64 : pred;
-        nzb = nzb < 8 ? nzb : 4 + nzb / 2;
-        uint32_t nzeros = ReadHybrid(br, state, l_ctx[nzb * P.num_bctx + bctx], T.alias, T.cfg, log_alpha);
-        if (nzeros > size - covered) {
-          err = kErrNzeros;
-          break;
-        }
-        const uint8_t nzv = uint8_t((nzeros + covered - 1) >> log2c);
-        for (uint32_t y = 0; y < cy; y++)
-          for (uint32_t x = 0; x < cx; x++) nzc[(lby + y) * 32 + lbx + x] = nzv;
-        const uint32_t hoff = P.num_bctx * 37 + 458 * bctx;
-        const uint16_t* order = T.orders + T.order_offset[ord * 3 + c];
-        CoefT* dst = gco + size_t(c) * 65536 + vb.coef_offset;
-        uint32_t prev = nzeros > size / 16 ? 0 : 1;
-        for (uint32_t k = covered; k < size && nzeros != 0; ++k) {
-          const uint32_t nzl = (nzeros + covered - 1) >> log2c;
-          const uint32_t ctx = hoff + (uint32_t(c_coeff_nnz_ctx[nzl & 63]) + c_coeff_freq_ctx[(k >> log2c) & 63]) * 2 + prev;
-          const uint32_t u = ReadHybrid(br, state, l_ctx[ctx], T.alias, T.cfg, log_alpha);
-          const uint32_t mag = u >> 1, neg = (~u) & 1;
-          const int32_t coeff = int32_t((mag ^ (neg - 1)) << shift);
-          if (u) {
-            const uint32_t pos = order[k];
-            if (pass == 0) dst[pos] = CoefT(coeff);
-            else dst[pos] = CoefT(dst[pos] + coeff);
-          }
-          prev = u != 0;
-          nzeros -= prev;
-        }
-        if (nzeros != 0) err = kErrNzeros;
-      }
-    }
-    if (!err && state != (0x13u << 16)) err |= kErrFinalState;
-    {
-      const uint64_t consumed = uint64_t(br.idx) * 32 - uint64_t(br.bits);
-      if (consumed > uint64_t(P.sec_size[sec]) * 8) err |= kErrOverread;
-      P.sec_end_bits[sec] = uint32_t(consumed);
-    }
-    if (err) atomicOr(&P.errors[g], err);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- entropy, every code
-// The streams libjxl's fastest and slowest efforts write: prefix codes instead of rANS (dec_huffman.h:28-41, dec_ans.h:
-// 170-197) and / or LZ77 copies of earlier values (dec_ans.h:288-353). Same walk as k_entropy_ans, tables in global
-// memory, one lane per section: the correctness path for these streams, not a tuned one.
+// The symbol reader for the streams libjxl's fastest and slowest efforts write: prefix codes instead of rANS
+// (dec_huffman.h:28-41, dec_ans.h:170-197) and / or LZ77 copies of earlier values (dec_ans.h:288-353).
 // Prefix-code lookup in the two-level tables the host builds (jxh_entropy.h AppendPrefixTables): `tab` = the cluster's
 // root, `root_bits` its index width, `bits` = the next >= 15 bits of the stream. Returns symbol << 8 | code length.
 __device__ __forceinline__ uint32_t PrefixLookup(const uint32_t* tab, uint32_t root_bits, uint32_t bits) {
@@ -387,6 +237,166 @@ __device__ __forceinline__ uint32_t GenericRead(GenericReader& r, uint32_t clust
   return v;
 }
 
+// ---------------------------------------------------------------------------------------------- entropy, one section per workgroup
+// k_entropy_ans and k_entropy_generic: one 64-lane workgroup per 256x256 group; all lanes zero the group's coefficient
+// planes, lane 0 then walks the (inherently serial) adaptive-context stream of each pass through WalkSection, the one
+// statement of dec_group.cc:470-639 for these two kernels. They differ in the symbol reader and in what it needs:
+//   k_entropy_ans      rANS with alias tables beyond the LDS budget (read in place from global memory), the selected slice of
+//                      the context map staged in LDS by all lanes
+//   k_entropy_generic  every code: prefix codes and / or LZ77 (its window in global memory), tables and context map in global
+//                      memory; the correctness path for these streams, not a tuned one
+struct AnsReader {
+  BitReader br;
+  uint32_t state, err;
+  const uint2* alias;
+  const uint32_t* cfg;
+  uint32_t log_alpha;
+};
+__device__ __forceinline__ uint32_t ReadSymbol(AnsReader& r, uint32_t cluster) { return ReadHybrid(r.br, r.state, cluster, r.alias, r.cfg, r.log_alpha); }
+__device__ __forceinline__ uint32_t ReadSymbol(GenericReader& r, uint32_t cluster) { return GenericRead(r, cluster); }
+
+// All 64 lanes zero the used part of the three planes of the group [b0, b1) of varblocks (16-byte stores).
+template <typename CoefT>
+__device__ __forceinline__ void ZeroGroup(const EntropyParams& P, uint32_t b0, uint32_t b1, CoefT* gco, uint32_t lane) {
+  if (b1 <= b0) return;
+  const JxlHipVarBlock last = P.blocks[b1 - 1];
+  const uint32_t total = last.coef_offset + (64u << c_log2_covered[last.strategy]);  // coefficients per channel
+  const uint32_t n16 = (total * uint32_t(sizeof(CoefT))) / 16;
+  for (int c = 0; c < 3; c++) {
+    uint4* dst = reinterpret_cast<uint4*>(gco + size_t(c) * 65536);
+    for (uint32_t i = lane; i < n16; i += 64) dst[i] = make_uint4(0, 0, 0, 0);
+  }
+}
+
+// Opens section `sec` (dec_group.cc:707-724): the frame's first_bit_offset, the histogram selector (kErrSelector into `err`
+// and set 0 when it names no set), and the coder's 32-bit start state where the stream is an ANS one (dec_ans.cc:402;
+// otherwise the state every stream ends in). Returns the selector.
+__device__ __forceinline__ uint32_t OpenSection(const EntropyParams& P, uint32_t sec, bool ans_state, BitReader& br, uint32_t& state, uint32_t& err) {
+  br.p = P.sections + P.sec_word[sec];
+  br.nwords = (P.sec_size[sec] + 3) / 4;
+  br.idx = 0;
+  br.buf = 0;
+  br.bits = 0;
+  BrRefill(br);
+  if (sec == 0 && P.first_bit_offset) BrRead(br, P.first_bit_offset);
+  const uint32_t hb = SelectorBits(P.num_hist);
+  BrRefill(br);
+  uint32_t sel = hb ? BrRead(br, hb) : 0;
+  if (sel >= P.num_hist) {
+    err |= kErrSelector;
+    sel = 0;
+  }
+  state = 0x13u << 16;
+  if (ans_state) {
+    BrRefill(br);
+    state = BrRead(br, 16);
+    BrRefill(br);
+    state |= BrRead(br, 16) << 16;
+  }
+  return sel;
+}
+
+// One lane walks pass `pass` of group g, varblocks [b0, b1): per block and channel (Y, X, B) the count of non-zeros under
+// the NonZeroContext of its prediction, then the coefficients in the pass's order under their ZeroDensityContext, pass 0
+// storing into the zeroed group and later passes adding; then the checks of dec_group.cc:724-731 (final state, bits read)
+// and the section's end bit. `rd` is opened (OpenSection), `ctx_map` the selected histogram set's slice (LDS or global),
+// `l_nz` the cleared 3 x 32 x 32 map of counts.
+template <typename CoefT, typename Reader>
+__device__ __forceinline__ void WalkSection(const EntropyParams& P, const PassDev& T, Reader& rd, const uint8_t* ctx_map, uint8_t* l_nz, CoefT* gco,
+                                            uint32_t g, uint32_t pass, uint32_t b0, uint32_t b1) {
+  const uint32_t sec = pass * P.num_groups + g;
+  const uint32_t shift = T.shift;
+  for (uint32_t bi = b0; bi < b1 && !rd.err; bi++) {
+    const JxlHipVarBlock vb = P.blocks[bi];
+    const uint32_t st = vb.strategy;
+    const uint32_t cx = c_covered_x[st], cy = c_covered_y[st], log2c = c_log2_covered[st];
+    const uint32_t covered = 1u << log2c, size = covered * 64;
+    const uint32_t ord = c_strategy_order[st];
+    const uint32_t qfi = QfBucket(vb.qf, P.qf_thr, P.nq);
+    const uint32_t fbx = vb.bx & 31, fby = vb.by & 31;
+#pragma unroll 1
+    for (int ci = 0; ci < 3 && !rd.err; ci++) {
+      const uint32_t c = ci == 0 ? 1u : (ci == 1 ? 0u : 2u);
+      uint32_t lbx, lby;
+      if (!ChannelCell(P.cs, c, fbx, fby, lbx, lby)) continue;
+      uint8_t* nzc = l_nz + c * 1024;
+      const uint32_t pred = PredictNonZeros([nzc](uint32_t i) { return uint32_t(nzc[i]); }, lbx, lby);
+      const uint32_t qfc = ChannelHShift(P.cs, c) ? QfBucket(P.blocks[bi - QfColumnBack(fbx, lbx)].qf, P.qf_thr, P.nq) : qfi;
+      const uint32_t bctx = P.bctx_lut[BctxLutIndex(c, ord, P.nq, qfc, P.ndc, vb.quant_dc_ctx)];
+      uint32_t nzeros = ReadSymbol(rd, ctx_map[NonZeroBucket(pred) * P.num_bctx + bctx]);
+      if (nzeros > size - covered) {
+        rd.err |= kErrNzeros;
+        break;
+      }
+      const uint8_t nzv = uint8_t(NonZerosPerBlock(nzeros, covered, log2c));
+      for (uint32_t y = 0; y < cy; y++)
+        for (uint32_t x = 0; x < cx; x++) nzc[(lby + y) * 32 + lbx + x] = nzv;
+      const uint32_t hoff = ZeroDensityBase(P.num_bctx, bctx);
+      const uint16_t* order = T.orders + T.order_offset[ord * 3 + c];
+      CoefT* dst = gco + size_t(c) * 65536 + vb.coef_offset;
+      uint32_t prev = nzeros > size / 16 ? 0 : 1;
+      for (uint32_t k = covered; k < size && nzeros != 0 && !rd.err; ++k) {
+        const uint32_t nzl = NonZerosPerBlock(nzeros, covered, log2c);
+        const uint32_t u = ReadSymbol(rd, ctx_map[ZeroDensityContext(hoff, c_coeff_nnz_ctx[nzl & 63], c_coeff_freq_ctx[(k >> log2c) & 63], prev)]);
+        if (u) {
+          const int32_t coeff = int32_t(TokenValue(u, shift));
+          const uint32_t pos = order[k];
+          if (pass == 0) dst[pos] = CoefT(coeff);
+          else dst[pos] = CoefT(dst[pos] + coeff);
+        }
+        prev = u != 0;
+        nzeros -= prev;
+      }
+      if (nzeros != 0) rd.err |= kErrNzeros;
+    }
+  }
+  uint32_t err = rd.err;
+  if (!err && rd.state != (0x13u << 16)) err |= kErrFinalState;
+  const uint64_t consumed = uint64_t(rd.br.idx) * 32 - uint64_t(rd.br.bits);
+  if (consumed > uint64_t(P.sec_size[sec]) * 8) err |= kErrOverread;
+  P.sec_end_bits[sec] = uint32_t(consumed);
+  if (err) atomicOr(&P.errors[g], err);
+}
+
+template <typename CoefT>
+__global__ __launch_bounds__(64) void k_entropy_ans(EntropyParams P) {
+  extern __shared__ __align__(16) uint8_t lds_raw[];
+  const uint32_t g = blockIdx.x, lane = threadIdx.x;
+  uint8_t* l_ctx = lds_raw;
+  uint8_t* l_nz = lds_raw + P.lds_ctx_bytes + P.lds_alias_bytes;  // 3 * 1024
+  const uint32_t b0 = P.gbb[g], b1 = P.gbb[g + 1];
+  CoefT* gco = static_cast<CoefT*>(P.coeffs) + size_t(g) * 3 * 65536;
+  ZeroGroup(P, b0, b1, gco, lane);
+  for (uint32_t pass = 0; pass < P.num_passes; pass++) {
+    const PassDev& T = P.passes[pass];
+    const uint32_t sec = pass * P.num_groups + g;
+    if (P.sec_size[sec] == 0) break;  // (a frame drawn from a prefix of its bytes: this pass of the group has not arrived)
+    __syncthreads();
+    for (uint32_t i = lane; i < 3 * 1024; i += 64) l_nz[i] = 0;
+    // lane 0 opens the section; all lanes then stage the slice of the context map its selector names
+    __shared__ uint32_t s_sel, s_state;
+    __shared__ BitReader s_br;
+    if (lane == 0) {
+      BitReader br;
+      uint32_t state, err = 0;
+      s_sel = OpenSection(P, sec, true, br, state, err);
+      if (err) atomicOr(&P.errors[g], err);  // (a selector that names no set is flagged, and the section is read with set 0)
+      s_state = state;
+      s_br = br;
+    }
+    __syncthreads();
+    {
+      const uint8_t* src = T.ctx_map + size_t(s_sel) * P.nctx;
+      for (uint32_t i = lane; i < P.nctx + 16; i += 64) l_ctx[i] = src[i];
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (lane != 0) continue;
+    AnsReader rd = {s_br, s_state, 0, T.alias, T.cfg, T.log_alpha};
+    WalkSection(P, T, rd, l_ctx, l_nz, gco, g, pass, b0, b1);
+  }
+}
+
 template <typename CoefT>
 __global__ __launch_bounds__(64) void k_entropy_generic(EntropyParams P) {
   extern __shared__ __align__(16) uint8_t lds_raw[];
@@ -394,22 +404,11 @@ __global__ __launch_bounds__(64) void k_entropy_generic(EntropyParams P) {
   uint8_t* l_nz = lds_raw;  // 3 * 1024
   const uint32_t b0 = P.gbb[g], b1 = P.gbb[g + 1];
   CoefT* gco = static_cast<CoefT*>(P.coeffs) + size_t(g) * 3 * 65536;
-  uint32_t total = 0;
-  if (b1 > b0) {
-    const JxlHipVarBlock last = P.blocks[b1 - 1];
-    total = last.coef_offset + (64u << c_log2_covered[last.strategy]);
-  }
-  {
-    const uint32_t n16 = (total * uint32_t(sizeof(CoefT))) / 16;
-    for (int c = 0; c < 3; c++) {
-      uint4* dst = reinterpret_cast<uint4*>(gco + size_t(c) * 65536);
-      for (uint32_t i = lane; i < n16; i += 64) dst[i] = make_uint4(0, 0, 0, 0);
-    }
-  }
+  ZeroGroup(P, b0, b1, gco, lane);
   for (uint32_t pass = 0; pass < P.num_passes; pass++) {
     const PassDev& T = P.passes[pass];
     const uint32_t sec = pass * P.num_groups + g;
-    if (P.sec_size[sec] == 0) break;  // (this pass of the group has not arrived: a frame drawn from a prefix; the group is zeroed above)
+    if (P.sec_size[sec] == 0) break;  // (a frame drawn from a prefix of its bytes: this pass of the group has not arrived)
     __syncthreads();
     for (uint32_t i = lane; i < 3 * 1024; i += 64) l_nz[i] = 0;
     __threadfence_block();
@@ -420,113 +419,22 @@ __global__ __launch_bounds__(64) void k_entropy_generic(EntropyParams P) {
     r.window = P.lz_window ? P.lz_window + size_t(g) * kLzWindow : nullptr;  // (passes run one after the other)
     r.num_decoded = r.num_to_copy = r.copy_pos = 0;
     r.err = 0;
-    r.br.p = P.sections + P.sec_word[sec];
-    r.br.nwords = (P.sec_size[sec] + 3) / 4;
-    r.br.idx = 0;
-    r.br.buf = 0;
-    r.br.bits = 0;
-    BrRefill(r.br);
-    if (sec == 0 && P.first_bit_offset) BrRead(r.br, P.first_bit_offset);
-    uint32_t hb = 0;
-    while ((1u << hb) < P.num_hist) hb++;
-    BrRefill(r.br);
-    uint32_t sel = hb ? BrRead(r.br, hb) : 0;
-    if (sel >= P.num_hist) {
-      r.err |= kErrSelector;
-      sel = 0;
-    }
-    r.state = 0x13u << 16;
-    if (!T.use_prefix) {  // dec_ans.cc:402: only an ANS stream starts with its state
-      BrRefill(r.br);
-      r.state = BrRead(r.br, 16);
-      BrRefill(r.br);
-      r.state |= BrRead(r.br, 16) << 16;
-    }
-    const uint8_t* ctx_map = T.ctx_map + size_t(sel) * P.nctx;
-    const uint32_t shift = T.shift;
-    for (uint32_t bi = b0; bi < b1 && !r.err; bi++) {
-      const JxlHipVarBlock vb = P.blocks[bi];
-      const uint32_t st = vb.strategy;
-      const uint32_t cx = c_covered_x[st], cy = c_covered_y[st], log2c = c_log2_covered[st];
-      const uint32_t covered = 1u << log2c, size = covered * 64;
-      const uint32_t ord = c_strategy_order[st];
-      uint32_t qfi = 0;
-      for (uint32_t t = 0; t + 1 < P.nq; t++) qfi += vb.qf > P.qf_thr[t];
-      const uint32_t fbx = vb.bx & 31, fby = vb.by & 31;
-#pragma unroll 1
-      for (int ci = 0; ci < 3 && !r.err; ci++) {
-        const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
-        const uint32_t hs = (P.cs >> (2 * c)) & 1u, vs = (P.cs >> (2 * c + 1)) & 1u;  // (subsampled channels: see k_entropy_ans)
-        if ((fbx & hs) | (fby & vs)) continue;
-        const uint32_t lbx = fbx >> hs, lby = fby >> vs;
-        uint8_t* nzc = l_nz + c * 1024;
-        uint32_t pred;
-        if (lbx == 0) pred = lby ? nzc[(lby - 1) * 32] : 32;
-        else if (lby == 0) pred = nzc[lbx - 1];
-        else pred = (uint32_t(nzc[(lby - 1) * 32 + lbx]) + nzc[lby * 32 + lbx - 1] + 1) >> 1;
-        uint32_t qfc = qfi;  // (the quant field at the channel's own column: see k_entropy_ans)
-        if (P.cs != 0 && hs) {
-          const uint32_t q = P.blocks[bi - (fbx - lbx)].qf;
-          qfc = 0;
-          for (uint32_t t = 0; t + 1 < P.nq; t++) qfc += q > P.qf_thr[t];
-        }
-        const uint32_t bctx = P.bctx_lut[((c * 13 + ord) * P.nq + qfc) * P.ndc + vb.quant_dc_ctx];
-        uint32_t nzb = pred >= 64 ? 64 : pred;
-        nzb = nzb < 8 ? nzb : 4 + nzb / 2;
-        uint32_t nzeros = GenericRead(r, ctx_map[nzb * P.num_bctx + bctx]);
-        if (nzeros > size - covered) {
-          r.err |= kErrNzeros;
-          break;
-        }
-        const uint8_t nzv = uint8_t((nzeros + covered - 1) >> log2c);
-        for (uint32_t y = 0; y < cy; y++)
-          for (uint32_t x = 0; x < cx; x++) nzc[(lby + y) * 32 + lbx + x] = nzv;
-        const uint32_t hoff = P.num_bctx * 37 + 458 * bctx;
-        const uint16_t* order = T.orders + T.order_offset[ord * 3 + c];
-        CoefT* dst = gco + size_t(c) * 65536 + vb.coef_offset;
-        uint32_t prev = nzeros > size / 16 ? 0 : 1;
-        for (uint32_t k = covered; k < size && nzeros != 0 && !r.err; ++k) {
-          const uint32_t nzl = (nzeros + covered - 1) >> log2c;
-          const uint32_t ctx = hoff + (uint32_t(c_coeff_nnz_ctx[nzl & 63]) + c_coeff_freq_ctx[(k >> log2c) & 63]) * 2 + prev;
-          const uint32_t u = GenericRead(r, ctx_map[ctx]);
-          const uint32_t mag = u >> 1, neg = (~u) & 1;
-          const int32_t coeff = int32_t((mag ^ (neg - 1)) << shift);
-          if (u) {
-            const uint32_t pos = order[k];
-            dst[pos] = CoefT(dst[pos] + coeff);
-          }
-          prev = u != 0;
-          nzeros -= prev;
-        }
-        if (nzeros != 0) r.err |= kErrNzeros;
-      }
-    }
-    uint32_t err = r.err;
-    if (!err && r.state != (0x13u << 16)) err |= kErrFinalState;
-    {
-      const uint64_t consumed = uint64_t(r.br.idx) * 32 - uint64_t(r.br.bits);
-      if (consumed > uint64_t(P.sec_size[sec]) * 8) err |= kErrOverread;
-      P.sec_end_bits[sec] = uint32_t(consumed);
-    }
-    if (err) atomicOr(&P.errors[g], err);
+    const uint32_t sel = OpenSection(P, sec, !T.use_prefix, r.br, r.state, r.err);  // (a selector that names no set: flagged, not read)
+    WalkSection(P, T, r, T.ctx_map + size_t(sel) * P.nctx, l_nz, gco, g, pass, b0, b1);
   }
 }
 
 // ---------------------------------------------------------------------------------------------- entropy, scalar form
-// Same decode as k_entropy_ans, restructured so that the serial chain runs on the scalar unit: every lane of the
-// wave executes the identical (wave-uniform) control flow, all decoder state lives in SGPRs, table reads that have a
-// uniform address go through the scalar cache (constant address space) or LDS + readfirstlane, and only the
-// coefficient stores are vector instructions (lane 0). The context-map / uint-config lookups of the NEXT coefficient
-// are issued speculatively for both outcomes (zero / non-zero) before the current symbol is resolved, which takes
-// them off the dependency chain: per symbol the chain is one LDS alias-table read + ~30 scalar ALU ops.
+// The decode of WalkSection (with jxl_hip_block_ctx.h's arithmetic), restructured so that the serial chain runs on
+// the scalar unit: every lane of the wave executes the identical (wave-uniform) control flow, all decoder state lives
+// in SGPRs, table reads that have a uniform address go through the scalar cache (constant address space) or LDS +
+// readfirstlane, and only the coefficient stores are vector instructions (lane 0). The context-map / uint-config
+// lookups of the NEXT coefficient are issued speculatively for both outcomes (zero / non-zero) before the current
+// symbol is resolved, which takes them off the dependency chain: per symbol the chain is one LDS alias-table read +
+// ~30 scalar ALU ops.
 typedef const uint32_t __attribute__((address_space(4)))* CU32;
 __device__ __forceinline__ CU32 AsConst(const void* p) { return (CU32)(uintptr_t)p; }
 __device__ __forceinline__ uint32_t Uni(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-
-__constant__ uint32_t c_strategy_info[27] = {  // covered_x | covered_y << 8 | log2_covered << 16 | order bucket << 24
-    0x00000101, 0x01000101, 0x01000101, 0x01000101, 0x02020202, 0x03040404, 0x04010201, 0x04010102, 0x05020401,
-    0x05020104, 0x06030402, 0x06030204, 0x01000101, 0x01000101, 0x01000101, 0x01000101, 0x01000101, 0x01000101,
-    0x07060808, 0x08050804, 0x08050408, 0x09081010, 0x0A071008, 0x0A070810, 0x0B0A2020, 0x0C092010, 0x0C091020};
 
 struct SBits {
   CU32 p;
@@ -681,8 +589,7 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_uni(EntropyBatch B) {
     JXL_REFILL();
     uint32_t tmp;
     if (sec == 0 && P.first_bit_offset) JXL_READ(P.first_bit_offset, tmp);
-    uint32_t hb = 0;
-    while ((1u << hb) < P.num_hist) hb++;
+    const uint32_t hb = SelectorBits(P.num_hist);
     JXL_REFILL();
     uint32_t sel = 0;
     if (hb) JXL_READ(hb, sel);
@@ -742,31 +649,19 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_uni(EntropyBatch B) {
       const uint32_t info = c_strategy_info[st];
       const uint32_t cx = info & 0xFF, cy = (info >> 8) & 0xFF, log2c = (info >> 16) & 0xFF, ord = info >> 24;
       const uint32_t covered = 1u << log2c, size = covered * 64;
-      uint32_t qfi = 0;
-      for (uint32_t t = 0; t + 1 < P.nq; t++) qfi += qf > P.qf_thr[t];
+      const uint32_t qfi = QfBucket(qf, P.qf_thr, P.nq);
       const uint32_t fbx = w0 & 31, fby = (w0 >> 16) & 31;
 #pragma unroll 1
       for (int ci = 0; ci < 3 && !err; ci++) {
         const uint32_t c = ci == 0 ? 1u : (ci == 1 ? 0u : 2u);
-        const uint32_t hs = (P.cs >> (2 * c)) & 1u, vs = (P.cs >> (2 * c + 1)) & 1u;  // (subsampled channels: see k_entropy_ans)
-        if ((fbx & hs) | (fby & vs)) continue;
-        const uint32_t lbx = fbx >> hs, lby = fby >> vs;
+        uint32_t lbx, lby;
+        if (!ChannelCell(P.cs, c, fbx, fby, lbx, lby)) continue;
         uint8_t* nzc = l_nz + c * 1024;
-        uint32_t pred;
-        if (lbx == 0) pred = lby ? Uni(nzc[(lby - 1) * 32]) : 32;
-        else if (lby == 0) pred = Uni(nzc[lbx - 1]);
-        else pred = (Uni(nzc[(lby - 1) * 32 + lbx]) + Uni(nzc[lby * 32 + lbx - 1]) + 1) >> 1;
-        uint32_t qfc = qfi;  // (the quant field at the channel's own column: see k_entropy_ans)
-        if (P.cs != 0 && hs) {
-          const uint32_t q = blk[(bi - (fbx - lbx)) * 3 + 1] >> 16;
-          qfc = 0;
-          for (uint32_t t = 0; t + 1 < P.nq; t++) qfc += q > P.qf_thr[t];
-        }
-        const uint32_t li = ((c * 13 + ord) * P.nq + qfc) * P.ndc + dcctx;
+        const uint32_t pred = PredictNonZeros([nzc](uint32_t i) { return Uni(nzc[i]); }, lbx, lby);
+        const uint32_t qfc = ChannelHShift(P.cs, c) ? QfBucket(blk[(bi - QfColumnBack(fbx, lbx)) * 3 + 1] >> 16, P.qf_thr, P.nq) : qfi;
+        const uint32_t li = BctxLutIndex(c, ord, P.nq, qfc, P.ndc, dcctx);
         const uint32_t bctx = (lut[li >> 2] >> ((li & 3) * 8)) & 0xFF;
-        uint32_t nzb = pred >= 64 ? 64 : pred;
-        nzb = nzb < 8 ? nzb : 4 + nzb / 2;
-        uint32_t cl = Uni(l_ctx[nzb * P.num_bctx + bctx]);
+        uint32_t cl = Uni(l_ctx[NonZeroBucket(pred) * P.num_bctx + bctx]);
         uint32_t cf = Uni(l_cfg[cl]);
         uint32_t nzeros;
         JXL_SYMBOL(cl, cf, nzeros);
@@ -775,32 +670,31 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_uni(EntropyBatch B) {
           break;
         }
         {
-          const uint8_t nzv = uint8_t((nzeros + covered - 1) >> log2c);
+          const uint8_t nzv = uint8_t(NonZerosPerBlock(nzeros, covered, log2c));
           for (uint32_t i = lane; i < cx * cy; i += 64) nzc[(lby + i / cx) * 32 + lbx + i % cx] = nzv;
         }
         if (nzeros == 0) continue;
-        const uint32_t hoff = P.num_bctx * 37 + 458 * bctx;
+        const uint32_t hoff = ZeroDensityBase(P.num_bctx, bctx);
         const uint16_t* order = T.orders + ooff[ord * 3 + c];
         CoefT* dst = gco + size_t(c) * 65536 + coef_offset;
         uint32_t prev = nzeros > size / 16 ? 0 : 1;
         uint32_t k = covered;
-        uint32_t nnz_cur = NnzCtx(((nzeros + covered - 1) >> log2c) & 63);
-        uint32_t nnz_nxt = NnzCtx(((nzeros - 1 + covered - 1) >> log2c) & 63);
-        cl = Uni(l_ctx[hoff + (nnz_cur + FreqCtx((k >> log2c) & 63)) * 2 + prev]);
+        uint32_t nnz_cur = NnzCtx(NonZerosPerBlock(nzeros, covered, log2c) & 63);
+        uint32_t nnz_nxt = NnzCtx(NonZerosPerBlock(nzeros - 1, covered, log2c) & 63);
+        cl = Uni(l_ctx[ZeroDensityContext(hoff, nnz_cur, FreqCtx((k >> log2c) & 63), prev)]);
         cf = Uni(l_cfg[cl]);
         uint32_t count = 0;
         for (;;) {
           // speculative lookups for coefficient k+1: A = this one is zero, B = this one is non-zero
           const uint32_t kn = k + 1;
           const uint32_t fq = FreqCtx((kn >> log2c) & 63);
-          const uint8_t rawA = l_ctx[hoff + (nnz_cur + fq) * 2];
-          const uint8_t rawB = l_ctx[hoff + (nnz_nxt + fq) * 2 + 1];
+          const uint8_t rawA = l_ctx[ZeroDensityContext(hoff, nnz_cur, fq, 0)];
+          const uint8_t rawB = l_ctx[ZeroDensityContext(hoff, nnz_nxt, fq, 1)];
           const uint32_t cfA_v = l_cfg[rawA], cfB_v = l_cfg[rawB];
           uint32_t u;
           JXL_SYMBOL(cl, cf, u);
           if (u) {
-            const uint32_t mag = u >> 1, neg = (~u) & 1;
-            const uint32_t coeff = (mag ^ (neg - 1)) << shift;
+            const uint32_t coeff = TokenValue(u, shift);
             if (lane == 0) l_list[count] = make_uint2(k, coeff);
             count++;
             nzeros--;
@@ -817,7 +711,7 @@ __global__ __launch_bounds__(64 * WPG) void k_entropy_uni(EntropyBatch B) {
               count = 0;
             }
             nnz_cur = nnz_nxt;
-            nnz_nxt = NnzCtx(((nzeros - 1 + covered - 1) >> log2c) & 63);
+            nnz_nxt = NnzCtx(NonZerosPerBlock(nzeros - 1, covered, log2c) & 63);
             cl = Uni(rawB);
             cf = Uni(cfB_v);
           } else {

@@ -48,6 +48,15 @@ for _i, _kw in enumerate(SUBSAMPLED_KW):
 # histograms that their alias tables do not fit beside the context map in LDS (tests/test_gpu_ac_walk.py asserts the kernels)
 DECODE_CASES["subsampled0_bctx1_prefix_lz77"] = lambda J: _subsampled(J, dict(SUBSAMPLED_KW[0], ac_code_mode=3), 1)
 DECODE_CASES["subsampled0_bctx1_clusters"] = lambda J: _subsampled(J, dict(SUBSAMPLED_KW[0], max_clusters=-200, big_coeffs=1), 1)
+# The section-per-workgroup kernels' pass accumulation and histogram selector (the other cases with passes or sets take the
+# lane kernel or k_entropy_uni on the device): two passes, two histogram sets (the frame has two groups), custom orders,
+# through the prefix / LZ77 reader and through alias tables beyond LDS. The writer cannot give the last of several passes
+# tables that large (it carries the lowest bits alone: 32-entry tables, at most 64 KiB of them), so the two-pass frame is
+# beyond LDS by its first pass, which decides for the frame, and hist2_clusters has every pass (its only one) beyond it.
+_PASSES2_HIST2 = dict(num_passes=2, num_histograms=2, custom_orders=1)
+DECODE_CASES["passes2_hist2_prefix_lz77"] = lambda J: J.encode_random(264, 200, ac_code_mode=3, **_PASSES2_HIST2)
+DECODE_CASES["passes2_hist2_clusters"] = lambda J: J.encode_random(264, 200, max_clusters=-200, big_coeffs=1, **_PASSES2_HIST2)
+DECODE_CASES["hist2_clusters"] = lambda J: J.encode_random(264, 200, max_clusters=-200, big_coeffs=1, num_histograms=2, custom_orders=1)
 SUBSAMPLED_BCTX = ["subsampled%d_bctx1" % i for i in range(len(SUBSAMPLED_KW))] + ["subsampled0_bctx1_prefix_lz77", "subsampled0_bctx1_clusters"]
 
 _cache = {}
@@ -86,6 +95,13 @@ def test_the_oracles_coefficients_are_the_readings(built, name):
         assert bad.size == 0, "group %d: %d coefficients differ, first at channel %d slot %d" % (g, len(bad), bad[0][0], bad[0][1])
         # (decode_group has checked that every pass's coder ended in its start state; the bit it stopped at is the oracle's)
         assert r["end_bits"] == [T["sections"][p][g][3] for p in range(T["num_passes"])]
+
+
+def _alias_tables_beyond_lds(T, p):
+    """jxlhip_frame_upload's condition for reading a pass's alias tables in place: 8 bytes an entry, beside the staged
+    context map (one set's contexts + 16, rounded up to 16 bytes) and 1 KiB + 4 * 5 KiB of working space in 150 KiB."""
+    ctx_bytes = (T["bctx"]["num_ctxs"] * 495 + 16 + 15) & ~15
+    return (len(p["clusters"]) << p["log_alpha"]) * 8 + ctx_bytes + 1024 + 4 * 5120 > 150 * 1024
 
 
 def _used(acs, g):
@@ -129,6 +145,19 @@ def test_the_cases_hold_what_they_are_for(built):
     assert len(case(J, "d05_clusters200")["tables"]["passes"][0]["clusters"]) > 1
     P = case(J, "subsampled0_bctx1_clusters")["tables"]["passes"][0]  # 200 alias tables of 128 entries: 200 KiB
     assert len(P["clusters"]) == 200 and P["log_alpha"] == 7 and not P["use_prefix"] and P["lz77"] is None
+    for n in ("passes2_hist2_prefix_lz77", "passes2_hist2_clusters", "hist2_clusters"):
+        T = case(J, n)["tables"]
+        P = T["passes"]
+        assert T["num_histograms"] == T["num_groups"] == 2 and any(any(r["ctx_offset"]) for r in case(J, n)["groups"]), n
+        if n == "hist2_clusters":
+            assert len(P) == 1 and _alias_tables_beyond_lds(T, P[0])
+            continue
+        assert [p["shift"] for p in P] == [1, 0] and not np.array_equal(P[0]["orders"], P[1]["orders"]), n
+        if n == "passes2_hist2_prefix_lz77":
+            assert all(p["use_prefix"] and p["lz77"] is not None for p in P)
+        else:
+            assert not any(p["use_prefix"] or p["lz77"] is not None for p in P)
+            assert _alias_tables_beyond_lds(T, P[0])  # (the frame's route goes by its largest pass; the writer's last pass stays small)
     for s in range(27):  # every strategy is there
         assert ((case(J, "strategy%d" % s)["acs"] >> 1) == s).any(), s
     # the RGBA stream: Modular data sits behind the coefficients, so the section goes on behind the walk

@@ -33,6 +33,9 @@ DEVICE_CASES = {
     "subsampled0_bctx1_prefix_lz77": (GENERIC, GENERIC),
     "subsampled0_bctx1_clusters": (LANES, ANS),  # (the lane kernel reads alias tables of any size in place)
     "prefix_lz77": (GENERIC, GENERIC),
+    "passes2_hist2_prefix_lz77": (GENERIC, GENERIC),  # the section-per-workgroup kernels' passes and selector
+    "passes2_hist2_clusters": (LANES, ANS),
+    "hist2_clusters": (LANES, ANS),
     "rgba": (LANES, UNI),
     "int32": (LANES, UNI),
 }

@@ -409,10 +409,10 @@ def test_reference_wasm_demo_streams(built, tmp_path):
 
 
 def _c_array(path, name):
-    """The integer initialiser list of the C array `name` in `path`."""
+    """The integer initialiser list of the C array (or one-array aggregate) `name` in `path`."""
     import re
     text = open(os.path.join(ROOT, path)).read()
-    m = re.search(r"\b%s\[[^\]]*\]\s*=\s*\{(.*?)\};" % re.escape(name), text, re.S)
+    m = re.search(r"\b%s(?:\[[^\]]*\])?\s*=\s*\{(.*?)\};" % re.escape(name), text, re.S)
     assert m, (path, name)
     return [int(t, 0) for t in re.findall(r"0x[0-9a-fA-F]+|\d+", re.sub(r"//.*", "", m.group(1)))]
 
@@ -443,8 +443,11 @@ def test_icc_stream_delivered_in_small_pieces(built, tmp_path):
 def test_context_model_tables_match_the_reference_source():
     """The AC context model's constant tables as the reference's source has them (tests/golden/ref_constant_tables.json,
     extracted by tests/golden/make_tables_golden.py from lib/jxl/ac_context.h:29-42,91-96 and coeff_order.h:44-46) against
-    every copy in this repository: the product's host and device tables, the arithmetic forms the kernels use, the
-    oracle's and the test encoder's. A shared transcription error would pass every encoder -> decoder test."""
+    every copy in this repository: the product's host tables, the HIP layer's one statement of the per-strategy tables
+    (csrc/hip/jxl_hip_block_ctx.h: host and device code read the same objects) with the packed word and the log2 built
+    from them, the arithmetic forms the kernels use, the oracle's and the test encoder's. A shared transcription
+    error would pass every encoder -> decoder test."""
+    hip = "libjxl_amd/csrc/hip/jxl_hip_block_ctx.h"
     ref = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_constant_tables.json")))
     freq, nnz = ref["kCoeffFreqContext"], ref["kCoeffNumNonzeroContext"]
     assert _c_array("libjxl_amd/csrc/host/jxh_vardct.h", "kCoeffFreqContext") == freq
@@ -455,14 +458,36 @@ def test_context_model_tables_match_the_reference_source():
     assert _c_array("libjxl_amd/csrc/hip/jxl_hip_kernels.h", "c_coeff_freq_ctx")[1:] == freq[1:]
     # the lane kernel's arithmetic form of kCoeffFreqContext (jxl_hip_entropy_lanes.h): min(b - 1, 7 + b / 2, 15 + b / 4)
     assert [min(b - 1, 7 + b // 2, 15 + b // 4) for b in range(1, 64)] == freq[1:]
-    for path, name in (("libjxl_amd/csrc/host/jxh_vardct.h", "kStrategyOrder"), ("libjxl_amd/csrc/hip/jxl_hip_kernels.h", "c_strategy_order"),
+    for path, name in (("libjxl_amd/csrc/host/jxh_vardct.h", "kStrategyOrder"), (hip, "kStrategyOrder"),
                        ("oracle/jxlo_vardct.h", "kStrategyOrder")):
         assert _c_array(path, name) == ref["kStrategyOrder"], path
     for path in ("libjxl_amd/csrc/host/jxh_vardct.h", "oracle/jxlo_vardct.h"):
         assert _c_array(path, "kDefault") == ref["kDefaultCtxMap"], path
         assert _c_array(path, "kCoveredX") == ref["covered_blocks_x"] and _c_array(path, "kCoveredY") == ref["covered_blocks_y"], path
         assert _c_array(path, "kStrategyQuantTable") == ref["strategy_to_quant_table"], path
-    assert _c_array("libjxl_amd/csrc/hip/jxl_hip_kernels.h", "c_strategy_qtable") == ref["strategy_to_quant_table"]
+    assert _c_array(hip, "kStrategyQuantTable") == ref["strategy_to_quant_table"]
+    assert _c_array(hip, "kCoveredX") == ref["covered_blocks_x"] and _c_array(hip, "kCoveredY") == ref["covered_blocks_y"]
+    # no table of these is typed a second time in the HIP layer: the device's copies are initialised from the objects above
+    hip_text = "".join(open(os.path.join(ROOT, "libjxl_amd/csrc/hip", n)).read() for n in sorted(os.listdir(os.path.join(ROOT, "libjxl_amd/csrc/hip"))))
+    for name in ("kCoveredX", "kCoveredY", "kStrategyOrder", "kStrategyQuantTable"):
+        assert hip_text.count(", ".join(map(str, _c_array(hip, name)))) == 1, name
+    for dev, host in (("c_covered_x", "kCoveredX"), ("c_covered_y", "kCoveredY"), ("c_strategy_order", "kStrategyOrder"),
+                      ("c_strategy_qtable", "kStrategyQuantTable"), ("c_log2_covered", "kLog2Covered"), ("c_strategy_info", "kStrategyInfo")):
+        assert "%s = %s;" % (dev, host) in hip_text, dev
+    # the packed word of k_entropy_uni and log2 covered are built from those objects by the constant expressions of
+    # MakeStrategyInfo / MakeLog2Covered, read here as written: every field of every strategy against the fixture
+    text = open(os.path.join(ROOT, hip)).read()
+    assert "r.v[s] = uint32_t(kCoveredX[s]) | uint32_t(kCoveredY[s]) << 8 | uint32_t(kLog2Covered[s]) << 16 | uint32_t(kStrategyOrder[s]) << 24;" in text
+    assert "r.v[s] = uint8_t(Log2CoveredX(s) + Log2CoveredY(s));" in text
+    import re
+    pinned = {int(s_): int(w, 16) for s_, w in re.findall(r"kStrategyInfo\[(\d+)\] == (0x[0-9A-Fa-f]+)", text)}  # (the header's static_asserts)
+    assert len(pinned) >= 3
+    for s_, w in pinned.items():
+        cx, cy = ref["covered_blocks_x"][s_], ref["covered_blocks_y"][s_]
+        assert (w & 0xFF, (w >> 8) & 0xFF, w >> 24) == (cx, cy, ref["kStrategyOrder"][s_]) and 1 << ((w >> 16) & 0xFF) == cx * cy, s_
+    for s_ in range(27):  # log2 covered = log2(cx * cy) is a whole number for every strategy: the sum of the two log2 is exact
+        cx, cy = ref["covered_blocks_x"][s_], ref["covered_blocks_y"][s_]
+        assert cx & (cx - 1) == 0 and cy & (cy - 1) == 0, s_
 
 
 def test_enum_colour_encodings_of_lossless_images_are_reported(built):
