@@ -18,6 +18,7 @@
 
 #include "../../../include/jxl_amd_hip.h"
 #include "../host/jxh_enc_shared.h"
+#include "../host/jxh_upload_plan.h"
 #include "jxl_hip_kernels.h"
 #include "jxl_hip_entropy_lanes.h"
 #include "jxl_hip_filter_fused.h"
@@ -25,6 +26,8 @@
 #include "jxl_hip_enc.h"
 #include "jxl_hip_canvas.h"
 #include "jxl_hip_dc.h"
+
+namespace upload = jxlhip::upload;
 
 namespace {
 #include "../host/afv_basis.inc"
@@ -178,7 +181,6 @@ struct JxlHipContext {
   // by ONE host-to-device copy at the end of the upload (HIP serialises API calls of all host threads: twenty small
   // copies per frame capped a multi-threaded uploader at ~0.6 ms per frame); the tables' Bufs are views into it.
   Buf frame_blob;
-  bool blob_mode = false;
   bool have_frame = false;
   // geometry
   uint32_t xs = 0, ys = 0, xb = 0, yb = 0, xg = 0, ng = 0, np = 0, xp = 0, yp = 0, coef_bits = 16;
@@ -375,28 +377,7 @@ static const JxlHipContext* PlaneHolder(const JxlHipContext* c) { return c->plan
 
 static size_t OutSampleBytes(const JxlHipContext* c) { return c->out_type == 2 ? 1 : (c->out_type == 0 ? 4 : 2); }
 static size_t OutPixelBytes(const JxlHipContext* c) { return OutSampleBytes(c) * c->out_nc; }
-static bool OutIsRgb8(const JxlHipContext* c) { return c->out_type == 2 && c->out_nc == 3 && c->out_bits == 8; }
-static bool OutIsGray8(const JxlHipContext* c) { return c->out_type == 2 && c->out_nc == 1 && c->out_bits == 8; }
-static bool OutIsRgbF32(const JxlHipContext* c) { return c->out_type == 0 && c->out_nc == 3 && !c->out_swap; }
-
-// Every index PrefixLookup (jxl_hip_kernels.h) can form from a cluster's two-level tables stays inside `table`, and
-// every code length it can return is at most 15 bits.
-static bool ValidPrefixTables(uint32_t offset_word, const uint32_t* table, size_t table_size) {
-  const size_t first = offset_word & 0xFFFFFFu, root_bits = offset_word >> 24;
-  if (root_bits > 15 || first + (size_t(1) << root_bits) > table_size) return false;
-  for (size_t r = 0; r < (size_t(1) << root_bits); r++) {
-    const uint32_t e = table[first + r];
-    if (!(e & 0x80u)) {
-      if ((e & 0xFFu) > 15) return false;
-      continue;
-    }
-    const size_t sub_bits = e & 0x7Fu, sub = first + (e >> 8);
-    if (sub_bits == 0 || root_bits + sub_bits > 15 || sub + (size_t(1) << sub_bits) > table_size) return false;
-    for (size_t j = 0; j < (size_t(1) << sub_bits); j++)
-      if ((table[sub + j] & 0x80u) || (table[sub + j] & 0xFFu) > 15) return false;
-  }
-  return true;
-}
+static bool OutIsRgb8(const JxlHipContext* c) { return upload::OutIsRgb8(c->out_type, c->out_nc, c->out_bits); }
 
 static int EnvInt(const char* name, int def) {
   const char* e = getenv(name);
@@ -489,6 +470,11 @@ static JxlHipContext* RecycleContext(int device) {
   return c;
 }
 
+// The DCT basis every context uploads (jxlhip_ctx_create): the [k][n] matrices of N = 1, 2 .. 256, matrix N at float
+// (N * N - 1) / 3, and behind them, 16-byte aligned, the transposed [n][k] ones.
+constexpr size_t kBasisFloats = 87381;  // (4^9 - 1) / 3
+constexpr size_t kBasisTransposed = kBasisFloats + 3;
+
 int jxlhip_ctx_create(int device, JxlHipContext** out) {
   if (!out) return JXLHIP_ERR_INVALID_ARGUMENT;
   *out = nullptr;
@@ -514,12 +500,11 @@ int jxlhip_ctx_create(int device, JxlHipContext** out) {
     }
   }
   // static tables
-  constexpr size_t kBasisFloats = 87381;
-  std::vector<float> bt(2 * kBasisFloats + 4);  // [k][n] matrices, then (16-byte aligned) the transposed [n][k] ones
+  std::vector<float> bt(2 * kBasisFloats + 4);
   for (int l = 0; l <= 8; l++) {
     const int N = 1 << l;
     float* dst = bt.data() + (size_t(N) * N - 1) / 3;
-    float* dst_t = dst + kBasisFloats + 3;
+    float* dst_t = dst + kBasisTransposed;
     for (int k = 0; k < N; k++)
       for (int n = 0; n < N; n++) {
         const float v = float((k ? std::sqrt(2.0) : 1.0) * std::cos((n + 0.5) * k * M_PI / N));
@@ -601,6 +586,7 @@ void jxlhip_ctx_destroy(JxlHipContext* c) {
   if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
+}  // extern "C"
 
 static int ApplyPendingWait(JxlHipContext* c) {
   if (c->pending_wait) {
@@ -642,9 +628,8 @@ static int StageReset(JxlHipContext* c) {
 }
 static int StageAlloc(JxlHipContext* c, size_t bytes, void** out) {
   Stage& s = c->stage;
-  const size_t need = (bytes + 63) & ~size_t(63);
+  const size_t need = upload::StagedBytes(bytes);
   if (s.used + need > s.cap) {  // a larger block: copies out of the current one may still be in flight
-    if (c->blob_mode) return JXLHIP_ERR_INVALID_ARGUMENT;  // (the blob's bound was wrong: the views would dangle)
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (hipStream_t cs = CopyStream(c->device)) HIP_TRY(hipStreamSynchronize(cs));
     size_t want = s.cap * 2 > need ? s.cap * 2 : need;
@@ -660,31 +645,26 @@ static int StageAlloc(JxlHipContext* c, size_t bytes, void** out) {
   s.used += need;
   return 0;
 }
-// Copies `bytes` already assembled in the staging block (`staged`, from StageAlloc) to `b`.
-static int UploadStaged(JxlHipContext* c, Buf& b, const void* staged, size_t bytes) {
-  if (c->blob_mode) {
-    const size_t at = size_t(static_cast<const uint8_t*>(staged) - c->stage.p);
-    if (!staged || at + (bytes ? bytes : 16) > c->frame_blob.cap) return JXLHIP_ERR_INVALID_ARGUMENT;  // (the bound was wrong)
-    if (!b.view) b.Free();
-    b.p = c->frame_blob.as<uint8_t>() + at;
-    b.cap = bytes ? bytes : 16;
-    b.view = true;
-    return 0;
-  }
-  int r = b.Ensure(bytes ? bytes : 16);
-  if (r) return r;
-  if (bytes) HIP_TRY(hipMemcpyAsync(b.p, staged, bytes, hipMemcpyHostToDevice, c->stream));
-  return 0;
-}
-static int UploadStaged(JxlHipContext* c, Buf& b, const void* staged, size_t bytes);
-static int UploadSplines(JxlHipContext* c, const JxlHipSplines& sp, uint32_t ysize);
+// A table to a buffer of its own: through the staging block, by an asynchronous copy on the context's stream (an empty
+// table still gets a valid address).
 static int Upload(JxlHipContext* c, Buf& b, const void* src, size_t bytes) {
   void* st = nullptr;
-  int r = StageAlloc(c, bytes ? bytes : 16, &st);  // (blob mode: an empty table still gets a valid address)
+  int r = StageAlloc(c, bytes, &st);
   if (r) return r;
-  if (bytes) memcpy(st, src, bytes);
-  return UploadStaged(c, b, st, bytes);
+  if ((r = b.Ensure(bytes ? bytes : 16))) return r;
+  if (!bytes) return 0;
+  memcpy(st, src, bytes);
+  HIP_TRY(hipMemcpyAsync(b.p, st, bytes, hipMemcpyHostToDevice, c->stream));
+  return 0;
 }
+// (the visitor of upload::Visit...Tables that does so for every table of a list; the first failure stays)
+struct PlainUploader {
+  JxlHipContext* c;
+  int r = 0;
+  void copy(Buf& b, size_t bytes, const void* src) {
+    if (!r) r = Upload(c, b, src, bytes);
+  }
+};
 // Small host-to-device copies of launch descriptions (parameter blocks, work lists): through the context's staging block
 // and the copy stream like the tables, complete when End() returns.
 struct ParamCopy {
@@ -713,26 +693,61 @@ struct ParamCopy {
   }
 };
 
-// Blob mode: sizes the staging block and the device blob for `bound` bytes of tables; until BlobEnd, Upload / UploadStaged
-// only place tables (the Bufs become views at the staging offsets) and BlobEnd copies everything at once.
-static int BlobBegin(JxlHipContext* c, size_t bound) {
+// A frame's tables live in ONE device allocation laid out like the staging block (JxlHipContext::frame_blob). BlobBegin
+// sizes both for the bytes the frame's table list takes; BlobPlacer, walking the same list, assembles each table at the
+// next staging offset and makes its Buf a view of the blob there; BlobEnd copies everything at once.
+static int BlobBegin(JxlHipContext* c, size_t bytes) {
   Stage& s = c->stage;
-  if (s.cap < bound) {
+  if (s.cap < bytes) {
     void* dummy = nullptr;
-    int r = StageAlloc(c, bound, &dummy);  // grows the block (the stream is idle here: StageReset ran)
+    int r = StageAlloc(c, bytes, &dummy);  // grows the block (the stream is idle here: StageReset ran)
     if (r) return r;
     s.used = 0;
   }
-  int r = c->frame_blob.Ensure(s.cap);
-  if (r) return r;
-  c->blob_mode = true;
-  return 0;
+  return c->frame_blob.Ensure(s.cap);
 }
-// `smooth` / `sigma`: the DC-path kernels of this frame (NULL = not asked for), launched on the copy stream behind the copy
-// they read, so that the event the upload waits for covers them too.
+// JXLHIP_UPLOAD_PROF=1 (a measurement aid) prints where the host time of an upload goes: microseconds per phase.
+struct UploadProf {
+  const bool on = EnvInt("JXLHIP_UPLOAD_PROF", 0) != 0;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  std::string line;
+  void lap(const char* what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    line += std::string(what) + " " + std::to_string(std::chrono::duration_cast<std::chrono::microseconds>(now - t0).count()) + "  ";
+    t0 = now;
+  }
+};
+struct BlobPlacer {
+  JxlHipContext* c;
+  UploadProf* prof;
+  void* place(Buf& b, size_t bytes) {
+    Stage& s = c->stage;
+    void* st = s.p + s.used;
+    if (!b.view) b.Free();
+    b.p = c->frame_blob.as<uint8_t>() + s.used;
+    b.cap = bytes ? bytes : 16;
+    b.view = true;
+    s.used += upload::StagedBytes(bytes);
+    return st;
+  }
+  void copy(Buf& b, size_t bytes, const void* src) {
+    void* st = place(b, bytes);
+    if (bytes) memcpy(st, src, bytes);
+  }
+  template <typename F>
+  void build(Buf& b, size_t bytes, F&& fill) { fill(place(b, bytes)); }
+  void phase(const char* what) { prof->lap(what); }
+};
+// Where a placed table is being assembled (the parameter blocks are filled once every buffer has its address).
+template <typename T>
+static T* Staged(JxlHipContext* c, const Buf& b) {
+  return reinterpret_cast<T*>(c->stage.p + (b.as<uint8_t>() - c->frame_blob.as<uint8_t>()));
+}
+// `smooth` / `sigma` / `dequant`: the DC-path kernels of this frame (NULL = not asked for), launched on the copy stream
+// behind the copy they read, so that the event the upload waits for covers them too.
 static int BlobEnd(JxlHipContext* c, const jxlhip::DcSmoothParams* smooth = nullptr, const jxlhip::SigmaParams* sigma = nullptr,
                    const jxlhip::DcDequantParams* dequant = nullptr) {
-  c->blob_mode = false;
   hipStream_t cs = CopyStream(c->device);
   if (!cs) cs = c->stream;
   if (c->stage.used) HIP_TRY(hipMemcpyAsync(c->frame_blob.p, c->stage.p, c->stage.used, hipMemcpyHostToDevice, cs));
@@ -753,36 +768,13 @@ static int BlobEnd(JxlHipContext* c, const jxlhip::DcSmoothParams* smooth = null
   return 0;
 }
 
-// The patch dictionary of a frame to the device: validated like every table a kernel indexes with (rectangles inside the
-// frame and inside their reference frame, row lists consistent). ysize rows; positions may reach xlimit x ylimit.
-static int UploadPatches(JxlHipContext* c, const JxlHipPatches& pt, uint32_t ysize, uint32_t xlimit, uint32_t ylimit) {
-  c->pat_positions = 0;
-  c->pat_uses_alpha = false;
+// What the context remembers of a frame's splines and patches (the tables themselves: upload::Visit...Tables).
+static void AdoptSplines(JxlHipContext* c, const JxlHipSplines& sp) { c->spl_segments = sp.num_segments; }
+static void AdoptPatches(JxlHipContext* c, const JxlHipPatches& pt) {
+  c->pat_positions = pt.num_positions;
+  c->pat_uses_alpha = pt.num_positions && pt.uses_alpha != 0;
   c->alpha_patched_valid = false;
-  if (!pt.num_positions) return 0;
-  int r;
-  if (!pt.records || !pt.row_start || !pt.row_list || pt.num_positions > (1u << 24) || pt.num_row_entries > (1u << 26)) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (pt.row_start[0] != 0 || pt.row_start[ysize] != pt.num_row_entries) return JXLHIP_ERR_INVALID_ARGUMENT;
-  for (uint32_t y = 0; y < ysize; y++)
-    if (pt.row_start[y] > pt.row_start[y + 1]) return JXLHIP_ERR_INVALID_ARGUMENT;
-  for (uint32_t i = 0; i < pt.num_positions; i++) {
-    const uint32_t* q = pt.records + size_t(i) * 8;
-    const uint32_t slot = q[6];
-    if (slot > 3 || !pt.slot_planes[slot] || (q[7] & 255) > 7 || ((q[7] >> 16) & 255) > 7 || !q[2] || !q[3]) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (pt.uses_alpha && !pt.slot_alpha[slot]) return JXLHIP_ERR_INVALID_ARGUMENT;  // (the reference frame kept no alpha plane)
-    if (uint64_t(q[4]) + q[2] > pt.slot_w[slot] || uint64_t(q[5]) + q[3] > pt.slot_h[slot]) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (uint64_t(q[0]) + q[2] > xlimit || uint64_t(q[1]) + q[3] > ylimit) return JXLHIP_ERR_INVALID_ARGUMENT;
-  }
-  for (uint32_t y = 0; y < ysize; y++)
-    for (uint32_t i = pt.row_start[y]; i < pt.row_start[y + 1]; i++) {
-      if (pt.row_list[i] >= pt.num_positions) return JXLHIP_ERR_INVALID_ARGUMENT;
-      const uint32_t* q = pt.records + size_t(pt.row_list[i]) * 8;
-      if (y < q[1] || y >= q[1] + q[3]) return JXLHIP_ERR_INVALID_ARGUMENT;  // (the row is one of the patch's rows)
-    }
-  if ((r = Upload(c, c->pat_rec, pt.records, size_t(pt.num_positions) * 32))) return r;
-  if ((r = Upload(c, c->pat_row_start, pt.row_start, (size_t(ysize) + 1) * 4))) return r;
-  if ((r = Upload(c, c->pat_row_list, pt.row_list, std::max<size_t>(4, size_t(pt.num_row_entries) * 4)))) return r;
-  c->pat_uses_alpha = pt.uses_alpha != 0;
+  if (!pt.num_positions) return;
   c->pat_premultiplied = pt.premultiplied != 0;
   for (int i = 0; i < 4; i++) {
     c->pat_src_alpha[i] = pt.slot_alpha[i];
@@ -790,341 +782,198 @@ static int UploadPatches(JxlHipContext* c, const JxlHipPatches& pt, uint32_t ysi
     c->pat_src_w[i] = pt.slot_w[i];
     c->pat_src_h[i] = pt.slot_h[i];
   }
-  c->pat_positions = pt.num_positions;
+}
+// The draw cache of a Modular frame's splines / its patch dictionary to the device, checked like a VarDCT frame's.
+static int UploadSplines(JxlHipContext* c, const JxlHipSplines& sp, uint32_t ysize) {
+  c->spl_segments = 0;
+  int r = upload::CheckSplines(sp, ysize);
+  if (r) return r;
+  PlainUploader up{c};
+  upload::VisitSplineTables(*c, sp, ysize, up);
+  if (!up.r) AdoptSplines(c, sp);
+  return up.r;
+}
+static int UploadPatches(JxlHipContext* c, const JxlHipPatches& pt, uint32_t ysize, uint32_t xlimit, uint32_t ylimit) {
+  AdoptPatches(c, JxlHipPatches{});
+  int r = upload::CheckPatches(pt, ysize, xlimit, ylimit);
+  if (r) return r;
+  PlainUploader up{c};
+  upload::VisitPatchTables(*c, pt, ysize, up);
+  if (!up.r) AdoptPatches(c, pt);
+  return up.r;
+}
+
+// -------------------------------------------------------------------------------------------------- frame upload
+static upload::UploadOptions OptionsOf(const JxlHipContext* c) {
+  upload::UploadOptions o;
+  o.band_halo = c->band_halo;
+  o.keep_filtered = c->keep_filtered;
+  o.keep_upsampled = c->keep_upsampled;
+  o.out_type = c->out_type;
+  o.out_nc = c->out_nc;
+  o.out_bits = c->out_bits;
+  o.out_swap = c->out_swap;
+  o.out_orient = c->out_orient;
+  o.have_alpha = c->have_alpha;
+  o.alpha_capacity = c->alpha.cap;
+  o.section_entropy = SectionEntropyForced();
+  o.no_lane_prefix = EnvInt("JXLHIP_NO_LANE_PREFIX", 0) != 0;
+  return o;
+}
+
+// Which kernel decodes the frame's AC sections (stays beside the kernels: LanesLdsLayout is the lane kernel's own).
+// Frames whose tables fit LDS are decoded by the lane-parallel kernel into scan order (its packed block records hold the
+// block contexts in 4 bits each): single-pass frames hand that layout to the transforms (scan_order), progressive frames
+// decode every pass into its own buffer and k_merge_passes sums them (lane_multi).
+struct EntropyRoute {
+  bool generic, any_lz77, lane_prefix, lanes, scan_order, lane_multi, alias_lds;
+  uint32_t lds_ctx_bytes, lds_alias_bytes;
+};
+static EntropyRoute EntropyRouteOf(const JxlHipFrameDesc& d, const upload::UploadOptions& o) {
+  EntropyRoute e = {};
+  const uint32_t nctx = d.num_block_ctxs * 495;
+  size_t alias_bytes_max = 0;
+  bool all_prefix = true;
+  for (uint32_t p = 0; p < d.num_passes; p++) {
+    const JxlHipPassDesc& s = d.passes[p];
+    e.generic = e.generic || s.use_prefix || s.lz77;
+    e.any_lz77 = e.any_lz77 || s.lz77;
+    all_prefix = all_prefix && s.use_prefix;
+    alias_bytes_max = std::max(alias_bytes_max, upload::AliasBytes(s));
+  }
+  e.lds_ctx_bytes = (nctx + 16 + 15) & ~15u;
+  e.alias_lds = e.lds_ctx_bytes + alias_bytes_max + 1024 + 4 * 5120 <= kLdsBudget;
+  e.lds_alias_bytes = e.alias_lds ? uint32_t((alias_bytes_max + 15) & ~size_t(15)) : 0;
+  e.lane_prefix = all_prefix && !e.any_lz77 && !o.no_lane_prefix;
+  e.lanes = !o.section_entropy && d.num_block_ctxs <= 16 && d.num_passes <= 8 && (!e.generic || e.lane_prefix);
+  for (uint32_t p = 0; e.lanes && p < d.num_passes; p++)  // (alias tables that do not fit LDS are read in place)
+    e.lanes = jxlhip::LanesLdsLayout(1, nctx, d.passes[p].num_clusters, d.passes[p].log_alpha, kLanesAdmitWaves, 64, false, e.lane_prefix).total <= kLdsBudget;
+  if (!e.lanes) e.lane_prefix = false;
+  e.scan_order = e.lanes && d.num_passes == 1;
+  e.lane_multi = e.lanes && d.num_passes > 1;
+  return e;
+}
+
+// The frame's table list: what the descriptor gives (upload::VisitFrameTables) and the two parameter tables the entropy
+// kernels read from device memory, which hold device addresses and are filled once every buffer has one.
+template <typename V>
+static void VisitTables(JxlHipContext* c, const JxlHipFrameDesc& d, const upload::Plan& P, V& v) {
+  upload::VisitFrameTables(*c, d, P, v);
+  v.build(c->passes_dev, size_t(d.num_passes) * sizeof(jxlhip::PassDev), [](void*) {});
+  v.build(c->ep_dev, sizeof(jxlhip::EntropyParams), [](void*) {});
+}
+
+// What the context remembers of the frame beside its tables.
+static void AdoptFrame(JxlHipContext* c, const JxlHipFrameDesc& d, const upload::Plan& P, const EntropyRoute& E) {
+  const upload::Geometry& g = P.g;
+  c->cs = g.cs;
+  c->xs = d.xsize; c->ys = d.ysize; c->xb = d.xsize_blocks; c->yb = d.ysize_blocks;
+  c->xg = d.xsize_groups; c->ng = d.num_groups; c->np = d.num_passes;
+  c->nblocks = d.num_blocks;
+  c->xp = c->xb * 8; c->yp = c->yb * 8;
+  c->ups = g.ups; c->oxs = g.oxs; c->oys = g.oys;
+  c->band_y0 = g.band_y0; c->band_y1 = g.band_y1; c->ext_y0 = g.ext_y0; c->ext_y1 = g.ext_y1;
+  upload::BuildGroupLists(d, g, &c->group_list, &c->absent_groups, &c->absent_blocks, &c->absent_sections);
+  c->coef_bits = d.coef_bits;
+  c->gab = d.gab; c->epf_iters = d.epf_iters;
+  c->epf_pass0 = d.epf_pass0_sigma_scale;
+  c->epf_pass2 = d.epf_pass2_sigma_scale;
+  c->epf_border = d.epf_border_sad_mul;
+  c->sec_size_host.assign(d.section_size, d.section_size + g.nsec);
+  c->sec_sel_host.resize(g.nsec);
+  upload::BuildSelectors(d, c->sec_sel_host.data());
+  c->pass_clusters.resize(d.num_passes);
+  c->pass_log_alpha.resize(d.num_passes);
+  for (uint32_t p = 0; p < d.num_passes; p++) {
+    c->pass_clusters[p] = d.passes[p].num_clusters;
+    c->pass_log_alpha[p] = d.passes[p].log_alpha;
+  }
+  if (c->pass_bufs.size() < d.num_passes) c->pass_bufs.resize(d.num_passes);
+  memcpy(c->list_begin, P.list_begin, sizeof(c->list_begin));
+  memcpy(c->list_count, P.list_count, sizeof(c->list_count));
+  c->plane_bytes = size_t(c->xp) * c->yp * 3 * 4;
+  c->color_out = P.px.color_out;
+  c->gray8_fast = P.px.gray8_fast;
+  c->ups_kept = P.px.ups_kept;
+  c->ct = d.color_target ? *d.color_target : JxlHipColorTarget{};
+  c->has_noise = d.has_noise != 0;
+  if (c->has_noise) {
+    memcpy(c->noise_lut, d.noise_lut, sizeof(c->noise_lut));
+    c->noise_seed[0] = d.noise_frame_index[0];
+    c->noise_seed[1] = d.noise_frame_index[1];
+    c->noise_ytox = d.base_corr_x;
+    c->noise_ytob = d.base_corr_b;
+  }
+  AdoptSplines(c, d.splines);
+  AdoptPatches(c, d.patches);
+  c->generic_codec = E.generic;
+  c->lane_prefix = E.lane_prefix;
+  c->lanes = E.lanes;
+  c->scan_order = E.scan_order;
+  c->lane_multi = E.lane_multi;
+  c->alias_lds = E.alias_lds;
+  c->lds_entropy = E.lds_ctx_bytes + E.lds_alias_bytes + 3072;
+  if (c->scan_order) {  // for jxlhip_download("coeffs")
+    c->blocks_host.assign(d.blocks, d.blocks + d.num_blocks);
+    c->gbb_host.assign(d.group_block_begin, d.group_block_begin + d.num_groups + 1);
+    c->orders_host.assign(d.passes[0].orders, d.passes[0].orders + d.passes[0].orders_size);
+    memcpy(c->order_offset_host, d.passes[0].order_offset, sizeof(c->order_offset_host));
+  }
+  c->ev_valid[0] = c->ev_valid[1] = c->ev_valid[2] = false;
+  c->generation++;
+}
+
+// The buffers the kernels write: allocated here (launch functions never allocate), cleared where a launch may leave them.
+static int EnsureWorkBuffers(JxlHipContext* c, const JxlHipFrameDesc& d, const upload::Plan& P, const EntropyRoute& E) {
+  int r;
+  const size_t nblk = P.g.nblk;
+  if (d.dc_device) {  // the planes of a DC frame decoded earlier (kUseDcFrame): used where they are
+    if (!c->dc.view) c->dc.Free();
+    c->dc.p = const_cast<float*>(d.dc_device);
+    c->dc.cap = nblk * 3 * 4;
+    c->dc.view = true;
+  } else {  // (the DC kernels' outputs are allocations of their own, not views of the blob)
+    if (P.dc.smooth && P.dc.dequant && (r = c->dc_raw.Ensure(nblk * 3 * 4))) return r;
+    if ((P.dc.smooth || P.dc.dequant) && (r = c->dc.Ensure(nblk * 3 * 4))) return r;
+  }
+  if (!d.inv_sigma && (r = c->inv_sigma.Ensure(nblk * 4))) return r;  // (computed here, or no EPF: never read)
+  // (progressive frames: the natural-layout buffer + one scan-order buffer per pass for the lane kernel)
+  const size_t coef_bytes = size_t(d.num_groups) * 3 * 65536 * (d.coef_bits / 8);
+  // (+ 64 bytes: a lane of the entropy kernel that decodes a CORRUPT section may write up to three coefficients past the
+  // last scan position of a block before it is stopped, jxl_hip_lanes_trip.inc: past the buffer for the very last block)
+  if ((r = c->coeffs.Ensure(coef_bytes * (d.num_passes > 1 ? d.num_passes + 1 : 1) + 64))) return r;
+  if ((r = c->errors.Ensure(size_t(d.num_groups) * 4))) return r;
+  HIP_TRY(hipMemsetAsync(c->errors.p, 0, size_t(d.num_groups) * 4, c->stream));  // groups outside a band stay clean
+  if (!c->plane_lender && (r = c->plane[0].Ensure(c->plane_bytes))) return r;
+  // (an upsampled frame's noise is generated and added at the IMAGE's resolution, behind the upsampling:
+  // dec_cache.cc:206-216, dec_group.cc PrepareNoiseInput: one generator per 256 x 256 square of the image)
+  if (c->has_noise && (r = c->noise.Ensure(size_t(c->oxs) * c->oys * 3 * 4))) return r;
+  if (((c->has_noise && c->ups != 1) || c->ups_kept) && (r = c->ups_planes.Ensure(size_t((c->oxs + 7) & ~7u) * c->oys * 3 * 4))) return r;
+  if (P.px.plane1 && (r = c->plane[1].Ensure(c->plane_bytes))) return r;
+  if ((r = c->rgb.Ensure(size_t(c->oxs) * c->oys * OutPixelBytes(c)))) return r;
+  uint32_t big = 0;  // the largest transforms go through scratch planes, 32 varblocks at a time
+  for (int s = 21; s < 27; s++) big = std::max(big, P.list_count[s]);
+  if (big && (r = c->scratch.Ensure(size_t(std::min(big, 32u)) * 3 * 2 * 65536 * 4))) return r;
+  if (E.any_lz77 && (r = c->lz_window.Ensure(size_t(d.num_groups) * jxlhip::kLzWindow * 4))) return r;
+  if ((r = c->sec_end.Ensure(P.g.nsec * 4))) return r;
+  HIP_TRY(hipMemsetAsync(c->sec_end.p, 0, P.g.nsec * 4, c->stream));
+  if ((r = c->kend.Ensure(size_t(d.num_blocks ? d.num_blocks : 1) * 3 * 4 * d.num_passes))) return r;
   return 0;
 }
 
-int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
-  if (!c || !d) return JXLHIP_ERR_INVALID_ARGUMENT;
-  // measurement aid: JXLHIP_UPLOAD_PROF=1 prints where the host time of an upload goes (microseconds per phase)
-  const bool prof = EnvInt("JXLHIP_UPLOAD_PROF", 0) != 0;
-  std::chrono::steady_clock::time_point tp0 = std::chrono::steady_clock::now();
-  std::string prof_line;
-  auto lap = [&](const char* what) {
-    if (!prof) return;
-    const auto now = std::chrono::steady_clock::now();
-    prof_line += std::string(what) + " " + std::to_string(std::chrono::duration_cast<std::chrono::microseconds>(now - tp0).count()) + "  ";
-    tp0 = now;
-  };
-  if (!d->xsize || !d->ysize || !d->num_groups || !d->num_passes || d->num_passes > 11) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (d->coef_bits != 16 && d->coef_bits != 32) return JXLHIP_ERR_INVALID_ARGUMENT;
-  uint32_t cs = 0, cs_maxh = 0, cs_maxv = 0;
-  for (int ch = 0; ch < 3; ch++) {
-    if (d->chroma_hshift[ch] > 1 || d->chroma_vshift[ch] > 1) return JXLHIP_ERR_INVALID_ARGUMENT;
-    cs |= uint32_t(d->chroma_hshift[ch]) << (2 * ch) | uint32_t(d->chroma_vshift[ch]) << (2 * ch + 1);
-    cs_maxh |= d->chroma_hshift[ch];
-    cs_maxv |= d->chroma_vshift[ch];
-  }
-  // (frame_dimensions.h:43-44: whole MCUs of a chroma-subsampled frame)
-  if (d->xsize_blocks != ((d->xsize + (8u << cs_maxh) - 1) / (8u << cs_maxh)) << cs_maxh ||
-      d->ysize_blocks != ((d->ysize + (8u << cs_maxv) - 1) / (8u << cs_maxv)) << cs_maxv)
-    return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (cs) {
-    // no adaptive DC smoothing (dec_frame.cc:206-212), no DC frame behind it, every varblock one block (checked below);
-    // a band whose neighbours' rows arrive as halos cannot upsample its edge rows: the other band form works
-    if (d->dc_smoothing || d->dc_device || d->linear_output != 2) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (c->band_halo && (d->band_group_row_begin | d->band_group_row_end)) return JXLHIP_ERR_UNSUPPORTED;
-  }
-  if (d->num_groups != d->xsize_groups * ((d->ysize + 255) / 256) || d->xsize_groups != (d->xsize + 255) / 256)
-    return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (d->num_qf_thresholds > 15 || d->num_block_ctxs == 0 || d->num_block_ctxs > 16 || d->num_dc_ctxs == 0)
-    return JXLHIP_ERR_INVALID_ARGUMENT;
-  HIP_TRY(hipSetDevice(c->device));
-  {
-    int pw = ApplyPendingWait(c);
-    if (pw) return pw;
-    if ((pw = StageReset(c))) return pw;
-    // the tables are overwritten from the copy stream: whatever still reads the old ones has to be finished
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
-  }
-  c->have_frame = false;
-  c->cs = cs;
-  c->xs = d->xsize; c->ys = d->ysize; c->xb = d->xsize_blocks; c->yb = d->ysize_blocks;
-  c->xg = d->xsize_groups; c->ng = d->num_groups; c->np = d->num_passes;
-  c->nblocks = d->num_blocks;
-  c->xp = c->xb * 8; c->yp = c->yb * 8;
-  c->ups = d->upsampling > 1 ? d->upsampling : 1;
-  c->oxs = c->ups == 1 ? d->xsize : d->out_xsize;
-  c->oys = c->ups == 1 ? d->ysize : d->out_ysize;
-  if (c->ups != 1) {
-    if ((c->ups != 2 && c->ups != 4 && c->ups != 8) || !d->upsampling_kernel || (d->band_group_row_begin | d->band_group_row_end) ||
-        (c->oxs + c->ups - 1) / c->ups != d->xsize || (c->oys + c->ups - 1) / c->ups != d->ysize)
-      return JXLHIP_ERR_INVALID_ARGUMENT;
-  }
-  uint32_t ext_row0 = 0, ext_row1 = d->num_groups / d->xsize_groups;  // group rows to entropy-decode and transform
-  {
-    const uint32_t yg = d->num_groups / d->xsize_groups;
-    uint32_t rb = d->band_group_row_begin, re = d->band_group_row_end;
-    if (rb == 0 && re == 0) re = yg;
-    if (rb >= re || re > yg) return JXLHIP_ERR_INVALID_ARGUMENT;
-    ext_row0 = (rb && !c->band_halo) ? rb - 1 : rb;
-    ext_row1 = (re < yg && !c->band_halo) ? re + 1 : re;
-    c->band_y0 = rb * 256;
-    c->ext_y0 = ext_row0 * 256;
-    c->ext_y1 = ext_row1 * 256 < d->ysize ? ext_row1 * 256 : d->ysize;
-    c->band_y1 = re * 256 < d->ysize ? re * 256 : d->ysize;
-    c->group_list.clear();
-    c->absent_groups.clear();
-    c->absent_sections.clear();
-    for (uint32_t g = ext_row0 * d->xsize_groups; g < ext_row1 * d->xsize_groups; g++) {
-      if (d->group_absent && d->group_absent[g]) {
-        for (uint32_t p = 0; p < d->num_passes; p++)
-          if (d->section_size[size_t(p) * d->num_groups + g]) return JXLHIP_ERR_INVALID_ARGUMENT;
-        c->absent_groups.push_back(g);
-      } else {
-        c->group_list.push_back(g);
-        // a partial frame's group is drawn from its leading passes (dec_frame.cc:620-680): the missing ones have size 0,
-        // and once one is missing all later ones are
-        bool missing = false;
-        for (uint32_t p = 1; d->group_absent && p < d->num_passes; p++) {
-          const bool empty = d->section_size[size_t(p) * d->num_groups + g] == 0;
-          if (missing && !empty) return JXLHIP_ERR_INVALID_ARGUMENT;
-          missing = missing || empty;
-          if (empty) {
-            c->absent_sections.push_back(p);
-            c->absent_sections.push_back(d->group_block_begin[g]);
-            c->absent_sections.push_back(d->group_block_begin[g + 1] - d->group_block_begin[g]);
-          }
-        }
-      }
-    }
-  }
-  c->coef_bits = d->coef_bits;
-  c->gab = d->gab; c->epf_iters = d->epf_iters;
-  // ---- validate varblocks against the geometry (the kernels index with these)
-  {
-    uint32_t prev_end = 0;
-    for (uint32_t g = 0; g < d->num_groups; g++) {
-      const uint32_t b0 = d->group_block_begin[g], b1 = d->group_block_begin[g + 1];
-      if (b0 != prev_end || b1 < b0 || b1 > d->num_blocks) return JXLHIP_ERR_INVALID_ARGUMENT;
-      prev_end = b1;
-      uint32_t off = 0;
-      const uint32_t gx0 = (g % d->xsize_groups) * 32, gy0 = (g / d->xsize_groups) * 32;
-      for (uint32_t i = b0; i < b1; i++) {
-        const JxlHipVarBlock& v = d->blocks[i];
-        if (v.strategy >= 27 || v.qf == 0 || v.qf > 256 || v.quant_dc_ctx >= d->num_dc_ctxs) return JXLHIP_ERR_INVALID_ARGUMENT;
-        const uint32_t cx = jxlhip::kCoveredX[v.strategy], cy = jxlhip::kCoveredY[v.strategy];
-        if (v.bx < gx0 || v.by < gy0 || v.bx + cx > gx0 + 32 || v.by + cy > gy0 + 32 || v.bx + cx > d->xsize_blocks || v.by + cy > d->ysize_blocks)
-          return JXLHIP_ERR_INVALID_ARGUMENT;
-        if (v.coef_offset != off) return JXLHIP_ERR_INVALID_ARGUMENT;
-        if (cs && cx * cy != 1) return JXLHIP_ERR_INVALID_ARGUMENT;  // (dec_modular.cc:534-538)
-        // (so a subsampled group's varblocks are its blocks in raster order: the entropy stage finds the block at a
-        // channel's own column, whose quant field its block context takes, that many entries back in the row)
-        if (cs) {
-          const uint32_t gw = std::min<uint32_t>(32, d->xsize_blocks - gx0);
-          if (v.bx != gx0 + (i - b0) % gw || v.by != gy0 + (i - b0) / gw) return JXLHIP_ERR_INVALID_ARGUMENT;
-        }
-        off += 64u * cx * cy;
-        if (off > 65536) return JXLHIP_ERR_INVALID_ARGUMENT;
-      }
-    }
-    if (prev_end != d->num_blocks) return JXLHIP_ERR_INVALID_ARGUMENT;
-  }
-  lap("validate");
-  // ---- pack the AC sections at 16-byte aligned offsets
-  const size_t nsec = size_t(d->num_groups) * d->num_passes;
-  std::vector<uint32_t> sec_word(nsec), sec_size(nsec);
-  size_t total = 0;
-  for (size_t i = 0; i < nsec; i++) {
-    sec_word[i] = uint32_t(total / 4);
-    sec_size[i] = d->section_size[i];
-    total += (size_t(d->section_size[i]) + 15 + 4) & ~size_t(15);
-  }
-  int r;
-  {
-    // every table this upload places (each rounded up to the staging granule), generously
-    size_t bound = 65536;
-    auto add = [&](size_t bytes) { bound += (bytes + 16 + 127) & ~size_t(63); };
-    const size_t nblk_b = size_t(d->xsize_blocks) * d->ysize_blocks, ntiles_b = size_t((d->xsize_blocks + 7) / 8) * ((d->ysize_blocks + 7) / 8);
-    add(total + 256); add(nsec * 4); add(nsec * 4);
-    add(size_t(d->num_blocks) * sizeof(JxlHipVarBlock)); add((size_t(d->num_groups) + 1) * 4); add(d->block_ctx_lut_size);
-    add(size_t(d->dequant_floats) * 4); add(nblk_b * 12); add(nblk_b * 4); add(nblk_b); add(ntiles_b); add(ntiles_b); add(ntiles_b + 64);
-    for (uint32_t p = 0; p < d->num_passes; p++) {
-      const JxlHipPassDesc& q = d->passes[p];
-      if (q.num_clusters > 256 || (!q.use_prefix && q.log_alpha > 8)) return JXLHIP_ERR_INVALID_ARGUMENT;
-      add(q.ctx_map_size); add(q.use_prefix ? 0 : (size_t(q.num_clusters) << q.log_alpha) * 8); add(size_t(q.num_clusters) * 4);
-      add(q.use_prefix ? 0 : (size_t(q.num_clusters) << q.log_alpha) * 8);  // (the lane kernel's packed form)
-      add(size_t(q.orders_size) * 2); add(size_t(q.prefix_table_size) * 4); add(size_t(q.num_clusters) * 4);
-    }
-    add(size_t(d->num_passes) * sizeof(jxlhip::PassDev)); add(64 * 25 * 4); add((size_t(d->num_blocks) + 1) * 4);
-    add((size_t(d->num_blocks) + 1) * 16);
-    add((size_t(d->num_blocks) + 16) * 4); add(sizeof(jxlhip::EntropyParams)); add(size_t(d->dequant_floats) * 4);
-    add(size_t(d->splines.num_segments) * 32); add((size_t(d->ysize) + 1) * 4); add(size_t(d->splines.num_row_segments) * 4 + 16);
-    add(size_t(d->patches.num_positions) * 32); add((size_t(d->ysize) + 1) * 4); add(size_t(d->patches.num_row_entries) * 4 + 16);
-    if ((r = BlobBegin(c, bound))) return r;
-  }
-  struct BlobGuard {  // whatever the outcome, later uploads of other kinds see the plain mode
-    JxlHipContext* c;
-    ~BlobGuard() { c->blob_mode = false; }
-  } blob_guard{c};
-  {
-    uint8_t* packed = nullptr;  // (+ 256: the lane kernel prefetches up to 64 bytes past a section)
-    if ((r = StageAlloc(c, total + 256, reinterpret_cast<void**>(&packed)))) return r;
-    size_t end = 0;
-    for (size_t i = 0; i < nsec; i++) {
-      const size_t at = size_t(sec_word[i]) * 4;
-      memset(packed + end, 0, at - end);
-      memcpy(packed + at, d->codestream + d->section_offset[i], d->section_size[i]);
-      end = at + d->section_size[i];
-    }
-    memset(packed + end, 0, total + 256 - end);
-    if ((r = UploadStaged(c, c->sections, packed, total + 256))) return r;
-  }
-  if ((r = Upload(c, c->sec_word, sec_word.data(), nsec * 4))) return r;
-  if ((r = Upload(c, c->sec_size, sec_size.data(), nsec * 4))) return r;
-  c->sec_size_host = sec_size;
-  {
-    // histogram selector of every first-pass section: its first ceil(log2(num_histograms)) bits (dec_group.cc:594-610)
-    uint32_t hb = 0;
-    while ((1u << hb) < d->num_histograms) hb++;
-    c->sec_sel_host.assign(nsec, 0);
-    for (size_t g = 0; hb && g < nsec; g++) {  // [pass * num_groups + group]
-      const uint8_t* p = d->codestream + d->section_offset[g];
-      const uint32_t bit0 = g == 0 ? d->first_section_bit_offset : 0;
-      uint64_t v = 0;
-      for (uint32_t b = 0; b < 8 && b < d->section_size[g]; b++) v |= uint64_t(p[b]) << (8 * b);
-      c->sec_sel_host[g] = uint32_t((v >> bit0) & ((1u << hb) - 1));
-    }
-  }
-  c->pass_clusters.assign(d->num_passes, 0);
-  c->pass_log_alpha.assign(d->num_passes, 0);
-  lap("sections");
-  if ((r = Upload(c, c->blocks, d->blocks, size_t(d->num_blocks) * sizeof(JxlHipVarBlock)))) return r;
-  if ((r = Upload(c, c->gbb, d->group_block_begin, (size_t(d->num_groups) + 1) * 4))) return r;
-  if ((r = Upload(c, c->bctx_lut, d->block_ctx_lut, d->block_ctx_lut_size))) return r;
-  if ((r = Upload(c, c->dequant, d->dequant, size_t(d->dequant_floats) * 4))) return r;
-  const size_t nblk = size_t(c->xb) * c->yb;
-  // DC image and 1 / sigma: final as handed over, or finished on the device (jxl_hip_dc.h) behind the table copy
-  jxlhip::DcSmoothParams smooth_p;
-  jxlhip::SigmaParams sigma_p;
-  const bool dev_smooth = d->dc_smoothing != 0 && c->xb > 2 && c->yb > 2;  // (compressed_dc.cc:134: smaller images are left alone)
-  const bool dev_sigma = !d->inv_sigma && d->epf_iters > 0;
-  jxlhip::DcDequantParams dequant_p;
-  const bool dev_dequant = d->dc_quantised != nullptr && !d->dc_device;
-  if ((!d->dc && !d->dc_device && !d->dc_quantised) || (dev_sigma && !d->sharpness)) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (dev_dequant) {
-    for (int ch = 0; ch < 3; ch++)
-      if (!(d->dc_step[ch] > 0.0f)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    const uint32_t xdg = (c->xb + 255) / 256, ydg = (c->yb + 255) / 256;
-    if ((r = Upload(c, c->dc_q, d->dc_quantised, nblk * 3 * 4))) return r;
-    if (d->dc_extra_precision && (r = Upload(c, c->dc_ep, d->dc_extra_precision, size_t(xdg) * ydg))) return r;
-    dequant_p.q = c->dc_q.as<int32_t>();
-    dequant_p.xs = c->xb;
-    dequant_p.ys = c->yb;
-    dequant_p.xgroups = xdg;
-    dequant_p.extra_precision = d->dc_extra_precision ? c->dc_ep.as<uint8_t>() : nullptr;
-    for (int ch = 0; ch < 3; ch++) dequant_p.step[ch] = d->dc_step[ch];
-    dequant_p.cfl_x = d->dc_cfl_x;
-    dequant_p.cfl_b = d->dc_cfl_b;
-    dequant_p.cs = cs;
-  }
-  if (d->dc_device) {  // the planes of a DC frame decoded earlier (kUseDcFrame): used where they are, never smoothed
-    if (!c->dc.view) c->dc.Free();
-    c->dc.p = const_cast<float*>(d->dc_device);
-    c->dc.cap = nblk * 3 * 4;
-    c->dc.view = true;
-  } else if (dev_smooth) {
-    for (int ch = 0; ch < 3; ch++)
-      if (!(d->dc_step[ch] > 0.0f)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (dev_dequant) {  // (the dequantised planes are a kernel's output: an allocation of their own, not a view of the blob)
-      if ((r = c->dc_raw.Ensure(nblk * 3 * 4))) return r;
-      dequant_p.out = c->dc_raw.as<float>();
-    } else if ((r = Upload(c, c->dc_raw, d->dc, nblk * 3 * 4))) {
-      return r;
-    }
-    if ((r = c->dc.Ensure(nblk * 3 * 4))) return r;
-    smooth_p.in = c->dc_raw.as<float>();
-    smooth_p.out = c->dc.as<float>();
-    smooth_p.xs = c->xb;
-    smooth_p.ys = c->yb;
-    for (int ch = 0; ch < 3; ch++) smooth_p.step[ch] = d->dc_step[ch];
-  } else if (dev_dequant) {
-    if ((r = c->dc.Ensure(nblk * 3 * 4))) return r;
-    dequant_p.out = c->dc.as<float>();
-  } else if ((r = Upload(c, c->dc, d->dc, nblk * 3 * 4))) {
-    return r;
-  }
-  if (dev_sigma) {
-    if (!(d->quant_scale > 0.0f)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if ((r = Upload(c, c->sharp, d->sharpness, nblk))) return r;
-    if ((r = c->inv_sigma.Ensure(nblk * 4))) return r;
-    sigma_p.blocks = c->blocks.as<JxlHipVarBlock>();
-    sigma_p.num_blocks = d->num_blocks;
-    sigma_p.xb = c->xb;
-    sigma_p.sharpness = c->sharp.as<uint8_t>();
-    sigma_p.inv_sigma = c->inv_sigma.as<float>();
-    sigma_p.quant_scale = d->quant_scale;
-    sigma_p.epf_quant_mul = d->epf_quant_mul;
-    memcpy(sigma_p.sharp_lut, d->epf_sharp_lut, sizeof(sigma_p.sharp_lut));
-  } else if (d->inv_sigma) {
-    if ((r = Upload(c, c->inv_sigma, d->inv_sigma, nblk * 4))) return r;
-  } else if ((r = c->inv_sigma.Ensure(nblk * 4))) {  // (no EPF: never read)
-    return r;
-  }
-  const size_t ntiles = size_t((c->xb + 7) / 8) * ((c->yb + 7) / 8);
-  if ((r = Upload(c, c->ytox, d->ytox, ntiles))) return r;
-  if ((r = Upload(c, c->ytob, d->ytob, ntiles))) return r;
-  lap("planes");
-  // ---- per-pass tables
-  if (c->pass_bufs.size() < d->num_passes) c->pass_bufs.resize(d->num_passes);
-  std::vector<jxlhip::PassDev> pd(d->num_passes);
-  const uint32_t nctx = d->num_block_ctxs * 495;
-  size_t alias_bytes_max = 0;
-  bool generic = false, any_lz77 = false;
-  for (uint32_t p = 0; p < d->num_passes; p++) {
-    const JxlHipPassDesc& s = d->passes[p];
-    if (s.num_clusters == 0 || s.num_clusters > 256) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (!s.use_prefix && (s.log_alpha < 5 || s.log_alpha > 8)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (s.use_prefix) {  // every table index the kernel can form must be inside the table
-      if (!s.prefix_offset || !s.prefix_table) return JXLHIP_ERR_INVALID_ARGUMENT;
-      for (uint32_t i = 0; i < s.num_clusters; i++) {
-        if (!ValidPrefixTables(s.prefix_offset[i], s.prefix_table, s.prefix_table_size)) return JXLHIP_ERR_INVALID_ARGUMENT;
-      }
-    }
-    if (s.lz77 && (s.lz_dist_ctx >= s.num_clusters || s.lz_min_length == 0)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    generic = generic || s.use_prefix || s.lz77;
-    if (s.ctx_map_size < size_t(d->num_histograms) * nctx + 16) return JXLHIP_ERR_INVALID_ARGUMENT;
-    for (uint32_t i = 0; i < s.ctx_map_size; i++)
-      if (s.ctx_map[i] >= s.num_clusters) return JXLHIP_ERR_INVALID_ARGUMENT;
-    PassBufs& pb = c->pass_bufs[p];
-    const size_t alias_bytes = s.use_prefix ? 0 : (size_t(s.num_clusters) << s.log_alpha) * 8;
-    alias_bytes_max = alias_bytes > alias_bytes_max ? alias_bytes : alias_bytes_max;
-    if ((r = Upload(c, pb.ctx_map, s.ctx_map, s.ctx_map_size))) return r;
-    if ((r = Upload(c, pb.alias, s.alias, alias_bytes))) return r;
-    {
-      // alias entry {cutoff u8, right u8, freq0 u16 | offsets1 u16, freq1 u16} -> the lane kernel's form
-      //   x = (freq0 - 1) & 0xFFF | uint config << 12 | cutoff << 24   taken when pos <  cutoff: symbol = slot, offset = pos
-      //   y = (freq1 - 1) & 0xFFF | offsets1 << 12 | right << 24        taken when pos >= cutoff
-      // (uint config of the entry's cluster: split_exponent | msb_in_token << 4 | lsb_in_token << 8, validated below)
-      void* st = nullptr;
-      if ((r = StageAlloc(c, alias_bytes ? alias_bytes : 16, &st))) return r;
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(s.alias);
-      uint32_t* dst = static_cast<uint32_t*>(st);
-      for (size_t i = 0; i < alias_bytes / 8; i++) {
-        const uint32_t ex = src[2 * i], ey = src[2 * i + 1];
-        const uint32_t cutoff = ex & 0xFF, right = (ex >> 8) & 0xFF, freq0 = ex >> 16, offs1 = ey & 0xFFFF, freq1 = ey >> 16;
-        const uint32_t uc = s.uint_cfg[i >> s.log_alpha];
-        const uint32_t cfg12 = (uc & 15u) | (((uc >> 8) & 15u) << 4) | (((uc >> 16) & 15u) << 8);
-        dst[2 * i] = ((freq0 - 1) & 0xFFFu) | (cfg12 << 12) | (cutoff << 24);
-        dst[2 * i + 1] = ((freq1 - 1) & 0xFFFu) | ((offs1 & 0xFFFu) << 12) | (right << 24);
-      }
-      if ((r = UploadStaged(c, pb.alias_packed, st, alias_bytes))) return r;
-    }
-    if ((r = Upload(c, pb.cfg, s.uint_cfg, size_t(s.num_clusters) * 4))) return r;
-    if ((r = Upload(c, pb.orders, s.orders, size_t(s.orders_size) * 2))) return r;
+// The entropy kernels' parameters: c->ep, its device copy and the per-pass table, assembled where they were placed.
+static void FillEntropyParams(JxlHipContext* c, const JxlHipFrameDesc& d, const upload::Plan& P, const EntropyRoute& E) {
+  jxlhip::PassDev* pd = Staged<jxlhip::PassDev>(c, c->passes_dev);
+  memset(pd, 0, size_t(d.num_passes) * sizeof(jxlhip::PassDev));
+  for (uint32_t p = 0; p < d.num_passes; p++) {
+    const JxlHipPassDesc& s = d.passes[p];
+    const PassBufs& pb = c->pass_bufs[p];
     pd[p].ctx_map = pb.ctx_map.as<uint8_t>();
     pd[p].alias = pb.alias.as<uint2>();
     pd[p].alias_packed = pb.alias_packed.as<uint2>();
     pd[p].cfg = pb.cfg.as<uint32_t>();
     pd[p].orders = pb.orders.as<uint16_t>();
     memcpy(pd[p].order_offset, s.order_offset, sizeof(s.order_offset));
-    for (uint32_t i = 0; i < s.num_clusters; i++) {  // hybrid-uint configs: split_exponent, msb_in_token, lsb_in_token
-      const uint32_t se = s.uint_cfg[i] & 0xFF, msb = (s.uint_cfg[i] >> 8) & 0xFF, lsb = (s.uint_cfg[i] >> 16) & 0xFF;
-      if (se > (s.use_prefix ? 15u : s.log_alpha) || msb > se || lsb > se - msb) return JXLHIP_ERR_INVALID_ARGUMENT;
-    }
-    if ((r = Upload(c, pb.ptable, s.prefix_table, s.use_prefix ? size_t(s.prefix_table_size) * 4 : 0))) return r;
-    if ((r = Upload(c, pb.poffset, s.prefix_offset, s.use_prefix ? size_t(s.num_clusters) * 4 : 0))) return r;
     pd[p].use_prefix = s.use_prefix ? 1 : 0;
     pd[p].lz77 = s.lz77 ? 1 : 0;
     pd[p].lz_min_symbol = s.lz_min_symbol;
@@ -1133,279 +982,69 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
     pd[p].lz_dist_ctx = s.lz_dist_ctx;
     pd[p].prefix_table = pb.ptable.as<uint32_t>();
     pd[p].prefix_offset = pb.poffset.as<uint32_t>();
-    if (s.lz77) any_lz77 = true;
     pd[p].log_alpha = s.log_alpha;
-    c->pass_clusters[p] = s.num_clusters;
-    c->pass_log_alpha[p] = s.log_alpha;
     pd[p].num_clusters = s.num_clusters;
     pd[p].shift = s.shift;
     pd[p].alias_lds = 0;
   }
-  if ((r = Upload(c, c->passes_dev, pd.data(), pd.size() * sizeof(jxlhip::PassDev)))) return r;
-  lap("tables");
-  // ---- work buffers
-  // (progressive frames: the natural-layout buffer + one scan-order buffer per pass for the lane kernel)
-  const size_t coef_bytes = size_t(d->num_groups) * 3 * 65536 * (d->coef_bits / 8);
-  // (+ 64 bytes: a lane of the entropy kernel that decodes a CORRUPT section may write up to three coefficients past the
-  // last scan position of a block before it is stopped, jxl_hip_lanes_trip.inc: past the buffer for the very last block)
-  if ((r = c->coeffs.Ensure(coef_bytes * (d->num_passes > 1 ? d->num_passes + 1 : 1) + 64))) return r;
-  if ((r = c->errors.Ensure(size_t(d->num_groups) * 4))) return r;
-  HIP_TRY(hipMemsetAsync(c->errors.p, 0, size_t(d->num_groups) * 4, c->stream));  // groups outside a band stay clean
-  const size_t plane_bytes = size_t(c->xp) * c->yp * 3 * 4;
-  c->plane_bytes = plane_bytes;
-  if (!c->plane_lender && (r = c->plane[0].Ensure(plane_bytes))) return r;
-  // pixels: RGB8 from every filter kernel, RGB f32 from the row-streaming one; any other format from the generic writer
-  // (k_color_out on the filtered planes, or k_upsample_color)
-  // (one 8-bit channel: from the row-streaming kernel's one-channel form when the frame ends in sRGB; the filtered planes
-  // are not kept beside it)
-  const bool rows_kernel = c->ups == 1 && (c->epf_iters == 1 || c->epf_iters == 2);
-#ifdef JXLHIP_NO_GRAY8_ROWS  // (scripts/measure_grey_xyb.py: the comparison build, one 8-bit channel from the generic writer)
-  const bool gray8 = false;
-#else
-  const bool gray8 = OutIsGray8(c) && rows_kernel && d->linear_output == 0 && !c->keep_filtered;
-#endif
-  c->color_out = !OutIsRgb8(c) && !gray8 && !(OutIsRgbF32(c) && rows_kernel);
-  if (c->out_orient) c->color_out = true;  // (the oriented layout is written by the generic writer)
-  // frames of images that are not XYB encoded (linear_output 2 = YCbCr, 3 = no colour transform): the colour stage is
-  // XybToRgb's other branches, which only the generic writers take
-  if (d->linear_output < 0 || d->linear_output > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (d->linear_output >= 2) c->color_out = true;
-  // an output encoding other than (linear) sRGB (jxl_hip_color.h): the frame's matrix gives linear RGB, the generic writer the rest
-  c->ct = d->color_target ? *d->color_target : JxlHipColorTarget{};
-  if (c->ct.tf > JXLHIP_TF_GAMMA || c->ct.tone > JXLHIP_TONE_HLG_OOTF) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->ct.tf) {
-    if (d->linear_output != 1) return JXLHIP_ERR_INVALID_ARGUMENT;
-    c->color_out = true;
-  }
-  // noise is added to the filtered planes between the filter launch and the colour conversion
-  c->has_noise = d->has_noise != 0;
-  if (c->has_noise) {
-    c->color_out = true;
-    memcpy(c->noise_lut, d->noise_lut, sizeof(c->noise_lut));
-    c->noise_seed[0] = d->noise_frame_index[0];
-    c->noise_seed[1] = d->noise_frame_index[1];
-    c->noise_ytox = d->base_corr_x;
-    c->noise_ytob = d->base_corr_b;
-    // (an upsampled frame's noise is generated and added at the IMAGE's resolution, behind the upsampling:
-    // dec_cache.cc:206-216, dec_group.cc PrepareNoiseInput: one generator per 256 x 256 square of the image)
-    const size_t nxs = c->ups == 1 ? c->xs : c->oxs, nys = c->ups == 1 ? c->ys : c->oys;
-    if ((r = c->noise.Ensure(nxs * nys * 3 * 4))) return r;
-    if (c->ups != 1 && (r = c->ups_planes.Ensure(size_t((c->oxs + 7) & ~7u) * c->oys * 3 * 4))) return r;
-  }
-  // (tests: the upsampled planes are kept, so the frame takes the route of a noisy upsampled frame without the noise)
-  c->ups_kept = c->keep_upsampled && c->ups != 1;
-  if (c->ups_kept) {
-    c->color_out = true;
-    if ((r = c->ups_planes.Ensure(size_t((c->oxs + 7) & ~7u) * c->oys * 3 * 4))) return r;
-  }
-  // splines are drawn over the filtered planes before noise and the colour conversion
-  // (an upsampled frame's splines and patches are drawn at its own resolution, on the planes the upsampling kernel reads:
-  // dec_cache.cc:193-212)
-  if (d->splines.num_segments) c->color_out = true;
-  if ((r = UploadSplines(c, d->splines, c->ys))) return r;
-  // patches: validated like every table a kernel indexes with (rectangles inside the frame and inside their reference)
-  if ((r = UploadPatches(c, d->patches, c->ys, c->xp, c->yp))) return r;
-  if (c->pat_positions) c->color_out = true;
-  if (c->pat_uses_alpha && c->ups != 1) return JXLHIP_ERR_UNSUPPORTED;
-  if (c->have_alpha && c->alpha.cap < size_t(c->oxs) * c->oys * 4) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if ((c->keep_filtered || c->ups != 1 || c->color_out) && (r = c->plane[1].Ensure(plane_bytes))) return r;
-  if ((r = c->rgb.Ensure(size_t(c->oxs) * c->oys * OutPixelBytes(c)))) return r;
-  if (c->ups != 1) {
-    if ((r = Upload(c, c->ups_kernel, d->upsampling_kernel, size_t(c->ups) * c->ups * 25 * 4))) return r;
-  }
-  lap("buffers");
-  // ---- transform work lists (block indices bucketed by strategy)
-  {
-    std::vector<uint32_t> count(27, 0);
-    auto in_band = [&](uint32_t i) { return uint32_t(d->blocks[i].by >> 5) >= ext_row0 && uint32_t(d->blocks[i].by >> 5) < ext_row1; };
-    for (uint32_t i = 0; i < d->num_blocks; i++)
-      if (in_band(i)) count[d->blocks[i].strategy]++;
-    uint32_t acc = 0;
-    for (int s = 0; s < 27; s++) {
-      c->list_begin[s] = acc;
-      c->list_count[s] = count[s];
-      acc += count[s];
-    }
-    std::vector<uint32_t> list(d->num_blocks ? d->num_blocks : 1), fill(27, 0);
-    for (uint32_t i = 0; i < d->num_blocks; i++) {
-      if (!in_band(i)) continue;
-      const int s = d->blocks[i].strategy;
-      list[c->list_begin[s] + fill[s]++] = i;
-    }
-    if ((r = Upload(c, c->tlist, list.data(), list.size() * 4))) return r;
-    {
-      // ... and, in the same order, everything k_idct_fast needs to know of a varblock in ONE 16-byte load (the kernel's
-      // waves live for a handful of dependent memory round trips: list entry -> block -> coefficients was three of them):
-      // {bx | by << 16, raw quant field, element offset of its coefficients (group * 3 * 65536 + offset in the group's planes),
-      // index of the varblock (for its coefficient counts)}
-      void* st = nullptr;
-      if ((r = StageAlloc(c, list.size() * 16, &st))) return r;
-      uint32_t* rec = static_cast<uint32_t*>(st);
-      for (size_t j = 0; j < list.size(); j++) {
-        const uint32_t i = list[j];
-        if (i >= d->num_blocks || (j >= acc)) {
-          rec[4 * j] = rec[4 * j + 1] = rec[4 * j + 2] = rec[4 * j + 3] = 0;
-          continue;
-        }
-        const JxlHipVarBlock& v = d->blocks[i];
-        const uint32_t g = uint32_t(v.by >> 5) * d->xsize_groups + (v.bx >> 5);
-        rec[4 * j] = uint32_t(v.bx) | uint32_t(v.by) << 16;
-        rec[4 * j + 1] = v.qf;
-        rec[4 * j + 2] = g * (3u * 65536u) + v.coef_offset;
-        rec[4 * j + 3] = i;
-      }
-      if ((r = UploadStaged(c, c->trecs, st, list.size() * 16))) return r;
-    }
-    uint32_t big = 0;
-    for (int s = 21; s < 27; s++) big = big > count[s] ? big : count[s];
-    if (big) {
-      const uint32_t chunk = big < 32 ? big : 32;
-      if ((r = c->scratch.Ensure(size_t(chunk) * 3 * 2 * 65536 * 4))) return r;
-    }
-  }
-  lap("lists");
-  // ---- kernel parameter blocks
   jxlhip::EntropyParams& ep = c->ep;
   memset(&ep, 0, sizeof(ep));
   ep.sections = c->sections.as<uint32_t>();
   ep.sec_word = c->sec_word.as<uint32_t>();
   ep.sec_size = c->sec_size.as<uint32_t>();
-  ep.first_bit_offset = d->first_section_bit_offset;
+  ep.first_bit_offset = d.first_section_bit_offset;
   ep.blocks = c->blocks.as<JxlHipVarBlock>();
   ep.gbb = c->gbb.as<uint32_t>();
   ep.bctx_lut = c->bctx_lut.as<uint8_t>();
-  ep.nq = d->num_qf_thresholds + 1;
-  ep.ndc = d->num_dc_ctxs;
-  ep.num_bctx = d->num_block_ctxs;
-  for (uint32_t i = 0; i < d->num_qf_thresholds; i++) ep.qf_thr[i] = d->qf_thresholds[i];
-  ep.num_hist = d->num_histograms;
-  ep.nctx = nctx;
-  ep.cs = cs;
+  ep.nq = d.num_qf_thresholds + 1;
+  ep.ndc = d.num_dc_ctxs;
+  ep.num_bctx = d.num_block_ctxs;
+  for (uint32_t i = 0; i < d.num_qf_thresholds; i++) ep.qf_thr[i] = d.qf_thresholds[i];
+  ep.num_hist = d.num_histograms;
+  ep.nctx = P.g.nctx;
+  ep.cs = P.g.cs;
   ep.passes = c->passes_dev.as<jxlhip::PassDev>();
-  ep.num_passes = d->num_passes;
-  ep.num_groups = d->num_groups;
+  ep.num_passes = d.num_passes;
+  ep.num_groups = d.num_groups;
   ep.coeffs = c->coeffs.p;
   ep.errors = c->errors.as<uint32_t>();
-  c->generic_codec = generic;
-  ep.lz_window = nullptr;
-  if (any_lz77) {
-    if ((r = c->lz_window.Ensure(size_t(d->num_groups) * jxlhip::kLzWindow * 4))) return r;
-    ep.lz_window = c->lz_window.as<uint32_t>();
-  }
-  if ((r = c->sec_end.Ensure(nsec * 4))) return r;
-  HIP_TRY(hipMemsetAsync(c->sec_end.p, 0, nsec * 4, c->stream));
+  ep.lz_window = E.any_lz77 ? c->lz_window.as<uint32_t>() : nullptr;
   ep.sec_end_bits = c->sec_end.as<uint32_t>();
-  ep.lds_ctx_bytes = (nctx + 16 + 15) & ~15u;
-  const size_t lds_budget = 150 * 1024;
-  c->alias_lds = ep.lds_ctx_bytes + alias_bytes_max + 1024 + 4 * 5120 <= lds_budget;
-  ep.lds_alias_bytes = c->alias_lds ? uint32_t((alias_bytes_max + 15) & ~size_t(15)) : 0;
-  c->lds_entropy = ep.lds_ctx_bytes + ep.lds_alias_bytes + 3072;
-  if (size_t(d->block_ctx_lut_size) < size_t(3) * 13 * ep.nq * ep.ndc) return JXLHIP_ERR_INVALID_ARGUMENT;
-  // single-pass frames whose tables fit LDS are decoded by the lane-parallel kernel into scan order
-  // (its packed block records hold the block contexts in 4 bits each: the codestream allows at most 16)
-  bool all_prefix = true;
-  for (uint32_t p = 0; p < d->num_passes; p++) all_prefix = all_prefix && d->passes[p].use_prefix;
-  c->lane_prefix = all_prefix && !any_lz77 && !EnvInt("JXLHIP_NO_LANE_PREFIX", 0);
-  c->lanes = !SectionEntropyForced() && ep.num_bctx <= 16 && d->num_passes <= 8 && (!generic || c->lane_prefix);
-  for (uint32_t p = 0; c->lanes && p < d->num_passes; p++)  // (alias tables that do not fit LDS are read in place)
-    c->lanes = jxlhip::LanesLdsLayout(1, ep.nctx, c->pass_clusters[p], c->pass_log_alpha[p], kLanesAdmitWaves, 64, false, c->lane_prefix).total <= kLdsBudget;
-  if (!c->lanes) c->lane_prefix = false;
-  // (sections that have not arrived: the lane kernel takes a list of the ones that have; the section-per-workgroup kernels
-  // step over a section of size 0 and leave the group's coefficients zeroed)
-  c->scan_order = c->lanes && d->num_passes == 1;
-  c->lane_multi = c->lanes && d->num_passes > 1;
-  const size_t kend_per_pass = size_t(d->num_blocks ? d->num_blocks : 1) * 3;
-  if ((r = c->kend.Ensure(kend_per_pass * 4 * d->num_passes))) return r;
+  ep.lds_ctx_bytes = E.lds_ctx_bytes;
+  ep.lds_alias_bytes = E.lds_alias_bytes;
+  const size_t kend_per_pass = size_t(d.num_blocks ? d.num_blocks : 1) * 3;
   ep.kend = c->kend.as<uint32_t>();
-  ep.coef_pass_base = c->lane_multi ? uint64_t(d->num_groups) * 3 * 65536 : 0;
-  ep.coef_pass_stride = uint64_t(d->num_groups) * 3 * 65536;
+  ep.coef_pass_base = E.lane_multi ? uint64_t(d.num_groups) * 3 * 65536 : 0;
+  ep.coef_pass_stride = uint64_t(d.num_groups) * 3 * 65536;
   ep.kend_pass_stride = uint32_t(kend_per_pass);
-  if (c->lane_multi) {  // k_merge_passes scatters through every pass's orders: validate them here
-    for (uint32_t p = 0; p < d->num_passes; p++)
-      for (int st = 0; st < 27; st++) {
-        if (!c->list_count[st]) continue;
-        const uint32_t size = d->dequant_size[jxlhip::kStrategyQuantTable[st]];
-        for (int ch = 0; ch < 3; ch++) {
-          const uint32_t oo = d->passes[p].order_offset[jxlhip::kStrategyOrder[st] * 3 + ch];
-          if (size_t(oo) + size > d->passes[p].orders_size) return JXLHIP_ERR_INVALID_ARGUMENT;
-          for (uint32_t k = 0; k < size; k++)
-            if (d->passes[p].orders[oo + k] >= size) return JXLHIP_ERR_INVALID_ARGUMENT;
-        }
-      }
-  }
-  {
-    // Per varblock, everything the lane kernel's block transition needs in one word, so that it does no dependent
-    // table lookups: column in the group (5 bits) | not in the group's first row (1) | log2 covered_x (3) |
-    // log2 covered_y (3) | block context of X, Y, B (4 bits each: ac_context.h:101-143 BlockCtxMap::Context, from the
-    // strategy's order bucket, the quant-field bucket and the DC bucket).
-    std::vector<uint32_t> recs(size_t(d->num_blocks) + 16, 0);
-    for (uint32_t i = 0; i < d->num_blocks; i++) {
-      const JxlHipVarBlock& v = d->blocks[i];
-      const uint32_t qfi = jxlhip::QfBucket(v.qf, ep.qf_thr, ep.nq);
-      const uint32_t fbx = v.bx & 31u, fby = v.by & 31u;
-      uint32_t rec = fbx | (fby ? 32u : 0u) | jxlhip::Log2CoveredX(v.strategy) << 6 | jxlhip::Log2CoveredY(v.strategy) << 9;
-      for (uint32_t ch = 0; ch < 3; ch++) {
-        // (chroma-subsampled frames: bit 24 + channel = the block is off the channel's grid and carries nothing for it,
-        // bit 27 + channel = the channel's columns are half the frame's)
-        const uint32_t hs = jxlhip::ChannelHShift(cs, ch);
-        uint32_t lbx, lby;
-        const bool carried = jxlhip::ChannelCell(cs, ch, fbx, fby, lbx, lby);
-        // (the quant field at the channel's own column: a subsampled group's varblocks are its blocks in raster order, validated above)
-        const uint32_t qfc = hs ? jxlhip::QfBucket(d->blocks[i - jxlhip::QfColumnBack(fbx, lbx)].qf, ep.qf_thr, ep.nq) : qfi;
-        const uint32_t bctx = d->block_ctx_lut[jxlhip::BctxLutIndex(ch, jxlhip::kStrategyOrder[v.strategy], ep.nq, qfc, ep.ndc, v.quant_dc_ctx)];
-        rec |= (bctx & 15u) << (12 + 4 * ch);
-        if (!carried) rec |= 1u << (24 + ch);
-        rec |= hs << (27 + ch);
-      }
-      recs[i] = rec;
-    }
-    if ((r = Upload(c, c->block_recs, recs.data(), recs.size() * 4))) return r;
-    ep.block_recs = c->block_recs.as<uint32_t>();
-  }
-  lap("records");
-  c->absent_blocks.clear();
-  for (uint32_t g : c->absent_groups) {
-    c->absent_blocks.push_back(d->group_block_begin[g]);
-    c->absent_blocks.push_back(d->group_block_begin[g + 1] - d->group_block_begin[g]);
-  }
-  if (c->scan_order) {
-    c->blocks_host.assign(d->blocks, d->blocks + d->num_blocks);
-    c->gbb_host.assign(d->group_block_begin, d->group_block_begin + d->num_groups + 1);
-    c->orders_host.assign(d->passes[0].orders, d->passes[0].orders + d->passes[0].orders_size);
-    memcpy(c->order_offset_host, d->passes[0].order_offset, sizeof(c->order_offset_host));
-  }
-  if ((r = Upload(c, c->ep_dev, &ep, sizeof(ep)))) return r;
-  c->generation++;
+  ep.block_recs = c->block_recs.as<uint32_t>();
+  memcpy(Staged<jxlhip::EntropyParams>(c, c->ep_dev), &ep, sizeof(ep));
+}
 
+static void FillTransformParams(JxlHipContext* c, const JxlHipFrameDesc& d) {
   jxlhip::TransformParams& tp = c->tp;
   memset(&tp, 0, sizeof(tp));
   tp.coeffs = c->coeffs.p;
-  tp.coef_bits = d->coef_bits;
+  tp.coef_bits = d.coef_bits;
   tp.blocks = c->blocks.as<JxlHipVarBlock>();
   tp.dequant = c->dequant.as<float>();
-  memcpy(tp.dq_offset, d->dequant_offset, sizeof(tp.dq_offset));
-  memcpy(tp.dq_size, d->dequant_size, sizeof(tp.dq_size));
-  for (int s = 0; s < 27; s++) {
-    if (c->list_count[s] == 0) continue;
-    const uint32_t k = jxlhip::kStrategyQuantTable[s];
-    if (d->dequant_size[k] != 64u * jxlhip::CoveredBlocks(s) || size_t(d->dequant_offset[k]) + 3 * size_t(d->dequant_size[k]) > d->dequant_floats)
-      return JXLHIP_ERR_INVALID_ARGUMENT;
-  }
+  memcpy(tp.dq_offset, d.dequant_offset, sizeof(tp.dq_offset));
+  memcpy(tp.dq_size, d.dequant_size, sizeof(tp.dq_size));
   tp.dense = c->transform_dense ? 1 : 0;
-  tp.cs = cs;
+  tp.cs = c->cs;
   tp.cs_out = c->plane[1].as<float>();  // (a YCbCr frame's colour stage is the generic writer: the second plane set exists)
   tp.dc = c->dc.as<float>();
   tp.ytox = c->ytox.as<int8_t>();
   tp.ytob = c->ytob.as<int8_t>();
   tp.basis_t = c->basis.as<float>();
-  tp.basis_n = c->basis.as<float>() + 87381 + 3;
-  tp.inv_global_scale = d->inv_global_scale;
-  tp.x_dm = d->x_dm;
-  tp.b_dm = d->b_dm;
-  tp.color_scale = d->color_scale;
-  tp.base_x = d->base_corr_x;
-  tp.base_b = d->base_corr_b;
-  memcpy(tp.biases, d->quant_biases, sizeof(tp.biases));
+  tp.basis_n = c->basis.as<float>() + kBasisTransposed;
+  tp.inv_global_scale = d.inv_global_scale;
+  tp.x_dm = d.x_dm;
+  tp.b_dm = d.b_dm;
+  tp.color_scale = d.color_scale;
+  tp.base_x = d.base_corr_x;
+  tp.base_b = d.base_corr_b;
+  memcpy(tp.biases, d.quant_biases, sizeof(tp.biases));
   tp.xb = c->xb; tp.yb = c->yb; tp.xg = c->xg; tp.xp = c->xp; tp.yp = c->yp;
   tp.out = PlaneHolder(c)->plane[0].as<float>();  // (a lender's buffer is checked again at launch: PrepareDownstream)
   tp.scratch = c->scratch.as<float>();
@@ -1416,67 +1055,122 @@ int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   tp.scan_order = c->scan_order ? 1 : 0;
   tp.kend = c->kend.as<uint32_t>();
   tp.orders = c->pass_bufs[0].orders.as<uint16_t>();
-  tp.dequant_scan = nullptr;
-  if (c->scan_order) {
-    // dequant tables in scan order for the kinds in use
-    std::vector<float> scan(d->dequant_floats, 0.0f);
-    for (int st = 0; st < 27; st++) {
-      if (!c->list_count[st]) continue;
-      const uint32_t kind = jxlhip::kStrategyQuantTable[st], size = d->dequant_size[kind];
-      for (int ch = 0; ch < 3; ch++) {
-        const uint32_t oo = d->passes[0].order_offset[jxlhip::kStrategyOrder[st] * 3 + ch];
-        if (size_t(oo) + size > d->passes[0].orders_size) return JXLHIP_ERR_INVALID_ARGUMENT;
-        const uint16_t* order = d->passes[0].orders + oo;
-        const float* m = d->dequant + d->dequant_offset[kind] + size_t(ch) * size;
-        float* o = scan.data() + d->dequant_offset[kind] + size_t(ch) * size;
-        for (uint32_t k = 0; k < size; k++) {
-          if (order[k] >= size) return JXLHIP_ERR_INVALID_ARGUMENT;
-          o[k] = m[order[k]];
-        }
-      }
-    }
-    if ((r = Upload(c, c->dequant_scan, scan.data(), scan.size() * 4))) return r;
-    tp.dequant_scan = c->dequant_scan.as<float>();
-  }
-  memcpy(tp.order_offset, d->passes[0].order_offset, sizeof(tp.order_offset));
+  tp.dequant_scan = c->scan_order ? c->dequant_scan.as<float>() : nullptr;
+  memcpy(tp.order_offset, d.passes[0].order_offset, sizeof(tp.order_offset));
+}
 
+static void FillFilterParams(JxlHipContext* c, const JxlHipFrameDesc& d) {
   jxlhip::FilterParams& fp = c->fp;
   memset(&fp, 0, sizeof(fp));
   fp.xs = c->xs; fp.ys = c->ys; fp.xp = c->xp; fp.yp = c->yp; fp.xb = c->xb;
   fp.y_begin = c->band_y0; fp.y_end = c->band_y1;
   fp.inv_sigma = c->inv_sigma.as<float>();
+  upload::FoldGaborish(d.gab_w, fp.gab_w);
   for (int ch = 0; ch < 3; ch++) {
-    const float w1 = d->gab_w[ch * 2], w2 = d->gab_w[ch * 2 + 1];
-    const float mul = 1.0f / (1.0f + 4 * (w1 + w2));
-    fp.gab_w[ch * 3] = mul;
-    fp.gab_w[ch * 3 + 1] = w1 * mul;
-    fp.gab_w[ch * 3 + 2] = w2 * mul;
-    fp.ch_scale[ch] = d->epf_channel_scale[ch];
-    fp.opsin_bias[ch] = d->opsin_bias[ch];
-    fp.opsin_bias_cbrt[ch] = cbrtf(d->opsin_bias[ch]);
+    fp.ch_scale[ch] = d.epf_channel_scale[ch];
+    fp.opsin_bias[ch] = d.opsin_bias[ch];
+    fp.opsin_bias_cbrt[ch] = cbrtf(d.opsin_bias[ch]);
   }
-  memcpy(fp.opsin_inv, d->opsin_inv, sizeof(fp.opsin_inv));
-  fp.linear_output = d->linear_output;
-  c->gray8_fast = OutIsGray8(c) && !c->color_out;
+  memcpy(fp.opsin_inv, d.opsin_inv, sizeof(fp.opsin_inv));
+  fp.linear_output = d.linear_output;
   fp.rgb = OutIsRgb8(c) || c->gray8_fast ? c->rgb.as<uint8_t>() : nullptr;
   fp.rgbf = !OutIsRgb8(c) && !c->gray8_fast && !c->color_out ? c->rgb.as<float>() : nullptr;
-  c->epf_pass0 = d->epf_pass0_sigma_scale;
-  c->epf_pass2 = d->epf_pass2_sigma_scale;
-  c->epf_border = d->epf_border_sad_mul;
-  c->ev_valid[0] = c->ev_valid[1] = c->ev_valid[2] = false;
-  if ((r = BlobEnd(c, dev_smooth && !d->dc_device ? &smooth_p : nullptr, dev_sigma ? &sigma_p : nullptr, dev_dequant ? &dequant_p : nullptr))) return r;  // (records the staging block's event on the copy stream)
+}
+
+// The DC-path kernels' parameters (jxl_hip_dc.h): DequantDC, adaptive smoothing, 1 / sigma, as the frame asks for them.
+struct DcParams {
+  jxlhip::DcDequantParams dequant;
+  jxlhip::DcSmoothParams smooth;
+  jxlhip::SigmaParams sigma;
+};
+static void FillDcParams(JxlHipContext* c, const JxlHipFrameDesc& d, const upload::Plan& P, DcParams* dp) {
+  if (P.dc.dequant) {
+    jxlhip::DcDequantParams& q = dp->dequant;
+    q.q = c->dc_q.as<int32_t>();
+    q.out = P.dc.smooth ? c->dc_raw.as<float>() : c->dc.as<float>();
+    q.xs = c->xb;
+    q.ys = c->yb;
+    q.xgroups = (c->xb + 255) / 256;
+    q.extra_precision = d.dc_extra_precision ? c->dc_ep.as<uint8_t>() : nullptr;
+    for (int ch = 0; ch < 3; ch++) q.step[ch] = d.dc_step[ch];
+    q.cfl_x = d.dc_cfl_x;
+    q.cfl_b = d.dc_cfl_b;
+    q.cs = c->cs;
+  }
+  if (P.dc.smooth) {
+    jxlhip::DcSmoothParams& s = dp->smooth;
+    s.in = c->dc_raw.as<float>();
+    s.out = c->dc.as<float>();
+    s.xs = c->xb;
+    s.ys = c->yb;
+    for (int ch = 0; ch < 3; ch++) s.step[ch] = d.dc_step[ch];
+  }
+  if (P.dc.sigma) {
+    jxlhip::SigmaParams& s = dp->sigma;
+    s.blocks = c->blocks.as<JxlHipVarBlock>();
+    s.num_blocks = d.num_blocks;
+    s.xb = c->xb;
+    s.sharpness = c->sharp.as<uint8_t>();
+    s.inv_sigma = c->inv_sigma.as<float>();
+    s.quant_scale = d.quant_scale;
+    s.epf_quant_mul = d.epf_quant_mul;
+    memcpy(s.sharp_lut, d.epf_sharp_lut, sizeof(s.sharp_lut));
+  }
+}
+
+extern "C" int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
+  if (!c || !d) return JXLHIP_ERR_INVALID_ARGUMENT;
+  UploadProf prof;
+  // 1. whether the descriptor is taken: decided on the host alone, so that a refused one costs no device call and
+  // leaves the context's tables as they were (but no frame to run: the caller meant to replace it)
+  const upload::UploadOptions opt = OptionsOf(c);
+  int r = upload::CheckFrameDesc(*d, opt);
+  upload::Plan P;
+  EntropyRoute E = {};
+  if (!r) {
+    P = upload::MakePlan(*d, opt);
+    E = EntropyRouteOf(*d, opt);
+    P.scan_order = E.scan_order;
+    r = upload::CheckOrders(*d, P.list_count, E.lanes ? d->num_passes : 0);
+  }
+  if (r) {
+    c->have_frame = false;
+    return r;
+  }
+  prof.lap("validate");
+  // 2. the tables are overwritten from the copy stream: whatever still reads the old ones has to be finished
+  HIP_TRY(hipSetDevice(c->device));
+  if ((r = ApplyPendingWait(c))) return r;
+  if ((r = StageReset(c))) return r;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
+  c->have_frame = false;
+  AdoptFrame(c, *d, P, E);
+  // 3. the tables: one list, walked once for the size of the blob and once to place them
+  upload::TableBound bound;
+  VisitTables(c, *d, P, bound);
+  if ((r = BlobBegin(c, bound.bytes))) return r;
+  BlobPlacer placer{c, &prof};
+  VisitTables(c, *d, P, placer);
+  // 4. work buffers, then the parameter blocks, which hold their addresses
+  if ((r = EnsureWorkBuffers(c, *d, P, E))) return r;
+  prof.lap("buffers");
+  DcParams dc;
+  FillDcParams(c, *d, P, &dc);
+  FillEntropyParams(c, *d, P, E);
+  FillTransformParams(c, *d);
+  FillFilterParams(c, *d);
+  if ((r = BlobEnd(c, P.dc.smooth ? &dc.smooth : nullptr, P.dc.sigma ? &dc.sigma : nullptr, P.dc.dequant ? &dc.dequant : nullptr))) return r;
   // The tables are resident when the call returns (batch launches over this context run on other contexts' streams).
   // (Leaving the copies of many contexts in flight at once instead, ordered by events, made every later kernel of the
   // process ~1.35x slower on this runtime: scripts/async_probe.py.)
   HIP_TRY(WaitEvent(c->stage.done));
-  lap("rest");
-  if (prof) fprintf(stderr, "[upload] %s\n", prof_line.c_str());
+  prof.lap("rest");
+  if (prof.on) fprintf(stderr, "[upload] %s\n", prof.line.c_str());
   c->have_frame = true;
   c->mod.have = false;  // (the context now holds a VarDCT frame, not the Modular one it may have held before)
   return 0;
 }
-
-}  // extern "C"
 
 template <typename CoefT>
 static int LaunchEntropy(JxlHipContext* c) {
@@ -2322,25 +2016,6 @@ extern "C" int jxlhip_run_entropy(JxlHipContext* c) {
 }
 
 
-// The draw cache of a frame's splines to the device (validated: every index a kernel forms from it is in range).
-static int UploadSplines(JxlHipContext* c, const JxlHipSplines& sp, uint32_t ysize) {
-  c->spl_segments = 0;
-  if (!sp.num_segments) return 0;
-  if (!sp.segments || !sp.row_start || !sp.row_segments || sp.num_segments > (1u << 26) || sp.num_row_segments > (1u << 30))
-    return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (sp.row_start[0] != 0 || sp.row_start[ysize] != sp.num_row_segments) return JXLHIP_ERR_INVALID_ARGUMENT;
-  for (uint32_t y = 0; y < ysize; y++)
-    if (sp.row_start[y] > sp.row_start[y + 1]) return JXLHIP_ERR_INVALID_ARGUMENT;
-  for (uint32_t i = 0; i < sp.num_row_segments; i++)
-    if (sp.row_segments[i] >= sp.num_segments) return JXLHIP_ERR_INVALID_ARGUMENT;
-  int r;
-  if ((r = Upload(c, c->spl_seg, sp.segments, size_t(sp.num_segments) * 32))) return r;
-  if ((r = Upload(c, c->spl_row_start, sp.row_start, (size_t(ysize) + 1) * 4))) return r;
-  if ((r = Upload(c, c->spl_row_seg, sp.row_segments, std::max<size_t>(4, size_t(sp.num_row_segments) * 4)))) return r;
-  c->spl_segments = sp.num_segments;
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------------------ Modular frames
 extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc* d) {
   if (!c || !d || !d->xsize || !d->ysize || !d->num_sections || !d->num_trees || !d->num_codes || d->num_trees != d->num_codes)
@@ -2428,7 +2103,7 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
     if (!k.use_prefix && (k.log_alpha < 5 || k.log_alpha > 8)) return JXLHIP_ERR_INVALID_ARGUMENT;
     if (k.use_prefix)
       for (uint32_t j = 0; j < k.num_clusters; j++) {
-        if (!ValidPrefixTables(k.prefix_offset[j], k.prefix_table, k.prefix_table_size)) return JXLHIP_ERR_INVALID_ARGUMENT;
+        if (!upload::ValidPrefixTables(k.prefix_offset[j], k.prefix_table, k.prefix_table_size)) return JXLHIP_ERR_INVALID_ARGUMENT;
       }
     if (k.lz77 && (k.lz_dist_ctx >= k.num_clusters || !k.lz_min_length)) return JXLHIP_ERR_INVALID_ARGUMENT;
     code_parts[i] = {put(k.ctx_map, k.ctx_map_size), put(k.alias, k.use_prefix ? 0 : (size_t(k.num_clusters) << k.log_alpha) * 8),
@@ -4111,8 +3786,7 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
   P.acs = c->enc_acs.as<uint8_t>();
   P.qf = c->enc_qf.as<int32_t>();
   P.coef_off = c->enc_off.as<uint32_t>();
-  constexpr size_t kBasisFloats = 87381;
-  P.basis_t = c->basis.as<float>() + kBasisFloats + 3;
+  P.basis_t = c->basis.as<float>() + kBasisTransposed;
   P.dequant = c->enc_dq.as<float>();
   memcpy(P.dq_offset, d->dequant_offset, sizeof(P.dq_offset));
   memcpy(P.dq_size, d->dequant_size, sizeof(P.dq_size));

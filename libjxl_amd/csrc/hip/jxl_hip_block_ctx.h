@@ -1,11 +1,14 @@
 // libjxl_amd — the HIP layer's one statement of the per-strategy tables and of the block-context rules of the AC
 // coefficient walk (lib/jxl/dec_group.cc:470-639, ac_context.h, entropy_coder.h). The section-per-workgroup entropy
 // kernels, the tokeniser of the encode path and jxlhip_frame_upload's block records all read these; the lane kernel
-// (jxl_hip_entropy_lanes.h) keeps its own fused forms.
+// (jxl_hip_entropy_lanes.h) keeps its own fused forms. A plain C++ compile (csrc/host/jxh_upload_plan.h, the CPU tests) sees
+// the constexpr tables and the rules as inline functions; the __constant__ copies exist under hipcc only.
 #ifndef JXL_HIP_BLOCK_CTX_H_
 #define JXL_HIP_BLOCK_CTX_H_
 
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 namespace jxlhip {
@@ -47,15 +50,19 @@ constexpr PerStrategy<uint32_t> kStrategyInfo = MakeStrategyInfo();
 static_assert(kStrategyInfo[0] == 0x00000101 && kStrategyInfo[18] == 0x07060808 && kStrategyInfo[26] == 0x0C091020, "the packing");
 static_assert(kLog2Covered[5] == 4 && kLog2Covered[25] == 9 && (1u << kLog2Covered[23]) == CoveredBlocks(23), "log2 covered");
 
+#ifdef __HIPCC__
 __constant__ PerStrategy<uint8_t> c_covered_x = kCoveredX;
 __constant__ PerStrategy<uint8_t> c_covered_y = kCoveredY;
 __constant__ PerStrategy<uint8_t> c_log2_covered = kLog2Covered;
 __constant__ PerStrategy<uint8_t> c_strategy_order = kStrategyOrder;
 __constant__ PerStrategy<uint8_t> c_strategy_qtable = kStrategyQuantTable;
 __constant__ PerStrategy<uint32_t> c_strategy_info = kStrategyInfo;
+#define JXLHIP_RULE __host__ __device__ __forceinline__
+#else
+#define JXLHIP_RULE inline
+#endif
 
 // ---------------------------------------------------------------------------------------------- block-context rules
-#define JXLHIP_RULE __host__ __device__ __forceinline__
 
 // ac_context.h:116-121 BlockCtxMap::Context: the bucket of a quant-field value among `nq` buckets (nq - 1 thresholds).
 template <typename Thresholds>

@@ -2,49 +2,12 @@
 // (box sizes, jxlp order, brob), chunked input with JxlDecoderReleaseInput, box buffers, header events, ICC getters and
 // the frame walk of animations, over damaged files fed in random pieces. Built by tests/test_kats.py with
 // -fsanitize=address,undefined. The pixel stages need a GPU and are not part of this: the HIP layer's entry points are
-// defined here as "no device" doubles (a decoder that reaches them returns JXL_DEC_ERROR, which is a valid end).
+// "no device" doubles (no_device_doubles.inc: a decoder that reaches them returns JXL_DEC_ERROR, which is a valid end).
 // Every run must end in JXL_DEC_SUCCESS / JXL_DEC_ERROR / input exhausted within a bounded number of calls.
 // usage: api_fuzz rounds file...
 #include "../../libjxl_amd/csrc/api/jxl_api.cc"
 
-extern "C" {
-int jxlhip_device_count(void) { return 0; }
-int jxlhip_ctx_create(int, JxlHipContext**) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-void jxlhip_ctx_destroy(JxlHipContext*) {}
-int jxlhip_download_pixels(JxlHipContext*, void*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_frame_upload(JxlHipContext*, const JxlHipFrameDesc*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_get_errors(JxlHipContext*, uint32_t*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_get_section_end_bits(JxlHipContext*, uint32_t*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_modular_download_buffer(JxlHipContext*, uint32_t, int32_t*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_modular_run(JxlHipContext*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_modular_status(JxlHipContext*, uint32_t*, uint32_t*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_modular_upload(JxlHipContext*, const JxlHipModFrameDesc*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_run_entropy(JxlHipContext*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_run_filter_color(JxlHipContext*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_run_transform(JxlHipContext*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_set_alpha(JxlHipContext*, const float*, uint32_t, uint32_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_set_output_format(JxlHipContext*, uint32_t, uint32_t, uint32_t, int) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_set_output_orientation(JxlHipContext*, uint32_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_set_output_unpremultiply(JxlHipContext*, int) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_canvas_set_unpremultiply(JxlHipCanvas*, int) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_canvas_create(int, uint32_t, uint32_t, uint32_t, uint32_t, JxlHipCanvas**) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-void jxlhip_canvas_destroy(JxlHipCanvas*) {}
-int jxlhip_canvas_blend(JxlHipCanvas*, JxlHipContext*, const JxlHipBlend*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_canvas_download(JxlHipCanvas*, uint32_t, uint32_t, uint32_t, int, uint32_t, void*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_canvas_download_alpha(JxlHipCanvas*, float*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_canvas_save_xyb(JxlHipCanvas*, JxlHipContext*, uint32_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_canvas_xyb_source(JxlHipCanvas*, uint32_t, const float**, uint32_t*, uint32_t*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_canvas_xyb_alpha(JxlHipCanvas*, uint32_t, const float**) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_download_alpha(JxlHipContext*, float*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_upsample_plane(JxlHipContext*, const float*, uint32_t, uint32_t, uint32_t, const float*, uint32_t, uint32_t, int, float*) {
-  return JXLHIP_ERR_INVALID_ARGUMENT;
-}
-int jxlhip_set_option(JxlHipContext*, const char*, int) { return JXLHIP_ERR_INVALID_ARGUMENT; }
-int jxlhip_debug_noise(JxlHipContext*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, const float*, float, float, uint32_t, uint32_t,
-                       float*, float*) {
-  return JXLHIP_ERR_INVALID_ARGUMENT;
-}
-}
+#include "no_device_doubles.inc"
 
 static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
 static uint32_t Rnd(uint32_t n) {

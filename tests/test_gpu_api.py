@@ -596,3 +596,37 @@ def test_more_contexts_than_pool_streams_on_concurrent_host_threads(built):
         for res in ex.map(work, range(12)):
             for i, rgb in res:
                 assert np.array_equal(rgb, serial[i]), "stream %d decoded differently on a shared stream" % i
+
+
+def test_a_refused_upload_leaves_the_context_as_it_was(built, monkeypatch):
+    """jxlhip_frame_upload decides on the host whether it takes a descriptor, before it touches the device or the context.
+    One context: a 64 x 32 frame is uploaded and decoded; a 4:2:0 frame whose varblocks are not in raster order is refused
+    (JXLHIP_ERR_INVALID_ARGUMENT = 1) and leaves no frame to run (JXLHIP_ERR_NO_FRAME = 2); the first frame, uploaded
+    again, decodes to the same pixels, and under JXLHIP_GUARD=1 no kernel has written next to a buffer."""
+    import ctypes
+    J = built
+    L = J.lib()
+    monkeypatch.setenv("JXLHIP_GUARD", "1")
+    L.jxlamd_frame_debug_swap_blocks.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
+    good = J.Frame(J.encode_rgb8(J.synth_image(64, 32, seed=3)))
+    bad = J.Frame(J.encode_rgb8(J.synth_image(64, 32, seed=3), strategy_mode=0, color_transform=2, chroma_subsampling=4))
+    c = J.HipContext()
+    try:
+        def decode():
+            c.upload(good)
+            c.run_all()
+            c.sync()
+            return c.pixels().copy()
+        first = decode()
+        assert L.jxlamd_frame_debug_swap_blocks(bad._h, 0, bad.info["xsize_blocks"] - 1) == 0
+        with pytest.raises(J.JxlAmdError, match="code 1"):
+            c.upload(bad)
+        with pytest.raises(J.JxlAmdError, match="code 2"):
+            c.run_all()
+        again = decode()
+        assert first.shape == (32, 64, 3) and np.array_equal(first, again)
+        assert c.check_guards() == 0, c.check_guards()
+    finally:
+        c.close()
+        good.close()
+        bad.close()

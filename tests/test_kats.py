@@ -246,3 +246,41 @@ def test_decoder_api_under_sanitizers_on_damaged_files(built, tmp_path):
     r = subprocess.run([out, "60"] + files, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "reached JXL_DEC_SUCCESS" in r.stdout
+
+
+def test_upload_plan_under_sanitizers_on_real_descriptors(built, tmp_path):
+    """tests/c/upload_plan_kats.cc: what jxlhip_frame_upload computes on the host (libjxl_amd/csrc/host/jxh_upload_plan.h)
+    built with AddressSanitizer + UBSan around libjxl_amd/csrc/api/jxl_api.cc, whose jxlamd_frame_upload_band hands the
+    program the descriptor of each stream below: every rule of the upload's checks refuses the one change that breaks it,
+    the packed words the kernels decode (block records, alias entries, work lists, section packing, scan-order dequant
+    tables) agree with a reading written in the program, and the table list's bound covers what placing takes. Each rule
+    is exercised by some stream."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_ac_walk import DECODE_CASES
+    J = built
+    out = os.path.join(str(tmp_path), "upload_plan_kats")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
+                    "-Wno-unused-function", "-Wno-subobject-linkage", "-I" + os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "c", "upload_plan_kats.cc"), "-o", out, "-lpthread"], check=True)
+    tall = J.encode_rgb8(J.synth_image(8, 520, seed=4))  # three group rows
+    runs = [("444", ["whole"], J.encode_rgb8(J.synth_image(64, 32, seed=3))),
+            ("420", ["whole"], J.encode_rgb8(J.synth_image(64, 32, seed=3), strategy_mode=0, color_transform=2, chroma_subsampling=4)),
+            ("prefix_lz77", ["whole"], DECODE_CASES["passes2_hist2_prefix_lz77"](J)),
+            ("clusters", ["whole"], DECODE_CASES["passes2_hist2_clusters"](J)),
+            ("dct32_dct128", ["whole"], J.encode_random(256, 256, strategy_mask=(1 << 5) | (1 << 21) | 1)),
+            ("tall", ["whole"], tall), ("tall_band", ["band", "1", "2"], tall),
+            ("partial2", ["partial"], J.encode_rgb8(J.synth_image(1100, 800, seed=9), num_passes=2)),
+            ("partial3_late", ["partial_late"], DECODE_CASES["passes3"](J))]  # (three passes, some groups with all of them: a pass can go missing in front of one that is there)
+    exercised = set()
+    for name, args, data in runs:
+        path = os.path.join(str(tmp_path), name + ".jxl")
+        open(path, "wb").write(data)
+        r = subprocess.run([out] + args + [path], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (name, (r.stdout + r.stderr)[-3000:])
+        line = [l for l in r.stdout.splitlines() if l.startswith("exercised:")]
+        assert len(line) == 1, (name, r.stdout)
+        exercised |= set(line[0].split()[1:])
+    import re
+    header = open(os.path.join(ROOT, "libjxl_amd", "csrc", "host", "jxh_upload_plan.h")).read()
+    rules = re.findall(r"^  kRule(\w+),", header, re.M)
+    assert len(rules) > 30 and exercised == set(rules), sorted(set(rules) ^ exercised)
