@@ -698,6 +698,39 @@ int jxlhip_enc_initial_quant_field(JxlHipContext* ctx, const float* xyb, uint32_
 int jxlhip_enc_masking_1x1(JxlHipContext* ctx, const float* xyb, uint32_t xsize, uint32_t ysize, float* out);
 /* Kernel time of the last jxlhip_enc_masking_1x1 (copies excluded), milliseconds. */
 int jxlhip_enc_masking_last_ms(JxlHipContext* ctx, float* ms);
+/* The cost estimate of the reference's AC-strategy search (EstimateEntropy, enc_ac_strategy.cc:364-511, with the constants of
+ * AcStrategyHeuristics::Init :1107-1123) for a list of candidate transforms, alone. All pointers are host memory. */
+typedef struct {
+  const float* xyb;         /* [3][ysize][xsize] X, Y, B: the planes the transforms would be taken of */
+  uint32_t xsize, ysize;    /* multiples of 8 */
+  const float* quant_field; /* [ysize / 8][xsize / 8]: aq_map of jxlhip_enc_initial_quant_field */
+  const float* mask1x1;     /* [ysize][xsize]: jxlhip_enc_masking_1x1 */
+  const int8_t* ytox;       /* one per 64x64 tile, ceil(xsize / 64) per row: the factors are v / 84 and 1 + v / 84 */
+  const int8_t* ytob;
+  float distance;           /* the Butteraugli target */
+  /* dequantisation tables, as JxlHipEncDesc: kind k, channel c at dequant[dequant_offset[k] + c * dequant_size[k]] */
+  const float* dequant;
+  uint32_t dequant_floats;
+  uint32_t dequant_offset[17], dequant_size[17];
+} JxlHipEncEstimateDesc;
+/* strategy: an AcStrategy number of the pure-DCT kinds up to 64x64 (0, 4 .. 11, 18 .. 20); (bx, by): its top-left block;
+ * entropy_mul: the multiplier of the bit estimate (not of the loss) the caller's walk attaches. */
+typedef struct {
+  uint32_t strategy, bx, by;
+  float entropy_mul;
+} JxlHipEncAcsCandidate;
+/* estimates[i] = EstimateEntropy of candidates[i]. scaled (may be NULL; for tests) receives per candidate 3 * R * C floats,
+ * candidate i starting at 3 * (the areas before it): channel X, Y, B, the quantised value before rounding (`val` of :432) of
+ * the coefficient of vertical frequency ky and horizontal frequency kx at ky * C + kx (tall transforms are NOT transposed
+ * here). Every candidate must lie inside the planes and inside one 64x64 tile; anything else, a null pointer, a strategy
+ * that is not listed, a size that is no multiple of 8 or a table that does not hold a used kind is
+ * JXLHIP_ERR_INVALID_ARGUMENT, decided on the host before any device call. powf is exact where the reference has
+ * FastPowf (:413). Synchronous; leaves the last jxlhip_enc_forward's state as it was. jxlenc_cpu_estimate_entropy
+ * (libjxlenc) is the CPU double with the same arguments less the context. */
+int jxlhip_enc_estimate_entropy(JxlHipContext* ctx, const JxlHipEncEstimateDesc* desc, const JxlHipEncAcsCandidate* candidates, size_t n,
+                                float* estimates, float* scaled);
+/* Kernel time of the last jxlhip_enc_estimate_entropy (all its launches, copies excluded), milliseconds. */
+int jxlhip_enc_estimate_last_ms(JxlHipContext* ctx, float* ms);
 /* Kernel time of the two quant-field kernels in the last pass of the last jxlhip_enc_forward / _rerun made with
  * quant_field_mode 1 (they are part of jxlhip_enc_last_ms too), milliseconds. */
 int jxlhip_enc_aq_last_ms(JxlHipContext* ctx, float* ms);

@@ -355,6 +355,14 @@ class HipContext:
         _check(L.jxlhip_enc_masking_last_ms(self._h, ctypes.byref(a)), "jxlhip_enc_masking_last_ms")
         return a.value
 
+    def enc_estimate_ms(self):
+        """Measurement: ms of the kernels of the last estimate_entropy on this context."""
+        L = lib()
+        L.jxlhip_enc_estimate_last_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+        a = ctypes.c_float()
+        _check(L.jxlhip_enc_estimate_last_ms(self._h, ctypes.byref(a)), "jxlhip_enc_estimate_last_ms")
+        return a.value
+
     def debug_ans_write(self, tokens, tables, capacity=None):
         """Test access: rANS-codes `tokens` ((n, 2) uint32 {context, value} pairs) as one section with the device's entropy
         kernels and the code `tables` (an AnsTables). Returns (the bit string as bytes, its length in bits); `capacity`
@@ -718,6 +726,9 @@ def _enc_lib():
             "cpu_ans_write": (c_int, [vp] * 3 + [sz]),
             "cpu_initial_quant_field": (c_int, [vp, u32, u32, ctypes.c_float, ctypes.c_float, vp, vp]),
             "cpu_masking_1x1": (c_int, [vp, u32, u32, vp]),
+            "cpu_estimate_entropy": (c_int, [vp, vp, sz, vp, vp]),
+            # (fn, ctx, xyb, xsize, ysize, quant_field, mask1x1, ytox, ytob, distance, candidates, n, estimates, scaled)
+            "estimate_entropy": (c_int, [vp, vp, vp, u32, u32, vp, vp, vp, vp, ctypes.c_float, vp, sz, vp, vp]),
             # what the next streams carry (test aids)
             "set_custom_upsampling": (None, [u32, u32]),
             "set_embedded_icc": (None, [cp, sz, sz]),
@@ -1127,6 +1138,52 @@ def masking_1x1(xyb, ctx=None):
         if r:
             raise JxlAmdError("jxlenc_cpu_masking_1x1 failed (%d)" % r)
     return out
+
+
+# JxlHipEncAcsCandidate; the blocks (x, y) the pure-DCT strategies of estimate_entropy cover
+ACS_CANDIDATE = np.dtype([("strategy", "<u4"), ("bx", "<u4"), ("by", "<u4"), ("entropy_mul", "<f4")])
+ACS_ESTIMATE_COVERED = {0: (1, 1), 4: (2, 2), 5: (4, 4), 6: (1, 2), 7: (2, 1), 8: (1, 4), 9: (4, 1), 10: (2, 4), 11: (4, 2),
+                        18: (8, 8), 19: (4, 8), 20: (8, 4)}
+
+
+def estimate_entropy(xyb, quant_field, mask1x1, ytox, ytob, distance, candidates, ctx=None, want_scaled=False):
+    """The cost estimate of the reference's AC-strategy search (EstimateEntropy) of `candidates`, (strategy, bx, by,
+    entropy_mul) each (or an ACS_CANDIDATE array), on X, Y, B planes [3][ysize][xsize] (float32, sizes multiples of 8) with
+    the quant field [ysize / 8][xsize / 8] of initial_quant_field, the masking of masking_1x1 and one int8 chroma-from-luma
+    factor per 64x64 tile: float32 estimates [n], or (estimates, scaled) where scaled holds per candidate [3][R][C] the
+    quantised values before rounding, candidates back to back. On the GPU (jxlhip_enc_estimate_entropy on `ctx`), or from
+    the CPU stream writer's own code when ctx is None; both on the default library's dequantisation tables."""
+    xyb = np.ascontiguousarray(xyb, np.float32)
+    if xyb.ndim != 3 or xyb.shape[0] != 3:
+        raise ValueError("xyb: [3][ysize][xsize]")
+    ys, xs = xyb.shape[1:]
+    tiles = ((ys + 63) // 64) * ((xs + 63) // 64)
+    qf = np.ascontiguousarray(quant_field, np.float32)
+    m = np.ascontiguousarray(mask1x1, np.float32)
+    tx, tb = np.ascontiguousarray(ytox, np.int8).ravel(), np.ascontiguousarray(ytob, np.int8).ravel()
+    if qf.size != (ys // 8) * (xs // 8) or m.size != ys * xs or tx.size != tiles or tb.size != tiles:
+        raise ValueError("quant_field [ysize / 8][xsize / 8], mask1x1 [ysize][xsize], ytox / ytob one per 64x64 tile")
+    if isinstance(candidates, np.ndarray) and candidates.dtype == ACS_CANDIDATE:
+        cand = np.ascontiguousarray(candidates)
+    else:
+        cand = np.array([tuple(c) for c in candidates], ACS_CANDIDATE)
+    n = len(cand)
+    est = np.zeros(n, np.float32)
+    scaled = None
+    if want_scaled:
+        area = sum(64 * ACS_ESTIMATE_COVERED.get(int(s), (0, 0))[0] * ACS_ESTIMATE_COVERED.get(int(s), (0, 0))[1] for s in cand["strategy"])
+        scaled = np.zeros(3 * area, np.float32)
+    fn = None
+    if ctx is not None:
+        fn = ctypes.cast(lib().jxlhip_enc_estimate_entropy, ctypes.c_void_p)
+    r = _enc_lib().jxlenc_estimate_entropy(fn, ctx._h if ctx is not None else None, xyb.ctypes.data, xs, ys, qf.ctypes.data, m.ctypes.data,
+                                           tx.ctypes.data, tb.ctypes.data, float(distance), cand.ctypes.data, n, est.ctypes.data,
+                                           scaled.ctypes.data if want_scaled else None)
+    if r:
+        if ctx is not None:
+            _check(r, "jxlhip_enc_estimate_entropy")
+        raise JxlAmdError("jxlenc_cpu_estimate_entropy failed (%d)" % r)
+    return (est, scaled) if want_scaled else est
 
 
 def encode_rgba8(img, **kw):

@@ -2137,6 +2137,152 @@ static void Masking1x1(const float* py, size_t xp, size_t yp, float* out) {
     }
 }
 
+// ---- the cost estimate of the reference's AC-strategy search (EstimateEntropy, enc_ac_strategy.cc:364-511; the weights
+// of AcStrategyHeuristics::Init :1107-1123 are jxh::EncEstimateWeights) for one pure-DCT candidate of R x C samples at
+// (x0, y0). float32, every expression written once and not contracted; k_enc_estimate (csrc/hip/jxl_hip_enc.h) restates
+// it operation by operation. The order of every sum:
+//   quant_norm16  one block: its field value; two: the larger; more: the 16th powers (three squarings, then q * q) summed
+//                 in raster order of the blocks, divided by their number, powf(., 1 / 16) (exact where the reference has
+//                 FastPowf).
+//   forward       rows t[y][kx] = sum over x = 0.. of px[y][x] * B_C[x][kx], then columns coef[ky][kx] = (sum over y = 0..
+//                 of t[y][kx] * B_R[y][ky]) * (1 / (R * C)): ForwardDct's sums, kept in the natural layout [ky][kx].
+//   val           (coef - coef_Y * factor) * ((1 / m) * quant_norm16), m the dequantisation weight of the coefficient in the
+//                 codestream layout (at ky * C + kx where R < C, else at kx * R + ky); factor = ytox / 84 for X, 0 for Y,
+//                 1 + ytob / 84 for B (YtoXRatio / YtoBRatio, chroma_from_luma.h). r = rintf(val); e = m * (val - r).
+//   inverse       columns u[y][kx] = sum over ky = 0.. of e[ky][kx] * B_R[y][ky], then rows p[y][x] = sum over kx = 0.. of
+//                 u[y][kx] * B_C[x][kx]; t = (mask1x1 + {12, 0, 4}) * p, squared three times.
+//   the three sums over a channel's R * C elements (sqrt(|r|), r != 0 as 0 / 1, t) are taken as the device's lanes take
+//                 them, EstimateLaneSum: K = 64 lanes (256 from 32x32 up) each add the elements l, l + K, .. in ascending
+//                 order; within each 64 lanes the partial sums are added pairwise at distances 32, 16 .. 1 (lane l with
+//                 lane l ^ d); the four groups of 256 as (s0 + s1) + (s2 + s3).
+//   combination   in the reference's order X, Y, B: entropy += cost_delta * sum; entropy += zeros_mul * (CeilLog2(nbits + 17)
+//                 + nbits), nbits = CeilLog2(nz + 1) + 1; loss += channel_mul * loss_c; after X alone, for two blocks or more,
+//                 entropy *= w and loss *= w. Then powf(loss / area, 1 / 8) * area / quant_norm16, entropy * entropy_mul
+//                 + info_loss_multiplier * that.
+static float EstimateLaneSum(const float* v, size_t n, size_t lanes) {
+  float part[256];
+  for (size_t l = 0; l < lanes; l++) {
+    float s = 0.0f;
+    for (size_t i = l; i < n; i += lanes) s += v[i];
+    part[l] = s;
+  }
+  float group[4] = {0, 0, 0, 0};
+  for (size_t g = 0; g < lanes / 64; g++) {
+    float* p = part + g * 64;
+    for (size_t d = 32; d > 0; d >>= 1)
+      for (size_t l = 0; l < d; l++) p[l] = p[l] + p[l + d];  // (lanes l and l ^ d hold the same sum; the low one is kept)
+    group[g] = p[0];
+  }
+  return lanes == 64 ? group[0] : (group[0] + group[1]) + (group[2] + group[3]);
+}
+static inline uint32_t CeilLog2Nonzero(uint32_t v) { return v <= 1 ? 0 : uint32_t(FloorLog2(v - 1)) + 1; }
+struct EstimateScratch {
+  std::vector<float> coef[3], t, e, sq, nzv, loss;
+};
+static float EstimateEntropy(const JxlHipEncEstimateDesc& d, const JxlHipEncAcsCandidate& cand, const float weights[3], float* scaled,
+                             EstimateScratch& S) {
+  uint32_t cx = 0, cy = 0, kind = 0;
+  jxh::EncEstimateShape(cand.strategy, &cx, &cy, &kind);
+  const size_t R = cy * 8, C = cx * 8, size = R * C, num_blocks = size_t(cx) * cy;
+  const size_t xp = d.xsize, plane = size_t(d.xsize) * d.ysize, xb = d.xsize / 8, x0 = size_t(cand.bx) * 8, y0 = size_t(cand.by) * 8;
+  const size_t lanes = size >= 1024 ? 256 : 64;
+  const float* br = GetBasis().m[FloorLog2(R)].data();
+  const float* bc = GetBasis().m[FloorLog2(C)].data();
+  const float* qf = d.quant_field + size_t(cand.by) * xb + cand.bx;
+  float quant_norm16 = 0.0f;
+  if (num_blocks == 1) {
+    quant_norm16 = qf[0];
+  } else if (num_blocks == 2) {
+    quant_norm16 = std::max(qf[0], cy == 2 ? qf[xb] : qf[1]);
+  } else {
+    for (size_t iy = 0; iy < cy; iy++)
+      for (size_t ix = 0; ix < cx; ix++) {
+        float q = qf[iy * xb + ix];
+        q *= q;
+        q *= q;
+        q *= q;
+        quant_norm16 += q * q;
+      }
+    quant_norm16 /= float(num_blocks);
+    quant_norm16 = std::pow(quant_norm16, 1.0f / 16.0f);
+  }
+  const float norm = 1.0f / (float(R) * float(C));
+  S.t.resize(size);
+  for (int c = 0; c < 3; c++) {
+    const float* px = d.xyb + plane * c + y0 * xp + x0;
+    S.coef[c].resize(size);
+    for (size_t y = 0; y < R; y++)
+      for (size_t kx = 0; kx < C; kx++) {
+        float s = 0;
+        for (size_t x = 0; x < C; x++) s += px[y * xp + x] * bc[x * C + kx];
+        S.t[y * C + kx] = s;
+      }
+    for (size_t ky = 0; ky < R; ky++)
+      for (size_t kx = 0; kx < C; kx++) {
+        float s = 0;
+        for (size_t y = 0; y < R; y++) s += S.t[y * C + kx] * br[y * R + ky];
+        S.coef[c][ky * C + kx] = s * norm;
+      }
+  }
+  const size_t tile = (cand.by / 8) * ((xb + 7) / 8) + cand.bx / 8;
+  const float factor[3] = {0.0f + float(d.ytox[tile]) / 84.0f, 0.0f, 1.0f + float(d.ytob[tile]) / 84.0f};
+  const float mask_off[3] = {12.0f, 0.0f, 4.0f};
+  float channel_mul[3];
+  jxh::EncEstimateChannelMul(channel_mul);
+  S.e.resize(size);
+  S.sq.resize(size);
+  S.nzv.resize(size);
+  S.loss.resize(size);
+  float entropy = 0.0f, loss = 0.0f;
+  for (int c = 0; c < 3; c++) {
+    const float* m = d.dequant + d.dequant_offset[kind] + size_t(c) * d.dequant_size[kind];
+    for (size_t ky = 0; ky < R; ky++)
+      for (size_t kx = 0; kx < C; kx++) {
+        const size_t k = ky * C + kx;
+        const float mk = m[R < C ? k : kx * R + ky];
+        const float in_y = S.coef[1][k] * factor[c];
+        const float val = (S.coef[c][k] - in_y) * ((1.0f / mk) * quant_norm16);
+        const float r = std::nearbyint(val);
+        if (scaled) scaled[size_t(c) * size + k] = val;
+        S.e[k] = mk * (val - r);
+        const float q = std::fabs(r);
+        S.sq[k] = std::sqrt(q);
+        S.nzv[k] = q == 0.0f ? 0.0f : 1.0f;
+      }
+    for (size_t y = 0; y < R; y++)
+      for (size_t kx = 0; kx < C; kx++) {
+        float s = 0;
+        for (size_t ky = 0; ky < R; ky++) s += S.e[ky * C + kx] * br[y * R + ky];
+        S.t[y * C + kx] = s;
+      }
+    const float* mask = d.mask1x1 + y0 * xp + x0;
+    for (size_t y = 0; y < R; y++)
+      for (size_t x = 0; x < C; x++) {
+        float s = 0;
+        for (size_t kx = 0; kx < C; kx++) s += S.t[y * C + kx] * bc[x * C + kx];
+        float t = (mask[y * xp + x] + mask_off[c]) * s;
+        t = t * t;
+        t = t * t;
+        t = t * t;
+        S.loss[y * C + x] = t;
+      }
+    entropy += weights[2] * EstimateLaneSum(S.sq.data(), size, lanes);
+    const uint32_t num_nzeros = uint32_t(EstimateLaneSum(S.nzv.data(), size, lanes));
+    const uint32_t nbits = CeilLog2Nonzero(num_nzeros + 1) + 1;
+    entropy += weights[1] * float(CeilLog2Nonzero(nbits + 17) + nbits);
+    loss += channel_mul[c] * EstimateLaneSum(S.loss.data(), size, lanes);
+    if (c == 0 && num_blocks >= 2) {
+      const float w = jxh::EncEstimateXWeight(uint32_t(num_blocks));
+      entropy *= w;
+      loss *= w;
+    }
+  }
+  const float loss_scalar = std::pow(loss / float(size), 1.0f / 8.0f) * float(size) / quant_norm16;
+  entropy *= cand.entropy_mul;
+  entropy += weights[0] * loss_scalar;
+  return entropy;
+}
+
 // The alpha plane of jxlenc_encode_rgba8 with its geometry: w x h samples (w = 0: frame sized), the extra channel's upsampling
 // factor and its shift against the frame.
 struct AlphaPlane {
@@ -2215,28 +2361,39 @@ static void HookCheck(int r, const char* which) {
 }
 
 // The forward path's descriptor of a frame BeginFrame has set up (ytox / ytob: the frame's own, written by the call).
-static JxlHipEncDesc ForwardDesc(FrameModel& f, const Params& p, float quant_ac) {
-  // the default dequantisation tables, flat, built once (they do not depend on the image)
-  static std::vector<float> flat;
-  static uint32_t flat_offset[17], flat_size[17];
-  static std::once_flag flat_once;
-  std::call_once(flat_once, [] {
+// The default dequantisation tables, flat, built once (they do not depend on the image), into the fields that
+// JxlHipEncDesc and JxlHipEncEstimateDesc share.
+struct DefaultDequantTables {
+  std::vector<float> flat;
+  uint32_t offset[17], size[17];
+  DefaultDequantTables() {
     jxh::DequantTables dq;
     for (int k = 0; k < 17; k++) {
-      flat_offset[k] = flat_size[k] = 0;
+      offset[k] = size[k] = 0;
       if (k >= 13) continue;  // 128 / 256 point tables: never selected here, not built
       dq.Compute(k);
-      flat_offset[k] = uint32_t(flat.size());
-      flat_size[k] = uint32_t(dq.table[k].size() / 3);
+      offset[k] = uint32_t(flat.size());
+      size[k] = uint32_t(dq.table[k].size() / 3);
       flat.insert(flat.end(), dq.table[k].begin(), dq.table[k].end());
     }
-  });
+  }
+};
+static const DefaultDequantTables& GetDefaultDequant() {
+  static const DefaultDequantTables t;
+  return t;
+}
+template <class Desc>
+static void DefaultDequant(Desc* d) {
+  const DefaultDequantTables& t = GetDefaultDequant();
+  memcpy(d->dequant_offset, t.offset, sizeof(t.offset));
+  memcpy(d->dequant_size, t.size, sizeof(t.size));
+  d->dequant = t.flat.data();
+  d->dequant_floats = uint32_t(t.flat.size());
+}
+static JxlHipEncDesc ForwardDesc(FrameModel& f, const Params& p, float quant_ac) {
   JxlHipEncDesc d;
   memset(&d, 0, sizeof(d));
-  memcpy(d.dequant_offset, flat_offset, sizeof(flat_offset));
-  memcpy(d.dequant_size, flat_size, sizeof(flat_size));
-  d.dequant = flat.data();
-  d.dequant_floats = uint32_t(flat.size());
+  DefaultDequant(&d);
   d.xsize = uint32_t(f.xs);
   d.ysize = uint32_t(f.ys);
   d.distance = p.distance;
@@ -3982,6 +4139,57 @@ int jxlenc_cpu_masking_1x1(const float* xyb, uint32_t xsize, uint32_t ysize, flo
     return -2;
   }
   return 0;
+}
+
+// The CPU double of jxlhip_enc_estimate_entropy (include/jxl_amd_hip.h): the same arguments without the context.
+int jxlenc_cpu_estimate_entropy(const JxlHipEncEstimateDesc* d, const JxlHipEncAcsCandidate* cand, size_t n, float* estimates, float* scaled) {
+  jxe::UseThreads();
+  if (!jxh::EncEstimateArgsOk(d, cand, n, estimates, nullptr)) return -1;
+  try {
+    float weights[3];
+    jxh::EncEstimateWeights(d->distance, weights);
+    std::vector<size_t> start(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+      uint32_t cx = 0, cy = 0, kind = 0;
+      jxh::EncEstimateShape(cand[i].strategy, &cx, &cy, &kind);
+      start[i + 1] = start[i] + size_t(3) * cx * cy * 64;
+    }
+#pragma omp parallel
+    {
+      jxe::EstimateScratch scratch;
+#pragma omp for schedule(dynamic, 16)
+      for (size_t i = 0; i < n; i++) estimates[i] = jxe::EstimateEntropy(*d, cand[i], weights, scaled ? scaled + start[i] : nullptr, scratch);
+    }
+  } catch (...) {
+    return -2;
+  }
+  return 0;
+}
+
+// The estimate through either form, `fn` being jxlhip_enc_estimate_entropy with its context, or NULL for the CPU double
+// (which takes no context), on the default library's dequantisation tables (what jxlenc_forward_model gives the forward call).
+typedef int (*JxlEncEstimateFn)(void* ctx, const JxlHipEncEstimateDesc* desc, const JxlHipEncAcsCandidate* cand, size_t n, float* estimates,
+                                float* scaled);
+int jxlenc_estimate_entropy(void* fn, void* ctx, const float* xyb, uint32_t xsize, uint32_t ysize, const float* quant_field, const float* mask1x1,
+                            const int8_t* ytox, const int8_t* ytob, float distance, const JxlHipEncAcsCandidate* cand, size_t n, float* estimates,
+                            float* scaled) {
+  JxlHipEncEstimateDesc d;
+  memset(&d, 0, sizeof(d));
+  try {
+    jxe::DefaultDequant(&d);
+  } catch (...) {
+    return -2;
+  }
+  d.xyb = xyb;
+  d.xsize = xsize;
+  d.ysize = ysize;
+  d.quant_field = quant_field;
+  d.mask1x1 = mask1x1;
+  d.ytox = ytox;
+  d.ytob = ytob;
+  d.distance = distance;
+  if (fn) return reinterpret_cast<JxlEncEstimateFn>(fn)(ctx, &d, cand, n, estimates, scaled);
+  return jxlenc_cpu_estimate_entropy(&d, cand, n, estimates, scaled);
 }
 
 // Test access: the raw outputs of one forward call made with the descriptor jxlenc_encode_rgb8_hooks builds

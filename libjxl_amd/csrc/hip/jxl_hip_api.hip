@@ -272,6 +272,11 @@ struct JxlHipContext {
   Buf enc_mask1x1;                                        // the per-pixel masking of jxlhip_enc_masking_1x1 (its Y plane goes through enc_aq_in)
   hipEvent_t mask_ev[2] = {nullptr, nullptr};             // ... and its kernel's time
   bool mask_timed = false;
+  // jxlhip_enc_estimate_entropy: its inputs (planes, quant field, mask1x1, factors, tables), the sorted candidates with
+  // their places and `scaled` offsets, and its outputs; its kernels' time
+  Buf est_planes, est_qf, est_mask, est_ytox, est_ytob, est_dq, est_cand, est_index, est_at, est_out, est_scaled;
+  hipEvent_t est_ev[2] = {nullptr, nullptr};
+  bool est_timed = false;
   bool enc_last_gaborish = false;
   uint32_t out_orient = 0;  // jxlhip_set_output_orientation: PixelOut::orient bits (0 = the image as coded)
   bool out_unpremul = false;  // jxlhip_set_output_unpremultiply (PixelOut::orient bit 3 for outputs that carry alpha)
@@ -465,6 +470,7 @@ static JxlHipContext* RecycleContext(int device) {
   for (size_t i = 0; i < sizeof(c->enc_ev) / sizeof(c->enc_ev[0]); i++) std::swap(c->enc_ev[i], o->enc_ev[i]);
   for (size_t i = 0; i < sizeof(c->ent_ev) / sizeof(c->ent_ev[0]); i++) std::swap(c->ent_ev[i], o->ent_ev[i]);
   for (size_t i = 0; i < sizeof(c->mask_ev) / sizeof(c->mask_ev[0]); i++) std::swap(c->mask_ev[i], o->mask_ev[i]);
+  for (size_t i = 0; i < sizeof(c->est_ev) / sizeof(c->est_ev[0]); i++) std::swap(c->est_ev[i], o->est_ev[i]);
   std::swap(c->stage, o->stage);
   jxlhip_ctx_destroy(o);  // (what is left of it: lazily created events, a stream of its own)
   return c;
@@ -542,6 +548,7 @@ static std::vector<Buf*> AllBufs(JxlHipContext* c) {
                 &c->enc_tok_off, &c->enc_tok_nzmap, &c->enc_tok_small, &c->enc_tok_out, &c->enc_tok_base, &c->tb_params, &c->tb_desc, &c->fb_params, &c->alpha, &c->sec_end, &c->lz_window, &c->mod.pool, &c->mod.sections, &c->mod.blob, &c->mod.streams,
                 &c->mod.rects, &c->mod.status, &c->mod.end_bits, &c->mod.scratch, &c->mod.windows, &c->mod.batch_streams, &c->mod.batch_ops, &c->frame_blob, &c->noise, &c->spl_seg, &c->spl_row_start, &c->spl_row_seg, &c->spl_planes, &c->pat_rec, &c->pat_row_start, &c->pat_row_list,
                 &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in, &c->enc_mask1x1,
+                &c->est_planes, &c->est_qf, &c->est_mask, &c->est_ytox, &c->est_ytob, &c->est_dq, &c->est_cand, &c->est_index, &c->est_at, &c->est_out, &c->est_scaled,
                 &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
   for (auto& pb : c->pass_bufs)
     for (Buf* b : {&pb.ctx_map, &pb.alias, &pb.cfg, &pb.orders, &pb.ptable, &pb.poffset, &pb.alias_packed}) all.push_back(b);
@@ -573,6 +580,8 @@ void jxlhip_ctx_destroy(JxlHipContext* c) {
   for (auto& ev : c->ent_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : c->mask_ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : c->est_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (c->stage.done) (void)hipEventDestroy(c->stage.done);
   if (c->stage.p) (void)hipHostFree(c->stage.p);
@@ -4154,6 +4163,107 @@ int jxlhip_enc_masking_last_ms(JxlHipContext* c, float* ms) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipEventSynchronize(c->mask_ev[1]));
   HIP_TRY(hipEventElapsedTime(ms, c->mask_ev[0], c->mask_ev[1]));
+  return 0;
+}
+
+// The cost estimate of the AC-strategy search (k_enc_estimate, jxl_hip_enc.h). Everything is checked here, on the host
+// (jxh::EncEstimateArgsOk: every candidate inside the planes and one tile, every table of the right size); the candidates are
+// sorted by strategy (stable) and each strategy present is one launch of the form its size asks for.
+int jxlhip_enc_estimate_entropy(JxlHipContext* c, const JxlHipEncEstimateDesc* d, const JxlHipEncAcsCandidate* cand, size_t n, float* estimates,
+                                float* scaled) {
+  size_t total_area = 0;
+  if (!c || !jxh::EncEstimateArgsOk(d, cand, n, estimates, &total_area) || n > (size_t(1) << 30)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  for (auto& ev : c->est_ev)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  if (!n) {
+    HIP_TRY(hipEventRecord(c->est_ev[0], c->stream));
+    HIP_TRY(hipEventRecord(c->est_ev[1], c->stream));
+    c->est_timed = true;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  const uint32_t xb = d->xsize / 8, yb = d->ysize / 8, tiles_x = (xb + 7) / 8, tiles_y = (yb + 7) / 8;
+  const size_t plane = size_t(d->xsize) * d->ysize, nb = size_t(xb) * yb, ntiles = size_t(tiles_x) * tiles_y;
+  // the candidates in launch order: by strategy, the caller's order inside one
+  std::vector<uint32_t> index(n);
+  for (size_t i = 0; i < n; i++) index[i] = uint32_t(i);
+  std::stable_sort(index.begin(), index.end(), [&](uint32_t a, uint32_t b) { return cand[a].strategy < cand[b].strategy; });
+  std::vector<JxlHipEncAcsCandidate> sorted(n);
+  std::vector<unsigned long long> start(n + 1, 0), at(n);
+  for (size_t i = 0; i < n; i++) {
+    uint32_t cx = 0, cy = 0, kind = 0;
+    jxh::EncEstimateShape(cand[i].strategy, &cx, &cy, &kind);
+    start[i + 1] = start[i] + 3ull * cx * cy * 64;
+  }
+  for (size_t i = 0; i < n; i++) {
+    sorted[i] = cand[index[i]];
+    at[i] = start[index[i]];
+  }
+  int r;
+  if ((r = c->est_planes.Ensure(3 * plane * 4)) || (r = c->est_qf.Ensure(nb * 4)) || (r = c->est_mask.Ensure(plane * 4)) ||
+      (r = c->est_ytox.Ensure(ntiles)) || (r = c->est_ytob.Ensure(ntiles)) || (r = c->est_dq.Ensure(size_t(d->dequant_floats) * 4)) ||
+      (r = c->est_cand.Ensure(n * sizeof(JxlHipEncAcsCandidate))) || (r = c->est_index.Ensure(n * 4)) || (r = c->est_at.Ensure(n * 8)) ||
+      (r = c->est_out.Ensure(n * 4)) || (scaled && (r = c->est_scaled.Ensure(3 * total_area * 4))))
+    return r;
+  HIP_TRY(hipMemcpyAsync(c->est_planes.p, d->xyb, 3 * plane * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->est_qf.p, d->quant_field, nb * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->est_mask.p, d->mask1x1, plane * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->est_ytox.p, d->ytox, ntiles, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->est_ytob.p, d->ytob, ntiles, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->est_dq.p, d->dequant, size_t(d->dequant_floats) * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->est_cand.p, sorted.data(), n * sizeof(JxlHipEncAcsCandidate), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->est_index.p, index.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->est_at.p, at.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+  jxlhip::EncEstimate P;
+  memset(&P, 0, sizeof(P));
+  P.planes = c->est_planes.as<float>();
+  P.quant = c->est_qf.as<float>();
+  P.mask = c->est_mask.as<float>();
+  P.ytox = c->est_ytox.as<int8_t>();
+  P.ytob = c->est_ytob.as<int8_t>();
+  P.basis_t = c->basis.as<float>() + kBasisTransposed;
+  P.estimates = c->est_out.as<float>();
+  P.scaled = scaled ? c->est_scaled.as<float>() : nullptr;
+  P.xp = d->xsize;
+  P.yp = d->ysize;
+  P.xb = xb;
+  P.tiles_x = tiles_x;
+  jxh::EncEstimateWeights(d->distance, P.weights);
+  jxh::EncEstimateChannelMul(P.channel_mul);
+  HIP_TRY(hipEventRecord(c->est_ev[0], c->stream));
+  for (size_t first = 0; first < n;) {
+    size_t last = first;
+    while (last < n && sorted[last].strategy == sorted[first].strategy) last++;
+    uint32_t kind = 0;
+    jxh::EncEstimateShape(sorted[first].strategy, &P.cx, &P.cy, &kind);
+    P.dequant = c->est_dq.as<float>() + d->dequant_offset[kind];
+    P.cand = c->est_cand.as<JxlHipEncAcsCandidate>() + first;
+    P.index = c->est_index.as<uint32_t>() + first;
+    P.scaled_at = c->est_at.as<unsigned long long>() + first;
+    P.n = uint32_t(last - first);
+    P.x_weight = P.cx * P.cy >= 2 ? jxh::EncEstimateXWeight(P.cx * P.cy) : 1.0f;
+    const uint32_t area = P.cx * P.cy * 64;
+    if (area < 1024) hipLaunchKernelGGL((jxlhip::k_enc_estimate<64, 1>), dim3((P.n + 3) / 4), dim3(256), 0, c->stream, P);
+    else if (area == 1024) hipLaunchKernelGGL((jxlhip::k_enc_estimate<256, 4>), dim3(P.n), dim3(256), 0, c->stream, P);
+    else hipLaunchKernelGGL((jxlhip::k_enc_estimate<256, 8>), dim3(P.n), dim3(256), 0, c->stream, P);
+    HIP_TRY(hipGetLastError());
+    first = last;
+  }
+  HIP_TRY(hipEventRecord(c->est_ev[1], c->stream));
+  c->est_timed = true;
+  HIP_TRY(hipMemcpyAsync(estimates, c->est_out.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (scaled) HIP_TRY(hipMemcpyAsync(scaled, c->est_scaled.p, 3 * total_area * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int jxlhip_enc_estimate_last_ms(JxlHipContext* c, float* ms) {
+  if (!c || !ms) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->est_timed) return JXLHIP_ERR_NO_FRAME;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->est_ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, c->est_ev[0], c->est_ev[1]));
   return 0;
 }
 

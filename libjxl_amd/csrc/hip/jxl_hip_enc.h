@@ -6,7 +6,9 @@
 // reference's AC-strategy search (enc_ac_strategy.cc:827-1068), and there is no Butteraugli loop
 // (enc_adaptive_quantization.cc:707-1115): those stay out. The quant field is the writer's own activity rule by default;
 // with quant_field_mode 1 it is the reference's initial adaptive quant field (enc_adaptive_quantization.cc:88-449,
-// 466-628, 1198-1247: k_enc_aq_cells, k_enc_aq_blocks and the tail of k_enc_select<true>). Every float expression keeps the
+// 466-628, 1198-1247: k_enc_aq_cells, k_enc_aq_blocks and the tail of k_enc_select<true>). Two inputs of the reference's search
+// exist as stand-alone entries that the forward path does not call yet: the per-pixel masking (k_enc_mask1x1) and the cost
+// estimate of a list of pure-DCT candidates (k_enc_estimate: EstimateEntropy, enc_ac_strategy.cc:364-511). Every float expression keeps the
 // operation order of the CPU writer with contraction off, so that the two agree except where cbrtf / log2f / exp2f differ
 // in the last place.
 #ifndef JXL_HIP_ENC_H_
@@ -881,6 +883,235 @@ __global__ __launch_bounds__(256) void k_enc_transform_tile(EncFwd P) {
         d4[1] = make_int4(q[4], q[5], q[6], q[7]);
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------- cost estimate of the AC-strategy search
+// EstimateEntropy of the reference (enc_ac_strategy.cc:364-511) for a list of candidate transforms of ONE pure-DCT kind
+// (the launch layer sorts a caller's list by kind), as csrc/enc/jxl_enc.cc EstimateEntropy states it in float32: the three
+// forward transforms, val = (coef - factor * coef_Y) * ((1 / m) * quant_norm16), its rounding, m * (val - round(val)) taken
+// back to pixels, times mask1x1 + {12, 0, 4}, to the eighth power, and the sums of sqrt(|round|), of the non-zero roundings
+// and of that loss. An estimate depends on its candidate alone, so the order of the list does not matter.
+// Two forms, by the transform's size:
+//   k_enc_estimate<64, 1>   a wave per candidate, four candidates per workgroup, for 64 .. 512 samples (8x8 .. 32x16): every
+//                           lane forms one output of a pass at a time (an 8x8 has exactly one per lane)
+//   k_enc_estimate<256, NB> a workgroup per candidate from 32x32 up: a thread accumulates NB outputs (4 at 32x32, else 8)
+//                           against one matrix element at a time, as k_enc_transform_tile does
+// Per group three LDS buffers of the transform's size (at most 16 KB each: 48 KB per workgroup, three workgroups per CU):
+// a (samples, then X's / B's coefficients, then the error, then the loss terms), t (the pass between rows and columns) and
+// y (Y's coefficients, which X and B are predicted from: Y is processed first, the three shares are kept apart and combined
+// by one lane in the reference's order X, Y, B). The DCT matrices up to 32 points are in LDS (the wave form: all of 1 .. 32;
+// the workgroup form: the 32-point one, which is all it needs besides the 64-point one); the 64-point one is read in place.
+// The inverse's column pass stores its result transposed so that the row pass reads LDS conflict-free.
+// Sums: the four matrix passes add in the CPU statement's order (index ascending, not contracted). The three reductions
+// follow EstimateLaneSum of the CPU statement, which was written to their shape: lane l adds elements l, l + lanes, ..;
+// within a wave pairwise at distances 32 .. 1 (shfl_xor: both partners form the same sum); the four waves of a workgroup
+// through LDS as (s0 + s1) + (s2 + s3). No atomics: the result does not depend on scheduling. The quant field's 16-norm is
+// summed by every lane alike in raster order, as the CPU statement does.
+struct EncEstimate {
+  const float* planes;  // [3][yp][xp]
+  const float* quant;   // [yp / 8][xb] the quant field per block
+  const float* mask;    // [yp][xp] mask1x1
+  const int8_t* ytox;   // per 64x64 tile
+  const int8_t* ytob;
+  const float* basis_t;                // [n][k] DCT matrices, level of N points at (N * N - 1) / 3
+  const float* dequant;                // this kind's weights: [3][R * C] in the codestream layout
+  const JxlHipEncAcsCandidate* cand;   // this launch's candidates (all of one strategy)
+  const uint32_t* index;               // ... their places in the caller's list
+  const unsigned long long* scaled_at; // ... where their `scaled` values start (read only if scaled is set)
+  float* estimates;                    // [the caller's n]
+  float* scaled;                       // or NULL
+  uint32_t n, xp, yp, xb, tiles_x;
+  uint32_t cx, cy;                     // blocks covered by the launch's transform
+  float weights[3];                    // info_loss_multiplier, zeros_mul, cost_delta
+  float channel_mul[3];
+  float x_weight;                      // (1 for a single block)
+};
+__device__ __forceinline__ uint32_t EncCeilLog2Nonzero(uint32_t v) { return v <= 1 ? 0u : 32u - uint32_t(__clz(int(v - 1))); }
+template <int kLanes, int NB>
+__global__ __launch_bounds__(256) void k_enc_estimate(EncEstimate P) {
+#pragma clang fp contract(off)
+  constexpr int kGroups = 256 / kLanes, kBuf = kLanes == 64 ? 512 : 4096, kWaves = kLanes / 64;
+  constexpr int kBasisFirst = kLanes == 64 ? 0 : 341, kBasisFloats = kLanes == 64 ? 1365 : 1024;
+  __shared__ __attribute__((aligned(16))) float s_buf[kGroups][3][kBuf];
+  __shared__ __attribute__((aligned(16))) float s_basis[kBasisFloats];
+  __shared__ float s_red[kGroups][3][kWaves], s_share[kGroups][3][3];
+  const uint32_t tid = threadIdx.x, grp = tid / kLanes, lane = tid % kLanes;
+  const uint32_t R = P.cy * 8, C = P.cx * 8, size = R * C, lc = 31u - uint32_t(__clz(int(C))), lr = 31u - uint32_t(__clz(int(R)));
+  const uint32_t num_blocks = P.cx * P.cy, items = size / NB;
+  for (int i = tid; i < kBasisFloats; i += 256) s_basis[i] = P.basis_t[kBasisFirst + i];
+  const uint32_t slot = blockIdx.x * kGroups + grp;
+  const bool live = slot < P.n;  // (a workgroup's last waves may have no candidate: they follow the last one and write nothing)
+  const JxlHipEncAcsCandidate cand = P.cand[live ? slot : P.n - 1];
+  const uint32_t x0 = cand.bx * 8, y0 = cand.by * 8;
+  float* const a = s_buf[grp][0];
+  float* const t = s_buf[grp][1];
+  float* const yc = s_buf[grp][2];
+  const float* bc = C == 64 ? P.basis_t + 1365 : s_basis + ((C * C - 1) / 3 - kBasisFirst);
+  const float* br = R == 64 ? P.basis_t + 1365 : s_basis + ((R * R - 1) / 3 - kBasisFirst);
+  // quant_norm16 (:384-414)
+  const float* qf = P.quant + size_t(cand.by) * P.xb + cand.bx;
+  float quant_norm16 = 0.0f;
+  if (num_blocks == 1) {
+    quant_norm16 = qf[0];
+  } else if (num_blocks == 2) {
+    quant_norm16 = fmaxf(qf[0], P.cy == 2 ? qf[P.xb] : qf[1]);
+  } else {
+    for (uint32_t iy = 0; iy < P.cy; iy++)
+      for (uint32_t ix = 0; ix < P.cx; ix++) {
+        float q = qf[iy * P.xb + ix];
+        q *= q;
+        q *= q;
+        q *= q;
+        quant_norm16 += q * q;
+      }
+    quant_norm16 /= float(num_blocks);
+    quant_norm16 = powf(quant_norm16, 1.0f / 16.0f);
+  }
+  const uint32_t tile = (cand.by / 8) * P.tiles_x + cand.bx / 8;
+  const float norm = 1.0f / (float(R) * float(C));
+  const size_t plane = size_t(P.xp) * P.yp;
+  __syncthreads();
+  for (int ci = 0; ci < 3; ci++) {
+    const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
+    const float* src = P.planes + plane * c + size_t(y0) * P.xp + x0;
+    for (uint32_t i = lane; i < size; i += kLanes) a[i] = src[size_t(i >> lc) * P.xp + (i & (C - 1))];
+    __syncthreads();
+    // forward rows: t[y][kx] = sum_x a[y][x] * B_C[x][kx]
+    for (uint32_t w = lane; w < items; w += kLanes) {
+      const uint32_t kx = w & (C - 1), r0 = (w >> lc) * NB;
+      float acc[NB];
+#pragma unroll
+      for (int j = 0; j < NB; j++) acc[j] = 0.0f;
+      for (uint32_t x = 0; x < C; x++) {
+        const float b = bc[x * C + kx];
+#pragma unroll
+        for (int j = 0; j < NB; j++) acc[j] += a[(r0 + j) * C + x] * b;
+      }
+#pragma unroll
+      for (int j = 0; j < NB; j++) t[(r0 + j) * C + kx] = acc[j];
+    }
+    __syncthreads();
+    // forward columns: coef[ky][kx] = (sum_y t[y][kx] * B_R[y][ky]) * norm, natural layout; Y's stay in yc
+    float* const coef = c == 1 ? yc : a;
+    for (uint32_t w = lane; w < items; w += kLanes) {
+      const uint32_t kx = w & (C - 1), k0 = (w >> lc) * NB;
+      float acc[NB];
+#pragma unroll
+      for (int j = 0; j < NB; j++) acc[j] = 0.0f;
+      for (uint32_t y = 0; y < R; y++) {
+        const float v = t[y * C + kx];
+#pragma unroll
+        for (int j = 0; j < NB; j++) acc[j] += v * br[y * R + k0 + j];
+      }
+#pragma unroll
+      for (int j = 0; j < NB; j++) coef[(k0 + j) * C + kx] = acc[j] * norm;
+    }
+    __syncthreads();
+    // val, its rounding, the error times the weight (:428-444)
+    const float factor = c == 0 ? 0.0f + float(P.ytox[tile]) / 84.0f : (c == 1 ? 0.0f : 1.0f + float(P.ytob[tile]) / 84.0f);
+    const float* m = P.dequant + size_t(c) * size;
+    float* const out = P.scaled && live ? P.scaled + P.scaled_at[slot] + size_t(c) * size : nullptr;
+    float sum_sqrt = 0.0f, sum_nz = 0.0f, sum_loss = 0.0f;
+    for (uint32_t k = lane; k < size; k += kLanes) {
+      const uint32_t ky = k >> lc, kx = k & (C - 1);
+      const float mk = m[R < C ? k : kx * R + ky];
+      const float in_y = yc[k] * factor;
+      const float val = (coef[k] - in_y) * ((1.0f / mk) * quant_norm16);
+      const float r = rintf(val);
+      if (out) out[k] = val;
+      const float e = mk * (val - r);
+      const float q = fabsf(r);
+      sum_sqrt += sqrtf(q);
+      sum_nz += q == 0.0f ? 0.0f : 1.0f;
+      a[k] = e;  // (X's and B's coefficients are not needed again; Y's stay in yc)
+    }
+    __syncthreads();
+    // inverse columns: u[y][kx] = sum_ky e[ky][kx] * B_R[y][ky], stored transposed: t[kx][y]
+    for (uint32_t w = lane; w < items; w += kLanes) {
+      const uint32_t kx = w & (C - 1), r0 = (w >> lc) * NB;
+      float acc[NB];
+#pragma unroll
+      for (int j = 0; j < NB; j++) acc[j] = 0.0f;
+      for (uint32_t ky = 0; ky < R; ky++) {
+        const float v = a[ky * C + kx];
+#pragma unroll
+        for (int j = 0; j < NB; j++) acc[j] += v * br[(r0 + j) * R + ky];
+      }
+#pragma unroll
+      for (int j = 0; j < NB; j++) t[kx * R + r0 + j] = acc[j];
+    }
+    __syncthreads();
+    // inverse rows: p[y][x] = sum_kx u[y][kx] * B_C[x][kx]; the masked eighth power into a[y][x] (:457-479)
+    const float mask_off = c == 0 ? 12.0f : (c == 1 ? 0.0f : 4.0f);
+    const float* mask = P.mask + size_t(y0) * P.xp + x0;
+    for (uint32_t w = lane; w < items; w += kLanes) {
+      const uint32_t y = w & (R - 1), c0 = (w >> lr) * NB;
+      float acc[NB];
+#pragma unroll
+      for (int j = 0; j < NB; j++) acc[j] = 0.0f;
+      for (uint32_t kx = 0; kx < C; kx++) {
+        const float v = t[kx * R + y];
+#pragma unroll
+        for (int j = 0; j < NB; j++) acc[j] += v * bc[(c0 + j) * C + kx];
+      }
+#pragma unroll
+      for (int j = 0; j < NB; j++) {
+        float v = (mask[size_t(y) * P.xp + c0 + j] + mask_off) * acc[j];
+        v = v * v;
+        v = v * v;
+        v = v * v;
+        a[y * C + c0 + j] = v;
+      }
+    }
+    __syncthreads();
+    for (uint32_t k = lane; k < size; k += kLanes) sum_loss += a[k];
+    // the three sums of the group: within a wave, then across the waves
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      sum_sqrt = sum_sqrt + __shfl_xor(sum_sqrt, d, 64);
+      sum_nz = sum_nz + __shfl_xor(sum_nz, d, 64);
+      sum_loss = sum_loss + __shfl_xor(sum_loss, d, 64);
+    }
+    if (kWaves > 1) {
+      if ((lane & 63) == 0) {
+        s_red[grp][0][lane >> 6] = sum_sqrt;
+        s_red[grp][1][lane >> 6] = sum_nz;
+        s_red[grp][2][lane >> 6] = sum_loss;
+      }
+      __syncthreads();
+      if (lane == 0) {
+        sum_sqrt = (s_red[grp][0][0] + s_red[grp][0][1 % kWaves]) + (s_red[grp][0][2 % kWaves] + s_red[grp][0][3 % kWaves]);
+        sum_nz = (s_red[grp][1][0] + s_red[grp][1][1 % kWaves]) + (s_red[grp][1][2 % kWaves] + s_red[grp][1][3 % kWaves]);
+        sum_loss = (s_red[grp][2][0] + s_red[grp][2][1 % kWaves]) + (s_red[grp][2][2 % kWaves] + s_red[grp][2][3 % kWaves]);
+      }
+    }
+    if (lane == 0) {
+      s_share[grp][c][0] = sum_sqrt;
+      s_share[grp][c][1] = sum_nz;
+      s_share[grp][c][2] = sum_loss;
+    }
+    __syncthreads();  // (a, t and s_red are written again by the next channel)
+  }
+  if (lane == 0 && live) {
+    // :488-509, in the reference's channel order
+    float entropy = 0.0f, loss = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      entropy += P.weights[2] * s_share[grp][c][0];
+      const uint32_t num_nzeros = uint32_t(s_share[grp][c][1]);
+      const uint32_t nbits = EncCeilLog2Nonzero(num_nzeros + 1) + 1;
+      entropy += P.weights[1] * float(EncCeilLog2Nonzero(nbits + 17) + nbits);
+      loss += P.channel_mul[c] * s_share[grp][c][2];
+      if (c == 0 && num_blocks >= 2) {
+        entropy *= P.x_weight;
+        loss *= P.x_weight;
+      }
+    }
+    const float loss_scalar = powf(loss / float(size), 1.0f / 8.0f) * float(size) / quant_norm16;
+    entropy *= cand.entropy_mul;
+    entropy += P.weights[0] * loss_scalar;
+    P.estimates[P.index[slot]] = entropy;
   }
 }
 

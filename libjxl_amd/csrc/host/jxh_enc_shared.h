@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../../include/jxl_amd_hip.h"  // JxlHipEncAnsDesc
+#include "../../../include/jxl_amd_hip.h"  // JxlHipEncAnsDesc, JxlHipEncEstimateDesc, JxlHipEncAcsCandidate
 
 namespace jxh {
 
@@ -61,6 +61,70 @@ inline float EncMeanMaxMixer(float distance) {
   float mean_max_mixer = 1.0f;
   if (distance > 1.54138f) mean_max_mixer = std::max(0.0f, 1.0f - (distance - 1.54138f) * 0.56391f);
   return mean_max_mixer;
+}
+
+// ---- the cost estimate of the AC-strategy search (jxlhip_enc_estimate_entropy and its CPU double)
+// The three weights of EstimateEntropy that depend on the distance alone (AcStrategyHeuristics::Init,
+// enc_ac_strategy.cc:1107-1123), float32 as ACSConfig holds them: {info_loss_multiplier, zeros_mul, cost_delta}.
+inline void EncEstimateWeights(float distance, float w[3]) {
+  const float kBias = 0.13731742964354549f;
+  const float ratio = (distance + kBias) / (1.0f + kBias);
+  w[0] = 1.2f;
+  w[1] = 9.3089059022677905f;
+  w[2] = 10.833273317067883f;
+  w[0] *= std::pow(ratio, 0.33677806662454718f);
+  w[1] *= std::pow(ratio, 0.50990926717963703f);
+  w[2] *= std::pow(ratio, 0.36702940662370243f);
+}
+// The weight of X's share for a transform of num_blocks >= 2 blocks (:499), and the weights of the channels' eighth-power
+// losses (:480-485: doubles rounded to float)
+inline float EncEstimateXWeight(uint32_t num_blocks) { return float(1.0 + std::min(3.0, num_blocks / 8.0)); }
+inline void EncEstimateChannelMul(float m[3]) {
+  m[0] = float(std::pow(8.2, 8.0));
+  m[1] = float(std::pow(1.0, 8.0));
+  m[2] = float(std::pow(1.03, 8.0));
+}
+// Blocks covered (x, y) and dequantisation-table kind of the pure-DCT strategies the estimate takes (ac_strategy.h:130-167,
+// quant_weights.h:352-382); false for any other strategy.
+inline bool EncEstimateShape(uint32_t strategy, uint32_t* cx, uint32_t* cy, uint32_t* kind) {
+  switch (strategy) {
+    case 0: *cx = 1, *cy = 1, *kind = 0; return true;    // 8x8
+    case 4: *cx = 2, *cy = 2, *kind = 4; return true;    // 16x16
+    case 5: *cx = 4, *cy = 4, *kind = 5; return true;    // 32x32
+    case 6: *cx = 1, *cy = 2, *kind = 6; return true;    // 16x8 (rows x columns)
+    case 7: *cx = 2, *cy = 1, *kind = 6; return true;    // 8x16
+    case 8: *cx = 1, *cy = 4, *kind = 7; return true;    // 32x8
+    case 9: *cx = 4, *cy = 1, *kind = 7; return true;    // 8x32
+    case 10: *cx = 2, *cy = 4, *kind = 8; return true;   // 32x16
+    case 11: *cx = 4, *cy = 2, *kind = 8; return true;   // 16x32
+    case 18: *cx = 8, *cy = 8, *kind = 11; return true;  // 64x64
+    case 19: *cx = 4, *cy = 8, *kind = 12; return true;  // 64x32
+    case 20: *cx = 8, *cy = 4, *kind = 12; return true;  // 32x64
+    default: return false;
+  }
+}
+// Everything both forms check before they touch a plane: pointers, sizes, the tables of every kind a candidate uses, and
+// each candidate inside the planes and inside one 64x64 tile. *total_area: the samples of all candidates together.
+inline bool EncEstimateArgsOk(const JxlHipEncEstimateDesc* d, const JxlHipEncAcsCandidate* cand, size_t n, const float* estimates, size_t* total_area) {
+  if (!d || (n && (!cand || !estimates))) return false;
+  if (!d->xyb || !d->quant_field || !d->mask1x1 || !d->ytox || !d->ytob || !d->dequant) return false;
+  if (!d->xsize || !d->ysize || (d->xsize & 7) || (d->ysize & 7) || d->xsize > (1u << 18) || d->ysize > (1u << 18)) return false;
+  if (!(d->distance > 0) || !std::isfinite(d->distance)) return false;
+  for (int k = 0; k < 17; k++)
+    if (size_t(d->dequant_offset[k]) + 3 * size_t(d->dequant_size[k]) > d->dequant_floats) return false;
+  const uint32_t xb = d->xsize / 8, yb = d->ysize / 8;
+  size_t area = 0;
+  for (size_t i = 0; i < n; i++) {
+    uint32_t cx, cy, kind;
+    if (!EncEstimateShape(cand[i].strategy, &cx, &cy, &kind)) return false;
+    if (d->dequant_size[kind] != cx * cy * 64) return false;
+    if (cand[i].bx >= xb || cand[i].by >= yb || cx > xb - cand[i].bx || cy > yb - cand[i].by) return false;
+    if ((cand[i].bx & 7) + cx > 8 || (cand[i].by & 7) + cy > 8) return false;
+    if (!std::isfinite(cand[i].entropy_mul)) return false;
+    area += size_t(cx) * cy * 64;
+  }
+  if (total_area) *total_area = area;
+  return true;
 }
 
 // sRGB EOTF of one 8-bit code (transfer_functions-inl.h TF_SRGB)
