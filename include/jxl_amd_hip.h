@@ -588,7 +588,11 @@ typedef struct {
   uint32_t xsize, ysize;
   float distance;         /* Butteraugli-style target: scales the thresholds of the transform selection */
   uint32_t gaborish;      /* 1: pre-sharpen with the approximate inverse of the decoder's Gaborish blur */
-  uint32_t strategy_mode; /* 0: DCT8 only, 1: activity-driven DCT 8..64 incl. rectangles */
+  /* 0: DCT8 only, 1: activity-driven DCT 8..64 incl. rectangles. 2, 3: the reference's AC-strategy search restricted to the
+   * pure-DCT kinds 8x8 .. 64x64 (enc_ac_strategy.cc ProcessRectACS; see jxlhip_enc_acs_walk): mask1x1, the cost estimate of
+   * every candidate the walk can ask for (on the sharpened planes, the adaptive quant field, chroma-from-luma factors 0)
+   * and the walk, all on the device; 2 is the aligned walk, 3 adds the floating passes. Both need quant_field_mode 1. */
+  uint32_t strategy_mode;
   uint32_t global_scale, quant_dc; /* Quantizer parameters of the frame (quantizer.h:82-114) */
   float quant_ac;         /* AC quant target the quant field is built around */
   /* 1: fit the chroma-from-luma factors of every 64x64 tile like the reference's fast path (enc_chroma_from_luma.cc:
@@ -731,6 +735,32 @@ int jxlhip_enc_estimate_entropy(JxlHipContext* ctx, const JxlHipEncEstimateDesc*
                                 float* estimates, float* scaled);
 /* Kernel time of the last jxlhip_enc_estimate_entropy (all its launches, copies excluded), milliseconds. */
 int jxlhip_enc_estimate_last_ms(JxlHipContext* ctx, float* ms);
+/* The merge walk of the reference's AC-strategy search (ProcessRectACS, enc_ac_strategy.cc:827-1059, from the 8x8 estimates
+ * on, decoding_speed_tier 0, DCT the only 8x8 kind), alone, on a caller's table of estimates in host memory.
+ *   estimates: per 64x64 tile in raster order (ceil(xb / 8) per row) [kind 0..9][cy][cx] floats, 640 per tile; kinds 8x8,
+ *   16x8, 8x16, 16x16, 32x16, 16x32, 32x32, 64x32, 32x64, 64x64 (rows x columns: AcStrategy 0, 6, 7, 4, 10, 11, 5, 19, 20,
+ *   18), (cx, cy) the candidate's top-left block inside the tile, each estimate with its kind's multiplier already applied
+ *   (jxlenc_acs_walk_candidates of libjxlenc lists what is read, with those multipliers). Entries nothing asks for are not read.
+ *   floating 0: the aligned walk (the reference's effort 5); 1: with the two floating passes (:1033-1057, every position).
+ * acs[yb * xb] receives (strategy << 1) | first-block bit, entropy (may be NULL) the walk's final entropy_estimate per block.
+ * One deviation, stated in csrc/host/jxh_enc_shared.h (AcsWalkTryMerge): a merge that would cut a transform placed earlier is
+ * refused, where the reference writes an overlapping strategy image. A null pointer, a zero size, distance <= 0 or
+ * floating > 1 is JXLHIP_ERR_INVALID_ARGUMENT before any device call. Synchronous; leaves the last jxlhip_enc_forward's state
+ * as it was. jxlenc_cpu_acs_walk (libjxlenc) is the CPU double with the same arguments less the context. */
+typedef struct {
+  uint32_t xb, yb;   /* the frame in 8x8 blocks */
+  float distance;    /* the Butteraugli target: the 8x8 estimates are multiplied by 1 - 0.4 / (distance + 1.4) */
+  uint32_t floating;
+} JxlHipEncAcsWalkDesc;
+int jxlhip_enc_acs_walk(JxlHipContext* ctx, const JxlHipEncAcsWalkDesc* desc, const float* estimates, uint8_t* acs, float* entropy);
+/* Kernel time of the three parts of the search in the last pass of the last jxlhip_enc_forward / _rerun made with
+ * strategy_mode 2 or 3: ms[0] the per-pixel masking, ms[1] all estimate launches, ms[2] the walk (they are part of
+ * jxlhip_enc_last_ms too). JXLHIP_ERR_NO_FRAME after anything else. */
+int jxlhip_enc_search_last_ms(JxlHipContext* ctx, float* ms);
+/* Test access: what the search of the last jxlhip_enc_forward made with strategy_mode 2 or 3 read and wrote, to host memory
+ * (any pointer may be NULL): the XYB planes before and after the sharpening [3][yp][xp] each (the same without Gaborish),
+ * aq_map [yb][xb], mask1x1 [yp][xp] and the estimate table (640 floats per tile; entries nothing asked for are zero). */
+int jxlhip_debug_enc_search(JxlHipContext* ctx, float* planes_before, float* planes_after, float* aq_map, float* mask1x1, float* estimates);
 /* Kernel time of the two quant-field kernels in the last pass of the last jxlhip_enc_forward / _rerun made with
  * quant_field_mode 1 (they are part of jxlhip_enc_last_ms too), milliseconds. */
 int jxlhip_enc_aq_last_ms(JxlHipContext* ctx, float* ms);

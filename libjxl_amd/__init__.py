@@ -355,6 +355,14 @@ class HipContext:
         _check(L.jxlhip_enc_masking_last_ms(self._h, ctypes.byref(a)), "jxlhip_enc_masking_last_ms")
         return a.value
 
+    def enc_search_ms(self):
+        """Measurement: ms of (mask1x1, all estimate launches, the walk) in the last forward pass made with acs_search 1 or 2."""
+        L = lib()
+        L.jxlhip_enc_search_last_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+        a = (ctypes.c_float * 3)()
+        _check(L.jxlhip_enc_search_last_ms(self._h, a), "jxlhip_enc_search_last_ms")
+        return tuple(a)
+
     def enc_estimate_ms(self):
         """Measurement: ms of the kernels of the last estimate_entropy on this context."""
         L = lib()
@@ -589,7 +597,8 @@ class EncParams(ctypes.Structure):
                 ("zero_ac", ctypes.c_int32), ("num_histograms", ctypes.c_int32), ("big_coeffs", ctypes.c_int32), ("num_passes", ctypes.c_int32), ("upsampling", ctypes.c_int32), ("custom_orders", ctypes.c_int32), ("custom_bctx", ctypes.c_int32),
                 ("custom_cmap", ctypes.c_int32), ("custom_lf", ctypes.c_int32), ("ac_code_mode", ctypes.c_int32),
                 ("noise", ctypes.c_int32), ("cfl_fit", ctypes.c_int32), ("color_transform", ctypes.c_int32), ("raw_quant", ctypes.c_int32),
-                ("chroma_subsampling", ctypes.c_int32), ("ec_upsampling", ctypes.c_int32), ("adaptive_quant", ctypes.c_int32)]
+                ("chroma_subsampling", ctypes.c_int32), ("ec_upsampling", ctypes.c_int32), ("adaptive_quant", ctypes.c_int32),
+                ("acs_search", ctypes.c_int32)]
 
 
 class EncHistDesc(ctypes.Structure):  # JxlHipEncHistDesc
@@ -729,6 +738,9 @@ def _enc_lib():
             "cpu_estimate_entropy": (c_int, [vp, vp, sz, vp, vp]),
             # (fn, ctx, xyb, xsize, ysize, quant_field, mask1x1, ytox, ytob, distance, candidates, n, estimates, scaled)
             "estimate_entropy": (c_int, [vp, vp, vp, u32, u32, vp, vp, vp, vp, ctypes.c_float, vp, sz, vp, vp]),
+            "cpu_acs_walk": (c_int, [vp] * 4),
+            "acs_walk_candidates": (ctypes.c_int64, [u32, u32, u32, vp, vp, sz]),
+            "cpu_debug_enc_search": (c_int, [vp] * 6),
             # what the next streams carry (test aids)
             "set_custom_upsampling": (None, [u32, u32]),
             "set_embedded_icc": (None, [cp, sz, sz]),
@@ -1184,6 +1196,72 @@ def estimate_entropy(xyb, quant_field, mask1x1, ytox, ytob, distance, candidates
             _check(r, "jxlhip_enc_estimate_entropy")
         raise JxlAmdError("jxlenc_cpu_estimate_entropy failed (%d)" % r)
     return (est, scaled) if want_scaled else est
+
+
+class AcsWalkDesc(ctypes.Structure):  # JxlHipEncAcsWalkDesc
+    _fields_ = [("xb", ctypes.c_uint32), ("yb", ctypes.c_uint32), ("distance", ctypes.c_float), ("floating", ctypes.c_uint32)]
+
+
+# the ten kinds of the walk's table in its order, as AcStrategy numbers (rows x columns: 8x8, 16x8, 8x16, 16x16, 32x16, 16x32,
+# 32x32, 64x32, 32x64, 64x64)
+ACS_WALK_STRATEGIES = (0, 6, 7, 4, 10, 11, 5, 19, 20, 18)
+
+
+def acs_walk_candidates(xb, yb, floating=0):
+    """The candidates the reference's merge walk over a frame of xb x yb blocks can ask for, with the multipliers it attaches:
+    (an ACS_CANDIDATE array grouped by kind, the uint32 place of each in the walk's table [tile][kind][cy][cx])."""
+    E = _enc_lib()
+    n = E.jxlenc_acs_walk_candidates(int(xb), int(yb), int(floating), None, None, 0)
+    if n < 0:
+        raise JxlAmdError("jxlenc_acs_walk_candidates failed (%d)" % n)
+    cand, index = np.zeros(n, ACS_CANDIDATE), np.zeros(n, np.uint32)
+    E.jxlenc_acs_walk_candidates(int(xb), int(yb), int(floating), cand.ctypes.data, index.ctypes.data, n)
+    return cand, index
+
+
+def ac_strategy_walk(estimates, xb, yb, distance, floating=0, ctx=None, want_entropy=False):
+    """The merge walk of the reference's AC-strategy search on a table of estimates, float32 [tiles][10][8][8] (tiles of 64x64
+    in raster order; see acs_walk_candidates): acs [yb][xb] uint8 = (strategy << 1) | first, or (acs, the walk's final
+    entropy estimate per block [yb][xb]). On the GPU (jxlhip_enc_acs_walk on `ctx`), or the CPU double when ctx is None."""
+    tiles = ((int(xb) + 7) // 8) * ((int(yb) + 7) // 8)
+    est = np.ascontiguousarray(estimates, np.float32)
+    if est.size != tiles * 640:
+        raise ValueError("estimates: [tiles][10][8][8]")
+    d = AcsWalkDesc(int(xb), int(yb), float(distance), int(floating))
+    acs = np.zeros((max(int(yb), 0), max(int(xb), 0)), np.uint8)
+    ent = np.zeros(acs.shape, np.float32)
+    if ctx is not None:
+        L = lib()
+        L.jxlhip_enc_acs_walk.argtypes = [ctypes.c_void_p, ctypes.POINTER(AcsWalkDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.jxlhip_enc_acs_walk(ctx._h, ctypes.byref(d), est.ctypes.data, acs.ctypes.data, ent.ctypes.data if want_entropy else None),
+               "jxlhip_enc_acs_walk")
+    else:
+        r = _enc_lib().jxlenc_cpu_acs_walk(ctypes.byref(d), est.ctypes.data, acs.ctypes.data, ent.ctypes.data if want_entropy else None)
+        if r:
+            raise JxlAmdError("jxlenc_cpu_acs_walk failed (%d)" % r)
+    return (acs, ent) if want_entropy else acs
+
+
+def enc_search_debug(ctx):
+    """Test access: what the search of the last enc_forward_model(img, ctx, adaptive_quant=1, acs_search=1 or 2) read and
+    wrote (ctx a HipContext or a CpuEncContext): dict of before / after (the XYB planes [3][yp][xp] before and after the
+    sharpening), aq_map [yb][xb], mask1x1 [yp][xp] and estimates [tiles][10][8][8]."""
+    xs, ys = ctx.enc_size
+    xb, yb = (xs + 7) // 8, (ys + 7) // 8
+    tiles = ((xb + 7) // 8) * ((yb + 7) // 8)
+    out = dict(before=np.zeros((3, yb * 8, xb * 8), np.float32), after=np.zeros((3, yb * 8, xb * 8), np.float32),
+               aq_map=np.zeros((yb, xb), np.float32), mask1x1=np.zeros((yb * 8, xb * 8), np.float32),
+               estimates=np.zeros((tiles, 10, 8, 8), np.float32))
+    args = [out[k].ctypes.data for k in ("before", "after", "aq_map", "mask1x1", "estimates")]
+    if isinstance(ctx, CpuEncContext):
+        r = _enc_lib().jxlenc_cpu_debug_enc_search(ctx._h, *args)
+        if r:
+            raise JxlAmdError("jxlenc_cpu_debug_enc_search failed (%d)" % r)
+    else:
+        L = lib()
+        L.jxlhip_debug_enc_search.argtypes = [ctypes.c_void_p] * 6
+        _check(L.jxlhip_debug_enc_search(ctx._h, *args), "jxlhip_debug_enc_search")
+    return out
 
 
 def encode_rgba8(img, **kw):

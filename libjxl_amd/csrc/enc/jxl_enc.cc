@@ -1270,6 +1270,9 @@ struct Params {
   int32_t adaptive_quant;  // 1 = image mode writes the reference's initial adaptive quant field (InitialQuantField below) in
                            //     place of the activity rule, and the global scale the reference derives for it; XYB frames
                            //     without subsampling, strategy_mode 0 or 1
+  int32_t acs_search;      // with adaptive_quant 1: the transforms are chosen by the reference's AC-strategy search over the pure-DCT
+                           //     kinds 8x8 .. 64x64 (AcStrategyWalk below) in place of the activity thresholds; 1 = the aligned
+                           //     walk, 2 = with the floating passes. strategy_mode is then not read (0 or 1)
 };
 
 static bool Fits(const FrameModel& f, size_t bx, size_t by, int st) {
@@ -2283,6 +2286,35 @@ static float EstimateEntropy(const JxlHipEncEstimateDesc& d, const JxlHipEncAcsC
   return entropy;
 }
 
+// ---- the merge walk of the reference's AC-strategy search (ProcessRectACS, enc_ac_strategy.cc:827-1059), on a table that
+// holds every estimate a walk could ask for: the float32 statement is jxh::AcsWalkTile (csrc/host/jxh_enc_shared.h), which
+// the kernel k_enc_acs_walk compiles too. Here: one tile after the other into the frame's strategy image, acs[yb * xb] =
+// (strategy << 1) | first, and (entropy != NULL) the walk's final entropy_estimate per block.
+static void AcStrategyWalk(const float* table, size_t xb, size_t yb, float distance, uint32_t floating, uint8_t* acs, float* entropy) {
+  const size_t tiles_x = DivCeil(xb, 8), tiles_y = DivCeil(yb, 8);
+  const float mul8x8 = jxh::AcsWalkMul8x8(distance);
+#pragma omp parallel for schedule(dynamic, 8)
+  for (size_t t = 0; t < tiles_x * tiles_y; t++) {
+    const size_t bx0 = (t % tiles_x) * 8, by0 = (t / tiles_x) * 8;
+    float tile_entropy[64];
+    uint8_t tile_acs[64], priority[64];
+    const jxh::AcsWalkState s = {table + t * jxh::kAcsWalkTileFloats, tile_entropy, tile_acs, priority, uint32_t(std::min<size_t>(8, xb - bx0)),
+                                 uint32_t(std::min<size_t>(8, yb - by0))};
+    jxh::AcsWalkTile(s, mul8x8, floating);
+    for (size_t y = 0; y < s.h; y++)
+      for (size_t x = 0; x < s.w; x++) {
+        const uint8_t a = tile_acs[y * 8 + x];
+        acs[(by0 + y) * xb + bx0 + x] = uint8_t((jxh::AcsWalkStrategy(a >> 1) << 1) | (a & 1));
+        if (entropy) entropy[(by0 + y) * xb + bx0 + x] = tile_entropy[y * 8 + x];
+      }
+  }
+}
+// What the search of an image-mode frame read and wrote (acs_search): test access through the CPU context
+struct SearchData {
+  size_t xp = 0, yp = 0;
+  std::vector<float> before, after, aq_map, mask1x1, table;  // planes [3][yp][xp] before / after the sharpening
+};
+
 // The alpha plane of jxlenc_encode_rgba8 with its geometry: w x h samples (w = 0: frame sized), the extra channel's upsampling
 // factor and its shift against the frame.
 struct AlphaPlane {
@@ -2307,6 +2339,7 @@ static float BeginFrame(FrameModel* fp, size_t xs, size_t ys, const Params& p, s
   f.img_xs = img_xs ? img_xs : xs;
   f.img_ys = img_ys ? img_ys : ys;
   if (p.adaptive_quant != 0 && p.adaptive_quant != 1) throw std::runtime_error("adaptive_quant: 0 or 1");
+  if (p.acs_search < 0 || p.acs_search > 2 || (p.acs_search && p.adaptive_quant != 1)) throw std::runtime_error("acs_search: 0, or 1 / 2 with adaptive_quant 1");
   const bool adaptive = p.adaptive_quant == 1;
   // (the field is defined over XYB planes at full resolution, under this writer's own transform choices)
   if (adaptive && (p.color_transform || f.Subsampled() || p.strategy_mode > 1)) throw std::runtime_error("adaptive_quant: unsupported parameters");
@@ -2398,7 +2431,7 @@ static JxlHipEncDesc ForwardDesc(FrameModel& f, const Params& p, float quant_ac)
   d.ysize = uint32_t(f.ys);
   d.distance = p.distance;
   d.gaborish = f.gab ? 1 : 0;
-  d.strategy_mode = uint32_t(p.strategy_mode);
+  d.strategy_mode = p.acs_search ? uint32_t(p.acs_search) + 1 : uint32_t(p.strategy_mode);
   d.global_scale = f.global_scale;
   d.quant_dc = f.quant_dc;
   d.quant_ac = quant_ac;
@@ -2537,7 +2570,7 @@ static void EncodeImageHooks(const uint8_t* rgb, size_t xs, size_t ys, const Par
 
 // model_only: stop before the bitstream assembly and hand the frame model out (the CPU form of the forward path).
 static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& p, std::vector<uint8_t>* out, size_t img_xs = 0,
-                        size_t img_ys = 0, const AlphaPlane* alpha = nullptr, FrameModel* model_only = nullptr) {
+                        size_t img_ys = 0, const AlphaPlane* alpha = nullptr, FrameModel* model_only = nullptr, SearchData* search = nullptr) {
   FrameModel f;
   const float quant_ac = BeginFrame(&f, xs, ys, p, img_xs, img_ys, alpha);
   const bool adaptive = p.adaptive_quant == 1;
@@ -2550,6 +2583,13 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
     // before the sharpening, at 0.62 of the distance when the frame has no Gaborish (enc_heuristics.cc:1118-1143)
     aq_map.resize(f.xb * f.yb);
     InitialQuantField(xyb[0].data(), xyb[1].data(), xyb[2].data(), xp, yp, f.gab ? p.distance : p.distance * 0.62f, 1.0f, aq_map.data(), nullptr);
+  }
+  std::vector<float> mask1x1;
+  if (p.acs_search) {  // what the search reads per pixel, before the sharpening like the field (enc_heuristics.cc:1118-1143)
+    mask1x1.resize(xp * yp);
+    Masking1x1(xyb[1].data(), xp, yp, mask1x1.data());
+    if (search)
+      for (int c = 0; c < 3; c++) search->before.insert(search->before.end(), xyb[c].begin(), xyb[c].end());
   }
   if (f.gab) {
     // Approximate inverse of the decoder's Gaborish blur K (3x3, default weights): y <- y + (x - K*y), 4 rounds.
@@ -2622,6 +2662,47 @@ static void EncodeImage(const uint8_t* rgb, size_t xs, size_t ys, const Params& 
   // strategy selection
   const float T64 = 0.004f * p.distance, T32 = 0.008f * p.distance, T16 = 0.016f * p.distance, TR = 0.011f * p.distance;
   uint32_t mask = p.strategy_mask ? p.strategy_mask : 0x7FFFFFFu;
+  if (p.acs_search) {
+    // the reference's search: the estimate of every candidate the walk can ask for, on the sharpened planes with the field
+    // and the masking from before the sharpening and chroma-from-luma factors 0 (what the reference has below effort 7),
+    // into the walk's table; then the walk
+    jxh::AcsWalkList list;
+    if (!jxh::AcsWalkCandidates(uint32_t(f.xb), uint32_t(f.yb), uint32_t(p.acs_search) - 1, &list)) throw std::runtime_error("acs_search: frame too large");
+    std::vector<float> planes;
+    for (int c = 0; c < 3; c++) planes.insert(planes.end(), xyb[c].begin(), xyb[c].end());
+    const size_t ntiles = DivCeil(f.xb, 8) * DivCeil(f.yb, 8);
+    const std::vector<int8_t> zero(ntiles, 0);
+    JxlHipEncEstimateDesc ed;
+    memset(&ed, 0, sizeof(ed));
+    DefaultDequant(&ed);
+    ed.xyb = planes.data();
+    ed.xsize = uint32_t(xp);
+    ed.ysize = uint32_t(yp);
+    ed.quant_field = aq_map.data();
+    ed.mask1x1 = mask1x1.data();
+    ed.ytox = ed.ytob = zero.data();
+    ed.distance = p.distance;
+    const size_t n = list.cand.size();
+    std::vector<float> table(ntiles * jxh::kAcsWalkTileFloats, 0.0f);
+    if (!jxh::EncEstimateArgsOk(&ed, list.cand.data(), n, table.data(), nullptr)) throw std::runtime_error("acs_search: estimate arguments");
+    float weights[3];
+    jxh::EncEstimateWeights(ed.distance, weights);
+#pragma omp parallel
+    {
+      EstimateScratch scratch;
+#pragma omp for schedule(dynamic, 16)
+      for (size_t i = 0; i < n; i++) table[list.index[i]] = EstimateEntropy(ed, list.cand[i], weights, nullptr, scratch);
+    }
+    AcStrategyWalk(table.data(), f.xb, f.yb, p.distance, uint32_t(p.acs_search) - 1, f.acs.data(), nullptr);
+    if (search) {
+      search->xp = xp;
+      search->yp = yp;
+      search->after.swap(planes);
+      search->aq_map = aq_map;
+      search->mask1x1.swap(mask1x1);
+      search->table.swap(table);
+    }
+  }
   for (size_t by = 0; by < f.yb; by++)
     for (size_t bx = 0; bx < f.xb; bx++) {
       if (f.acs[by * f.xb + bx] != 0xFF) continue;
@@ -3758,6 +3839,7 @@ struct JxlEncParams {
   int32_t chroma_subsampling;  // YCbCr frames: channel modes of Cb, Y, Cr (4 = 4:2:0, 8 = 4:2:2, 12 = 4:4:0), see jxe::Params
   int32_t ec_upsampling;   // jxlenc_encode_rgba8: upsampling factor of the alpha channel, see jxe::Params
   int32_t adaptive_quant;  // 1 = the reference's initial adaptive quant field, see jxe::Params
+  int32_t acs_search;      // 1, 2 = the reference's AC-strategy search (aligned / with the floating passes), see jxe::Params
 };
 
 // The next VarDCT streams code their own upsampling weights (mask bit k: the 2^(k+1)-fold matrix; 0: default weights again).
@@ -3957,6 +4039,8 @@ struct JxlEncCpuCtx {
   std::vector<std::vector<jxe::Token>> tokens;  // per group
   std::vector<std::vector<uint8_t>> coded;      // per group (jxlenc_cpu_ans_sizes)
   std::vector<uint32_t> coded_bits;
+  jxe::SearchData search;  // of the last forward call made with strategy_mode 2 or 3 (jxlenc_cpu_debug_enc_search)
+  bool have_search = false;
 };
 JxlEncCpuCtx* jxlenc_cpu_ctx_new(void) { return new JxlEncCpuCtx; }
 void jxlenc_cpu_ctx_free(JxlEncCpuCtx* c) { delete c; }
@@ -3969,13 +4053,15 @@ int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHi
   JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
   jxe::UseThreads();
   if (!rgb || !d || !acs || !qf || !dc || stride < size_t(d->xsize) * 3) return -1;
-  if (c) c->have_model = c->have_tokens = c->resident = false;
+  if (c) c->have_model = c->have_tokens = c->resident = c->have_search = false;
+  if (d->strategy_mode > 3 || (d->strategy_mode > 1 && d->quant_field_mode != 1)) return -1;
   jxe::Params q;
   memset(&q, 0, sizeof(q));
   q.distance = d->distance;
   q.epf_iters = -1;
   q.gab = int32_t(d->gaborish);
-  q.strategy_mode = int32_t(d->strategy_mode);
+  q.strategy_mode = d->strategy_mode > 1 ? 1 : int32_t(d->strategy_mode);
+  q.acs_search = d->strategy_mode > 1 ? int32_t(d->strategy_mode) - 1 : 0;
   q.cfl_fit = int32_t(d->cfl_fit);
   q.adaptive_quant = int32_t(d->quant_field_mode);
   q.seed = 1;
@@ -3988,7 +4074,8 @@ int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHi
   jxe::FrameModel local;
   jxe::FrameModel& f = c ? c->f : local;
   try {
-    jxe::EncodeImage(rgb, d->xsize, d->ysize, q, nullptr, 0, 0, nullptr, &f);
+    if (c) c->search = jxe::SearchData();
+    jxe::EncodeImage(rgb, d->xsize, d->ysize, q, nullptr, 0, 0, nullptr, &f, c && q.acs_search ? &c->search : nullptr);
   } catch (...) {
     return -2;
   }
@@ -4002,7 +4089,47 @@ int jxlenc_cpu_forward(void* ctx, const uint8_t* rgb, size_t stride, const JxlHi
   if (coeffs)
     for (size_t g = 0; g < f.coeffs.size(); g++) memcpy(coeffs + g * 3 * 65536, f.coeffs[g].data(), size_t(3) * 65536 * 4);
   if (c) c->have_model = true;
+  if (c) c->have_search = q.acs_search != 0;
   return 0;
+}
+
+// The CPU double of jxlhip_debug_enc_search (include/jxl_amd_hip.h), on a JxlEncCpuCtx. -5: the last forward call on it was
+// not made with strategy_mode 2 or 3.
+int jxlenc_cpu_debug_enc_search(void* ctx, float* planes_before, float* planes_after, float* aq_map, float* mask1x1, float* estimates) {
+  JxlEncCpuCtx* c = static_cast<JxlEncCpuCtx*>(ctx);
+  if (!c) return -1;
+  if (!c->have_search) return -5;
+  const jxe::SearchData& s = c->search;
+  if (planes_before) memcpy(planes_before, s.before.data(), s.before.size() * 4);
+  if (planes_after) memcpy(planes_after, s.after.data(), s.after.size() * 4);
+  if (aq_map) memcpy(aq_map, s.aq_map.data(), s.aq_map.size() * 4);
+  if (mask1x1) memcpy(mask1x1, s.mask1x1.data(), s.mask1x1.size() * 4);
+  if (estimates) memcpy(estimates, s.table.data(), s.table.size() * 4);
+  return 0;
+}
+
+// The CPU double of jxlhip_enc_acs_walk (include/jxl_amd_hip.h): the same arguments without the context.
+int jxlenc_cpu_acs_walk(const JxlHipEncAcsWalkDesc* d, const float* estimates, uint8_t* acs, float* entropy) {
+  jxe::UseThreads();
+  if (!jxh::AcsWalkArgsOk(d, estimates, acs)) return -1;
+  jxe::AcStrategyWalk(estimates, d->xb, d->yb, d->distance, d->floating, acs, entropy);
+  return 0;
+}
+
+// The candidates a walk over a frame of xb x yb blocks can ask for (jxh::AcsWalkCandidates), grouped by kind: cand[capacity]
+// and index[capacity] (either may be NULL) receive the first min(n, capacity) candidates and their places in the walk's table.
+// Returns n, or -1 for sizes or a mode the walk does not take.
+int64_t jxlenc_acs_walk_candidates(uint32_t xb, uint32_t yb, uint32_t floating, JxlHipEncAcsCandidate* cand, uint32_t* index, size_t capacity) {
+  jxh::AcsWalkList list;
+  try {
+    if (!jxh::AcsWalkCandidates(xb, yb, floating, &list)) return -1;
+  } catch (...) {
+    return -2;
+  }
+  const size_t n = std::min(capacity, list.cand.size());
+  if (cand && n) memcpy(cand, list.cand.data(), n * sizeof(JxlHipEncAcsCandidate));
+  if (index && n) memcpy(index, list.index.data(), n * 4);
+  return int64_t(list.cand.size());
 }
 
 int jxlenc_cpu_token_counts(void* ctx, const JxlHipEncTokDesc* d, uint32_t* totals) {

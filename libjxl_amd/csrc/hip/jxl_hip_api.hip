@@ -366,6 +366,15 @@ struct JxlHipContext {
   size_t lds_entropy = 0;
   bool alias_lds = false;
   int final_plane = 0;  // which plane set holds the filtered XYB after jxlhip_run_filter_color
+  // the AC-strategy search of the forward path (strategy_mode 2, 3): its own mask1x1, zero chroma-from-luma factors, the
+  // candidate list of the frame size it was last built for (srch_xb x srch_yb blocks, srch_floating; kind k is
+  // srch_first[k] .. srch_first[k + 1]) with the index array k_enc_estimate writes through, and the walk's table; the times
+  // of mask1x1, the estimate launches and the walk in the last pass. jxlhip_enc_acs_walk has buffers of its own.
+  // (Behind everything else, so that no member the decode stages read moves.)
+  Buf srch_mask, srch_zero, srch_cand, srch_index, srch_table, walk_table, walk_acs, walk_entropy;
+  uint32_t srch_xb = 0, srch_yb = 0, srch_floating = 0;
+  size_t srch_first[jxh::kAcsWalkKinds + 1] = {};
+  hipEvent_t srch_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 // JXLHIP_ENTROPY=1 (a test hook): no frame takes the lane-parallel k_entropy_lanes, every frame the wave-per-section
@@ -471,6 +480,7 @@ static JxlHipContext* RecycleContext(int device) {
   for (size_t i = 0; i < sizeof(c->ent_ev) / sizeof(c->ent_ev[0]); i++) std::swap(c->ent_ev[i], o->ent_ev[i]);
   for (size_t i = 0; i < sizeof(c->mask_ev) / sizeof(c->mask_ev[0]); i++) std::swap(c->mask_ev[i], o->mask_ev[i]);
   for (size_t i = 0; i < sizeof(c->est_ev) / sizeof(c->est_ev[0]); i++) std::swap(c->est_ev[i], o->est_ev[i]);
+  for (size_t i = 0; i < sizeof(c->srch_ev) / sizeof(c->srch_ev[0]); i++) std::swap(c->srch_ev[i], o->srch_ev[i]);
   std::swap(c->stage, o->stage);
   jxlhip_ctx_destroy(o);  // (what is left of it: lazily created events, a stream of its own)
   return c;
@@ -549,6 +559,7 @@ static std::vector<Buf*> AllBufs(JxlHipContext* c) {
                 &c->mod.rects, &c->mod.status, &c->mod.end_bits, &c->mod.scratch, &c->mod.windows, &c->mod.batch_streams, &c->mod.batch_ops, &c->frame_blob, &c->noise, &c->spl_seg, &c->spl_row_start, &c->spl_row_seg, &c->spl_planes, &c->pat_rec, &c->pat_row_start, &c->pat_row_list,
                 &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in, &c->enc_mask1x1,
                 &c->est_planes, &c->est_qf, &c->est_mask, &c->est_ytox, &c->est_ytob, &c->est_dq, &c->est_cand, &c->est_index, &c->est_at, &c->est_out, &c->est_scaled,
+                &c->srch_mask, &c->srch_zero, &c->srch_cand, &c->srch_index, &c->srch_table, &c->walk_table, &c->walk_acs, &c->walk_entropy,
                 &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
   for (auto& pb : c->pass_bufs)
     for (Buf* b : {&pb.ctx_map, &pb.alias, &pb.cfg, &pb.orders, &pb.ptable, &pb.poffset, &pb.alias_packed}) all.push_back(b);
@@ -582,6 +593,8 @@ void jxlhip_ctx_destroy(JxlHipContext* c) {
   for (auto& ev : c->mask_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : c->est_ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : c->srch_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (c->stage.done) (void)hipEventDestroy(c->stage.done);
   if (c->stage.p) (void)hipHostFree(c->stage.p);
@@ -3699,6 +3712,34 @@ static int EncAqEnsure(JxlHipContext* c, uint32_t xp, uint32_t yp, jxlhip::EncAq
   return 0;
 }
 
+// What the search of strategy_mode 2 / 3 needs besides the forward path's own buffers: the candidate list of the frame size
+// (built on the host and uploaded once per (xb, yb, floating): a second frame of the same size and jxlhip_enc_forward_rerun
+// upload nothing), the walk's table with the entries nothing writes at zero, the masking plane, the zero factors, the events.
+static int EncSearchPrepare(JxlHipContext* c, const jxlhip::EncFwd& P, uint32_t floating) {
+  const size_t tiles = size_t((P.xb + 7) / 8) * ((P.yb + 7) / 8);
+  int r;
+  if ((r = c->srch_mask.Ensure(size_t(P.xp) * P.yp * 4)) || (r = c->srch_zero.Ensure(tiles)) || (r = c->srch_table.Ensure(tiles * jxh::kAcsWalkTileFloats * 4)))
+    return r;
+  for (auto& ev : c->srch_ev)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  HIP_TRY(hipMemsetAsync(c->srch_zero.p, 0, tiles, c->stream));
+  if (c->srch_xb == P.xb && c->srch_yb == P.yb && c->srch_floating == floating && c->srch_cand.p) return 0;
+  c->srch_xb = c->srch_yb = 0;
+  jxh::AcsWalkList list;
+  if (!jxh::AcsWalkCandidates(P.xb, P.yb, floating, &list)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  const size_t n = list.cand.size();
+  if ((r = c->srch_cand.Ensure(n * sizeof(JxlHipEncAcsCandidate))) || (r = c->srch_index.Ensure(n * 4))) return r;
+  HIP_TRY(hipMemcpyAsync(c->srch_cand.p, list.cand.data(), n * sizeof(JxlHipEncAcsCandidate), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->srch_index.p, list.index.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->srch_table.p, 0, tiles * jxh::kAcsWalkTileFloats * 4, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (the list is a local)
+  memcpy(c->srch_first, list.first, sizeof(c->srch_first));
+  c->srch_xb = P.xb;
+  c->srch_yb = P.yb;
+  c->srch_floating = floating;
+  return 0;
+}
+
 // The kernel sequence of the forward path on the context's stream (P.planes is set on the way).
 static int EncLaunch(JxlHipContext* c, jxlhip::EncFwd& P, bool gaborish) {
   const size_t nb = size_t(P.xb) * P.yb, ng = size_t(P.xg) * P.yg;
@@ -3716,6 +3757,19 @@ static int EncLaunch(JxlHipContext* c, jxlhip::EncFwd& P, bool gaborish) {
     HIP_TRY(hipEventRecord(c->enc_ev[4], c->stream));
     EncAqLaunch(c, A);
     HIP_TRY(hipEventRecord(c->enc_ev[5], c->stream));
+  }
+  const bool search = P.strategy_mode >= 2;  // (jxlhip_enc_forward has prepared the list and the buffers: EncSearchPrepare)
+  if (search) {  // the per-pixel masking, like the field from the planes before the sharpening
+    jxlhip::EncMask1x1 M;
+    M.y = P.planes + size_t(P.xp) * P.yp;
+    M.out = c->srch_mask.as<float>();
+    M.xp = P.xp;
+    M.yp = P.yp;
+    jxh::EncMask1x1Weights(M.w);
+    HIP_TRY(hipEventRecord(c->srch_ev[0], c->stream));
+    hipLaunchKernelGGL(jxlhip::k_enc_mask1x1, dim3((P.xp + jxlhip::kMaskCols - 1) / jxlhip::kMaskCols, (P.yp + jxlhip::kMaskRows - 1) / jxlhip::kMaskRows),
+                       dim3(256), 0, c->stream, M);
+    HIP_TRY(hipEventRecord(c->srch_ev[1], c->stream));
   }
   if (gaborish) {
     if (getenv("JXLHIP_ENC_SHARPEN_ROUNDS")) {  // the one-round-per-launch form: orig = sets[2]; 2 -> 0 -> 1 -> 0 -> 1
@@ -3735,10 +3789,62 @@ static int EncLaunch(JxlHipContext* c, jxlhip::EncFwd& P, bool gaborish) {
       P.planes = sets[0];
     }
   }
-  hipLaunchKernelGGL(jxlhip::k_enc_activity, dim3((P.xb + 7) / 8, P.yb), dim3(64), 0, c->stream, P);
   const uint32_t tiles = ((P.xb + 7) / 8) * ((P.yb + 7) / 8);
-  if (P.quant_field_mode) hipLaunchKernelGGL(jxlhip::k_enc_select<true>, dim3(tiles), dim3(64), 0, c->stream, P);
-  else hipLaunchKernelGGL(jxlhip::k_enc_select<false>, dim3(tiles), dim3(64), 0, c->stream, P);
+  if (search) {
+    // the reference's search in place of the activity rule: every candidate's estimate on the resident planes (the field
+    // and the masking from before the sharpening, chroma-from-luma factors 0, the frame's own distance) into the walk's
+    // table, one launch per kind, then the walk, which also writes the quant field
+    jxlhip::EncEstimate E;
+    memset(&E, 0, sizeof(E));
+    E.planes = P.planes;
+    E.quant = P.aq_map;
+    E.mask = c->srch_mask.as<float>();
+    E.ytox = E.ytob = c->srch_zero.as<int8_t>();
+    E.basis_t = P.basis_t;
+    E.estimates = c->srch_table.as<float>();
+    E.xp = P.xp;
+    E.yp = P.yp;
+    E.xb = P.xb;
+    E.tiles_x = (P.xb + 7) / 8;
+    jxh::EncEstimateWeights(P.distance, E.weights);
+    jxh::EncEstimateChannelMul(E.channel_mul);
+    HIP_TRY(hipEventRecord(c->srch_ev[2], c->stream));
+    for (uint32_t k = 0; k < jxh::kAcsWalkKinds; k++) {
+      const size_t first = c->srch_first[k], n = c->srch_first[k + 1] - first;
+      if (!n) continue;
+      uint32_t dq_kind = 0;
+      jxh::EncEstimateShape(jxh::AcsWalkStrategy(k), &E.cx, &E.cy, &dq_kind);
+      E.dequant = P.dequant + P.dq_offset[dq_kind];
+      E.cand = c->srch_cand.as<JxlHipEncAcsCandidate>() + first;
+      E.index = c->srch_index.as<uint32_t>() + first;
+      E.n = uint32_t(n);
+      E.x_weight = E.cx * E.cy >= 2 ? jxh::EncEstimateXWeight(E.cx * E.cy) : 1.0f;
+      const uint32_t area = E.cx * E.cy * 64;
+      if (area < 1024) hipLaunchKernelGGL((jxlhip::k_enc_estimate<64, 1>), dim3((E.n + 3) / 4), dim3(256), 0, c->stream, E);
+      else if (area == 1024) hipLaunchKernelGGL((jxlhip::k_enc_estimate<256, 4>), dim3(E.n), dim3(256), 0, c->stream, E);
+      else hipLaunchKernelGGL((jxlhip::k_enc_estimate<256, 8>), dim3(E.n), dim3(256), 0, c->stream, E);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c->srch_ev[3], c->stream));
+    jxlhip::EncAcsWalk W;
+    memset(&W, 0, sizeof(W));
+    W.table = c->srch_table.as<float>();
+    W.acs = P.acs;
+    W.qf = P.qf;
+    W.aq_map = P.aq_map;
+    W.xb = P.xb;
+    W.yb = P.yb;
+    W.floating = P.strategy_mode - 2;
+    W.mul8x8 = jxh::AcsWalkMul8x8(P.distance);
+    W.mean_max_mixer = P.mean_max_mixer;
+    W.inv_gs = P.inv_gs;
+    hipLaunchKernelGGL(jxlhip::k_enc_acs_walk, dim3(tiles), dim3(64), 0, c->stream, W);
+    HIP_TRY(hipEventRecord(c->srch_ev[4], c->stream));
+  } else {
+    hipLaunchKernelGGL(jxlhip::k_enc_activity, dim3((P.xb + 7) / 8, P.yb), dim3(64), 0, c->stream, P);
+    if (P.quant_field_mode) hipLaunchKernelGGL(jxlhip::k_enc_select<true>, dim3(tiles), dim3(64), 0, c->stream, P);
+    else hipLaunchKernelGGL(jxlhip::k_enc_select<false>, dim3(tiles), dim3(64), 0, c->stream, P);
+  }
   hipLaunchKernelGGL(jxlhip::k_enc_offsets, dim3(uint32_t(ng)), dim3(64), 0, c->stream, P);
   HIP_TRY(hipMemsetAsync(c->enc_coef.p, 0, ng * 3 * 65536 * 4, c->stream));
   HIP_TRY(hipEventRecord(c->enc_ev[2], c->stream));
@@ -3755,10 +3861,18 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
                        int32_t* coeffs) {
   if (!c || !rgb || !d || !acs || !qf || !dc) return JXLHIP_ERR_INVALID_ARGUMENT;  // (coeffs may be NULL: they stay on the device)
   if (!d->xsize || !d->ysize || d->xsize > (1u << 18) || d->ysize > (1u << 18) || stride < size_t(d->xsize) * 3) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!(d->distance > 0) || !d->global_scale || !d->quant_dc || !d->dequant || d->strategy_mode > 1 || d->quant_field_mode > 1)
+  if (!(d->distance > 0) || !d->global_scale || !d->quant_dc || !d->dequant || d->strategy_mode > 3 || d->quant_field_mode > 1)
     return JXLHIP_ERR_INVALID_ARGUMENT;
   for (int k = 0; k < 17; k++)
     if (size_t(d->dequant_offset[k]) + 3 * size_t(d->dequant_size[k]) > d->dequant_floats) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (d->strategy_mode >= 2) {  // the search: the adaptive field, a size the walk takes, a table of the right size for every kind it estimates
+    if (d->quant_field_mode != 1 || !std::isfinite(d->distance) || !jxh::AcsWalkSizeOk((d->xsize + 7) / 8, (d->ysize + 7) / 8)) return JXLHIP_ERR_INVALID_ARGUMENT;
+    for (uint32_t k = 0; k < jxh::kAcsWalkKinds; k++) {
+      uint32_t cx = 0, cy = 0, dq_kind = 0;
+      jxh::EncEstimateShape(jxh::AcsWalkStrategy(k), &cx, &cy, &dq_kind);
+      if (d->dequant_size[dq_kind] != cx * cy * 64) return JXLHIP_ERR_INVALID_ARGUMENT;
+    }
+  }
   HIP_TRY(hipSetDevice(c->device));
   jxlhip::EncFwd P;
   memset(&P, 0, sizeof(P));
@@ -3824,6 +3938,7 @@ int jxlhip_enc_forward(JxlHipContext* c, const uint8_t* rgb, size_t stride, cons
   }
   HIP_TRY(hipMemsetAsync(c->enc_ytox.p, 0, ntiles, c->stream));
   HIP_TRY(hipMemsetAsync(c->enc_ytob.p, 0, ntiles, c->stream));
+  if (P.strategy_mode >= 2 && (r = EncSearchPrepare(c, P, P.strategy_mode - 2))) return r;
   HIP_TRY(hipEventRecord(c->enc_ev[0], c->stream));
   if ((r = EncLaunch(c, P, d->gaborish != 0))) return r;
   c->enc_last = P;
@@ -4264,6 +4379,60 @@ int jxlhip_enc_estimate_last_ms(JxlHipContext* c, float* ms) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipEventSynchronize(c->est_ev[1]));
   HIP_TRY(hipEventElapsedTime(ms, c->est_ev[0], c->est_ev[1]));
+  return 0;
+}
+
+// The merge walk alone (k_enc_acs_walk, jxl_hip_enc.h) on a caller's table; buffers of its own, so that the last forward
+// call's search data and state stay what they were.
+int jxlhip_enc_acs_walk(JxlHipContext* c, const JxlHipEncAcsWalkDesc* d, const float* estimates, uint8_t* acs, float* entropy) {
+  if (!c || !jxh::AcsWalkArgsOk(d, estimates, acs)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nb = size_t(d->xb) * d->yb, tiles = size_t((d->xb + 7) / 8) * ((d->yb + 7) / 8);
+  int r;
+  if ((r = c->walk_table.Ensure(tiles * jxh::kAcsWalkTileFloats * 4)) || (r = c->walk_acs.Ensure(nb)) || (entropy && (r = c->walk_entropy.Ensure(nb * 4))))
+    return r;
+  HIP_TRY(hipMemcpyAsync(c->walk_table.p, estimates, tiles * jxh::kAcsWalkTileFloats * 4, hipMemcpyHostToDevice, c->stream));
+  jxlhip::EncAcsWalk W;
+  memset(&W, 0, sizeof(W));
+  W.table = c->walk_table.as<float>();
+  W.acs = c->walk_acs.as<uint8_t>();
+  W.entropy = entropy ? c->walk_entropy.as<float>() : nullptr;
+  W.xb = d->xb;
+  W.yb = d->yb;
+  W.floating = d->floating;
+  W.mul8x8 = jxh::AcsWalkMul8x8(d->distance);
+  hipLaunchKernelGGL(jxlhip::k_enc_acs_walk, dim3(uint32_t(tiles)), dim3(64), 0, c->stream, W);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(acs, c->walk_acs.p, nb, hipMemcpyDeviceToHost, c->stream));
+  if (entropy) HIP_TRY(hipMemcpyAsync(entropy, c->walk_entropy.p, nb * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int jxlhip_enc_search_last_ms(JxlHipContext* c, float* ms) {
+  if (!c || !ms) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->enc_timed || c->enc_last.strategy_mode < 2) return JXLHIP_ERR_NO_FRAME;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->srch_ev[4]));
+  HIP_TRY(hipEventElapsedTime(&ms[0], c->srch_ev[0], c->srch_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms[1], c->srch_ev[2], c->srch_ev[3]));
+  HIP_TRY(hipEventElapsedTime(&ms[2], c->srch_ev[3], c->srch_ev[4]));
+  return 0;
+}
+
+int jxlhip_debug_enc_search(JxlHipContext* c, float* planes_before, float* planes_after, float* aq_map, float* mask1x1, float* estimates) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->enc_timed || c->enc_last.strategy_mode < 2) return JXLHIP_ERR_NO_FRAME;
+  HIP_TRY(hipSetDevice(c->device));
+  const jxlhip::EncFwd& F = c->enc_last;
+  const size_t plane = size_t(F.xp) * F.yp, nb = size_t(F.xb) * F.yb, tiles = size_t((F.xb + 7) / 8) * ((F.yb + 7) / 8);
+  const float* before = c->enc_last_gaborish ? c->enc_planes[2].as<float>() : c->enc_planes[0].as<float>();
+  if (planes_before) HIP_TRY(hipMemcpyAsync(planes_before, before, 3 * plane * 4, hipMemcpyDeviceToHost, c->stream));
+  if (planes_after) HIP_TRY(hipMemcpyAsync(planes_after, F.planes, 3 * plane * 4, hipMemcpyDeviceToHost, c->stream));
+  if (aq_map) HIP_TRY(hipMemcpyAsync(aq_map, F.aq_map, nb * 4, hipMemcpyDeviceToHost, c->stream));
+  if (mask1x1) HIP_TRY(hipMemcpyAsync(mask1x1, c->srch_mask.p, plane * 4, hipMemcpyDeviceToHost, c->stream));
+  if (estimates) HIP_TRY(hipMemcpyAsync(estimates, c->srch_table.p, tiles * jxh::kAcsWalkTileFloats * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -2,13 +2,15 @@
 // activity, transform selection + quant field, forward DCT + DC extraction + quantisation with chroma-from-luma.
 // What the reference does in enc_xyb.cc:83-174 (SRGBToXYB), enc_gaborish.cc:21-70, enc_group.cc:380-533
 // (ComputeCoefficients: TransformFromPixels, DCFromLowestFrequencies, QuantizeBlockAC / QuantizeRoundtripYBlockAC) and
-// enc_transforms-inl.h. The transform selection is the one of this repo's CPU stream writer (csrc/enc), NOT the
-// reference's AC-strategy search (enc_ac_strategy.cc:827-1068), and there is no Butteraugli loop
-// (enc_adaptive_quantization.cc:707-1115): those stay out. The quant field is the writer's own activity rule by default;
+// enc_transforms-inl.h. By default the transform selection is the one of this repo's CPU stream writer (csrc/enc), not the
+// reference's AC-strategy search (enc_ac_strategy.cc:827-1068; opt-in, below), and there is no Butteraugli loop
+// (enc_adaptive_quantization.cc:707-1115). The quant field is the writer's own activity rule by default;
 // with quant_field_mode 1 it is the reference's initial adaptive quant field (enc_adaptive_quantization.cc:88-449,
-// 466-628, 1198-1247: k_enc_aq_cells, k_enc_aq_blocks and the tail of k_enc_select<true>). Two inputs of the reference's search
-// exist as stand-alone entries that the forward path does not call yet: the per-pixel masking (k_enc_mask1x1) and the cost
-// estimate of a list of pure-DCT candidates (k_enc_estimate: EstimateEntropy, enc_ac_strategy.cc:364-511). Every float expression keeps the
+// 466-628, 1198-1247: k_enc_aq_cells, k_enc_aq_blocks and the tail of k_enc_select<true>). With strategy_mode 2 / 3 (and
+// that quant field) the transforms are chosen by the reference's search restricted to the pure-DCT kinds instead: the
+// per-pixel masking (k_enc_mask1x1), the cost estimate of every candidate (k_enc_estimate: EstimateEntropy,
+// enc_ac_strategy.cc:364-511) and the merge walk (k_enc_acs_walk: ProcessRectACS :827-1059), each also a stand-alone entry;
+// k_enc_activity and k_enc_select are then not launched. Every float expression keeps the
 // operation order of the CPU writer with contraction off, so that the two agree except where cbrtf / log2f / exp2f differ
 // in the last place.
 #ifndef JXL_HIP_ENC_H_
@@ -1113,6 +1115,69 @@ __global__ __launch_bounds__(256) void k_enc_estimate(EncEstimate P) {
     entropy += P.weights[0] * loss_scalar;
     P.estimates[P.index[slot]] = entropy;
   }
+}
+
+// The merge walk of the reference's AC-strategy search (ProcessRectACS, enc_ac_strategy.cc:827-1059) over one 64x64 tile per
+// wave, on a table that holds every estimate the walk can ask for (k_enc_estimate wrote it through the candidate list's
+// index array, or a caller brought it: jxlhip_enc_acs_walk). The float32 statement is jxh::AcsWalkTile of
+// csrc/host/jxh_enc_shared.h, the text the CPU double compiles, with contraction off in every function that adds. The tile's
+// table (2 560 B), entropy_estimate[64], the strategy image and priority[64] are in LDS. The walk is serial by construction
+// from the first floating square on (each reads what the one before wrote), and the aligned squares of one level, which
+// are independent, are a small part of it: lane 0 walks, the wave's other lanes load the table before and write the results
+// after. In the forward path (qf != NULL) every lane then aggregates the adaptive quant field over the transform its block
+// starts, the arithmetic of k_enc_select<true>'s tail: AdjustQuantField and SetQuantFieldRect.
+struct EncAcsWalk {
+  const float* table;   // [tiles][10][8][8]
+  uint8_t* acs;         // [yb][xb] (strategy << 1) | first
+  float* entropy;       // [yb][xb] the walk's final entropy_estimate, or NULL
+  int32_t* qf;          // [yb][xb] quant field at first blocks, or NULL
+  const float* aq_map;  // [yb][xb], read with qf
+  uint32_t xb, yb, floating;
+  float mul8x8, mean_max_mixer, inv_gs;
+};
+__global__ __launch_bounds__(64) void k_enc_acs_walk(EncAcsWalk P) {
+#pragma clang fp contract(off)
+  __shared__ float s_est[jxh::kAcsWalkTileFloats];
+  __shared__ float s_entropy[64], s_aq[64];
+  __shared__ uint8_t s_acs[64], s_priority[64];
+  const uint32_t tiles_x = (P.xb + 7) / 8;
+  const uint32_t t = blockIdx.x, lane = threadIdx.x, x = lane & 7, y = lane >> 3;
+  const uint32_t bx0 = (t % tiles_x) * 8, by0 = (t / tiles_x) * 8;
+  const uint32_t w = min(8u, P.xb - bx0), h = min(8u, P.yb - by0);
+  const bool inside = x < w && y < h;
+  const size_t bi = size_t(by0 + y) * P.xb + bx0 + x;
+  for (uint32_t i = lane; i < jxh::kAcsWalkTileFloats; i += 64) s_est[i] = P.table[size_t(t) * jxh::kAcsWalkTileFloats + i];
+  s_aq[lane] = P.qf && inside ? P.aq_map[bi] : 0.0f;
+  __syncthreads();
+  if (lane == 0) {
+    const jxh::AcsWalkState s = {s_est, s_entropy, s_acs, s_priority, w, h};
+    jxh::AcsWalkTile(s, P.mul8x8, P.floating);
+  }
+  __syncthreads();
+  if (!inside) return;
+  const uint32_t a = s_acs[lane], kind = a >> 1;
+  P.acs[bi] = uint8_t((jxh::AcsWalkStrategy(kind) << 1) | (a & 1));
+  if (P.entropy) P.entropy[bi] = s_entropy[lane];
+  if (!P.qf) return;
+  int32_t q = 0;
+  if (a & 1) {
+    // the covered blocks in raster order: the largest, and the mean mixed in from four blocks on
+    const uint32_t cx = 1u << jxh::AcsWalkLog2X(kind), cy = 1u << jxh::AcsWalkLog2Y(kind);
+    float mx = s_aq[lane], mean = 0.0f;
+    for (uint32_t yy = 0; yy < cy; yy++)
+      for (uint32_t xx = 0; xx < cx; xx++) {
+        const float v = s_aq[(y + yy) * 8 + x + xx];
+        mean += v;
+        mx = fmaxf(v, mx);
+      }
+    mean /= float(cy * cx);
+    if (cy * cx >= 4) {
+      mx *= P.mean_max_mixer;
+      mx += (1.0f - P.mean_max_mixer) * mean;
+    }
+    q = int(fmaxf(1.0f, fminf(mx * P.inv_gs + 0.5f, 256.0f)));
+  }
+  P.qf[bi] = q;
 }
 
 // ---------------------------------------------------------------------------------------------- tokenisation

@@ -1,14 +1,16 @@
 // What the host stream writer (csrc/enc/jxl_enc.cc) and the host side of the device forward path (csrc/hip/jxl_hip_api.hip)
 // must state identically: float32 arithmetic whose results the two are compared on bit for bit, and the walk over a
-// caller's ANS tables that keeps every index formed from them in bounds. Host code only; one text, two compilers.
+// caller's ANS tables that keeps every index formed from them in bounds. Host code, one text for two compilers; the merge
+// walk of the AC-strategy search (JXH_HD below) is compiled as device code as well.
 #ifndef JXH_ENC_SHARED_H_
 #define JXH_ENC_SHARED_H_
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
-#include "../../../include/jxl_amd_hip.h"  // JxlHipEncAnsDesc, JxlHipEncEstimateDesc, JxlHipEncAcsCandidate
+#include "../../../include/jxl_amd_hip.h"  // JxlHipEncAnsDesc, JxlHipEncEstimateDesc, JxlHipEncAcsCandidate, JxlHipEncAcsWalkDesc
 
 namespace jxh {
 
@@ -125,6 +127,298 @@ inline bool EncEstimateArgsOk(const JxlHipEncEstimateDesc* d, const JxlHipEncAcs
   }
   if (total_area) *total_area = area;
   return true;
+}
+
+// ---- the merge walk of the AC-strategy search (ProcessRectACS, enc_ac_strategy.cc:827-1059, with TryMergeAcs :618-653,
+// SetEntropyForTransform :655-665, FindBestFirstLevelDivisionForSquare :703-825 and the two crossing tests :302-362), for
+// decoding_speed_tier 0 and DCT as the only 8x8 kind. Every estimate the walk could ask for is in a table before it starts
+// (an estimate depends on the candidate alone; the walk's state only decides whether it is asked for), so the walk is
+// float32 additions in the reference's raster orders, std::min and <. One text for the CPU double (csrc/enc/jxl_enc.cc), the
+// launch layer and the kernel (k_enc_acs_walk, csrc/hip/jxl_hip_enc.h): JXH_HD makes it device code there as well, and every
+// function that adds floats turns contraction off for itself.
+#if defined(__HIPCC__)
+#define JXH_HD __host__ __device__ __forceinline__
+#else
+#define JXH_HD inline
+#endif
+
+// The ten kinds the walk places, in the order of the table: 8x8, 16x8, 8x16, 16x16, 32x16, 16x32, 32x32, 64x32, 32x64, 64x64
+// (rows x columns, as the reference names them). Blocks covered are 1 << log2; the multipliers are the reference's
+// entropy_mul16X8 .. entropy_mul64X64 (:892-897), both rectangles of a square taking the rectangle's; 1 (0.8 / 0.8) for the 8x8.
+constexpr uint32_t kAcsWalkKinds = 10, kAcsWalkTileFloats = kAcsWalkKinds * 64;
+JXH_HD uint32_t AcsWalkLog2X(uint32_t kind) { return uint32_t(0x3322211100ull >> (4 * kind)) & 15u; }
+JXH_HD uint32_t AcsWalkLog2Y(uint32_t kind) { return uint32_t(0x3232121010ull >> (4 * kind)) & 15u; }
+JXH_HD uint32_t AcsWalkStrategy(uint32_t kind) {
+  return kind == 0 ? 0u : kind == 1 ? 6u : kind == 2 ? 7u : kind == 3 ? 4u : kind == 4 ? 10u : kind == 5 ? 11u : kind == 6 ? 5u : kind == 7 ? 19u : kind == 8 ? 20u : 18u;
+}
+inline float AcsWalkEntropyMul(uint32_t kind) {
+  const float m[kAcsWalkKinds] = {1.0f, 1.21f, 1.21f, 1.34f, 1.49f, 1.49f, 1.48f, 2.25f, 2.25f, 2.25f};
+  return m[kind];
+}
+// What the 8x8 estimate, loss included, is multiplied by (:863-866: the three constants are floats)
+inline float AcsWalkMul8x8(float distance) { return 1.0f + (-0.4f) / (distance + 1.4f); }
+
+// The table the walk reads: per 64x64 tile (raster order) [kind][cy][cx] floats, (cx, cy) the candidate's top-left block
+// inside the tile; the estimate already carries the kind's multiplier. Entries nothing asks for are never read.
+inline size_t AcsWalkTableIndex(size_t tile, uint32_t kind, uint32_t cx, uint32_t cy) { return tile * kAcsWalkTileFloats + kind * 64 + cy * 8 + cx; }
+
+// The candidates a walk over a tile of w x h blocks can ask for, one bit (cy * 8 + cx) per kind. The aligned walk: every
+// candidate aligned to its own size in both directions that fits (the squares' halves, and the odd last rows' and columns'
+// TryMergeAcs, come to exactly that). The floating passes (:1033-1057, step 1) add the 16-level square and its four halves
+// at every position not even in both coordinates, the 32-level one at every position not a multiple of four in both.
+inline void AcsWalkTileAsks(uint32_t w, uint32_t h, uint32_t floating, uint64_t asked[kAcsWalkKinds]) {
+  for (uint32_t k = 0; k < kAcsWalkKinds; k++) {
+    asked[k] = 0;
+    const uint32_t kx = 1u << AcsWalkLog2X(k), ky = 1u << AcsWalkLog2Y(k);
+    for (uint32_t cy = 0; cy + ky <= h; cy += ky)
+      for (uint32_t cx = 0; cx + kx <= w; cx += kx) asked[k] |= uint64_t(1) << (cy * 8 + cx);
+  }
+  if (!floating) return;
+  auto square = [&](uint32_t blocks, uint32_t jxk, uint32_t cx, uint32_t cy) {  // kinds jxk, jxk + 1 (KXJ), jxk + 2 (JXJ)
+    const uint32_t half = blocks / 2;
+    asked[jxk] |= (uint64_t(1) << (cy * 8 + cx)) | (uint64_t(1) << (cy * 8 + cx + half));
+    asked[jxk + 1] |= (uint64_t(1) << (cy * 8 + cx)) | (uint64_t(1) << ((cy + half) * 8 + cx));
+    asked[jxk + 2] |= uint64_t(1) << (cy * 8 + cx);
+  };
+  for (uint32_t cy = 0; cy + 1 < h; cy++)
+    for (uint32_t cx = 0; cx + 1 < w; cx++)
+      if ((cy | cx) % 2 != 0) square(2, 1, cx, cy);
+  for (uint32_t cy = 0; cy + 3 < h; cy++)
+    for (uint32_t cx = 0; cx + 3 < w; cx++)
+      if ((cy | cx) % 4 != 0) square(4, 4, cx, cy);
+}
+
+// The sizes a walk is defined for: blocks per side as the forward path has them, and a table whose indices fit 32 bits.
+inline bool AcsWalkSizeOk(uint32_t xb, uint32_t yb) {
+  if (!xb || !yb || xb > (1u << 15) || yb > (1u << 15)) return false;
+  return uint64_t((xb + 7) / 8) * ((yb + 7) / 8) * kAcsWalkTileFloats < (uint64_t(1) << 31);
+}
+// The candidate list of a frame of xb x yb blocks, grouped by kind (kind k is cand[first[k]] .. cand[first[k + 1]]), tiles in
+// raster order inside a kind and positions in raster order inside a tile; index[i] is the table entry of cand[i].
+struct AcsWalkList {
+  std::vector<JxlHipEncAcsCandidate> cand;
+  std::vector<uint32_t> index;
+  size_t first[kAcsWalkKinds + 1];
+};
+inline bool AcsWalkCandidates(uint32_t xb, uint32_t yb, uint32_t floating, AcsWalkList* out) {
+  if (!out || !AcsWalkSizeOk(xb, yb) || floating > 1) return false;
+  out->cand.clear();
+  out->index.clear();
+  const uint32_t tiles_x = (xb + 7) / 8, tiles_y = (yb + 7) / 8;
+  for (uint32_t k = 0; k < kAcsWalkKinds; k++) {
+    out->first[k] = out->cand.size();
+    for (uint32_t ty = 0; ty < tiles_y; ty++)
+      for (uint32_t tx = 0; tx < tiles_x; tx++) {
+        uint64_t asked[kAcsWalkKinds];
+        AcsWalkTileAsks(std::min(8u, xb - tx * 8), std::min(8u, yb - ty * 8), floating, asked);
+        for (uint32_t i = 0; i < 64; i++)
+          if (asked[k] >> i & 1) {
+            out->cand.push_back({AcsWalkStrategy(k), tx * 8 + (i & 7), ty * 8 + (i >> 3), AcsWalkEntropyMul(k)});
+            out->index.push_back(uint32_t(AcsWalkTableIndex(size_t(ty) * tiles_x + tx, k, i & 7, i >> 3)));
+          }
+      }
+  }
+  out->first[kAcsWalkKinds] = out->cand.size();
+  return true;
+}
+// What both forms of the stand-alone walk check before anything else
+inline bool AcsWalkArgsOk(const JxlHipEncAcsWalkDesc* d, const float* estimates, const uint8_t* acs) {
+  if (!d || !estimates || !acs || !AcsWalkSizeOk(d->xb, d->yb) || d->floating > 1) return false;
+  return d->distance > 0 && std::isfinite(d->distance);
+}
+
+// The state of one tile's walk: the tile's table, entropy_estimate[64], the strategy image of the tile as (kind << 1) | first
+// on an 8 x 8 grid, priority[64], and the tile's size in blocks (smaller than 8 at the right and bottom frame edges).
+// Coordinates are the tile's own: the reference's bx, by are multiples of 8, so `x % 8`, `x & ~7` and the image-size tests
+// read the same on them (a coordinate of 8 is either beyond the image or a multiple of 8: both return false).
+struct AcsWalkState {
+  const float* est;
+  float* entropy;
+  uint8_t* acs;
+  uint8_t* priority;
+  uint32_t w, h;
+};
+JXH_HD bool AcsWalkCrossesH(const AcsWalkState& s, uint32_t start_x, uint32_t y, uint32_t end_x) {  // :302-330
+  if (start_x >= s.w || y >= s.h) return false;
+  if (y % 8 == 0) return false;
+  end_x = end_x < s.w ? end_x : s.w;
+  while (start_x != 0 && !(s.acs[y * 8 + start_x] & 1)) --start_x;
+  for (uint32_t x = start_x; x < end_x;) {
+    const uint32_t a = s.acs[y * 8 + x];
+    if (a & 1) x += 1u << AcsWalkLog2X(a >> 1);
+    else return true;
+  }
+  return false;
+}
+JXH_HD bool AcsWalkCrossesV(const AcsWalkState& s, uint32_t x, uint32_t start_y, uint32_t end_y) {  // :332-362
+  if (x >= s.w || start_y >= s.h) return false;
+  if (x % 8 == 0) return false;
+  end_y = end_y < s.h ? end_y : s.h;
+  while (start_y != 0 && !(s.acs[start_y * 8 + x] & 1)) --start_y;
+  for (uint32_t y = start_y; y < end_y;) {
+    const uint32_t a = s.acs[y * 8 + x];
+    if (a & 1) y += 1u << AcsWalkLog2Y(a >> 1);
+    else return true;
+  }
+  return false;
+}
+// The four tests at the head of the square function (:725-732): does a transform placed earlier reach across the outline
+// of the blocks x blocks_y rectangle at (cx, cy)?
+JXH_HD bool AcsWalkLeaks(const AcsWalkState& s, uint32_t cx, uint32_t cy, uint32_t bx, uint32_t by) {
+  return AcsWalkCrossesH(s, cx, cy, cx + bx) || AcsWalkCrossesH(s, cx, cy + by, cx + bx) || AcsWalkCrossesV(s, cx, cy, cy + by) ||
+         AcsWalkCrossesV(s, cx + bx, cy, cy + by);
+}
+JXH_HD void AcsWalkSet(const AcsWalkState& s, uint32_t cx, uint32_t cy, uint32_t kind) {  // AcStrategyImage::Set
+  const uint32_t kx = 1u << AcsWalkLog2X(kind), ky = 1u << AcsWalkLog2Y(kind);
+  for (uint32_t iy = 0; iy < ky; iy++)
+    for (uint32_t ix = 0; ix < kx; ix++) s.acs[(cy + iy) * 8 + cx + ix] = uint8_t((kind << 1) | ((iy | ix) == 0 ? 1 : 0));
+}
+JXH_HD void AcsWalkSetEntropy(const AcsWalkState& s, uint32_t cx, uint32_t cy, uint32_t kind, float entropy) {  // :655-665
+  const uint32_t kx = 1u << AcsWalkLog2X(kind), ky = 1u << AcsWalkLog2Y(kind);
+  for (uint32_t dy = 0; dy < ky; dy++)
+    for (uint32_t dx = 0; dx < kx; dx++) s.entropy[(cy + dy) * 8 + cx + dx] = 0.0f;
+  s.entropy[cy * 8 + cx] = entropy;
+}
+// Two guards are not the reference's. They make every placement cover whole earlier transforms only, whatever the table
+// holds, so that the strategy image is a valid tiling by construction (the kernels after the walk index by it); on a table of
+// finite estimates above zero neither can refuse anything (tests/test_acs_walk.py holds them to that):
+//   - TryMergeAcs makes the four tests of AcsWalkLeaks before it accepts. In a full tile the reference tries DCT32X64 at
+//     (0, 4) after the 64-level square, whose halves carry no priority; over a DCT64X32 placed by that square it would leave
+//     an orphaned half. With finite positive estimates TryMergeAcs has placed that DCT64X32 itself, with its priority.
+//   - the square function places a half only if it took its estimate: the reference's FLT_MAX stand-in for "not taken" is
+//     below an infinite sum.
+// TryMergeAcs (:618-653)
+JXH_HD void AcsWalkTryMerge(const AcsWalkState& s, uint32_t kind, uint32_t cx, uint32_t cy, uint8_t candidate_priority) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const uint32_t kx = 1u << AcsWalkLog2X(kind), ky = 1u << AcsWalkLog2Y(kind);
+  float entropy_current = 0;
+  for (uint32_t iy = 0; iy < ky; ++iy)
+    for (uint32_t ix = 0; ix < kx; ++ix) {
+      if (s.priority[(cy + iy) * 8 + (cx + ix)] >= candidate_priority) return;
+      entropy_current += s.entropy[(cy + iy) * 8 + (cx + ix)];
+    }
+  const float entropy_candidate = s.est[kind * 64 + cy * 8 + cx];
+  if (entropy_candidate >= entropy_current) return;
+  if (AcsWalkLeaks(s, cx, cy, kx, ky)) return;
+  for (uint32_t iy = 0; iy < ky; iy++)
+    for (uint32_t ix = 0; ix < kx; ix++) {
+      s.entropy[(cy + iy) * 8 + cx + ix] = 0;
+      s.priority[(cy + iy) * 8 + cx + ix] = candidate_priority;
+    }
+  AcsWalkSet(s, cx, cy, kind);
+  s.entropy[cy * 8 + cx] = entropy_candidate;
+}
+// FindBestFirstLevelDivisionForSquare (:703-825) with allow_square_transform true; jxk is the kind of the tall half, jxk + 1
+// the wide one's, jxk + 2 the square's.
+JXH_HD void AcsWalkSquare(const AcsWalkState& s, uint32_t blocks, uint32_t jxk, uint32_t cx, uint32_t cy) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const uint32_t half = blocks / 2, kxj = jxk + 1, jxj = jxk + 2;
+  if (AcsWalkLeaks(s, cx, cy, blocks, blocks)) return;
+  const bool allow_JXK = !AcsWalkCrossesV(s, cx + half, cy, cy + blocks);
+  const bool allow_KXJ = !AcsWalkCrossesH(s, cx, cy + half, cx + blocks);
+  float entropy[2][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
+  for (uint32_t dy = 0; dy < blocks; ++dy)
+    for (uint32_t dx = 0; dx < blocks; ++dx) entropy[dy / half][dx / half] += s.entropy[(cy + dy) * 8 + (cx + dx)];
+  const float kMax = 3.402823466e+38f;
+  float entropy_JXK_left = kMax, entropy_JXK_right = kMax, entropy_KXJ_top = kMax, entropy_KXJ_bottom = kMax;
+  const bool take_left = allow_JXK && uint32_t(s.acs[cy * 8 + cx] >> 1) != jxk, take_right = allow_JXK && uint32_t(s.acs[cy * 8 + cx + half] >> 1) != jxk;
+  const bool take_top = allow_KXJ && uint32_t(s.acs[cy * 8 + cx] >> 1) != kxj, take_bottom = allow_KXJ && uint32_t(s.acs[(cy + half) * 8 + cx] >> 1) != kxj;
+  if (take_left) entropy_JXK_left = s.est[jxk * 64 + cy * 8 + cx];
+  if (take_right) entropy_JXK_right = s.est[jxk * 64 + cy * 8 + cx + half];
+  if (take_top) entropy_KXJ_top = s.est[kxj * 64 + cy * 8 + cx];
+  if (take_bottom) entropy_KXJ_bottom = s.est[kxj * 64 + (cy + half) * 8 + cx];
+  const float entropy_JXJ = s.est[jxj * 64 + cy * 8 + cx];
+  const float left = entropy[0][0] + entropy[1][0], right = entropy[0][1] + entropy[1][1];
+  const float top = entropy[0][0] + entropy[0][1], bottom = entropy[1][0] + entropy[1][1];
+  // (std::min(a, b) is b < a ? b : a)
+  const float costJxN = (left < entropy_JXK_left ? left : entropy_JXK_left) + (right < entropy_JXK_right ? right : entropy_JXK_right);
+  const float costNxJ = (top < entropy_KXJ_top ? top : entropy_KXJ_top) + (bottom < entropy_KXJ_bottom ? bottom : entropy_KXJ_bottom);
+  if (entropy_JXJ < costJxN && entropy_JXJ < costNxJ) {
+    AcsWalkSet(s, cx, cy, jxj);
+    AcsWalkSetEntropy(s, cx, cy, jxj, entropy_JXJ);
+  } else if (costJxN < costNxJ) {
+    if (take_left && entropy_JXK_left < left) {
+      AcsWalkSet(s, cx, cy, jxk);
+      AcsWalkSetEntropy(s, cx, cy, jxk, entropy_JXK_left);
+    }
+    if (take_right && entropy_JXK_right < right) {
+      AcsWalkSet(s, cx + half, cy, jxk);
+      AcsWalkSetEntropy(s, cx + half, cy, jxk, entropy_JXK_right);
+    }
+  } else {
+    if (take_top && entropy_KXJ_top < top) {
+      AcsWalkSet(s, cx, cy, kxj);
+      AcsWalkSetEntropy(s, cx, cy, kxj, entropy_KXJ_top);
+    }
+    if (take_bottom && entropy_KXJ_bottom < bottom) {
+      AcsWalkSet(s, cx, cy + half, kxj);
+      AcsWalkSetEntropy(s, cx, cy + half, kxj, entropy_KXJ_bottom);
+    }
+  }
+}
+// ProcessRectACS (:860-1058) from the 8x8 estimates on. The merge table is kTransformsForMerge (:907-920) as kinds of this
+// header: {16X8, 2}, {8X16, 2}, {16X32, 4}, {32X16, 4}, {64X32, 6}, {32X64, 6}; the loop body is the reference's, test by test.
+JXH_HD void AcsWalkTile(const AcsWalkState& s, float mul8x8, uint32_t floating) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  for (uint32_t i = 0; i < 64; i++) {
+    s.entropy[i] = 0.0f;
+    s.priority[i] = 0;
+    s.acs[i] = 1;  // (written for the whole grid: the blocks outside a partial tile are never read)
+  }
+  for (uint32_t iy = 0; iy < s.h; iy++)
+    for (uint32_t ix = 0; ix < s.w; ix++) s.entropy[iy * 8 + ix] = s.est[iy * 8 + ix] * mul8x8;
+  const uint32_t w = s.w, h = s.h;
+  for (uint32_t m = 0; m < 6; m++) {
+    const uint32_t kind = m == 0 ? 1u : m == 1 ? 2u : m == 2 ? 5u : m == 3 ? 4u : m == 4 ? 7u : 8u;
+    const uint8_t priority = m < 2 ? 2 : m < 4 ? 4 : 6;
+    const uint32_t kx = 1u << AcsWalkLog2X(kind), ky = 1u << AcsWalkLog2Y(kind);
+    for (uint32_t cy = 0; cy + ky - 1 < h; cy += ky)
+      for (uint32_t cx = 0; cx + kx - 1 < w; cx += kx) {
+        if (cy + 7 < h && cx + 7 < w) {
+          if (kind == 8) {
+            if ((cy | cx) % 8 == 0) AcsWalkSquare(s, 8, 7, cx, cy);
+            continue;
+          } else if (kind == 4) {
+            continue;
+          }
+        }
+        if ((kind == 5 && cy % 4 != 0) || (kind == 4 && cx % 4 != 0)) continue;
+        if (cy + 3 < h && cx + 3 < w) {
+          if (kind == 5) {
+            if ((cy | cx) % 4 == 0) AcsWalkSquare(s, 4, 4, cx, cy);
+            continue;
+          } else if (kind == 4) {
+            continue;
+          }
+        }
+        if ((kind == 5 && cy % 4 != 0) || (kind == 4 && cx % 4 != 0)) continue;
+        if (cy + 1 < h && cx + 1 < w) {
+          if (kind == 2) {
+            if ((cy | cx) % 2 == 0) AcsWalkSquare(s, 2, 1, cx, cy);
+            continue;
+          } else if (kind == 1) {
+            continue;
+          }
+        }
+        if ((kind == 2 && cy % 2 == 1) || (kind == 1 && cx % 2 == 1)) continue;
+        AcsWalkTryMerge(s, kind, cx, cy, priority);
+      }
+  }
+  if (!floating) return;
+  for (uint32_t cy = 0; cy + 1 < h; ++cy)
+    for (uint32_t cx = 0; cx + 1 < w; ++cx)
+      if ((cy | cx) % 2 != 0) AcsWalkSquare(s, 2, 1, cx, cy);
+  for (uint32_t cy = 0; cy + 3 < h; ++cy)
+    for (uint32_t cx = 0; cx + 3 < w; ++cx) {
+      if ((cy | cx) % 4 == 0) continue;
+      AcsWalkSquare(s, 4, 4, cx, cy);
+    }
 }
 
 // sRGB EOTF of one 8-bit code (transfer_functions-inl.h TF_SRGB)
