@@ -414,6 +414,18 @@ int jxlhip_debug_pixel_route(JxlHipContext* ctx, uint32_t* route);
  * k_entropy_lanes (the frame is kept in scan order when it has one pass), 1: k_entropy_uni, 2: k_entropy_ans (alias tables
  * beyond the LDS budget, read in place), 3: k_entropy_generic (prefix codes and / or LZ77). */
 int jxlhip_debug_entropy_route(JxlHipContext* ctx, uint32_t* route);
+/* Test access: the order in which the lane kernel's workgroups of the batch last prepared on `ctx0` (the first context of a
+ * jxlhip_run_entropy_batch call) are dispatched. wg_unit[p] = the unit (sections of one frame that share a histogram set,
+ * numbered in frame order) of the p-th workgroup, est[p] = that unit's estimated length (1/16 token; longest first unless
+ * JXLHIP_WG_ORDER says otherwise). `n` is the room in both arrays, at least the batch's workgroups; the entries past them
+ * are set to 0xFFFFFFFF / 0. */
+int jxlhip_debug_entropy_order(JxlHipContext* ctx0, uint32_t* wg_unit, uint64_t* est, size_t n);
+/* Measurement aid: the per-wave records of a lane-kernel launch made on `ctx0` under JXLHIP_LANES_PROF=2 (records are kept,
+ * not printed, and the launch is not waited for): eight uint64 per workgroup, [1] and [7] = the wave's first and last
+ * instruction on the clock all XCDs share (100 MHz), [6] = HW_ID | XCC_ID << 32. `back` = 0 is the last launch, 1 the one
+ * before it, ... up to 7. Waits for the stream. *workgroups = the launch's
+ * workgroups; `records` (may be NULL) has room for `n` of them. */
+int jxlhip_debug_entropy_timeline(JxlHipContext* ctx0, uint32_t back, uint64_t* records, size_t n, size_t* workgroups);
 
 /* Debug aid: with JXLHIP_GUARD=1 in the environment every device buffer of a context is allocated with a 4 KiB guard
  * band either side, filled with a pattern. Waits for the device, then *touched = 0 when every band is intact, else

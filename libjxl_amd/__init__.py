@@ -475,6 +475,28 @@ class HipContext:
         _check(L.jxlhip_debug_entropy_route(self._h, ctypes.byref(r)), "jxlhip_debug_entropy_route")
         return int(r.value)
 
+    def entropy_order(self, room=65536):
+        """Test access (jxlhip_debug_entropy_order): of the lane-kernel batch last prepared with this context first, the unit
+        of every workgroup in dispatch order and the estimated length of that unit."""
+        L = lib()
+        L.jxlhip_debug_entropy_order.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        unit, est = np.zeros(room, np.uint32), np.zeros(room, np.uint64)
+        _check(L.jxlhip_debug_entropy_order(self._h, unit.ctypes.data, est.ctypes.data, room), "jxlhip_debug_entropy_order")
+        n = int((unit != 0xFFFFFFFF).sum())
+        return unit[:n].copy(), est[:n].copy()
+
+    def entropy_timeline(self, back=0):
+        """Measurement aid (jxlhip_debug_entropy_timeline, JXLHIP_LANES_PROF=2): the (workgroups, 8) uint64 records of the
+        lane-kernel launch `back` launches ago on this context."""
+        L = lib()
+        L.jxlhip_debug_entropy_timeline.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+                                                    ctypes.POINTER(ctypes.c_size_t)]
+        n = ctypes.c_size_t()
+        _check(L.jxlhip_debug_entropy_timeline(self._h, back, None, 0, ctypes.byref(n)), "jxlhip_debug_entropy_timeline")
+        rec = np.zeros((n.value, 8), np.uint64)
+        _check(L.jxlhip_debug_entropy_timeline(self._h, back, rec.ctypes.data, n.value, ctypes.byref(n)), "jxlhip_debug_entropy_timeline")
+        return rec
+
     def section_end_bits(self):
         """jxlhip_get_section_end_bits: [pass][group], the bit (from the section's first byte) where the entropy stage's
         coefficient walk ended."""

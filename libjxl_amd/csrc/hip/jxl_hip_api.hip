@@ -18,6 +18,7 @@
 
 #include "../../../include/jxl_amd_hip.h"
 #include "../host/jxh_enc_shared.h"
+#include "../host/jxh_launch_order.h"
 #include "../host/jxh_upload_plan.h"
 #include "jxl_hip_kernels.h"
 #include "jxl_hip_entropy_lanes.h"
@@ -225,6 +226,12 @@ struct JxlHipContext {
   bool batch_a6 = false;      // ... or keeps them in LDS in the six-byte form (jxl_hip_entropy_lanes.h LanesLdsLayout)
   bool batch_prefix = false;  // ... decodes prefix codes
   int batch_kernel = -1;
+  // JXLHIP_LANES_PROF=2 (measurement aid): the per-wave records of the last kTimelineKeep lane-kernel launches
+  Buf lanes_timeline;
+  size_t timeline_launches = 0, timeline_stride = 0, timeline_wgs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int batch_order = -1;                  // JXLHIP_WG_ORDER the batch was planned under
+  std::vector<uint32_t> batch_wg_unit;   // (jxlhip_debug_entropy_order) workgroup -> unit as uploaded, and the
+  std::vector<uint64_t> batch_wg_est;    // estimate of every workgroup's unit (jxh_launch_order.h)
   std::vector<uint32_t> sec_size_host, sec_sel_host, pass_clusters, pass_log_alpha;
   // Coefficient layout of this frame (see TransformParams::scan_order); scan order is produced by k_entropy_lanes.
   // band decode: groups this context decodes (band + one group row either side), pixel rows it produces
@@ -554,7 +561,7 @@ int jxlhip_ctx_create(int device, JxlHipContext** out) {
 static std::vector<Buf*> AllBufs(JxlHipContext* c) {
   std::vector<Buf*> all = {&c->basis, &c->sections, &c->sec_word, &c->sec_size, &c->blocks, &c->gbb, &c->bctx_lut, &c->dequant, &c->dc, &c->dc_raw, &c->dc_q, &c->dc_ep, &c->sharp,
                 &c->inv_sigma, &c->ytox, &c->ytob, &c->passes_dev, &c->coeffs, &c->errors, &c->plane[0], &c->plane[1],
-                &c->plane[2], &c->rgb, &c->tlist, &c->scratch, &c->ep_dev, &c->batch_params, &c->batch_map, &c->batch_lanes, &c->ups_kernel, &c->kend, &c->block_recs, &c->dequant_scan, &c->ec_stage, &c->alpha_patched, &c->trecs, &c->enc_tok_orders, &c->enc_tok_blk, &c->enc_tok_info,
+                &c->plane[2], &c->rgb, &c->tlist, &c->scratch, &c->ep_dev, &c->batch_params, &c->batch_map, &c->batch_lanes, &c->lanes_timeline, &c->ups_kernel, &c->kend, &c->block_recs, &c->dequant_scan, &c->ec_stage, &c->alpha_patched, &c->trecs, &c->enc_tok_orders, &c->enc_tok_blk, &c->enc_tok_info,
                 &c->enc_tok_off, &c->enc_tok_nzmap, &c->enc_tok_small, &c->enc_tok_out, &c->enc_tok_base, &c->tb_params, &c->tb_desc, &c->fb_params, &c->alpha, &c->sec_end, &c->lz_window, &c->mod.pool, &c->mod.sections, &c->mod.blob, &c->mod.streams,
                 &c->mod.rects, &c->mod.status, &c->mod.end_bits, &c->mod.scratch, &c->mod.windows, &c->mod.batch_streams, &c->mod.batch_ops, &c->frame_blob, &c->noise, &c->spl_seg, &c->spl_row_start, &c->spl_row_seg, &c->spl_planes, &c->pat_rec, &c->pat_row_start, &c->pat_row_list,
                 &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in, &c->enc_mask1x1,
@@ -935,9 +942,10 @@ static void AdoptFrame(JxlHipContext* c, const JxlHipFrameDesc& d, const upload:
   c->lane_multi = E.lane_multi;
   c->alias_lds = E.alias_lds;
   c->lds_entropy = E.lds_ctx_bytes + E.lds_alias_bytes + 3072;
+  if (c->lanes || c->scan_order)  // (PrepareBatch's cost estimate; jxlhip_download("coeffs"))
+    c->gbb_host.assign(d.group_block_begin, d.group_block_begin + d.num_groups + 1);
   if (c->scan_order) {  // for jxlhip_download("coeffs")
     c->blocks_host.assign(d.blocks, d.blocks + d.num_blocks);
-    c->gbb_host.assign(d.group_block_begin, d.group_block_begin + d.num_groups + 1);
     c->orders_host.assign(d.passes[0].orders, d.passes[0].orders + d.passes[0].orders_size);
     memcpy(c->order_offset_host, d.passes[0].order_offset, sizeof(c->order_offset_host));
   }
@@ -1658,8 +1666,26 @@ static int LaunchEntropyLanesW(JxlHipContext* c0) {
   b.debug = uint32_t(EnvInt("JXLHIP_LANES_DEBUG", 0));
   b.prof = nullptr;
   b.started = c0->batch_ctxs.size() > 1 ? GateCounter(c0) : nullptr;
-  const bool prof = EnvInt("JXLHIP_LANES_PROF", 0) != 0;  // debugging aid: per-wave cycle split, printed to stderr
+  // debugging aid: per-wave cycle split, printed to stderr (1); 2: per-wave start and end on the clock all XCDs share, kept
+  // for jxlhip_debug_entropy_timeline and not waited for, so that the launches around this one overlap it as they do unprofiled
+  const int prof_mode = EnvInt("JXLHIP_LANES_PROF", 0);
+  const bool prof = prof_mode != 0 && prof_mode != 2;
   const size_t nwaves = c0->batch_wgs;
+  if (AIDS && prof_mode == 2) {
+    constexpr size_t kTimelineKeep = sizeof(c0->timeline_wgs) / sizeof(c0->timeline_wgs[0]);
+    if (nwaves * 64 > c0->timeline_stride) {  // (the first launch, or a larger one: earlier records are dropped)
+      HIP_TRY(hipStreamSynchronize(c0->stream));
+      int r = c0->lanes_timeline.Ensure(nwaves * 64 * kTimelineKeep);
+      if (r) return r;
+      c0->timeline_stride = nwaves * 64;
+      for (size_t& w : c0->timeline_wgs) w = 0;
+    }
+    const size_t slot = c0->timeline_launches++ % kTimelineKeep;
+    c0->timeline_wgs[slot] = nwaves;
+    b.prof = reinterpret_cast<unsigned long long*>(c0->lanes_timeline.as<uint8_t>() + slot * c0->timeline_stride);
+    b.debug |= 64;
+    HIP_TRY(hipMemsetAsync(b.prof, 0, nwaves * 64, c0->stream));
+  }
   if (prof) {
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.prof), nwaves * 64));
     HIP_TRY(hipMemsetAsync(b.prof, 0, nwaves * 64, c0->stream));
@@ -1739,7 +1765,11 @@ static int LaunchEntropyUniBatch(JxlHipContext* c0) {
 // kernel, the lane -> section assignment (sections sorted by compressed size inside each frame so that the lanes of a
 // wave finish together; `lanes_per_wave` populated lanes per wave so that small batches still spread over all SIMDs).
 static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n, int kernel) {
-  bool same = c0->batch_ctxs.size() == n && c0->batch_kernel == kernel;
+  // measurement aid: JXLHIP_WG_ORDER = 0 emits the lane kernel's workgroups in frame order, 2 in frame order dealt over
+  // the XCDs (jxh_launch_order.h kDealt); 1, the default: longest estimated unit first
+  int wg_order = EnvInt("JXLHIP_WG_ORDER", 1);
+  if (wg_order < 0 || wg_order > 2) wg_order = 1;
+  bool same = c0->batch_ctxs.size() == n && c0->batch_kernel == kernel && c0->batch_order == wg_order;
   for (size_t i = 0; same && i < n; i++) same = c0->batch_ctxs[i] == ctxs[i] && c0->batch_gens[i] == ctxs[i]->generation;
   if (same) return 0;
   std::vector<jxlhip::EntropyParams> params(n);
@@ -1767,6 +1797,8 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
     struct Unit {
       uint32_t frame, sel, pass, begin, count, min_lanes, lanes;
     };
+    std::vector<uint64_t> unit_est;
+    std::vector<uint32_t> unit_waves;
     std::vector<Unit> units;
     std::vector<uint32_t> order;
     size_t min_total = 0, total_sections = 0;
@@ -1820,6 +1852,18 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
     for (const Unit& u : units) {
       const uint32_t waves = (u.lanes + lanes_per_wave - 1) / lanes_per_wave;
       const uint32_t unit_index = uint32_t(unit_desc.size() / 4);
+      {  // how long the unit will take: its queue replayed with the sections' estimated costs
+        const JxlHipContext* c = ctxs[u.frame];
+        const uint32_t* sz = c->sec_size_host.data() + size_t(u.pass) * c->ng;
+        std::vector<uint32_t> bytes(u.count), blocks(u.count);
+        for (uint32_t j = 0; j < u.count; j++) {
+          const uint32_t g = list[u.begin + j];
+          bytes[j] = sz[g];
+          blocks[j] = g + 1 < c->gbb_host.size() ? c->gbb_host[g + 1] - c->gbb_host[g] : 0;
+        }
+        unit_est.push_back(jxh::launch_order::UnitEstimate(bytes.data(), blocks.data(), u.count, u.lanes));
+        unit_waves.push_back(waves);
+      }
       unit_desc.push_back(u.frame | u.sel << 16);
       unit_desc.push_back(u.begin);
       unit_desc.push_back(u.count);
@@ -1829,6 +1873,23 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
         map.push_back(unit_index);
         wave_lanes.push_back(uint8_t(cnt));
       }
+    }
+    // The hardware starts workgroups in index order, and those of the next launch in the LDS slots that ending ones free:
+    // the longest units go first, so that what starts last is short (jxh_launch_order.h). Only the workgroup -> unit map
+    // is permuted; the waves of a unit stay adjacent.
+    {
+      const std::vector<uint32_t> from = jxh::launch_order::OrderWorkgroups(unit_est.data(), unit_waves.data(), units.size(), wg_order);
+      std::vector<uint32_t> map2(map.size());
+      std::vector<uint8_t> lanes2(map.size());
+      c0->batch_wg_est.resize(map.size());
+      for (size_t p = 0; p < from.size(); p++) {
+        map2[p] = map[from[p]];
+        lanes2[p] = wave_lanes[from[p]];
+        c0->batch_wg_est[p] = unit_est[map2[p]];
+      }
+      map.swap(map2);
+      wave_lanes.swap(lanes2);
+      c0->batch_wg_unit = map;
     }
     // LDS of the launch = the largest workgroup. With the alias tables in LDS a CU holds 160 KB / that many workgroups;
     // when that leaves part of the launch waiting for a second round (libjxl-sized tables: 128 clusters x 2^6 slots are
@@ -1872,6 +1933,8 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
               total_sections, min_total, lanes_per_wave, map.size(), lds,
               c0->lane_prefix ? "prefix" : (a6 ? "lds6" : (galias ? "global" : "lds8")));
   } else {
+    c0->batch_wg_unit.clear();
+    c0->batch_wg_est.clear();
     for (size_t i = 0; i < n; i++) {
       const uint32_t wgs = (ctxs[i]->ng + kEntropyWPG - 1) / kEntropyWPG;
       for (uint32_t j = 0; j < wgs; j++) map.push_back(uint32_t(i) << 16 | j);
@@ -1908,6 +1971,7 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
   c0->batch_wgs = uint32_t(map.size());
   c0->batch_lds = lds;
   c0->batch_kernel = kernel;
+  c0->batch_order = wg_order;
   return 0;
 }
 
@@ -3271,6 +3335,32 @@ int jxlhip_debug_pixel_route(JxlHipContext* c, uint32_t* route) {
   return 0;
 }
 
+// Test access: the workgroup -> unit map of the lane-kernel batch last prepared on `ctx0` (the first context of a
+// jxlhip_run_entropy_batch call) and the estimated length of every workgroup's unit, in dispatch order. `n` is the room
+// in both arrays; entries past the batch's workgroups are set to 0xFFFFFFFF / 0.
+int jxlhip_debug_entropy_order(JxlHipContext* ctx0, uint32_t* wg_unit, uint64_t* est, size_t n) {
+  if (!ctx0 || !wg_unit || !est) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (ctx0->batch_wg_unit.size() > n) return JXLHIP_ERR_INVALID_ARGUMENT;
+  for (size_t i = 0; i < n; i++) {
+    const bool in = i < ctx0->batch_wg_unit.size();
+    wg_unit[i] = in ? ctx0->batch_wg_unit[i] : 0xFFFFFFFFu;
+    est[i] = in ? ctx0->batch_wg_est[i] : 0;
+  }
+  return 0;
+}
+int jxlhip_debug_entropy_timeline(JxlHipContext* ctx0, uint32_t back, uint64_t* records, size_t n, size_t* workgroups) {
+  if (!ctx0 || !workgroups) return JXLHIP_ERR_INVALID_ARGUMENT;
+  constexpr size_t kKeep = sizeof(ctx0->timeline_wgs) / sizeof(ctx0->timeline_wgs[0]);
+  if (back >= kKeep || back >= ctx0->timeline_launches) return JXLHIP_ERR_INVALID_ARGUMENT;
+  const size_t slot = (ctx0->timeline_launches - 1 - back) % kKeep, wgs = ctx0->timeline_wgs[slot];
+  *workgroups = wgs;
+  if (!records) return 0;
+  if (n < wgs || !wgs) return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(ctx0->device));
+  HIP_TRY(hipStreamSynchronize(ctx0->stream));
+  HIP_TRY(hipMemcpy(records, ctx0->lanes_timeline.as<uint8_t>() + slot * ctx0->timeline_stride, wgs * 64, hipMemcpyDeviceToHost));
+  return 0;
+}
 int jxlhip_debug_entropy_route(JxlHipContext* c, uint32_t* route) {
   if (!c || !route) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;

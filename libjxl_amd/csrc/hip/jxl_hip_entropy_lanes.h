@@ -58,7 +58,8 @@ struct EntropyLaneBatch {
   uint32_t wait_shift;          // the service phase runs once (waiting lanes << wait_shift) >= runnable lanes
   uint32_t refill_mask;         // a refill round every (refill_mask + 1) rounds (a power of two)
   uint32_t debug;               // measurement aid: bit 0 = skip the coefficient stores (results are then invalid),
-                                // bit 1 = report every section's coefficient-token count in its error word
+                                // bit 1 = report every section's coefficient-token count in its error word,
+                                // bit 6 = prof words 1 and 7 hold the wave's start and end (wall_clock64), word 6 HW_ID | XCC_ID << 32
   unsigned long long* started;  // optional (may be NULL): every workgroup adds 1 when it begins (the host gates other launches on
                                 // "all of this launch's workgroups hold their LDS": jxl_hip_api.hip EntropyGate)
   unsigned long long* prof;     // optional (may be NULL): per wave {cycles total, cycles in service, services, hot trips,
@@ -179,6 +180,8 @@ __global__ __launch_bounds__(64) void k_entropy_lanes(EntropyLaneBatch B_) {
   }
   extern __shared__ __align__(16) uint8_t lds_raw[];
   const uint32_t tid = threadIdx.x, lane = tid & 63;
+  unsigned long long t_wall = 0;  // (measurement aid, debug bit 6: when the workgroup started, on the clock all XCDs share)
+  if (AIDS && B.prof && (B.debug & 64)) t_wall = wall_clock64();
   if (B_.started && tid == 0) __hip_atomic_fetch_add(B_.started, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   // ---- the launch description and the frame's parameter block, through the scalar cache into SGPRs
   typedef const uint32_t __attribute__((address_space(4)))* CU32;
@@ -936,11 +939,15 @@ __global__ __launch_bounds__(64) void k_entropy_lanes(EntropyLaneBatch B_) {
     o[6] = t_dma;
     o[7] = t_trans;
     if (B.debug & 32) o[6] = n_calls;  // (measurement aid: calls of the trip loop instead of the lanes served)
-    if (B.debug & 16) {  // (measurement aid: where the wave ran: HW_ID | XCC_ID << 32 instead of the lanes served)
+    if (B.debug & (16 | 64)) {  // (measurement aid: where the wave ran: HW_ID | XCC_ID << 32 instead of the lanes served)
       uint32_t hw, xcc;
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
       o[6] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
+    }
+    if (B.debug & 64) {  // (measurement aid: the wave's start and end instead of the service and transition cycles)
+      o[1] = t_wall;
+      o[7] = wall_clock64();
     }
   }
   if (B.prof) {  // lane-trips of the wave (how full its trips were)
