@@ -119,6 +119,15 @@ int jxlamd_modframe_parse_at(const uint8_t* data, size_t size, size_t frame_pos,
 size_t jxlamd_modframe_end(const JxlAmdModFrame* frame, uint32_t* duration_last_timecode);
 void jxlamd_modframe_placement(const JxlAmdModFrame* frame, JxlAmdFramePlacement* placement);
 size_t jxlamd_modframe_placement_sized(const JxlAmdModFrame* frame, void* placement, size_t out_size);
+/* Test access to a frame's splines, as sized copies (at most out_size bytes are written; the return value is the size of the
+ * whole in bytes, 0 for a frame without splines or an unknown `what`). what = 0: the dictionary as parsed, int32 words:
+ * quantisation adjustment, number of splines, then per spline its starting point x, y, the number of further control
+ * points, their double deltas (x, y each), 3 x 32 colour DCT integers (X, Y, B) and 32 sigma DCT integers. what = 1 .. 3:
+ * the draw cache built from it, as JxlHipSplines lays it out: segments (8 floats each), row_start (ysize + 1 uint32),
+ * row_segments (uint32). what = 4: four words: the xsize and ysize the cache was built for (the frame's own, also when the
+ * frame is upsampled) and, as floats, the y_to_x and y_to_b used (a Modular frame: 0 and 1). */
+size_t jxlamd_frame_splines(const JxlAmdFrame* frame, uint32_t what, void* out, size_t out_size);
+size_t jxlamd_modframe_splines(const JxlAmdModFrame* frame, uint32_t what, void* out, size_t out_size);
 void jxlamd_modframe_free(JxlAmdModFrame* frame);
 /* info[0..15]: xsize, ysize, colour channels, has alpha, bits per sample, streams, channel buffers, transform operations,
  * extra channels, compressed bytes of all sections; [10..12] largest symbol-table set (words), LZ77 anywhere, largest

@@ -586,6 +586,28 @@ int jxlhip_canvas_download_alpha(JxlHipCanvas* canvas, float* dst, size_t n);
  * [n][4], out planar [4][n]; for the reference's own blending vectors (lib/jxl/alpha_test.cc) against the kernel itself. */
 int jxlhip_debug_blend(int device, const float* bg, const float* fg, size_t n, const JxlHipBlend* blend, uint32_t has_alpha,
                        uint32_t alpha_premultiplied, float* out);
+/* Test entry: the blend kernel as jxlhip_canvas_blend launches it, on host arrays: a canvas of xsize x ysize, the slot the
+ * colour background comes from and the slot the alpha background comes from (each planar [4][ysize][xsize]: the first reads
+ * planes 0..2, the second plane 3; NULL: a slot never written, zeros), the frame fg (interleaved [fysize][fxsize][4]) placed
+ * at blend->x0 / y0, which may lie partly or wholly outside; out planar [4][ysize][xsize]. source / alpha_source / save_slot
+ * of `blend` are not used. Sizes of 0 or above 16384, unknown modes and origins beyond +-2^20 are refused before any launch. */
+int jxlhip_debug_blend_rect(int device, uint32_t xsize, uint32_t ysize, const float* bg_color, const float* bg_alpha, const float* fg,
+                            uint32_t fxsize, uint32_t fysize, const JxlHipBlend* blend, uint32_t has_alpha, uint32_t alpha_premultiplied,
+                            float* out);
+/* Test entry: the patch kernel alone on dense host planes [3][ysize][xsize] (alpha_in / alpha_out [ysize][xsize], both or
+ * neither; given exactly when patches->uses_alpha is set), rows y_begin .. y_end. Here patches->slot_planes[k]
+ * ([3][slot_h][slot_w]) and slot_alpha[k] ([slot_h][slot_w]) are HOST arrays. The dictionary is checked like an upload's
+ * (rectangles inside their slot and inside the rows of the planes, row lists consistent; a rectangle may reach past xsize,
+ * where the kernel clips it, up to column 32768) and refused before any launch otherwise, as are NULLs, sizes of 0 or above
+ * 16384, an empty dictionary and y_end > ysize. */
+int jxlhip_debug_patches(JxlHipContext* ctx, const float* planes_in, const float* alpha_in, uint32_t xsize, uint32_t ysize,
+                         const JxlHipPatches* patches, uint32_t y_begin, uint32_t y_end, float* planes_out, float* alpha_out);
+/* Test entry: the spline kernel alone on dense host planes [3][ysize][xsize] and a draw cache in host memory, rows
+ * y_begin .. y_end (the other rows come back as given). Refused before any launch: NULLs, sizes of 0 or above 16384, an empty
+ * cache, y_end > ysize, row lists that are inconsistent or name a missing segment, a segment value that is not finite, a
+ * centre or maximum distance beyond 2^30. */
+int jxlhip_debug_splines(JxlHipContext* ctx, const float* planes_in, uint32_t xsize, uint32_t ysize, const JxlHipSplines* splines,
+                         uint32_t y_begin, uint32_t y_end, float* planes_out);
 
 /* ---- Forward path (first slice): the pixel-domain half of a VarDCT encode on the device.
  * Replaces, behind lib/jxl/enc_frame.cc:1135-1166's per-group loop: SRGBToXYB (enc_xyb.cc:152-174), the Gaborish

@@ -88,6 +88,36 @@ def _check(r, what):
         raise JxlAmdError("%s failed: code %d %s" % (what, r, err.decode() if err else ""))
 
 
+def _frame_splines(fn, handle):
+    """What jxlamd_frame_splines / jxlamd_modframe_splines hand out, or None for a frame without splines."""
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+    fn.restype = ctypes.c_size_t
+
+    def part(what, dtype):
+        a = np.zeros(int(fn(handle, what, None, 0)) // 4, dtype)
+        if a.size:
+            fn(handle, what, a.ctypes.data, a.nbytes)
+        return a
+
+    words = part(0, np.int32)
+    if not words.size:
+        return None
+    w = [int(v) for v in words]
+    splines, pos = [], 2
+    for _ in range(w[1]):
+        n = w[pos + 2]
+        deltas = [(w[pos + 3 + 2 * k], w[pos + 4 + 2 * k]) for k in range(n)]
+        q = pos + 3 + 2 * n
+        splines.append(dict(start=(w[pos], w[pos + 1]), deltas=deltas, color=[w[q + 32 * c:q + 32 * c + 32] for c in range(3)],
+                            sigma=w[q + 96:q + 128]))
+        pos = q + 128
+    assert pos == len(w)
+    used = part(4, np.uint32)
+    return dict(dictionary=dict(adjustment=w[0], splines=splines), words=words, segments=part(1, np.float32).reshape(-1, 8),
+                row_start=part(2, np.uint32), row_segments=part(3, np.uint32), xsize=int(used[0]), ysize=int(used[1]),
+                y_to_x=float(used[2:3].view(np.float32)[0]), y_to_b=float(used[3:4].view(np.float32)[0]))
+
+
 class Frame:
     """Host-parsed frame (headers, DC, tables); AC sections stay compressed."""
 
@@ -131,6 +161,10 @@ class Frame:
         k = np.zeros((factor, factor, 5, 5), np.float32)
         _check(L.jxlamd_upsampling_kernels(self._h, factor, k.ctypes.data), "jxlamd_upsampling_kernels")
         return k
+
+    def splines(self):
+        """Test access: the spline dictionary as parsed and the draw cache built from it (None: no splines)."""
+        return _frame_splines(lib().jxlamd_frame_splines, self._h)
 
     def close(self):
         if self._h:
@@ -177,6 +211,10 @@ class ModFrame:
         if L.jxlamd_modframe_section(self._h, index, ctypes.byref(off), ctypes.byref(size)):
             raise IndexError("no section %d" % index)
         return int(off.value), int(size.value)
+
+    def splines(self):
+        """Test access: as Frame.splines()."""
+        return _frame_splines(lib().jxlamd_modframe_splines, self._h)
 
     def close(self):
         if self._h:

@@ -571,6 +571,71 @@ size_t jxlamd_modframe_placement_sized(const JxlAmdModFrame* f, void* out, size_
   if (out) memcpy(out, &p, out_size < sizeof(p) ? out_size : sizeof(p));
   return sizeof(p);
 }
+// Test access to a frame's splines (jxl_amd.h): the dictionary as parsed, in the words jxlenc_set_splines takes, and the draw
+// cache built from it. A sized copy: at most out_size bytes are written, the return value is the size of the whole.
+static size_t CopySplines(bool has, const jxh::Splines& s, uint32_t xsize, uint32_t ysize, float y_to_x, float y_to_b, uint32_t what,
+                          void* out, size_t out_size) {
+  if (!has) return 0;
+  std::vector<int32_t> words;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (what) {
+    case 0:
+      words.push_back(s.quant_adjust);
+      words.push_back(int32_t(s.splines.size()));
+      for (size_t i = 0; i < s.splines.size(); i++) {
+        const jxh::QuantSpline& q = s.splines[i];
+        words.push_back(int32_t(s.start[i].x));
+        words.push_back(int32_t(s.start[i].y));
+        words.push_back(int32_t(q.deltas.size()));
+        for (const auto& d : q.deltas) {
+          words.push_back(int32_t(d.first));
+          words.push_back(int32_t(d.second));
+        }
+        for (int c = 0; c < 3; c++) words.insert(words.end(), q.color_dct[c], q.color_dct[c] + 32);
+        words.insert(words.end(), q.sigma_dct, q.sigma_dct + 32);
+      }
+      break;
+    case 1:
+      src = s.segments.data();
+      bytes = s.segments.size() * sizeof(float);
+      break;
+    case 2:
+      src = s.row_start.data();
+      bytes = s.row_start.size() * sizeof(uint32_t);
+      break;
+    case 3:
+      src = s.row_segments.data();
+      bytes = s.row_segments.size() * sizeof(uint32_t);
+      break;
+    case 4: {
+      words.resize(4);
+      words[0] = int32_t(xsize);
+      words[1] = int32_t(ysize);
+      memcpy(&words[2], &y_to_x, 4);
+      memcpy(&words[3], &y_to_b, 4);
+      break;
+    }
+    default:
+      return 0;
+  }
+  if (!src) {
+    src = words.data();
+    bytes = words.size() * sizeof(int32_t);
+  }
+  if (out && bytes) memcpy(out, src, out_size < bytes ? out_size : bytes);
+  return bytes;
+}
+size_t jxlamd_frame_splines(const JxlAmdFrame* f, uint32_t what, void* out, size_t out_size) {
+  if (!f) return 0;
+  const jxh::FramePlan& P = f->plan;
+  return CopySplines(P.has_splines, P.splines, uint32_t(P.dim.xsize), uint32_t(P.dim.ysize), P.base_corr_x, P.base_corr_b, what, out, out_size);
+}
+size_t jxlamd_modframe_splines(const JxlAmdModFrame* f, uint32_t what, void* out, size_t out_size) {
+  if (!f) return 0;
+  const jxh::ModFramePlan& P = f->plan;
+  return CopySplines(P.has_splines, P.splines, uint32_t(P.dim.xsize), uint32_t(P.dim.ysize), 0.0f, 1.0f, what, out, out_size);
+}
 void jxlamd_modframe_free(JxlAmdModFrame* f) { delete f; }
 size_t jxlamd_modframe_end(const JxlAmdModFrame* f, uint32_t* t) {
   if (t) {

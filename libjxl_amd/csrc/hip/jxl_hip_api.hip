@@ -3742,6 +3742,154 @@ int jxlhip_debug_blend(int device, const float* bg, const float* fg, size_t n, c
   return e == hipSuccess ? 0 : -int(e);
 }
 
+// Device buffers of one test entry: freed together, whichever way the entry leaves.
+namespace {
+struct DebugBufs {
+  Buf b[12];
+  ~DebugBufs() {
+    for (Buf& x : b) x.Free();
+  }
+  // `bytes` of host memory into buffer k (NULL: the buffer stays empty)
+  int Put(int k, const void* host, size_t bytes) {
+    if (!host) return 0;
+    int r = b[k].Ensure(bytes);
+    if (r) return r;
+    HIP_TRY(hipMemcpy(b[k].p, host, bytes, hipMemcpyHostToDevice));
+    return 0;
+  }
+};
+}  // namespace
+
+// Test entry: k_canvas_blend as jxlhip_canvas_blend launches it, on a caller's canvas, backgrounds and frame.
+int jxlhip_debug_blend_rect(int device, uint32_t xsize, uint32_t ysize, const float* bg_color, const float* bg_alpha, const float* fg,
+                            uint32_t fxsize, uint32_t fysize, const JxlHipBlend* b, uint32_t has_alpha, uint32_t premultiplied, float* out) {
+  if (!fg || !b || !out || !xsize || !ysize || !fxsize || !fysize) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (xsize > (1u << 14) || ysize > (1u << 14) || fxsize > (1u << 14) || fysize > (1u << 14)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (b->mode > 4 || b->alpha_mode > 4 || b->x0 < -(1 << 20) || b->x0 > (1 << 20) || b->y0 < -(1 << 20) || b->y0 > (1 << 20))
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(device));
+  const size_t bytes = size_t(xsize) * ysize * 16, fbytes = size_t(fxsize) * fysize * 16;
+  DebugBufs d;
+  int r;
+  if ((r = d.Put(0, bg_color, bytes)) || (r = d.Put(1, bg_alpha, bytes)) || (r = d.Put(2, fg, fbytes)) || (r = d.b[3].Ensure(bytes))) return r;
+  jxlhip::BlendParams P;
+  memset(&P, 0, sizeof(P));
+  P.out = d.b[3].as<float>();
+  P.bg_color = d.b[0].as<float>();
+  P.bg_alpha = d.b[1].as<float>();
+  P.fg = d.b[2].as<float>();
+  P.w = xsize;
+  P.h = ysize;
+  P.fw = fxsize;
+  P.fh = fysize;
+  P.x0 = b->x0;
+  P.y0 = b->y0;
+  P.mode = b->mode;
+  P.alpha_mode = b->alpha_mode;
+  P.clamp = b->clamp;
+  P.alpha_clamp = b->alpha_clamp;
+  P.has_alpha = has_alpha;
+  P.premultiplied = premultiplied;
+  hipLaunchKernelGGL(jxlhip::k_canvas_blend, dim3((xsize + 255) / 256, ysize), dim3(256), 0, nullptr, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, d.b[3].p, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Test entry: k_patches_add as the filter stage launches it, on a caller's dense planes; the reference frames and every
+// table come from host memory and are checked like an upload's (upload::CheckPatches) before anything is launched.
+int jxlhip_debug_patches(JxlHipContext* c, const float* planes_in, const float* alpha_in, uint32_t xsize, uint32_t ysize, const JxlHipPatches* pt,
+                         uint32_t y_begin, uint32_t y_end, float* planes_out, float* alpha_out) {
+  if (!c || !planes_in || !planes_out || !pt || !xsize || !ysize || xsize > (1u << 14) || ysize > (1u << 14)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (y_begin >= y_end || y_end > ysize || !pt->num_positions) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if ((alpha_in != nullptr) != (pt->uses_alpha != 0) || (alpha_in != nullptr) != (alpha_out != nullptr)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 4; k++)
+    if (pt->slot_planes[k] && (!pt->slot_w[k] || !pt->slot_h[k] || pt->slot_w[k] > (1u << 14) || pt->slot_h[k] > (1u << 14)))
+      return JXLHIP_ERR_INVALID_ARGUMENT;
+  // (a rectangle may reach past xsize, as on a VarDCT frame it may reach into the padding: the kernel clips its columns at
+  // xsize, which a test must be able to show; rows come from the row lists alone, and those are checked)
+  int r = upload::CheckPatches(*pt, ysize, 1u << 15, ysize);
+  if (r) return r;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((r = ApplyPendingWait(c))) return r;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const size_t n = size_t(xsize) * ysize;
+  DebugBufs d;
+  if ((r = d.Put(0, planes_in, n * 12)) || (r = d.Put(1, alpha_in, n * 4)) || (r = d.Put(2, pt->records, size_t(pt->num_positions) * 32)) ||
+      (r = d.Put(3, pt->row_start, (size_t(ysize) + 1) * 4)) || (r = d.Put(4, pt->row_list, size_t(pt->num_row_entries) * 4)))
+    return r;
+  jxlhip::PatchParams pp;
+  memset(&pp, 0, sizeof(pp));
+  for (int k = 0; k < 4; k++) {
+    if (!pt->slot_planes[k]) continue;
+    const size_t sn = size_t(pt->slot_w[k]) * pt->slot_h[k];
+    if ((r = d.Put(5 + k, pt->slot_planes[k], sn * 12))) return r;
+    if (alpha_in && (r = d.Put(9 + k, pt->slot_alpha[k], sn * 4))) return r;
+    pp.slot_planes[k] = d.b[5 + k].as<float>();
+    pp.slot_alpha[k] = d.b[9 + k].as<float>();
+    pp.slot_w[k] = pt->slot_w[k];
+    pp.slot_h[k] = pt->slot_h[k];
+  }
+  pp.planes = d.b[0].as<float>();
+  pp.alpha = d.b[1].as<float>();
+  pp.alpha_stride = xsize;
+  pp.premultiplied = pt->premultiplied ? 1 : 0;
+  pp.records = d.b[2].as<uint32_t>();
+  pp.row_start = d.b[3].as<uint32_t>();
+  pp.row_list = d.b[4].as<uint32_t>();
+  pp.stride = xsize;
+  pp.plane_stride = n;
+  pp.xsize = xsize;
+  pp.y_begin = y_begin;
+  pp.y_end = y_end;
+  hipLaunchKernelGGL(jxlhip::k_patches_add, dim3(y_end - y_begin), dim3(256), 0, c->stream, pp);
+  hipError_t e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(c->stream);  // (before the buffers go, whatever was enqueued)
+  if (e == hipSuccess) e = es;
+  if (e == hipSuccess) e = hipMemcpy(planes_out, d.b[0].p, n * 12, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && alpha_out) e = hipMemcpy(alpha_out, d.b[1].p, n * 4, hipMemcpyDeviceToHost);
+  return e == hipSuccess ? 0 : -int(e);
+}
+
+// Test entry: k_splines_add as the filter stage launches it, on a caller's dense planes and a draw cache from host memory,
+// checked like an upload's (upload::CheckSplines); segments the kernel's llroundf could not take are refused as well.
+int jxlhip_debug_splines(JxlHipContext* c, const float* planes_in, uint32_t xsize, uint32_t ysize, const JxlHipSplines* sp, uint32_t y_begin,
+                         uint32_t y_end, float* planes_out) {
+  if (!c || !planes_in || !planes_out || !sp || !xsize || !ysize || xsize > (1u << 14) || ysize > (1u << 14)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (y_begin >= y_end || y_end > ysize || !sp->num_segments) return JXLHIP_ERR_INVALID_ARGUMENT;
+  int r = upload::CheckSplines(*sp, ysize);
+  if (r) return r;
+  for (size_t i = 0; i < size_t(sp->num_segments) * 8; i++) {
+    const float v = sp->segments[i];
+    if (!std::isfinite(v) || ((i & 7) < 3 && std::fabs(v) > float(1 << 30))) return JXLHIP_ERR_INVALID_ARGUMENT;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  if ((r = ApplyPendingWait(c))) return r;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const size_t n = size_t(xsize) * ysize;
+  DebugBufs d;
+  if ((r = d.Put(0, planes_in, n * 12)) || (r = d.Put(1, sp->segments, size_t(sp->num_segments) * 32)) ||
+      (r = d.Put(2, sp->row_start, (size_t(ysize) + 1) * 4)) || (r = d.Put(3, sp->row_segments, size_t(sp->num_row_segments) * 4)))
+    return r;
+  jxlhip::SplineParams P;
+  memset(&P, 0, sizeof(P));
+  P.planes = d.b[0].as<float>();
+  P.segments = d.b[1].as<float>();
+  P.row_start = d.b[2].as<uint32_t>();
+  P.row_segments = d.b[3].as<uint32_t>();
+  P.stride = xsize;
+  P.plane_stride = n;
+  P.xsize = xsize;
+  P.y_begin = y_begin;
+  P.y_end = y_end;
+  hipLaunchKernelGGL(jxlhip::k_splines_add, dim3(y_end - y_begin), dim3(256), 0, c->stream, P);
+  hipError_t e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(c->stream);  // (before the buffers go, whatever was enqueued)
+  if (e == hipSuccess) e = es;
+  if (e == hipSuccess) e = hipMemcpy(planes_out, d.b[0].p, n * 12, hipMemcpyDeviceToHost);
+  return e == hipSuccess ? 0 : -int(e);
+}
+
 int jxlhip_canvas_download(JxlHipCanvas* v, uint32_t data_type, uint32_t num_channels, uint32_t bits, int big_endian, uint32_t orientation,
                            void* dst, size_t stride) {
   if (!v || !dst || num_channels < 1 || num_channels > 4 || orientation < 1 || orientation > 8) return JXLHIP_ERR_INVALID_ARGUMENT;

@@ -40,6 +40,9 @@ struct Decoded {
   std::vector<uint8_t> rgb8;   // interleaved, out_xsize*out_ysize*out_channels
   std::vector<float> rgbf;     // planar 3 x ysize x xsize (after transfer function, before uint8)
   std::vector<float> alphaf;   // the alpha plane as floats (images with alpha)
+  // the draw cache of the frame's splines as built (8 floats per segment; row lists; y_to_x, y_to_b, xsize, ysize used)
+  std::vector<float> spline_segments, spline_used;
+  std::vector<uint32_t> spline_row_start, spline_row_segments;
   std::vector<float> xyb_save; // frames kept before the colour transform: 3 x out_ysize x out_xsize (dec_cache.cc:225-230)
   // VarDCT intermediates
   std::vector<int32_t> coeffs;     // [group][c][65536], block-contiguous per varblock
@@ -612,6 +615,15 @@ static void PatchAlpha(FrameState* s, size_t xs, size_t ys) {
 
 // frame_index / nonvisible_index: the visible frames before this one and the invisible ones since (they seed the noise).
 // The frame is rendered at its own size; Decode() places it on the canvas (crop origin, blending with a reference slot).
+static void DumpSplineCache(const Splines& sp, size_t xs, size_t ys, float y_to_x, float y_to_b, Decoded* out) {
+  out->spline_segments.clear();
+  for (const SplineSegment& g : sp.segments)
+    out->spline_segments.insert(out->spline_segments.end(), {g.center_x, g.center_y, g.maximum_distance, g.inv_sigma,
+                                                             g.sigma_over_4_times_intensity, g.color[0], g.color[1], g.color[2]});
+  out->spline_row_start.assign(sp.segment_y_start.begin(), sp.segment_y_start.end());
+  out->spline_row_segments.assign(sp.segment_indices.begin(), sp.segment_indices.end());
+  out->spline_used = {y_to_x, y_to_b, float(xs), float(ys)};
+}
 static void DecodeFrame(BitReader& br, const ImageHeader& ih, Decoded* out, bool want_dumps, size_t frame_index = 0,
                         size_t nonvisible_index = 0, const XybSlot* xyb_slots = nullptr) {
   FrameState st;
@@ -817,6 +829,7 @@ static void DecodeFrame(BitReader& br, const ImageHeader& ih, Decoded* out, bool
     Planes3 splined;
     if (s->has_splines) {  // dec_cache.cc:198-201: after the filters, before upsampling and noise
       InitSplineDrawCache(&s->splines, d.xsize, d.ysize, s->base_corr_x, s->base_corr_b);  // dec_frame.cc:303-308
+      if (want_dumps) DumpSplineCache(s->splines, d.xsize, d.ysize, s->base_corr_x, s->base_corr_b, out);
       splined = *cur;
       DrawSplines(s->splines, splined.p[0].data(), splined.p[1].data(), splined.p[2].data(), splined.stride, d.xsize, d.ysize);
       cur = &splined;
@@ -910,6 +923,7 @@ static void DecodeFrame(BitReader& br, const ImageHeader& ih, Decoded* out, bool
     }
     if (s->has_splines) {  // the same stage on the three colour channels of a Modular frame (default colour correlation: 0, 1)
       InitSplineDrawCache(&s->splines, xs, ys, s->base_corr_x, s->base_corr_b);
+      if (want_dumps) DumpSplineCache(s->splines, xs, ys, s->base_corr_x, s->base_corr_b, out);
       DrawSplines(s->splines, out->rgbf.data(), out->rgbf.data() + xs * ys, out->rgbf.data() + 2 * xs * ys, xs, xs, ys);
     }
     if (fh.frame_type == 2 || fh.frame_type == 1 || fh.save_before_color_transform) out->xyb_save = out->rgbf;
@@ -1222,7 +1236,8 @@ void jxlo_animation(JxloHandle* h, uint32_t* a) {
   a[6] = d.fh.timecode;
 }
 // Named buffers: "rgb8","rgbf","coeffs","nzeros","xyb_idct","xyb_filtered","dc","acs","quant","sharpness","ytox",
-// "ytob","inv_sigma","quant_dc","modular". Returns pointer and byte size (0 if absent).
+// "ytob","inv_sigma","quant_dc","modular", ...; the draw cache of the splines: "spline_segments", "spline_row_start",
+// "spline_row_segments", "spline_used" (y_to_x, y_to_b, xsize, ysize). Returns pointer and byte size (0 if absent).
 const void* jxlo_buffer(JxloHandle* h, const char* name, size_t* nbytes) {
   jxlo::Decoded& d = h->d;
   std::string n(name);
@@ -1234,6 +1249,7 @@ const void* jxlo_buffer(JxloHandle* h, const char* name, size_t* nbytes) {
   JXLO_BUF(rgb8) JXLO_BUF(rgbf) JXLO_BUF(coeffs) JXLO_BUF(nzeros) JXLO_BUF(xyb_idct) JXLO_BUF(xyb_filtered) JXLO_BUF(dc)
   JXLO_BUF(acs) JXLO_BUF(quant) JXLO_BUF(sharpness) JXLO_BUF(ytox) JXLO_BUF(ytob) JXLO_BUF(inv_sigma) JXLO_BUF(quant_dc) JXLO_BUF(dc_unsmoothed)
   JXLO_BUF(modular) JXLO_BUF(alphaf) JXLO_BUF(ac_walk)
+  JXLO_BUF(spline_segments) JXLO_BUF(spline_used) JXLO_BUF(spline_row_start) JXLO_BUF(spline_row_segments)
 #undef JXLO_BUF
   *nbytes = 0;
   return nullptr;

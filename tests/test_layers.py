@@ -2,7 +2,9 @@
 reference slots, invisible layers, animations whose frames are deltas over the previous canvas (lib/jxl/blending.cc,
 alpha.cc, render_pipeline/stage_blending.cc, dec_cache.cc:268-290). CPU part: the oracle against the closed form of
 alpha-over and the host's placement fields; GPU part: the canvas kernels (jxlhip_canvas_*) behind the decoder API
-against the oracle."""
+against the oracle. The oracle's canvas loop and k_canvas_blend itself (every mode pair, any origin, empty and separate
+slots) are held to an independent reading of blending.cc / stage_blending.cc: tests/blending_np.py with
+tests/test_blending_np.py and tests/test_gpu_blending.py."""
 import numpy as np
 import pytest
 

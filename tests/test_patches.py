@@ -1,11 +1,15 @@
 """Patches (lib/jxl/dec_patch_dictionary.cc, render_pipeline/stage_patches.cc): a reference-only frame
 kept before its colour transform (what libjxl codes its patch atlas as: an XYB Modular frame), and a frame whose
 dictionary draws rectangles of it over the decoded XYB planes, before the splines. CPU part: the oracle's placement
-against the atlas decoded on its own, the host's parse; GPU part: k_patches_add behind the decoder API against the oracle."""
+against the atlas decoded on its own, the host's parse; GPU part: k_patches_add behind the decoder API against the oracle.
+The reading of PerformBlending the oracle is held to here lives in tests/blending_np.py; tests/test_blending_np.py holds
+the oracle to it on crafted samples as well, and tests/test_gpu_blending.py holds k_patches_add itself to it, sample for
+sample, on crafted planes and dictionaries."""
 import numpy as np
 import pytest
 
 import replay_util as R
+from blending_np import perform_blending as _blend_np  # (tests/test_oracle.py reaches it under this name too)
 
 
 def _case(J):
@@ -136,41 +140,6 @@ def _alpha_case(J):
             pos.append((4 + (k % 13) * 22, 3 + (k // 13) * 17, mode, (k >> 1) & 1, ec_mode, k & 1))
             k += 1
     return img, atlas, [dict(x0=4, y0=6, xsize=24, ysize=18, positions=pos)]
-
-
-def _blend_np(bg, bga, fg, fga, mode, clamp, ec_mode, ec_clamp, premultiplied):
-    """blending.cc:40-190 + alpha.cc:17-101 for an image whose one extra channel is alpha, read independently of the oracle's
-    restatement: float32 arithmetic, array-wise. bg / fg: [3][h][w]; returns the blended colour planes and alpha."""
-    f = np.float32
-    c01 = lambda v: np.clip(v, f(0), f(1))
-    one = f(1)
-    a = {0: bga, 1: fga, 2: bga + fga, 3: bga * (c01(fga) if ec_clamp else fga),
-         4: one - (one - (c01(fga) if ec_clamp else fga)) * (one - bga), 5: one - (one - (c01(bga) if ec_clamp else bga)) * (one - fga),
-         6: bga, 7: fga}[ec_mode]
-    if mode == 0:
-        out = bg
-    elif mode == 1:
-        out = fg
-    elif mode == 2:
-        out = bg + fg
-    elif mode == 3:
-        out = bg * (c01(fg) if clamp else fg)
-    elif mode in (4, 5):
-        bot, bota, top, topa = (bg, bga, fg, fga) if mode == 4 else (fg, fga, bg, bga)
-        ta = c01(topa) if clamp else topa
-        new_a = one - (one - ta) * (one - bota)
-        if premultiplied:
-            out = top + bot * (one - ta)
-        else:
-            with np.errstate(divide="ignore"):
-                r = np.where(new_a > 0, one / new_a, f(0)).astype(f)
-            out = (top * ta + bot * bota * (one - ta)) * r
-        a = new_a
-    elif mode == 6:
-        out = bg + fg * (c01(fga) if clamp else fga)
-    else:
-        out = fg + bg * (c01(bga) if clamp else bga)
-    return out.astype(f), a.astype(f)
 
 
 @pytest.mark.parametrize("premultiplied", [False, True])

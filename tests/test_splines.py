@@ -1,7 +1,9 @@
 """Splines (lib/jxl/splines.cc, render_pipeline/stage_splines.cc). The dictionary parse is checked on a
 stream libjxl itself made (tools/wasm_demo/jxl_decoder_test.js:25-31, written by jxl_from_tree: a 320x320 Modular frame
 whose only content is a spline), the rendering against the closed form of the splat, and the GPU path against the
-oracle on that stream and on streams of the synthetic writer (VarDCT and lossless)."""
+oracle on that stream and on streams of the synthetic writer (VarDCT and lossless). The oracle's spline code is the host's
+under another name: what holds both, and k_splines_add itself, to an independent reading of splines.cc is
+tests/splines_f64.py with tests/test_splines_f64.py (dictionary, draw cache, rendering) and tests/test_gpu_splines_f64.py."""
 import math
 import os
 
