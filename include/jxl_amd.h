@@ -140,6 +140,9 @@ void jxlamd_modframe_info(const JxlAmdModFrame* frame, uint32_t* info);
 int jxlamd_modframe_section(const JxlAmdModFrame* frame, uint32_t index, uint64_t* offset, uint32_t* size);
 /* Hands the plan to a context (jxlhip_modular_upload); then jxlhip_modular_run + jxlhip_download_pixels. */
 int jxlamd_modframe_upload(const JxlAmdModFrame* frame, JxlHipContext* ctx);
+/* Test aid: pushes the first rectangle of inverse-transform operation `op` of the parsed frame one column outside its
+ * buffer: a descriptor the upload's validation must refuse. Returns 0, or 1 when there is no such operation. */
+int jxlamd_modframe_debug_shift_op(JxlAmdModFrame* frame, uint32_t op);
 /* Channel buffer of extra channel `index` after the run (jxlhip_modular_download_buffer), or 0xFFFFFFFF. */
 uint32_t jxlamd_modframe_extra_buffer(const JxlAmdModFrame* frame, uint32_t index);
 /* Thread-local description of the last failure of a jxlamd_* call ("" if none). */

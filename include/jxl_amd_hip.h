@@ -488,10 +488,11 @@ typedef struct JxlHipModOp {  /* one inverse-transform step */
    * buffers); all local operations of a set of frames run before any other, those of one `level` and kind in ONE launch,
    * so operations that share a level must not touch overlapping samples. local = 0: the frame's own transforms, one
    * level per list entry, after the deepest local level.
-   * jxlhip_modular_upload checks that every rectangle lies inside its buffer and that an unsqueeze output is not one of its
-   * inputs, so no operation reads or writes outside the pool. It does NOT check the schedule: that operations sharing a
-   * level are disjoint, or that palette outputs 1.. do not alias the index rectangle. A description that breaks this
-   * decodes to wrong samples (a race), not to an error. */
+   * What jxlhip_modular_upload checks is stated rule by rule in enum ModRule (libjxl_amd/csrc/host/jxh_modular_upload_plan.h:
+   * kModRuleOpFields .. kModRuleUnsqueezeAlias for operations): every rectangle lies inside its buffer and an unsqueeze
+   * output is not one of its inputs, so no operation reads or writes outside the pool. It does NOT check the schedule: that
+   * operations sharing a level are disjoint, or that palette outputs 1.. do not alias the index rectangle. A description
+   * that breaks this decodes to wrong samples (a race), not to an error. */
   uint32_t level, local;
 } JxlHipModOp;
 typedef struct JxlHipModFrameDesc {
@@ -533,7 +534,8 @@ typedef struct JxlHipModFrameDesc {
   int32_t linear_output;
   const struct JxlHipColorTarget* color_target; /* as JxlHipFrameDesc::color_target (XYB frames only) */
 } JxlHipModFrameDesc;
-/* Copies a Modular frame's tables and sections to the device (the arrays may be released afterwards). */
+/* Copies a Modular frame's tables and sections to the device (the arrays may be released afterwards). A descriptor that
+ * breaks a rule of enum ModRule is refused before any device call: the context keeps its tables but has no frame to run. */
 int jxlhip_modular_upload(JxlHipContext* ctx, const JxlHipModFrameDesc* desc);
 /* Decodes every stream (one lane each), undoes the transforms and writes the pixels in the format of
  * jxlhip_set_output_format; results through jxlhip_download_pixels / jxlhip_download_rgb8. Stage time: which = 0. */

@@ -690,6 +690,11 @@ int jxlamd_modframe_section(const JxlAmdModFrame* f, uint32_t index, uint64_t* o
 uint32_t jxlamd_modframe_extra_buffer(const JxlAmdModFrame* f, uint32_t index) {
   return f && index < f->plan.extra_buffer.size() ? f->plan.extra_buffer[index] : 0xFFFFFFFFu;
 }
+int jxlamd_modframe_debug_shift_op(JxlAmdModFrame* f, uint32_t op) {
+  if (!f || op >= f->plan.ops.size() || !f->plan.ops[op].w) return 1;
+  f->plan.ops[op].ox[0] = f->plan.buffers[f->plan.ops[op].buf[0]].first - f->plan.ops[op].w + 1;
+  return 0;
+}
 int jxlamd_modframe_upload(const JxlAmdModFrame* f, JxlHipContext* ctx) {
   g_last_error.clear();
   if (!f || !ctx) {

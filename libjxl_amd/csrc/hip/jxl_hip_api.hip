@@ -19,6 +19,7 @@
 #include "../../../include/jxl_amd_hip.h"
 #include "../host/jxh_enc_shared.h"
 #include "../host/jxh_launch_order.h"
+#include "../host/jxh_modular_upload_plan.h"
 #include "../host/jxh_upload_plan.h"
 #include "jxl_hip_kernels.h"
 #include "jxl_hip_entropy_lanes.h"
@@ -146,12 +147,7 @@ struct PassBufs {
   Buf ctx_map, alias, cfg, orders, ptable, poffset, alias_packed;
 };
 
-// One launch of the Modular transform / output kernels over the frames of a set (ModularBuildOps).
-struct ModLaunch {
-  uint32_t kind;  // 0 RCT, 1 palette, 2 unsqueeze, 3 output, 4 / 5 / 6 float planes, splines, patches
-  size_t offset;  // of the first parameter block in the blob
-  uint32_t count, gx, gy;
-};
+using ModLaunch = upload::ModLaunch;  // one launch of the Modular transform / output kernels over the frames of a set
 
 // Pinned host staging block of a context: every table of a frame is assembled in it and leaves through asynchronous
 // copies on the context's stream, so that an upload neither blocks on pageable-memory copies nor synchronises per table.
@@ -812,26 +808,6 @@ static void AdoptPatches(JxlHipContext* c, const JxlHipPatches& pt) {
     c->pat_src_h[i] = pt.slot_h[i];
   }
 }
-// The draw cache of a Modular frame's splines / its patch dictionary to the device, checked like a VarDCT frame's.
-static int UploadSplines(JxlHipContext* c, const JxlHipSplines& sp, uint32_t ysize) {
-  c->spl_segments = 0;
-  int r = upload::CheckSplines(sp, ysize);
-  if (r) return r;
-  PlainUploader up{c};
-  upload::VisitSplineTables(*c, sp, ysize, up);
-  if (!up.r) AdoptSplines(c, sp);
-  return up.r;
-}
-static int UploadPatches(JxlHipContext* c, const JxlHipPatches& pt, uint32_t ysize, uint32_t xlimit, uint32_t ylimit) {
-  AdoptPatches(c, JxlHipPatches{});
-  int r = upload::CheckPatches(pt, ysize, xlimit, ylimit);
-  if (r) return r;
-  PlainUploader up{c};
-  upload::VisitPatchTables(*c, pt, ysize, up);
-  if (!up.r) AdoptPatches(c, pt);
-  return up.r;
-}
-
 // -------------------------------------------------------------------------------------------------- frame upload
 static upload::UploadOptions OptionsOf(const JxlHipContext* c) {
   upload::UploadOptions o;
@@ -2103,483 +2079,257 @@ extern "C" int jxlhip_run_entropy(JxlHipContext* c) {
 
 
 // ------------------------------------------------------------------------------------------------ Modular frames
-extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc* d) {
-  if (!c || !d || !d->xsize || !d->ysize || !d->num_sections || !d->num_trees || !d->num_codes || d->num_trees != d->num_codes)
-    return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (d->num_color != 1 && d->num_color != 3) return JXLHIP_ERR_INVALID_ARGUMENT;
-  HIP_TRY(hipSetDevice(c->device));
-  {
-    int pw = ApplyPendingWait(c);
-    if (pw) return pw;
-    if ((pw = StageReset(c))) return pw;
-  }
+// What the context remembers of a Modular frame beside its tables.
+static void AdoptModFrame(JxlHipContext* c, const JxlHipModFrameDesc& d, const upload::ModPlan& P) {
   JxlHipContext::Modular& M = c->mod;
-  M.have = false;
-  c->have_frame = false;
-  int r;
-  // ---- channel pool
-  M.buf_off.assign(d->num_buffers, 0);
-  M.buf_w.assign(d->num_buffers, 0);
-  M.buf_h.assign(d->num_buffers, 0);
-  size_t pool = 0;
-  for (uint32_t i = 0; i < d->num_buffers; i++) {
-    M.buf_off[i] = pool;
-    M.buf_w[i] = d->buffers[i].w;
-    M.buf_h[i] = d->buffers[i].h;
-    pool += (size_t(d->buffers[i].w) * d->buffers[i].h + 3) & ~size_t(3);
+  M.buf_off = P.buf_off;
+  M.buf_w.resize(d.num_buffers);
+  M.buf_h.resize(d.num_buffers);
+  for (uint32_t i = 0; i < d.num_buffers; i++) {
+    M.buf_w[i] = d.buffers[i].w;
+    M.buf_h[i] = d.buffers[i].h;
   }
-  if ((r = M.pool.Ensure((pool + 4) * 4))) return r;
-  // (a channel buffer that no stream covers must read as zeros, not as the previous frame's samples)
-  HIP_TRY(hipMemsetAsync(M.pool.p, 0, (pool + 4) * 4, c->stream));
-  // ---- sections, 4-byte aligned, zero padded
-  std::vector<size_t> sec_off(d->num_sections);
-  size_t total = 0;
-  for (uint32_t i = 0; i < d->num_sections; i++) {
-    sec_off[i] = total;
-    total += (size_t(d->section_size[i]) + 3 + 8) & ~size_t(3);
-  }
-  std::vector<uint8_t> packed(total + 16, 0);
-  for (uint32_t i = 0; i < d->num_sections; i++) memcpy(packed.data() + sec_off[i], d->codestream + d->section_offset[i], d->section_size[i]);
-  if ((r = Upload(c, M.sections, packed.data(), packed.size()))) return r;
-  // ---- trees and codes: one blob, device pointers patched in
-  std::vector<uint8_t> blob;
-  auto put = [&](const void* src, size_t bytes) {
-    const size_t at = (blob.size() + 15) & ~size_t(15);
-    blob.resize(at + bytes);
-    if (bytes) memcpy(blob.data() + at, src, bytes);
-    return at;
-  };
-  std::vector<size_t> tree_at(d->num_trees), code_at(d->num_codes);
-  std::vector<std::vector<size_t>> code_parts(d->num_codes);  // ctx_map, alias, cfg, prefix_table, prefix_offset
-  for (uint32_t i = 0; i < d->num_trees; i++) {
-    // the kernel's 16-byte nodes: leaves carry -1 - predictor, the offset, the histogram their context maps to, the multiplier
-    std::vector<jxlhip::ModTreeNode> packed_tree(d->tree_size[i]);
-    for (uint32_t k = 0; k < d->tree_size[i]; k++) {  // every index the walk can follow must exist
-      const JxlHipModTreeNode& nd = d->trees[i][k];
-      if (nd.property >= int32_t(jxlhip::kModMaxProps)) return JXLHIP_ERR_UNSUPPORTED;
-      // children behind their parent (the breadth-first order dec_ma.cc:107-159 produces): a back edge would make the
-      // kernel's tree walk spin forever
-      if (nd.property >= 0 && (nd.lchild >= d->tree_size[i] || nd.rchild >= d->tree_size[i] || nd.lchild <= k || nd.rchild <= k))
-        return JXLHIP_ERR_INVALID_ARGUMENT;
-      if (nd.property < 0 && (nd.predictor > 13 || nd.lchild >= d->codes[i].ctx_map_size || !d->codes[i].ctx_map)) return JXLHIP_ERR_INVALID_ARGUMENT;
-      jxlhip::ModTreeNode& o = packed_tree[k];
-      if (nd.property >= 0) {
-        o.property = nd.property;
-        o.splitval = nd.splitval;
-        o.lchild = nd.lchild;
-        o.rchild = nd.rchild;
-      } else {
-        o.property = -1 - int32_t(nd.predictor);
-        o.splitval = nd.offset;
-        o.lchild = d->codes[i].ctx_map[nd.lchild];
-        o.rchild = nd.multiplier;
-      }
-    }
-    tree_at[i] = put(packed_tree.data(), packed_tree.size() * sizeof(jxlhip::ModTreeNode));
-  }
-  for (uint32_t i = 0; i < d->num_codes; i++) {
-    const JxlHipModCode& k = d->codes[i];
-    if (!d->tree_size[i]) {  // (an absent global tree)
-      code_parts[i] = {0, 0, 0, 0, 0};
-      continue;
-    }
-    if (!k.num_clusters || k.num_clusters > 256 || !k.ctx_map_size) return JXLHIP_ERR_INVALID_ARGUMENT;
-    for (uint32_t j = 0; j < k.ctx_map_size; j++)
-      if (k.ctx_map[j] >= k.num_clusters) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (!k.use_prefix && (k.log_alpha < 5 || k.log_alpha > 8)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (k.use_prefix)
-      for (uint32_t j = 0; j < k.num_clusters; j++) {
-        if (!upload::ValidPrefixTables(k.prefix_offset[j], k.prefix_table, k.prefix_table_size)) return JXLHIP_ERR_INVALID_ARGUMENT;
-      }
-    if (k.lz77 && (k.lz_dist_ctx >= k.num_clusters || !k.lz_min_length)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    code_parts[i] = {put(k.ctx_map, k.ctx_map_size), put(k.alias, k.use_prefix ? 0 : (size_t(k.num_clusters) << k.log_alpha) * 8),
-                     put(k.uint_cfg, size_t(k.num_clusters) * 4), put(k.prefix_table, k.use_prefix ? size_t(k.prefix_table_size) * 4 : 0),
-                     put(k.prefix_offset, k.use_prefix ? size_t(k.num_clusters) * 4 : 0)};
-  }
-  const size_t codes_at = (blob.size() + 15) & ~size_t(15);
-  blob.resize(codes_at + size_t(d->num_codes) * sizeof(jxlhip::ModCode));
-  if ((r = M.blob.Ensure(blob.size() + 16))) return r;
-  uint8_t* dev = M.blob.as<uint8_t>();
-  M.code_table_words.assign(d->num_codes, 0);
-  for (uint32_t i = 0; i < d->num_codes; i++) {
-    const JxlHipModCode& k = d->codes[i];
-    jxlhip::ModCode mc;
-    memset(&mc, 0, sizeof(mc));
-    mc.ctx_map = dev + code_parts[i][0];
-    mc.alias = reinterpret_cast<const uint2*>(dev + code_parts[i][1]);
-    mc.cfg = reinterpret_cast<const uint32_t*>(dev + code_parts[i][2]);
-    mc.prefix_table = reinterpret_cast<const uint32_t*>(dev + code_parts[i][3]);
-    mc.prefix_offset = reinterpret_cast<const uint32_t*>(dev + code_parts[i][4]);
-    mc.log_alpha = k.log_alpha;
-    mc.use_prefix = k.use_prefix;
-    mc.lz77 = k.lz77;
-    mc.lz_min_symbol = k.lz_min_symbol;
-    mc.lz_min_length = k.lz_min_length;
-    mc.lz_len_cfg = k.lz_len_cfg;
-    mc.lz_dist_ctx = k.lz_dist_ctx;
-    mc.num_clusters = k.num_clusters;
-    if (d->tree_size[i])
-      mc.table_words = k.use_prefix ? k.prefix_table_size + 2 * k.num_clusters : ((k.num_clusters << k.log_alpha) * 2 + k.num_clusters);
-    M.code_table_words[i] = mc.table_words;
-    memcpy(blob.data() + codes_at + size_t(i) * sizeof(mc), &mc, sizeof(mc));
-  }
-  HIP_TRY(hipMemcpyAsync(M.blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
-  // ---- rectangles and streams
-  std::vector<jxlhip::ModChannel> rects(d->num_rects ? d->num_rects : 1);
-  for (uint32_t i = 0; i < d->num_rects; i++) {
-    const JxlHipModRect& q = d->rects[i];
-    if (q.buffer >= d->num_buffers || uint64_t(q.x0) + q.w > M.buf_w[q.buffer] || uint64_t(q.y0) + q.h > M.buf_h[q.buffer])
-      return JXLHIP_ERR_INVALID_ARGUMENT;
-    rects[i].data = M.pool.as<int32_t>() + M.buf_off[q.buffer] + size_t(q.y0) * M.buf_w[q.buffer] + q.x0;
-    rects[i].stride = M.buf_w[q.buffer];
-    rects[i].w = q.w;
-    rects[i].h = q.h;
-    rects[i].sig = q.sig;
-  }
-  if ((r = Upload(c, M.rects, rects.data(), rects.size() * sizeof(rects[0])))) return r;
-  M.nstreams = d->num_streams;
-  if ((r = M.status.Ensure(size_t(d->num_streams + 1) * 4))) return r;
-  if ((r = M.end_bits.Ensure(size_t(d->num_streams + 1) * 4))) return r;
-  size_t scratch_ints = 0, window_words = 0;
-  std::vector<size_t> scratch_at(d->num_streams, 0), window_at(d->num_streams, 0);
-  std::vector<uint32_t> window_mask(d->num_streams, 0);
-  for (uint32_t i = 0; i < d->num_streams; i++) {
-    const JxlHipModStream& q = d->streams[i];
-    if (q.section >= d->num_sections || q.tree >= d->num_trees || q.code >= d->num_codes || !d->tree_size[q.tree] ||
-        uint64_t(q.first_rect) + q.num_rects > d->num_rects || q.bit_offset > uint64_t(d->section_size[q.section]) * 8 ||
-        q.num_props < 16 || q.num_props > uint32_t(jxlhip::kModMaxProps))
-      return JXLHIP_ERR_INVALID_ARGUMENT;
-    if (q.uses_wp) {
-      scratch_at[i] = scratch_ints;
-      scratch_ints += size_t(q.max_width + 2) * 2 * jxlhip::kModWpEntry;
-    }
-    if (d->codes[q.code].lz77) {
-      uint32_t w = 256;
-      while (w < q.num_samples && w < (1u << 20)) w <<= 1;  // as large as the stream can fill, at most the format's 2^20
-      window_at[i] = window_words;
-      window_mask[i] = w - 1;
-      window_words += w;
-    }
-  }
-  if ((r = M.scratch.Ensure((scratch_ints + 4) * 4))) return r;
-  if ((r = M.windows.Ensure((window_words + 4) * 4))) return r;
-  M.streams_host.assign(d->num_streams, jxlhip::ModStream());
-  M.stream_samples.assign(d->num_streams, 0);
-  for (uint32_t i = 0; i < d->num_streams; i++) {
-    const JxlHipModStream& q = d->streams[i];
-    jxlhip::ModStream& o = M.streams_host[i];
-    memset(&o, 0, sizeof(o));
-    o.words = reinterpret_cast<const uint32_t*>(M.sections.as<uint8_t>() + sec_off[q.section]);
-    o.bit_offset = q.bit_offset;
-    o.size_bytes = d->section_size[q.section];
-    o.tree = reinterpret_cast<const jxlhip::ModTreeNode*>(dev + tree_at[q.tree]);
-    o.tree_nodes = d->tree_size[q.tree];
-    o.code = reinterpret_cast<const jxlhip::ModCode*>(dev + codes_at) + q.code;
-    o.channels = M.rects.as<jxlhip::ModChannel>() + q.first_rect;
-    o.num_channels = q.num_rects;
-    o.stream_id = q.stream_id;
-    o.first_channel_index = q.first_channel_index;
-    memcpy(o.wp, q.wp, sizeof(o.wp));
-    o.uses_wp = q.uses_wp;
-    o.num_props = q.num_props;
-    o.dist_multiplier = q.dist_multiplier;
-    o.wp_scratch = q.uses_wp ? M.scratch.as<int32_t>() + scratch_at[i] : nullptr;
-    o.lz_window = d->codes[q.code].lz77 ? M.windows.as<uint32_t>() + window_at[i] : nullptr;
-    o.lz_window_mask = window_mask[i];
-    o.status = M.status.as<uint32_t>() + i;
-    o.end_bit = M.end_bits.as<uint32_t>() + i;
-    M.stream_samples[i] = q.num_samples;
-  }
-  if ((r = Upload(c, M.streams, M.streams_host.data(), M.streams_host.size() * sizeof(jxlhip::ModStream)))) return r;
-  // ---- operations and output
-  M.ops.assign(d->ops, d->ops + d->num_ops);
-  for (const JxlHipModOp& op : M.ops) {
-    const uint32_t nbuf = op.kind == 0 ? 3 : (op.kind == 1 ? 2 + op.nb : 3);
-    if (op.kind > 3 || nbuf > 6 || op.local > 1 || op.level >= d->num_ops) return JXLHIP_ERR_INVALID_ARGUMENT;
-    for (uint32_t j = 0; j < nbuf; j++)
-      if (op.buf[j] >= d->num_buffers) return JXLHIP_ERR_INVALID_ARGUMENT;
-    // the w x h rectangle of buffer j at that buffer's origin lies inside it
-    auto inside = [&](uint32_t j, uint32_t w, uint32_t h) {
-      return uint64_t(op.ox[j]) + w <= M.buf_w[op.buf[j]] && uint64_t(op.oy[j]) + h <= M.buf_h[op.buf[j]];
-    };
-    if (op.kind == 0) {
-      for (uint32_t j = 0; j < 3; j++)
-        if (!inside(j, op.w, op.h)) return JXLHIP_ERR_INVALID_ARGUMENT;
-      if (op.param >= 42) return JXLHIP_ERR_INVALID_ARGUMENT;
-    } else if (op.kind == 1) {  // the palette is a whole buffer; index and outputs are rectangles
-      if (op.nb < 1 || op.nb > 4 || M.buf_h[op.buf[0]] < op.nb || op.param != M.buf_w[op.buf[0]] || op.ox[0] || op.oy[0])
-        return JXLHIP_ERR_INVALID_ARGUMENT;
-      for (uint32_t j = 1; j < 2 + op.nb; j++)
-        if (!inside(j, op.w, op.h)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    } else {  // averages and residuals follow from the output's size: they add up by construction, each must lie in its buffer
-      const bool hz = op.kind == 2;
-      const uint32_t n = hz ? op.w : op.h, na = n - n / 2, nr = n / 2;
-      if (!inside(0, hz ? na : op.w, hz ? op.h : na) || !inside(1, hz ? nr : op.w, hz ? op.h : nr) || !inside(2, op.w, op.h))
-        return JXLHIP_ERR_INVALID_ARGUMENT;
-      if (op.buf[2] == op.buf[0] || op.buf[2] == op.buf[1]) return JXLHIP_ERR_INVALID_ARGUMENT;  // (a line is read while it is written)
-    }
-  }
-  for (uint32_t j = 0; j < d->num_color + (d->has_alpha ? 1 : 0); j++) {
-    if (d->out_buffer[j] >= d->num_buffers || M.buf_w[d->out_buffer[j]] != d->xsize || M.buf_h[d->out_buffer[j]] != d->ysize)
-      return JXLHIP_ERR_INVALID_ARGUMENT;
-    M.out_buffer[j] = d->out_buffer[j];
-  }
-  M.num_color = d->num_color;
-  M.has_alpha = d->has_alpha;
-  M.bits = d->bits;
-  M.alpha_bits = d->alpha_bits;
-  {  // sample depths: low byte = bits, bits 8..15 = exponent bits of a float type (image_metadata.cc BitDepth: 2..8, mantissa 2..23)
-    auto depth_ok = [](uint32_t d) {
-      const uint32_t bits = d & 0xFF, e = (d >> 8) & 0xFF;
-      if (d >> 16) return false;
-      if (e == 0) return bits >= 1 && bits <= 31;
-      return e >= 2 && e <= 8 && bits >= e + 3 && bits <= e + 24 && bits <= 32;
-    };
-    if (!depth_ok(M.bits) || !depth_ok(M.alpha_bits) || (M.alpha_bits >> 8) || (M.alpha_bits & 0xFF) > 24) return JXLHIP_ERR_INVALID_ARGUMENT;
-  }
-  M.xs = d->xsize;
-  M.ys = d->ysize;
-  c->oxs = c->xs = d->xsize;
-  c->oys = c->ys = d->ysize;
-  if ((r = c->rgb.Ensure(size_t(c->oxs) * c->oys * OutPixelBytes(c)))) return r;
-  HIP_TRY(hipStreamSynchronize(c->stream));  // the staging vectors are locals
-  if (d->splines.num_segments && d->num_color != 3) return JXLHIP_ERR_UNSUPPORTED;
-  M.xyb = d->xyb != 0;
+  M.code_table_words = P.table_words;
+  M.nstreams = d.num_streams;
+  M.stream_samples.resize(d.num_streams);
+  for (uint32_t i = 0; i < d.num_streams; i++) M.stream_samples[i] = d.streams[i].num_samples;
+  M.ops.assign(d.ops, d.ops + d.num_ops);
+  for (uint32_t j = 0; j < d.num_color + (d.has_alpha ? 1 : 0); j++) M.out_buffer[j] = d.out_buffer[j];
+  M.num_color = d.num_color;
+  M.has_alpha = d.has_alpha;
+  M.bits = d.bits;
+  M.alpha_bits = d.alpha_bits;
+  M.xs = d.xsize;
+  M.ys = d.ysize;
+  c->oxs = c->xs = d.xsize;
+  c->oys = c->ys = d.ysize;
+  M.xyb = d.xyb != 0;
   if (M.xyb) {
-    if (d->num_color != 3) return JXLHIP_ERR_UNSUPPORTED;
     memset(&M.xyb_color, 0, sizeof(M.xyb_color));
     for (int ch = 0; ch < 3; ch++) {
-      M.xyb_factor[ch] = d->xyb_factor[ch];
-      M.xyb_color.opsin_bias[ch] = d->opsin_bias[ch];
-      M.xyb_color.opsin_bias_cbrt[ch] = cbrtf(d->opsin_bias[ch]);
+      M.xyb_factor[ch] = d.xyb_factor[ch];
+      M.xyb_color.opsin_bias[ch] = d.opsin_bias[ch];
+      M.xyb_color.opsin_bias_cbrt[ch] = cbrtf(d.opsin_bias[ch]);
     }
-    memcpy(M.xyb_color.opsin_inv, d->opsin_inv, sizeof(M.xyb_color.opsin_inv));
-    M.xyb_color.linear_output = d->linear_output;
+    memcpy(M.xyb_color.opsin_inv, d.opsin_inv, sizeof(M.xyb_color.opsin_inv));
+    M.xyb_color.linear_output = d.linear_output;
   }
-  M.xyb_target = d->color_target ? *d->color_target : JxlHipColorTarget{};
-  if (M.xyb_target.tf > JXLHIP_TF_GAMMA || M.xyb_target.tone > JXLHIP_TONE_HLG_OOTF) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (M.xyb_target.tf && (!M.xyb || d->linear_output != 1)) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if ((r = UploadSplines(c, d->splines, d->ysize))) return r;
-  if (d->patches.num_positions && d->patches.uses_alpha) return JXLHIP_ERR_UNSUPPORTED;  // (the frame's alpha is an integer channel here)
-  if ((r = UploadPatches(c, d->patches, d->ysize, d->xsize, d->ysize))) return r;
-  const bool float_planes = c->spl_segments || c->keep_xyb || c->pat_positions;
-  if (float_planes && d->num_color != 3) return JXLHIP_ERR_UNSUPPORTED;
-  if (float_planes && (r = c->spl_planes.Ensure(size_t(d->xsize) * d->ysize * 3 * 4))) return r;
-  M.have = true;
-  M.batch_ctxs.clear();
+  M.xyb_target = d.color_target ? *d.color_target : JxlHipColorTarget{};
+  AdoptSplines(c, d.splines);
+  AdoptPatches(c, d.patches);
+}
+
+// The buffers of a Modular frame: those its tables go to and those the kernels write (launch functions never allocate).
+// The order of the first allocations decides the buffers' addresses: with `streams` in front of `status` the lossless
+// benchmark ran 0.6 % slower on identical kernels (profiles/modular_upload_compare.txt).
+static int EnsureModBuffers(JxlHipContext* c, const JxlHipModFrameDesc& d, const upload::ModPlan& P) {
+  JxlHipContext::Modular& M = c->mod;
+  int r;
+  if ((r = M.pool.Ensure((P.pool_ints + 4) * 4))) return r;
+  // (a channel buffer that no stream covers must read as zeros, not as the previous frame's samples)
+  HIP_TRY(hipMemsetAsync(M.pool.p, 0, (P.pool_ints + 4) * 4, c->stream));
+  if ((r = M.sections.Ensure(P.section_bytes))) return r;
+  if ((r = M.blob.Ensure(P.blob_bytes + 16))) return r;
+  if ((r = M.rects.Ensure(upload::ModChannelEntries(d) * sizeof(jxlhip::ModChannel)))) return r;
+  if ((r = M.status.Ensure((size_t(d.num_streams) + 1) * 4))) return r;
+  if ((r = M.end_bits.Ensure((size_t(d.num_streams) + 1) * 4))) return r;
+  if ((r = M.scratch.Ensure((P.scratch_ints + 4) * 4))) return r;
+  if ((r = M.windows.Ensure((P.window_words + 4) * 4))) return r;
+  if ((r = M.streams.Ensure(std::max<size_t>(16, size_t(d.num_streams) * sizeof(jxlhip::ModStream))))) return r;
+  if ((r = c->rgb.Ensure(size_t(c->oxs) * c->oys * OutPixelBytes(c)))) return r;
+  if (P.float_planes && (r = c->spl_planes.Ensure(size_t(d.xsize) * d.ysize * 3 * 4))) return r;
+  return 0;
+}
+
+// Every table of the frame, built in the staging block with the device addresses it will hold, and sent from there on
+// the context's stream. The stream descriptors also stay on the host: jxlhip_modular_run_batch sorts those of a set.
+static int SendModTables(JxlHipContext* c, const JxlHipModFrameDesc& d, const upload::ModPlan& P) {
+  JxlHipContext::Modular& M = c->mod;
+  auto send = [c](Buf& dst, size_t bytes, auto&& fill) -> int {
+    void* st = nullptr;
+    const int r = StageAlloc(c, bytes, &st);
+    if (r || !bytes) return r;
+    fill(st);
+    HIP_TRY(hipMemcpyAsync(dst.p, st, bytes, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  };
+  upload::ModBases b;
+  b.pool = uintptr_t(M.pool.p);
+  b.sections = uintptr_t(M.sections.p);
+  b.blob = uintptr_t(M.blob.p);
+  b.rects = uintptr_t(M.rects.p);
+  b.scratch = uintptr_t(M.scratch.p);
+  b.windows = uintptr_t(M.windows.p);
+  b.status = uintptr_t(M.status.p);
+  b.end_bits = uintptr_t(M.end_bits.p);
+  int r;
+  if ((r = send(M.sections, P.section_bytes, [&](void* p) { upload::PackModSections(d, P, static_cast<uint8_t*>(p)); }))) return r;
+  if ((r = send(M.blob, P.blob_bytes, [&](void* p) { upload::BuildModBlob(d, P, static_cast<uint8_t*>(p), b.blob); }))) return r;
+  if ((r = send(M.rects, upload::ModChannelEntries(d) * sizeof(jxlhip::ModChannel),
+                [&](void* p) { upload::BuildModChannels(d, P, static_cast<jxlhip::ModChannel*>(p), b.pool); })))
+    return r;
+  if ((r = send(M.streams, size_t(d.num_streams) * sizeof(jxlhip::ModStream), [&](void* p) {
+         jxlhip::ModStream* s = static_cast<jxlhip::ModStream*>(p);
+         upload::BuildModStreams(d, P, s, b);
+         M.streams_host.assign(s, s + d.num_streams);
+       })))
+    return r;
+  if (!d.num_streams) M.streams_host.clear();
+  PlainUploader up{c};
+  upload::VisitSplineTables(*c, d.splines, d.ysize, up);
+  upload::VisitPatchTables(*c, d.patches, d.ysize, up);
+  return up.r;
+}
+
+extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc* d) {
+  if (!c || !d) return JXLHIP_ERR_INVALID_ARGUMENT;
+  // 1. whether the descriptor is taken: decided on the host alone (upload::ModRule), so that a refused one costs no
+  // device call and leaves the context's tables as they were (but no frame to run: the caller meant to replace it)
+  upload::ModUploadOptions opt;
+  opt.keep_xyb = c->keep_xyb;
+  int r = upload::CheckModFrameDesc(*d, opt);
+  c->mod.have = false;
+  c->have_frame = false;
+  if (r) return r;
+  const upload::ModPlan P = upload::MakeModPlan(*d, opt);
+  // 2. the tables are overwritten on the context's stream, behind whatever still reads the old ones
+  HIP_TRY(hipSetDevice(c->device));
+  if ((r = ApplyPendingWait(c))) return r;
+  if ((r = StageReset(c))) return r;
+  // 3. - 5. what the context remembers, the buffers, then the tables, which hold the buffers' addresses
+  AdoptModFrame(c, *d, P);
+  if ((r = EnsureModBuffers(c, *d, P))) return r;
+  if ((r = SendModTables(c, *d, P))) return r;
+  // The tables are resident and the descriptor's arrays free when the call returns, as for a VarDCT frame: batch launches
+  // over this context run on other contexts' streams, and copies left in flight slow later kernels (jxlhip_frame_upload).
+  HIP_TRY(hipEventRecord(c->stage.done, c->stream));
+  c->stage.recorded = true;
+  HIP_TRY(WaitEvent(c->stage.done));
+  c->mod.have = true;
+  c->mod.batch_ctxs.clear();
   c->generation++;
   return 0;
 }
 
-// The inverse transforms and the pixel writer of a set of frames, as launches over parameter-block arrays. First the
-// local phase: the operations that undo the transforms of single group streams. They are group-sized, those of different
-// groups touch disjoint rectangles and private buffers, and inside a group `level` orders them; so ALL operations of one
-// level and kind, of every group of every frame, are one launch (a frame with an RCT in each of its 135 groups: one RCT
-// launch). Then the frames' own transforms on whole channels, level k of every frame that has one in one launch per kind.
-// The two never share a launch: its grid is sized for its largest block, and one 4K channel beside thousands of group
-// blocks would start mostly empty workgroups. Built once per set (cached with the stream list), blocks in `blob` (host),
-// launches in `launches`.
+// The parameter blocks of the passes behind the inverse transforms, one fill function per pass (false: the frame does not
+// take the pass); they live with the kernels' structs. Frames with patches / splines / kept XYB planes: colour samples to
+// float planes (kind 4), the patches (kind 6), then the splines (kind 5) over them (dec_cache.cc:193-201), then the output
+// (kind 3) reads them.
+static bool ModFloatPlanes(const JxlHipContext* c) { return c->spl_segments || c->keep_xyb || c->pat_positions; }
+static bool FillModPlanes(const JxlHipContext* c, jxlhip::ModOutput* o) {
+  if (!ModFloatPlanes(c)) return false;
+  const JxlHipContext::Modular& M = c->mod;
+  for (uint32_t j = 0; j < 3; j++) {
+    o->ch[j] = M.pool.as<int32_t>() + M.buf_off[M.out_buffer[j]];
+    o->stride[j] = M.xs;
+  }
+  o->num_color = 3;
+  o->bits = M.bits;
+  o->w = M.xs;
+  o->h = M.ys;
+  o->fplanes = c->spl_planes.as<float>();
+  o->fmode = 1;
+  o->xyb = M.xyb ? 1 : 0;  // (the planes then hold XYB; the final pass converts what it reads back)
+  memcpy(o->xyb_factor, M.xyb_factor, sizeof(o->xyb_factor));
+  return true;
+}
+static bool FillModPatches(const JxlHipContext* c, jxlhip::PatchParams* pp) {
+  if (!c->pat_positions) return false;
+  const JxlHipContext::Modular& M = c->mod;
+  pp->planes = c->spl_planes.as<float>();
+  pp->records = c->pat_rec.as<uint32_t>();
+  pp->row_start = c->pat_row_start.as<uint32_t>();
+  pp->row_list = c->pat_row_list.as<uint32_t>();
+  for (int k = 0; k < 4; k++) {
+    pp->slot_planes[k] = c->pat_src[k];
+    pp->slot_w[k] = c->pat_src_w[k];
+    pp->slot_h[k] = c->pat_src_h[k];
+  }
+  pp->stride = M.xs;
+  pp->plane_stride = size_t(M.xs) * M.ys;
+  pp->xsize = M.xs;
+  pp->y_begin = 0;
+  pp->y_end = M.ys;
+  return true;
+}
+static bool FillModSplines(const JxlHipContext* c, jxlhip::SplineParams* sp) {
+  if (!c->spl_segments) return false;
+  const JxlHipContext::Modular& M = c->mod;
+  sp->planes = c->spl_planes.as<float>();
+  sp->segments = c->spl_seg.as<float>();
+  sp->row_start = c->spl_row_start.as<uint32_t>();
+  sp->row_segments = c->spl_row_seg.as<uint32_t>();
+  sp->stride = M.xs;
+  sp->plane_stride = size_t(M.xs) * M.ys;
+  sp->xsize = M.xs;
+  sp->y_begin = 0;
+  sp->y_end = M.ys;
+  return true;
+}
+static bool FillModOutput(const JxlHipContext* c, jxlhip::ModOutput* o) {  // (every frame: a set has at least one, so this launch always exists)
+  const JxlHipContext::Modular& M = c->mod;
+  if (ModFloatPlanes(c)) {
+    o->fplanes = c->spl_planes.as<float>();
+    o->fmode = 2;
+  }
+  o->xyb = M.xyb ? 1 : 0;
+  memcpy(o->xyb_factor, M.xyb_factor, sizeof(o->xyb_factor));
+  o->color = M.xyb_color;
+  o->target = M.xyb_target;
+  for (uint32_t j = 0; j < M.num_color + (M.has_alpha ? 1 : 0); j++) {
+    o->ch[j] = M.pool.as<int32_t>() + M.buf_off[M.out_buffer[j]];
+    o->stride[j] = M.xs;
+  }
+  o->num_color = M.num_color;
+  o->has_alpha = M.has_alpha;
+  o->bits = M.bits;
+  o->alpha_bits = M.alpha_bits;
+  o->w = M.xs;
+  o->h = M.ys;
+  o->po.dst = c->rgb.p;
+  o->po.alpha = nullptr;
+  o->po.xsize = M.xs;
+  o->po.ysize = M.ys;
+  o->po.orient = c->out_orient | (c->out_unpremul ? 8u : 0u);
+  o->po.type = c->out_type;
+  o->po.nc = c->out_nc;
+  o->po.bits = c->out_bits;
+  o->po.swap = c->out_swap;
+  return true;
+}
+// One pass over the frames of a set that take it: a zeroed block each, one launch. `rows`: one workgroup per row (the
+// spline and patch kernels) instead of 256 columns per workgroup.
+template <typename Block>
+static void ModAppendPass(JxlHipContext* const* ctxs, size_t n, uint32_t kind, bool rows, bool (*fill)(const JxlHipContext*, Block*),
+                          std::vector<uint8_t>* blob, std::vector<ModLaunch>* launches) {
+  upload::ModBlobAlign(blob);
+  ModLaunch L{kind, blob->size(), 0, 0, 0};
+  for (size_t i = 0; i < n; i++) {
+    Block b;
+    memset(&b, 0, sizeof(b));
+    if (!fill(ctxs[i], &b)) continue;
+    upload::ModBlobAppend(blob, &b, sizeof(b));
+    L.count++;
+    L.gx = rows ? 1 : std::max(L.gx, (ctxs[i]->mod.xs + 255) / 256);
+    L.gy = std::max(L.gy, ctxs[i]->mod.ys);
+  }
+  if (L.count) launches->push_back(L);
+}
+// The inverse transforms (upload::BuildModSchedule) and the pixel writer of a set of frames, as launches over
+// parameter-block arrays. Built once per set (cached with the stream list), blocks in `blob` (host), launches in `launches`.
 static void ModularBuildOps(JxlHipContext* const* ctxs, size_t n, std::vector<uint8_t>* blob, std::vector<ModLaunch>* launches) {
   blob->clear();
   launches->clear();
-  auto append = [&](const void* p, size_t bytes) {
-    const size_t at = blob->size();
-    blob->resize(at + bytes);
-    memcpy(blob->data() + at, p, bytes);
-  };
-  auto align = [&]() { blob->resize((blob->size() + 15) & ~size_t(15)); };
-  struct Ref {
-    uint32_t phase, level, kind;  // kind: the ModLaunch kind
-    uint32_t ctx, op;
-  };
-  std::vector<Ref> refs;
+  std::vector<upload::ModFrameOps> frames(n);
   for (size_t i = 0; i < n; i++) {
     const JxlHipContext::Modular& M = ctxs[i]->mod;
-    for (size_t k = 0; k < M.ops.size(); k++) {
-      const JxlHipModOp& op = M.ops[k];
-      const uint32_t kind = op.kind >= 2 ? 2 : op.kind;
-      refs.push_back({op.local ? 0u : 1u, op.level, kind, uint32_t(i), uint32_t(k)});
-    }
+    frames[i] = {uintptr_t(M.pool.p), M.buf_off.data(), M.buf_w.data(), M.ops.data(), M.ops.size()};
   }
-  std::stable_sort(refs.begin(), refs.end(), [](const Ref& a, const Ref& b) {
-    return a.phase != b.phase ? a.phase < b.phase : (a.level != b.level ? a.level < b.level : a.kind < b.kind);
-  });
-  for (size_t first = 0; first < refs.size();) {
-    size_t end = first;
-    while (end < refs.size() && refs[end].phase == refs[first].phase && refs[end].level == refs[first].level && refs[end].kind == refs[first].kind) end++;
-    const uint32_t kind = refs[first].kind;
-    align();
-    ModLaunch L{kind, blob->size(), 0, 0, 0};
-    for (size_t q = first; q < end; q++) {
-      const JxlHipContext::Modular& M = ctxs[refs[q].ctx]->mod;
-      const JxlHipModOp& op = M.ops[refs[q].op];
-      int32_t* pool = M.pool.as<int32_t>();
-      auto at = [&](uint32_t j) { return pool + M.buf_off[op.buf[j]] + size_t(op.oy[j]) * M.buf_w[op.buf[j]] + op.ox[j]; };
-      if (!op.w || !op.h) continue;
-      if (kind == 0) {
-        jxlhip::ModRct p;
-        memset(&p, 0, sizeof(p));
-        for (uint32_t j = 0; j < 3; j++) {
-          p.stride[j] = M.buf_w[op.buf[j]];
-          p.c[j] = at(j);
-        }
-        p.w = op.w;
-        p.h = op.h;
-        p.type = op.param;
-        append(&p, sizeof(p));
-        L.gx = std::max(L.gx, (op.w + 255) / 256);
-        L.gy = std::max(L.gy, op.h);
-      } else if (kind == 1) {
-        jxlhip::ModPalette p;
-        memset(&p, 0, sizeof(p));
-        p.palette = pool + M.buf_off[op.buf[0]];
-        p.index = at(1);
-        p.index_stride = M.buf_w[op.buf[1]];
-        for (uint32_t j = 0; j < op.nb; j++) {
-          p.out[j] = at(2 + j);
-          p.out_stride[j] = M.buf_w[op.buf[2 + j]];
-        }
-        p.palette_w = op.param;
-        p.nb = op.nb;
-        p.w = op.w;
-        p.h = op.h;
-        p.bit_depth = op.bit_depth;
-        append(&p, sizeof(p));
-        L.gx = std::max(L.gx, (op.w + 255) / 256);
-        L.gy = std::max(L.gy, op.h);
-      } else {
-        const bool hz = op.kind == 2;
-        const uint32_t len = hz ? op.w : op.h;
-        jxlhip::ModUnsqueeze p;
-        memset(&p, 0, sizeof(p));
-        p.avg = at(0);
-        p.res = at(1);
-        p.out = at(2);
-        p.lines = hz ? op.h : op.w;
-        p.na = len - len / 2;
-        p.nr = len / 2;
-        const uint32_t wa = M.buf_w[op.buf[0]], wr = M.buf_w[op.buf[1]], wo = M.buf_w[op.buf[2]];
-        p.avg_line = hz ? wa : 1;
-        p.avg_step = hz ? 1 : wa;
-        p.res_line = hz ? wr : 1;
-        p.res_step = hz ? 1 : wr;
-        p.out_line = hz ? wo : 1;
-        p.out_step = hz ? 1 : wo;
-        append(&p, sizeof(p));
-        L.gx = std::max(L.gx, (p.lines + 63) / 64);
-        L.gy = 1;
-      }
-      L.count++;
-    }
-    if (L.count) launches->push_back(L);
-    first = end;
-  }
-  // frames with patches / splines: colour samples to float planes (kind 4), the patches (kind 6), then the splines (kind 5)
-  // over them (dec_cache.cc:193-201), then the output reads them
-  for (uint32_t pass : {4u, 6u, 5u}) {
-    align();
-    ModLaunch S{pass, blob->size(), 0, 0, 0};
-    for (size_t i = 0; i < n; i++) {
-      const JxlHipContext* c = ctxs[i];
-      const JxlHipContext::Modular& M = c->mod;
-      if (pass == 4 ? !(c->spl_segments || c->keep_xyb || c->pat_positions) : (pass == 6 ? !c->pat_positions : !c->spl_segments)) continue;
-      if (pass == 6) {
-        jxlhip::PatchParams pp;
-        memset(&pp, 0, sizeof(pp));
-        pp.planes = c->spl_planes.as<float>();
-        pp.records = c->pat_rec.as<uint32_t>();
-        pp.row_start = c->pat_row_start.as<uint32_t>();
-        pp.row_list = c->pat_row_list.as<uint32_t>();
-        for (int k = 0; k < 4; k++) {
-          pp.slot_planes[k] = c->pat_src[k];
-          pp.slot_w[k] = c->pat_src_w[k];
-          pp.slot_h[k] = c->pat_src_h[k];
-        }
-        pp.stride = M.xs;
-        pp.plane_stride = size_t(M.xs) * M.ys;
-        pp.xsize = M.xs;
-        pp.y_begin = 0;
-        pp.y_end = M.ys;
-        append(&pp, sizeof(pp));
-        S.gx = 1;
-      } else if (pass == 4) {
-        jxlhip::ModOutput o;
-        memset(&o, 0, sizeof(o));
-        for (uint32_t j = 0; j < 3; j++) {
-          o.ch[j] = M.pool.as<int32_t>() + M.buf_off[M.out_buffer[j]];
-          o.stride[j] = M.xs;
-        }
-        o.num_color = 3;
-        o.bits = M.bits;
-        o.w = M.xs;
-        o.h = M.ys;
-        o.fplanes = c->spl_planes.as<float>();
-        o.fmode = 1;
-        o.xyb = M.xyb ? 1 : 0;  // (the planes then hold XYB; the final pass converts what it reads back)
-        memcpy(o.xyb_factor, M.xyb_factor, sizeof(o.xyb_factor));
-        append(&o, sizeof(o));
-        S.gx = std::max(S.gx, (M.xs + 255) / 256);
-      } else {
-        jxlhip::SplineParams sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.planes = c->spl_planes.as<float>();
-        sp.segments = c->spl_seg.as<float>();
-        sp.row_start = c->spl_row_start.as<uint32_t>();
-        sp.row_segments = c->spl_row_seg.as<uint32_t>();
-        sp.stride = M.xs;
-        sp.plane_stride = size_t(M.xs) * M.ys;
-        sp.xsize = M.xs;
-        sp.y_begin = 0;
-        sp.y_end = M.ys;
-        append(&sp, sizeof(sp));
-        S.gx = 1;
-      }
-      S.count++;
-      S.gy = std::max(S.gy, M.ys);
-    }
-    if (S.count) launches->push_back(S);
-  }
-  align();
-  ModLaunch L{3, blob->size(), 0, 0, 0};
-  for (size_t i = 0; i < n; i++) {
-    const JxlHipContext* c = ctxs[i];
-    const JxlHipContext::Modular& M = c->mod;
-    int32_t* pool = M.pool.as<int32_t>();
-    jxlhip::ModOutput o;
-    memset(&o, 0, sizeof(o));
-    if (c->spl_segments || c->keep_xyb || c->pat_positions) {
-      o.fplanes = c->spl_planes.as<float>();
-      o.fmode = 2;
-    }
-    o.xyb = M.xyb ? 1 : 0;
-    memcpy(o.xyb_factor, M.xyb_factor, sizeof(o.xyb_factor));
-    o.color = M.xyb_color;
-    o.target = M.xyb_target;
-    for (uint32_t j = 0; j < M.num_color + (M.has_alpha ? 1 : 0); j++) {
-      o.ch[j] = pool + M.buf_off[M.out_buffer[j]];
-      o.stride[j] = M.xs;
-    }
-    o.num_color = M.num_color;
-    o.has_alpha = M.has_alpha;
-    o.bits = M.bits;
-    o.alpha_bits = M.alpha_bits;
-    o.w = M.xs;
-    o.h = M.ys;
-    o.po.dst = c->rgb.p;
-    o.po.alpha = nullptr;
-    o.po.xsize = M.xs;
-    o.po.ysize = M.ys;
-    o.po.orient = c->out_orient | (c->out_unpremul ? 8u : 0u);
-    o.po.type = c->out_type;
-    o.po.nc = c->out_nc;
-    o.po.bits = c->out_bits;
-    o.po.swap = c->out_swap;
-    append(&o, sizeof(o));
-    L.count++;
-    L.gx = std::max(L.gx, (M.xs + 255) / 256);
-    L.gy = std::max(L.gy, M.ys);
-  }
-  launches->push_back(L);
+  upload::BuildModSchedule(frames.data(), n, blob, launches);
+  ModAppendPass(ctxs, n, 4, false, FillModPlanes, blob, launches);
+  ModAppendPass(ctxs, n, 6, true, FillModPatches, blob, launches);
+  ModAppendPass(ctxs, n, 5, true, FillModSplines, blob, launches);
+  ModAppendPass(ctxs, n, 3, false, FillModOutput, blob, launches);
 }
 static int ModularLaunchOps(const std::vector<ModLaunch>& launches, const uint8_t* dev, hipStream_t st) {
   for (const ModLaunch& L : launches)

@@ -25,56 +25,9 @@
 
 #include "jxl_hip_color.h"
 #include "jxl_hip_kernels.h"
+#include "jxl_hip_modular_abi.h"
 
 namespace jxlhip {
-
-struct ModTreeNode {  // 16 bytes (jxlhip_modular_upload packs the boundary's nodes): one load per step of the walk
-  int32_t property;   // decision: the property tested (>= 0); leaf: -1 - predictor
-  int32_t splitval;   // leaf: offset
-  uint32_t lchild;    // leaf: histogram (the context already mapped through the code's context map)
-  uint32_t rchild;    // leaf: multiplier
-};
-
-struct ModCode {  // one entropy code (global or local to a stream); pointers into device memory
-  const uint8_t* ctx_map;   // context -> cluster
-  const uint2* alias;       // cluster << log_alpha (ANS)
-  const uint32_t* cfg;      // per cluster: split_exp | msb << 8 | lsb << 16
-  const uint32_t* prefix_table;
-  const uint32_t* prefix_offset;
-  uint32_t log_alpha, use_prefix, lz77, lz_min_symbol, lz_min_length, lz_len_cfg, lz_dist_ctx;
-  uint32_t table_words;     // 32-bit words of the symbol tables a wave may stage in LDS: the alias table (ANS) or the prefix
-                            // table, then one word per cluster (cfg), then for prefix codes one more per cluster (offsets)
-  uint32_t num_clusters, pad[3];
-};
-
-struct ModChannel {  // one channel of a stream: a rectangle of a frame channel buffer
-  int32_t* data;     // top-left sample of the rectangle
-  uint32_t stride;   // samples per row of the underlying buffer
-  uint32_t w, h;
-  uint32_t sig;      // channels of a stream with equal `sig` have identical size and shifts ("previous channel" properties)
-};
-
-struct ModStream {
-  const uint32_t* words;   // section bytes (4-byte aligned start)
-  uint32_t bit_offset;     // where the stream's sample data begins
-  uint32_t size_bytes;     // section size: reads beyond it are zero, consuming beyond it is an error
-  const ModTreeNode* tree;
-  uint32_t tree_nodes;
-  const ModCode* code;
-  const ModChannel* channels;
-  uint32_t num_channels;
-  uint32_t stream_id;      // MA property 1
-  uint32_t first_channel_index;  // MA property 0 of channels[0] (the following count up)
-  int32_t wp[11];          // weighted predictor header: p1C p2C p3Ca..p3Ce, w0..w3
-  uint32_t uses_wp;        // the tree tests property 15 or predicts with predictor 6
-  uint32_t num_props;      // 16 + 4 * referenced previous channels
-  uint32_t dist_multiplier;
-  int32_t* wp_scratch;     // 5 arrays of 2 * (max width + 2) ints (uses_wp only)
-  uint32_t* lz_window;     // lz_window_mask + 1 entries (code->lz77 only)
-  uint32_t lz_window_mask;
-  uint32_t* status;        // out: 0 ok, bit 0 = ANS final state, bit 1 = over-read, bit 2 = LZ77 length overflow
-  uint32_t* end_bit;       // out: bit position after the last sample
-};
 
 __constant__ int8_t c_special_distances[120][2] = {
     {0, 1},  {1, 0},  {1, 1},  {-1, 1}, {0, 2},  {2, 0},  {1, 2},  {-1, 2}, {2, 1},  {-2, 1}, {2, 2},  {-2, 2},
@@ -251,7 +204,6 @@ struct ModWp {
   int64_t prediction[4];
   int64_t pred;
 };
-constexpr uint32_t kModWpEntry = 8;  // ints per row entry
 // `ldiv` = (1 << 24) / (i + 1) for i in 0..63 in LDS (the reference's divlookup, context_predict.h:79-90): both
 // divisions of the predictor have divisors of at most 64, and an integer division is ~30 vector instructions here.
 __device__ __forceinline__ uint32_t ModErrorWeight(uint32_t x, uint32_t maxweight, const uint32_t* ldiv) {
@@ -343,7 +295,6 @@ __device__ __forceinline__ int64_t ModPredict(uint32_t p, int64_t left, int64_t 
   }
 }
 
-constexpr int kModMaxProps = 16 + 4 * 4;  // property 15 + up to four referenced previous channels (host refuses trees beyond)
 constexpr uint32_t kModTreeLdsNodes = 2048;  // largest tree kept in LDS (32 KB)
 
 constexpr uint32_t kModTableLdsWords = 8192;  // largest symbol-table set kept in LDS (32 KB)
@@ -636,16 +587,9 @@ __global__ __launch_bounds__(64) void k_modular_streams(const ModStream* streams
   *S.end_bit = uint32_t(consumed);
 }
 
-// ---- inverse transforms on channel rectangles: whole channels for the frame's own transforms, a group's rectangle of the
-// frame's buffers (or a private buffer) for the transforms of a group stream. The blocks carry pointers to the first
-// sample of each rectangle and the strides of the buffers they lie in.
-struct ModRct {
-  int32_t* c[3];  // the three channels in stored order
-  uint32_t stride[3];
-  uint32_t w, h, type;
-};
+// ---- inverse transforms on channel rectangles (parameter blocks: jxl_hip_modular_abi.h)
 // Every transform kernel takes an array of parameter blocks, one per blockIdx.z: a launch does one level of many groups
-// and frames (jxl_hip_api.hip, ModularBuildOps), grid x / y sized for the largest.
+// and frames (csrc/host/jxh_modular_upload_plan.h, BuildModSchedule), grid x / y sized for the largest.
 __global__ __launch_bounds__(256) void k_modular_rct(const ModRct* ops) {  // rct.cc:97-147
   const ModRct& P = ops[blockIdx.z];
   const uint32_t x = blockIdx.x * 256 + threadIdx.x;
@@ -689,13 +633,6 @@ __device__ __forceinline__ int64_t ModSmoothTendency(int64_t before, int64_t avg
   }
   return t;
 }
-struct ModUnsqueeze {
-  const int32_t* avg;
-  const int32_t* res;
-  int32_t* out;
-  uint32_t lines, na, nr;             // lines to do; averages / residuals per line
-  uint32_t avg_line, avg_step, res_line, res_step, out_line, out_step;  // strides between lines / between samples of a line
-};
 // One thread per line (a row for a horizontal step, a column for a vertical one): squeeze.cc:128-330. A line is a serial
 // chain through the smooth-tendency term; its loads are issued four samples ahead of that chain.
 __global__ __launch_bounds__(64) void k_modular_unsqueeze(const ModUnsqueeze* ops) {
@@ -730,12 +667,6 @@ __global__ __launch_bounds__(64) void k_modular_unsqueeze(const ModUnsqueeze* op
   if (na > nr) out[size_t(2 * nr) * os] = avg[size_t(na - 1) * as];
 }
 
-struct ModPalette {  // palette.cc:26-202, the form without delta entries and predictor (nb_deltas == 0, predictor 0)
-  const int32_t* palette;  // [nb_channels][palette_w]
-  const int32_t* index;    // the index channel's rectangle
-  int32_t* out[4];         // the output rectangles; out[0] may be the index rectangle itself
-  uint32_t palette_w, nb, w, h, bit_depth, index_stride, out_stride[4];
-};
 __constant__ int16_t c_palette_delta[72][3] = {
     {0, 0, 0},       {4, 4, 4},       {11, 0, 0},      {0, 0, -13},     {0, -12, 0},     {-10, -10, -10},
     {-18, -18, -18}, {-27, -27, -27}, {-18, -18, 0},   {0, 0, -32},     {-32, 0, 0},     {-37, -37, -37},

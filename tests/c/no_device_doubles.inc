@@ -1,6 +1,7 @@
 // The HIP layer's entry points that libjxl_amd/csrc/api/jxl_api.cc calls, as "no device" doubles for CPU programs built
-// around it (api_fuzz.cc, upload_plan_kats.cc): a decoder that reaches them gets an error, which is a valid end.
-// KATS_OWN_FRAME_UPLOAD: the including program defines jxlhip_frame_upload itself.
+// around it (api_fuzz.cc, upload_plan_kats.cc, modular_upload_kats.cc): a decoder that reaches them gets an error, which
+// is a valid end. KATS_OWN_FRAME_UPLOAD / KATS_OWN_MODULAR_UPLOAD: the including program defines jxlhip_frame_upload /
+// jxlhip_modular_upload itself.
 extern "C" {
 int jxlhip_device_count(void) { return 0; }
 int jxlhip_ctx_create(int, JxlHipContext**) { return JXLHIP_ERR_INVALID_ARGUMENT; }
@@ -14,7 +15,9 @@ int jxlhip_get_section_end_bits(JxlHipContext*, uint32_t*, size_t) { return JXLH
 int jxlhip_modular_download_buffer(JxlHipContext*, uint32_t, int32_t*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
 int jxlhip_modular_run(JxlHipContext*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
 int jxlhip_modular_status(JxlHipContext*, uint32_t*, uint32_t*, size_t) { return JXLHIP_ERR_INVALID_ARGUMENT; }
+#ifndef KATS_OWN_MODULAR_UPLOAD
 int jxlhip_modular_upload(JxlHipContext*, const JxlHipModFrameDesc*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
+#endif
 int jxlhip_run_entropy(JxlHipContext*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
 int jxlhip_run_filter_color(JxlHipContext*) { return JXLHIP_ERR_INVALID_ARGUMENT; }
 int jxlhip_run_transform(JxlHipContext*) { return JXLHIP_ERR_INVALID_ARGUMENT; }

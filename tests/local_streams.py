@@ -4,6 +4,18 @@ its default effort, made by the repository's stream writer; shared by the CPU an
 import numpy as np
 
 
+def lossless_image(J, w, h, channels, seed):
+    """The synthetic image with `channels` channels (grey, grey + alpha, RGB, RGBA; the alpha is a ramp pattern)."""
+    rgb = J.synth_image(w, h, seed=seed)
+    y, x = np.mgrid[0:h, 0:w]
+    alpha = ((x * 3 + y * 5) % 256).astype(np.uint8)
+    if channels == 1:
+        return np.ascontiguousarray(rgb[..., 1:2])
+    if channels == 2:
+        return np.ascontiguousarray(np.dstack([rgb[..., 1], alpha]))
+    return np.ascontiguousarray(rgb if channels == 3 else np.dstack([rgb, alpha]))
+
+
 def mixed_image(w, h, channels, seed, colors=12):
     """Noise, except: the first 256 x 256 group holds `colors` colours in all channels (an all-channel palette fits), the
     group right of it few values in its first channel only (a single-channel palette fits), and, when the image is three

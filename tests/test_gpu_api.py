@@ -630,3 +630,41 @@ def test_a_refused_upload_leaves_the_context_as_it_was(built, monkeypatch):
         c.close()
         good.close()
         bad.close()
+
+
+def test_a_refused_modular_upload_leaves_the_context_as_it_was(built, monkeypatch):
+    """jxlhip_modular_upload decides on the host whether it takes a descriptor (upload::ModRule), before it touches the
+    device or the context. One context: a 64 x 48 lossless frame is uploaded and decoded; the same frame with the first
+    rectangle of its RCT pushed one column outside its buffer -- a rule the upload used to reach only after it had
+    overwritten the context's tables -- is refused (JXLHIP_ERR_INVALID_ARGUMENT = 1) and leaves no frame to run
+    (JXLHIP_ERR_NO_FRAME = 2); the first frame, uploaded again, decodes to the encoder's input, and under JXLHIP_GUARD=1
+    no kernel has written next to a buffer."""
+    import ctypes
+    J = built
+    L = J.lib()
+    monkeypatch.setenv("JXLHIP_GUARD", "1")
+    L.jxlamd_modframe_debug_shift_op.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    img = J.synth_image(64, 48, seed=3)
+    data = J.encode_lossless(img, J.LOSSLESS_RCT)
+    good, bad = J.ModFrame(data), J.ModFrame(data)
+    c = J.HipContext()
+    try:
+        def decode():
+            c.upload_modular(good)
+            c.run_modular()
+            c.sync()
+            r, status, _ = c.modular_status()
+            assert r == 0 and not any(status)
+            return c.pixels().copy()
+        assert np.array_equal(decode(), img)
+        assert bad.info["num_ops"] >= 1 and L.jxlamd_modframe_debug_shift_op(bad._h, 0) == 0
+        with pytest.raises(J.JxlAmdError, match="code 1"):
+            c.upload_modular(bad)
+        with pytest.raises(J.JxlAmdError, match="code 2"):
+            c.run_modular()
+        assert np.array_equal(decode(), img)
+        assert c.check_guards() == 0, c.check_guards()
+    finally:
+        c.close()
+        good.close()
+        bad.close()

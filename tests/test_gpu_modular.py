@@ -9,6 +9,8 @@ import sys
 import numpy as np
 import pytest
 
+from local_streams import lossless_image as _lossless_image
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
@@ -116,17 +118,6 @@ def test_lossless_through_the_decoder_api(built, tmp_path):
     rc, events, out, px = R.run(R.container(data), tmp_path, "u8", 4, "chunk=5000")
     assert rc == 0, out
     assert np.array_equal(np.frombuffer(px, np.uint8).reshape(260, 520, 4), G.golden_image(name))
-
-
-def _lossless_image(J, w, h, channels, seed):
-    rgb = J.synth_image(w, h, seed=seed)
-    y, x = np.mgrid[0:h, 0:w]
-    alpha = ((x * 3 + y * 5) % 256).astype(np.uint8)
-    if channels == 1:
-        return np.ascontiguousarray(rgb[..., 1:2])
-    if channels == 2:
-        return np.ascontiguousarray(np.dstack([rgb[..., 1], alpha]))
-    return np.ascontiguousarray(rgb if channels == 3 else np.dstack([rgb, alpha]))
 
 
 @pytest.mark.parametrize("flags,size,channels", [
