@@ -112,6 +112,9 @@ typedef struct JxlAmdModFrame JxlAmdModFrame;
 /* Parses the first frame of a codestream as a Modular frame: headers, TOC, global tree and histograms and every stream's
  * group header; no sample is decoded on the host. `data` must stay valid until the frame has been uploaded. */
 int jxlamd_modframe_parse(const uint8_t* data, size_t size, JxlAmdModFrame** frame);
+/* Which of the two front-ends takes the codestream's first frame, from its frame header alone: *modular = 1 for
+ * jxlamd_modframe_parse, 0 for jxlamd_frame_parse. */
+int jxlamd_frame_is_modular(const uint8_t* data, size_t size, uint32_t* modular);
 /* The reference frames a Modular frame's patches read: as jxlamd_frame_set_patch_sources (before the upload). */
 int jxlamd_modframe_set_patch_sources(JxlAmdModFrame* frame, const float* const* planes, const uint32_t* xsize, const uint32_t* ysize);
 /* As jxlamd_frame_parse_at / jxlamd_frame_end, for Modular frames. */

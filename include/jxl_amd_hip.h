@@ -288,6 +288,43 @@ int jxlhip_download_rgb8_rows(JxlHipContext* ctx, uint8_t* dst, size_t stride, u
 /* Device pointer of the RGB8 result (xsize * 3 bytes per row, tightly packed). */
 const uint8_t* jxlhip_rgb8_device_ptr(JxlHipContext* ctx);
 
+/* ---- Output into device memory the caller owns (a tensor of the framework that consumes the image), instead of the
+ * context's own interleaved buffer. Element (c, y, x) of the OUTPUT image (after jxlhip_set_output_orientation) goes to
+ * data[c * stride_c + y * stride_y + x * stride_x], strides in elements: planar (CHW), interleaved (HWC), padded pitches
+ * and one image of an NCHW batch are all this map. The library never writes outside [data, data + bytes).
+ *   v = the float the f32 writer of jxlhip_set_output_format(ctx, 0, num_channels, 0, 0) stores for the same frame and
+ *       options (alpha as the last of 2 / 4 channels, un-premultiplication, R for 1 / 2 channels of a colour image).
+ *   Float types: v = fmin(fmax(v, 0), 1) first when clamp01 is set (a NaN becomes 0); then t = v * scale[c] rounded to
+ *       float, then t + bias[c] rounded to float (two operations, never a fused one), then round-to-nearest-even to dtype.
+ *   JXLHIP_TENSOR_U8: scale 1, bias 0 and clamp01 0 only; the sample is the 8-bit sample of the generic writer (v * 255
+ *       plus the dither cell of interleave index c at the oriented position, each rounded; clamped; nearest even).
+ * While a tensor is bound the context allocates no pixel buffer, jxlhip_download_pixels / _rgb8 / _rgb8_rows answer
+ * JXLHIP_ERR_INVALID_ARGUMENT and jxlhip_rgb8_device_ptr NULL, band uploads and the jxlhip_canvas_* calls that take the
+ * context answer JXLHIP_ERR_UNSUPPORTED, and jxlhip_set_output_format is not consulted. Call before the upload, which checks
+ * the descriptor again against the image's size (a refused one launches nothing). NULL: the context's own buffer again.
+ * A context that is destroyed drops its binding.
+ * Ordering, without any host wait: the first launch that writes the tensor waits for what consumer_stream holds at that
+ * call (the consumer's earlier fill or read of the tensor), and consumer_stream waits for the last such launch of the
+ * call (jxlhip_run_filter_color[_batch], jxlhip_modular_run[_batch]; in a batch every context's own consumer_stream).
+ * With a float dtype, three channels, stride_x 1 and no orientation, a frame that would get RGB f32 from the row-streaming
+ * filter kernel gets the tensor from that kernel too (jxlhip_debug_pixel_route: 3); everything else goes through the
+ * generic writer. */
+#define JXLHIP_TENSOR_F32 0u
+#define JXLHIP_TENSOR_U8 2u
+#define JXLHIP_TENSOR_F16 5u
+#define JXLHIP_TENSOR_BF16 6u
+typedef struct {
+  void* data;                         /* device memory on the context's device */
+  size_t bytes;                       /* room behind data */
+  uint32_t dtype;                     /* JXLHIP_TENSOR_* */
+  uint32_t num_channels;              /* 1..4, as jxlhip_set_output_format's */
+  int64_t stride_c, stride_y, stride_x; /* in elements, > 0 */
+  float scale[4], bias[4];
+  uint32_t clamp01;
+  void* consumer_stream;              /* hipStream_t (0 = the null stream) */
+} JxlHipTensorOut;
+int jxlhip_set_output_tensor(JxlHipContext* ctx, const JxlHipTensorOut* tensor);
+
 /* Per-group error flags written by the entropy kernel: bit0 invalid nzeros, bit1 ANS final state,
  * bit2 section over-read, bit3 invalid histogram selector. Synchronous. `flags` has num_groups entries.
  * Returns JXLHIP_ERR_STREAM if any flag is set. */
@@ -408,7 +445,8 @@ int jxlhip_debug_noise(JxlHipContext* ctx, const float* xyb, uint32_t xsize, uin
 
 /* Test access: who writes the pixels of the VarDCT frame the context last uploaded. *route = 0: the generic writer behind
  * the filter kernel (k_color_out / k_upsample_color), 1: the filter kernel itself (RGB8, RGB f32), 2: the one-channel
- * 8-bit form of the row-streaming filter kernel (k_filter_rows2<true, EPF, GAB, true>). */
+ * 8-bit form of the row-streaming filter kernel (k_filter_rows2<true, EPF, GAB, true>), 3: its tensor form
+ * (k_filter_rows2<false, EPF, GAB, false, true>, jxlhip_set_output_tensor). */
 int jxlhip_debug_pixel_route(JxlHipContext* ctx, uint32_t* route);
 /* Test access: which kernel jxlhip_run_entropy launches for the VarDCT frame the context last uploaded. *route = 0:
  * k_entropy_lanes (the frame is kept in scan order when it has one pass), 1: k_entropy_uni, 2: k_entropy_ans (alias tables

@@ -228,6 +228,26 @@ class ModFrame:
             pass
 
 
+TENSOR_F32, TENSOR_U8, TENSOR_F16, TENSOR_BF16 = 0, 2, 5, 6  # JXLHIP_TENSOR_*
+
+
+class TensorOut(ctypes.Structure):  # JxlHipTensorOut
+    _fields_ = [("data", ctypes.c_void_p), ("bytes", ctypes.c_size_t), ("dtype", ctypes.c_uint32), ("num_channels", ctypes.c_uint32),
+                ("stride_c", ctypes.c_int64), ("stride_y", ctypes.c_int64), ("stride_x", ctypes.c_int64),
+                ("scale", ctypes.c_float * 4), ("bias", ctypes.c_float * 4), ("clamp01", ctypes.c_uint32),
+                ("consumer_stream", ctypes.c_void_p)]
+
+
+def frame_is_modular(data):
+    """Whether the codestream's first frame is Modular-coded (ModFrame, upload_modular) or VarDCT (Frame, upload)."""
+    L = lib()
+    L.jxlamd_frame_is_modular.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
+    m = ctypes.c_uint32()
+    data = bytes(data)
+    _check(L.jxlamd_frame_is_modular(data, len(data), ctypes.byref(m)), "jxlamd_frame_is_modular")
+    return bool(m.value)
+
+
 class HipContext:
     """One HIP stream + the device buffers of one frame (include/jxl_amd_hip.h)."""
 
@@ -356,6 +376,29 @@ class HipContext:
         """JxlDataType numbering: 0 f32, 2 u8, 3 u16, 5 f16; call before upload."""
         _check(lib().jxlhip_set_output_format(self._h, data_type, num_channels, bits, 1 if big_endian else 0), "jxlhip_set_output_format")
         self._out = (data_type, num_channels)
+
+    def set_output_tensor(self, ptr, nbytes=0, dtype=TENSOR_F16, num_channels=3, strides=None, scale=None, bias=None, clamp=False, stream=0):
+        """jxlhip_set_output_tensor: the pixels of the next uploads go to caller-owned device memory at `ptr` (`nbytes` of
+        room) instead of the context's own buffer; ptr=None unbinds. dtype: TENSOR_U8 / _F16 / _BF16 / _F32; strides =
+        (stride_c, stride_y, stride_x) in elements of the output image; float types store v * scale[c] + bias[c] (after a
+        clamp to 0..1 if asked), each step rounded; stream: the consumer's hipStream_t as an integer (0 = the null stream),
+        ordered before and behind the writes without a host wait. Call before upload. libjxl_amd.torch_io binds a tensor."""
+        L = lib()
+        L.jxlhip_set_output_tensor.argtypes = [ctypes.c_void_p, ctypes.POINTER(TensorOut)]
+        if ptr is None:
+            _check(L.jxlhip_set_output_tensor(self._h, None), "jxlhip_set_output_tensor")
+            self._tensor = None
+            return
+        t = TensorOut()
+        t.data, t.bytes, t.dtype, t.num_channels = int(ptr), int(nbytes), int(dtype), int(num_channels)
+        t.stride_c, t.stride_y, t.stride_x = [int(s) for s in strides]
+        for c in range(4):
+            t.scale[c] = 1.0 if scale is None or c >= len(scale) else float(scale[c])
+            t.bias[c] = 0.0 if bias is None or c >= len(bias) else float(bias[c])
+        t.clamp01 = 1 if clamp else 0
+        t.consumer_stream = int(stream) or None
+        _check(L.jxlhip_set_output_tensor(self._h, ctypes.byref(t)), "jxlhip_set_output_tensor")
+        self._tensor = t
 
     def set_output_orientation(self, orientation=1):
         """Undo this image orientation (1..8, EXIF numbering) in the pixel writer; call before upload."""

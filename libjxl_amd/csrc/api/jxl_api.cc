@@ -110,6 +110,30 @@ uint32_t jxlamd_frame_complete_passes(const JxlAmdFrame* f, size_t have_bytes, u
   }
   return complete;
 }
+// Which front-end takes the codestream's first frame, from its header alone: *modular = 1 for jxlamd_modframe_parse, 0 for
+// jxlamd_frame_parse.
+int jxlamd_frame_is_modular(const uint8_t* data, size_t size, uint32_t* modular) {
+  g_last_error.clear();
+  if (!data || !modular) {
+    g_last_error = "invalid argument";
+    return 1;
+  }
+  try {
+    jxh::FrameParser parser(data, size);
+    jxh::ImageHeader ih;
+    const size_t pos = parser.ParseImageHeader(&ih);
+    if (ih.have_preview) {  // (the first frame is the preview, its default size the preview's: ParseFrameAt)
+      ih.xsize = ih.preview_xsize;
+      ih.ysize = ih.preview_ysize;
+    }
+    *modular = parser.FrameIsModular(pos, ih) ? 1 : 0;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return 2;
+  }
+  return 0;
+}
+
 static int ParseFrameAt(const uint8_t* data, size_t size, size_t frame_pos, size_t frame_index, JxlParallelRunner runner,
                         void* runner_opaque, bool allow_partial, JxlAmdFrame** out) {
   g_last_error.clear();

@@ -20,6 +20,7 @@
 #include "../host/jxh_enc_shared.h"
 #include "../host/jxh_launch_order.h"
 #include "../host/jxh_modular_upload_plan.h"
+#include "../host/jxh_tensor_out.h"
 #include "../host/jxh_upload_plan.h"
 #include "jxl_hip_kernels.h"
 #include "jxl_hip_entropy_lanes.h"
@@ -30,6 +31,7 @@
 #include "jxl_hip_dc.h"
 
 namespace upload = jxlhip::upload;
+namespace tensor_out = jxlhip::tensor_out;
 
 namespace {
 #include "../host/afv_basis.inc"
@@ -254,6 +256,12 @@ struct JxlHipContext {
                                // neighbouring bands that its filters read arrive through jxlhip_halo_unpack
   // output pixel format (jxlhip_set_output_format; JxlDataType numbering): RGB8 by default
   uint32_t out_type = 2, out_nc = 3, out_bits = 8, out_swap = 0;
+  // jxlhip_set_output_tensor: the pixels go to the caller's memory in `tensor`'s layout and type instead of `rgb`, which
+  // is then not allocated (OutType / OutChannels / OutBits / OutSwap say what the writers make). tensor_fused (set at
+  // upload): from k_filter_rows2's tensor form. tensor_event orders the writers against tensor.consumer_stream.
+  bool tensor_bound = false, tensor_fused = false;
+  JxlHipTensorOut tensor{};
+  hipEvent_t tensor_event = nullptr;
   // forward (encoder) path, jxlhip_enc_forward: device buffers and the kernel time of the last call
   Buf enc_rgb, enc_planes[3], enc_act, enc_acs, enc_qf, enc_off, enc_dc, enc_coef, enc_lut, enc_dq, enc_ytox, enc_ytob;
   hipEvent_t enc_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // whole sequence; the transform kernel of its last pass; the two adaptive-quant kernels of its last pass (quant_field_mode 1)
@@ -392,9 +400,39 @@ static bool SectionEntropyForced() {
 static JxlHipContext* PlaneHolder(JxlHipContext* c) { return c->plane_lender ? c->plane_lender : c; }
 static const JxlHipContext* PlaneHolder(const JxlHipContext* c) { return c->plane_lender ? c->plane_lender : c; }
 
+// The sample format the writers make: the bound tensor's, else jxlhip_set_output_format's.
+static uint32_t OutType(const JxlHipContext* c) { return c->tensor_bound ? c->tensor.dtype : c->out_type; }
+static uint32_t OutChannels(const JxlHipContext* c) { return c->tensor_bound ? c->tensor.num_channels : c->out_nc; }
+static uint32_t OutBits(const JxlHipContext* c) { return c->tensor_bound ? 8u : c->out_bits; }
+static uint32_t OutSwap(const JxlHipContext* c) { return c->tensor_bound ? 0u : c->out_swap; }
 static size_t OutSampleBytes(const JxlHipContext* c) { return c->out_type == 2 ? 1 : (c->out_type == 0 ? 4 : 2); }
 static size_t OutPixelBytes(const JxlHipContext* c) { return OutSampleBytes(c) * c->out_nc; }
-static bool OutIsRgb8(const JxlHipContext* c) { return upload::OutIsRgb8(c->out_type, c->out_nc, c->out_bits); }
+// (the context's own RGB8 rows: never a tensor, whatever its type)
+static bool OutIsRgb8(const JxlHipContext* c) { return !c->tensor_bound && upload::OutIsRgb8(c->out_type, c->out_nc, c->out_bits); }
+// Room of the context's own pixel buffer for the frame: none while a tensor is bound.
+static size_t OwnPixelBytes(const JxlHipContext* c) { return c->tensor_bound ? 0 : size_t(c->oxs) * c->oys * OutPixelBytes(c); }
+
+// Where and how the generic writers store (PixelOut's layout half): the context's interleaved rows, or the bound tensor.
+static void FillPixelOutLayout(const JxlHipContext* c, jxlhip::PixelOut* po) {
+  po->type = OutType(c);
+  po->nc = OutChannels(c);
+  po->bits = OutBits(c);
+  po->swap = OutSwap(c);
+  if (c->tensor_bound) {
+    const JxlHipTensorOut& t = c->tensor;
+    po->dst = t.data;
+    po->stride_c = t.stride_c;
+    po->stride_y = t.stride_y;
+    po->stride_x = t.stride_x;
+    po->tensor = 1;
+    po->clamp01 = t.clamp01 ? 1 : 0;
+    memcpy(po->scale, t.scale, sizeof(po->scale));
+    memcpy(po->bias, t.bias, sizeof(po->bias));
+    return;
+  }
+  po->dst = c->rgb.p;
+  jxlhip::SetInterleaved(po, (po->orient & 4) ? po->ysize : po->xsize);
+}
 
 static int EnvInt(const char* name, int def) {
   const char* e = getenv(name);
@@ -574,6 +612,9 @@ void jxlhip_ctx_destroy(JxlHipContext* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+  // (the caller's tensor is the caller's to free from here on: whoever takes this context from the pool starts unbound)
+  c->tensor_bound = c->tensor_fused = false;
+  c->tensor = JxlHipTensorOut{};
   if (c->basis.p && !c->pooled_once && !GuardOn() && EnvInt("JXLHIP_CTX_POOL", 1)) {  // keep it for the next jxlhip_ctx_create (see RecycleContext)
     size_t bytes = 0;
     for (Buf* b : AllBufs(c))
@@ -607,11 +648,51 @@ void jxlhip_ctx_destroy(JxlHipContext* c) {
   if (c->transform_done) (void)hipEventDestroy(c->transform_done);
   if (c->filter_done) (void)hipEventDestroy(c->filter_done);
   if (c->halo_event) (void)hipEventDestroy(c->halo_event);
+  if (c->tensor_event) (void)hipEventDestroy(c->tensor_event);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
   if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 }  // extern "C"
+
+// Bound tensors against their consumers' streams, with no host wait (the pattern of jxlhip_halo_unpack_batch / _pack_batch).
+// Before the first launch of a call that writes them: the launch stream `ls` waits for what every consumer stream holds
+// now (the consumer's earlier fill or read of the tensor). After the last one: every consumer stream waits for `ls`.
+// Contexts without a tensor cost nothing; consecutive contexts on one consumer stream cost one event.
+static int TensorsBeforeWriters(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) {
+  bool any = false;
+  hipStream_t waited = nullptr;
+  for (size_t i = 0; i < n; i++) {
+    JxlHipContext* c = ctxs[i];
+    if (!c->tensor_bound) continue;
+    const hipStream_t cs = static_cast<hipStream_t>(c->tensor.consumer_stream);
+    if (any && cs == waited) continue;
+    if (!c->tensor_event) HIP_TRY(hipEventCreateWithFlags(&c->tensor_event, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->tensor_event, cs));
+    HIP_TRY(hipStreamWaitEvent(ls, c->tensor_event, 0));
+    any = true;
+    waited = cs;
+  }
+  return 0;
+}
+static int TensorsAfterWriters(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) {
+  hipEvent_t done = nullptr;
+  hipStream_t told = nullptr;
+  for (size_t i = 0; i < n; i++) {
+    JxlHipContext* c = ctxs[i];
+    if (!c->tensor_bound) continue;
+    const hipStream_t cs = static_cast<hipStream_t>(c->tensor.consumer_stream);
+    if (done && cs == told) continue;
+    if (!done) {  // (one record behind the last writer serves every consumer stream)
+      if (!c->tensor_event) HIP_TRY(hipEventCreateWithFlags(&c->tensor_event, hipEventDisableTiming));
+      HIP_TRY(hipEventRecord(c->tensor_event, ls));
+      done = c->tensor_event;
+    }
+    HIP_TRY(hipStreamWaitEvent(cs, done, 0));
+    told = cs;
+  }
+  return 0;
+}
 
 static int ApplyPendingWait(JxlHipContext* c) {
   if (c->pending_wait) {
@@ -809,16 +890,31 @@ static void AdoptPatches(JxlHipContext* c, const JxlHipPatches& pt) {
   }
 }
 // -------------------------------------------------------------------------------------------------- frame upload
+// The bound tensor against the frame: whole frames only, and the descriptor's rules (jxh_tensor_out.h) at the size of the
+// output image, which a transposing orientation turns. *reach: bytes from the tensor's first element to behind the last one.
+static int CheckBoundTensor(const JxlHipContext* c, const upload::Geometry& g, uint32_t group_rows, uint64_t* reach) {
+  if (g.band_row0 != 0 || g.band_row1 != group_rows) return JXLHIP_ERR_UNSUPPORTED;
+  const bool transposed = (c->out_orient & 4) != 0;
+  const uint32_t w = transposed ? g.oys : g.oxs, h = transposed ? g.oxs : g.oys;
+  const int r = tensor_out::CheckTensorOut(c->tensor, w, h);
+  if (r) return r;
+  uint64_t max_offset = 0;
+  tensor_out::MaxOffset(c->tensor, w, h, &max_offset);
+  *reach = (max_offset + 1) * tensor_out::ElemBytes(c->tensor.dtype);
+  return 0;
+}
 static upload::UploadOptions OptionsOf(const JxlHipContext* c) {
   upload::UploadOptions o;
   o.band_halo = c->band_halo;
   o.keep_filtered = c->keep_filtered;
   o.keep_upsampled = c->keep_upsampled;
-  o.out_type = c->out_type;
-  o.out_nc = c->out_nc;
-  o.out_bits = c->out_bits;
-  o.out_swap = c->out_swap;
+  o.out_type = OutType(c);
+  o.out_nc = OutChannels(c);
+  o.out_bits = OutBits(c);
+  o.out_swap = OutSwap(c);
   o.out_orient = c->out_orient;
+  o.tensor = c->tensor_bound;
+  o.tensor_rows = c->tensor_bound && c->tensor.stride_x == 1;
   o.have_alpha = c->have_alpha;
   o.alpha_capacity = c->alpha.cap;
   o.section_entropy = SectionEntropyForced();
@@ -899,6 +995,7 @@ static void AdoptFrame(JxlHipContext* c, const JxlHipFrameDesc& d, const upload:
   c->plane_bytes = size_t(c->xp) * c->yp * 3 * 4;
   c->color_out = P.px.color_out;
   c->gray8_fast = P.px.gray8_fast;
+  c->tensor_fused = P.px.tensor_fused;
   c->ups_kept = P.px.ups_kept;
   c->ct = d.color_target ? *d.color_target : JxlHipColorTarget{};
   c->has_noise = d.has_noise != 0;
@@ -956,7 +1053,7 @@ static int EnsureWorkBuffers(JxlHipContext* c, const JxlHipFrameDesc& d, const u
   if (c->has_noise && (r = c->noise.Ensure(size_t(c->oxs) * c->oys * 3 * 4))) return r;
   if (((c->has_noise && c->ups != 1) || c->ups_kept) && (r = c->ups_planes.Ensure(size_t((c->oxs + 7) & ~7u) * c->oys * 3 * 4))) return r;
   if (P.px.plane1 && (r = c->plane[1].Ensure(c->plane_bytes))) return r;
-  if ((r = c->rgb.Ensure(size_t(c->oxs) * c->oys * OutPixelBytes(c)))) return r;
+  if (!c->tensor_bound && (r = c->rgb.Ensure(OwnPixelBytes(c)))) return r;
   uint32_t big = 0;  // the largest transforms go through scratch planes, 32 varblocks at a time
   for (int s = 21; s < 27; s++) big = std::max(big, P.list_count[s]);
   if (big && (r = c->scratch.Ensure(size_t(std::min(big, 32u)) * 3 * 2 * 65536 * 4))) return r;
@@ -1079,6 +1176,7 @@ static void FillFilterParams(JxlHipContext* c, const JxlHipFrameDesc& d) {
   }
   memcpy(fp.opsin_inv, d.opsin_inv, sizeof(fp.opsin_inv));
   fp.linear_output = d.linear_output;
+  if (c->tensor_bound) return;  // (no pixel buffer of the context's own: the tensor form reads FusedFilterParams' t_ fields)
   fp.rgb = OutIsRgb8(c) || c->gray8_fast ? c->rgb.as<uint8_t>() : nullptr;
   fp.rgbf = !OutIsRgb8(c) && !c->gray8_fast && !c->color_out ? c->rgb.as<float>() : nullptr;
 }
@@ -1129,8 +1227,9 @@ extern "C" int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   UploadProf prof;
   // 1. whether the descriptor is taken: decided on the host alone, so that a refused one costs no device call and
   // leaves the context's tables as they were (but no frame to run: the caller meant to replace it)
-  const upload::UploadOptions opt = OptionsOf(c);
+  upload::UploadOptions opt = OptionsOf(c);
   int r = upload::CheckFrameDesc(*d, opt);
+  if (!r && c->tensor_bound) r = CheckBoundTensor(c, upload::MakeGeometry(*d, opt), d->num_groups / d->xsize_groups, &opt.tensor_reach);
   upload::Plan P;
   EntropyRoute E = {};
   if (!r) {
@@ -1325,10 +1424,24 @@ static void FillFusedParams(const JxlHipContext* c, jxlhip::FusedFilterParams* p
     p->f.rgb = nullptr;
     p->f.rgbf = nullptr;
   }  // the upsampling / colour kernel produces the pixels
+  if (c->tensor_fused) {  // (PixelRouteOf: three float planes with adjacent columns, every byte offset below 2^31)
+    const JxlHipTensorOut& t = c->tensor;
+    const size_t elem = tensor_out::ElemBytes(t.dtype);
+    p->t_dtype = t.dtype;
+    p->t_data = t.data;
+    p->t_stride_c = uint32_t(uint64_t(t.stride_c) * elem);
+    p->t_stride_y = uint32_t(uint64_t(t.stride_y) * elem);
+    p->t_parity = uint32_t((uintptr_t(t.data) / elem) & 1);
+    p->t_clamp01 = t.clamp01 ? 1 : 0;
+    for (int ch = 0; ch < 3; ch++) {
+      p->t_scale[ch] = t.scale[ch];
+      p->t_bias[ch] = t.bias[ch];
+    }
+  }
 }
 static int FilterKey(const JxlHipContext* c) {
   const int epf = c->epf_iters < 0 ? 0 : (c->epf_iters > 3 ? 3 : c->epf_iters);
-  return (c->gray8_fast ? 8 : 0) + (c->gab ? 4 : 0) + epf;
+  return (c->tensor_fused ? 16 : 0) + (c->gray8_fast ? 8 : 0) + (c->gab ? 4 : 0) + epf;
 }
 // Builds (or re-uses) the description of a set of frames for the batched transform and filter launches.
 static int PrepareDownstream(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n) {
@@ -1425,8 +1538,12 @@ static int LaunchFilterRows(JxlHipContext* c0, const JxlHipContext::FilterGroup&
   const RowsKernel n2t = jxlhip::k_filter_rows2<true, 2, false>, n2f = jxlhip::k_filter_rows2<false, 2, false>;
   const RowsKernel k1g = jxlhip::k_filter_rows2<true, 1, true, true>, k2g = jxlhip::k_filter_rows2<true, 2, true, true>;
   const RowsKernel n1g = jxlhip::k_filter_rows2<true, 1, false, true>, n2g = jxlhip::k_filter_rows2<true, 2, false, true>;
+  const RowsKernel k1x = jxlhip::k_filter_rows2<false, 1, true, false, true>, k2x = jxlhip::k_filter_rows2<false, 2, true, false, true>;
+  const RowsKernel n1x = jxlhip::k_filter_rows2<false, 1, false, false, true>, n2x = jxlhip::k_filter_rows2<false, 2, false, false, true>;
   if (gray && !g.u8srgb) return JXLHIP_ERR_INVALID_ARGUMENT;
-  const RowsKernel k = gray ? (gab ? (epf == 2 ? k2g : k1g) : (epf == 2 ? n2g : n1g))
+  const bool tensor = (g.key & 16) != 0;  // (every frame of the group writes a caller's tensor: FilterKey)
+  const RowsKernel k = tensor ? (gab ? (epf == 2 ? k2x : k1x) : (epf == 2 ? n2x : n1x))
+                       : gray ? (gab ? (epf == 2 ? k2g : k1g) : (epf == 2 ? n2g : n1g))
                        : gab ? (epf == 2 ? (g.u8srgb ? k2t : k2f) : (g.u8srgb ? k1t : k1f))
                              : (epf == 2 ? (g.u8srgb ? n2t : n2f) : (g.u8srgb ? n1t : n1f));
   for (uint32_t z = 0; z < g.count; z += 65535) {  // grid z limit
@@ -2136,7 +2253,7 @@ static int EnsureModBuffers(JxlHipContext* c, const JxlHipModFrameDesc& d, const
   if ((r = M.scratch.Ensure((P.scratch_ints + 4) * 4))) return r;
   if ((r = M.windows.Ensure((P.window_words + 4) * 4))) return r;
   if ((r = M.streams.Ensure(std::max<size_t>(16, size_t(d.num_streams) * sizeof(jxlhip::ModStream))))) return r;
-  if ((r = c->rgb.Ensure(size_t(c->oxs) * c->oys * OutPixelBytes(c)))) return r;
+  if (!c->tensor_bound && (r = c->rgb.Ensure(OwnPixelBytes(c)))) return r;
   if (P.float_planes && (r = c->spl_planes.Ensure(size_t(d.xsize) * d.ysize * 3 * 4))) return r;
   return 0;
 }
@@ -2190,6 +2307,10 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
   int r = upload::CheckModFrameDesc(*d, opt);
   c->mod.have = false;
   c->have_frame = false;
+  if (!r && c->tensor_bound) {  // (the bound tensor against the image's size, which a transposing orientation turns)
+    const bool transposed = (c->out_orient & 4) != 0;
+    r = tensor_out::CheckTensorOut(c->tensor, transposed ? d->ysize : d->xsize, transposed ? d->xsize : d->ysize);
+  }
   if (r) return r;
   const upload::ModPlan P = upload::MakeModPlan(*d, opt);
   // 2. the tables are overwritten on the context's stream, behind whatever still reads the old ones
@@ -2286,15 +2407,11 @@ static bool FillModOutput(const JxlHipContext* c, jxlhip::ModOutput* o) {  // (e
   o->alpha_bits = M.alpha_bits;
   o->w = M.xs;
   o->h = M.ys;
-  o->po.dst = c->rgb.p;
   o->po.alpha = nullptr;
   o->po.xsize = M.xs;
   o->po.ysize = M.ys;
   o->po.orient = c->out_orient | (c->out_unpremul ? 8u : 0u);
-  o->po.type = c->out_type;
-  o->po.nc = c->out_nc;
-  o->po.bits = c->out_bits;
-  o->po.swap = c->out_swap;
+  FillPixelOutLayout(c, &o->po);
   return true;
 }
 // One pass over the frames of a set that take it: a zeroed block each, one launch. `rows`: one workgroup per row (the
@@ -2359,7 +2476,7 @@ extern "C" int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n) {
   for (size_t i = 0; i < n; i++) {
     if (!ctxs[i] || ctxs[i]->device != c0->device) return JXLHIP_ERR_INVALID_ARGUMENT;
     if (!ctxs[i]->mod.have) return JXLHIP_ERR_NO_FRAME;
-    if (size_t(ctxs[i]->oxs) * ctxs[i]->oys * OutPixelBytes(ctxs[i]) > ctxs[i]->rgb.cap) return JXLHIP_ERR_INVALID_ARGUMENT;
+    if (OwnPixelBytes(ctxs[i]) > ctxs[i]->rgb.cap) return JXLHIP_ERR_INVALID_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(c0->device));
   if (n > 1) {
@@ -2417,6 +2534,10 @@ extern "C" int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n) {
     HIP_TRY(hipEventRecord(ctxs[i]->down_done, ctxs[i]->stream));
     HIP_TRY(hipStreamWaitEvent(c0->stream, ctxs[i]->down_done, 0));
   }
+  {
+    const int tw = TensorsBeforeWriters(ctxs, n, c0->stream);
+    if (tw) return tw;
+  }
   HIP_TRY(hipEventRecord(c0->ev[0], c0->stream));
   if (M0.batch_n) {
     // A stream is a chain of dependent latencies: as few streams per wave as still leaves every SIMD of the device a
@@ -2440,6 +2561,10 @@ extern "C" int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n) {
     if (r) return r;
   }
   HIP_TRY(hipEventRecord(c0->ev[1], c0->stream));
+  {
+    const int tw = TensorsAfterWriters(ctxs, n, c0->stream);
+    if (tw) return tw;
+  }
   c0->ev_valid[0] = true;
   if (n > 1) {
     if (!c0->batch_done) HIP_TRY(hipEventCreateWithFlags(&c0->batch_done, hipEventDisableTiming));
@@ -2505,9 +2630,11 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
   if (r) return r;
   JxlHipContext* c0 = ctxs[0];
   const hipStream_t ls = c0->fstream;
+  if ((r = TensorsBeforeWriters(ctxs, n, ls))) return r;
   HIP_TRY(hipEventRecord(c0->ev[4], ls));
   for (const JxlHipContext::FilterGroup& g : c0->fgroups) {
     const bool gray = (g.key & 8) != 0;  // (only frames of the row-streaming kernel: set at upload)
+    if ((g.key & 16) && (g.key & 3) != 1 && (g.key & 3) != 2) return JXLHIP_ERR_INVALID_ARGUMENT;  // (the tensor form is the row-streaming kernel's)
     switch (g.key & 7) {
       case 0: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<false, 0>(c0, g); break;
       case 1: r = LaunchFilterRows(c0, g, 1, false, gray); break;
@@ -2602,15 +2729,11 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
     jxlhip::PixelOut po;
     memset(&po, 0, sizeof(po));
     if (c->color_out) {
-      po.dst = c->rgb.p;
       po.alpha = c->have_alpha ? (c->alpha_patched_valid ? c->alpha_patched.as<float>() : c->alpha.as<float>()) : nullptr;
       po.xsize = c->oxs;
       po.ysize = c->oys;
       po.orient = c->out_orient | (c->out_unpremul ? 8u : 0u);
-      po.type = c->out_type;
-      po.nc = c->out_nc;
-      po.bits = c->out_bits;
-      po.swap = c->out_swap;
+      FillPixelOutLayout(c, &po);
     }
     if (c->ups == 1) {
       jxlhip::ColorOutParams cp;
@@ -2679,6 +2802,7 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
     }
   }
   HIP_TRY(hipEventRecord(c0->ev[5], ls));
+  if ((r = TensorsAfterWriters(ctxs, n, ls))) return r;
   c0->ev_valid[2] = true;
   for (size_t i = 0; i < n; i++) ctxs[i]->final_plane = 1;
   for (size_t i = 1; i < n; i++) ctxs[i]->ev_valid[2] = false;
@@ -2867,6 +2991,23 @@ int jxlhip_set_output_format(JxlHipContext* c, uint32_t data_type, uint32_t num_
   return 0;
 }
 
+int jxlhip_set_output_tensor(JxlHipContext* c, const JxlHipTensorOut* t) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (t) {  // what can be said without an image (one pixel); the upload checks again at the image's size
+    const int r = tensor_out::CheckTensorOut(*t, 1, 1);
+    if (r) return r;
+    c->tensor = *t;
+  } else {
+    c->tensor = JxlHipTensorOut{};
+  }
+  c->tensor_bound = t != nullptr;
+  c->tensor_fused = false;
+  c->have_frame = false;  // (a frame uploaded for the other destination has no writer for this one: upload again)
+  c->mod.have = false;
+  c->generation++;  // cached batch descriptions hold the pixel pointers
+  return 0;
+}
+
 int jxlhip_set_output_orientation(JxlHipContext* c, uint32_t orientation) {
   if (!c || orientation < 1 || orientation > 8) return JXLHIP_ERR_INVALID_ARGUMENT;
   // EXIF numbering -> mirror x (1) | mirror y (2) | transpose (4): stage_write.cc:441-458
@@ -2950,7 +3091,7 @@ int jxlhip_upsample_plane(JxlHipContext* c, const float* plane, uint32_t xsize, 
 }
 
 int jxlhip_download_pixels(JxlHipContext* c, void* dst, size_t stride) {
-  if (!c || !dst) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c || !dst || c->tensor_bound) return JXLHIP_ERR_INVALID_ARGUMENT;  // (a bound tensor holds the pixels, not the context)
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   const bool transposed = (c->out_orient & 4) != 0;  // rows of the output are columns of the image
   const size_t row = size_t(transposed ? c->oys : c->oxs) * OutPixelBytes(c), rows = transposed ? c->oxs : c->oys;
@@ -3008,6 +3149,7 @@ static int DebugColor(JxlHipContext* c, const float* xyb, size_t n, int linear_o
     cp.po.type = 0;
     cp.po.nc = 3;
     cp.po.bits = 32;
+    jxlhip::SetInterleaved(&cp.po, cp.po.xsize);
     hipLaunchKernelGGL(jxlhip::k_color_out, dim3(uint32_t((n + 63) / 64), 1), dim3(256), 0, c->stream, cp);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -3081,7 +3223,7 @@ int jxlhip_debug_noise(JxlHipContext* c, const float* xyb, uint32_t xsize, uint3
 int jxlhip_debug_pixel_route(JxlHipContext* c, uint32_t* route) {
   if (!c || !route) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
-  *route = c->color_out || c->ups != 1 ? 0u : (c->gray8_fast ? 2u : 1u);
+  *route = c->color_out || c->ups != 1 ? 0u : (c->tensor_fused ? 3u : (c->gray8_fast ? 2u : 1u));
   return 0;
 }
 
@@ -3144,7 +3286,7 @@ int jxlhip_sync(JxlHipContext* c) {
 }
 
 int jxlhip_download_rgb8(JxlHipContext* c, uint8_t* dst, size_t stride) {
-  if (!c || !dst) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c || !dst || c->tensor_bound) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   if (stride < size_t(c->oxs) * 3 || !OutIsRgb8(c)) return JXLHIP_ERR_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
@@ -3158,7 +3300,7 @@ int jxlhip_download_rgb8(JxlHipContext* c, uint8_t* dst, size_t stride) {
 }
 
 int jxlhip_download_rgb8_rows(JxlHipContext* c, uint8_t* dst, size_t stride, uint32_t y_begin, uint32_t y_end) {
-  if (!c || !dst) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c || !dst || c->tensor_bound) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   if (stride < size_t(c->oxs) * 3 || y_begin >= y_end || y_end > c->oys || !OutIsRgb8(c)) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (c->out_orient & 4) return JXLHIP_ERR_INVALID_ARGUMENT;  // a transposed output has other rows: jxlhip_download_pixels
@@ -3173,7 +3315,7 @@ int jxlhip_download_rgb8_rows(JxlHipContext* c, uint8_t* dst, size_t stride, uin
   return 0;
 }
 
-const uint8_t* jxlhip_rgb8_device_ptr(JxlHipContext* c) { return c && c->have_frame ? c->rgb.as<uint8_t>() : nullptr; }
+const uint8_t* jxlhip_rgb8_device_ptr(JxlHipContext* c) { return c && c->have_frame && !c->tensor_bound ? c->rgb.as<uint8_t>() : nullptr; }
 
 int jxlhip_get_errors(JxlHipContext* c, uint32_t* flags, size_t n) {
   if (!c || !flags) return JXLHIP_ERR_INVALID_ARGUMENT;
@@ -3341,6 +3483,7 @@ void jxlhip_canvas_destroy(JxlHipCanvas* v) {
 
 int jxlhip_canvas_save_xyb(JxlHipCanvas* v, JxlHipContext* c, uint32_t slot) {
   if (!v || !c || slot > 7 || c->device != v->device) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->tensor_bound) return JXLHIP_ERR_UNSUPPORTED;  // (composed frames keep the context's own buffers)
   HIP_TRY(hipSetDevice(v->device));
   {
     int pw = ApplyPendingWait(c);
@@ -3411,6 +3554,7 @@ int jxlhip_canvas_xyb_alpha(JxlHipCanvas* v, uint32_t slot, const float** alpha)
 int jxlhip_canvas_blend(JxlHipCanvas* v, JxlHipContext* c, const JxlHipBlend* b) {
   if (!v || !c || !b || c->device != v->device) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (b->mode > 4 || b->alpha_mode > 4 || b->source > 3 || b->alpha_source > 3 || b->save_slot > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->tensor_bound) return JXLHIP_ERR_UNSUPPORTED;  // (the frame's pixels are in the caller's tensor, not in c->rgb)
   if (!c->have_frame && !c->mod.have) return JXLHIP_ERR_NO_FRAME;
   if (c->out_type != 0 || c->out_nc != 4 || c->out_swap || c->out_orient) return JXLHIP_ERR_INVALID_ARGUMENT;  // f32 x 4 as coded
   if (size_t(c->oxs) * c->oys * 16 > c->rgb.cap) return JXLHIP_ERR_INVALID_ARGUMENT;
@@ -3660,6 +3804,7 @@ int jxlhip_canvas_download(JxlHipCanvas* v, uint32_t data_type, uint32_t num_cha
   po.nc = num_channels;
   po.bits = (data_type == 2 || data_type == 3) ? (bits && bits < full ? bits : full) : 0;
   po.swap = big_endian && sample > 1;
+  jxlhip::SetInterleaved(&po, (po.orient & 4) ? po.ysize : po.xsize);
   hipStream_t st = v->last_stream;
   hipLaunchKernelGGL(jxlhip::k_canvas_out, dim3((v->xs + 255) / 256, v->ys), dim3(256), 0, st, static_cast<const float*>(v->cur.as<float>()), po);
   HIP_TRY(hipGetLastError());

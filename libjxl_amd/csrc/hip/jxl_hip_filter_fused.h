@@ -31,6 +31,14 @@ struct FusedFilterParams {
   float sm[3], bsm[3];     // per EPF stage (0, 1, 2): sigma multipliers for block-interior / block-border pixels
   float* filtered;         // optional (may be NULL): filtered XYB planes for tests (same geometry as f.in)
   uint32_t debug;          // measurement aid (results invalid when set): bit 0 skip Gaborish, 1 skip EPF, 2 skip colour maths
+  // k_filter_rows2's tensor form only (jxlhip_set_output_tensor; no other kernel reads them): three planes of rows whose
+  // columns are adjacent elements. Strides in BYTES; every offset the image reaches is below 2^31 (PixelRouteOf).
+  uint32_t t_dtype;        // PixelOut::type numbering: 0 f32, 5 f16, kTypeBf16
+  void* t_data;
+  uint32_t t_stride_c, t_stride_y;
+  uint32_t t_parity;       // element index of t_data itself, mod 2: pairs are stored whole where the element index is even
+  uint32_t t_clamp01;
+  float t_scale[3], t_bias[3];
 };
 
 constexpr int kFusedTW = 64, kFusedTH = 16;  // 37 KB of LDS with a 3-pixel halo: two tiles fit beside an entropy workgroup
@@ -493,10 +501,16 @@ __device__ __forceinline__ P2 BufP2(__amdgpu_buffer_rsrc_t r, uint32_t voff, uin
 // colour stage alone (for a grey image, whose matrix has three equal rows, the pixel: dec_xyb.cc:228-232, stage_write.cc
 // num_color_ = 1). The filters are the same, all three XYB channels feed their sums; of the colour stage one matrix row, one
 // curve and one dither cell are left, spelled as in the RGB form, so the samples equal the RGB form's red channel bit for bit.
-template <bool U8SRGB, int EPF = 1, bool GAB = true, bool GREY = false>
+// TENSOR (without U8SRGB): the launch's frames all write a caller's planar tensor and nothing else (jxlhip_set_output_tensor:
+// f32, f16 or bf16, three planes whose rows hold adjacent columns). The samples are the float writer's, bit for bit: the
+// same matrix and Srgb2, then TensorAffine per channel. A lane stores its two pixels of a plane together (8 bytes of f32, a
+// packed pair of 16-bit types) where the pair's element index is even, and one by one where it is odd (every second row of
+// a contiguous tensor of odd width) or the second pixel lies outside the frame.
+template <bool U8SRGB, int EPF = 1, bool GAB = true, bool GREY = false, bool TENSOR = false>
 __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFilterParams* params, int strip_rows) {
   static_assert(EPF == 1 || EPF == 2, "(Gaborish +) one or two EPF iterations");
   static_assert(U8SRGB || !GREY, "the one-channel writer exists for 8-bit sRGB only");
+  static_assert(!TENSOR || !U8SRGB, "the tensor writer stores the float writer's samples");
   constexpr int HALO = kRowsHalo + (EPF == 2 ? 1 : 0);
   FusedFilterParams P;
   LoadParams(P, params + blockIdx.z);
@@ -528,9 +542,13 @@ __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFil
   const __amdgpu_buffer_rsrc_t in_buf = RawBuffer(P.f.in), sig_buf = RawBuffer(P.f.inv_sigma);
   const __amdgpu_buffer_rsrc_t dither_buf = RawBuffer(c_dither), rgb_buf = RawBuffer(P.f.rgb);
   const uint32_t plane_bytes = uint32_t(gplane * 4);  // (three planes of at most 1 GiB: offsets fit 32 bits)
-  const GF32W filtered = U8SRGB ? nullptr : (GF32W)(uintptr_t)P.filtered;
-  const bool has_rgb = U8SRGB || P.f.rgb != nullptr;
-  const GF32W rgbf = U8SRGB ? nullptr : (GF32W)(uintptr_t)P.f.rgbf;
+  const GF32W filtered = U8SRGB || TENSOR ? nullptr : (GF32W)(uintptr_t)P.filtered;
+  const bool has_rgb = U8SRGB || (!TENSOR && P.f.rgb != nullptr);
+  const GF32W rgbf = U8SRGB || TENSOR ? nullptr : (GF32W)(uintptr_t)P.f.rgbf;
+  // TENSOR: the lane's column in bytes (f32: 4 per element, else 2) and the buffer over the caller's memory
+  const uint32_t t_f32 = TENSOR ? uint32_t(P.t_dtype == 0) : 0u;
+  const uint32_t vten = TENSOR ? uint32_t(x) << (t_f32 ? 2 : 1) : 0u;
+  const __amdgpu_buffer_rsrc_t ten_buf = RawBuffer(TENSOR ? P.t_data : nullptr);
   const bool linear_output = U8SRGB ? false : P.f.linear_output != 0;
   const P2 zero2 = P2{0.0f, 0.0f};
   // sliding windows as rings of 4 rows indexed with the step's phase (the row loop is unrolled by 4): a window shift is a
@@ -733,7 +751,11 @@ __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFil
             if (emit1) filtered[c * gplane + gi + 1] = o[c].y;
           }
         }
-        if (has_rgb || rgbf) {
+        if (has_rgb || rgbf || TENSOR) {
+          // (the general form reaches this point through a branch on its runtime destinations, so the filters' last
+          // multiplications never contract into the colour stage's first additions; here the test is constant, and without
+          // this fence they do, which moves a sample by an ulp of float32 now and then)
+          if constexpr (TENSOR) asm volatile("" : "+v"(o[0].x), "+v"(o[0].y), "+v"(o[1].x), "+v"(o[1].y), "+v"(o[2].x), "+v"(o[2].y));
           const P2 X = o[0], Y = o[1], Bc = o[2];
           const P2 gr = (Y + X) - P.f.opsin_bias_cbrt[0], gg = (Y - X) - P.f.opsin_bias_cbrt[1], gb = Bc - P.f.opsin_bias_cbrt[2];
           const P2 mr = (gr * gr) * gr + P.f.opsin_bias[0], mg = (gg * gg) * gg + P.f.opsin_bias[1], mb = (gb * gb) * gb + P.f.opsin_bias[2];
@@ -757,7 +779,45 @@ __global__ __launch_bounds__(64 * kRowsWaves) void k_filter_rows2(const FusedFil
           P2 cg = P.f.opsin_inv[5] * mb + (P.f.opsin_inv[4] * mg + P.f.opsin_inv[3] * mr);
           P2 cb = P.f.opsin_inv[8] * mb + (P.f.opsin_inv[7] * mg + P.f.opsin_inv[6] * mr);
           const bool even = ((r & xs) & 1) == 0;  // (r * xs + x) * 3 with x even: the row's parity decides the alignment
-          if (!U8SRGB && rgbf) {  // float output (stage_write.cc:334-370): the samples as they are
+          if constexpr (TENSOR) {
+            if (!linear_output) {
+              cr = Srgb2(cr);
+              cg = Srgb2(cg);
+              cb = Srgb2(cb);
+            }
+            const P2 ch[3] = {cr, cg, cb};
+            const uint32_t trow = uint32_t(r) * P.t_stride_y;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+              const float tx = TensorAffine(ch[c].x, P.t_scale[c], P.t_bias[c], P.t_clamp01);
+              const float ty = TensorAffine(ch[c].y, P.t_scale[c], P.t_bias[c], P.t_clamp01);
+              const uint32_t so = trow + uint32_t(c) * P.t_stride_c;  // scalar: the row of plane c, in bytes
+              // x is even: the parity of the pair's element index is that of the row's first element
+              const bool whole = emit1 && (((so >> (t_f32 ? 2 : 1)) + P.t_parity) & 1u) == 0;
+              if (t_f32) {
+                typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+                if (whole) {
+                  __builtin_amdgcn_raw_buffer_store_b64(u2{__float_as_uint(tx), __float_as_uint(ty)}, ten_buf, vten, so, 0);
+                } else {
+                  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tx), ten_buf, vten, so, 0);
+                  if (emit1) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ty), ten_buf, vten + 4, so, 0);
+                }
+              } else {
+                // one packed round-to-nearest-even conversion of the pair (v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32)
+                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+                typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+                const f2 pair = f2{tx, ty};
+                const uint32_t w = P.t_dtype == 5 ? __builtin_bit_cast(uint32_t, __builtin_convertvector(pair, h2))
+                                                  : __builtin_bit_cast(uint32_t, __builtin_convertvector(pair, b2));
+                if (whole) {
+                  __builtin_amdgcn_raw_buffer_store_b32(w, ten_buf, vten, so, 0);
+                } else {
+                  __builtin_amdgcn_raw_buffer_store_b16(uint16_t(w), ten_buf, vten, so, 0);
+                  if (emit1) __builtin_amdgcn_raw_buffer_store_b16(uint16_t(w >> 16), ten_buf, vten + 2, so, 0);
+                }
+              }
+            }
+          } else if (!U8SRGB && rgbf) {  // float output (stage_write.cc:334-370): the samples as they are
             if (!linear_output) {
               cr = Srgb2(cr);
               cg = Srgb2(cg);

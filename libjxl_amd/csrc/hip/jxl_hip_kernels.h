@@ -1543,7 +1543,7 @@ struct FilterParams {
 // Every output format of the boundary (JxlPixelFormat; stage_write.cc:266-286,334-370,548-590): written by k_color_out
 // and k_upsample_color. `type` uses the JxlDataType values (0 f32, 2 u8, 3 u16, 5 f16).
 struct PixelOut {
-  void* dst;           // interleaved, tightly packed rows of samples
+  void* dst;           // the context's interleaved, tightly packed rows of samples, or the caller's tensor
   const float* alpha;  // plane of the image size in [0, 1], or NULL (opaque)
   uint32_t xsize, type, nc, bits, swap;  // bits: sample depth of the unsigned types; swap: byte-swapped (big endian) samples
   // Undoing the image's orientation (stage_write.cc:292-306,341-343,441-458,664-699): bit 0 = mirror x, bit 1 = mirror y,
@@ -1551,13 +1551,28 @@ struct PixelOut {
   // Bit 3: the colour samples of a pixel with alpha are divided by max(alpha, 2^-26) on the way out (JxlDecoderSetUnpremultiplyAlpha
   // on an image whose alpha is associated: stage_write.cc:359-361,460-482, after the transfer function as there).
   uint32_t orient, ysize;
+  // Sample c of output pixel (row, column) is element c * stride_c + row * stride_y + column * stride_x of dst. The
+  // context's own buffer: 1, row length * nc, nc. A tensor (jxlhip_set_output_tensor): the caller's strides, `type` may
+  // also be kTypeBf16, and tensor != 0 makes float samples v -> [clamp to 0..1] -> v * scale[c] -> + bias[c] (TensorAffine).
+  int64_t stride_c, stride_y, stride_x;
+  uint32_t tensor, clamp01;
+  float scale[4], bias[4];
 };
-// Where pixel (x, y) of the decoded image goes and which dither cell it takes (the reference dithers after the flips).
+constexpr uint32_t kTypeBf16 = 6;  // JXLHIP_TENSOR_BF16 (the other types are JxlDataType values)
+// The strides of interleaved, tightly packed rows of `row_pixels` pixels (o->nc set).
+inline void SetInterleaved(PixelOut* o, uint32_t row_pixels) {
+  o->stride_c = 1;
+  o->stride_x = o->nc;
+  o->stride_y = int64_t(row_pixels) * o->nc;
+}
+// Where pixel (x, y) of the decoded image goes (the element of its sample 0) and which dither cell it takes (the reference
+// dithers after the flips). Transposed orientations: the output's rows are the image's columns.
 __device__ __forceinline__ size_t PixelOutIndex(const PixelOut& o, int x, int y, int* dx, int* dy) {
   const int ox = (o.orient & 1) ? int(o.xsize) - 1 - x : x, oy = (o.orient & 2) ? int(o.ysize) - 1 - y : y;
   *dx = ox;
   *dy = oy;
-  return (o.orient & 4) ? size_t(ox) * o.ysize + oy : size_t(oy) * o.xsize + ox;
+  return (o.orient & 4) ? size_t(ox) * size_t(o.stride_y) + size_t(oy) * size_t(o.stride_x)
+                        : size_t(oy) * size_t(o.stride_y) + size_t(ox) * size_t(o.stride_x);
 }
 
 __device__ __forceinline__ int MirrorI(int x, int n) {
@@ -1591,9 +1606,51 @@ __device__ __forceinline__ uint8_t ToU8(float v, int x, int y, int c) {
   return ToU8D(v, c_dither[((y + c * 13) & 31) * 32 + ((x + c * 23) & 31)]);
 }
 
+// A tensor's float sample from the writer's float (jxlhip_set_output_tensor): clamp if asked, then Mul, then Add, each
+// rounded, never fused, so that one line of NumPy reproduces the bits (-0.0f * 1 + 0 is +0.0f: scale 1 / bias 0 is no identity).
+__device__ __forceinline__ float TensorAffine(float v, float scale, float bias, uint32_t clamp01) {
+#pragma clang fp contract(off)
+  if (clamp01) v = __builtin_fminf(__builtin_fmaxf(v, 0.0f), 1.0f);
+  const float t = v * scale;
+  return t + bias;
+}
+// float -> bfloat16 bits, round to nearest even (gfx950 converts in hardware: v_cvt_pk_bf16_f32; a NaN stays a NaN)
+__device__ __forceinline__ uint32_t Bf16Bits(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
+// Sample c of a pixel, float f, to element `index` of the output in its format: the one statement of the format switch
+// (StorePixel, k_modular_output). 8-bit samples are dithered with the channel's interleave index at the oriented position
+// (dx, dy) (stage_write.cc:266-286), wider ones are not.
+__device__ __forceinline__ void StoreSample(const PixelOut& o, size_t index, uint32_t c, float f, int dx, int dy) {
+  if (o.type == 2) {
+#pragma clang fp contract(off)  // Mul, then Add the dither, each rounded (stage_write.cc MakeUnsigned): no FMA
+    const float mul = float((1u << o.bits) - 1u);
+    const float t = __builtin_amdgcn_fmed3f(f * mul + c_dither[((dy + int(c) * 13) & 31) * 32 + ((dx + int(c) * 23) & 31)], 0.0f, mul);
+    static_cast<uint8_t*>(o.dst)[index] = uint8_t(__float2int_rn(t));
+    return;
+  }
+  if (o.type == 3) {
+    const float mul = float((1u << o.bits) - 1u);
+    uint32_t u = uint32_t(__float2int_rn(__builtin_amdgcn_fmed3f(f * mul, 0.0f, mul)));
+    if (o.swap) u = ((u & 0xFF) << 8) | (u >> 8);
+    static_cast<uint16_t*>(o.dst)[index] = uint16_t(u);
+    return;
+  }
+  if (o.tensor) f = TensorAffine(f, c == 0 ? o.scale[0] : (c == 1 ? o.scale[1] : (c == 2 ? o.scale[2] : o.scale[3])),
+                                 c == 0 ? o.bias[0] : (c == 1 ? o.bias[1] : (c == 2 ? o.bias[2] : o.bias[3])), o.clamp01);
+  if (o.type == 5) {
+    uint32_t u = __half_as_ushort(__float2half_rn(f));
+    if (o.swap) u = ((u & 0xFF) << 8) | (u >> 8);
+    static_cast<uint16_t*>(o.dst)[index] = uint16_t(u);
+  } else if (o.type == kTypeBf16) {
+    static_cast<uint16_t*>(o.dst)[index] = uint16_t(Bf16Bits(f));
+  } else {
+    uint32_t u = __float_as_uint(f);
+    if (o.swap) u = __builtin_bswap32(u);
+    static_cast<uint32_t*>(o.dst)[index] = u;
+  }
+}
+
 // One pixel in any output format. Colour images hand out R (and alpha) when fewer than three channels are asked for,
-// like the reference (stage_write.cc:334-370: num_color_ = 1); 8-bit samples are dithered with the channel's interleave
-// index (stage_write.cc:266-286), wider ones are not.
+// like the reference (stage_write.cc:334-370: num_color_ = 1).
 constexpr float kSmallAlphaOut = 1.0f / float(1u << 26);  // alpha.h:22 kSmallAlpha
 __device__ __forceinline__ void StorePixel(const PixelOut& o, int x, int y, float r, float g, float b) {
   const uint32_t nc = o.nc, ncol = nc < 3 ? 1u : 3u;
@@ -1607,29 +1664,8 @@ __device__ __forceinline__ void StorePixel(const PixelOut& o, int x, int y, floa
     }
   }
   int dx, dy;
-  const size_t base = PixelOutIndex(o, x, y, &dx, &dy) * nc;
-  for (uint32_t c = 0; c < nc; c++) {
-    const float f = v[c];
-    if (o.type == 2) {
-#pragma clang fp contract(off)  // Mul, then Add the dither, each rounded (stage_write.cc MakeUnsigned): no FMA
-      const float mul = float((1u << o.bits) - 1u);
-      const float t = __builtin_amdgcn_fmed3f(f * mul + c_dither[((dy + int(c) * 13) & 31) * 32 + ((dx + int(c) * 23) & 31)], 0.0f, mul);
-      static_cast<uint8_t*>(o.dst)[base + c] = uint8_t(__float2int_rn(t));
-    } else if (o.type == 3) {
-      const float mul = float((1u << o.bits) - 1u);
-      uint32_t u = uint32_t(__float2int_rn(__builtin_amdgcn_fmed3f(f * mul, 0.0f, mul)));
-      if (o.swap) u = ((u & 0xFF) << 8) | (u >> 8);
-      static_cast<uint16_t*>(o.dst)[base + c] = uint16_t(u);
-    } else if (o.type == 5) {
-      uint32_t u = __half_as_ushort(__float2half_rn(f));
-      if (o.swap) u = ((u & 0xFF) << 8) | (u >> 8);
-      static_cast<uint16_t*>(o.dst)[base + c] = uint16_t(u);
-    } else {
-      uint32_t u = __float_as_uint(f);
-      if (o.swap) u = __builtin_bswap32(u);
-      static_cast<uint32_t*>(o.dst)[base + c] = u;
-    }
-  }
+  const size_t base = PixelOutIndex(o, x, y, &dx, &dy);
+  for (uint32_t c = 0; c < nc; c++) StoreSample(o, base + size_t(c) * size_t(o.stride_c), c, v[c], dx, dy);
 }
 
 }  // namespace jxlhip

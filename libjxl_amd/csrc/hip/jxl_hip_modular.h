@@ -800,29 +800,8 @@ __global__ __launch_bounds__(256) void k_modular_output(const ModOutput* ops) {
     }
   }
   int dx, dy;
-  const size_t base = PixelOutIndex(P.po, int(x), int(y), &dx, &dy) * nc;
-  for (uint32_t c = 0; c < nc; c++) {
-    const float f = s[c];
-    if (P.po.type == 2) {
-#pragma clang fp contract(off)  // Mul, then Add the dither, each rounded (stage_write.cc MakeUnsigned): no FMA
-      const float m = float((1u << P.po.bits) - 1u);
-      const float t = __builtin_amdgcn_fmed3f(f * m + c_dither[((uint32_t(dy) + c * 13) & 31) * 32 + ((uint32_t(dx) + c * 23) & 31)], 0.0f, m);
-      static_cast<uint8_t*>(P.po.dst)[base + c] = uint8_t(__float2int_rn(t));
-    } else if (P.po.type == 3) {
-      const float m = float((1u << P.po.bits) - 1u);
-      uint32_t u = uint32_t(__float2int_rn(__builtin_amdgcn_fmed3f(f * m, 0.0f, m)));
-      if (P.po.swap) u = ((u & 0xFF) << 8) | (u >> 8);
-      static_cast<uint16_t*>(P.po.dst)[base + c] = uint16_t(u);
-    } else if (P.po.type == 5) {
-      uint32_t u = __half_as_ushort(__float2half_rn(f));
-      if (P.po.swap) u = ((u & 0xFF) << 8) | (u >> 8);
-      static_cast<uint16_t*>(P.po.dst)[base + c] = uint16_t(u);
-    } else {
-      uint32_t u = __float_as_uint(f);
-      if (P.po.swap) u = __builtin_bswap32(u);
-      static_cast<uint32_t*>(P.po.dst)[base + c] = u;
-    }
-  }
+  const size_t base = PixelOutIndex(P.po, int(x), int(y), &dx, &dy);
+  for (uint32_t c = 0; c < nc; c++) StoreSample(P.po, base + size_t(c) * size_t(P.po.stride_c), c, s[c], dx, dy);
   }
 }
 

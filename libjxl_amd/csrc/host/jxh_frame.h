@@ -176,6 +176,15 @@ class FrameParser {
     return codestream_base_ + br.BitPos() / 8;
   }
 
+  // Whether the frame that starts at byte `pos` is Modular-coded (ModFrameParser's) or VarDCT (ParseFrame's): its header alone.
+  bool FrameIsModular(size_t pos, const ImageHeader& ih) {
+    BitReader br(data_ + pos, codestream_base_ + cs_size_ - pos);
+    FrameHeader fh;
+    ReadFrameHeader(br, ih, &fh);
+    JXH_CHECK(!br.Overread(), "truncated frame header");
+    return fh.modular;
+  }
+
   // Parses the frame that starts at byte `pos` of the buffer. Throws jxh::Error for unsupported streams.
   // frame_index / nonvisible_index: the shown frames before this one and the invisible ones since (dec_frame.cc:160-168;
   // they seed the noise). The plan is of the frame at its own size: where it sits on the canvas and how it blends with

@@ -29,6 +29,11 @@ struct UploadOptions {
   size_t alpha_capacity = 0;     // bytes of the alpha plane that was set
   bool section_entropy = false;  // JXLHIP_ENTROPY=1: no frame takes the lane kernel
   bool no_lane_prefix = false;   // JXLHIP_NO_LANE_PREFIX
+  // jxlhip_set_output_tensor: the pixels go to a caller's tensor (out_type / out_nc then describe it; out_type may be
+  // JXLHIP_TENSOR_BF16). tensor_rows: its columns are adjacent elements (stride_x 1); tensor_reach: bytes from its first
+  // element to behind the last one the frame's image reaches. The defaults mean "no tensor".
+  bool tensor = false, tensor_rows = false;
+  uint64_t tensor_reach = 0;
 };
 inline bool OutIsRgb8(uint32_t type, uint32_t nc, uint32_t bits) { return type == 2 && nc == 3 && bits == 8; }
 inline bool OutIsGray8(uint32_t type, uint32_t nc, uint32_t bits) { return type == 2 && nc == 1 && bits == 8; }
@@ -349,25 +354,34 @@ struct PixelRoute {
   bool gray8_fast;  // one 8-bit sRGB channel from k_filter_rows2's one-channel form (the filtered planes are not kept beside it)
   bool ups_kept;    // (tests) the upsampled planes are kept: the route of a noisy upsampled frame without the noise
   bool plane1;      // the second plane set is needed
+  bool tensor_fused = false;  // a caller's planar float tensor from k_filter_rows2's tensor form
 };
 inline PixelRoute PixelRouteOf(const JxlHipFrameDesc& d, const UploadOptions& o) {
   const uint32_t ups = d.upsampling > 1 ? d.upsampling : 1;
-  const bool rgb8 = OutIsRgb8(o.out_type, o.out_nc, o.out_bits), g8 = OutIsGray8(o.out_type, o.out_nc, o.out_bits);
+  // (a tensor is never the context's own RGB8 / one-channel rows, whatever its type)
+  const bool rgb8 = !o.tensor && OutIsRgb8(o.out_type, o.out_nc, o.out_bits), g8 = !o.tensor && OutIsGray8(o.out_type, o.out_nc, o.out_bits);
   const bool rows_kernel = ups == 1 && (d.epf_iters == 1 || d.epf_iters == 2);
 #ifdef JXLHIP_NO_GRAY8_ROWS  // (scripts/measure_grey_xyb.py: the comparison build, one 8-bit channel from the generic writer)
   const bool gray8 = false;
 #else
   const bool gray8 = g8 && rows_kernel && d.linear_output == 0 && !o.keep_filtered;
 #endif
+  // The frame would get RGB f32 from the row-streaming kernel, and the tensor is three planes of a float type whose rows
+  // the kernel's 32-bit offsets reach (that form writes nothing else: kept filtered planes go through the generic writer).
+  const bool float_type = o.out_type == JXLHIP_TENSOR_F32 || o.out_type == JXLHIP_TENSOR_F16 || o.out_type == JXLHIP_TENSOR_BF16;
+  const bool tensor_rows = o.tensor && float_type && o.out_nc == 3 && o.tensor_rows && o.tensor_reach < (uint64_t(1) << 31) &&
+                           rows_kernel && !o.keep_filtered;
+  const bool rgbf32 = !o.tensor && OutIsRgbF32(o.out_type, o.out_nc, o.out_swap) && rows_kernel;
   PixelRoute r;
   r.ups_kept = o.keep_upsampled && ups != 1;
-  r.color_out = (!rgb8 && !gray8 && !(OutIsRgbF32(o.out_type, o.out_nc, o.out_swap) && rows_kernel)) ||
+  r.color_out = (!rgb8 && !gray8 && !rgbf32 && !tensor_rows) ||
                 o.out_orient ||                               // the oriented layout
                 d.linear_output >= 2 ||                       // XybToRgb's other branches
                 (d.color_target && d.color_target->tf) ||     // the frame's matrix gives linear RGB, the generic writer the rest
                 d.has_noise ||                                // added between the filter launch and the colour conversion
                 r.ups_kept || d.splines.num_segments || d.patches.num_positions;  // drawn over the filtered planes
   r.gray8_fast = g8 && !r.color_out;
+  r.tensor_fused = tensor_rows && !r.color_out;
   r.plane1 = o.keep_filtered || ups != 1 || r.color_out;
   return r;
 }
