@@ -325,6 +325,35 @@ typedef struct {
 } JxlHipTensorOut;
 int jxlhip_set_output_tensor(JxlHipContext* ctx, const JxlHipTensorOut* tensor);
 
+/* ---- The same, cropped and resized on the way: a box of the oriented output image, resampled to out_xsize x out_ysize,
+ * goes to the caller's tensor, whose extents are the OUTPUT size (every rule of JxlHipTensorOut holds at that size).
+ *   Source sample v: as above, the float the f32 writer of jxlhip_set_output_format(ctx, 0, num_channels, 0, 0) stores.
+ *   Filter: the separable antialiased triangle filter of the box alone (samples outside the box do not exist, as if the
+ *       image had been cropped first). Per axis, n_in the box extent and n_out the output extent, in double on the host:
+ *         scale = n_in / n_out, support = max(scale, 1), center = scale * (i + 0.5),
+ *         lo = max(0, trunc(center - support + 0.5)), hi = min(n_in, trunc(center + support + 0.5)),
+ *         w_j = max(0, 1 - |(j - center + 0.5) / support|) for j in [lo, hi), divided by their sum, then rounded to float:
+ *       torch.nn.functional.interpolate(mode="bilinear", antialias=True, align_corners=False) of the cropped image in
+ *       float64, and Pillow's rule. The kernels accumulate in float32 (two passes, a float32 value between them).
+ *   Float types: then the arithmetic of jxlhip_set_output_tensor (clamp01, * scale[c], + bias[c], each rounded; to dtype).
+ *   JXLHIP_TENSOR_U8: scale 1, bias 0, no clamp; the sample is v * 255 rounded to float, clamped to [0, 255], rounded to
+ *       nearest even. NO dither: a dither cell has no meaning at a resampled position.
+ * While the binding is set the context renders as for jxlhip_set_output_format(ctx, 0, num_channels, 0, 0) into a pixel
+ * buffer of its own, which stays private: jxlhip_download_pixels / _rgb8 / _rgb8_rows answer JXLHIP_ERR_INVALID_ARGUMENT and
+ * jxlhip_rgb8_device_ptr NULL, band uploads and the jxlhip_canvas_* calls JXLHIP_ERR_UNSUPPORTED, as for a bound tensor.
+ * The two resample launches are the tail of jxlhip_run_filter_color[_batch] / jxlhip_modular_run[_batch] (one launch per
+ * pass for all the contexts of a batch that have such a binding), inside the ordering described above. Setting this
+ * binding clears a bound tensor and the other way round; a destroyed context drops it. The upload checks the descriptor
+ * again at the image's size (a refused one launches nothing). NULL: unbound. Output extents up to 16384. */
+#define JXLHIP_RESAMPLE_TRIANGLE 0u
+typedef struct {
+  JxlHipTensorOut tensor;                          /* extents: out_xsize x out_ysize */
+  uint32_t out_xsize, out_ysize;
+  uint32_t box_x0, box_y0, box_xsize, box_ysize;   /* in the oriented output image; all 0: the whole image */
+  uint32_t filter;                                 /* JXLHIP_RESAMPLE_TRIANGLE */
+} JxlHipResizedOut;
+int jxlhip_set_output_resized(JxlHipContext* ctx, const JxlHipResizedOut* out);
+
 /* Per-group error flags written by the entropy kernel: bit0 invalid nzeros, bit1 ANS final state,
  * bit2 section over-read, bit3 invalid histogram selector. Synchronous. `flags` has num_groups entries.
  * Returns JXLHIP_ERR_STREAM if any flag is set. */
@@ -442,6 +471,12 @@ int jxlhip_debug_color_target(JxlHipContext* ctx, const float* xyb, size_t n, co
  * oversized planes (more than 2^24 samples), an empty or outlying band and values that are not finite. */
 int jxlhip_debug_noise(JxlHipContext* ctx, const float* xyb, uint32_t xsize, uint32_t ysize, uint32_t seed0, uint32_t seed1,
                        const float* lut, float ytox, float ytob, uint32_t y_begin, uint32_t y_end, float* raw_out, float* xyb_out);
+
+/* Test entry: the two resample passes alone (k_resample_rows, then k_resample_columns) on `src`, host memory, interleaved
+ * [ysize][xsize][nc] floats, into the descriptor's tensor, ordered against its consumer_stream as a decode is; complete
+ * when it returns. Refuses whatever the descriptor's check refuses for an image of xsize x ysize, an nc that is not the
+ * tensor's num_channels, and sources of more than 2^26 samples, before any launch. */
+int jxlhip_debug_resample(JxlHipContext* ctx, const float* src, uint32_t xsize, uint32_t ysize, uint32_t nc, const JxlHipResizedOut* out);
 
 /* Test access: who writes the pixels of the VarDCT frame the context last uploaded. *route = 0: the generic writer behind
  * the filter kernel (k_color_out / k_upsample_color), 1: the filter kernel itself (RGB8, RGB f32), 2: the one-channel

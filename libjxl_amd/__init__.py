@@ -238,6 +238,36 @@ class TensorOut(ctypes.Structure):  # JxlHipTensorOut
                 ("consumer_stream", ctypes.c_void_p)]
 
 
+RESAMPLE_TRIANGLE = 0  # JXLHIP_RESAMPLE_*
+
+
+class ResizedOut(ctypes.Structure):  # JxlHipResizedOut
+    _fields_ = [("tensor", TensorOut), ("out_xsize", ctypes.c_uint32), ("out_ysize", ctypes.c_uint32),
+                ("box_x0", ctypes.c_uint32), ("box_y0", ctypes.c_uint32), ("box_xsize", ctypes.c_uint32), ("box_ysize", ctypes.c_uint32),
+                ("filter", ctypes.c_uint32)]
+
+
+def _tensor_out(ptr, nbytes, dtype, num_channels, strides, scale, bias, clamp, stream):
+    t = TensorOut()
+    t.data, t.bytes, t.dtype, t.num_channels = int(ptr), int(nbytes), int(dtype), int(num_channels)
+    t.stride_c, t.stride_y, t.stride_x = [int(s) for s in strides]
+    for c in range(4):
+        t.scale[c] = 1.0 if scale is None or c >= len(scale) else float(scale[c])
+        t.bias[c] = 0.0 if bias is None or c >= len(bias) else float(bias[c])
+    t.clamp01 = 1 if clamp else 0
+    t.consumer_stream = int(stream) or None
+    return t
+
+
+def _resized_out(ptr, nbytes, dtype, num_channels, strides, out_size, box, scale, bias, clamp, stream, filter):
+    d = ResizedOut()
+    d.tensor = _tensor_out(ptr, nbytes, dtype, num_channels, strides, scale, bias, clamp, stream)
+    d.out_xsize, d.out_ysize = int(out_size[0]), int(out_size[1])
+    d.box_x0, d.box_y0, d.box_xsize, d.box_ysize = [int(v) for v in (box if box is not None else (0, 0, 0, 0))]
+    d.filter = int(filter)
+    return d
+
+
 def frame_is_modular(data):
     """Whether the codestream's first frame is Modular-coded (ModFrame, upload_modular) or VarDCT (Frame, upload)."""
     L = lib()
@@ -389,16 +419,37 @@ class HipContext:
             _check(L.jxlhip_set_output_tensor(self._h, None), "jxlhip_set_output_tensor")
             self._tensor = None
             return
-        t = TensorOut()
-        t.data, t.bytes, t.dtype, t.num_channels = int(ptr), int(nbytes), int(dtype), int(num_channels)
-        t.stride_c, t.stride_y, t.stride_x = [int(s) for s in strides]
-        for c in range(4):
-            t.scale[c] = 1.0 if scale is None or c >= len(scale) else float(scale[c])
-            t.bias[c] = 0.0 if bias is None or c >= len(bias) else float(bias[c])
-        t.clamp01 = 1 if clamp else 0
-        t.consumer_stream = int(stream) or None
+        t = _tensor_out(ptr, nbytes, dtype, num_channels, strides, scale, bias, clamp, stream)
         _check(L.jxlhip_set_output_tensor(self._h, ctypes.byref(t)), "jxlhip_set_output_tensor")
         self._tensor = t
+
+    def set_output_resized(self, ptr, nbytes=0, dtype=TENSOR_F16, num_channels=3, strides=None, out_size=None, box=None, scale=None,
+                           bias=None, clamp=False, stream=0, filter=RESAMPLE_TRIANGLE):
+        """jxlhip_set_output_resized: a box of the next uploads' oriented output image, box = (x0, y0, xsize, ysize) or None
+        for the whole image, is resampled (antialiased triangle filter) to out_size = (out_xsize, out_ysize) and goes to the
+        caller-owned device memory at `ptr`, described as for set_output_tensor at the OUTPUT size; ptr=None unbinds.
+        uint8 takes the undithered 8-bit sample. Replaces a bound tensor. libjxl_amd.torch_io.bind_resized binds a tensor."""
+        L = lib()
+        L.jxlhip_set_output_resized.argtypes = [ctypes.c_void_p, ctypes.POINTER(ResizedOut)]
+        if ptr is None:
+            _check(L.jxlhip_set_output_resized(self._h, None), "jxlhip_set_output_resized")
+            self._resized = None
+            return
+        d = _resized_out(ptr, nbytes, dtype, num_channels, strides, out_size, box, scale, bias, clamp, stream, filter)
+        _check(L.jxlhip_set_output_resized(self._h, ctypes.byref(d)), "jxlhip_set_output_resized")
+        self._resized = d
+
+    def debug_resample(self, src, ptr, nbytes, dtype, strides, out_size, box=None, scale=None, bias=None, clamp=False, stream=0,
+                       filter=RESAMPLE_TRIANGLE, num_channels=None):
+        """Test entry: the two resample passes alone on src [ysize, xsize, nc] (host floats) into the device memory at `ptr`,
+        described as for set_output_resized (num_channels: the tensor's, nc unless given); complete on return."""
+        src = np.ascontiguousarray(src, np.float32)
+        ys, xs, nc = src.shape
+        d = _resized_out(ptr, nbytes, dtype, nc if num_channels is None else num_channels, strides, out_size, box, scale, bias, clamp, stream, filter)
+        L = lib()
+        L.jxlhip_debug_resample.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.POINTER(ResizedOut)]
+        _check(L.jxlhip_debug_resample(self._h, src.ctypes.data, xs, ys, nc, ctypes.byref(d)), "jxlhip_debug_resample")
 
     def set_output_orientation(self, orientation=1):
         """Undo this image orientation (1..8, EXIF numbering) in the pixel writer; call before upload."""

@@ -20,6 +20,7 @@
 #include "../host/jxh_enc_shared.h"
 #include "../host/jxh_launch_order.h"
 #include "../host/jxh_modular_upload_plan.h"
+#include "../host/jxh_resample_plan.h"
 #include "../host/jxh_tensor_out.h"
 #include "../host/jxh_upload_plan.h"
 #include "jxl_hip_kernels.h"
@@ -29,9 +30,11 @@
 #include "jxl_hip_enc.h"
 #include "jxl_hip_canvas.h"
 #include "jxl_hip_dc.h"
+#include "jxl_hip_resample.h"
 
 namespace upload = jxlhip::upload;
 namespace tensor_out = jxlhip::tensor_out;
+namespace resample = jxlhip::resample;
 
 namespace {
 #include "../host/afv_basis.inc"
@@ -386,6 +389,17 @@ struct JxlHipContext {
   uint32_t srch_xb = 0, srch_yb = 0, srch_floating = 0;
   size_t srch_first[jxh::kAcsWalkKinds + 1] = {};
   hipEvent_t srch_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // jxlhip_set_output_resized: the context renders f32 pixels of resized.tensor.num_channels channels into `rgb` as for
+  // jxlhip_set_output_format(0, nc, 0, 0), and the resample passes (jxl_hip_resample.h) take a box of them to the caller's
+  // tensor. rs_block (placed at upload): the descriptor and the two tap tables; rs_dev: the descriptor's host copy, from
+  // which a batched launch builds its array (rs_batch on the launch's first context, kept while the set stays the same);
+  // rs_tmp: the rows between the passes; rs_src: jxlhip_debug_resample's source.
+  bool resized_bound = false;
+  JxlHipResizedOut resized{};
+  resample::ResampleDev rs_dev{};
+  Buf rs_block, rs_tmp, rs_src, rs_batch;
+  std::vector<const JxlHipContext*> rs_batch_ctxs;
+  std::vector<uint64_t> rs_batch_gens;
 };
 
 // JXLHIP_ENTROPY=1 (a test hook): no frame takes the lane-parallel k_entropy_lanes, every frame the wave-per-section
@@ -401,14 +415,25 @@ static JxlHipContext* PlaneHolder(JxlHipContext* c) { return c->plane_lender ? c
 static const JxlHipContext* PlaneHolder(const JxlHipContext* c) { return c->plane_lender ? c->plane_lender : c; }
 
 // The sample format the writers make: the bound tensor's, else jxlhip_set_output_format's.
-static uint32_t OutType(const JxlHipContext* c) { return c->tensor_bound ? c->tensor.dtype : c->out_type; }
-static uint32_t OutChannels(const JxlHipContext* c) { return c->tensor_bound ? c->tensor.num_channels : c->out_nc; }
-static uint32_t OutBits(const JxlHipContext* c) { return c->tensor_bound ? 8u : c->out_bits; }
-static uint32_t OutSwap(const JxlHipContext* c) { return c->tensor_bound ? 0u : c->out_swap; }
-static size_t OutSampleBytes(const JxlHipContext* c) { return c->out_type == 2 ? 1 : (c->out_type == 0 ? 4 : 2); }
-static size_t OutPixelBytes(const JxlHipContext* c) { return OutSampleBytes(c) * c->out_nc; }
+// (a resized binding: what jxlhip_set_output_format(ctx, 0, num_channels, 0, 0) would have set, into the context's own buffer)
+static uint32_t OutType(const JxlHipContext* c) { return c->tensor_bound ? c->tensor.dtype : (c->resized_bound ? 0u : c->out_type); }
+static uint32_t OutChannels(const JxlHipContext* c) {
+  return c->tensor_bound ? c->tensor.num_channels : (c->resized_bound ? c->resized.tensor.num_channels : c->out_nc);
+}
+static uint32_t OutBits(const JxlHipContext* c) { return c->tensor_bound ? 8u : (c->resized_bound ? 16u : c->out_bits); }
+static uint32_t OutSwap(const JxlHipContext* c) { return c->tensor_bound || c->resized_bound ? 0u : c->out_swap; }
+static size_t OutSampleBytes(const JxlHipContext* c) { return c->resized_bound ? 4 : (c->out_type == 2 ? 1 : (c->out_type == 0 ? 4 : 2)); }
+static size_t OutPixelBytes(const JxlHipContext* c) { return OutSampleBytes(c) * (c->resized_bound ? c->resized.tensor.num_channels : c->out_nc); }
 // (the context's own RGB8 rows: never a tensor, whatever its type)
-static bool OutIsRgb8(const JxlHipContext* c) { return !c->tensor_bound && upload::OutIsRgb8(c->out_type, c->out_nc, c->out_bits); }
+static bool OutIsRgb8(const JxlHipContext* c) {
+  return !c->tensor_bound && !c->resized_bound && upload::OutIsRgb8(c->out_type, c->out_nc, c->out_bits);
+}
+// The pixels are the caller's (a bound tensor) or feed the caller's tensor (a resized binding): downloads, bands and
+// canvases are refused alike. The tensor whose consumer stream the writes are ordered against.
+static bool CallerOwnsPixels(const JxlHipContext* c) { return c->tensor_bound || c->resized_bound; }
+static const JxlHipTensorOut* CallerTensor(const JxlHipContext* c) {
+  return c->tensor_bound ? &c->tensor : (c->resized_bound ? &c->resized.tensor : nullptr);
+}
 // Room of the context's own pixel buffer for the frame: none while a tensor is bound.
 static size_t OwnPixelBytes(const JxlHipContext* c) { return c->tensor_bound ? 0 : size_t(c->oxs) * c->oys * OutPixelBytes(c); }
 
@@ -601,7 +626,7 @@ static std::vector<Buf*> AllBufs(JxlHipContext* c) {
                 &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in, &c->enc_mask1x1,
                 &c->est_planes, &c->est_qf, &c->est_mask, &c->est_ytox, &c->est_ytob, &c->est_dq, &c->est_cand, &c->est_index, &c->est_at, &c->est_out, &c->est_scaled,
                 &c->srch_mask, &c->srch_zero, &c->srch_cand, &c->srch_index, &c->srch_table, &c->walk_table, &c->walk_acs, &c->walk_entropy,
-                &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
+                &c->rs_block, &c->rs_tmp, &c->rs_src, &c->rs_batch, &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
   for (auto& pb : c->pass_bufs)
     for (Buf* b : {&pb.ctx_map, &pb.alias, &pb.cfg, &pb.orders, &pb.ptable, &pb.poffset, &pb.alias_packed}) all.push_back(b);
   return all;
@@ -615,6 +640,8 @@ void jxlhip_ctx_destroy(JxlHipContext* c) {
   // (the caller's tensor is the caller's to free from here on: whoever takes this context from the pool starts unbound)
   c->tensor_bound = c->tensor_fused = false;
   c->tensor = JxlHipTensorOut{};
+  c->resized_bound = false;
+  c->resized = JxlHipResizedOut{};
   if (c->basis.p && !c->pooled_once && !GuardOn() && EnvInt("JXLHIP_CTX_POOL", 1)) {  // keep it for the next jxlhip_ctx_create (see RecycleContext)
     size_t bytes = 0;
     for (Buf* b : AllBufs(c))
@@ -664,8 +691,9 @@ static int TensorsBeforeWriters(JxlHipContext* const* ctxs, size_t n, hipStream_
   hipStream_t waited = nullptr;
   for (size_t i = 0; i < n; i++) {
     JxlHipContext* c = ctxs[i];
-    if (!c->tensor_bound) continue;
-    const hipStream_t cs = static_cast<hipStream_t>(c->tensor.consumer_stream);
+    const JxlHipTensorOut* t = CallerTensor(c);
+    if (!t) continue;
+    const hipStream_t cs = static_cast<hipStream_t>(t->consumer_stream);
     if (any && cs == waited) continue;
     if (!c->tensor_event) HIP_TRY(hipEventCreateWithFlags(&c->tensor_event, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(c->tensor_event, cs));
@@ -680,8 +708,9 @@ static int TensorsAfterWriters(JxlHipContext* const* ctxs, size_t n, hipStream_t
   hipStream_t told = nullptr;
   for (size_t i = 0; i < n; i++) {
     JxlHipContext* c = ctxs[i];
-    if (!c->tensor_bound) continue;
-    const hipStream_t cs = static_cast<hipStream_t>(c->tensor.consumer_stream);
+    const JxlHipTensorOut* t = CallerTensor(c);
+    if (!t) continue;
+    const hipStream_t cs = static_cast<hipStream_t>(t->consumer_stream);
     if (done && cs == told) continue;
     if (!done) {  // (one record behind the last writer serves every consumer stream)
       if (!c->tensor_event) HIP_TRY(hipEventCreateWithFlags(&c->tensor_event, hipEventDisableTiming));
@@ -889,6 +918,81 @@ static void AdoptPatches(JxlHipContext* c, const JxlHipPatches& pt) {
     c->pat_src_h[i] = pt.slot_h[i];
   }
 }
+// ------------------------------------------------------------------------------------- resized binding (jxh_resample_plan.h)
+// The descriptor and the tap tables of `d` (which CheckResizedOut took for an image of w x h whose f32 pixels are `src`, rows
+// of w pixels) into the context's block: built in the staging block, one copy on the context's stream, complete on return.
+// The caller has made sure that nothing reads the block or the staging block any more.
+static int PlaceResample(JxlHipContext* c, const JxlHipResizedOut& d, uint32_t w, uint32_t h, const float* src) {
+  const resample::Box b = resample::BoxOf(d, w, h);
+  const resample::BlockLayout l = resample::LayoutOf(b, d.out_xsize, d.out_ysize);
+  int r;
+  if ((r = c->rs_block.Ensure(l.bytes))) return r;
+  if ((r = c->rs_tmp.Ensure(resample::TmpBytes(b, d.tensor.num_channels, d.out_ysize)))) return r;
+  if ((r = StageReset(c))) return r;
+  void* st = nullptr;
+  if ((r = StageAlloc(c, l.bytes, &st))) return r;
+  if ((r = resample::PlaceBlock(d, b, src, w, c->rs_tmp.as<float>(), st, uintptr_t(c->rs_block.p)))) return r;
+  memcpy(&c->rs_dev, static_cast<uint8_t*>(st) + l.desc, sizeof(c->rs_dev));
+  HIP_TRY(hipMemcpyAsync(c->rs_block.p, st, l.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->stage.done, c->stream));
+  c->stage.recorded = true;
+  HIP_TRY(WaitEvent(c->stage.done));
+  return 0;
+}
+// ... of the frame the context has just adopted: the source is its own pixel buffer at the oriented output size.
+static int PlaceResampleOfFrame(JxlHipContext* c) {
+  const bool transposed = (c->out_orient & 4) != 0;
+  return PlaceResample(c, c->resized, transposed ? c->oys : c->oxs, transposed ? c->oxs : c->oys, c->rgb.as<float>());
+}
+static int LaunchResamplePasses(const resample::ResampleDev* descs, uint32_t n, uint32_t v_tiles, uint32_t h_tiles, hipStream_t ls) {
+  hipLaunchKernelGGL(jxlhip::k_resample_rows, dim3(v_tiles), dim3(256), 0, ls, descs, n);
+  hipLaunchKernelGGL(jxlhip::k_resample_columns, dim3(h_tiles), dim3(256), 0, ls, descs, n);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// The tail of a filter + colour or Modular launch: the two passes, once for every context of the set that has a resized
+// binding, behind the writers on `ls`. One such context: its own block is the launch's descriptor array. Several: their
+// descriptors side by side with running tile origins, on the set's first context, rebuilt only when the set changed.
+static int LaunchResample(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) {
+  std::vector<const JxlHipContext*> set;
+  for (size_t i = 0; i < n; i++)
+    if (ctxs[i]->resized_bound) set.push_back(ctxs[i]);
+  if (set.empty()) return 0;
+  if (set.size() == 1) {
+    const JxlHipContext* c = set[0];
+    return LaunchResamplePasses(c->rs_block.as<resample::ResampleDev>(), 1, c->rs_dev.v_tiles, c->rs_dev.h_tiles, ls);
+  }
+  JxlHipContext* c0 = ctxs[0];
+  std::vector<uint64_t> gens(set.size());
+  std::vector<resample::ResampleDev> descs(set.size());
+  uint64_t v = 0, h = 0;
+  for (size_t i = 0; i < set.size(); i++) {
+    gens[i] = set[i]->generation;
+    descs[i] = set[i]->rs_dev;
+    descs[i].v_tile0 = uint32_t(v);
+    descs[i].h_tile0 = uint32_t(h);
+    v += descs[i].v_tiles;
+    h += descs[i].h_tiles;
+  }
+  if (v > 0x7FFFFFFFu || h > 0x7FFFFFFFu) return JXLHIP_ERR_UNSUPPORTED;
+  if (set != c0->rs_batch_ctxs || gens != c0->rs_batch_gens) {
+    c0->rs_batch_ctxs.clear();
+    const size_t bytes = descs.size() * sizeof(resample::ResampleDev);
+    int r = c0->rs_batch.Ensure(bytes);
+    if (r) return r;
+    // (on the launch stream itself: behind an earlier launch that still reads the array, and without a host wait)
+    void* st = nullptr;
+    if ((r = StageReset(c0)) || (r = StageAlloc(c0, bytes, &st))) return r;
+    memcpy(st, descs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(c0->rs_batch.p, st, bytes, hipMemcpyHostToDevice, ls));
+    HIP_TRY(hipEventRecord(c0->stage.done, ls));
+    c0->stage.recorded = true;
+    c0->rs_batch_ctxs = set;
+    c0->rs_batch_gens = gens;
+  }
+  return LaunchResamplePasses(c0->rs_batch.as<resample::ResampleDev>(), uint32_t(set.size()), uint32_t(v), uint32_t(h), ls);
+}
+
 // -------------------------------------------------------------------------------------------------- frame upload
 // The bound tensor against the frame: whole frames only, and the descriptor's rules (jxh_tensor_out.h) at the size of the
 // output image, which a transposing orientation turns. *reach: bytes from the tensor's first element to behind the last one.
@@ -902,6 +1006,13 @@ static int CheckBoundTensor(const JxlHipContext* c, const upload::Geometry& g, u
   tensor_out::MaxOffset(c->tensor, w, h, &max_offset);
   *reach = (max_offset + 1) * tensor_out::ElemBytes(c->tensor.dtype);
   return 0;
+}
+// The resized binding against the frame: whole frames only, and the descriptor's rules (jxh_resample_plan.h) at the size
+// of the oriented output image.
+static int CheckBoundResized(const JxlHipContext* c, const upload::Geometry& g, uint32_t group_rows) {
+  if (g.band_row0 != 0 || g.band_row1 != group_rows) return JXLHIP_ERR_UNSUPPORTED;
+  const bool transposed = (c->out_orient & 4) != 0;
+  return resample::CheckResizedOut(c->resized, transposed ? g.oys : g.oxs, transposed ? g.oxs : g.oys);
 }
 static upload::UploadOptions OptionsOf(const JxlHipContext* c) {
   upload::UploadOptions o;
@@ -1230,6 +1341,7 @@ extern "C" int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   upload::UploadOptions opt = OptionsOf(c);
   int r = upload::CheckFrameDesc(*d, opt);
   if (!r && c->tensor_bound) r = CheckBoundTensor(c, upload::MakeGeometry(*d, opt), d->num_groups / d->xsize_groups, &opt.tensor_reach);
+  if (!r && c->resized_bound) r = CheckBoundResized(c, upload::MakeGeometry(*d, opt), d->num_groups / d->xsize_groups);
   upload::Plan P;
   EntropyRoute E = {};
   if (!r) {
@@ -1270,6 +1382,7 @@ extern "C" int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   // (Leaving the copies of many contexts in flight at once instead, ordered by events, made every later kernel of the
   // process ~1.35x slower on this runtime: scripts/async_probe.py.)
   HIP_TRY(WaitEvent(c->stage.done));
+  if (c->resized_bound && (r = PlaceResampleOfFrame(c))) return r;
   prof.lap("rest");
   if (prof.on) fprintf(stderr, "[upload] %s\n", prof.line.c_str());
   c->have_frame = true;
@@ -2311,6 +2424,10 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
     const bool transposed = (c->out_orient & 4) != 0;
     r = tensor_out::CheckTensorOut(c->tensor, transposed ? d->ysize : d->xsize, transposed ? d->xsize : d->ysize);
   }
+  if (!r && c->resized_bound) {
+    const bool transposed = (c->out_orient & 4) != 0;
+    r = resample::CheckResizedOut(c->resized, transposed ? d->ysize : d->xsize, transposed ? d->xsize : d->ysize);
+  }
   if (r) return r;
   const upload::ModPlan P = upload::MakeModPlan(*d, opt);
   // 2. the tables are overwritten on the context's stream, behind whatever still reads the old ones
@@ -2326,6 +2443,7 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
   HIP_TRY(hipEventRecord(c->stage.done, c->stream));
   c->stage.recorded = true;
   HIP_TRY(WaitEvent(c->stage.done));
+  if (c->resized_bound && (r = PlaceResampleOfFrame(c))) return r;
   c->mod.have = true;
   c->mod.batch_ctxs.clear();
   c->generation++;
@@ -2559,6 +2677,10 @@ extern "C" int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n) {
   {
     int r = ModularLaunchOps(M0.batch_launches, M0.batch_ops.as<uint8_t>(), c0->stream);
     if (r) return r;
+  }
+  {
+    const int rr = LaunchResample(ctxs, n, c0->stream);
+    if (rr) return rr;
   }
   HIP_TRY(hipEventRecord(c0->ev[1], c0->stream));
   {
@@ -2801,6 +2923,7 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
       HIP_TRY(hipGetLastError());
     }
   }
+  if ((r = LaunchResample(ctxs, n, ls))) return r;
   HIP_TRY(hipEventRecord(c0->ev[5], ls));
   if ((r = TensorsAfterWriters(ctxs, n, ls))) return r;
   c0->ev_valid[2] = true;
@@ -3002,9 +3125,53 @@ int jxlhip_set_output_tensor(JxlHipContext* c, const JxlHipTensorOut* t) {
   }
   c->tensor_bound = t != nullptr;
   c->tensor_fused = false;
+  c->resized_bound = false;  // (one destination at a time)
+  c->resized = JxlHipResizedOut{};
   c->have_frame = false;  // (a frame uploaded for the other destination has no writer for this one: upload again)
   c->mod.have = false;
   c->generation++;  // cached batch descriptions hold the pixel pointers
+  return 0;
+}
+
+int jxlhip_set_output_resized(JxlHipContext* c, const JxlHipResizedOut* d) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (d) {  // what can be said without an image (any box that fits 32 bits is inside); the upload checks again
+    const int r = resample::CheckResizedOut(*d, resample::kAnyImageExtent, resample::kAnyImageExtent);
+    if (r) return r;
+    c->resized = *d;
+  } else {
+    c->resized = JxlHipResizedOut{};
+  }
+  c->resized_bound = d != nullptr;
+  c->tensor_bound = c->tensor_fused = false;  // (one destination at a time)
+  c->tensor = JxlHipTensorOut{};
+  c->have_frame = false;  // (a frame uploaded for another destination has neither the pixel buffer nor the tables: upload again)
+  c->mod.have = false;
+  c->generation++;
+  return 0;
+}
+
+int jxlhip_debug_resample(JxlHipContext* c, const float* src, uint32_t xsize, uint32_t ysize, uint32_t nc, const JxlHipResizedOut* d) {
+  if (!c || !src || !d) return JXLHIP_ERR_INVALID_ARGUMENT;
+  int r = resample::CheckResizedOut(*d, xsize, ysize);
+  if (r) return r;
+  if (nc != d->tensor.num_channels || uint64_t(xsize) * ysize * nc > (uint64_t(1) << 26)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((r = ApplyPendingWait(c))) return r;
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (whatever still reads the context's block or its source)
+  if (c->resized_bound) c->have_frame = c->mod.have = false;  // (an uploaded frame's tables are overwritten: upload again)
+  const size_t bytes = size_t(xsize) * ysize * nc * 4;
+  if ((r = c->rs_src.Ensure(bytes))) return r;
+  HIP_TRY(hipMemcpy(c->rs_src.p, src, bytes, hipMemcpyHostToDevice));
+  if ((r = PlaceResample(c, *d, xsize, ysize, c->rs_src.as<float>()))) return r;
+  const hipStream_t cs = static_cast<hipStream_t>(d->tensor.consumer_stream);
+  if (!c->tensor_event) HIP_TRY(hipEventCreateWithFlags(&c->tensor_event, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(c->tensor_event, cs));
+  HIP_TRY(hipStreamWaitEvent(c->stream, c->tensor_event, 0));
+  if ((r = LaunchResamplePasses(c->rs_block.as<resample::ResampleDev>(), 1, c->rs_dev.v_tiles, c->rs_dev.h_tiles, c->stream))) return r;
+  HIP_TRY(hipEventRecord(c->tensor_event, c->stream));
+  HIP_TRY(hipStreamWaitEvent(cs, c->tensor_event, 0));
+  HIP_TRY(WaitStream(c->stream));
   return 0;
 }
 
@@ -3091,7 +3258,7 @@ int jxlhip_upsample_plane(JxlHipContext* c, const float* plane, uint32_t xsize, 
 }
 
 int jxlhip_download_pixels(JxlHipContext* c, void* dst, size_t stride) {
-  if (!c || !dst || c->tensor_bound) return JXLHIP_ERR_INVALID_ARGUMENT;  // (a bound tensor holds the pixels, not the context)
+  if (!c || !dst || CallerOwnsPixels(c)) return JXLHIP_ERR_INVALID_ARGUMENT;  // (a bound tensor holds the pixels, not the context)
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   const bool transposed = (c->out_orient & 4) != 0;  // rows of the output are columns of the image
   const size_t row = size_t(transposed ? c->oys : c->oxs) * OutPixelBytes(c), rows = transposed ? c->oxs : c->oys;
@@ -3286,7 +3453,7 @@ int jxlhip_sync(JxlHipContext* c) {
 }
 
 int jxlhip_download_rgb8(JxlHipContext* c, uint8_t* dst, size_t stride) {
-  if (!c || !dst || c->tensor_bound) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c || !dst || CallerOwnsPixels(c)) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   if (stride < size_t(c->oxs) * 3 || !OutIsRgb8(c)) return JXLHIP_ERR_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
@@ -3300,7 +3467,7 @@ int jxlhip_download_rgb8(JxlHipContext* c, uint8_t* dst, size_t stride) {
 }
 
 int jxlhip_download_rgb8_rows(JxlHipContext* c, uint8_t* dst, size_t stride, uint32_t y_begin, uint32_t y_end) {
-  if (!c || !dst || c->tensor_bound) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c || !dst || CallerOwnsPixels(c)) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   if (stride < size_t(c->oxs) * 3 || y_begin >= y_end || y_end > c->oys || !OutIsRgb8(c)) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (c->out_orient & 4) return JXLHIP_ERR_INVALID_ARGUMENT;  // a transposed output has other rows: jxlhip_download_pixels
@@ -3315,7 +3482,7 @@ int jxlhip_download_rgb8_rows(JxlHipContext* c, uint8_t* dst, size_t stride, uin
   return 0;
 }
 
-const uint8_t* jxlhip_rgb8_device_ptr(JxlHipContext* c) { return c && c->have_frame && !c->tensor_bound ? c->rgb.as<uint8_t>() : nullptr; }
+const uint8_t* jxlhip_rgb8_device_ptr(JxlHipContext* c) { return c && c->have_frame && !CallerOwnsPixels(c) ? c->rgb.as<uint8_t>() : nullptr; }
 
 int jxlhip_get_errors(JxlHipContext* c, uint32_t* flags, size_t n) {
   if (!c || !flags) return JXLHIP_ERR_INVALID_ARGUMENT;
@@ -3483,7 +3650,7 @@ void jxlhip_canvas_destroy(JxlHipCanvas* v) {
 
 int jxlhip_canvas_save_xyb(JxlHipCanvas* v, JxlHipContext* c, uint32_t slot) {
   if (!v || !c || slot > 7 || c->device != v->device) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->tensor_bound) return JXLHIP_ERR_UNSUPPORTED;  // (composed frames keep the context's own buffers)
+  if (CallerOwnsPixels(c)) return JXLHIP_ERR_UNSUPPORTED;  // (composed frames keep the context's own buffers)
   HIP_TRY(hipSetDevice(v->device));
   {
     int pw = ApplyPendingWait(c);
@@ -3554,7 +3721,7 @@ int jxlhip_canvas_xyb_alpha(JxlHipCanvas* v, uint32_t slot, const float** alpha)
 int jxlhip_canvas_blend(JxlHipCanvas* v, JxlHipContext* c, const JxlHipBlend* b) {
   if (!v || !c || !b || c->device != v->device) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (b->mode > 4 || b->alpha_mode > 4 || b->source > 3 || b->alpha_source > 3 || b->save_slot > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->tensor_bound) return JXLHIP_ERR_UNSUPPORTED;  // (the frame's pixels are in the caller's tensor, not in c->rgb)
+  if (CallerOwnsPixels(c)) return JXLHIP_ERR_UNSUPPORTED;  // (the frame's pixels are in the caller's tensor, not in c->rgb)
   if (!c->have_frame && !c->mod.have) return JXLHIP_ERR_NO_FRAME;
   if (c->out_type != 0 || c->out_nc != 4 || c->out_swap || c->out_orient) return JXLHIP_ERR_INVALID_ARGUMENT;  // f32 x 4 as coded
   if (size_t(c->oxs) * c->oys * 16 > c->rgb.cap) return JXLHIP_ERR_INVALID_ARGUMENT;

@@ -1616,6 +1616,21 @@ __device__ __forceinline__ float TensorAffine(float v, float scale, float bias, 
 }
 // float -> bfloat16 bits, round to nearest even (gfx950 converts in hardware: v_cvt_pk_bf16_f32; a NaN stays a NaN)
 __device__ __forceinline__ uint32_t Bf16Bits(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
+// Float f to element `index` of `dst` in one of the float formats (5 f16, kTypeBf16, else f32), to nearest even: the tail
+// of StoreSample, and of the resample pass that writes a tensor (jxl_hip_resample.h).
+__device__ __forceinline__ void StoreFloatSample(void* dst, uint32_t type, uint32_t swap, size_t index, float f) {
+  if (type == 5) {
+    uint32_t u = __half_as_ushort(__float2half_rn(f));
+    if (swap) u = ((u & 0xFF) << 8) | (u >> 8);
+    static_cast<uint16_t*>(dst)[index] = uint16_t(u);
+  } else if (type == kTypeBf16) {
+    static_cast<uint16_t*>(dst)[index] = uint16_t(Bf16Bits(f));
+  } else {
+    uint32_t u = __float_as_uint(f);
+    if (swap) u = __builtin_bswap32(u);
+    static_cast<uint32_t*>(dst)[index] = u;
+  }
+}
 // Sample c of a pixel, float f, to element `index` of the output in its format: the one statement of the format switch
 // (StorePixel, k_modular_output). 8-bit samples are dithered with the channel's interleave index at the oriented position
 // (dx, dy) (stage_write.cc:266-286), wider ones are not.
@@ -1636,17 +1651,7 @@ __device__ __forceinline__ void StoreSample(const PixelOut& o, size_t index, uin
   }
   if (o.tensor) f = TensorAffine(f, c == 0 ? o.scale[0] : (c == 1 ? o.scale[1] : (c == 2 ? o.scale[2] : o.scale[3])),
                                  c == 0 ? o.bias[0] : (c == 1 ? o.bias[1] : (c == 2 ? o.bias[2] : o.bias[3])), o.clamp01);
-  if (o.type == 5) {
-    uint32_t u = __half_as_ushort(__float2half_rn(f));
-    if (o.swap) u = ((u & 0xFF) << 8) | (u >> 8);
-    static_cast<uint16_t*>(o.dst)[index] = uint16_t(u);
-  } else if (o.type == kTypeBf16) {
-    static_cast<uint16_t*>(o.dst)[index] = uint16_t(Bf16Bits(f));
-  } else {
-    uint32_t u = __float_as_uint(f);
-    if (o.swap) u = __builtin_bswap32(u);
-    static_cast<uint32_t*>(o.dst)[index] = u;
-  }
+  StoreFloatSample(o.dst, o.type, o.swap, index, f);
 }
 
 // One pixel in any output format. Colour images hand out R (and alpha) when fewer than three channels are asked for,

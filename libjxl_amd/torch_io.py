@@ -3,6 +3,7 @@ in the layout and type the consumer asked for, into memory the consumer owns. to
 
     img = torch_io.decode_to_tensor(data, dtype=torch.float16, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225))
     batch = torch_io.decode_batch_to_tensor(datas, dtype=torch.bfloat16)     # (N, 3, H, W), one launch per stage
+    crops = torch_io.decode_batch_to_tensor(datas, size=(224, 224), boxes=boxes)  # any sizes: crop + antialiased resize
 
 Float types hold v * (1 / std[c]) + (-mean[c] / std[c]) of the decoder's float sample v in [0, 1] (scale and bias computed
 in float32, the product and the sum each rounded to float32, then to the type); uint8 holds the dithered 8-bit sample.
@@ -55,6 +56,30 @@ def bind(ctx, tensor, layout="CHW", mean=None, std=None, clamp=False, stream=Non
     ctx._bound_tensor = tensor  # keeps the memory alive while it is bound
 
 
+def bind_resized(ctx, tensor, layout="CHW", box=None, mean=None, std=None, clamp=False, stream=None):
+    """Binds a 3-d device tensor as the output of ctx's next uploads like bind(), but the image is cropped to box =
+    (x0, y0, xsize, ysize) of the oriented output image (None: the whole image) and resized, with the antialiased triangle
+    filter of torch.nn.functional.interpolate(mode="bilinear", antialias=True), to the tensor's own height and width
+    (jxlhip_set_output_resized). uint8 holds the undithered 8-bit sample."""
+    if layout not in ("CHW", "HWC"):
+        raise ValueError("layout is 'CHW' or 'HWC'")
+    if tensor.dim() != 3 or not tensor.is_cuda or tensor.dtype not in _DTYPES:
+        raise ValueError("a 3-d uint8 / float16 / bfloat16 / float32 tensor on the device")
+    if box is not None and (len(box) != 4 or min(box) < 0 or box[2] == 0 or box[3] == 0):
+        raise ValueError("box is (x0, y0, xsize, ysize) with non-zero extents, or None for the whole image")
+    st = tensor.stride()
+    sc, sy, sx = (st[0], st[1], st[2]) if layout == "CHW" else (st[2], st[0], st[1])
+    channels = tensor.shape[0] if layout == "CHW" else tensor.shape[2]
+    h, w = _image_size(tensor, layout)
+    scale, bias = affine(mean, std, channels)
+    if stream is None:
+        stream = torch.cuda.current_stream(tensor.device)
+    room = tensor.untyped_storage().nbytes() - tensor.storage_offset() * tensor.element_size()
+    ctx.set_output_resized(tensor.data_ptr(), room, _DTYPES[tensor.dtype], channels, (sc, sy, sx), (w, h),
+                           None if box is None else tuple(int(v) for v in box), scale, bias, clamp, getattr(stream, "cuda_stream", stream))
+    ctx._bound_tensor = tensor  # keeps the memory alive while it is bound
+
+
 def _alloc(shape_chw, dtype, layout, device):
     c, h, w = shape_chw
     return torch.empty((c, h, w) if layout == "CHW" else (h, w, c), dtype=dtype, device="cuda:%d" % device)
@@ -64,19 +89,31 @@ def _image_size(out, layout):
     return (out.shape[1], out.shape[2]) if layout == "CHW" else (out.shape[0], out.shape[1])
 
 
-def decode_to_tensor(data, dtype=torch.float16, layout="CHW", mean=None, std=None, clamp=False, channels=3, device=0, out=None):
+def decode_to_tensor(data, dtype=torch.float16, layout="CHW", mean=None, std=None, clamp=False, channels=3, device=0, out=None,
+                     size=None, box=None):
     """One-shot: a VarDCT or Modular codestream's first frame -> a device tensor (allocated unless `out` is given).
+    size = (height, width): the image, or box = (x0, y0, xsize, ysize) of it, is resized to that size on the device
+    (bind_resized); an `out` given with it must have that size. Without `size` the tensor has the image's own size.
     Raises JxlAmdError on sections or streams the kernels flagged as corrupt."""
+    if box is not None and size is None:
+        raise ValueError("box needs size")
     modular = J.frame_is_modular(data)
     f = J.ModFrame(data) if modular else J.Frame(data)
     c = J.HipContext(device)
     try:
         w, h = (f.info["xsize"], f.info["ysize"]) if modular else (f.info["out_xsize"], f.info["out_ysize"])
-        if out is None:
-            out = _alloc((channels, h, w), dtype, layout, device)
-        elif _image_size(out, layout) != (h, w):
-            raise ValueError("out is %r for an image of %d x %d" % (tuple(out.shape), w, h))
-        bind(c, out, layout, mean, std, clamp)
+        if size is not None:
+            if out is None:
+                out = _alloc((channels, int(size[0]), int(size[1])), dtype, layout, device)
+            elif _image_size(out, layout) != (int(size[0]), int(size[1])):
+                raise ValueError("out is %r for size %r" % (tuple(out.shape), tuple(size)))
+            bind_resized(c, out, layout, box, mean, std, clamp)
+        else:
+            if out is None:
+                out = _alloc((channels, h, w), dtype, layout, device)
+            elif _image_size(out, layout) != (h, w):
+                raise ValueError("out is %r for an image of %d x %d" % (tuple(out.shape), w, h))
+            bind(c, out, layout, mean, std, clamp)
         if modular:
             c.upload_modular(f)
             c.run_modular()
@@ -95,9 +132,68 @@ def decode_to_tensor(data, dtype=torch.float16, layout="CHW", mean=None, std=Non
         f.close()
 
 
-def decode_batch_to_tensor(datas, out=None, dtype=torch.float16, mean=None, std=None, clamp=False, channels=3, device=0):
+def _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device, size, boxes):
+    """decode_batch_to_tensor with `size`: frames of any size, VarDCT and Modular mixed, each cropped to its box and resized
+    into out[i]. The VarDCT contexts share the three batched stage launches, the Modular ones run_modular_batch; the resample
+    passes are one launch pair per family."""
+    n = len(datas)
+    hh, ww = int(size[0]), int(size[1])
+    if boxes is None:
+        boxes = [None] * n
+    if len(boxes) != n:
+        raise ValueError("%d boxes for %d frames" % (len(boxes), n))
+    if out is None:
+        out = torch.empty((n, channels, hh, ww), dtype=dtype, device="cuda:%d" % device)
+    elif tuple(out.shape) != (n, channels, hh, ww):
+        raise ValueError("out is %r, size %r needs %r" % (tuple(out.shape), tuple(size), (n, channels, hh, ww)))
+    modular = [J.frame_is_modular(d) for d in datas]
+    frames, ctxs = [], []
+    try:
+        for d, m in zip(datas, modular):
+            frames.append(J.ModFrame(d) if m else J.Frame(d))
+        for i, f in enumerate(frames):
+            c = J.HipContext(device)
+            ctxs.append(c)
+            bind_resized(c, out[i], "CHW", boxes[i], mean, std, clamp)
+            if modular[i]:
+                c.upload_modular(f)
+            else:
+                c.upload(f)
+        var = [c for c, m in zip(ctxs, modular) if not m]
+        mod = [c for c, m in zip(ctxs, modular) if m]
+        if var:
+            J.run_entropy_batch(var)
+            J.run_transform_batch(var)
+            J.run_filter_color_batch(var)
+        if mod:
+            J.run_modular_batch(mod)
+        for i, c in enumerate(ctxs):
+            if modular[i]:
+                r, status, _ = c.modular_status()
+                if r:
+                    raise J.JxlAmdError("frame %d: corrupt Modular streams: %r" % (i, [(k, s) for k, s in enumerate(status) if s]))
+            else:
+                r, flags = c.errors()
+                if r:
+                    raise J.JxlAmdError("frame %d: corrupt AC sections: %r" % (i, [(g, e) for g, e in enumerate(flags) if e]))
+        return out
+    finally:
+        for c in ctxs:
+            c.close()
+        for f in frames:
+            f.close()
+
+
+def decode_batch_to_tensor(datas, out=None, dtype=torch.float16, mean=None, std=None, clamp=False, channels=3, device=0, size=None,
+                           boxes=None):
     """VarDCT frames of one size -> one (N, C, H, W) tensor: a context per frame, each bound to out[i], and one launch per
-    stage for the whole set (run_entropy_batch / run_transform_batch / run_filter_color_batch)."""
+    stage for the whole set (run_entropy_batch / run_transform_batch / run_filter_color_batch). With size = (height, width)
+    the frames may differ in size and kind (VarDCT, Modular); each is resized to that size, frame i cropped to boxes[i] first
+    (a box (x0, y0, xsize, ysize) or None per frame)."""
+    if size is not None:
+        return _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device, size, boxes)
+    if boxes is not None:
+        raise ValueError("boxes needs size")
     frames = [J.Frame(d) for d in datas]
     ctxs = []
     try:
