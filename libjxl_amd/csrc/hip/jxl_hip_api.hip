@@ -18,7 +18,7 @@
 
 #include "../../../include/jxl_amd_hip.h"
 #include "../host/jxh_enc_shared.h"
-#include "../host/jxh_launch_order.h"
+#include "../host/jxh_lane_plan.h"
 #include "../host/jxh_modular_upload_plan.h"
 #include "../host/jxh_resample_plan.h"
 #include "../host/jxh_tensor_out.h"
@@ -35,6 +35,7 @@
 namespace upload = jxlhip::upload;
 namespace tensor_out = jxlhip::tensor_out;
 namespace resample = jxlhip::resample;
+namespace lane_plan = jxh::lane_plan;
 
 namespace {
 #include "../host/afv_basis.inc"
@@ -220,19 +221,13 @@ struct JxlHipContext {
   } mod;
   size_t plane_bytes = 0;  // bytes of plane[0] the current frame needs
   Buf ep_dev;                         // device copy of `ep` (the entropy kernel reads it through the scalar cache)
-  size_t batch_off_units = 0, batch_off_queue = 0, batch_off_wave_lanes = 0, batch_units = 0;  // layout of batch_lanes
   Buf batch_params, batch_map, batch_lanes;  // jxlhip_run_entropy_batch: parameter blocks, workgroup map, lane map
-  uint32_t batch_wait_shift = 2;
-  bool batch_galias = false;  // the lane kernel reads its alias tables from global memory (PrepareBatch)
-  bool batch_a6 = false;      // ... or keeps them in LDS in the six-byte form (jxl_hip_entropy_lanes.h LanesLdsLayout)
-  bool batch_prefix = false;  // ... decodes prefix codes
+  lane_plan::LanePlan batch_plan;            // ... and what the launch reads of them (PrepareBatch; jxh_lane_plan.h)
+  lane_plan::LaneOverrides batch_overrides;  // the measurement aids the batch was planned under
   int batch_kernel = -1;
   // JXLHIP_LANES_PROF=2 (measurement aid): the per-wave records of the last kTimelineKeep lane-kernel launches
   Buf lanes_timeline;
   size_t timeline_launches = 0, timeline_stride = 0, timeline_wgs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int batch_order = -1;                  // JXLHIP_WG_ORDER the batch was planned under
-  std::vector<uint32_t> batch_wg_unit;   // (jxlhip_debug_entropy_order) workgroup -> unit as uploaded, and the
-  std::vector<uint64_t> batch_wg_est;    // estimate of every workgroup's unit (jxh_launch_order.h)
   std::vector<uint32_t> sec_size_host, sec_sel_host, pass_clusters, pass_log_alpha;
   // Coefficient layout of this frame (see TransformParams::scan_order); scan order is produced by k_entropy_lanes.
   // band decode: groups this context decodes (band + one group row either side), pixel rows it produces
@@ -329,8 +324,6 @@ struct JxlHipContext {
   uint32_t order_offset_host[39] = {};
   std::vector<const JxlHipContext*> batch_ctxs;
   std::vector<uint64_t> batch_gens;
-  uint32_t batch_wgs = 0;
-  size_t batch_lds = 0;
   hipEvent_t batch_done = nullptr;
   // Set by jxlhip_run_entropy_batch on the contexts whose coefficients a launch on ANOTHER context's stream produces;
   // applied (hipStreamWaitEvent on this context's stream) by the next call that touches those results. Enqueuing the
@@ -462,6 +455,19 @@ static void FillPixelOutLayout(const JxlHipContext* c, jxlhip::PixelOut* po) {
 static int EnvInt(const char* name, int def) {
   const char* e = getenv(name);
   return e && *e ? atoi(e) : def;
+}
+// The measurement aids of the lane launch plan (jxh_lane_plan.h LaneOverrides). JXLHIP_WG_ORDER = 0 emits the lane kernel's
+// workgroups in frame order, 2 in frame order dealt over the XCDs (jxh_launch_order.h kDealt); 1, the default and what
+// any other value means: longest estimated unit first.
+static lane_plan::LaneOverrides LaneOverridesFromEnv() {
+  lane_plan::LaneOverrides o;
+  o.lanes_per_wave = EnvInt("JXLHIP_LANES", 0);
+  o.table_form = EnvInt("JXLHIP_GALIAS", -1);
+  o.a6 = EnvInt("JXLHIP_A6", 1);
+  o.wg_order = EnvInt("JXLHIP_WG_ORDER", 1);
+  if (o.wg_order < 0 || o.wg_order > 2) o.wg_order = 1;
+  o.wait_shift = uint32_t(EnvInt("JXLHIP_WAIT_SHIFT", 1));
+  return o;
 }
 
 extern "C" {
@@ -1855,18 +1861,19 @@ static int EndDownstreamBatch(JxlHipContext* const* ctxs, size_t n, bool filter_
 template <typename CoefT, bool AIDS, bool GALIAS, bool PREFIX = false, bool A6 = false>
 static int LaunchEntropyLanesW(JxlHipContext* c0) {
   auto k = jxlhip::k_entropy_lanes<CoefT, AIDS, GALIAS, PREFIX, A6>;
-  if (c0->batch_lds > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(c0->batch_lds)));
+  const lane_plan::LanePlan& P = c0->batch_plan;
+  if (P.lds > 48 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(P.lds)));
   jxlhip::EntropyLaneBatch b;
   b.params = c0->batch_params.as<jxlhip::EntropyParams>();
   uint8_t* blob = c0->batch_lanes.as<uint8_t>();
   b.wg_unit = c0->batch_map.as<uint32_t>();
   b.list = reinterpret_cast<const uint32_t*>(blob);
-  b.units = reinterpret_cast<const uint4*>(blob + c0->batch_off_units);
-  b.queue = reinterpret_cast<uint32_t*>(blob + c0->batch_off_queue);
-  b.wave_lanes = blob + c0->batch_off_wave_lanes;
-  HIP_TRY(hipMemsetAsync(b.queue, 0, c0->batch_units * 4, c0->stream));
-  b.wait_shift = c0->batch_wait_shift;
+  b.units = reinterpret_cast<const uint4*>(blob + P.off_units);
+  b.queue = reinterpret_cast<uint32_t*>(blob + P.off_queue);
+  b.wave_lanes = blob + P.off_wave_lanes;
+  HIP_TRY(hipMemsetAsync(b.queue, 0, P.units * 4, c0->stream));
+  b.wait_shift = P.wait_shift;
   b.refill_mask = jxlhip::kLanesAsmTrip<CoefT, GALIAS, PREFIX> ? 0u : jxlhip::kLanesRefillEvery - 1;
   b.extra_pass_min = jxlhip::kLanesExtraPassMin;
   b.debug = uint32_t(EnvInt("JXLHIP_LANES_DEBUG", 0));
@@ -1876,7 +1883,7 @@ static int LaunchEntropyLanesW(JxlHipContext* c0) {
   // for jxlhip_debug_entropy_timeline and not waited for, so that the launches around this one overlap it as they do unprofiled
   const int prof_mode = EnvInt("JXLHIP_LANES_PROF", 0);
   const bool prof = prof_mode != 0 && prof_mode != 2;
-  const size_t nwaves = c0->batch_wgs;
+  const size_t nwaves = P.wg_unit.size();
   if (AIDS && prof_mode == 2) {
     constexpr size_t kTimelineKeep = sizeof(c0->timeline_wgs) / sizeof(c0->timeline_wgs[0]);
     if (nwaves * 64 > c0->timeline_stride) {  // (the first launch, or a larger one: earlier records are dropped)
@@ -1896,7 +1903,7 @@ static int LaunchEntropyLanesW(JxlHipContext* c0) {
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.prof), nwaves * 64));
     HIP_TRY(hipMemsetAsync(b.prof, 0, nwaves * 64, c0->stream));
   }
-  hipLaunchKernelGGL(k, dim3(c0->batch_wgs), dim3(64), c0->batch_lds, c0->stream, b);
+  hipLaunchKernelGGL(k, dim3(uint32_t(P.wg_unit.size())), dim3(64), P.lds, c0->stream, b);
   HIP_TRY(hipGetLastError());
   if (b.started) {
     // "resident" = as many of its workgroups as the chip's LDS holds at once, less a margin (the rest start as the first
@@ -1907,8 +1914,8 @@ static int LaunchEntropyLanesW(JxlHipContext* c0) {
       cus = g_gate[c0->device].cus;
       lds_cu = g_gate[c0->device].lds_per_cu;
     }
-    const unsigned long long per_cu = c0->batch_lds ? lds_cu / c0->batch_lds : 8, cap = cus * (per_cu ? per_cu : 1) * 3 / 4;
-    GateAdvance(c0->device, c0->batch_wgs, cap);
+    const unsigned long long per_cu = P.lds ? lds_cu / P.lds : 8, cap = cus * (per_cu ? per_cu : 1) * 3 / 4;
+    GateAdvance(c0->device, P.wg_unit.size(), cap);
   }
   if (prof) {
     std::vector<unsigned long long> h(nwaves * 8);
@@ -1947,237 +1954,91 @@ static int LaunchEntropyLanesW(JxlHipContext* c0) {
 // memory; the last two also as the instrumented build (JXLHIP_LANES_DEBUG / JXLHIP_LANES_PROF, measurement aids).
 template <typename CoefT>
 static int LaunchEntropyLanes(JxlHipContext* c0) {
-  if (c0->batch_prefix) return LaunchEntropyLanesW<CoefT, false, true, true>(c0);
+  const lane_plan::LanePlan::Form form = c0->batch_plan.form;
+  if (form == lane_plan::LanePlan::kPrefix) return LaunchEntropyLanesW<CoefT, false, true, true>(c0);
   if constexpr (sizeof(CoefT) == 2) {
-    if (c0->batch_a6) return LaunchEntropyLanesW<CoefT, false, false, false, true>(c0);
+    if (form == lane_plan::LanePlan::kLds6) return LaunchEntropyLanesW<CoefT, false, false, false, true>(c0);
   }
+  const bool galias = form == lane_plan::LanePlan::kGlobal;
   if (EnvInt("JXLHIP_LANES_DEBUG", 0) || EnvInt("JXLHIP_LANES_PROF", 0))
-    return c0->batch_galias ? LaunchEntropyLanesW<CoefT, true, true>(c0) : LaunchEntropyLanesW<CoefT, true, false>(c0);
-  return c0->batch_galias ? LaunchEntropyLanesW<CoefT, false, true>(c0) : LaunchEntropyLanesW<CoefT, false, false>(c0);
+    return galias ? LaunchEntropyLanesW<CoefT, true, true>(c0) : LaunchEntropyLanesW<CoefT, true, false>(c0);
+  return galias ? LaunchEntropyLanesW<CoefT, false, true>(c0) : LaunchEntropyLanesW<CoefT, false, false>(c0);
 }
 
 template <typename CoefT>
 static int LaunchEntropyUniBatch(JxlHipContext* c0) {
   auto k = jxlhip::k_entropy_uni<CoefT, kEntropyWPG>;
-  if (c0->batch_lds > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(c0->batch_lds)));
+  const lane_plan::LanePlan& P = c0->batch_plan;
+  if (P.lds > 48 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(P.lds)));
   jxlhip::EntropyBatch b{c0->batch_params.as<jxlhip::EntropyParams>(), c0->batch_map.as<uint32_t>()};
-  hipLaunchKernelGGL(k, dim3(c0->batch_wgs), dim3(64 * kEntropyWPG), c0->batch_lds, c0->stream, b);
+  hipLaunchKernelGGL(k, dim3(uint32_t(P.wg_unit.size())), dim3(64 * kEntropyWPG), P.lds, c0->stream, b);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-// Builds (or re-uses) the description of a batch: parameter blocks, workgroup -> frame map and, for the lane-parallel
-// kernel, the lane -> section assignment (sections sorted by compressed size inside each frame so that the lanes of a
-// wave finish together; `lanes_per_wave` populated lanes per wave so that small batches still spread over all SIMDs).
+// Builds (or re-uses) the description of a batch in four steps: key, plan, place, remember. The plan (jxh_lane_plan.h) is
+// a function of the set, the device and the measurement aids, so these are the key; it holds the workgroup map and, for
+// the lane-parallel kernel, the lane -> section assignment, and stays in the context for the launch to read.
 static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n, int kernel) {
-  // measurement aid: JXLHIP_WG_ORDER = 0 emits the lane kernel's workgroups in frame order, 2 in frame order dealt over
-  // the XCDs (jxh_launch_order.h kDealt); 1, the default: longest estimated unit first
-  int wg_order = EnvInt("JXLHIP_WG_ORDER", 1);
-  if (wg_order < 0 || wg_order > 2) wg_order = 1;
-  bool same = c0->batch_ctxs.size() == n && c0->batch_kernel == kernel && c0->batch_order == wg_order;
+  const lane_plan::LaneOverrides overrides = LaneOverridesFromEnv();
+  bool same = c0->batch_ctxs.size() == n && c0->batch_kernel == kernel && c0->batch_overrides == overrides;
   for (size_t i = 0; same && i < n; i++) same = c0->batch_ctxs[i] == ctxs[i] && c0->batch_gens[i] == ctxs[i]->generation;
   if (same) return 0;
-  std::vector<jxlhip::EntropyParams> params(n);
-  std::vector<uint32_t> map, list, unit_desc;
-  std::vector<uint8_t> wave_lanes;
-  size_t lds = 0;
-  for (size_t i = 0; i < n; i++) params[i] = ctxs[i]->ep;
+
+  lane_plan::LanePlan plan;
   if (kernel == 2) {
-    // unit = the sections of one frame that share a histogram set (a workgroup stages ONE set's slice of the context
-    // map; the selector is read from the first bits of every section at upload). The lanes of a unit take its sections
-    // from a queue, largest first, so the split by lanes below only fixes HOW MANY lanes serve a unit:
-    //   * a launch lasts as long as its busiest lane, which cannot beat the unit's longest section, so a unit gets
-    //     about (its total cost) / (cost of its longest section) lanes: more would idle (typical 4K d1.0 frame: 135
-    //     sections of 12k-100k tokens, 60 lanes). The cost of a section is estimated as bytes + kSectionBytes (token
-    //     counts are unknown before decoding; a constant term dominates in sparse sections);
-    //   * small batches that leave SIMDs empty spread over up to one lane per section;
-    //   * the lanes of a unit are split evenly over its waves.
-    // One wave per workgroup: the waves of a workgroup slow each other down (a lone 4K frame, one lane per wave: 832
-    // cycles per trip with four waves per workgroup, 517 with two, 417 with one; 29.6 / 24.1 / 19.6 ms for the frame:
-    // profiles/r04_single_frame.txt), and a workgroup of its own per wave costs only another copy of the tables in LDS.
-    constexpr uint32_t kSectionBytes = 4000;
-    constexpr size_t kTargetWaves = 1024;
-    const int forced = EnvInt("JXLHIP_LANES", 0);  // measurement aid: lanes per wave
-    c0->batch_wait_shift = uint32_t(EnvInt("JXLHIP_WAIT_SHIFT", 1));
-    struct Unit {
-      uint32_t frame, sel, pass, begin, count, min_lanes, lanes;
-    };
-    std::vector<uint64_t> unit_est;
-    std::vector<uint32_t> unit_waves;
-    std::vector<Unit> units;
-    std::vector<uint32_t> order;
-    size_t min_total = 0, total_sections = 0;
+    std::vector<lane_plan::LaneFrame> frames(n);
     for (size_t i = 0; i < n; i++) {
       const JxlHipContext* c = ctxs[i];
-      for (uint32_t pass = 0; pass < c->np; pass++)
-      for (uint32_t sel = 0; sel < c->ep.num_hist; sel++) {
-        const uint32_t* sz = c->sec_size_host.data() + size_t(pass) * c->ng;    // [pass * num_groups + group]
-        const uint32_t* ssel = c->sec_sel_host.data() + size_t(pass) * c->ng;
-        order.clear();
-        for (uint32_t g : c->group_list) {
-          if (pass && sz[g] == 0 && !c->absent_sections.empty()) continue;  // (a partial frame: this pass of the group has not arrived)
-          if (ssel[g] == sel || (sel == 0 && ssel[g] >= c->ep.num_hist)) order.push_back(g);
-        }
-        if (order.empty()) continue;
-        std::stable_sort(order.begin(), order.end(), [sz](uint32_t a, uint32_t b) { return sz[a] > sz[b]; });
-        uint64_t total = 0;
-        for (uint32_t g : order) total += uint64_t(sz[g]) + kSectionBytes;
-        const uint64_t longest = uint64_t(sz[order[0]]) + kSectionBytes;
-        Unit u;
-        u.frame = uint32_t(i);
-        u.sel = sel;
-        u.pass = pass;
-        u.begin = uint32_t(list.size());
-        u.count = uint32_t(order.size());
-        u.min_lanes = uint32_t((total + longest - 1) / longest);
-        u.min_lanes = u.min_lanes > u.count ? u.count : (u.min_lanes ? u.min_lanes : 1);
-        u.lanes = u.min_lanes;
-        list.insert(list.end(), order.begin(), order.end());
-        min_total += u.min_lanes;
-        total_sections += u.count;
-        units.push_back(u);
-      }
+      frames[i] = {c->ng, c->np, c->ep.num_hist, c->ep.nctx, c->sec_size_host.data(), c->sec_sel_host.data(), c->group_list.data(),
+                   c->group_list.size(), !c->absent_sections.empty(), c->gbb_host.data(), c->gbb_host.size(), c->pass_clusters.data(),
+                   c->pass_log_alpha.data()};
     }
-    // lanes per wave: the fewest that fit all lanes into kTargetWaves waves (a trip costs ~900 + 20 * lanes cycles)
-    uint32_t lanes_per_wave = 1;
-    while (lanes_per_wave < 64 && (min_total + lanes_per_wave - 1) / lanes_per_wave > kTargetWaves) lanes_per_wave *= 2;
-    if (forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) lanes_per_wave = uint32_t(forced);
-    if (lanes_per_wave >= 32) {  // dense regime: all of a unit's lanes in one wave (a trip costs about the same for 14 or 55 lanes)
-      lanes_per_wave = 64;
-      for (Unit& u : units)  // the wave's spare lanes are free: shorter lists per lane
-        if (u.lanes < 64) u.lanes = u.count < 64 ? u.count : 64;
-    }
-    if (lanes_per_wave == 1 && min_total < kTargetWaves) {  // room to spare: more lanes per unit, up to one per section
-      const double grow = double(kTargetWaves) / double(min_total);
-      for (Unit& u : units) {
-        const uint32_t want = uint32_t(double(u.min_lanes) * grow);
-        u.lanes = want > u.count ? u.count : (want < u.min_lanes ? u.min_lanes : want);
-      }
-    }
-    for (const Unit& u : units) {
-      const uint32_t waves = (u.lanes + lanes_per_wave - 1) / lanes_per_wave;
-      const uint32_t unit_index = uint32_t(unit_desc.size() / 4);
-      {  // how long the unit will take: its queue replayed with the sections' estimated costs
-        const JxlHipContext* c = ctxs[u.frame];
-        const uint32_t* sz = c->sec_size_host.data() + size_t(u.pass) * c->ng;
-        std::vector<uint32_t> bytes(u.count), blocks(u.count);
-        for (uint32_t j = 0; j < u.count; j++) {
-          const uint32_t g = list[u.begin + j];
-          bytes[j] = sz[g];
-          blocks[j] = g + 1 < c->gbb_host.size() ? c->gbb_host[g + 1] - c->gbb_host[g] : 0;
-        }
-        unit_est.push_back(jxh::launch_order::UnitEstimate(bytes.data(), blocks.data(), u.count, u.lanes));
-        unit_waves.push_back(waves);
-      }
-      unit_desc.push_back(u.frame | u.sel << 16);
-      unit_desc.push_back(u.begin);
-      unit_desc.push_back(u.count);
-      unit_desc.push_back(u.pass);
-      for (uint32_t w = 0; w < waves; w++) {  // even split of the unit's lanes over its waves
-        const uint32_t cnt = u.lanes / waves + (w < u.lanes % waves ? 1u : 0u);
-        map.push_back(unit_index);
-        wave_lanes.push_back(uint8_t(cnt));
-      }
-    }
-    // The hardware starts workgroups in index order, and those of the next launch in the LDS slots that ending ones free:
-    // the longest units go first, so that what starts last is short (jxh_launch_order.h). Only the workgroup -> unit map
-    // is permuted; the waves of a unit stay adjacent.
-    {
-      const std::vector<uint32_t> from = jxh::launch_order::OrderWorkgroups(unit_est.data(), unit_waves.data(), units.size(), wg_order);
-      std::vector<uint32_t> map2(map.size());
-      std::vector<uint8_t> lanes2(map.size());
-      c0->batch_wg_est.resize(map.size());
-      for (size_t p = 0; p < from.size(); p++) {
-        map2[p] = map[from[p]];
-        lanes2[p] = wave_lanes[from[p]];
-        c0->batch_wg_est[p] = unit_est[map2[p]];
-      }
-      map.swap(map2);
-      wave_lanes.swap(lanes2);
-      c0->batch_wg_unit = map;
-    }
-    // LDS of the launch = the largest workgroup. With the alias tables in LDS a CU holds 160 KB / that many workgroups;
-    // when that leaves part of the launch waiting for a second round (libjxl-sized tables: 128 clusters x 2^6 slots are
-    // 64 KB), the tables stay in global memory instead: a cached global round trip on every token's serial chain, but
-    // every frame resident (JXLHIP_GALIAS = 0 / 1 forces either form: measurement aid)
-    // Between the two, for tables of up to 128 clusters and 8192 slots (128 x 2^6: what libjxl writes for large frames): the six-byte
-    // form of the tables in LDS (70 KB per frame: two frames per CU instead of one), when THAT leaves the launch resident.
-    size_t lds_by_form[3] = {0, 0, 0};
-    const size_t num_wgs = map.size();  // (`map` holds one unit per wave)
-    bool a6_ok = !c0->lane_prefix && c0->coef_bits == 16 && EnvInt("JXLHIP_A6", 1) != 0;
-    for (int form = 0; form < 3; form++)
-      for (size_t wg = 0; wg < num_wgs; wg++) {
-        const JxlHipContext* c = ctxs[unit_desc[size_t(map[wg]) * 4] & 0xFFFF];
-        const uint32_t up = unit_desc[size_t(map[wg]) * 4 + 3];  // the unit's pass
-        if (c->pass_log_alpha[up] > 7 || c->pass_clusters[up] > jxlhip::kLanesA6Clusters ||
-            (size_t(c->pass_clusters[up]) << c->pass_log_alpha[up]) > jxlhip::kLanesA6Slots)
-          a6_ok = false;
-        size_t l = jxlhip::LanesLdsLayout(1, c->ep.nctx, c->pass_clusters[up], c->pass_log_alpha[up], 0, 0, form == 0 && !c0->lane_prefix,
-                                          c0->lane_prefix, form == 2).wave0;
-        l += size_t(jxlhip::kLanesPerLaneBytes) * 64;
-        lds_by_form[form] = l > lds_by_form[form] ? l : lds_by_form[form];
-      }
-    int dev_cus = 256;
+    lane_plan::LaneBatchTraits traits;
+    traits.prefix = c0->lane_prefix;
+    traits.coef_bits = c0->coef_bits;
+    traits.lds_budget = kLdsBudget;
+    int dev_cus = int(traits.device_cus);  // (what a failing query leaves)
     (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c0->device);
-    const size_t resident = lds_by_form[0] ? size_t(dev_cus) * ((160 * 1024) / lds_by_form[0]) : num_wgs;
-    bool galias = lds_by_form[0] > kLdsBudget || resident < num_wgs;
-    const int forced_form = EnvInt("JXLHIP_GALIAS", -1);
-    if (forced_form == 0 && lds_by_form[0] <= kLdsBudget) galias = false;
-    if (forced_form == 1) galias = true;
-    if (c0->lane_prefix) galias = true;  // (prefix codes have no alias tables: the two forms are the same)
-    const size_t resident6 = lds_by_form[2] ? size_t(dev_cus) * ((160 * 1024) / lds_by_form[2]) : num_wgs;
-    const bool a6 = a6_ok && lds_by_form[2] <= kLdsBudget &&
-                    ((galias && forced_form != 1 && resident6 >= num_wgs) || EnvInt("JXLHIP_A6", 1) == 2);  // (2: whenever eligible; tests)
-    if (a6) galias = false;
-    c0->batch_a6 = a6;
-    c0->batch_galias = galias;
-    c0->batch_prefix = c0->lane_prefix;
-    lds = lds_by_form[a6 ? 2 : (galias ? 1 : 0)];
+    traits.device_cus = uint32_t(dev_cus);
+    plan = lane_plan::PlanLaneBatch(frames.data(), n, traits, overrides);
     if (EnvInt("JXLHIP_PACK_DEBUG", 0))
-      fprintf(stderr, "[pack] units %zu sections %zu lanes(min) %zu lanes/wave %u waves/wg 1 workgroups %zu lds %zu tables %s\n", units.size(),
-              total_sections, min_total, lanes_per_wave, map.size(), lds,
-              c0->lane_prefix ? "prefix" : (a6 ? "lds6" : (galias ? "global" : "lds8")));
+      fprintf(stderr, "[pack] units %zu sections %zu lanes(min) %zu lanes/wave %u waves/wg 1 workgroups %zu lds %zu tables %s\n", plan.units,
+              plan.total_sections, plan.min_lanes_total, plan.lanes_per_wave, plan.wg_unit.size(), plan.lds, lane_plan::FormName(plan.form));
   } else {
-    c0->batch_wg_unit.clear();
-    c0->batch_wg_est.clear();
+    std::vector<uint32_t> groups(n);
+    std::vector<size_t> table_bytes(n);
     for (size_t i = 0; i < n; i++) {
-      const uint32_t wgs = (ctxs[i]->ng + kEntropyWPG - 1) / kEntropyWPG;
-      for (uint32_t j = 0; j < wgs; j++) map.push_back(uint32_t(i) << 16 | j);
-      const size_t l = size_t(ctxs[i]->ep.lds_ctx_bytes) + ctxs[i]->ep.lds_alias_bytes + 1024 + kEntropyWPG * 5120;
-      lds = l > lds ? l : lds;
+      groups[i] = ctxs[i]->ng;
+      table_bytes[i] = size_t(ctxs[i]->ep.lds_ctx_bytes) + ctxs[i]->ep.lds_alias_bytes;
     }
+    plan = lane_plan::PlanUniBatch(groups.data(), table_bytes.data(), n, kEntropyWPG);
   }
+
+  std::vector<jxlhip::EntropyParams> params(n);
+  for (size_t i = 0; i < n; i++) params[i] = ctxs[i]->ep;
   int r;
   if ((r = c0->batch_params.Ensure(params.size() * sizeof(params[0])))) return r;
-  if ((r = c0->batch_map.Ensure(map.size() * 4))) return r;
+  if ((r = c0->batch_map.Ensure(plan.wg_unit.size() * 4))) return r;
   ParamCopy pc;
   if ((r = pc.Begin(c0))) return r;
   if ((r = pc.Add(c0->batch_params.p, params.data(), params.size() * sizeof(params[0])))) return r;
-  if ((r = pc.Add(c0->batch_map.p, map.data(), map.size() * 4))) return r;
-  if (!list.empty()) {
-    // one buffer: section list | unit descriptors (16-byte aligned) | queue counters | populated lanes per wave
-    const size_t o_units = (list.size() * 4 + 15) & ~size_t(15), o_queue = o_units + unit_desc.size() * 4;
-    const size_t o_wl = o_queue + unit_desc.size(), total = o_wl + wave_lanes.size();
-    std::vector<uint8_t> blob(total, 0);
-    memcpy(blob.data(), list.data(), list.size() * 4);
-    memcpy(blob.data() + o_units, unit_desc.data(), unit_desc.size() * 4);
-    memcpy(blob.data() + o_wl, wave_lanes.data(), wave_lanes.size());
-    if ((r = c0->batch_lanes.Ensure(total))) return r;
-    if ((r = pc.Add(c0->batch_lanes.p, blob.data(), total))) return r;
-    c0->batch_off_units = o_units;
-    c0->batch_off_queue = o_queue;
-    c0->batch_off_wave_lanes = o_wl;
-    c0->batch_units = unit_desc.size() / 4;
+  if ((r = pc.Add(c0->batch_map.p, plan.wg_unit.data(), plan.wg_unit.size() * 4))) return r;
+  if (!plan.list.empty()) {
+    std::vector<uint8_t> blob(plan.blob_bytes);
+    lane_plan::PackLaneBlob(plan, blob.data());
+    if ((r = c0->batch_lanes.Ensure(blob.size()))) return r;
+    if ((r = pc.Add(c0->batch_lanes.p, blob.data(), blob.size()))) return r;
   }
   if ((r = pc.End())) return r;
+
   c0->batch_ctxs.assign(ctxs, ctxs + n);
   c0->batch_gens.resize(n);
   for (size_t i = 0; i < n; i++) c0->batch_gens[i] = ctxs[i]->generation;
-  c0->batch_wgs = uint32_t(map.size());
-  c0->batch_lds = lds;
   c0->batch_kernel = kernel;
-  c0->batch_order = wg_order;
+  c0->batch_overrides = overrides;
+  c0->batch_plan = std::move(plan);
   return 0;
 }
 
@@ -3399,11 +3260,12 @@ int jxlhip_debug_pixel_route(JxlHipContext* c, uint32_t* route) {
 // in both arrays; entries past the batch's workgroups are set to 0xFFFFFFFF / 0.
 int jxlhip_debug_entropy_order(JxlHipContext* ctx0, uint32_t* wg_unit, uint64_t* est, size_t n) {
   if (!ctx0 || !wg_unit || !est) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (ctx0->batch_wg_unit.size() > n) return JXLHIP_ERR_INVALID_ARGUMENT;
+  const lane_plan::LanePlan& P = ctx0->batch_plan;
+  const size_t have = P.wg_est.size();  // (a scalar-form batch has no estimates and reports nothing)
+  if (have > n) return JXLHIP_ERR_INVALID_ARGUMENT;
   for (size_t i = 0; i < n; i++) {
-    const bool in = i < ctx0->batch_wg_unit.size();
-    wg_unit[i] = in ? ctx0->batch_wg_unit[i] : 0xFFFFFFFFu;
-    est[i] = in ? ctx0->batch_wg_est[i] : 0;
+    wg_unit[i] = i < have ? P.wg_unit[i] : 0xFFFFFFFFu;
+    est[i] = i < have ? P.wg_est[i] : 0;
   }
   return 0;
 }

@@ -1,4 +1,4 @@
-// Order of the workgroups of a batched k_entropy_lanes launch (jxl_hip_api.hip PrepareBatch): host only, no HIP types.
+// Order of the workgroups of a batched k_entropy_lanes launch (jxh_lane_plan.h PlanLaneBatch): host only, no HIP types.
 //
 // A unit (the sections of one frame that share a histogram set) lasts as long as its busiest lane. A launch ends with its
 // last unit, and the workgroups of the NEXT launch start in the LDS slots the ending ones free, in dispatch order: what
