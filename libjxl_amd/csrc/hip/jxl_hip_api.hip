@@ -18,6 +18,7 @@
 
 #include "../../../include/jxl_amd_hip.h"
 #include "../host/jxh_enc_shared.h"
+#include "../host/jxh_filter_plan.h"
 #include "../host/jxh_lane_plan.h"
 #include "../host/jxh_modular_upload_plan.h"
 #include "../host/jxh_resample_plan.h"
@@ -36,6 +37,7 @@ namespace upload = jxlhip::upload;
 namespace tensor_out = jxlhip::tensor_out;
 namespace resample = jxlhip::resample;
 namespace lane_plan = jxh::lane_plan;
+namespace filter_plan = jxh::filter_plan;
 
 namespace {
 #include "../host/afv_basis.inc"
@@ -352,17 +354,13 @@ struct JxlHipContext {
   hipEvent_t planes_event = nullptr;
   hipStream_t planes_stream = nullptr;
   // jxlhip_run_transform_batch / jxlhip_run_filter_color_batch: description of the frame set launched from this context
-  struct FilterGroup {
-    int key;  // gaborish * 4 + epf iterations, + 8: frames of the one-channel 8-bit form (JxlHipContext::gray8_fast)
-    uint32_t first, count, tiles_x, tiles_y;
-    bool u8srgb;  // every frame of the group writes 8-bit sRGB only (k_filter_rows2<true>)
-  };
+  // (fgroups: the filter launches, jxh_filter_plan.h; fb_params holds the frames' blocks in the plan's order)
   Buf tb_params, tb_desc, fb_params;
   std::vector<const JxlHipContext*> db_ctxs;
   std::vector<uint64_t> db_gens;
   uint32_t desc_begin[27] = {}, desc_count[27] = {};  // (entry 21: the 8x8 DCT varblocks of chroma-subsampled frames)
   uint32_t cs = 0;  // chroma-subsampled frame: hshift of channel c in bit 2 * c, vshift in bit 2 * c + 1 (0 = 4:4:4)
-  std::vector<FilterGroup> fgroups;
+  std::vector<filter_plan::FilterGroup> fgroups;
   hipEvent_t down_done = nullptr;
   uint64_t generation = 0;            // bumped by every jxlhip_frame_upload
   std::vector<PassBufs> pass_bufs;
@@ -430,8 +428,11 @@ static const JxlHipTensorOut* CallerTensor(const JxlHipContext* c) {
 // Room of the context's own pixel buffer for the frame: none while a tensor is bound.
 static size_t OwnPixelBytes(const JxlHipContext* c) { return c->tensor_bound ? 0 : size_t(c->oxs) * c->oys * OutPixelBytes(c); }
 
-// Where and how the generic writers store (PixelOut's layout half): the context's interleaved rows, or the bound tensor.
-static void FillPixelOutLayout(const JxlHipContext* c, jxlhip::PixelOut* po) {
+// The generic writers' block for an image of xsize x ysize: orientation and un-premultiplication, then where and how they
+// store: the context's interleaved rows, or the bound tensor.
+static void FillPixelOut(const JxlHipContext* c, uint32_t xsize, uint32_t ysize, float* alpha, jxlhip::PixelOut* po) {
+  po->alpha = alpha; po->xsize = xsize; po->ysize = ysize;
+  po->orient = c->out_orient | (c->out_unpremul ? 8u : 0u);
   po->type = OutType(c);
   po->nc = OutChannels(c);
   po->bits = OutBits(c);
@@ -1558,9 +1559,24 @@ static void FillFusedParams(const JxlHipContext* c, jxlhip::FusedFilterParams* p
     }
   }
 }
-static int FilterKey(const JxlHipContext* c) {
-  const int epf = c->epf_iters < 0 ? 0 : (c->epf_iters > 3 ? 3 : c->epf_iters);
-  return (c->tensor_fused ? 16 : 0) + (c->gray8_fast ? 8 : 0) + (c->gab ? 4 : 0) + epf;
+// Plans the filter launches of a set (jxh_filter_plan.h) into c0->fgroups; `fparams`: the frames' blocks in launch order.
+static int PlanFilterLaunches(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n, std::vector<jxlhip::FusedFilterParams>* fparams) {
+  std::vector<jxlhip::FusedFilterParams> blocks(n);
+  std::vector<filter_plan::FilterFrame> frames(n);
+  for (size_t i = 0; i < n; i++) {
+    const JxlHipContext* c = ctxs[i];
+    const jxlhip::FusedFilterParams& b = blocks[i];
+    FillFusedParams(c, &blocks[i]);
+    frames[i] = {filter_plan::FormOf(c->epf_iters, c->gab, c->gray8_fast, c->tensor_fused), c->xs, c->band_y1 - c->band_y0,
+                 b.f.rgb != nullptr, b.f.rgbf != nullptr, b.filtered != nullptr, b.f.linear_output != 0};
+  }
+  filter_plan::FilterPlan plan;
+  const int r = filter_plan::PlanFilterGroups(frames.data(), n, &plan);
+  if (r) return r;
+  c0->fgroups = std::move(plan.groups);
+  fparams->resize(n);
+  for (size_t j = 0; j < n; j++) (*fparams)[j] = blocks[plan.order[j]];
+  return 0;
 }
 // Builds (or re-uses) the description of a set of frames for the batched transform and filter launches.
 static int PrepareDownstream(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n) {
@@ -1587,28 +1603,10 @@ static int PrepareDownstream(JxlHipContext* c0, JxlHipContext* const* ctxs, size
     }
     c0->desc_count[s] = uint32_t(desc.size()) - c0->desc_begin[s];
   }
-  // filter launches: frames grouped by (gaborish, epf iterations), one grid z slice per frame
-  std::vector<size_t> order(n);
-  for (size_t i = 0; i < n; i++) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return FilterKey(ctxs[a]) < FilterKey(ctxs[b]); });
-  std::vector<jxlhip::FusedFilterParams> fparams(n);
-  c0->fgroups.clear();
-  for (size_t j = 0; j < n; j++) {
-    const JxlHipContext* c = ctxs[order[j]];
-    FillFusedParams(c, &fparams[j]);
-    const int key = FilterKey(c);
-    const uint32_t tx = (c->xs + jxlhip::kFusedTW - 1) / jxlhip::kFusedTW;
-    const uint32_t ty = (c->band_y1 - c->band_y0 + jxlhip::kFusedTH - 1) / jxlhip::kFusedTH;
-    if (c0->fgroups.empty() || c0->fgroups.back().key != key) c0->fgroups.push_back({key, uint32_t(j), 0, 0, 0, true});
-    JxlHipContext::FilterGroup& g = c0->fgroups.back();
-    g.count++;
-    g.u8srgb = g.u8srgb && fparams[j].f.rgb && !fparams[j].f.rgbf && !fparams[j].filtered && !fparams[j].f.linear_output;
-    // (a one-channel frame has no other form to fall back to: every other writer would put three bytes per pixel into its rows)
-    if (c->gray8_fast && !g.u8srgb) return JXLHIP_ERR_INVALID_ARGUMENT;
-    g.tiles_x = tx > g.tiles_x ? tx : g.tiles_x;
-    g.tiles_y = ty > g.tiles_y ? ty : g.tiles_y;
-  }
+  // filter launches: frames grouped by filter form, one grid z slice per frame
+  std::vector<jxlhip::FusedFilterParams> fparams;
   int r;
+  if ((r = PlanFilterLaunches(c0, ctxs, n, &fparams))) return r;
   if ((r = c0->tb_params.Ensure(n * sizeof(tparams[0])))) return r;
   if ((r = c0->tb_desc.Ensure((desc.size() + 1) * sizeof(uint2)))) return r;
   if ((r = c0->fb_params.Ensure(n * sizeof(fparams[0])))) return r;
@@ -1626,10 +1624,33 @@ static int PrepareDownstream(JxlHipContext* c0, JxlHipContext* const* ctxs, size
   return 0;
 }
 
-template <bool GAB, int EPF>
-static int LaunchFused(JxlHipContext* c0, const JxlHipContext::FilterGroup& g) {
-  auto k = jxlhip::k_filter_fused<GAB, EPF>;
-  constexpr size_t lds = jxlhip::FusedLdsBytes(GAB, EPF);
+typedef void (*FusedKernel)(const jxlhip::FusedFilterParams*);
+typedef void (*RowsKernel)(const jxlhip::FusedFilterParams*, int);
+// The tile kernel of a form with 0 or 3 EPF iterations.
+static FusedKernel FusedKernelOf(const filter_plan::FilterForm& f) {
+  static const FusedKernel kTable[2][2] = {  // [3 iterations][Gaborish]
+      {jxlhip::k_filter_fused<false, 0>, jxlhip::k_filter_fused<true, 0>},
+      {jxlhip::k_filter_fused<false, 3>, jxlhip::k_filter_fused<true, 3>}};
+  return kTable[f.epf == 3][f.gab];
+}
+// The row-streaming kernel of a form with 1 or 2 EPF iterations. The tensor writer has one form whatever the group writes;
+// the one-channel writer is an 8-bit sRGB form (PlanFilterGroups refuses a grey group that is not).
+static RowsKernel RowsKernelOf(const filter_plan::FilterForm& f, bool u8srgb) {
+  static const RowsKernel kTable[4][2][2] = {  // [writer][2 iterations][Gaborish]
+      {{jxlhip::k_filter_rows2<false, 1, false>, jxlhip::k_filter_rows2<false, 1>},
+       {jxlhip::k_filter_rows2<false, 2, false>, jxlhip::k_filter_rows2<false, 2>}},
+      {{jxlhip::k_filter_rows2<true, 1, false>, jxlhip::k_filter_rows2<true, 1>},
+       {jxlhip::k_filter_rows2<true, 2, false>, jxlhip::k_filter_rows2<true, 2>}},
+      {{jxlhip::k_filter_rows2<true, 1, false, true>, jxlhip::k_filter_rows2<true, 1, true, true>},
+       {jxlhip::k_filter_rows2<true, 2, false, true>, jxlhip::k_filter_rows2<true, 2, true, true>}},
+      {{jxlhip::k_filter_rows2<false, 1, false, false, true>, jxlhip::k_filter_rows2<false, 1, true, false, true>},
+       {jxlhip::k_filter_rows2<false, 2, false, false, true>, jxlhip::k_filter_rows2<false, 2, true, false, true>}}};
+  return kTable[f.tensor ? 3 : f.grey ? 2 : u8srgb ? 1 : 0][f.epf == 2][f.gab];
+}
+
+static int LaunchFused(JxlHipContext* c0, const filter_plan::FilterGroup& g) {
+  const FusedKernel k = FusedKernelOf(g.form);
+  const size_t lds = jxlhip::FusedLdsBytes(g.form.gab, g.form.epf);
   if (lds > 48 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
   for (uint32_t z = 0; z < g.count; z += 65535) {  // grid z limit
@@ -1641,36 +1662,30 @@ static int LaunchFused(JxlHipContext* c0, const JxlHipContext::FilterGroup& g) {
   return 0;
 }
 
-// (Gaborish +) EPF1 (the d1.0 configuration) or EPF1 + EPF2 (`epf` = 2): the row-streaming kernel, no LDS.
-static int LaunchFilterRows(JxlHipContext* c0, const JxlHipContext::FilterGroup& g, int epf, bool gab, bool gray = false) {
-  const uint32_t cols = g.tiles_x * jxlhip::kFusedTW, rows = g.tiles_y * jxlhip::kFusedTH;  // upper bounds of the group
-  const uint32_t gx = ((cols + jxlhip::kRows2Cols - 1) / jxlhip::kRows2Cols + jxlhip::kRowsWaves - 1) / jxlhip::kRowsWaves;
-  // strip height: every strip re-reads and re-filters 6 halo rows, so the taller the better as long as the launch still
-  // has several waves for each of the chip's 1024 SIMDs (256 measured no better than 64: 0.0374 / 0.0361 / 0.0374 ms per 4K frame)
-  uint32_t strip = jxlhip::kRowsStrip;
-  if (uint64_t(gx) * jxlhip::kRowsWaves * ((rows + 2 * strip - 1) / (2 * strip)) * g.count >= 6 * 1024) strip *= 2;
-  const uint32_t gy = (rows + strip - 1) / strip;
-  typedef void (*RowsKernel)(const jxlhip::FusedFilterParams*, int);
-  const RowsKernel k1t = jxlhip::k_filter_rows2<true, 1>, k1f = jxlhip::k_filter_rows2<false, 1>;
-  const RowsKernel k2t = jxlhip::k_filter_rows2<true, 2>, k2f = jxlhip::k_filter_rows2<false, 2>;
-  const RowsKernel n1t = jxlhip::k_filter_rows2<true, 1, false>, n1f = jxlhip::k_filter_rows2<false, 1, false>;
-  const RowsKernel n2t = jxlhip::k_filter_rows2<true, 2, false>, n2f = jxlhip::k_filter_rows2<false, 2, false>;
-  const RowsKernel k1g = jxlhip::k_filter_rows2<true, 1, true, true>, k2g = jxlhip::k_filter_rows2<true, 2, true, true>;
-  const RowsKernel n1g = jxlhip::k_filter_rows2<true, 1, false, true>, n2g = jxlhip::k_filter_rows2<true, 2, false, true>;
-  const RowsKernel k1x = jxlhip::k_filter_rows2<false, 1, true, false, true>, k2x = jxlhip::k_filter_rows2<false, 2, true, false, true>;
-  const RowsKernel n1x = jxlhip::k_filter_rows2<false, 1, false, false, true>, n2x = jxlhip::k_filter_rows2<false, 2, false, false, true>;
-  if (gray && !g.u8srgb) return JXLHIP_ERR_INVALID_ARGUMENT;
-  const bool tensor = (g.key & 16) != 0;  // (every frame of the group writes a caller's tensor: FilterKey)
-  const RowsKernel k = tensor ? (gab ? (epf == 2 ? k2x : k1x) : (epf == 2 ? n2x : n1x))
-                       : gray ? (gab ? (epf == 2 ? k2g : k1g) : (epf == 2 ? n2g : n1g))
-                       : gab ? (epf == 2 ? (g.u8srgb ? k2t : k2f) : (g.u8srgb ? k1t : k1f))
-                             : (epf == 2 ? (g.u8srgb ? n2t : n2f) : (g.u8srgb ? n1t : n1f));
+// (Gaborish +) EPF1 (the d1.0 configuration) or EPF1 + EPF2: the row-streaming kernel, no LDS.
+static int LaunchFilterRows(JxlHipContext* c0, const filter_plan::FilterGroup& g) {
+  const filter_plan::RowsGridDims d = filter_plan::RowsGrid(g.tiles_x, g.tiles_y, g.count);
+  const RowsKernel k = RowsKernelOf(g.form, g.u8srgb);
   for (uint32_t z = 0; z < g.count; z += 65535) {  // grid z limit
     const uint32_t zn = g.count - z < 65535 ? g.count - z : 65535;
     const jxlhip::FusedFilterParams* fp = c0->fb_params.as<jxlhip::FusedFilterParams>() + g.first + z;
-    hipLaunchKernelGGL(k, dim3(gx, gy, zn), dim3(64 * jxlhip::kRowsWaves), 0, c0->fstream, fp, int(strip));
+    hipLaunchKernelGGL(k, dim3(d.gx, d.gy, zn), dim3(64 * jxlhip::kRowsWaves), 0, c0->fstream, fp, int(d.strip));
   }
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// A launch per group of the set's plan, in the plan's order.
+static int LaunchFilterGroups(JxlHipContext* c0) {
+  for (const filter_plan::FilterGroup& g : c0->fgroups) {
+    int r;
+    switch (filter_plan::KernelOf(g.form)) {
+      case filter_plan::kFusedKernel: r = LaunchFused(c0, g); break;
+      case filter_plan::kRowsKernel: r = LaunchFilterRows(c0, g); break;
+      default: r = JXLHIP_ERR_INVALID_ARGUMENT;
+    }
+    if (r) return r;
+  }
   return 0;
 }
 
@@ -2311,6 +2326,108 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
   return 0;
 }
 
+// ---- The parameter blocks of the kernels behind the filters, each stated once: the VarDCT filter stage, the Modular passes
+// and the test entries fill them through these. The blocks come zeroed (memset: padding included).
+// Three dense or padded planes, `plane_stride` floats apart, and the rows the patch and spline kernels take (a test entry
+// builds one from its arguments).
+struct PlaneView {
+  float* planes;
+  uint32_t stride;
+  size_t plane_stride;
+  uint32_t xsize, y_begin, y_end;
+};
+static PlaneView FrameView(const JxlHipContext* c) {  // the filtered planes of a VarDCT frame, its band
+  return {c->plane[1].as<float>(), c->xp, size_t(c->xp) * c->yp, c->xs, c->band_y0, c->band_y1};
+}
+static PlaneView ModularView(const JxlHipContext* c) {  // the float planes of a Modular frame
+  return {c->spl_planes.as<float>(), c->mod.xs, size_t(c->mod.xs) * c->mod.ys, c->mod.xs, 0, c->mod.ys};
+}
+// The tables of the patches / splines / noise on the device: a context's (upload) or what a test entry staged.
+struct PatchTables {
+  const uint32_t *records, *row_start, *row_list;
+  const float* const* slot_planes;  // [4], as slot_w, slot_h
+  const uint32_t *slot_w, *slot_h;
+};
+struct PatchAlpha {  // the alpha plane the patches blend into (dense rows), and the reference frames' ([4])
+  float* plane;
+  size_t stride;
+  uint32_t premultiplied;
+  const float* const* slot;
+};
+struct SplineTables {
+  const float* segments;
+  const uint32_t *row_start, *row_segments;
+};
+struct NoiseTables {
+  float* raw;
+  uint32_t seed0, seed1;
+  const float* lut;  // [8]
+  float ytox, ytob;
+};
+static PatchTables PatchTablesOf(const JxlHipContext* c) {
+  return {c->pat_rec.as<uint32_t>(), c->pat_row_start.as<uint32_t>(), c->pat_row_list.as<uint32_t>(), c->pat_src, c->pat_src_w, c->pat_src_h};
+}
+static SplineTables SplineTablesOf(const JxlHipContext* c) {
+  return {c->spl_seg.as<float>(), c->spl_row_start.as<uint32_t>(), c->spl_row_seg.as<uint32_t>()};
+}
+static NoiseTables NoiseTablesOf(const JxlHipContext* c) {
+  return {c->noise.as<float>(), c->noise_seed[0], c->noise_seed[1], c->noise_lut, c->noise_ytox, c->noise_ytob};
+}
+// `alpha` NULL: the image has no alpha channel, or the patches leave it alone.
+static void FillPatchParams(const PlaneView& v, const PatchTables& t, const PatchAlpha* alpha, jxlhip::PatchParams* pp) {
+  pp->planes = v.planes; pp->stride = v.stride; pp->plane_stride = v.plane_stride;
+  pp->xsize = v.xsize; pp->y_begin = v.y_begin; pp->y_end = v.y_end;
+  pp->records = t.records; pp->row_start = t.row_start; pp->row_list = t.row_list;
+  for (int k = 0; k < 4; k++) {
+    pp->slot_planes[k] = t.slot_planes[k]; pp->slot_w[k] = t.slot_w[k]; pp->slot_h[k] = t.slot_h[k];
+    if (alpha) pp->slot_alpha[k] = alpha->slot[k];
+  }
+  if (!alpha) return;
+  pp->alpha = alpha->plane; pp->alpha_stride = alpha->stride; pp->premultiplied = alpha->premultiplied;
+}
+static void FillSplineParams(const PlaneView& v, const SplineTables& t, jxlhip::SplineParams* sp) {
+  sp->planes = v.planes; sp->stride = v.stride; sp->plane_stride = v.plane_stride;
+  sp->xsize = v.xsize; sp->y_begin = v.y_begin; sp->y_end = v.y_end;
+  sp->segments = t.segments; sp->row_start = t.row_start; sp->row_segments = t.row_segments;
+}
+// Three planes [3][yp][xp] of an image of xs x ys, and the rows the noise and colour kernels take.
+struct PaddedPlanes {
+  float* planes;
+  uint32_t xs, ys, xp, yp, y_begin, y_end;
+};
+static PaddedPlanes FilteredPlanes(const JxlHipContext* c) {  // the frame's resolution (what c->fp describes)
+  return {c->plane[1].as<float>(), c->xs, c->ys, c->xp, c->yp, c->band_y0, c->band_y1};
+}
+static PaddedPlanes UpsampledPlanes(const JxlHipContext* c) {  // the image's resolution, behind the upsampling
+  return {c->ups_planes.as<float>(), c->oxs, c->oys, (c->oxs + 7) & ~7u, c->oys, 0, c->oys};
+}
+// `xgroups`, `ngroups`: the 256 x 256 generator groups across and in all.
+static void FillNoiseParams(const PaddedPlanes& v, const NoiseTables& t, uint32_t xgroups, uint32_t ngroups, jxlhip::NoiseParams* np) {
+  np->raw = t.raw; np->planes = v.planes;
+  np->xsize = v.xs; np->ysize = v.ys; np->xp = v.xp; np->yp = v.yp;
+  np->xgroups = xgroups; np->ngroups = ngroups; np->seed[0] = t.seed0; np->seed[1] = t.seed1;
+  memcpy(np->lut, t.lut, sizeof(np->lut));
+  np->ytox = t.ytox; np->ytob = t.ytob;
+  np->y_begin = v.y_begin; np->y_end = v.y_end;
+}
+// The random planes of every group, then their high-pass onto `rows` rows of `columns` samples.
+static void LaunchNoise(const jxlhip::NoiseParams& np, uint32_t columns, uint32_t rows, hipStream_t st) {
+  hipLaunchKernelGGL(jxlhip::k_noise_random, dim3((np.ngroups * 8 + 63) / 64), dim3(64), 0, st, np);
+  hipLaunchKernelGGL(jxlhip::k_noise_add, dim3((columns + 63) / 64, (rows + 3) / 4), dim3(256), 0, st, np);
+}
+// The colour stage on `v`: the frame's constants (`fp`) with the geometry of the planes it reads.
+static void FillColorOutParams(const jxlhip::FilterParams& fp, const PaddedPlanes& v, const jxlhip::PixelOut& po, const JxlHipColorTarget& t,
+                               jxlhip::ColorOutParams* cp) {
+  cp->f = fp;  // (the frame's constants)
+  cp->f.in = v.planes;
+  cp->f.xs = v.xs; cp->f.ys = v.ys; cp->f.xp = v.xp; cp->f.yp = v.yp;
+  cp->f.y_begin = v.y_begin; cp->f.y_end = v.y_end;
+  cp->po = po; cp->t = t;
+}
+static void LaunchColorOut(const jxlhip::ColorOutParams& cp, hipStream_t st) {
+  hipLaunchKernelGGL(jxlhip::k_color_out, dim3((cp.f.xs + 63) / 64, (cp.f.y_end - cp.f.y_begin + 3) / 4), dim3(256), 0, st, cp);
+}
+
 // The parameter blocks of the passes behind the inverse transforms, one fill function per pass (false: the frame does not
 // take the pass); they live with the kernels' structs. Frames with patches / splines / kept XYB planes: colour samples to
 // float planes (kind 4), the patches (kind 6), then the splines (kind 5) over them (dec_cache.cc:193-201), then the output
@@ -2333,38 +2450,13 @@ static bool FillModPlanes(const JxlHipContext* c, jxlhip::ModOutput* o) {
   memcpy(o->xyb_factor, M.xyb_factor, sizeof(o->xyb_factor));
   return true;
 }
-static bool FillModPatches(const JxlHipContext* c, jxlhip::PatchParams* pp) {
-  if (!c->pat_positions) return false;
-  const JxlHipContext::Modular& M = c->mod;
-  pp->planes = c->spl_planes.as<float>();
-  pp->records = c->pat_rec.as<uint32_t>();
-  pp->row_start = c->pat_row_start.as<uint32_t>();
-  pp->row_list = c->pat_row_list.as<uint32_t>();
-  for (int k = 0; k < 4; k++) {
-    pp->slot_planes[k] = c->pat_src[k];
-    pp->slot_w[k] = c->pat_src_w[k];
-    pp->slot_h[k] = c->pat_src_h[k];
-  }
-  pp->stride = M.xs;
-  pp->plane_stride = size_t(M.xs) * M.ys;
-  pp->xsize = M.xs;
-  pp->y_begin = 0;
-  pp->y_end = M.ys;
-  return true;
+static bool FillModPatches(const JxlHipContext* c, jxlhip::PatchParams* pp) {  // (no alpha: upload refuses patches that use it)
+  if (c->pat_positions) FillPatchParams(ModularView(c), PatchTablesOf(c), nullptr, pp);
+  return c->pat_positions != 0;
 }
 static bool FillModSplines(const JxlHipContext* c, jxlhip::SplineParams* sp) {
-  if (!c->spl_segments) return false;
-  const JxlHipContext::Modular& M = c->mod;
-  sp->planes = c->spl_planes.as<float>();
-  sp->segments = c->spl_seg.as<float>();
-  sp->row_start = c->spl_row_start.as<uint32_t>();
-  sp->row_segments = c->spl_row_seg.as<uint32_t>();
-  sp->stride = M.xs;
-  sp->plane_stride = size_t(M.xs) * M.ys;
-  sp->xsize = M.xs;
-  sp->y_begin = 0;
-  sp->y_end = M.ys;
-  return true;
+  if (c->spl_segments) FillSplineParams(ModularView(c), SplineTablesOf(c), sp);
+  return c->spl_segments != 0;
 }
 static bool FillModOutput(const JxlHipContext* c, jxlhip::ModOutput* o) {  // (every frame: a set has at least one, so this launch always exists)
   const JxlHipContext::Modular& M = c->mod;
@@ -2386,11 +2478,7 @@ static bool FillModOutput(const JxlHipContext* c, jxlhip::ModOutput* o) {  // (e
   o->alpha_bits = M.alpha_bits;
   o->w = M.xs;
   o->h = M.ys;
-  o->po.alpha = nullptr;
-  o->po.xsize = M.xs;
-  o->po.ysize = M.ys;
-  o->po.orient = c->out_orient | (c->out_unpremul ? 8u : 0u);
-  FillPixelOutLayout(c, &o->po);
+  FillPixelOut(c, M.xs, M.ys, nullptr, &o->po);
   return true;
 }
 // One pass over the frames of a set that take it: a zeroed block each, one launch. `rows`: one workgroup per row (the
@@ -2608,6 +2696,112 @@ int jxlhip_run_transform_batch(JxlHipContext* const* ctxs, size_t n) {
   return EndDownstreamBatch(ctxs, n);
 }
 
+// ---- The steps of jxlhip_run_filter_color_batch behind the filters, each over the frames in the order given, on `ls`.
+// The patches, onto the filtered planes; where they blend the alpha channel, into a copy of the frame's alpha plane.
+static int LaunchPatches(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) {
+  for (size_t i = 0; i < n; i++) {
+    JxlHipContext* c = ctxs[i];
+    c->alpha_patched_valid = false;
+    if (!c->pat_positions) continue;
+    PatchAlpha alpha = {};
+    if (c->pat_uses_alpha) {  // the frame's alpha plane must be there by now (jxlhip_set_alpha); blended into a copy of it
+      const size_t bytes = size_t(c->xs) * c->ys * 4;
+      if (!c->have_alpha || c->alpha.cap < bytes) return JXLHIP_ERR_INVALID_ARGUMENT;
+      int ar = c->alpha_patched.Ensure(bytes);
+      if (ar) return ar;
+      HIP_TRY(hipMemcpyAsync(c->alpha_patched.p, c->alpha.p, bytes, hipMemcpyDeviceToDevice, ls));
+      alpha = {c->alpha_patched.as<float>(), c->xs, c->pat_premultiplied ? 1u : 0u, c->pat_src_alpha};
+      c->alpha_patched_valid = true;
+    }
+    jxlhip::PatchParams pp;
+    memset(&pp, 0, sizeof(pp));
+    FillPatchParams(FrameView(c), PatchTablesOf(c), c->pat_uses_alpha ? &alpha : nullptr, &pp);
+    hipLaunchKernelGGL(jxlhip::k_patches_add, dim3(c->band_y1 - c->band_y0), dim3(256), 0, ls, pp);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+static int LaunchSplines(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) {
+  for (size_t i = 0; i < n; i++) {
+    const JxlHipContext* c = ctxs[i];
+    if (!c->spl_segments) continue;
+    jxlhip::SplineParams sp;
+    memset(&sp, 0, sizeof(sp));
+    FillSplineParams(FrameView(c), SplineTablesOf(c), &sp);
+    hipLaunchKernelGGL(jxlhip::k_splines_add, dim3(c->band_y1 - c->band_y0), dim3(256), 0, ls, sp);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+// Noise onto the filtered planes of the frames coded at the image's resolution (upsampled frames: LaunchUpsampledWriter).
+static int LaunchFrameNoise(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) {
+  for (size_t i = 0; i < n; i++) {
+    const JxlHipContext* c = ctxs[i];
+    if (!c->has_noise || c->ups != 1) continue;
+    jxlhip::NoiseParams np;
+    memset(&np, 0, sizeof(np));
+    FillNoiseParams(FilteredPlanes(c), NoiseTablesOf(c), c->xg, c->ng, &np);
+    LaunchNoise(np, c->xs, c->band_y1 - c->band_y0, ls);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+// An upsampled frame: straight to pixels, or (noise, kept planes) to planes at the image's resolution, the noise onto
+// them, then the colour stage.
+static int LaunchUpsampledWriter(const JxlHipContext* c, const jxlhip::PixelOut& po, hipStream_t ls) {
+  const bool to_planes = c->has_noise || c->ups_kept;
+  const PaddedPlanes big = UpsampledPlanes(c);
+  jxlhip::UpsampleParams up;
+  up.f = c->fp;
+  up.f.in = c->plane[1].as<float>();
+  up.f.rgb = c->rgb.as<uint8_t>();
+  up.kernel = c->ups_kernel.as<float>();
+  up.n = c->ups;
+  up.oxs = c->oxs;
+  up.oys = c->oys;
+  up.po = po;
+  up.xyb_out = to_planes ? big.planes : nullptr;
+  up.oxp = to_planes ? big.xp : 0;
+  up.t = c->ct;
+  hipLaunchKernelGGL(jxlhip::k_upsample_color, dim3((c->xs + 63) / 64, (c->ys + 3) / 4), dim3(256), 0, ls, up);
+  HIP_TRY(hipGetLastError());
+  if (c->has_noise) {
+    jxlhip::NoiseParams np;
+    memset(&np, 0, sizeof(np));
+    const uint32_t xgroups = (c->oxs + 255) / 256;
+    FillNoiseParams(big, NoiseTablesOf(c), xgroups, xgroups * ((c->oys + 255) / 256), &np);
+    LaunchNoise(np, c->oxs, c->oys, ls);
+  }
+  if (to_planes) {
+    jxlhip::ColorOutParams cp;
+    FillColorOutParams(c->fp, big, po, c->ct, &cp);
+    LaunchColorOut(cp, ls);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+// The frames whose pixels the filter kernel did not write: the colour stage, or the upsampling in front of it.
+static int LaunchPixelWriters(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) {
+  for (size_t i = 0; i < n; i++) {
+    const JxlHipContext* c = ctxs[i];
+    if (c->ups == 1 && !c->color_out) continue;
+    jxlhip::PixelOut po;
+    memset(&po, 0, sizeof(po));
+    if (c->color_out)
+      FillPixelOut(c, c->oxs, c->oys, c->have_alpha ? (c->alpha_patched_valid ? c->alpha_patched.as<float>() : c->alpha.as<float>()) : nullptr, &po);
+    if (c->ups != 1) {
+      const int r = LaunchUpsampledWriter(c, po, ls);
+      if (r) return r;
+      continue;
+    }
+    jxlhip::ColorOutParams cp;
+    FillColorOutParams(c->fp, FilteredPlanes(c), po, c->ct, &cp);
+    LaunchColorOut(cp, ls);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
 int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
   int r = BeginDownstreamBatch(ctxs, n, true);
   if (r) return r;
@@ -2615,175 +2809,11 @@ int jxlhip_run_filter_color_batch(JxlHipContext* const* ctxs, size_t n) {
   const hipStream_t ls = c0->fstream;
   if ((r = TensorsBeforeWriters(ctxs, n, ls))) return r;
   HIP_TRY(hipEventRecord(c0->ev[4], ls));
-  for (const JxlHipContext::FilterGroup& g : c0->fgroups) {
-    const bool gray = (g.key & 8) != 0;  // (only frames of the row-streaming kernel: set at upload)
-    if ((g.key & 16) && (g.key & 3) != 1 && (g.key & 3) != 2) return JXLHIP_ERR_INVALID_ARGUMENT;  // (the tensor form is the row-streaming kernel's)
-    switch (g.key & 7) {
-      case 0: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<false, 0>(c0, g); break;
-      case 1: r = LaunchFilterRows(c0, g, 1, false, gray); break;
-      case 2: r = LaunchFilterRows(c0, g, 2, false, gray); break;
-      case 3: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<false, 3>(c0, g); break;
-      case 4: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<true, 0>(c0, g); break;
-      case 5: r = LaunchFilterRows(c0, g, 1, true, gray); break;
-      case 6: r = LaunchFilterRows(c0, g, 2, true, gray); break;
-      default: r = gray ? JXLHIP_ERR_INVALID_ARGUMENT : LaunchFused<true, 3>(c0, g); break;
-    }
-    if (r) return r;
-  }
-  for (size_t i = 0; i < n; i++) {
-    JxlHipContext* c = ctxs[i];
-    c->alpha_patched_valid = false;
-    if (!c->pat_positions) continue;
-    jxlhip::PatchParams pp;
-    memset(&pp, 0, sizeof(pp));
-    if (c->pat_uses_alpha) {  // the frame's alpha plane must be there by now (jxlhip_set_alpha); blended into a copy of it
-      const size_t bytes = size_t(c->xs) * c->ys * 4;
-      if (!c->have_alpha || c->alpha.cap < bytes) return JXLHIP_ERR_INVALID_ARGUMENT;
-      int ar = c->alpha_patched.Ensure(bytes);
-      if (ar) return ar;
-      HIP_TRY(hipMemcpyAsync(c->alpha_patched.p, c->alpha.p, bytes, hipMemcpyDeviceToDevice, ls));
-      pp.alpha = c->alpha_patched.as<float>();
-      pp.alpha_stride = c->xs;
-      pp.premultiplied = c->pat_premultiplied ? 1 : 0;
-      for (int k = 0; k < 4; k++) pp.slot_alpha[k] = c->pat_src_alpha[k];
-      c->alpha_patched_valid = true;
-    }
-    pp.planes = c->plane[1].as<float>();
-    pp.records = c->pat_rec.as<uint32_t>();
-    pp.row_start = c->pat_row_start.as<uint32_t>();
-    pp.row_list = c->pat_row_list.as<uint32_t>();
-    for (int k = 0; k < 4; k++) {
-      pp.slot_planes[k] = c->pat_src[k];
-      pp.slot_w[k] = c->pat_src_w[k];
-      pp.slot_h[k] = c->pat_src_h[k];
-    }
-    pp.stride = c->xp;
-    pp.plane_stride = size_t(c->xp) * c->yp;
-    pp.xsize = c->xs;
-    pp.y_begin = c->band_y0;
-    pp.y_end = c->band_y1;
-    hipLaunchKernelGGL(jxlhip::k_patches_add, dim3(c->band_y1 - c->band_y0), dim3(256), 0, ls, pp);
-    HIP_TRY(hipGetLastError());
-  }
-  for (size_t i = 0; i < n; i++) {
-    const JxlHipContext* c = ctxs[i];
-    if (!c->spl_segments) continue;
-    jxlhip::SplineParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.planes = c->plane[1].as<float>();
-    sp.segments = c->spl_seg.as<float>();
-    sp.row_start = c->spl_row_start.as<uint32_t>();
-    sp.row_segments = c->spl_row_seg.as<uint32_t>();
-    sp.stride = c->xp;
-    sp.plane_stride = size_t(c->xp) * c->yp;
-    sp.xsize = c->xs;
-    sp.y_begin = c->band_y0;
-    sp.y_end = c->band_y1;
-    hipLaunchKernelGGL(jxlhip::k_splines_add, dim3(c->band_y1 - c->band_y0), dim3(256), 0, ls, sp);
-    HIP_TRY(hipGetLastError());
-  }
-  for (size_t i = 0; i < n; i++) {
-    const JxlHipContext* c = ctxs[i];
-    if (!c->has_noise || c->ups != 1) continue;  // (upsampled frames: behind the upsampling, below)
-    jxlhip::NoiseParams np;
-    memset(&np, 0, sizeof(np));
-    np.raw = c->noise.as<float>();
-    np.planes = c->plane[1].as<float>();
-    np.xsize = c->xs;
-    np.ysize = c->ys;
-    np.xp = c->xp;
-    np.yp = c->yp;
-    np.xgroups = c->xg;
-    np.ngroups = c->ng;
-    np.seed[0] = c->noise_seed[0];
-    np.seed[1] = c->noise_seed[1];
-    memcpy(np.lut, c->noise_lut, sizeof(np.lut));
-    np.ytox = c->noise_ytox;
-    np.ytob = c->noise_ytob;
-    np.y_begin = c->band_y0;
-    np.y_end = c->band_y1;
-    hipLaunchKernelGGL(jxlhip::k_noise_random, dim3((c->ng * 8 + 63) / 64), dim3(64), 0, ls, np);
-    hipLaunchKernelGGL(jxlhip::k_noise_add, dim3((c->xs + 63) / 64, (c->band_y1 - c->band_y0 + 3) / 4), dim3(256), 0, ls, np);
-    HIP_TRY(hipGetLastError());
-  }
-  for (size_t i = 0; i < n; i++) {
-    const JxlHipContext* c = ctxs[i];
-    if (c->ups == 1 && !c->color_out) continue;
-    jxlhip::PixelOut po;
-    memset(&po, 0, sizeof(po));
-    if (c->color_out) {
-      po.alpha = c->have_alpha ? (c->alpha_patched_valid ? c->alpha_patched.as<float>() : c->alpha.as<float>()) : nullptr;
-      po.xsize = c->oxs;
-      po.ysize = c->oys;
-      po.orient = c->out_orient | (c->out_unpremul ? 8u : 0u);
-      FillPixelOutLayout(c, &po);
-    }
-    if (c->ups == 1) {
-      jxlhip::ColorOutParams cp;
-      cp.f = c->fp;
-      cp.f.in = c->plane[1].as<float>();
-      cp.po = po;
-      cp.t = c->ct;
-      hipLaunchKernelGGL(jxlhip::k_color_out, dim3((c->xs + 63) / 64, (c->band_y1 - c->band_y0 + 3) / 4), dim3(256), 0, ls, cp);
-      HIP_TRY(hipGetLastError());
-      continue;
-    }
-    jxlhip::UpsampleParams up;
-    up.f = c->fp;
-    up.f.in = c->plane[1].as<float>();
-    up.f.rgb = c->rgb.as<uint8_t>();
-    up.kernel = c->ups_kernel.as<float>();
-    up.n = c->ups;
-    up.oxs = c->oxs;
-    up.oys = c->oys;
-    up.po = po;
-    up.xyb_out = nullptr;
-    up.oxp = 0;
-    up.t = c->ct;
-    const bool to_planes = c->has_noise || c->ups_kept;
-    if (to_planes) {  // upsample to planes, add the noise at the image's resolution, then the colour stage
-      up.xyb_out = c->ups_planes.as<float>();
-      up.oxp = (c->oxs + 7) & ~7u;
-    }
-    hipLaunchKernelGGL(jxlhip::k_upsample_color, dim3((c->xs + 63) / 64, (c->ys + 3) / 4), dim3(256), 0, ls, up);
-    HIP_TRY(hipGetLastError());
-    if (c->has_noise) {
-      jxlhip::NoiseParams np;
-      memset(&np, 0, sizeof(np));
-      np.raw = c->noise.as<float>();
-      np.planes = up.xyb_out;
-      np.xsize = c->oxs;
-      np.ysize = c->oys;
-      np.xp = up.oxp;
-      np.yp = c->oys;
-      np.xgroups = (c->oxs + 255) / 256;
-      np.ngroups = np.xgroups * ((c->oys + 255) / 256);
-      np.seed[0] = c->noise_seed[0];
-      np.seed[1] = c->noise_seed[1];
-      memcpy(np.lut, c->noise_lut, sizeof(np.lut));
-      np.ytox = c->noise_ytox;
-      np.ytob = c->noise_ytob;
-      np.y_begin = 0;
-      np.y_end = c->oys;
-      hipLaunchKernelGGL(jxlhip::k_noise_random, dim3((np.ngroups * 8 + 63) / 64), dim3(64), 0, ls, np);
-      hipLaunchKernelGGL(jxlhip::k_noise_add, dim3((c->oxs + 63) / 64, (c->oys + 3) / 4), dim3(256), 0, ls, np);
-    }
-    if (to_planes) {
-      jxlhip::ColorOutParams cp;
-      cp.f = c->fp;
-      cp.f.in = up.xyb_out;
-      cp.f.xs = c->oxs;
-      cp.f.ys = c->oys;
-      cp.f.xp = up.oxp;
-      cp.f.yp = c->oys;
-      cp.f.y_begin = 0;
-      cp.f.y_end = c->oys;
-      cp.po = po;
-      cp.t = c->ct;
-      hipLaunchKernelGGL(jxlhip::k_color_out, dim3((c->oxs + 63) / 64, (c->oys + 3) / 4), dim3(256), 0, ls, cp);
-      HIP_TRY(hipGetLastError());
-    }
-  }
+  if ((r = LaunchFilterGroups(c0))) return r;
+  if ((r = LaunchPatches(ctxs, n, ls))) return r;
+  if ((r = LaunchSplines(ctxs, n, ls))) return r;
+  if ((r = LaunchFrameNoise(ctxs, n, ls))) return r;
+  if ((r = LaunchPixelWriters(ctxs, n, ls))) return r;
   if ((r = LaunchResample(ctxs, n, ls))) return r;
   HIP_TRY(hipEventRecord(c0->ev[5], ls));
   if ((r = TensorsAfterWriters(ctxs, n, ls))) return r;
@@ -3158,27 +3188,21 @@ static int DebugColor(JxlHipContext* c, const float* xyb, size_t n, int linear_o
   }
   hipError_t e = hipMemcpy(in.p, xyb, n * 12, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
+    jxlhip::PixelOut po;
+    memset(&po, 0, sizeof(po));
+    po.dst = out.p;
+    po.xsize = uint32_t(n);
+    po.ysize = 1;
+    po.type = 0;
+    po.nc = 3;
+    po.bits = 32;
+    jxlhip::SetInterleaved(&po, po.xsize);
     jxlhip::ColorOutParams cp;
     memset(&cp, 0, sizeof(cp));
-    cp.f = c->fp;
-    cp.f.in = in.as<float>();
-    cp.f.xs = cp.f.xp = uint32_t(n);
-    cp.f.ys = cp.f.yp = 1;
-    cp.f.y_begin = 0;
-    cp.f.y_end = 1;
+    FillColorOutParams(c->fp, {in.as<float>(), uint32_t(n), 1, uint32_t(n), 1, 0, 1}, po, t ? *t : JxlHipColorTarget{}, &cp);
     cp.f.linear_output = t ? 1 : linear_output;
-    if (t) {
-      memcpy(cp.f.opsin_inv, t->matrix, sizeof(cp.f.opsin_inv));
-      cp.t = *t;
-    }
-    cp.po.dst = out.p;
-    cp.po.xsize = uint32_t(n);
-    cp.po.ysize = 1;
-    cp.po.type = 0;
-    cp.po.nc = 3;
-    cp.po.bits = 32;
-    jxlhip::SetInterleaved(&cp.po, cp.po.xsize);
-    hipLaunchKernelGGL(jxlhip::k_color_out, dim3(uint32_t((n + 63) / 64), 1), dim3(256), 0, c->stream, cp);
+    if (t) memcpy(cp.f.opsin_inv, t->matrix, sizeof(cp.f.opsin_inv));
+    LaunchColorOut(cp, c->stream);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(rgb, out.p, n * 12, hipMemcpyDeviceToHost);
@@ -3222,21 +3246,10 @@ int jxlhip_debug_noise(JxlHipContext* c, const float* xyb, uint32_t xsize, uint3
   if (e == hipSuccess) {
     jxlhip::NoiseParams np;
     memset(&np, 0, sizeof(np));
-    np.raw = raw.as<float>();
-    np.planes = planes.as<float>();
-    np.xsize = np.xp = xsize;
-    np.ysize = np.yp = ysize;
-    np.xgroups = (xsize + 255) / 256;
-    np.ngroups = np.xgroups * ((ysize + 255) / 256);
-    np.seed[0] = seed0;
-    np.seed[1] = seed1;
-    memcpy(np.lut, lut, sizeof(np.lut));
-    np.ytox = ytox;
-    np.ytob = ytob;
-    np.y_begin = y_begin;
-    np.y_end = y_end;
-    hipLaunchKernelGGL(jxlhip::k_noise_random, dim3((np.ngroups * 8 + 63) / 64), dim3(64), 0, c->stream, np);
-    hipLaunchKernelGGL(jxlhip::k_noise_add, dim3((xsize + 63) / 64, (y_end - y_begin + 3) / 4), dim3(256), 0, c->stream, np);
+    const uint32_t xgroups = (xsize + 255) / 256;
+    FillNoiseParams({planes.as<float>(), xsize, ysize, xsize, ysize, y_begin, y_end}, {raw.as<float>(), seed0, seed1, lut, ytox, ytob}, xgroups,
+                    xgroups * ((ysize + 255) / 256), &np);
+    LaunchNoise(np, xsize, y_end - y_begin, c->stream);
     e = hipGetLastError();
     if (e == hipSuccess && raw_out) e = hipMemcpyAsync(raw_out, raw.p, bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(xyb_out, planes.p, bytes, hipMemcpyDeviceToHost, c->stream);
@@ -3741,30 +3754,23 @@ int jxlhip_debug_patches(JxlHipContext* c, const float* planes_in, const float* 
   if ((r = d.Put(0, planes_in, n * 12)) || (r = d.Put(1, alpha_in, n * 4)) || (r = d.Put(2, pt->records, size_t(pt->num_positions) * 32)) ||
       (r = d.Put(3, pt->row_start, (size_t(ysize) + 1) * 4)) || (r = d.Put(4, pt->row_list, size_t(pt->num_row_entries) * 4)))
     return r;
-  jxlhip::PatchParams pp;
-  memset(&pp, 0, sizeof(pp));
+  const float *slot_planes[4] = {}, *slot_alpha[4] = {};
+  uint32_t slot_w[4] = {}, slot_h[4] = {};
   for (int k = 0; k < 4; k++) {
     if (!pt->slot_planes[k]) continue;
     const size_t sn = size_t(pt->slot_w[k]) * pt->slot_h[k];
     if ((r = d.Put(5 + k, pt->slot_planes[k], sn * 12))) return r;
     if (alpha_in && (r = d.Put(9 + k, pt->slot_alpha[k], sn * 4))) return r;
-    pp.slot_planes[k] = d.b[5 + k].as<float>();
-    pp.slot_alpha[k] = d.b[9 + k].as<float>();
-    pp.slot_w[k] = pt->slot_w[k];
-    pp.slot_h[k] = pt->slot_h[k];
+    slot_planes[k] = d.b[5 + k].as<float>();
+    slot_alpha[k] = d.b[9 + k].as<float>();
+    slot_w[k] = pt->slot_w[k];
+    slot_h[k] = pt->slot_h[k];
   }
-  pp.planes = d.b[0].as<float>();
-  pp.alpha = d.b[1].as<float>();
-  pp.alpha_stride = xsize;
-  pp.premultiplied = pt->premultiplied ? 1 : 0;
-  pp.records = d.b[2].as<uint32_t>();
-  pp.row_start = d.b[3].as<uint32_t>();
-  pp.row_list = d.b[4].as<uint32_t>();
-  pp.stride = xsize;
-  pp.plane_stride = n;
-  pp.xsize = xsize;
-  pp.y_begin = y_begin;
-  pp.y_end = y_end;
+  const PatchAlpha alpha = {d.b[1].as<float>(), xsize, pt->premultiplied ? 1u : 0u, slot_alpha};  // (a null plane without alpha_in)
+  jxlhip::PatchParams pp;
+  memset(&pp, 0, sizeof(pp));
+  FillPatchParams({d.b[0].as<float>(), xsize, n, xsize, y_begin, y_end},
+                  {d.b[2].as<uint32_t>(), d.b[3].as<uint32_t>(), d.b[4].as<uint32_t>(), slot_planes, slot_w, slot_h}, &alpha, &pp);
   hipLaunchKernelGGL(jxlhip::k_patches_add, dim3(y_end - y_begin), dim3(256), 0, c->stream, pp);
   hipError_t e = hipGetLastError();
   const hipError_t es = hipStreamSynchronize(c->stream);  // (before the buffers go, whatever was enqueued)
@@ -3796,15 +3802,7 @@ int jxlhip_debug_splines(JxlHipContext* c, const float* planes_in, uint32_t xsiz
     return r;
   jxlhip::SplineParams P;
   memset(&P, 0, sizeof(P));
-  P.planes = d.b[0].as<float>();
-  P.segments = d.b[1].as<float>();
-  P.row_start = d.b[2].as<uint32_t>();
-  P.row_segments = d.b[3].as<uint32_t>();
-  P.stride = xsize;
-  P.plane_stride = n;
-  P.xsize = xsize;
-  P.y_begin = y_begin;
-  P.y_end = y_end;
+  FillSplineParams({d.b[0].as<float>(), xsize, n, xsize, y_begin, y_end}, {d.b[1].as<float>(), d.b[2].as<uint32_t>(), d.b[3].as<uint32_t>()}, &P);
   hipLaunchKernelGGL(jxlhip::k_splines_add, dim3(y_end - y_begin), dim3(256), 0, c->stream, P);
   hipError_t e = hipGetLastError();
   const hipError_t es = hipStreamSynchronize(c->stream);  // (before the buffers go, whatever was enqueued)

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "jxl_hip_color.h"
+#include "jxl_hip_filter_abi.h"
 #include "jxl_hip_kernels.h"
 
 namespace jxlhip {
@@ -41,7 +42,8 @@ struct FusedFilterParams {
   float t_scale[3], t_bias[3];
 };
 
-constexpr int kFusedTW = 64, kFusedTH = 16;  // 37 KB of LDS with a 3-pixel halo: two tiles fit beside an entropy workgroup
+// (kFusedTW x kFusedTH, the tile, and the row kernel's kRowsStrip / kRowsWaves / kRows2Cols: jxl_hip_filter_abi.h, shared with
+// the host's launch plan)
 constexpr int kFusedThreads = 512;  // 8 waves per tile: two resident tiles give every SIMD four waves to hide LDS latency
 constexpr int kFusedSigW = kFusedTW / 8 + 3, kFusedSigH = kFusedTH / 8 + 3;  // sigma blocks around a tile
 __host__ __device__ constexpr int FusedHalo(bool gab, int epf) {
@@ -377,8 +379,6 @@ __global__ __launch_bounds__(256) void k_upsample_plane(UpsamplePlaneParams P) {
 // the four SADs of stage_epf.cc:225-367 for pixel o are P_v(o - (1,0)), P_h(o - (0,1)), P_h(o), P_v(o): every P is
 // used by two pixels and computed once.
 constexpr int kRowsHalo = 3;                          // Gaborish 1 + EPF1 2
-constexpr int kRowsStrip = 64;                        // output rows per wave
-constexpr int kRowsWaves = 4;                         // waves (adjacent column groups) per workgroup
 
 __device__ __forceinline__ float FromLeft(float v) {  // the value held by the lane of column x - 1 (wave_shr:1)
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, true));
@@ -404,7 +404,6 @@ __device__ __forceinline__ float FmacFromRight(float acc, float v, float w) {
 // output); the inner horizontal neighbour of a pixel is the other element of the pair, the outer one comes from the
 // adjacent lane.
 typedef float f2 __attribute__((ext_vector_type(2)));
-constexpr int kRows2Cols = 120;  // output columns per wave: 128 - 2 * 4 (left halo rounded up to a whole pair)
 __device__ __forceinline__ f2 LeftOf(f2 v) { return f2{FromLeft(v.y), v.x}; }     // the columns x - 1 of the pair's columns
 __device__ __forceinline__ f2 RightOf(f2 v) { return f2{v.y, FromRight(v.x)}; }   // the columns x + 1
 __device__ __forceinline__ f2 Abs2(f2 v) { return __builtin_elementwise_abs(v); }
