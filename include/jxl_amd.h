@@ -91,6 +91,46 @@ int jxlamd_frame_debug_swap_blocks(JxlAmdFrame* frame, uint32_t i, uint32_t j);
 int jxlamd_frame_upload_band(const JxlAmdFrame* frame, JxlHipContext* ctx, uint32_t group_row_begin, uint32_t group_row_end);
 /* Output transfer function of the frame's pixels: 0 = sRGB, 1 = linear (JxlDecoderSetOutputColorProfile); before upload. */
 void jxlamd_frame_set_linear_output(JxlAmdFrame* frame, int linear);
+/* The colour stage the JxlDecoder gives a frame of an XYB image whose encoding is tagged by enums (or is grey), for callers
+ * of this frame-level API: rendered to `target` (NULL: the image's own encoding; PQ, HLG, P3, grey luminance rows ...)
+ * for `desired_intensity` (0 = the image's). Frames of other images keep the sRGB / linear stage. Before upload; returns
+ * non-zero (see jxlamd_last_error) for a target the stage cannot render. */
+int jxlamd_frame_set_color_output(JxlAmdFrame* frame, const JxlColorEncoding* target, float desired_intensity);
+
+/* ---- Reduced decode: the image at 1/8 scale from the frame's own DC image, which the first sections of the file hold.
+ * The reduced image of a frame of xsize_blocks x ysize_blocks 8x8 blocks has that size, ceil(xsize / 8) x ceil(ysize / 8).
+ * Sample (bx, by) is the frame's DC sample as a full decode builds it (DequantDC, compressed_dc.cc:201-296, then
+ * AdaptiveDCSmoothing unless the frame has kSkipAdaptiveDCSmoothing), through the frame's own colour stage and the output
+ * stage of the context (format, orientation, tensor and resized bindings at the reduced size). Gaborish, EPF and noise are
+ * NOT applied (noise is zero-mean and is left out silently). By the format's construction this is the 8x8 block mean of the
+ * image in XYB, exactly for DCT8 blocks and approximately under larger transforms. The definition is this project's own:
+ * the reference has no 1/8-size output (it draws DC-only frames at full size through its 8x upsampler).
+ *
+ * jxlamd_frame_dc_extent: from the headers and the TOC alone, *need = the number of leading bytes of the buffer that the
+ * reduced parse reads: the largest end of TOC sections 0 .. num_dc_groups (DC global and the DC groups; the TOC may be
+ * permuted), or the frame's end for a frame coded as one section. The buffer may be a prefix of the file, bare or in a
+ * `jxlc` box (a box whose declared end lies beyond the buffer is accepted here and by the reduced parse); too short for the
+ * headers and the TOC: fails with "truncated frame header", come back with more. */
+int jxlamd_frame_dc_extent(const uint8_t* data, size_t size, size_t* need);
+/* Parses the first frame for a reduced decode from the whole file or any prefix of at least `need` bytes ("truncated frame"
+ * with fewer): headers, TOC, the DC global section in full (its Modular tree may code the DC streams), then each DC group up
+ * to the end of its VarDCT DC stream, through the runner. No AC global section, no block lists. Refused, each with its own
+ * jxlamd_last_error text and before any DC group is decoded: a Modular frame; a first frame that is not a regular,
+ * full-canvas, is_last, kReplace frame (animations, layers, crops, reference-only and DC frames); kUseDcFrame; patches;
+ * splines; frame upsampling above 1; chroma subsampling; an image that is not XYB-encoded; a first frame that is the image's
+ * preview. Extra channels are
+ * accepted and ignored: the output is opaque colour. jxlamd_frame_upload / _upload_band refuse such a frame. */
+int jxlamd_frame_parse_reduced(const uint8_t* data, size_t size, JxlParallelRunner runner, void* runner_opaque, JxlAmdFrame** frame);
+int jxlamd_frame_is_reduced(const JxlAmdFrame* frame);
+/* width_height = {xsize_blocks, ysize_blocks}: the size of the reduced image (before the context's orientation). */
+void jxlamd_frame_reduced_size(const JxlAmdFrame* frame, uint32_t* width_height);
+/* Test access, as sized copies: the three coded integer planes X, Y, B ([3][ysize_blocks][xsize_blocks], `n` values of room)
+ * and the precision shift of every DC group (`groups` bytes of room); either may be NULL. A reduced frame or a whole one. */
+int jxlamd_frame_dc_quantised(const JxlAmdFrame* frame, int32_t* q, size_t n, uint8_t* extra_precision, size_t groups);
+/* Hands the DC image to a context (jxlhip_reduced_upload) with the colour description jxlamd_frame_upload would fill; then
+ * jxlhip_reduced_run. A reduced frame, or a whole one (it holds the same DC) that the reduced parse would have taken: the same
+ * refusals apply to it here. jxlamd_frame_set_linear_output / _set_color_output apply as before. */
+int jxlamd_frame_upload_reduced(const JxlAmdFrame* frame, JxlHipContext* ctx);
 /* Extra channels (alpha, ...) of the frame. jxlamd_frame_extra_pending() != 0: their data continues behind the
  * coefficients of the AC group sections; run the entropy stage, then jxlamd_frame_finish_extra() (which reads the section
  * end positions from the context). jxlamd_frame_extra_plane() returns channel `index` as xsize * ysize int32 samples

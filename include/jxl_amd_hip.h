@@ -374,6 +374,9 @@ int jxlhip_get_section_end_bits(JxlHipContext* ctx, uint32_t* bits, size_t n);
  *   "kend"         uint32 [num_blocks][3]: scan position after the last non-zero coefficient of a (varblock, channel);
  *                  frames decoded in scan order only (after the entropy stage)
  *   "transform_lists" uint32 [entries][2] = {strategy, varblock index}: the transform work lists in launch order
+ *   "dc"           float [3][ysize_blocks][xsize_blocks]: the DC image after smoothing, as the transform stage reads it; of a
+ *                  reduced upload (jxlhip_reduced_upload) after its run, only with option "keep_dc"
+ *   "inv_sigma"    float [ysize_blocks][xsize_blocks]: 1 / sigma of the EPF per block
  * Returns the number of bytes the buffer needs through *needed when dst is NULL. */
 int jxlhip_download(JxlHipContext* ctx, const char* name, void* dst, size_t dst_size, size_t* needed);
 
@@ -398,6 +401,8 @@ int jxlhip_download(JxlHipContext* ctx, const char* name, void* dst, size_t dst_
  * launches enqueued after it wait ON THE DEVICE (hipStreamWaitValue64) until its workgroups are resident. The wait has no
  * bound, hence off by default, and the library ignores the option when the runtime may run kernels one at a time
  * (AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING, GPU_MAX_HW_QUEUES=1, counter collection by rocprofv3).
+ * "keep_dc" = 1 (test aid; takes effect at the next jxlhip_reduced_upload): k_reduced_pixels also stores its smoothed DC
+ * planes for jxlhip_download("dc").
  * "blocking_sync" = 1 (process-wide for the context's device): host threads that wait for the device sleep instead of
  * spinning; for servers that pipeline frames over more host threads than they have CPUs to spare. */
 int jxlhip_set_option(JxlHipContext* ctx, const char* name, int value);
@@ -619,6 +624,45 @@ int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n);
 int jxlhip_modular_status(JxlHipContext* ctx, uint32_t* status, uint32_t* end_bits, size_t n);
 /* Test access: a channel buffer's int32 samples (w * h) after the run; synchronous. */
 int jxlhip_modular_download_buffer(JxlHipContext* ctx, uint32_t buffer, int32_t* dst, size_t n);
+
+/* ---- Reduced output: the 1/8-scale image of a VarDCT frame from its DC image alone (jxl_amd.h states what the image is).
+ * No AC entropy, no inverse transform, no loop filter: one kernel (k_reduced_pixels, csrc/hip/jxl_hip_reduced.h)
+ * dequantises the three coded integer planes (DequantDC), smooths them (AdaptiveDCSmoothing), runs the frame's colour stage
+ * and stores through the generic pixel writer, for all the contexts of a batch in one launch. The arithmetic is that of
+ * jxlhip_frame_upload's k_dc_dequant and k_dc_smooth (shared device functions): the DC planes agree bit for bit. */
+typedef struct JxlHipReducedDesc {
+  uint32_t xsize_blocks, ysize_blocks;   /* the size of the reduced image */
+  const int32_t* dc_quantised;           /* [3][ysize_blocks][xsize_blocks]: the coded integers of X, Y, B */
+  const uint8_t* dc_extra_precision;     /* per DC group of 256 x 256 blocks, row-major: the integers are in units of step /
+                                          * 2^this; NULL = 0, for a frame of one DC group only */
+  float dc_step[3];                      /* DC quantisation step of X, Y, B */
+  float dc_cfl_x, dc_cfl_b;              /* chroma from luma at DC */
+  uint32_t dc_smoothing;                 /* != 0: AdaptiveDCSmoothing (the frame has no kSkipAdaptiveDCSmoothing) */
+  float opsin_inv[9], opsin_bias[3];     /* the colour stage, as JxlHipFrameDesc's */
+  int32_t linear_output;                 /* 0 = sRGB transfer function, 1 = linear (XYB frames only) */
+  const struct JxlHipColorTarget* color_target; /* as JxlHipFrameDesc::color_target */
+} JxlHipReducedDesc;
+/* Copies the integers, the precision bytes and the kernel's descriptor to the device in ONE staged copy; allocates no
+ * coefficient buffer, no full-resolution plane and no AC table. The context's output settings apply at the reduced size:
+ * jxlhip_set_output_format (every type; 1 or 3 channels: 2 and 4 answer JXLHIP_ERR_UNSUPPORTED, the reduced image is opaque
+ * colour), _orientation, jxlhip_set_output_tensor, and jxlhip_set_output_resized with the box in reduced-image coordinates;
+ * the descriptor, the tensor and the resized binding are checked on the host at the reduced size (csrc/host/
+ * jxh_reduced_plan.h enum ReducedRule) and a refused one launches nothing. Output settings changed after the upload make
+ * jxlhip_reduced_run answer JXLHIP_ERR_INVALID_ARGUMENT: upload again.
+ * While a context holds a reduced upload, jxlhip_run_entropy / _transform / _filter_color, their _batch forms and
+ * jxlhip_run_all, jxlhip_halo_*, the jxlhip_canvas_* calls that take the context and jxlhip_download of anything but "dc"
+ * answer JXLHIP_ERR_UNSUPPORTED and launch nothing; jxlhip_frame_upload / jxlhip_modular_upload make it an ordinary context
+ * again. jxlhip_set_option(ctx, "keep_dc", 1) before the upload (test aid): the kernel also stores its smoothed DC planes
+ * for jxlhip_download(ctx, "dc") ([3][ysize_blocks][xsize_blocks] floats); off, the planes exist nowhere. */
+int jxlhip_reduced_upload(JxlHipContext* ctx, const JxlHipReducedDesc* desc);
+/* Writes the reduced image: jxlhip_download_pixels / _rgb8 hand it out, or the bound tensor holds it; a resized binding's two
+ * resample launches follow the kernel (the context renders f32 into its private buffer first, as for a full frame). The
+ * ordering against a tensor's consumer stream is jxlhip_set_output_tensor's, without a host wait. JXLHIP_ERR_INVALID_ARGUMENT on a
+ * context whose last upload was not a reduced one (JXLHIP_ERR_NO_FRAME: none at all). Stage time: which = 0. */
+int jxlhip_reduced_run(JxlHipContext* ctx);
+/* Same for `n` contexts of one device that each hold a reduced upload (any sizes, formats and bindings): ONE launch of the
+ * kernel, then one launch pair of the resampler for those with a resized binding. */
+int jxlhip_reduced_run_batch(JxlHipContext* const* ctxs, size_t n);
 
 /* ---- Canvas: the frames of a multi-frame codestream composed on the device (lib/jxl/blending.cc, alpha.cc,
  * render_pipeline/stage_blending.cc; dec_cache.cc:268-290 for where it sits: after the colour conversion, in the output

@@ -124,13 +124,19 @@ class Frame:
     INFO = ("xsize", "ysize", "xsize_blocks", "ysize_blocks", "num_groups", "num_dc_groups", "num_passes", "used_acs",
             "epf_iters", "gab", "coef_bits", "ac_bytes", "log_alpha", "num_clusters", "ctx_map_size")
 
-    def __init__(self, data, threads=0, frame_pos=0, frame_index=0):
-        """frame_pos / frame_index: a later frame of an animation (frame_pos = the `end` of the frame before it)."""
+    def __init__(self, data, threads=0, frame_pos=0, frame_index=0, reduced=False):
+        """frame_pos / frame_index: a later frame of an animation (frame_pos = the `end` of the frame before it).
+        reduced=True: the parse of a reduced decode (jxlamd_frame_parse_reduced): headers, TOC and the DC sections alone, from
+        the whole file or any prefix of at least frame_dc_extent(data) bytes; HipContext.upload_reduced takes the frame."""
         L = lib()
         self._data = bytes(data)  # must outlive upload
         self._h = ctypes.c_void_p()
+        self.reduced = bool(reduced)
+        if reduced and (frame_pos or frame_index):
+            raise ValueError("a reduced parse takes the first frame")
         L.jxlamd_frame_parse_at.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+        L.jxlamd_frame_parse_reduced.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
         L.jxlamd_frame_end.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
         L.jxlamd_frame_end.restype = ctypes.c_size_t
         runner = None
@@ -139,8 +145,11 @@ class Frame:
             pool = L.JxlThreadParallelRunnerCreate(None, threads)
             runner = ctypes.cast(L.JxlThreadParallelRunner, ctypes.c_void_p)
         try:
-            _check(L.jxlamd_frame_parse_at(self._data, len(self._data), frame_pos, frame_index, runner, pool, ctypes.byref(self._h)),
-                   "jxlamd_frame_parse_at")
+            if reduced:
+                _check(L.jxlamd_frame_parse_reduced(self._data, len(self._data), runner, pool, ctypes.byref(self._h)), "jxlamd_frame_parse_reduced")
+            else:
+                _check(L.jxlamd_frame_parse_at(self._data, len(self._data), frame_pos, frame_index, runner, pool, ctypes.byref(self._h)),
+                       "jxlamd_frame_parse_at")
         finally:
             if pool:
                 L.JxlThreadParallelRunnerDestroy(pool)
@@ -151,8 +160,43 @@ class Frame:
         L.jxlamd_frame_out_size(self._h, wh)
         self.info["out_xsize"], self.info["out_ysize"] = int(wh[0]), int(wh[1])  # the image (upsampled frames: > frame size)
         t = (ctypes.c_uint32 * 3)()
-        self.end = int(L.jxlamd_frame_end(self._h, t))  # byte offset behind the frame
+        self.end = int(L.jxlamd_frame_end(self._h, t))  # byte offset behind the frame (it may lie beyond a prefix given to a reduced parse)
         self.duration, self.is_last, self.timecode = int(t[0]), bool(t[1]), int(t[2])
+
+    def reduced_size(self):
+        """(width, height) of the reduced image: the frame's size in 8x8 blocks."""
+        L = lib()
+        L.jxlamd_frame_reduced_size.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        wh = (ctypes.c_uint32 * 2)()
+        L.jxlamd_frame_reduced_size(self._h, wh)
+        return int(wh[0]), int(wh[1])
+
+    def dc_quantised(self):
+        """Test access: (the coded DC integers of X, Y, B as int32 [3, ysize_blocks, xsize_blocks], the precision shift of
+        every DC group as uint8). A reduced frame or a whole one."""
+        L = lib()
+        L.jxlamd_frame_dc_quantised.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+        w, h = self.reduced_size()
+        q = np.empty((3, h, w), np.int32)
+        ep = np.empty(self.info["num_dc_groups"], np.uint8)
+        _check(L.jxlamd_frame_dc_quantised(self._h, q.ctypes.data, q.size, ep.ctypes.data, ep.size), "jxlamd_frame_dc_quantised")
+        return q, ep
+
+    def set_linear_output(self, linear=True):
+        """The sRGB transfer function (False) or none (True) on the way out; before upload."""
+        L = lib()
+        L.jxlamd_frame_set_linear_output.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.jxlamd_frame_set_linear_output.restype = None
+        L.jxlamd_frame_set_linear_output(self._h, 1 if linear else 0)
+
+    def set_color_output(self, target=None, desired_intensity=0.0):
+        """The colour stage the JxlDecoder gives an XYB image tagged with an enum encoding (PQ, HLG, P3, grey ...): rendered
+        to `target` (a ctypes JxlColorEncoding; None: the image's own encoding) for desired_intensity (0: the image's)
+        (jxlamd_frame_set_color_output); before upload."""
+        L = lib()
+        L.jxlamd_frame_set_color_output.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float]
+        _check(L.jxlamd_frame_set_color_output(self._h, None if target is None else ctypes.byref(target), desired_intensity),
+               "jxlamd_frame_set_color_output")
 
     def upsampling_kernels(self, factor):
         """The factor x factor 5x5 upsampling kernels the host builds from the image's coded or default weights."""
@@ -268,6 +312,17 @@ def _resized_out(ptr, nbytes, dtype, num_channels, strides, out_size, box, scale
     return d
 
 
+def frame_dc_extent(data):
+    """The number of leading bytes of `data` (the file or a prefix of it) that a reduced parse, Frame(data, reduced=True),
+    reads: up to the end of the DC sections. Raises JxlAmdError "truncated frame header" when `data` is too short to tell."""
+    L = lib()
+    L.jxlamd_frame_dc_extent.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    need = ctypes.c_size_t()
+    data = bytes(data)
+    _check(L.jxlamd_frame_dc_extent(data, len(data), ctypes.byref(need)), "jxlamd_frame_dc_extent")
+    return int(need.value)
+
+
 def frame_is_modular(data):
     """Whether the codestream's first frame is Modular-coded (ModFrame, upload_modular) or VarDCT (Frame, upload)."""
     L = lib()
@@ -376,6 +431,21 @@ class HipContext:
         b0, b1 = band if band else (0, 0)
         _check(lib().jxlamd_frame_upload_band(frame._h, self._h, b0, b1), "jxlamd_frame_upload_band")
         self.frame_info = dict(frame.info)
+
+    def upload_reduced(self, frame):
+        """The frame's DC image as a reduced (1/8-scale) image: a Frame(data, reduced=True) or a whole Frame. Then
+        run_reduced(); pixels() / rgb8() hand out the reduced image, or the bound tensor holds it."""
+        L = lib()
+        L.jxlamd_frame_upload_reduced.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.jxlamd_frame_upload_reduced(frame._h, self._h), "jxlamd_frame_upload_reduced")
+        w, h = frame.reduced_size()
+        self.frame_info = dict(frame.info)
+        self.frame_info["out_xsize"], self.frame_info["out_ysize"] = w, h
+
+    def run_reduced(self):
+        L = lib()
+        L.jxlhip_reduced_run.argtypes = [ctypes.c_void_p]
+        _check(L.jxlhip_reduced_run(self._h), "jxlhip_reduced_run")
 
     def halo_rows(self):
         """Rows of the neighbouring bands the filters of this band read (after an upload)."""
@@ -708,6 +778,30 @@ def run_modular_batch(ctxs):
     """Every stream of several resident Modular frames as one launch (jxlhip_modular_run_batch)."""
     arr = (ctypes.c_void_p * len(ctxs))(*[c._h for c in ctxs])
     _check(lib().jxlhip_modular_run_batch(arr, len(ctxs)), "jxlhip_modular_run_batch")
+
+
+def run_reduced_batch(ctxs):
+    """The reduced images of several contexts (upload_reduced) in one kernel launch (jxlhip_reduced_run_batch)."""
+    L = lib()
+    L.jxlhip_reduced_run_batch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+    arr = (ctypes.c_void_p * len(ctxs))(*[c._h for c in ctxs])
+    _check(L.jxlhip_reduced_run_batch(arr, len(ctxs)), "jxlhip_reduced_run_batch")
+
+
+def decode_reduced(data, data_type=2, num_channels=3, device=0, threads=0):
+    """One-shot helper: the image at 1/8 scale from the DC sections of a VarDCT codestream (or a prefix of at least
+    frame_dc_extent(data) bytes) -> ceil(H / 8) x ceil(W / 8) x C samples. Gaborish, EPF and noise are not applied. Raises
+    JxlAmdError with the parser's text for a stream the reduced parse refuses; there is no fallback to a full decode."""
+    f = Frame(data, threads, reduced=True)
+    c = HipContext(device)
+    try:
+        c.set_output_format(data_type, num_channels)
+        c.upload_reduced(f)
+        c.run_reduced()
+        return c.pixels()
+    finally:
+        c.close()
+        f.close()
 
 
 def decode_lossless(data, num_channels=3, data_type=2, device=0):

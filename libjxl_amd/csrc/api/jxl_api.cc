@@ -22,6 +22,7 @@
 #include "../host/jxh_color.h"
 #include "../host/jxh_frame.h"
 #include "../host/jxh_modframe.h"
+#include "jxl_amd_frame.h"
 
 namespace {
 thread_local std::string g_last_error;
@@ -42,14 +43,8 @@ jxh::ParallelFor MakeParallelFor(JxlParallelRunner runner, void* opaque) {
 }
 }  // namespace
 
-struct JxlAmdFrame {
-  jxh::FramePlan plan;
-  jxh::ColorOutput color;  // the output encoding the decoder asks of an XYB frame (PrepareColorOutput)
-  const uint8_t* data = nullptr;
-  size_t size = 0;
-  uint32_t coef_bits = 16;
-  std::vector<JxlHipPassDesc> pass_desc;
-};
+// (struct JxlAmdFrame: jxl_amd_frame.h)
+void jxlamd_internal::SetLastError(const std::string& text) { g_last_error = text; }
 
 extern "C" {
 
@@ -71,7 +66,7 @@ int jxlamd_frame_parse(const uint8_t* data, size_t size, JxlParallelRunner runne
 }
 
 static int ParseFrameAt(const uint8_t* data, size_t size, size_t frame_pos, size_t frame_index, JxlParallelRunner runner,
-                        void* runner_opaque, bool allow_partial, JxlAmdFrame** out);
+                        void* runner_opaque, bool allow_partial, JxlAmdFrame** out, bool reduced = false);
 int jxlamd_frame_parse_at(const uint8_t* data, size_t size, size_t frame_pos, size_t frame_index, JxlParallelRunner runner,
                           void* runner_opaque, JxlAmdFrame** out) {
   return ParseFrameAt(data, size, frame_pos, frame_index, runner, runner_opaque, false, out);
@@ -135,7 +130,7 @@ int jxlamd_frame_is_modular(const uint8_t* data, size_t size, uint32_t* modular)
 }
 
 static int ParseFrameAt(const uint8_t* data, size_t size, size_t frame_pos, size_t frame_index, JxlParallelRunner runner,
-                        void* runner_opaque, bool allow_partial, JxlAmdFrame** out) {
+                        void* runner_opaque, bool allow_partial, JxlAmdFrame** out, bool reduced) {
   g_last_error.clear();
   if (!data || !out) {
     g_last_error = "invalid argument";
@@ -145,6 +140,7 @@ static int ParseFrameAt(const uint8_t* data, size_t size, size_t frame_pos, size
   std::unique_ptr<JxlAmdFrame> f(new JxlAmdFrame);
   try {
     jxh::FrameParser parser(data, size);
+    if (reduced) parser.AllowCutContainer();
     jxh::ImageHeader ih;
     size_t pos = parser.ParseImageHeader(&ih);
     const bool first = !frame_pos || frame_pos == pos;
@@ -156,7 +152,7 @@ static int ParseFrameAt(const uint8_t* data, size_t size, size_t frame_pos, size
       ih.xsize = ih.preview_xsize;   // (frame_header.h:450-463)
       ih.ysize = ih.preview_ysize;
     }
-    parser.ParseFrame(pos, ih, &f->plan, MakeParallelFor(runner, runner_opaque), frame_index, 0, allow_partial);
+    parser.ParseFrame(pos, ih, &f->plan, MakeParallelFor(runner, runner_opaque), frame_index, 0, allow_partial, reduced);
     if (first && ih.have_preview && (f->plan.fh.frame_type != 0 || f->plan.fh.custom_size || f->plan.fh.blend.mode != 0))
       throw std::runtime_error("invalid preview frame");  // frame_header.cc:224-227, 372-376
   } catch (const std::exception& e) {
@@ -170,6 +166,63 @@ static int ParseFrameAt(const uint8_t* data, size_t size, size_t frame_pos, size
   max_bits += jxh::CeilLog2(f->plan.fh.num_passes);
   f->coef_bits = max_bits < 16 ? 16 : 32;
   *out = f.release();
+  return 0;
+}
+
+// ---- Reduced decode: the frame's own 1/8-scale image (its DC image), from the leading sections of the file alone.
+int jxlamd_frame_dc_extent(const uint8_t* data, size_t size, size_t* need) {
+  g_last_error.clear();
+  if (!data || !need) {
+    g_last_error = "invalid argument";
+    return 1;
+  }
+  try {
+    jxh::FrameParser parser(data, size);
+    parser.AllowCutContainer();
+    jxh::ImageHeader ih;
+    size_t pos = 0;
+    try {
+      pos = parser.ParseImageHeader(&ih);
+    } catch (const jxh::Error& e) {  // (the caller comes back with more bytes, whichever header ran out)
+      if (std::string(e.what()) == "truncated image header") throw jxh::Error("truncated frame header");
+      throw;
+    }
+    if (ih.have_preview) {
+      ih.xsize = ih.preview_xsize;
+      ih.ysize = ih.preview_ysize;
+    }
+    if (pos >= size) throw jxh::Error("truncated frame header");
+    jxh::FramePlan plan;
+    size_t extent = 0;
+    parser.ParseFrame(pos, ih, &plan, jxh::SerialFor, 0, 0, false, false, &extent);
+    *need = extent;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return 2;
+  }
+  return 0;
+}
+int jxlamd_frame_parse_reduced(const uint8_t* data, size_t size, JxlParallelRunner runner, void* runner_opaque, JxlAmdFrame** out) {
+  return ParseFrameAt(data, size, 0, 0, runner, runner_opaque, false, out, true);
+}
+int jxlamd_frame_is_reduced(const JxlAmdFrame* f) { return f && f->plan.reduced ? 1 : 0; }
+void jxlamd_frame_reduced_size(const JxlAmdFrame* f, uint32_t* wh) {
+  wh[0] = uint32_t(f->plan.dim.xsize_blocks);
+  wh[1] = uint32_t(f->plan.dim.ysize_blocks);
+}
+int jxlamd_frame_dc_quantised(const JxlAmdFrame* f, int32_t* q, size_t n, uint8_t* extra_precision, size_t groups) {
+  g_last_error.clear();
+  if (!f || f->plan.dc_q.empty()) {
+    g_last_error = "the frame holds no coded DC integers";
+    return 1;
+  }
+  const jxh::FramePlan& P = f->plan;
+  if ((q && n < P.dc_q.size()) || (extra_precision && groups < P.dc_extra_precision.size())) {
+    g_last_error = "invalid argument";
+    return 1;
+  }
+  if (q) memcpy(q, P.dc_q.data(), P.dc_q.size() * sizeof(int32_t));
+  if (extra_precision) memcpy(extra_precision, P.dc_extra_precision.data(), P.dc_extra_precision.size());
   return 0;
 }
 
@@ -347,6 +400,10 @@ int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t 
     return 1;
   }
   const jxh::FramePlan& P = f->plan;
+  if (P.reduced) {
+    g_last_error = "the frame was parsed for a reduced decode (jxlamd_frame_parse_reduced): jxlamd_frame_upload_reduced takes it";
+    return 1;
+  }
   JxlHipFrameDesc d;
   memset(&d, 0, sizeof(d));
   d.xsize = uint32_t(P.dim.xsize);
@@ -851,8 +908,47 @@ int jxlamd_modframe_upload(const JxlAmdModFrame* f, JxlHipContext* ctx) {
 }
 
 // ------------------------------------------------------------------------------------------------ JxlDecoder
+// ---- The colour stage of an XYB frame, stated once for the decoder (PrepareColorOutput) and for the frame-level callers
+// (jxlamd_frame_set_color_output). Which images take it: those tagged by enums, and an ICC-tagged grey one too (towards D65
+// grey with the sRGB or linear curve, for its luminance rows: the header's enum fields are the defaults then).
+static bool TakesColorStage(const jxh::ImageHeader& ih) { return ih.xyb_encoded && (!ih.want_icc || ih.gray); }
+// The stage's description for an image rendered to `dst` at desired_intensity (0: the image's own).
+static bool ColorTargetOf(const jxh::ImageHeader& ih, const JxlColorEncoding& dst, float desired_intensity, JxlHipColorTarget* t,
+                          std::string* err) {
+  JxlColorEncoding src;
+  jxh::EncodingFromHeader(ih, &src);
+  return jxh::MakeColorOutput(src, ih.intensity_target, dst, desired_intensity, ih.inv_opsin, t, err);
+}
+// What a frame keeps of it: the matrix, and the target itself where the generic writer has to render it.
+static void AdoptColorTarget(const JxlHipColorTarget& t, jxh::ColorOutput* out) {
+  const bool generic = jxh::NeedsGenericWriter(t);
+  out->active = true;
+  out->linear = generic || t.tf == JXLHIP_TF_LINEAR;
+  memcpy(out->matrix, t.matrix, sizeof(out->matrix));
+  if (generic) out->target = t;
+}
 void jxlamd_frame_set_linear_output(JxlAmdFrame* f, int linear) {
   if (f) f->plan.ih.linear_tf = linear != 0;
+}
+// The colour stage the JxlDecoder gives a frame of an XYB image with an enum-tagged (or grey) encoding, for callers of the
+// frame-level API: towards `target` (NULL: the image's own encoding) at desired_intensity (0: the image's). Other images
+// keep the default stage (sRGB or linear by jxlamd_frame_set_linear_output). Before the upload.
+int jxlamd_frame_set_color_output(JxlAmdFrame* f, const JxlColorEncoding* target, float desired_intensity) {
+  g_last_error.clear();
+  if (!f) return 1;
+  const jxh::ImageHeader& ih = f->plan.ih;
+  f->color = jxh::ColorOutput();
+  if (!TakesColorStage(ih)) return 0;
+  JxlColorEncoding own;
+  jxh::EncodingFromHeader(ih, &own);
+  JxlHipColorTarget t;
+  std::string err;
+  if (!ColorTargetOf(ih, target ? *target : own, desired_intensity, &t, &err)) {
+    g_last_error = err;
+    return 1;
+  }
+  AdoptColorTarget(t, &f->color);
+  return 0;
 }
 int jxlamd_frame_extra_pending(const JxlAmdFrame* f) { return f && f->plan.extra_pending ? 1 : 0; }
 int jxlamd_frame_finish_extra(JxlAmdFrame* f, JxlHipContext* ctx) { return jxlamd_frame_finish_extra_mt(f, ctx, nullptr, nullptr); }
@@ -1409,23 +1505,16 @@ static bool ToneMappedAfterBlending(const JxlDecoder* d, const jxh::FrameHeader&
 static JxlDecoderStatus PrepareColorOutput(JxlDecoder* d, const jxh::ImageHeader& ih, const jxh::FrameHeader& fh,
                                            jxh::ColorOutput* out) {
   *out = jxh::ColorOutput();
-  // (an ICC-tagged grey XYB image takes the stage too, towards D65 grey with the sRGB or linear curve, for its luminance rows:
-  // the header's enum fields are the defaults then)
-  if (!XybEnumImage(d) && !(d->ih.xyb_encoded && d->ih.gray)) return JXL_DEC_SUCCESS;
-  JxlColorEncoding src, dst;
-  jxh::EncodingFromHeader(ih, &src);
+  if (!TakesColorStage(d->ih)) return JXL_DEC_SUCCESS;
+  JxlColorEncoding dst;
   RenderedEncoding(d, &dst);
   JxlHipColorTarget t;
   std::string err;
-  if (!jxh::MakeColorOutput(src, ih.intensity_target, dst, d->desired_intensity, ih.inv_opsin, &t, &err)) return Fail(d, err);
-  const bool generic = jxh::NeedsGenericWriter(t);
+  if (!ColorTargetOf(ih, dst, d->desired_intensity, &t, &err)) return Fail(d, err);
   // (blending happens in the output encoding; the reference then tone-maps the blended, already encoded samples: not done here)
   if (t.tone && ToneMappedAfterBlending(d, fh))
     return Fail(d, "unsupported: tone mapping of a frame that is blended or kept for reference");
-  out->active = true;
-  out->linear = generic || t.tf == JXLHIP_TF_LINEAR;
-  memcpy(out->matrix, t.matrix, sizeof(out->matrix));
-  if (generic) out->target = t;
+  AdoptColorTarget(t, out);
   return JXL_DEC_SUCCESS;
 }
 

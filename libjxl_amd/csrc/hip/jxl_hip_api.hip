@@ -21,6 +21,7 @@
 #include "../host/jxh_filter_plan.h"
 #include "../host/jxh_lane_plan.h"
 #include "../host/jxh_modular_upload_plan.h"
+#include "../host/jxh_reduced_plan.h"
 #include "../host/jxh_resample_plan.h"
 #include "../host/jxh_tensor_out.h"
 #include "../host/jxh_upload_plan.h"
@@ -32,7 +33,9 @@
 #include "jxl_hip_canvas.h"
 #include "jxl_hip_dc.h"
 #include "jxl_hip_resample.h"
+#include "jxl_hip_reduced.h"
 
+namespace reduced = jxlhip::reduced;
 namespace upload = jxlhip::upload;
 namespace tensor_out = jxlhip::tensor_out;
 namespace resample = jxlhip::resample;
@@ -391,6 +394,21 @@ struct JxlHipContext {
   Buf rs_block, rs_tmp, rs_src, rs_batch;
   std::vector<const JxlHipContext*> rs_batch_ctxs;
   std::vector<uint64_t> rs_batch_gens;
+  // jxlhip_reduced_upload: the context holds the inputs of a reduced image instead of a frame (have_frame and mod.have are
+  // then both false). red_block (placed at upload, one staged copy): the kernel's descriptor, the DC groups' precision bytes
+  // and the coded integers (jxh_reduced_plan.h BlockLayout); red.dev: the descriptor's host copy, from which a batched launch
+  // builds its array (red_batch on the launch's first context, kept while the set stays the same). The pixels go to `rgb`
+  // or the bound tensor, the kept DC planes (option "keep_dc") to `dc`.
+  bool keep_dc = false;
+  struct Reduced {
+    bool have = false, ran = false, dc_kept = false;
+    uint64_t generation = 0;  // the context's, as the upload left it: output settings changed since ask for another upload
+    jxlhip::ReducedDev dev{};
+    std::vector<const JxlHipContext*> batch_ctxs;
+    std::vector<uint64_t> batch_gens;
+    uint32_t batch_tiles = 0;
+  } red;
+  Buf red_block, red_batch;
 };
 
 // JXLHIP_ENTROPY=1 (a test hook): no frame takes the lane-parallel k_entropy_lanes, every frame the wave-per-section
@@ -633,7 +651,7 @@ static std::vector<Buf*> AllBufs(JxlHipContext* c) {
                 &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in, &c->enc_mask1x1,
                 &c->est_planes, &c->est_qf, &c->est_mask, &c->est_ytox, &c->est_ytob, &c->est_dq, &c->est_cand, &c->est_index, &c->est_at, &c->est_out, &c->est_scaled,
                 &c->srch_mask, &c->srch_zero, &c->srch_cand, &c->srch_index, &c->srch_table, &c->walk_table, &c->walk_acs, &c->walk_entropy,
-                &c->rs_block, &c->rs_tmp, &c->rs_src, &c->rs_batch, &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
+                &c->rs_block, &c->rs_tmp, &c->rs_src, &c->rs_batch, &c->red_block, &c->red_batch, &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
   for (auto& pb : c->pass_bufs)
     for (Buf* b : {&pb.ctx_map, &pb.alias, &pb.cfg, &pb.orders, &pb.ptable, &pb.poffset, &pb.alias_packed}) all.push_back(b);
   return all;
@@ -1359,6 +1377,7 @@ extern "C" int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   }
   if (r) {
     c->have_frame = false;
+    c->red.have = c->red.ran = false;
     return r;
   }
   prof.lap("validate");
@@ -1369,6 +1388,7 @@ extern "C" int jxlhip_frame_upload(JxlHipContext* c, const JxlHipFrameDesc* d) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
   c->have_frame = false;
+  c->red.have = c->red.ran = false;  // (an ordinary context again)
   AdoptFrame(c, *d, P, E);
   // 3. the tables: one list, walked once for the size of the blob and once to place them
   upload::TableBound bound;
@@ -1429,6 +1449,7 @@ static int LaunchEntropy(JxlHipContext* c) {
 
 static int RunEntropySingle(JxlHipContext* c) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->red.have) return JXLHIP_ERR_UNSUPPORTED;  // (a reduced upload has no AC stage: jxlhip_reduced_run)
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   HIP_TRY(hipSetDevice(c->device));
   {
@@ -1787,6 +1808,7 @@ static int BeginDownstreamBatch(JxlHipContext* const* ctxs, size_t n, bool filte
   JxlHipContext* c0 = ctxs[0];
   for (size_t i = 0; i < n; i++) {
     if (!ctxs[i]) return JXLHIP_ERR_INVALID_ARGUMENT;
+    if (ctxs[i]->red.have) return JXLHIP_ERR_UNSUPPORTED;  // (a reduced upload has neither transforms nor filters)
     if (!ctxs[i]->have_frame) return JXLHIP_ERR_NO_FRAME;
     if (ctxs[i]->device != c0->device || ctxs[i]->coef_bits != c0->coef_bits) return JXLHIP_ERR_INVALID_ARGUMENT;
   }
@@ -2066,6 +2088,7 @@ extern "C" int jxlhip_run_entropy_batch(JxlHipContext* const* ctxs, size_t n) {
   for (size_t i = 0; i < n; i++) {
     const JxlHipContext* c = ctxs[i];
     if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+    if (c->red.have) return JXLHIP_ERR_UNSUPPORTED;
     if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
     if (c->device != c0->device) return JXLHIP_ERR_INVALID_ARGUMENT;
     if (n > 1 && !c->absent_groups.empty()) return JXLHIP_ERR_INVALID_ARGUMENT;  // (partial frames go one at a time: jxlhip_run_entropy)
@@ -2173,6 +2196,7 @@ static int ZeroAbsentGroups(JxlHipContext* c) {
 
 extern "C" int jxlhip_run_entropy(JxlHipContext* c) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->red.have) return JXLHIP_ERR_UNSUPPORTED;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   const int r = ZeroAbsentGroups(c);
   if (r) return r;
@@ -2296,6 +2320,7 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
   int r = upload::CheckModFrameDesc(*d, opt);
   c->mod.have = false;
   c->have_frame = false;
+  c->red.have = c->red.ran = false;
   if (!r && c->tensor_bound) {  // (the bound tensor against the image's size, which a transposing orientation turns)
     const bool transposed = (c->out_orient & 4) != 0;
     r = tensor_out::CheckTensorOut(c->tensor, transposed ? d->ysize : d->xsize, transposed ? d->xsize : d->ysize);
@@ -2681,6 +2706,137 @@ extern "C" int jxlhip_modular_download_buffer(JxlHipContext* c, uint32_t buffer,
   return 0;
 }
 
+// ------------------------------------------------------------------------------------- reduced output (jxl_hip_reduced.h)
+// The colour stage's and the writer's blocks of a reduced image, as FillFilterParams and FillPixelOut make a frame's.
+static void FillReducedDev(const JxlHipContext* c, const JxlHipReducedDesc& d, const reduced::ReducedHead& head, jxlhip::ReducedDev* dev) {
+  memset(dev, 0, sizeof(*dev));
+  dev->h = head;
+  jxlhip::FilterParams& fp = dev->f;
+  for (int ch = 0; ch < 3; ch++) {
+    fp.opsin_bias[ch] = d.opsin_bias[ch];
+    fp.opsin_bias_cbrt[ch] = cbrtf(d.opsin_bias[ch]);
+  }
+  memcpy(fp.opsin_inv, d.opsin_inv, sizeof(fp.opsin_inv));
+  fp.linear_output = d.linear_output;
+  FillPixelOut(c, d.xsize_blocks, d.ysize_blocks, nullptr, &dev->po);
+  dev->t = d.color_target ? *d.color_target : JxlHipColorTarget{};
+}
+
+extern "C" int jxlhip_reduced_upload(JxlHipContext* c, const JxlHipReducedDesc* d) {
+  if (!c || !d) return JXLHIP_ERR_INVALID_ARGUMENT;
+  // 1. whether the descriptor and the bindings are taken at the reduced size: on the host alone, before any device call
+  int r = reduced::CheckReducedDesc(*d);
+  if (!r && (OutChannels(c) == 2 || OutChannels(c) == 4)) r = JXLHIP_ERR_UNSUPPORTED;  // (the reduced image is opaque colour)
+  const bool transposed = (c->out_orient & 4) != 0;
+  const uint32_t w = transposed ? d->ysize_blocks : d->xsize_blocks, h = transposed ? d->xsize_blocks : d->ysize_blocks;
+  if (!r && c->tensor_bound) r = tensor_out::CheckTensorOut(c->tensor, w, h);
+  if (!r && c->resized_bound) r = resample::CheckResizedOut(c->resized, w, h);
+  c->have_frame = false;  // (the caller meant to replace whatever the context held)
+  c->mod.have = false;
+  c->red.have = c->red.ran = false;
+  if (r) return r;
+  // 2. the block is overwritten: whatever still reads the old one has to be finished
+  HIP_TRY(hipSetDevice(c->device));
+  if ((r = ApplyPendingWait(c))) return r;
+  if ((r = StageReset(c))) return r;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
+  c->xb = d->xsize_blocks; c->yb = d->ysize_blocks;
+  c->xs = c->oxs = d->xsize_blocks; c->ys = c->oys = d->ysize_blocks;
+  c->ups = 1;
+  c->generation++;
+  // 3. the buffers the kernel writes, then the block, which holds their addresses: one staged copy
+  const reduced::BlockLayout l = reduced::LayoutOf(*d, sizeof(jxlhip::ReducedDev));
+  if ((r = c->red_block.Ensure(l.bytes))) return r;
+  if (!c->tensor_bound && (r = c->rgb.Ensure(OwnPixelBytes(c)))) return r;
+  c->red.dc_kept = c->keep_dc;
+  if (c->keep_dc && (r = c->dc.Ensure(l.q_bytes))) return r;
+  void* st = nullptr;
+  if ((r = StageAlloc(c, l.bytes, &st))) return r;
+  reduced::ReducedHead head;
+  if ((r = reduced::PlaceBlock(*d, l, c->keep_dc ? c->dc.as<float>() : nullptr, st, uintptr_t(c->red_block.p), &head))) return r;
+  FillReducedDev(c, *d, head, &c->red.dev);
+  memcpy(static_cast<uint8_t*>(st) + l.desc, &c->red.dev, sizeof(c->red.dev));
+  hipStream_t cs = CopyStream(c->device);
+  if (!cs) cs = c->stream;
+  HIP_TRY(hipMemcpyAsync(c->red_block.p, st, l.bytes, hipMemcpyHostToDevice, cs));
+  HIP_TRY(hipEventRecord(c->stage.done, cs));
+  c->stage.recorded = true;
+  // (resident when the call returns: a batched launch over this context runs on another context's stream)
+  HIP_TRY(WaitEvent(c->stage.done));
+  if (c->resized_bound && (r = PlaceResampleOfFrame(c))) return r;
+  c->red.generation = c->generation;
+  c->red.have = true;
+  return 0;
+}
+
+extern "C" int jxlhip_reduced_run_batch(JxlHipContext* const* ctxs, size_t n) {
+  if (!ctxs || !n) return JXLHIP_ERR_INVALID_ARGUMENT;
+  JxlHipContext* c0 = ctxs[0];
+  for (size_t i = 0; i < n; i++) {
+    JxlHipContext* c = ctxs[i];
+    if (!c || c->device != c0->device) return JXLHIP_ERR_INVALID_ARGUMENT;
+    if (!c->red.have) return c->have_frame || c->mod.have ? JXLHIP_ERR_INVALID_ARGUMENT : JXLHIP_ERR_NO_FRAME;
+    if (c->red.generation != c->generation) return JXLHIP_ERR_INVALID_ARGUMENT;  // (output settings changed since the upload)
+  }
+  HIP_TRY(hipSetDevice(c0->device));
+  int r;
+  if (n > 1 && (r = EnsureOwnStream(c0))) return r;
+  const hipStream_t ls = c0->stream;
+  for (size_t i = 0; i < n; i++)
+    if ((r = ApplyPendingWait(ctxs[i]))) return r;
+  for (size_t i = 1; i < n; i++) {  // the launch runs on the first context's stream, after what the others still have in flight
+    if (!ctxs[i]->down_done) HIP_TRY(hipEventCreateWithFlags(&ctxs[i]->down_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ctxs[i]->down_done, ctxs[i]->stream));
+    HIP_TRY(hipStreamWaitEvent(ls, ctxs[i]->down_done, 0));
+  }
+  // One context: its own block begins with the launch's descriptor. Several: their descriptors side by side with running
+  // tile origins, on the set's first context, rebuilt only when the set changed.
+  const jxlhip::ReducedDev* descs = c0->red_block.as<jxlhip::ReducedDev>();
+  uint32_t tiles = c0->red.dev.h.tiles;
+  if (n > 1) {
+    JxlHipContext::Reduced& R = c0->red;
+    bool same = R.batch_ctxs.size() == n;
+    for (size_t i = 0; same && i < n; i++) same = R.batch_ctxs[i] == ctxs[i] && R.batch_gens[i] == ctxs[i]->generation;
+    if (!same) {
+      R.batch_ctxs.clear();
+      const size_t bytes = reduced::BatchBytes(n, sizeof(jxlhip::ReducedDev));
+      if ((r = c0->red_batch.Ensure(bytes))) return r;
+      std::vector<const void*> each(n);
+      for (size_t i = 0; i < n; i++) each[i] = &ctxs[i]->red.dev;
+      // (on the launch stream itself: behind an earlier launch that still reads the array, and without a host wait)
+      void* st = nullptr;
+      if ((r = StageReset(c0)) || (r = StageAlloc(c0, bytes, &st))) return r;
+      if ((r = reduced::PlaceBatch(each.data(), n, sizeof(jxlhip::ReducedDev), st, bytes, &R.batch_tiles))) return r;
+      HIP_TRY(hipMemcpyAsync(c0->red_batch.p, st, bytes, hipMemcpyHostToDevice, ls));
+      HIP_TRY(hipEventRecord(c0->stage.done, ls));
+      c0->stage.recorded = true;
+      R.batch_ctxs.assign(ctxs, ctxs + n);
+      R.batch_gens.resize(n);
+      for (size_t i = 0; i < n; i++) R.batch_gens[i] = ctxs[i]->generation;
+    }
+    descs = c0->red_batch.as<jxlhip::ReducedDev>();
+    tiles = R.batch_tiles;
+  }
+  if ((r = TensorsBeforeWriters(ctxs, n, ls))) return r;
+  HIP_TRY(hipEventRecord(c0->ev[0], ls));
+  hipLaunchKernelGGL(jxlhip::k_reduced_pixels, dim3(tiles), dim3(256), 0, ls, descs, uint32_t(n));
+  HIP_TRY(hipGetLastError());
+  if ((r = LaunchResample(ctxs, n, ls))) return r;
+  HIP_TRY(hipEventRecord(c0->ev[1], ls));
+  if ((r = TensorsAfterWriters(ctxs, n, ls))) return r;
+  c0->ev_valid[0] = true;
+  for (size_t i = 1; i < n; i++) ctxs[i]->ev_valid[0] = false;
+  if (n > 1) {
+    if (!c0->batch_done) HIP_TRY(hipEventCreateWithFlags(&c0->batch_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c0->batch_done, ls));
+    for (size_t i = 1; i < n; i++) ctxs[i]->pending_wait = c0->batch_done;
+  }
+  for (size_t i = 0; i < n; i++) ctxs[i]->red.ran = true;  // (the pixel download entry points need it)
+  return 0;
+}
+extern "C" int jxlhip_reduced_run(JxlHipContext* c) { return jxlhip_reduced_run_batch(&c, 1); }
+
 extern "C" {
 
 int jxlhip_run_transform_batch(JxlHipContext* const* ctxs, size_t n) {
@@ -2845,6 +3001,7 @@ int jxlhip_share_planes(JxlHipContext* c, JxlHipContext* lender) {
 // the neighbouring band's planes (another context: another GPU's, through any device-to-device transport).
 int jxlhip_halo_rows(JxlHipContext* c, uint32_t* rows) {
   if (!c || !rows) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->red.have) return JXLHIP_ERR_UNSUPPORTED;
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   *rows = uint32_t(jxlhip::FusedHalo(c->gab != 0, int(c->epf_iters)));
   return 0;
@@ -2976,6 +3133,10 @@ int jxlhip_set_option(JxlHipContext* c, const char* name, int value) {
     c->entropy_gate = value != 0;
     return 0;
   }
+  if (std::string(name) == "keep_dc") {  // (takes effect at the next reduced upload)
+    c->keep_dc = value != 0;
+    return 0;
+  }
   if (std::string(name) == "keep_xyb_planes") {  // (takes effect at the next Modular upload)
     c->keep_xyb = value != 0;
     c->generation++;
@@ -3020,6 +3181,7 @@ int jxlhip_set_output_tensor(JxlHipContext* c, const JxlHipTensorOut* t) {
   c->resized = JxlHipResizedOut{};
   c->have_frame = false;  // (a frame uploaded for the other destination has no writer for this one: upload again)
   c->mod.have = false;
+  c->red.have = c->red.ran = false;
   c->generation++;  // cached batch descriptions hold the pixel pointers
   return 0;
 }
@@ -3038,6 +3200,7 @@ int jxlhip_set_output_resized(JxlHipContext* c, const JxlHipResizedOut* d) {
   c->tensor = JxlHipTensorOut{};
   c->have_frame = false;  // (a frame uploaded for another destination has neither the pixel buffer nor the tables: upload again)
   c->mod.have = false;
+  c->red.have = c->red.ran = false;
   c->generation++;
   return 0;
 }
@@ -3050,7 +3213,7 @@ int jxlhip_debug_resample(JxlHipContext* c, const float* src, uint32_t xsize, ui
   HIP_TRY(hipSetDevice(c->device));
   if ((r = ApplyPendingWait(c))) return r;
   HIP_TRY(hipStreamSynchronize(c->stream));  // (whatever still reads the context's block or its source)
-  if (c->resized_bound) c->have_frame = c->mod.have = false;  // (an uploaded frame's tables are overwritten: upload again)
+  if (c->resized_bound) c->have_frame = c->mod.have = c->red.have = c->red.ran = false;  // (an uploaded frame's tables are overwritten: upload again)
   const size_t bytes = size_t(xsize) * ysize * nc * 4;
   if ((r = c->rs_src.Ensure(bytes))) return r;
   HIP_TRY(hipMemcpy(c->rs_src.p, src, bytes, hipMemcpyHostToDevice));
@@ -3150,7 +3313,7 @@ int jxlhip_upsample_plane(JxlHipContext* c, const float* plane, uint32_t xsize, 
 
 int jxlhip_download_pixels(JxlHipContext* c, void* dst, size_t stride) {
   if (!c || !dst || CallerOwnsPixels(c)) return JXLHIP_ERR_INVALID_ARGUMENT;  // (a bound tensor holds the pixels, not the context)
-  if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
+  if (!c->have_frame && !c->red.ran) return JXLHIP_ERR_NO_FRAME;  // (a reduced upload that has run: the reduced image)
   const bool transposed = (c->out_orient & 4) != 0;  // rows of the output are columns of the image
   const size_t row = size_t(transposed ? c->oys : c->oxs) * OutPixelBytes(c), rows = transposed ? c->oxs : c->oys;
   if (stride < row) return JXLHIP_ERR_INVALID_ARGUMENT;
@@ -3329,7 +3492,8 @@ int jxlhip_sync(JxlHipContext* c) {
 
 int jxlhip_download_rgb8(JxlHipContext* c, uint8_t* dst, size_t stride) {
   if (!c || !dst || CallerOwnsPixels(c)) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
+  if (!c->have_frame && !c->red.ran) return JXLHIP_ERR_NO_FRAME;
+  if (c->red.ran && (c->out_orient & 4)) return JXLHIP_ERR_INVALID_ARGUMENT;  // (transposed rows: jxlhip_download_pixels)
   if (stride < size_t(c->oxs) * 3 || !OutIsRgb8(c)) return JXLHIP_ERR_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
   {
@@ -3391,6 +3555,22 @@ int jxlhip_get_section_end_bits(JxlHipContext* c, uint32_t* bits, size_t n) {
 
 int jxlhip_download(JxlHipContext* c, const char* name, void* dst, size_t dst_size, size_t* needed) {
   if (!c || !name) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->red.have) {  // a reduced upload: the kept DC planes of its run, and nothing of the AC stages
+    if (std::string(name) != "dc") return JXLHIP_ERR_UNSUPPORTED;
+    if (!c->red.dc_kept || !c->red.ran) return JXLHIP_ERR_INVALID_ARGUMENT;  // needs jxlhip_set_option("keep_dc", 1) and a run
+    const size_t dc_bytes = size_t(c->xb) * c->yb * 12;
+    if (needed) *needed = dc_bytes;
+    if (!dst) return 0;
+    if (dst_size < dc_bytes) return JXLHIP_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(c->device));
+    {
+      int pw = ApplyPendingWait(c);
+      if (pw) return pw;
+    }
+    HIP_TRY(hipMemcpyAsync(dst, c->dc.p, dc_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+  }
   if (!c->have_frame) return JXLHIP_ERR_NO_FRAME;
   const void* src = nullptr;
   size_t bytes = 0;
@@ -3526,6 +3706,7 @@ void jxlhip_canvas_destroy(JxlHipCanvas* v) {
 int jxlhip_canvas_save_xyb(JxlHipCanvas* v, JxlHipContext* c, uint32_t slot) {
   if (!v || !c || slot > 7 || c->device != v->device) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (CallerOwnsPixels(c)) return JXLHIP_ERR_UNSUPPORTED;  // (composed frames keep the context's own buffers)
+  if (c->red.have) return JXLHIP_ERR_UNSUPPORTED;          // (a reduced image is no frame of the canvas's size)
   HIP_TRY(hipSetDevice(v->device));
   {
     int pw = ApplyPendingWait(c);
@@ -3597,6 +3778,7 @@ int jxlhip_canvas_blend(JxlHipCanvas* v, JxlHipContext* c, const JxlHipBlend* b)
   if (!v || !c || !b || c->device != v->device) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (b->mode > 4 || b->alpha_mode > 4 || b->source > 3 || b->alpha_source > 3 || b->save_slot > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (CallerOwnsPixels(c)) return JXLHIP_ERR_UNSUPPORTED;  // (the frame's pixels are in the caller's tensor, not in c->rgb)
+  if (c->red.have) return JXLHIP_ERR_UNSUPPORTED;
   if (!c->have_frame && !c->mod.have) return JXLHIP_ERR_NO_FRAME;
   if (c->out_type != 0 || c->out_nc != 4 || c->out_swap || c->out_orient) return JXLHIP_ERR_INVALID_ARGUMENT;  // f32 x 4 as coded
   if (size_t(c->oxs) * c->oys * 16 > c->rgb.cap) return JXLHIP_ERR_INVALID_ARGUMENT;

@@ -3,6 +3,8 @@
 //                  quantisation steps, each DC group's extra-precision shift, chroma from luma with the DC factors).
 //   k_dc_smooth  = AdaptiveDCSmoothing, reference lib/jxl/compressed_dc.cc:50-52 (weights), :64-128 (ComputePixelChannel /
 //                  ComputePixel: the multiply-adds below are the reference's MulAdd chain), :130-198 (borders kept).
+//                  The bodies of both are __device__ functions (DcDequantSample, DcSmoothSample) that the reduced output's
+//                  kernel (jxl_hip_reduced.h) calls too: one statement of the arithmetic, bit-equal planes.
 //   k_epf_sigma  = ComputeSigma, reference lib/jxl/epf.cc:39-81 (1 / sigma per 8x8 block from the varblock's quant-field
 //                  value and the block's sharpness; the reference's mirrored padding is not stored: the filter kernels
 //                  mirror their reads about the frame).
@@ -32,8 +34,46 @@ struct DcDequantParams {
                       // plane, no chroma from luma (compressed_dc.cc:232-250)
 };
 
-// One thread per block. The products are not contracted into multiply-adds: the oracle's (and the reference's scalar)
-// order of operations, so that the planes agree bit for bit.
+// DequantDC of one 4:4:4 sample: the coded integers of X, Y, B to the three DC values, with the DC group's precision
+// shift `ep` and chroma from luma. The products are not contracted into multiply-adds: the oracle's (and the reference's
+// scalar) order of operations, so that the planes agree bit for bit. Shared by k_dc_dequant and k_reduced_pixels
+// (jxl_hip_reduced.h).
+__device__ __forceinline__ void DcDequantSample(int32_t qx, int32_t qy, int32_t qb, uint32_t ep, const float* step, float cfl_x, float cfl_b,
+                                                float* out_x, float* out_y, float* out_b) {
+#pragma clang fp contract(off)
+  const float mul = 1.0f / float(1u << (ep & 3u));
+  const float in_x = float(qx) * (step[0] * mul);
+  const float in_y = float(qy) * (step[1] * mul);
+  const float in_b = float(qb) * (step[2] * mul);
+  *out_y = in_y;
+  *out_x = in_y * cfl_x + in_x;
+  *out_b = in_y * cfl_b + in_b;
+}
+
+// AdaptiveDCSmoothing of one interior sample (compressed_dc.cc:64-128): m points at the sample in the first plane, the
+// other two planes lie `plane` floats apart and the rows `stride` floats (the planes in memory, or a tile of them in
+// LDS). The multiply-adds are the reference's MulAdd chain, the gap is measured in steps by a division. Shared likewise.
+__device__ __forceinline__ void DcSmoothSample(const float* m0, size_t plane, size_t stride, const float* step, float* out) {
+  const float w1 = 0.20345139757231578f, w2 = 0.0334829185968739f, w0 = 1.0f - 4.0f * (w1 + w2);
+  float mc[3], sm[3], gap = 0.5f;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const float* m = m0 + plane * c;
+    const float* t = m - stride;
+    const float* b = m + stride;
+    const float corner = (t[-1] + t[1]) + (b[-1] + b[1]);
+    const float side = (m[-1] + m[1]) + (t[0] + b[0]);
+    mc[c] = m[0];
+    sm[c] = __builtin_fmaf(corner, w2, __builtin_fmaf(side, w1, mc[c] * w0));
+    gap = fmaxf(gap, fabsf((mc[c] - sm[c]) / step[c]));
+  }
+  float factor = __builtin_fmaf(-4.0f, gap, 3.0f);
+  factor = factor < 0.0f ? 0.0f : factor;
+#pragma unroll
+  for (int c = 0; c < 3; c++) out[c] = __builtin_fmaf(sm[c] - mc[c], factor, mc[c]);
+}
+
+// One thread per block.
 __global__ __launch_bounds__(256) void k_dc_dequant(DcDequantParams P) {
 #pragma clang fp contract(off)
   const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -50,13 +90,11 @@ __global__ __launch_bounds__(256) void k_dc_dequant(DcDequantParams P) {
     return;
   }
   const uint32_t ep = P.extra_precision ? P.extra_precision[(y >> 8) * P.xgroups + (x >> 8)] : 0u;
-  const float mul = 1.0f / float(1u << (ep & 3u));
-  const float in_x = float(P.q[at]) * (P.step[0] * mul);
-  const float in_y = float(P.q[plane + at]) * (P.step[1] * mul);
-  const float in_b = float(P.q[2 * plane + at]) * (P.step[2] * mul);
-  P.out[plane + at] = in_y;
-  P.out[at] = in_y * P.cfl_x + in_x;
-  P.out[2 * plane + at] = in_y * P.cfl_b + in_b;
+  float vx, vy, vb;
+  DcDequantSample(P.q[at], P.q[plane + at], P.q[2 * plane + at], ep, P.step, P.cfl_x, P.cfl_b, &vx, &vy, &vb);
+  P.out[plane + at] = vy;
+  P.out[at] = vx;
+  P.out[2 * plane + at] = vb;
 }
 
 struct DcSmoothParams {
@@ -76,23 +114,10 @@ __global__ __launch_bounds__(256) void k_dc_smooth(DcSmoothParams P) {
     for (int c = 0; c < 3; c++) P.out[plane * c + at] = P.in[plane * c + at];
     return;
   }
-  const float w1 = 0.20345139757231578f, w2 = 0.0334829185968739f, w0 = 1.0f - 4.0f * (w1 + w2);
-  float mc[3], sm[3], gap = 0.5f;
+  float v[3];
+  DcSmoothSample(P.in + at, plane, P.xs, P.step, v);
 #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const float* m = P.in + plane * c + at;
-    const float* t = m - P.xs;
-    const float* b = m + P.xs;
-    const float corner = (t[-1] + t[1]) + (b[-1] + b[1]);
-    const float side = (m[-1] + m[1]) + (t[0] + b[0]);
-    mc[c] = m[0];
-    sm[c] = __builtin_fmaf(corner, w2, __builtin_fmaf(side, w1, mc[c] * w0));
-    gap = fmaxf(gap, fabsf((mc[c] - sm[c]) / P.step[c]));
-  }
-  float factor = __builtin_fmaf(-4.0f, gap, 3.0f);
-  factor = factor < 0.0f ? 0.0f : factor;
-#pragma unroll
-  for (int c = 0; c < 3; c++) P.out[plane * c + at] = __builtin_fmaf(sm[c] - mc[c], factor, mc[c]);
+  for (int c = 0; c < 3; c++) P.out[plane * c + at] = v[c];
 }
 
 struct SigmaParams {

@@ -65,6 +65,7 @@ struct FramePlan {
   std::vector<uint8_t> dc_extra_precision;  // per DC group: the integers are in units of step / 2^this
   float dc_cfl_x = 0.0f, dc_cfl_b = 1.0f;   // chroma from luma at DC: base correlation + DC factor * colour scale
   bool dc_smoothing = false;        // the frame asks for the smoothing (no kSkipAdaptiveDCSmoothing)
+  bool reduced = false;             // ParseFrame's reduced mode: dc_q, dc_extra_precision and the DC scalars alone are filled
   bool use_dc_frame = false;        // kUseDcFrame: `dc` stays empty, the DC image is `dc_source` (device planes of a DC frame)
   const float* dc_source = nullptr;  // [3][ysize_blocks][xsize_blocks] floats on the device (jxlamd_frame_set_dc_source)
   float dc_step[3] = {1, 1, 1};     // DC quantisation step per channel (the smoothing measures its gap in steps)
@@ -126,6 +127,10 @@ static inline void SerialFor(size_t n, const std::function<void(size_t)>& f) {
 class FrameParser {
  public:
   FrameParser(const uint8_t* data, size_t size) : data_(data), size_(size) {}
+  // The buffer may be a prefix of the file (jxlamd_frame_dc_extent, the reduced parse): a `jxlc` box whose declared end lies
+  // beyond the buffer is then taken for as far as the buffer goes, and a buffer that ends before the codestream box is
+  // "truncated frame header" (the caller comes back with more), not a bad file.
+  void AllowCutContainer() { allow_cut_container_ = true; }
 
   // Parses signature + image header; returns the byte position of the first frame.
   size_t ParseImageHeader(ImageHeader* ih) {
@@ -146,6 +151,10 @@ class FrameParser {
           hdr = 16;
         }
         if (bsize == 0) bsize = n - pos;
+        if (allow_cut_container_ && bsize >= hdr && bsize > n - pos) {
+          JXH_CHECK(!memcmp(d + pos + 4, "jxlc", 4), "truncated frame header");
+          bsize = n - pos;
+        }
         JXH_CHECK(bsize >= hdr && bsize <= n - pos, "bad box size");  // (no addition: a 64-bit size cannot wrap)
         if (!memcmp(d + pos + 4, "jxlc", 4)) {
           codestream_base_ = pos + hdr;
@@ -156,6 +165,7 @@ class FrameParser {
         JXH_CHECK(memcmp(d + pos + 4, "jxlp", 4) != 0, "unsupported: jxlp boxes");
         pos += bsize;
       }
+      JXH_CHECK(found || !allow_cut_container_, "truncated frame header");
       JXH_CHECK(found, "no codestream box");
     } else {
       cs_size_ = n;
@@ -189,15 +199,36 @@ class FrameParser {
   // frame_index / nonvisible_index: the shown frames before this one and the invisible ones since (dec_frame.cc:160-168;
   // they seed the noise). The plan is of the frame at its own size: where it sits on the canvas and how it blends with
   // a reference slot (fh.x0 / y0, fh.blend) is the caller's business (the decoder API composes on a JxlHipCanvas).
+  // reduced: the parse of a reduced decode (FramePlan::reduced): headers, TOC, DC global and the DC groups' VarDCT DC streams
+  // only, from any prefix of the buffer that holds those sections; everything a 1/8-scale image cannot come from is refused
+  // before a DC group is decoded. dc_extent != NULL: headers and TOC alone; *dc_extent = the number of leading bytes of the
+  // buffer such a parse reads, and nothing else of the plan is filled.
   void ParseFrame(size_t pos, const ImageHeader& ih, FramePlan* plan, const ParallelFor& pfor = SerialFor, size_t frame_index = 0,
-                  size_t nonvisible_index = 0, bool allow_partial = false) {
+                  size_t nonvisible_index = 0, bool allow_partial = false, bool reduced = false, size_t* dc_extent = nullptr) {
     FramePlan& P = *plan;
     P.ih = ih;
     P.frame_index = frame_index;
     P.nonvisible_index = nonvisible_index;
+    P.reduced = reduced;
+    reduced_ = reduced;
     BitReader br(data_ + pos, codestream_base_ + cs_size_ - pos);
     ReadFrameHeader(br, ih, &P.fh);
     const FrameHeader& fh = P.fh;
+    if (reduced || dc_extent) JXH_CHECK(!br.Overread(), "truncated frame header");
+    if (reduced) {
+      // The reduced image is the frame's own DC image through the XYB colour stage: every frame that has none, whose DC
+      // image lies elsewhere or is not at 1/8 of the canvas, or that draws more than its coefficients, is refused.
+      JXH_CHECK(!ih.have_preview, "reduced decode: the first frame is a preview");
+      JXH_CHECK(!fh.modular, "reduced decode: a Modular frame has no DC image");
+      JXH_CHECK(fh.frame_type == 0 && !fh.custom_size && fh.is_last && fh.blend.mode == 0,
+                "reduced decode: the first frame is not a regular, full-canvas, last frame that replaces the canvas");
+      JXH_CHECK(!(fh.flags & FrameHeader::kUseDcFrame), "reduced decode: the frame takes its DC image from a DC frame (kUseDcFrame)");
+      JXH_CHECK(!(fh.flags & FrameHeader::kPatches), "reduced decode: the frame has patches");
+      JXH_CHECK(!(fh.flags & FrameHeader::kSplines), "reduced decode: the frame has splines");
+      JXH_CHECK(fh.upsampling == 1, "reduced decode: the frame is upsampled");
+      JXH_CHECK(fh.Is444(), "reduced decode: the frame is chroma-subsampled");
+      JXH_CHECK(ih.xyb_encoded, "reduced decode: the image is not XYB-encoded");
+    }
     // (frame types: 1 = kDCFrame, decoded like any frame and kept before the colour transform as the DC image of a later
     // frame; 2 = kReferenceOnly: kept for patches; 3 = kSkipProgressive)
     JXH_CHECK(!fh.modular, "unsupported: Modular frames on the GPU path");
@@ -229,7 +260,20 @@ class FrameParser {
     const size_t base = pos + br.BitPos() / 8;
     const size_t have = codestream_base_ + cs_size_;  // bytes of the buffer that belong to the codestream
     bool partial = false;
-    if (base + toc.total > have) {
+    // What a reduced parse reads: up to the largest end of the DC global section and the DC groups (the TOC may be
+    // permuted); the whole of a frame coded as one section.
+    size_t dc_end = base + toc.total;
+    if (entries > 1) {
+      dc_end = base;
+      for (size_t i = 0; i < 1 + d.num_dc_groups; i++) dc_end = std::max<size_t>(dc_end, base + toc.offset[i] + toc.size[i]);
+    }
+    if (dc_extent) {
+      *dc_extent = dc_end;
+      return;
+    }
+    if (reduced) {
+      JXH_CHECK(dc_end <= have, "truncated frame");
+    } else if (base + toc.total > have) {
       // A prefix of the frame: usable once the DC image and the AC global section are whole (FrameDecoder::HasDecodedDC,
       // decode.cc:2464-2468). Frames in one section, and frames whose AC sections also carry extra-channel data, wait.
       JXH_CHECK(allow_partial && entries > 1 && ih.extra.empty(), "truncated frame");
@@ -240,6 +284,23 @@ class FrameParser {
     const size_t xb = d.xsize_blocks, yb = d.ysize_blocks;
     P.dc_q.assign(3 * xb * yb, 0);
     P.dc_extra_precision.assign(d.num_dc_groups, 0);
+    if (reduced) {  // (no AC metadata, no AC global section, no block lists: the plan holds the DC image's inputs alone)
+      if (entries == 1) {
+        BitReader r(data_ + base + toc.offset[0], toc.size[0]);
+        DcGlobal(r, &P);
+        DcGroup(r, &P, 0);
+        JXH_CHECK(!r.Overread(), "section over-read");
+      } else {
+        {
+          BitReader r(data_ + base + toc.offset[0], toc.size[0]);
+          DcGlobal(r, &P);
+          JXH_CHECK(!r.Overread(), "DC global over-read");
+        }
+        RunDcGroups(pfor, base, toc, &P);
+      }
+      FinalizeDc(&P);
+      return;
+    }
     P.acs.assign(xb * yb, 0xFF);
     P.ytox.assign(DivCeil(xb, 8) * DivCeil(yb, 8), 0);
     P.ytob.assign(P.ytox.size(), 0);
@@ -273,19 +334,7 @@ class FrameParser {
         JXH_CHECK(!r.Overread(), "DC global over-read");
       }
       const auto t1 = now();
-      std::string err;
-      std::mutex err_mu;  // DC groups run on the caller's threads: the first failure is kept
-      pfor(d.num_dc_groups, [&](size_t g) {
-        try {
-          BitReader r(data_ + base + toc.offset[1 + g], toc.size[1 + g]);
-          DcGroup(r, &P, g);
-          JXH_CHECK(!r.Overread(), "DC group over-read");
-        } catch (const std::exception& e) {
-          std::lock_guard<std::mutex> lk(err_mu);
-          if (err.empty()) err = e.what();
-        }
-      });
-      JXH_CHECK(err.empty(), err);
+      RunDcGroups(pfor, base, toc, &P);
       const auto t2 = now();
       FinalizeDc(&P);
       const auto t3 = now();
@@ -335,6 +384,23 @@ class FrameParser {
   }
 
  private:
+  // The DC groups, on the caller's threads: the first failure is kept.
+  void RunDcGroups(const ParallelFor& pfor, size_t base, const Toc& toc, FramePlan* P) {
+    std::string err;
+    std::mutex err_mu;
+    pfor(P->dim.num_dc_groups, [&](size_t g) {
+      try {
+        BitReader r(data_ + base + toc.offset[1 + g], toc.size[1 + g]);
+        DcGroup(r, P, g);
+        JXH_CHECK(!r.Overread(), "DC group over-read");
+      } catch (const std::exception& e) {
+        std::lock_guard<std::mutex> lk(err_mu);
+        if (err.empty()) err = e.what();
+      }
+    });
+    JXH_CHECK(err.empty(), err);
+  }
+
   void DcGlobal(BitReader& br, FramePlan* P) {
     if (P->fh.flags & FrameHeader::kPatches) {  // dec_frame.cc:271-285
       DecodePatches(br, P->dim.xsize_padded, P->dim.ysize_padded, P->ih.extra.size(), &P->patches);
@@ -516,7 +582,7 @@ class FrameParser {
         memcpy(&P->dc_q[row], qx, bw * sizeof(int32_t));
         memcpy(&P->dc_q[plane + row], qy, bw * sizeof(int32_t));
         memcpy(&P->dc_q[2 * plane + row], qb, bw * sizeof(int32_t));
-        if (bc.num_dc_ctxs <= 1) continue;  // (one DC context: the buckets stay 0)
+        if (bc.num_dc_ctxs <= 1 || reduced_) continue;  // (one DC context: the buckets stay 0; a reduced parse has no use for them)
         for (size_t x = 0; x < bw; x++) {
           size_t idx = row + x;
           uint8_t bucket = 0;
@@ -534,6 +600,7 @@ class FrameParser {
         }
       }
     }
+    if (reduced_) return;  // (what follows in the section, extra channels and the AC metadata, draws nothing at 1/8)
     if (!P->extra.ch.empty()) {  // Modular DC group: channels of the global image squeezed 8x or more (stream 1 + ndc + g)
       std::lock_guard<std::mutex> lk(extra_mu_);  // (DC groups run on several threads; the channel list is shared)
       DecodeExtraRect(br, P, bx0 * 8, by0 * 8, d.dc_group_dim, d.dc_group_dim, 3, 1000, int(1 + ndc + g));
@@ -733,6 +800,8 @@ class FrameParser {
   const uint8_t* data_;
   size_t size_;
   size_t codestream_base_ = 0, cs_size_ = 0;
+  bool allow_cut_container_ = false;
+  bool reduced_ = false;  // ParseFrame's `reduced`: the DC groups stop behind their VarDCT DC stream
   DequantTables dq_;
   std::mutex extra_mu_;
   int32_t ytox_dc_ = 0, ytob_dc_ = 0;

@@ -4,6 +4,7 @@ in the layout and type the consumer asked for, into memory the consumer owns. to
     img = torch_io.decode_to_tensor(data, dtype=torch.float16, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225))
     batch = torch_io.decode_batch_to_tensor(datas, dtype=torch.bfloat16)     # (N, 3, H, W), one launch per stage
     crops = torch_io.decode_batch_to_tensor(datas, size=(224, 224), boxes=boxes)  # any sizes: crop + antialiased resize
+    thumbs = torch_io.decode_batch_to_tensor(datas, size=(224, 224), reduce=8)    # from the 1/8-scale DC image: no AC decode
 
 Float types hold v * (1 / std[c]) + (-mean[c] / std[c]) of the decoder's float sample v in [0, 1] (scale and bias computed
 in float32, the product and the sum each rounded to float32, then to the type); uint8 holds the dithered 8-bit sample.
@@ -89,14 +90,65 @@ def _image_size(out, layout):
     return (out.shape[1], out.shape[2]) if layout == "CHW" else (out.shape[0], out.shape[1])
 
 
+def _check_reduce(reduce):
+    if reduce not in (1, 8):
+        raise ValueError("reduce is 1 (the image) or 8 (its 1/8-scale DC image)")
+
+
+def _decode_reduced(datas, outs, layout, mean, std, clamp, boxes, resized):
+    """The reduced route of decode_to_tensor / decode_batch_to_tensor: frame i's 1/8-scale image into outs[i] (bound whole,
+    or resized from boxes[i] of the reduced image), one kernel launch for the set. Every stream is parsed once; `outs` is a
+    list, its entries tensors or callables (w, h) -> tensor, or one callable (the frames' reduced sizes) -> such a list. A
+    stream the reduced parse refuses raises JxlAmdError with the parser's text: no fallback to a full decode."""
+    frames, ctxs, made = [], [], []
+    try:
+        for d in datas:
+            frames.append(J.Frame(d, reduced=True))
+        if callable(outs):
+            outs = outs([f.reduced_size() for f in frames])
+        for i, f in enumerate(frames):
+            w, h = f.reduced_size()
+            o = outs[i](w, h) if callable(outs[i]) else outs[i]
+            made.append(o)
+            c = J.HipContext(o.device.index or 0)
+            ctxs.append(c)
+            if resized:
+                bind_resized(c, o, layout, boxes[i], mean, std, clamp)
+            else:
+                if _image_size(o, layout) != (h, w):
+                    raise ValueError("out is %r for a reduced image of %d x %d" % (tuple(o.shape), w, h))
+                bind(c, o, layout, mean, std, clamp)
+            c.upload_reduced(f)
+        J.run_reduced_batch(ctxs)
+        return made
+    finally:
+        for c in ctxs:
+            c.close()
+        for f in frames:
+            f.close()
+
+
 def decode_to_tensor(data, dtype=torch.float16, layout="CHW", mean=None, std=None, clamp=False, channels=3, device=0, out=None,
-                     size=None, box=None):
+                     size=None, box=None, reduce=1):
     """One-shot: a VarDCT or Modular codestream's first frame -> a device tensor (allocated unless `out` is given).
     size = (height, width): the image, or box = (x0, y0, xsize, ysize) of it, is resized to that size on the device
     (bind_resized); an `out` given with it must have that size. Without `size` the tensor has the image's own size.
+    reduce=8: from the frame's 1/8-scale DC image instead (VarDCT frames; `data` may be a prefix of frame_dc_extent(data)
+    bytes): the tensor is (C, ceil(H / 8), ceil(W / 8)) without `size`, and `box` is in reduced-image coordinates.
     Raises JxlAmdError on sections or streams the kernels flagged as corrupt."""
     if box is not None and size is None:
         raise ValueError("box needs size")
+    _check_reduce(reduce)
+    if reduce == 8:
+        if size is not None:
+            if out is None:
+                out = _alloc((channels, int(size[0]), int(size[1])), dtype, layout, device)
+            elif _image_size(out, layout) != (int(size[0]), int(size[1])):
+                raise ValueError("out is %r for size %r" % (tuple(out.shape), tuple(size)))
+            target = out
+        else:
+            target = out if out is not None else (lambda w, h: _alloc((channels, h, w), dtype, layout, device))
+        return _decode_reduced([data], [target], layout, mean, std, clamp, [box], size is not None)[0]
     modular = J.frame_is_modular(data)
     f = J.ModFrame(data) if modular else J.Frame(data)
     c = J.HipContext(device)
@@ -184,12 +236,43 @@ def _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device,
             f.close()
 
 
+def _decode_batch_reduced(datas, out, dtype, mean, std, clamp, channels, device, size, boxes):
+    """decode_batch_to_tensor with reduce=8: without `size`, frames of one reduced size; with it, of any."""
+    n = len(datas)
+    if size is None and boxes is not None:
+        raise ValueError("boxes needs size")
+    if boxes is None:
+        boxes = [None] * n
+    if len(boxes) != n:
+        raise ValueError("%d boxes for %d frames" % (len(boxes), n))
+    batch = []
+
+    def images(sizes):  # (called with the parsed frames' reduced sizes: the batch tensor, one image per frame)
+        if size is None:
+            if len(set(sizes)) != 1:
+                raise ValueError("frames of one size: %r" % sorted(set(sizes)))
+            shape = (n, channels, sizes[0][1], sizes[0][0])
+        else:
+            shape = (n, channels, int(size[0]), int(size[1]))
+        if out is not None and tuple(out.shape) != shape:
+            raise ValueError("out is %r, the frames need %r" % (tuple(out.shape), shape))
+        batch.append(out if out is not None else torch.empty(shape, dtype=dtype, device="cuda:%d" % device))
+        return [batch[0][i] for i in range(n)]
+
+    _decode_reduced(datas, images, "CHW", mean, std, clamp, boxes, size is not None)
+    return batch[0]
+
+
 def decode_batch_to_tensor(datas, out=None, dtype=torch.float16, mean=None, std=None, clamp=False, channels=3, device=0, size=None,
-                           boxes=None):
+                           boxes=None, reduce=1):
     """VarDCT frames of one size -> one (N, C, H, W) tensor: a context per frame, each bound to out[i], and one launch per
     stage for the whole set (run_entropy_batch / run_transform_batch / run_filter_color_batch). With size = (height, width)
     the frames may differ in size and kind (VarDCT, Modular); each is resized to that size, frame i cropped to boxes[i] first
-    (a box (x0, y0, xsize, ysize) or None per frame)."""
+    (a box (x0, y0, xsize, ysize) or None per frame). reduce=8: every frame's 1/8-scale DC image instead (VarDCT frames;
+    datas[i] may be a prefix of frame_dc_extent bytes; boxes in reduced-image coordinates), one launch for the set."""
+    _check_reduce(reduce)
+    if reduce == 8:
+        return _decode_batch_reduced(datas, out, dtype, mean, std, clamp, channels, device, size, boxes)
     if size is not None:
         return _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device, size, boxes)
     if boxes is not None:
