@@ -14,6 +14,7 @@
 #include <new>
 #include <chrono>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../../include/jxl_amd_hip.h"
@@ -23,7 +24,9 @@
 #include "../host/jxh_modular_upload_plan.h"
 #include "../host/jxh_reduced_plan.h"
 #include "../host/jxh_resample_plan.h"
+#include "../host/jxh_set_memo.h"
 #include "../host/jxh_tensor_out.h"
+#include "../host/jxh_transform_plan.h"
 #include "../host/jxh_upload_plan.h"
 #include "jxl_hip_kernels.h"
 #include "jxl_hip_entropy_lanes.h"
@@ -41,6 +44,9 @@ namespace tensor_out = jxlhip::tensor_out;
 namespace resample = jxlhip::resample;
 namespace lane_plan = jxh::lane_plan;
 namespace filter_plan = jxh::filter_plan;
+namespace transform_plan = jxh::transform_plan;
+struct JxlHipContext;
+using SetMemo = jxh::SetMemo<JxlHipContext>;  // the set a batched launch's description was built for (jxh_set_memo.h)
 
 namespace {
 #include "../host/afv_basis.inc"
@@ -216,8 +222,7 @@ struct JxlHipContext {
     float xyb_factor[3] = {0, 0, 0};
     jxlhip::FilterParams xyb_color;
     JxlHipColorTarget xyb_target;
-    std::vector<const JxlHipContext*> batch_ctxs;
-    std::vector<uint64_t> batch_gens;
+    SetMemo batch_set;
     uint32_t batch_n = 0, batch_tree_cap = 0, batch_table_cap = 0;
     bool batch_wp = true, batch_refs = true;
     std::vector<uint32_t> code_table_words;  // per entropy code: words of its symbol tables (ModCode::table_words)
@@ -327,8 +332,7 @@ struct JxlHipContext {
   std::vector<uint32_t> gbb_host;
   std::vector<uint16_t> orders_host;
   uint32_t order_offset_host[39] = {};
-  std::vector<const JxlHipContext*> batch_ctxs;
-  std::vector<uint64_t> batch_gens;
+  SetMemo batch_set;  // jxlhip_run_entropy_batch: the set batch_plan was made for, under batch_kernel and batch_overrides
   hipEvent_t batch_done = nullptr;
   // Set by jxlhip_run_entropy_batch on the contexts whose coefficients a launch on ANOTHER context's stream produces;
   // applied (hipStreamWaitEvent on this context's stream) by the next call that touches those results. Enqueuing the
@@ -357,11 +361,14 @@ struct JxlHipContext {
   hipEvent_t planes_event = nullptr;
   hipStream_t planes_stream = nullptr;
   // jxlhip_run_transform_batch / jxlhip_run_filter_color_batch: description of the frame set launched from this context
-  // (fgroups: the filter launches, jxh_filter_plan.h; fb_params holds the frames' blocks in the plan's order)
+  // (tlaunches: the transform launches, jxh_transform_plan.h, over tb_desc; tblocks: the frames' transform blocks as
+  // resolved for the set, i.e. with the plane holder's buffer, the host copy of tb_params; fgroups: the filter launches,
+  // jxh_filter_plan.h; fb_params holds the frames' blocks in the plan's order). down_set: the set all of it was built for,
+  // with each frame's plane buffer, which a lender's upload may have reallocated without the borrower's generation moving.
   Buf tb_params, tb_desc, fb_params;
-  std::vector<const JxlHipContext*> db_ctxs;
-  std::vector<uint64_t> db_gens;
-  uint32_t desc_begin[27] = {}, desc_count[27] = {};  // (entry 21: the 8x8 DCT varblocks of chroma-subsampled frames)
+  SetMemo down_set;
+  std::vector<jxlhip::TransformParams> tblocks;
+  std::vector<transform_plan::TransformLaunch> tlaunches;
   uint32_t cs = 0;  // chroma-subsampled frame: hshift of channel c in bit 2 * c, vshift in bit 2 * c + 1 (0 = 4:4:4)
   std::vector<filter_plan::FilterGroup> fgroups;
   hipEvent_t down_done = nullptr;
@@ -392,8 +399,7 @@ struct JxlHipContext {
   JxlHipResizedOut resized{};
   resample::ResampleDev rs_dev{};
   Buf rs_block, rs_tmp, rs_src, rs_batch;
-  std::vector<const JxlHipContext*> rs_batch_ctxs;
-  std::vector<uint64_t> rs_batch_gens;
+  SetMemo rs_batch_set;
   // jxlhip_reduced_upload: the context holds the inputs of a reduced image instead of a frame (have_frame and mod.have are
   // then both false). red_block (placed at upload, one staged copy): the kernel's descriptor, the DC groups' precision bytes
   // and the coded integers (jxh_reduced_plan.h BlockLayout); red.dev: the descriptor's host copy, from which a batched launch
@@ -404,8 +410,7 @@ struct JxlHipContext {
     bool have = false, ran = false, dc_kept = false;
     uint64_t generation = 0;  // the context's, as the upload left it: output settings changed since ask for another upload
     jxlhip::ReducedDev dev{};
-    std::vector<const JxlHipContext*> batch_ctxs;
-    std::vector<uint64_t> batch_gens;
+    SetMemo batch_set;
     uint32_t batch_tiles = 0;
   } red;
   Buf red_block, red_batch;
@@ -988,11 +993,9 @@ static int LaunchResample(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) 
     return LaunchResamplePasses(c->rs_block.as<resample::ResampleDev>(), 1, c->rs_dev.v_tiles, c->rs_dev.h_tiles, ls);
   }
   JxlHipContext* c0 = ctxs[0];
-  std::vector<uint64_t> gens(set.size());
   std::vector<resample::ResampleDev> descs(set.size());
   uint64_t v = 0, h = 0;
   for (size_t i = 0; i < set.size(); i++) {
-    gens[i] = set[i]->generation;
     descs[i] = set[i]->rs_dev;
     descs[i].v_tile0 = uint32_t(v);
     descs[i].h_tile0 = uint32_t(h);
@@ -1000,8 +1003,8 @@ static int LaunchResample(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) 
     h += descs[i].h_tiles;
   }
   if (v > 0x7FFFFFFFu || h > 0x7FFFFFFFu) return JXLHIP_ERR_UNSUPPORTED;
-  if (set != c0->rs_batch_ctxs || gens != c0->rs_batch_gens) {
-    c0->rs_batch_ctxs.clear();
+  if (!c0->rs_batch_set.Matches(set.data(), set.size())) {
+    c0->rs_batch_set.Forget();
     const size_t bytes = descs.size() * sizeof(resample::ResampleDev);
     int r = c0->rs_batch.Ensure(bytes);
     if (r) return r;
@@ -1012,8 +1015,7 @@ static int LaunchResample(JxlHipContext* const* ctxs, size_t n, hipStream_t ls) 
     HIP_TRY(hipMemcpyAsync(c0->rs_batch.p, st, bytes, hipMemcpyHostToDevice, ls));
     HIP_TRY(hipEventRecord(c0->stage.done, ls));
     c0->stage.recorded = true;
-    c0->rs_batch_ctxs = set;
-    c0->rs_batch_gens = gens;
+    c0->rs_batch_set.Remember(set.data(), set.size());
   }
   return LaunchResamplePasses(c0->rs_batch.as<resample::ResampleDev>(), uint32_t(set.size()), uint32_t(v), uint32_t(h), ls);
 }
@@ -1190,9 +1192,10 @@ static int EnsureWorkBuffers(JxlHipContext* c, const JxlHipFrameDesc& d, const u
   if (((c->has_noise && c->ups != 1) || c->ups_kept) && (r = c->ups_planes.Ensure(size_t((c->oxs + 7) & ~7u) * c->oys * 3 * 4))) return r;
   if (P.px.plane1 && (r = c->plane[1].Ensure(c->plane_bytes))) return r;
   if (!c->tensor_bound && (r = c->rgb.Ensure(OwnPixelBytes(c)))) return r;
-  uint32_t big = 0;  // the largest transforms go through scratch planes, 32 varblocks at a time
-  for (int s = 21; s < 27; s++) big = std::max(big, P.list_count[s]);
-  if (big && (r = c->scratch.Ensure(size_t(std::min(big, 32u)) * 3 * 2 * 65536 * 4))) return r;
+  uint32_t big = 0;  // the largest transforms go through scratch planes, a launch's varblocks at a time
+  for (uint32_t s = 0; s < jxlhip::kTransformStrategies; s++)
+    if (jxlhip::TransformClassOf(s) == jxlhip::kBigClass) big = std::max(big, P.list_count[s]);
+  if (big && (r = c->scratch.Ensure(jxlhip::BigScratchBytes(big)))) return r;
   if (E.any_lz77 && (r = c->lz_window.Ensure(size_t(d.num_groups) * jxlhip::kLzWindow * 4))) return r;
   if ((r = c->sec_end.Ensure(P.g.nsec * 4))) return r;
   HIP_TRY(hipMemsetAsync(c->sec_end.p, 0, P.g.nsec * 4, c->stream));
@@ -1285,7 +1288,9 @@ static void FillTransformParams(JxlHipContext* c, const JxlHipFrameDesc& d) {
   tp.base_b = d.base_corr_b;
   memcpy(tp.biases, d.quant_biases, sizeof(tp.biases));
   tp.xb = c->xb; tp.yb = c->yb; tp.xg = c->xg; tp.xp = c->xp; tp.yp = c->yp;
-  tp.out = PlaneHolder(c)->plane[0].as<float>();  // (a lender's buffer is checked again at launch: PrepareDownstream)
+  // (the planes as they stand now: every launch takes `out` and `cs_out` from the block ResolveTransformBlocks makes for
+  // its set, where a lender's buffer is checked)
+  tp.out = PlaneHolder(c)->plane[0].as<float>();
   tp.scratch = c->scratch.as<float>();
   tp.tlist = c->tlist.as<uint32_t>();
   tp.trecs = c->trecs.as<uint4>();
@@ -1466,87 +1471,59 @@ static int RunEntropySingle(JxlHipContext* c) {
 }
 
 // ---- transform + filter launches, batched over the frames of a set ---------------------------------------------------
-// Varblocks a workgroup of the strategy's kernel handles.
-static uint32_t BlocksPerWG(int s) {
-  const uint32_t cx = jxlhip::kCoveredX[s], cy = jxlhip::kCoveredY[s];
-  if (s == 0 || (s >= 4 && s <= 11) || (s >= 18 && s <= 20))  // k_idct_fast: max(rows, columns) threads per varblock
-    return jxlhip::IdctFastThreads(cx, cy) / ((cx > cy ? cx : cy) * 8);
-  return 4;  // k_special
+// The kernel of a descriptor list (jxl_hip_transform_abi.h): the strategy's class and covered blocks pick it, and the list
+// of chroma-subsampled frames takes the 8x8 DCT's CS form.
+typedef void (*ListKernel)(const jxlhip::TransformParams*, const uint2*, uint32_t);
+template <typename CoefT, uint32_t S>
+constexpr ListKernel KernelOfStrategy() {
+  if constexpr (jxlhip::TransformClassOf(S) == jxlhip::kFastClass)
+    return jxlhip::k_idct_fast<CoefT, jxlhip::kCoveredX[S], jxlhip::kCoveredY[S]>;
+  else
+    return jxlhip::k_special<CoefT>;
+}
+template <typename CoefT, size_t... S>
+static ListKernel ListKernelOf(uint32_t list, std::index_sequence<S...>) {
+  static const ListKernel kTable[] = {KernelOfStrategy<CoefT, uint32_t(S)>()..., jxlhip::k_idct_fast<CoefT, 1, 1, true>};
+  static_assert(sizeof...(S) == jxlhip::kSubsampledList && sizeof(kTable) / sizeof(kTable[0]) == jxlhip::kTransformLists, "a kernel per list");
+  return kTable[list];
 }
 
-template <typename CoefT, int CX, int CY, bool CS = false>
-static int LaunchIdctFast(JxlHipContext* c0, int s) {
-  constexpr int C = CX * 8, R = CY * 8, TB = R > C ? R : C, GROUPS = jxlhip::IdctFastThreads(CX, CY) / TB;
-  constexpr size_t lds = size_t(GROUPS) * R * (C + 1) * sizeof(float);
-  const int li = CS ? 21 : s;  // (the work list; the strategy stays s)
-  hipLaunchKernelGGL((jxlhip::k_idct_fast<CoefT, CX, CY, CS>), dim3(c0->desc_count[li]), dim3(jxlhip::IdctFastThreads(CX, CY)), lds, c0->stream,
-                     c0->tb_params.as<jxlhip::TransformParams>(), c0->tb_desc.as<uint2>() + c0->desc_begin[li], uint32_t(s));
-  return 0;
-}
-
+// A launch per entry of the set's plan (jxh_transform_plan.h), in the plan's order. Every address comes from the frame's
+// resolved block (ResolveTransformBlocks).
 template <typename CoefT>
 static int LaunchTransforms(JxlHipContext* c0) {
-  for (int s = 0; s < 21; s++) {
-    if (!c0->desc_count[s]) continue;
-    int e = 0;
-    switch (s) {
-      case 0: e = LaunchIdctFast<CoefT, 1, 1>(c0, s); break;
-      case 4: e = LaunchIdctFast<CoefT, 2, 2>(c0, s); break;
-      case 5: e = LaunchIdctFast<CoefT, 4, 4>(c0, s); break;
-      case 6: e = LaunchIdctFast<CoefT, 1, 2>(c0, s); break;
-      case 7: e = LaunchIdctFast<CoefT, 2, 1>(c0, s); break;
-      case 8: e = LaunchIdctFast<CoefT, 1, 4>(c0, s); break;
-      case 9: e = LaunchIdctFast<CoefT, 4, 1>(c0, s); break;
-      case 10: e = LaunchIdctFast<CoefT, 2, 4>(c0, s); break;
-      case 11: e = LaunchIdctFast<CoefT, 4, 2>(c0, s); break;
-      case 18: e = LaunchIdctFast<CoefT, 8, 8>(c0, s); break;  // (the 64-class: one varblock per wave)
-      case 19: e = LaunchIdctFast<CoefT, 4, 8>(c0, s); break;
-      case 20: e = LaunchIdctFast<CoefT, 8, 4>(c0, s); break;
-      default:
-        hipLaunchKernelGGL((jxlhip::k_special<CoefT>), dim3(c0->desc_count[s]), dim3(256), 0, c0->stream,
-                           c0->tb_params.as<jxlhip::TransformParams>(), c0->tb_desc.as<uint2>() + c0->desc_begin[s], uint32_t(s));
-    }
-    if (e) return e;
-    HIP_TRY(hipGetLastError());
-  }
-  if (c0->desc_count[21]) {  // the 8x8 DCT varblocks of chroma-subsampled frames
-    int e = LaunchIdctFast<CoefT, 1, 1, true>(c0, 0);
-    if (e) return e;
-    HIP_TRY(hipGetLastError());
-  }
-  // ... whose subsampled channels then go back to the frame's resolution, in front of the filters
-  for (const JxlHipContext* c : c0->db_ctxs) {
-    if (!c->cs) continue;
-    for (uint32_t ch = 0; ch < 3; ch++) {
-      jxlhip::ChromaUpParams up;
-      up.hs = (c->cs >> (2 * ch)) & 1u;
-      up.vs = (c->cs >> (2 * ch + 1)) & 1u;
-      if (!(up.hs | up.vs)) continue;
-      const size_t plane = size_t(c->xp) * c->yp;
-      up.src = c->plane[1].as<float>() + ch * plane;
-      up.dst = PlaneHolder(c)->plane[0].as<float>() + ch * plane;
-      up.xs = c->xs;
-      up.ys = c->ys;
-      up.xp = c->xp;
-      up.y0 = c->ext_y0;
-      up.y1 = c->ext_y1;
-      if (up.y1 <= up.y0) continue;
-      hipLaunchKernelGGL(jxlhip::k_chroma_upsample, dim3((up.xs + 63) / 64, (up.y1 - up.y0 + 3) / 4), dim3(256), 0, c0->stream, up);
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  // 128/256-class transforms go through per-frame global scratch: one frame at a time (rare)
-  for (const JxlHipContext* c : c0->db_ctxs)
-    for (int s = 21; s < 27; s++) {
-      const uint32_t n = c->list_count[s];
-      if (!n) continue;
-      const uint32_t* list = c->tlist.as<uint32_t>() + c->list_begin[s];
-      for (uint32_t i = 0; i < n; i += 32) {
-        const uint32_t m = n - i < 32 ? n - i : 32;
-        hipLaunchKernelGGL((jxlhip::k_dct_big<CoefT>), dim3(m * 3), dim3(256), 0, c0->stream, c->tp, list + i, m, uint32_t(s));
+  for (const transform_plan::TransformLaunch& L : c0->tlaunches) {
+    const dim3 grid(L.grid_x, L.grid_y), block(L.block);
+    switch (L.kind) {
+      case transform_plan::kListLaunch:
+        hipLaunchKernelGGL(ListKernelOf<CoefT>(L.list, std::make_index_sequence<jxlhip::kSubsampledList>()), grid, block, L.lds, c0->stream,
+                           c0->tb_params.as<jxlhip::TransformParams>(), c0->tb_desc.as<uint2>() + L.first, L.strategy);
+        break;
+      case transform_plan::kChromaUpLaunch: {  // a subsampled channel back to the frame's resolution, in front of the filters
+        const JxlHipContext* c = c0->down_set[L.frame];
+        const jxlhip::TransformParams& tp = c0->tblocks[L.frame];
+        const size_t plane = size_t(tp.xp) * tp.yp;
+        jxlhip::ChromaUpParams up;
+        up.src = tp.cs_out + L.channel * plane;
+        up.dst = tp.out + L.channel * plane;
+        up.xs = c->xs;
+        up.ys = c->ys;
+        up.xp = tp.xp;
+        up.y0 = c->ext_y0;
+        up.y1 = c->ext_y1;
+        up.hs = (tp.cs >> (2 * L.channel)) & 1u;
+        up.vs = (tp.cs >> (2 * L.channel + 1)) & 1u;
+        hipLaunchKernelGGL(jxlhip::k_chroma_upsample, grid, block, 0, c0->stream, up);
+        break;
       }
-      HIP_TRY(hipGetLastError());
+      case transform_plan::kBigLaunch: {  // through the frame's global scratch: one frame at a time (rare)
+        const jxlhip::TransformParams& tp = c0->tblocks[L.frame];
+        hipLaunchKernelGGL((jxlhip::k_dct_big<CoefT>), grid, block, 0, c0->stream, tp, tp.tlist + tp.list_begin[L.strategy] + L.first, L.count, L.strategy);
+        break;
+      }
     }
+    HIP_TRY(hipGetLastError());
+  }
   return 0;
 }
 
@@ -1599,49 +1576,61 @@ static int PlanFilterLaunches(JxlHipContext* c0, JxlHipContext* const* ctxs, siz
   for (size_t j = 0; j < n; j++) (*fparams)[j] = blocks[plan.order[j]];
   return 0;
 }
-// Builds (or re-uses) the description of a set of frames for the batched transform and filter launches.
-static int PrepareDownstream(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n) {
-  bool same = c0->db_ctxs.size() == n;
-  for (size_t i = 0; same && i < n; i++) same = c0->db_ctxs[i] == ctxs[i] && c0->db_gens[i] == ctxs[i]->generation;
-  if (same) return 0;
-  std::vector<jxlhip::TransformParams> tparams(n);
+// Each frame's transform block as the set's launches take it: the frame's own, with the planes of whoever holds them now.
+static int ResolveTransformBlocks(JxlHipContext* const* ctxs, size_t n, std::vector<jxlhip::TransformParams>* blocks) {
+  blocks->resize(n);
   for (size_t i = 0; i < n; i++) {
-    tparams[i] = ctxs[i]->tp;
-    const JxlHipContext* h = PlaneHolder(ctxs[i]);
-    if (!h->plane[0].p || h->plane[0].cap < ctxs[i]->plane_bytes) return JXLHIP_ERR_INVALID_ARGUMENT;  // lender too small
-    tparams[i].out = h->plane[0].as<float>();
-    if (ctxs[i]->cs && (!ctxs[i]->plane[1].p || ctxs[i]->plane[1].cap < ctxs[i]->plane_bytes)) return JXLHIP_ERR_INVALID_ARGUMENT;
-    tparams[i].cs_out = ctxs[i]->plane[1].as<float>();
+    const JxlHipContext* c = ctxs[i];
+    jxlhip::TransformParams& tp = (*blocks)[i];
+    tp = c->tp;
+    const JxlHipContext* h = PlaneHolder(c);
+    if (!h->plane[0].p || h->plane[0].cap < c->plane_bytes) return JXLHIP_ERR_INVALID_ARGUMENT;  // lender too small
+    tp.out = h->plane[0].as<float>();
+    if (c->cs && (!c->plane[1].p || c->plane[1].cap < c->plane_bytes)) return JXLHIP_ERR_INVALID_ARGUMENT;
+    tp.cs_out = c->plane[1].as<float>();
   }
-  std::vector<uint2> desc;
-  for (int s = 0; s < 22; s++) {  // (21: the 8x8 DCT varblocks of chroma-subsampled frames, which list 0 leaves out)
-    c0->desc_begin[s] = uint32_t(desc.size());
-    const int st = s == 21 ? 0 : s;
-    const uint32_t bpw = BlocksPerWG(st);
-    for (size_t i = 0; i < n; i++) {
-      if (st == 0 && (ctxs[i]->cs != 0) != (s == 21)) continue;
-      for (uint32_t j = 0; j < ctxs[i]->list_count[st]; j += bpw) desc.push_back(make_uint2(uint32_t(i), j));
-    }
-    c0->desc_count[s] = uint32_t(desc.size()) - c0->desc_begin[s];
+  return 0;
+}
+static void PlanTransforms(JxlHipContext* const* ctxs, size_t n, transform_plan::TransformPlan* plan) {
+  std::vector<transform_plan::TransformFrame> frames(n);
+  for (size_t i = 0; i < n; i++) {
+    const JxlHipContext* c = ctxs[i];
+    memcpy(frames[i].list_count, c->list_count, sizeof(frames[i].list_count));
+    frames[i].cs = c->cs;
+    frames[i].xs = c->xs;
+    frames[i].ext_y0 = c->ext_y0;
+    frames[i].ext_y1 = c->ext_y1;
   }
-  // filter launches: frames grouped by filter form, one grid z slice per frame
-  std::vector<jxlhip::FusedFilterParams> fparams;
+  transform_plan::PlanTransformLaunches(frames.data(), n, plan);
+}
+// Builds (or re-uses) the description of a set of frames for the batched transform and filter launches: resolve the
+// frames' blocks, plan the transforms, plan the filters, ensure the buffers, copy.
+static int PrepareDownstream(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n) {
+  std::vector<uintptr_t> planes(n);  // (what a block's `out` will be)
+  for (size_t i = 0; i < n; i++) planes[i] = uintptr_t(PlaneHolder(ctxs[i])->plane[0].p);
+  if (c0->down_set.Matches(ctxs, n, planes.data())) return 0;
+  c0->down_set.Forget();
   int r;
+  if ((r = ResolveTransformBlocks(ctxs, n, &c0->tblocks))) return r;
+  transform_plan::TransformPlan tplan;
+  PlanTransforms(ctxs, n, &tplan);
+  std::vector<jxlhip::FusedFilterParams> fparams;
   if ((r = PlanFilterLaunches(c0, ctxs, n, &fparams))) return r;
+  const std::vector<jxlhip::TransformParams>& tparams = c0->tblocks;
+  static_assert(sizeof(transform_plan::WorkgroupDesc) == sizeof(uint2), "the kernels read a descriptor as a uint2");
   if ((r = c0->tb_params.Ensure(n * sizeof(tparams[0])))) return r;
-  if ((r = c0->tb_desc.Ensure((desc.size() + 1) * sizeof(uint2)))) return r;
+  if ((r = c0->tb_desc.Ensure((tplan.desc.size() + 1) * sizeof(uint2)))) return r;
   if ((r = c0->fb_params.Ensure(n * sizeof(fparams[0])))) return r;
   {
     ParamCopy pc;
     if ((r = pc.Begin(c0))) return r;
     if ((r = pc.Add(c0->tb_params.p, tparams.data(), n * sizeof(tparams[0])))) return r;
-    if ((r = pc.Add(c0->tb_desc.p, desc.data(), desc.size() * sizeof(uint2)))) return r;
+    if ((r = pc.Add(c0->tb_desc.p, tplan.desc.data(), tplan.desc.size() * sizeof(uint2)))) return r;
     if ((r = pc.Add(c0->fb_params.p, fparams.data(), n * sizeof(fparams[0])))) return r;
     if ((r = pc.End())) return r;
   }
-  c0->db_ctxs.assign(ctxs, ctxs + n);
-  c0->db_gens.resize(n);
-  for (size_t i = 0; i < n; i++) c0->db_gens[i] = ctxs[i]->generation;
+  c0->tlaunches = std::move(tplan.launches);
+  c0->down_set.Remember(ctxs, n, planes.data());
   return 0;
 }
 
@@ -1915,7 +1904,7 @@ static int LaunchEntropyLanesW(JxlHipContext* c0) {
   b.extra_pass_min = jxlhip::kLanesExtraPassMin;
   b.debug = uint32_t(EnvInt("JXLHIP_LANES_DEBUG", 0));
   b.prof = nullptr;
-  b.started = c0->batch_ctxs.size() > 1 ? GateCounter(c0) : nullptr;
+  b.started = c0->batch_set.size() > 1 ? GateCounter(c0) : nullptr;
   // debugging aid: per-wave cycle split, printed to stderr (1); 2: per-wave start and end on the clock all XCDs share, kept
   // for jxlhip_debug_entropy_timeline and not waited for, so that the launches around this one overlap it as they do unprofiled
   const int prof_mode = EnvInt("JXLHIP_LANES_PROF", 0);
@@ -2019,9 +2008,7 @@ static int LaunchEntropyUniBatch(JxlHipContext* c0) {
 // the lane-parallel kernel, the lane -> section assignment, and stays in the context for the launch to read.
 static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n, int kernel) {
   const lane_plan::LaneOverrides overrides = LaneOverridesFromEnv();
-  bool same = c0->batch_ctxs.size() == n && c0->batch_kernel == kernel && c0->batch_overrides == overrides;
-  for (size_t i = 0; same && i < n; i++) same = c0->batch_ctxs[i] == ctxs[i] && c0->batch_gens[i] == ctxs[i]->generation;
-  if (same) return 0;
+  if (c0->batch_set.Matches(ctxs, n) && c0->batch_kernel == kernel && c0->batch_overrides == overrides) return 0;
 
   lane_plan::LanePlan plan;
   if (kernel == 2) {
@@ -2070,9 +2057,7 @@ static int PrepareBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n,
   }
   if ((r = pc.End())) return r;
 
-  c0->batch_ctxs.assign(ctxs, ctxs + n);
-  c0->batch_gens.resize(n);
-  for (size_t i = 0; i < n; i++) c0->batch_gens[i] = ctxs[i]->generation;
+  c0->batch_set.Remember(ctxs, n);
   c0->batch_kernel = kernel;
   c0->batch_overrides = overrides;
   c0->batch_plan = std::move(plan);
@@ -2346,7 +2331,7 @@ extern "C" int jxlhip_modular_upload(JxlHipContext* c, const JxlHipModFrameDesc*
   HIP_TRY(WaitEvent(c->stage.done));
   if (c->resized_bound && (r = PlaceResampleOfFrame(c))) return r;
   c->mod.have = true;
-  c->mod.batch_ctxs.clear();
+  c->mod.batch_set.Forget();
   c->generation++;
   return 0;
 }
@@ -2576,9 +2561,7 @@ extern "C" int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n) {
     if (r) return r;
   }
   JxlHipContext::Modular& M0 = c0->mod;
-  bool same = M0.batch_ctxs.size() == n;
-  for (size_t i = 0; same && i < n; i++) same = M0.batch_ctxs[i] == ctxs[i] && M0.batch_gens[i] == ctxs[i]->generation;
-  if (!same) {
+  if (!M0.batch_set.Matches(ctxs, n)) {
     // every stream of every frame, largest first: the lanes of a wave then carry streams of similar length
     struct Ref {
       uint32_t samples;
@@ -2593,9 +2576,7 @@ extern "C" int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n) {
     int r = M0.batch_streams.Ensure(flat.size() * sizeof(jxlhip::ModStream));
     if (r) return r;
     HIP_TRY(hipMemcpy(M0.batch_streams.p, flat.data(), flat.size() * sizeof(jxlhip::ModStream), hipMemcpyHostToDevice));
-    M0.batch_ctxs.assign(ctxs, ctxs + n);
-    M0.batch_gens.resize(n);
-    for (size_t i = 0; i < n; i++) M0.batch_gens[i] = ctxs[i]->generation;
+    M0.batch_set.Remember(ctxs, n);
     M0.batch_n = uint32_t(all.size());
     uint32_t cap = 0;  // LDS room for the largest tree of the batch that fits (waves whose streams share a tree stage it)
     for (const Ref& q : all)
@@ -2796,10 +2777,8 @@ extern "C" int jxlhip_reduced_run_batch(JxlHipContext* const* ctxs, size_t n) {
   uint32_t tiles = c0->red.dev.h.tiles;
   if (n > 1) {
     JxlHipContext::Reduced& R = c0->red;
-    bool same = R.batch_ctxs.size() == n;
-    for (size_t i = 0; same && i < n; i++) same = R.batch_ctxs[i] == ctxs[i] && R.batch_gens[i] == ctxs[i]->generation;
-    if (!same) {
-      R.batch_ctxs.clear();
+    if (!R.batch_set.Matches(ctxs, n)) {
+      R.batch_set.Forget();
       const size_t bytes = reduced::BatchBytes(n, sizeof(jxlhip::ReducedDev));
       if ((r = c0->red_batch.Ensure(bytes))) return r;
       std::vector<const void*> each(n);
@@ -2811,9 +2790,7 @@ extern "C" int jxlhip_reduced_run_batch(JxlHipContext* const* ctxs, size_t n) {
       HIP_TRY(hipMemcpyAsync(c0->red_batch.p, st, bytes, hipMemcpyHostToDevice, ls));
       HIP_TRY(hipEventRecord(c0->stage.done, ls));
       c0->stage.recorded = true;
-      R.batch_ctxs.assign(ctxs, ctxs + n);
-      R.batch_gens.resize(n);
-      for (size_t i = 0; i < n; i++) R.batch_gens[i] = ctxs[i]->generation;
+      R.batch_set.Remember(ctxs, n);
     }
     descs = c0->red_batch.as<jxlhip::ReducedDev>();
     tiles = R.batch_tiles;

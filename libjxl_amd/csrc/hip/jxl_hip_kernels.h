@@ -23,6 +23,7 @@
 
 #include "../../../include/jxl_amd_hip.h"
 #include "jxl_hip_block_ctx.h"
+#include "jxl_hip_transform_abi.h"
 
 namespace jxlhip {
 
@@ -966,9 +967,7 @@ __device__ __forceinline__ void WaveLdsSync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// threads per workgroup: one wave (e.g. two 32x32 varblocks, 8.4 KB of LDS; eight 8x8 ones), so that a workgroup fits into
-// the LDS the resident entropy workgroups leave free and a barrier stalls one wave only
-__host__ __device__ constexpr int IdctFastThreads(int cx, int cy) { return (void(cx), void(cy), 64); }
+// (IdctFastThreads, the threads per workgroup, and the other sizes the launches share: jxl_hip_transform_abi.h)
 
 // CS: the frame is chroma subsampled (TransformParams::cs; the 8x8 class only: such frames have no larger varblocks).
 template <typename CoefT, int CX, int CY, bool CS = false>
@@ -978,7 +977,8 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
   JXL_TRANSFORM_PREAMBLE();
   static_assert(!CS || (CX == 1 && CY == 1), "chroma-subsampled frames: varblocks of one block only");
   static_assert(IdctFastThreads(CX, CY) == 64, "WaveLdsSync: the workgroup is one wave");
-  constexpr int R = CY * 8, C = CX * 8, SIZE = R * C, TB = R > C ? R : C, S = C + 1, TILE = R * S;
+  constexpr int R = CY * 8, C = CX * 8, SIZE = R * C, TB = IdctFastBlockThreads(CX, CY), S = C + 1, TILE = IdctFastTileFloats(CX, CY);
+  static_assert(TB == (R > C ? R : C) && TILE == R * S, "the tile the launch sizes the LDS for");
   constexpr int LOGC = CX == 1 ? 3 : (CX == 2 ? 4 : (CX == 4 ? 5 : 6));
   extern __shared__ __align__(16) float lds_f[];
   const int grp = threadIdx.x / TB, t = threadIdx.x % TB;
@@ -1237,9 +1237,10 @@ __global__ __launch_bounds__(IdctFastThreads(CX, CY)) __attribute__((amdgpu_wave
 
 // 128/256-class transforms: one workgroup per (varblock, channel), intermediates in global scratch.
 template <typename CoefT>
-__global__ __launch_bounds__(256) void k_dct_big(TransformParams P, const uint32_t* list, uint32_t n, uint32_t strategy) {
-  const uint32_t li = blockIdx.x / 3;
-  const int c = blockIdx.x % 3;
+__global__ __launch_bounds__(kBigThreads) void k_dct_big(TransformParams P, const uint32_t* list, uint32_t n, uint32_t strategy) {
+  static_assert(kBigWGsPerBlock == 3 && kBigThreads == 256 && kBigScratchFloatsPerWG == 2 * 65536, "a workgroup per channel, strides of 256 threads, two scratch planes");
+  const uint32_t li = blockIdx.x / kBigWGsPerBlock;
+  const int c = blockIdx.x % kBigWGsPerBlock;
   if (li >= n) return;
   const uint32_t CX = c_covered_x[strategy], CY = c_covered_y[strategy];
   const uint32_t R = CY * 8, C = CX * 8, SIZE = R * C;
@@ -1254,7 +1255,7 @@ __global__ __launch_bounds__(256) void k_dct_big(TransformParams P, const uint32
   const uint32_t tile = (vb.by / 8) * tiles_x + vb.bx / 8;
   const float x_cc = P.base_x + float(P.ytox[tile]) * P.color_scale;
   const float b_cc = P.base_b + float(P.ytob[tile]) * P.color_scale;
-  float* s_coef = P.scratch + size_t(blockIdx.x) * 2 * 65536;
+  float* s_coef = P.scratch + size_t(blockIdx.x) * kBigScratchFloatsPerWG;
   float* s_tmp = s_coef + 65536;
   const uint32_t ord = c_strategy_order[strategy];
   if (c != 1) {  // dequantised Y first (into s_tmp, free until the first transform pass) for the chroma-from-luma term
@@ -1314,11 +1315,12 @@ __global__ __launch_bounds__(256) void k_dct_big(TransformParams P, const uint32
 __device__ __forceinline__ float B4(const float* bt4, int n, int k) { return bt4[k * 4 + n]; }
 __device__ __forceinline__ float B8(const float* bt8, int n, int k) { return bt8[k * 8 + n]; }
 
-// 8x8-coverage special transforms; 64 threads per varblock (one per pixel), 4 varblocks per workgroup.
+// 8x8-coverage special transforms; 64 threads per varblock (one per pixel), kSpecialBlocksPerWG varblocks per workgroup.
 template <typename CoefT>
-__global__ __launch_bounds__(256) void k_special(const TransformParams* params, const uint2* desc, uint32_t strategy) {
+__global__ __launch_bounds__(kSpecialThreads) void k_special(const TransformParams* params, const uint2* desc, uint32_t strategy) {
   JXL_TRANSFORM_PREAMBLE();
-  __shared__ float l_all[4][4][64];
+  __shared__ float l_all[kSpecialBlocksPerWG][4][64];
+  static_assert(kSpecialThreads >> 6 == kSpecialBlocksPerWG, "threadIdx.x >> 6 indexes l_all");
   const int sub = threadIdx.x >> 6, t = threadIdx.x & 63;
   float* l_y = l_all[sub][0];  // dequantised Y stays resident for the chroma-from-luma of X and B
   float* l_xb = l_all[sub][1];
@@ -1499,9 +1501,9 @@ struct ChromaUpParams {
   uint32_t hs, vs;   // the channel's shifts (0 or 1, not both 0)
 };
 __device__ __forceinline__ uint32_t ChromaMirror(int32_t i, uint32_t n) { return i < 0 ? 0u : (uint32_t(i) >= n ? n - 1 : uint32_t(i)); }
-__global__ __launch_bounds__(256) void k_chroma_upsample(ChromaUpParams P) {
+__global__ __launch_bounds__(kChromaUpThreads) void k_chroma_upsample(ChromaUpParams P) {
 #pragma clang fp contract(off)
-  const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = P.y0 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  const uint32_t x = blockIdx.x * kChromaUpCols + (threadIdx.x % kChromaUpCols), y = P.y0 + blockIdx.y * kChromaUpRows + (threadIdx.x / kChromaUpCols);
   if (x >= P.xs || y >= P.y1) return;
   const uint32_t ws = (P.xs + 1) / 2, hh = (P.ys + 1) / 2;
   auto row_value = [&](uint32_t r) -> float {  // the horizontal stage's output at column x of (subsampled) row r

@@ -144,3 +144,74 @@ def test_batch_of_three_frames(built):
         for c, fr in zip(ctxs, frames):
             c.close()
             fr.close()
+
+
+def test_one_batch_of_every_launch_kind_in_two_orders(built):
+    """One run_transform_batch over the large-class frame, the scan-order frame, a 4:2:0 frame and a frame of k_special's
+    strategies: every kind of launch the set's plan holds (descriptor lists 0 and 21 beside each other, the upsampling of
+    two channels, chunks of the big class through the frame's resolved block), with the frames in two orders. Each frame
+    against its own reading, and bit for bit what the same frame gives when it runs alone (a subsampled frame over its own
+    rows and columns: the upsampling writes those, and nothing writes the padding of the planes beyond them)."""
+    J = built
+    cases = [(S.mixed_stream(J, "large"), 0), (S.mixed_stream(J, "one_pass"), 0), (S.subsampled_stream(J, S.SUBSAMPLED_KW[0]), S.CS420),
+             (S.batch_stream(J, 0), 0)]
+    assert S.SUBSAMPLED_KW[0] == dict(chroma_subsampling=S.CS420)
+    fields = [_oracle_side(d) for d, _ in cases]
+    assert fields[0]["size"] == (648, 392) and fields[2]["size"] == (264, 200)
+    S.assert_mixed_holds(fields[0]["acs"], "large")
+    S.assert_holds(fields[3]["acs"], S.NOT_DCT)
+    alone = [_run(J, d) for d, _ in cases]
+    alone = [a[2] for a in alone]  # (xyb_idct)
+    frames = [J.Frame(d, threads=2) for d, _ in cases]
+    ctxs = [J.HipContext() for _ in cases]
+    try:
+        for c, fr in zip(ctxs, frames):
+            c.upload(fr)
+            c.run_entropy()
+            c.sync()
+            r, flags = c.errors()
+            assert r == 0 and not any(flags)
+        for order in ((0, 1, 2, 3), (2, 3, 1, 0)):
+            J.run_transform_batch([ctxs[i] for i in order])
+            for c in ctxs:
+                c.sync()
+            for i in order:
+                planes = ctxs[i].download("xyb_idct")
+                _check(fields[i], ctxs[i].download("coeffs"), ctxs[i].download("dc"), planes, cases[i][1])
+                w, h = fields[i]["size"] if cases[i][1] else planes.shape[:0:-1]
+                assert np.array_equal(planes[:, :h, :w].view(np.uint32), alone[i][:, :h, :w].view(np.uint32)), "frame %d in order %s differs from its run alone" % (i, order)
+    finally:
+        for c, fr in zip(ctxs, frames):
+            c.close()
+            fr.close()
+
+
+def test_planes_shared_after_the_upload(built):
+    """jxlhip_share_planes behind the upload: the frame's block still names its own planes, the set's resolved block the
+    lender's. Every transform class (the big one took the block as uploaded) must write where the filters read: the pixels
+    of the large-class frame equal an unshared decode's. The lender holds the same frame and has not run, so its planes
+    hold nothing a misdirected class could leave to be found there."""
+    J = built
+    data = S.mixed_stream(J, "large")
+    S.assert_mixed_holds(_oracle_side(data)["acs"], "large")
+    fr = J.Frame(data, threads=2)
+    a, b, c = J.HipContext(), J.HipContext(), J.HipContext()
+    try:
+        c.upload(fr)
+        c.run_entropy()
+        c.run_transform()
+        c.run_filter_color()
+        want = c.rgb8().copy()
+        a.upload(fr)
+        b.upload(fr)
+        b.share_planes(a)
+        b.run_entropy()
+        b.run_transform()
+        b.run_filter_color()
+        got = b.rgb8()
+        assert got.shape == want.shape and want.max() > want.min()
+        assert np.array_equal(got, want), "%d samples differ" % int((got != want).sum())
+    finally:
+        for x in (a, b, c):
+            x.close()
+        fr.close()
