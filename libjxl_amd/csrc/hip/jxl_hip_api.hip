@@ -21,6 +21,7 @@
 #include "../host/jxh_enc_shared.h"
 #include "../host/jxh_filter_plan.h"
 #include "../host/jxh_lane_plan.h"
+#include "../host/jxh_modular_launch_plan.h"
 #include "../host/jxh_modular_upload_plan.h"
 #include "../host/jxh_reduced_plan.h"
 #include "../host/jxh_resample_plan.h"
@@ -43,6 +44,7 @@ namespace upload = jxlhip::upload;
 namespace tensor_out = jxlhip::tensor_out;
 namespace resample = jxlhip::resample;
 namespace lane_plan = jxh::lane_plan;
+namespace modular_launch = jxh::modular_launch;
 namespace filter_plan = jxh::filter_plan;
 namespace transform_plan = jxh::transform_plan;
 struct JxlHipContext;
@@ -222,12 +224,13 @@ struct JxlHipContext {
     float xyb_factor[3] = {0, 0, 0};
     jxlhip::FilterParams xyb_color;
     JxlHipColorTarget xyb_target;
-    SetMemo batch_set;
-    uint32_t batch_n = 0, batch_tree_cap = 0, batch_table_cap = 0;
-    bool batch_wp = true, batch_refs = true;
     std::vector<uint32_t> code_table_words;  // per entropy code: words of its symbol tables (ModCode::table_words)
-    Buf batch_ops;                            // parameter blocks of the set's transform / output launches
-    std::vector<ModLaunch> batch_launches;
+    // jxlhip_modular_run_batch (PrepareModBatch): the set batch_plan was made for, under batch_lanes_override;
+    // batch_streams holds the set's stream descriptors in launch order
+    SetMemo batch_set;
+    int batch_lanes_override = 0;  // JXLHIP_MOD_LANES (measurement aid) as the plan was made under it
+    modular_launch::ModBatchPlan batch_plan;
+    Buf batch_ops;  // parameter blocks of the set's transform / output launches
   } mod;
   size_t plane_bytes = 0;  // bytes of plane[0] the current frame needs
   Buf ep_dev;                         // device copy of `ep` (the entropy kernel reads it through the scalar cache)
@@ -762,6 +765,28 @@ static int ApplyPendingWait(JxlHipContext* c) {
     HIP_TRY(hipStreamWaitEvent(c->stream, c->filter_wait, 0));
     c->filter_wait = nullptr;
   }
+  return 0;
+}
+// The two ends of a batched launch that runs on the first context's stream (the Modular and the reduced batch). Before it:
+// the pending waits of the set, then the first stream waits for what the others still have in flight.
+static int JoinSetOnFirstStream(JxlHipContext* const* ctxs, size_t n) {
+  int r;
+  for (size_t i = 0; i < n; i++)
+    if ((r = ApplyPendingWait(ctxs[i]))) return r;
+  for (size_t i = 1; i < n; i++) {
+    if (!ctxs[i]->down_done) HIP_TRY(hipEventCreateWithFlags(&ctxs[i]->down_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ctxs[i]->down_done, ctxs[i]->stream));
+    HIP_TRY(hipStreamWaitEvent(ctxs[0]->stream, ctxs[i]->down_done, 0));
+  }
+  return 0;
+}
+// Behind it: the next call on one of the other contexts waits for the launch.
+static int PublishBatchDone(JxlHipContext* const* ctxs, size_t n) {
+  if (n < 2) return 0;
+  JxlHipContext* c0 = ctxs[0];
+  if (!c0->batch_done) HIP_TRY(hipEventCreateWithFlags(&c0->batch_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(c0->batch_done, c0->stream));
+  for (size_t i = 1; i < n; i++) ctxs[i]->pending_wait = c0->batch_done;
   return 0;
 }
 
@@ -2503,9 +2528,7 @@ static void ModAppendPass(JxlHipContext* const* ctxs, size_t n, uint32_t kind, b
     memset(&b, 0, sizeof(b));
     if (!fill(ctxs[i], &b)) continue;
     upload::ModBlobAppend(blob, &b, sizeof(b));
-    L.count++;
-    L.gx = rows ? 1 : std::max(L.gx, (ctxs[i]->mod.xs + 255) / 256);
-    L.gy = std::max(L.gy, ctxs[i]->mod.ys);
+    modular_launch::ModPassAdd(&L, rows, ctxs[i]->mod.xs, ctxs[i]->mod.ys);
   }
   if (L.count) launches->push_back(L);
 }
@@ -2525,25 +2548,72 @@ static void ModularBuildOps(JxlHipContext* const* ctxs, size_t n, std::vector<ui
   ModAppendPass(ctxs, n, 5, true, FillModSplines, blob, launches);
   ModAppendPass(ctxs, n, 3, false, FillModOutput, blob, launches);
 }
-static int ModularLaunchOps(const std::vector<ModLaunch>& launches, const uint8_t* dev, hipStream_t st) {
-  for (const ModLaunch& L : launches)
-    for (uint32_t z = 0; z < L.count; z += 65535) {  // grid z / y limit
-      const uint32_t zn = std::min<uint32_t>(L.count - z, 65535);
-      const uint32_t gy = std::min<uint32_t>(L.gy, 4096);  // (the row loops stride by the grid)
-      if (L.kind == 0)
-        hipLaunchKernelGGL(jxlhip::k_modular_rct, dim3(L.gx, gy, zn), dim3(256), 0, st, reinterpret_cast<const jxlhip::ModRct*>(dev + L.offset) + z);
-      else if (L.kind == 1)
-        hipLaunchKernelGGL(jxlhip::k_modular_palette, dim3(L.gx, gy, zn), dim3(256), 0, st, reinterpret_cast<const jxlhip::ModPalette*>(dev + L.offset) + z);
-      else if (L.kind == 2)
-        hipLaunchKernelGGL(jxlhip::k_modular_unsqueeze, dim3(L.gx, zn), dim3(64), 0, st, reinterpret_cast<const jxlhip::ModUnsqueeze*>(dev + L.offset) + z);
-      else if (L.kind == 5)  // (one workgroup per row: the full height, not the strided grid of the sample kernels)
-        hipLaunchKernelGGL(jxlhip::k_splines_add_batch, dim3(L.gy, zn), dim3(256), 0, st, reinterpret_cast<const jxlhip::SplineParams*>(dev + L.offset) + z);
-      else if (L.kind == 6)
-        hipLaunchKernelGGL(jxlhip::k_patches_add_batch, dim3(L.gy, zn), dim3(256), 0, st, reinterpret_cast<const jxlhip::PatchParams*>(dev + L.offset) + z);
-      else
-        hipLaunchKernelGGL(jxlhip::k_modular_output, dim3(L.gx, gy, zn), dim3(256), 0, st, reinterpret_cast<const jxlhip::ModOutput*>(dev + L.offset) + z);
-      HIP_TRY(hipGetLastError());
-    }
+// Builds (or re-uses) the description of a set in four steps: key, plan, place, remember. The plan
+// (jxh_modular_launch_plan.h) is a function of the set and of JXLHIP_MOD_LANES (measurement aid), so these are the key.
+// A changed variable over an unchanged set therefore describes the set anew, its two copies included (it used to change
+// the lanes of the next launch without a copy): the price of one key for everything the plan holds.
+static int PrepareModBatch(JxlHipContext* c0, JxlHipContext* const* ctxs, size_t n) {
+  JxlHipContext::Modular& M0 = c0->mod;
+  const int lanes_override = EnvInt("JXLHIP_MOD_LANES", 0);
+  if (M0.batch_set.Matches(ctxs, n) && M0.batch_lanes_override == lanes_override) return 0;
+  M0.batch_set.Forget();  // (what is on the device is no set's until both copies below have been made)
+
+  std::vector<modular_launch::ModStreamFrame> frames(n);
+  for (size_t i = 0; i < n; i++) {
+    const JxlHipContext::Modular& M = ctxs[i]->mod;
+    frames[i] = {M.streams_host.data(), M.stream_samples.data(), M.streams_host.size(), M.code_table_words.data(), M.code_table_words.size()};
+  }
+  std::vector<jxlhip::ModStream> flat;
+  modular_launch::ModBatchPlan plan = modular_launch::PlanModStreams(frames.data(), n, lanes_override, &flat);
+  std::vector<uint8_t> ops_blob;
+  std::vector<ModLaunch> launches;
+  ModularBuildOps(ctxs, n, &ops_blob, &launches);
+  plan.grids = modular_launch::ExpandModLaunches(launches);
+  if (EnvInt("JXLHIP_PACK_DEBUG", 0))
+    fprintf(stderr, "[modular pack] streams %u lanes %u workgroups %u lds %u tree_cap %u table_cap %u form %s\n", plan.n, plan.lanes, plan.workgroups,
+            plan.lds, plan.tree_cap, plan.table_cap, modular_launch::FormName(plan));
+
+  int r;
+  if ((r = M0.batch_streams.Ensure(flat.size() * sizeof(jxlhip::ModStream)))) return r;
+  HIP_TRY(hipMemcpy(M0.batch_streams.p, flat.data(), flat.size() * sizeof(jxlhip::ModStream), hipMemcpyHostToDevice));
+  if ((r = M0.batch_ops.Ensure(ops_blob.size() + 16))) return r;
+  if (!ops_blob.empty()) HIP_TRY(hipMemcpy(M0.batch_ops.p, ops_blob.data(), ops_blob.size(), hipMemcpyHostToDevice));
+
+  M0.batch_set.Remember(ctxs, n);
+  M0.batch_lanes_override = lanes_override;
+  M0.batch_plan = std::move(plan);
+  return 0;
+}
+static int LaunchModStreams(const JxlHipContext* c0) {
+  const modular_launch::ModBatchPlan& P = c0->mod.batch_plan;
+  if (!P.n) return 0;
+  auto kernel = P.wp ? (P.refs ? jxlhip::k_modular_streams<true, true> : jxlhip::k_modular_streams<true, false>)
+                     : (P.refs ? jxlhip::k_modular_streams<false, true> : jxlhip::k_modular_streams<false, false>);
+  if (P.lds > 48 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(P.lds)));
+  hipLaunchKernelGGL(kernel, dim3(P.workgroups), dim3(64), P.lds, c0->stream, c0->mod.batch_streams.as<jxlhip::ModStream>(), P.n, P.lanes,
+                     P.tree_cap, P.table_cap);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+static int ModularLaunchOps(const std::vector<modular_launch::ModGrid>& grids, const uint8_t* dev, hipStream_t st) {
+  for (const modular_launch::ModGrid& g : grids) {
+    const dim3 grid(g.grid[0], g.grid[1], g.grid[2]), block(g.block);
+    const uint8_t* at = dev + g.offset;
+    if (g.kind == 0)
+      hipLaunchKernelGGL(jxlhip::k_modular_rct, grid, block, 0, st, reinterpret_cast<const jxlhip::ModRct*>(at) + g.first);
+    else if (g.kind == 1)
+      hipLaunchKernelGGL(jxlhip::k_modular_palette, grid, block, 0, st, reinterpret_cast<const jxlhip::ModPalette*>(at) + g.first);
+    else if (g.kind == 2)
+      hipLaunchKernelGGL(jxlhip::k_modular_unsqueeze, grid, block, 0, st, reinterpret_cast<const jxlhip::ModUnsqueeze*>(at) + g.first);
+    else if (g.kind == 5)
+      hipLaunchKernelGGL(jxlhip::k_splines_add_batch, grid, block, 0, st, reinterpret_cast<const jxlhip::SplineParams*>(at) + g.first);
+    else if (g.kind == 6)
+      hipLaunchKernelGGL(jxlhip::k_patches_add_batch, grid, block, 0, st, reinterpret_cast<const jxlhip::PatchParams*>(at) + g.first);
+    else  // (3 the output, 4 the float planes)
+      hipLaunchKernelGGL(jxlhip::k_modular_output, grid, block, 0, st, reinterpret_cast<const jxlhip::ModOutput*>(at) + g.first);
+    HIP_TRY(hipGetLastError());
+  }
   return 0;
 }
 
@@ -2556,98 +2626,19 @@ extern "C" int jxlhip_modular_run_batch(JxlHipContext* const* ctxs, size_t n) {
     if (OwnPixelBytes(ctxs[i]) > ctxs[i]->rgb.cap) return JXLHIP_ERR_INVALID_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(c0->device));
-  if (n > 1) {
-    const int r = EnsureOwnStream(c0);
-    if (r) return r;
-  }
-  JxlHipContext::Modular& M0 = c0->mod;
-  if (!M0.batch_set.Matches(ctxs, n)) {
-    // every stream of every frame, largest first: the lanes of a wave then carry streams of similar length
-    struct Ref {
-      uint32_t samples;
-      const jxlhip::ModStream* s;
-    };
-    std::vector<Ref> all;
-    for (size_t i = 0; i < n; i++)
-      for (size_t j = 0; j < ctxs[i]->mod.streams_host.size(); j++) all.push_back({ctxs[i]->mod.stream_samples[j], &ctxs[i]->mod.streams_host[j]});
-    std::stable_sort(all.begin(), all.end(), [](const Ref& a, const Ref& b) { return a.samples > b.samples; });
-    std::vector<jxlhip::ModStream> flat(all.size() ? all.size() : 1);
-    for (size_t i = 0; i < all.size(); i++) flat[i] = *all[i].s;
-    int r = M0.batch_streams.Ensure(flat.size() * sizeof(jxlhip::ModStream));
-    if (r) return r;
-    HIP_TRY(hipMemcpy(M0.batch_streams.p, flat.data(), flat.size() * sizeof(jxlhip::ModStream), hipMemcpyHostToDevice));
-    M0.batch_set.Remember(ctxs, n);
-    M0.batch_n = uint32_t(all.size());
-    uint32_t cap = 0;  // LDS room for the largest tree of the batch that fits (waves whose streams share a tree stage it)
-    for (const Ref& q : all)
-      if (q.s->tree_nodes <= jxlhip::kModTreeLdsNodes && q.s->tree_nodes > cap) cap = q.s->tree_nodes;
-    M0.batch_tree_cap = cap;
-    M0.batch_wp = M0.batch_refs = false;  // the kernel form: what some stream of the launch needs
-    for (const Ref& q : all) {
-      M0.batch_wp = M0.batch_wp || q.s->uses_wp != 0;
-      M0.batch_refs = M0.batch_refs || q.s->num_props > 16;
-    }
-    uint32_t tcap = 0;  // likewise for the largest set of symbol tables that fits
-    for (size_t i = 0; i < n; i++)
-      for (uint32_t w : ctxs[i]->mod.code_table_words)
-        if (w <= jxlhip::kModTableLdsWords && w > tcap) tcap = w;
-    M0.batch_table_cap = tcap;
-    std::vector<uint8_t> ops_blob;
-    ModularBuildOps(ctxs, n, &ops_blob, &M0.batch_launches);
-    r = M0.batch_ops.Ensure(ops_blob.size() + 16);
-    if (r) return r;
-    if (!ops_blob.empty()) HIP_TRY(hipMemcpy(M0.batch_ops.p, ops_blob.data(), ops_blob.size(), hipMemcpyHostToDevice));
-  }
-  for (size_t i = 0; i < n; i++) {
-    int pw = ApplyPendingWait(ctxs[i]);
-    if (pw) return pw;
-  }
-  for (size_t i = 1; i < n; i++) {  // the launch runs on the first context's stream, after what the others still have in flight
-    if (!ctxs[i]->down_done) HIP_TRY(hipEventCreateWithFlags(&ctxs[i]->down_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ctxs[i]->down_done, ctxs[i]->stream));
-    HIP_TRY(hipStreamWaitEvent(c0->stream, ctxs[i]->down_done, 0));
-  }
-  {
-    const int tw = TensorsBeforeWriters(ctxs, n, c0->stream);
-    if (tw) return tw;
-  }
+  int r;
+  if (n > 1 && (r = EnsureOwnStream(c0))) return r;
+  if ((r = PrepareModBatch(c0, ctxs, n))) return r;
+  if ((r = JoinSetOnFirstStream(ctxs, n))) return r;
+  if ((r = TensorsBeforeWriters(ctxs, n, c0->stream))) return r;
   HIP_TRY(hipEventRecord(c0->ev[0], c0->stream));
-  if (M0.batch_n) {
-    // A stream is a chain of dependent latencies: as few streams per wave as still leaves every SIMD of the device a
-    // few waves (JXLHIP_MOD_LANES overrides: measurement aid). 384 lossless 4K frames = 53 760 streams: 32 lanes per wave
-    // 2 219 MP/s, 16 lanes 2 360, 8 lanes 1 864, 4 lanes 1 166: up to four waves per SIMD.
-    uint32_t lanes = 1;
-    while (lanes < 64 && M0.batch_n / lanes > 4096) lanes *= 2;
-    const int forced = EnvInt("JXLHIP_MOD_LANES", 0);
-    if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16 || forced == 32 || forced == 64) lanes = uint32_t(forced);
-    const uint32_t lds = jxlhip::ModLdsBytes(lanes, M0.batch_tree_cap, M0.batch_table_cap);
-    auto kernel = M0.batch_wp ? (M0.batch_refs ? jxlhip::k_modular_streams<true, true> : jxlhip::k_modular_streams<true, false>)
-                              : (M0.batch_refs ? jxlhip::k_modular_streams<false, true> : jxlhip::k_modular_streams<false, false>);
-    if (lds > 48 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(kernel, dim3((M0.batch_n + lanes - 1) / lanes), dim3(64), lds, c0->stream,
-                       M0.batch_streams.as<jxlhip::ModStream>(), M0.batch_n, lanes, M0.batch_tree_cap, M0.batch_table_cap);
-    HIP_TRY(hipGetLastError());
-  }
-  {
-    int r = ModularLaunchOps(M0.batch_launches, M0.batch_ops.as<uint8_t>(), c0->stream);
-    if (r) return r;
-  }
-  {
-    const int rr = LaunchResample(ctxs, n, c0->stream);
-    if (rr) return rr;
-  }
+  if ((r = LaunchModStreams(c0))) return r;
+  if ((r = ModularLaunchOps(c0->mod.batch_plan.grids, c0->mod.batch_ops.as<uint8_t>(), c0->stream))) return r;
+  if ((r = LaunchResample(ctxs, n, c0->stream))) return r;
   HIP_TRY(hipEventRecord(c0->ev[1], c0->stream));
-  {
-    const int tw = TensorsAfterWriters(ctxs, n, c0->stream);
-    if (tw) return tw;
-  }
-  c0->ev_valid[0] = true;
-  if (n > 1) {
-    if (!c0->batch_done) HIP_TRY(hipEventCreateWithFlags(&c0->batch_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c0->batch_done, c0->stream));
-    for (size_t i = 1; i < n; i++) ctxs[i]->pending_wait = c0->batch_done;
-  }
+  if ((r = TensorsAfterWriters(ctxs, n, c0->stream))) return r;
+  c0->ev_valid[0] = true;  // (the other contexts' ev_valid[0] stay as they are, unlike the reduced batch, which clears them)
+  if ((r = PublishBatchDone(ctxs, n))) return r;
   for (size_t i = 0; i < n; i++) ctxs[i]->have_frame = true;  // (the pixel download entry points need it)
   return 0;
 }
@@ -2764,13 +2755,7 @@ extern "C" int jxlhip_reduced_run_batch(JxlHipContext* const* ctxs, size_t n) {
   int r;
   if (n > 1 && (r = EnsureOwnStream(c0))) return r;
   const hipStream_t ls = c0->stream;
-  for (size_t i = 0; i < n; i++)
-    if ((r = ApplyPendingWait(ctxs[i]))) return r;
-  for (size_t i = 1; i < n; i++) {  // the launch runs on the first context's stream, after what the others still have in flight
-    if (!ctxs[i]->down_done) HIP_TRY(hipEventCreateWithFlags(&ctxs[i]->down_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ctxs[i]->down_done, ctxs[i]->stream));
-    HIP_TRY(hipStreamWaitEvent(ls, ctxs[i]->down_done, 0));
-  }
+  if ((r = JoinSetOnFirstStream(ctxs, n))) return r;
   // One context: its own block begins with the launch's descriptor. Several: their descriptors side by side with running
   // tile origins, on the set's first context, rebuilt only when the set changed.
   const jxlhip::ReducedDev* descs = c0->red_block.as<jxlhip::ReducedDev>();
@@ -2803,12 +2788,8 @@ extern "C" int jxlhip_reduced_run_batch(JxlHipContext* const* ctxs, size_t n) {
   HIP_TRY(hipEventRecord(c0->ev[1], ls));
   if ((r = TensorsAfterWriters(ctxs, n, ls))) return r;
   c0->ev_valid[0] = true;
-  for (size_t i = 1; i < n; i++) ctxs[i]->ev_valid[0] = false;
-  if (n > 1) {
-    if (!c0->batch_done) HIP_TRY(hipEventCreateWithFlags(&c0->batch_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c0->batch_done, ls));
-    for (size_t i = 1; i < n; i++) ctxs[i]->pending_wait = c0->batch_done;
-  }
+  for (size_t i = 1; i < n; i++) ctxs[i]->ev_valid[0] = false;  // (the Modular batch leaves them as they are)
+  if ((r = PublishBatchDone(ctxs, n))) return r;
   for (size_t i = 0; i < n; i++) ctxs[i]->red.ran = true;  // (the pixel download entry points need it)
   return 0;
 }

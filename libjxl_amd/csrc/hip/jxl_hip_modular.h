@@ -295,16 +295,7 @@ __device__ __forceinline__ int64_t ModPredict(uint32_t p, int64_t left, int64_t 
   }
 }
 
-constexpr uint32_t kModTreeLdsNodes = 2048;  // largest tree kept in LDS (32 KB)
-
-constexpr uint32_t kModTableLdsWords = 8192;  // largest symbol-table set kept in LDS (32 KB)
-
-// Dynamic LDS of a workgroup (one wave, `lanes` streams): the properties [property][lane], then `tree_cap` tree nodes,
-// then `table_cap` words of symbol tables.
-__host__ __device__ inline uint32_t ModLdsBytes(uint32_t lanes, uint32_t tree_cap, uint32_t table_cap) {
-  return kModMaxProps * lanes * 4 + tree_cap * 16 + table_cap * 4 + 64 * 4;  // (+ the weighted predictor's division table)
-}
-
+// (kModTreeLdsNodes, kModTableLdsWords and the workgroup's LDS layout, ModLdsBytes: jxl_hip_modular_abi.h)
 // One lane per stream, `lanes` (a power of two, <= 64) streams per workgroup; `streams` holds `n` descriptors.
 // WP / REFS = false compile the weighted predictor / the previous-channel properties out (the host picks the form no
 // stream of the launch needs more than): half the registers, twice the waves per SIMD to hide the chain's latencies.

@@ -72,6 +72,15 @@ struct ModStream {
 constexpr uint32_t kModWpEntry = 8;       // ints per row entry of the weighted predictor's scratch
 constexpr int kModMaxProps = 16 + 4 * 4;  // property 15 + up to four referenced previous channels (host refuses trees beyond)
 
+// k_modular_streams and its launch (csrc/host/jxh_modular_launch_plan.h) share these.
+constexpr uint32_t kModTreeLdsNodes = 2048;   // largest tree kept in LDS (32 KB)
+constexpr uint32_t kModTableLdsWords = 8192;  // largest symbol-table set kept in LDS (32 KB)
+// Dynamic LDS of a workgroup (one wave, `lanes` streams): the properties [property][lane], then `tree_cap` tree nodes,
+// then `table_cap` words of symbol tables.
+constexpr uint32_t ModLdsBytes(uint32_t lanes, uint32_t tree_cap, uint32_t table_cap) {
+  return kModMaxProps * lanes * 4 + tree_cap * 16 + table_cap * 4 + 64 * 4;  // (+ the weighted predictor's division table)
+}
+
 // ---- inverse transforms on channel rectangles: whole channels for the frame's own transforms, a group's rectangle of the
 // frame's buffers (or a private buffer) for the transforms of a group stream. The blocks carry pointers to the first
 // sample of each rectangle and the strides of the buffers they lie in.

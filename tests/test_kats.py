@@ -286,24 +286,11 @@ def test_upload_plan_under_sanitizers_on_real_descriptors(built, tmp_path):
     assert len(rules) > 30 and exercised == set(rules), sorted(set(rules) ^ exercised)
 
 
-def test_modular_upload_plan_under_sanitizers_on_real_descriptors(built, tmp_path):
-    """tests/c/modular_upload_kats.cc: what jxlhip_modular_upload computes on the host
-    (libjxl_amd/csrc/host/jxh_modular_upload_plan.h) built with AddressSanitizer + UBSan around
-    libjxl_amd/csrc/api/jxl_api.cc, whose jxlamd_modframe_upload hands the program the descriptor of each stream below:
-    every rule of the upload's checks refuses the one change that breaks it, with the code the upload always returned for
-    it; against fake base addresses the pool, the packed sections, the tree / code blob and every pointer of every stream,
-    code and channel descriptor agree with a reading written in the program; every inverse-transform operation is in one
-    launch of its own phase, level and kind, whose blocks address the operation's rectangles. Each rule is exercised by
-    some stream."""
-    import re
-    import numpy as np
+def modular_upload_streams(J):
+    """The thirteen Modular streams the upload's and the launch's plans are held on: (name, ["second"] for the frame behind
+    the first, bytes)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import local_streams
-    J = built
-    out = os.path.join(str(tmp_path), "modular_upload_kats")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
-                    "-Wno-unused-function", "-Wno-subobject-linkage", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "modular_upload_kats.cc"), "-o", out, "-lpthread"], check=True)
 
     def lossless(flags, size, channels, **kw):
         return J.encode_lossless(local_streams.lossless_image(J, size[0], size[1], channels, seed=7 + flags), flags, seed=flags, **kw)
@@ -316,7 +303,7 @@ def test_modular_upload_plan_under_sanitizers_on_real_descriptors(built, tmp_pat
         J.set_splines(None)
     patched = J.encode_patched(img, J.synth_image(64, 48, seed=9), [dict(x0=4, y0=6, xsize=20, ysize=16, positions=[(10, 10, 2, 0), (250, 170, 1, 0)])],
                                lossless=True)
-    runs = [("plain", [], lossless(0, (64, 48), 3)),
+    return [("plain", [], lossless(0, (64, 48), 3)),
             ("rct", [], lossless(16, (300, 280), 3)),
             ("rct_wp_alpha", [], lossless(16 | 4, (300, 280), 4)),
             ("rct_squeeze", [], lossless(16 | 8, (300, 280), 3)),             # stream 0, DC group and AC groups carry channels
@@ -330,6 +317,25 @@ def test_modular_upload_plan_under_sanitizers_on_real_descriptors(built, tmp_pat
             ("xyb_splines", [], with_splines),
             ("xyb_patches", ["second"], patched),
             ("fjxl_prefix", [], open(os.path.join(ROOT, "tests", "golden", "fjxl_300x280_rgb_e2.jxl"), "rb").read())]
+
+
+def test_modular_upload_plan_under_sanitizers_on_real_descriptors(built, tmp_path):
+    """tests/c/modular_upload_kats.cc: what jxlhip_modular_upload computes on the host
+    (libjxl_amd/csrc/host/jxh_modular_upload_plan.h) built with AddressSanitizer + UBSan around
+    libjxl_amd/csrc/api/jxl_api.cc, whose jxlamd_modframe_upload hands the program the descriptor of each stream below:
+    every rule of the upload's checks refuses the one change that breaks it, with the code the upload always returned for
+    it; against fake base addresses the pool, the packed sections, the tree / code blob and every pointer of every stream,
+    code and channel descriptor agree with a reading written in the program; every inverse-transform operation is in one
+    launch of its own phase, level and kind, whose blocks address the operation's rectangles. Each rule is exercised by
+    some stream."""
+    import re
+    J = built
+    out = os.path.join(str(tmp_path), "modular_upload_kats")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
+                    "-Wno-unused-function", "-Wno-subobject-linkage", "-I" + os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "c", "modular_upload_kats.cc"), "-o", out, "-lpthread"], check=True)
+
+    runs = modular_upload_streams(J)
     exercised = set()
     for name, args, data in runs:
         path = os.path.join(str(tmp_path), name + ".jxl")
