@@ -131,6 +131,37 @@ int jxlamd_frame_dc_quantised(const JxlAmdFrame* frame, int32_t* q, size_t n, ui
  * jxlhip_reduced_run. A reduced frame, or a whole one (it holds the same DC) that the reduced parse would have taken: the same
  * refusals apply to it here. jxlamd_frame_set_linear_output / _set_color_output apply as before. */
 int jxlamd_frame_upload_reduced(const JxlAmdFrame* frame, JxlHipContext* ctx);
+
+/* ---- Region decode: only the 256 x 256 groups a box of the output image reads. The window is the smallest rectangle of
+ * whole groups that covers the box grown by the reach of the frame's loop filters (0 to 7 pixels: Gaborish 1, EPF 2 / 3 / 6)
+ * and clipped to the frame. It is uploaded as a frame of its own (csrc/host/jxh_window_plan.h BuildWindowDesc): the context
+ * then IS a frame of the window's size for every later call (the stage launches and their batch forms, downloads, tensor and
+ * resized bindings; jxlhip_get_errors is indexed by window group), and every pixel of the caller's box equals the whole
+ * decode's bit for bit, since the same kernels run the same arithmetic on the same inputs. The window's DC image is the
+ * frame's (jxlhip_dc_window).
+ * jxlamd_frame_plan_window needs no device. box = {x0, y0, xsize, ysize} in the oriented output image (what
+ * JxlHipResizedOut takes; all zero: the whole image), num_channels as jxlhip_set_output_format's; window->orientation is
+ * read: the orientation the context's output undoes (jxlhip_set_output_orientation; 0 or 1: none), everything else is
+ * written. Returns non-zero (jxlamd_last_error) for a box jxlhip_set_output_resized would refuse at the image's size.
+ * reason != 0 (enum WholeFrameReason of jxh_window_plan.h: 1 partial or reduced parse, 2 upsampling, 3 chroma subsampling,
+ * 4 noise, 5 patches, 6 splines, 7 kUseDcFrame, 8 an output with alpha, 9 a single-section frame, 10 a frame of one group,
+ * 11 a window that equals the frame): the window is the whole frame, `box` the caller's, and jxlamd_frame_upload_window is
+ * jxlamd_frame_upload. A reason is a report, not an error.
+ * Deviation from a whole decode: a damaged AC section in a group the window does not read is not seen. */
+typedef struct {
+  uint32_t orientation;                 /* in: 1..8, EXIF numbering (0 = 1) */
+  uint32_t x0, y0, xsize, ysize;        /* the window in frame pixels */
+  uint32_t gx0, gy0, gxs, gys;          /* and in groups: frame group (gy0 + i / gxs) * frame groups per row + gx0 + i % gxs
+                                         * is the window's group i */
+  uint32_t box[4];                      /* the caller's box in the oriented coordinates of the window image: bind this one */
+  uint32_t groups_taken, groups_in_frame;
+  uint32_t reason;
+} JxlAmdWindow;
+size_t jxlamd_sizeof_window(void);
+int jxlamd_frame_plan_window(const JxlAmdFrame* frame, const uint32_t box[4], uint32_t num_channels, JxlAmdWindow* window);
+/* Uploads the window jxlamd_frame_plan_window planned for this frame (the plan is made again from window->orientation and
+ * the window's own rectangle, and must agree). Bind the output first, with window->box. */
+int jxlamd_frame_upload_window(const JxlAmdFrame* frame, JxlHipContext* ctx, const JxlAmdWindow* window);
 /* Extra channels (alpha, ...) of the frame. jxlamd_frame_extra_pending() != 0: their data continues behind the
  * coefficients of the AC group sections; run the entropy stage, then jxlamd_frame_finish_extra() (which reads the section
  * end positions from the context). jxlamd_frame_extra_plane() returns channel `index` as xsize * ysize int32 samples

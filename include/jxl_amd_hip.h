@@ -34,6 +34,7 @@ extern "C" {
 #define JXLHIP_ERR_NO_FRAME 2
 #define JXLHIP_ERR_STREAM 3 /* the entropy kernel flagged a corrupt AC section; see jxlhip_get_errors */
 #define JXLHIP_ERR_UNSUPPORTED 4
+#define JXLHIP_ERR_GUARD 5 /* a test entry found a write outside the buffer it watches */
 
 typedef struct JxlHipContext JxlHipContext;
 
@@ -663,6 +664,39 @@ int jxlhip_reduced_run(JxlHipContext* ctx);
 /* Same for `n` contexts of one device that each hold a reduced upload (any sizes, formats and bindings): ONE launch of the
  * kernel, then one launch pair of the resampler for those with a resized binding. */
 int jxlhip_reduced_run_batch(JxlHipContext* const* ctxs, size_t n);
+
+/* ---- The DC image of a window of a frame (region decode; jxl_amd.h "Region decode"): a rectangle of whole 256 x 256
+ * groups is uploaded as a frame of its own (a JxlHipFrameDesc of the window's size whose dc_device is what this call
+ * leaves), but its DC image must be the FRAME's: dequantised with each DC group's precision shift, looked up at the
+ * sample's place in the frame, and smoothed with the true neighbours across the window's edge. One kernel (k_dc_window,
+ * csrc/hip/jxl_hip_dc_window.h) makes the window's three dense float planes from the `apron`: the coded integers of the
+ * window grown by one block on every side and clipped to the frame. Samples on the FRAME's border are copied unsmoothed
+ * (compressed_dc.cc:141-147,171-175); samples on the window's edge elsewhere are smoothed from the apron. The arithmetic
+ * is DcDequantSample and DcSmoothSample of jxl_hip_dc.h: the planes equal that rectangle of the whole frame's DC image
+ * (jxlhip_frame_upload's k_dc_dequant + k_dc_smooth) bit for bit. All rectangles are in 8x8 blocks of the frame. */
+typedef struct JxlHipDcWindow {
+  uint32_t frame_xsize_blocks, frame_ysize_blocks;
+  uint32_t win_x0, win_y0, win_xsize, win_ysize;          /* the window */
+  uint32_t apron_x0, apron_y0, apron_xsize, apron_ysize;  /* the window grown by one block and clipped to the frame */
+  const int32_t* apron;                  /* host memory, [3][apron_ysize][apron_xsize]: the coded integers of X, Y, B */
+  const uint8_t* dc_extra_precision;     /* the FRAME's, per DC group of 256 x 256 blocks, row-major; NULL = 0, for a
+                                          * frame of one DC group only */
+  uint32_t num_dc_groups;                /* entries of dc_extra_precision */
+  float dc_step[3];
+  float dc_cfl_x, dc_cfl_b;
+  uint32_t dc_smoothing;                 /* != 0: AdaptiveDCSmoothing */
+} JxlHipDcWindow;
+/* Copies the apron to the device and runs the kernel on the copy stream, where the DC kernels of jxlhip_frame_upload run;
+ * complete when it returns. jxlhip_dc_window_planes hands out the [3][win_ysize][win_xsize] floats, in a buffer the
+ * context owns (NULL before the first call): valid until the context's next jxlhip_dc_window or its destruction, which
+ * covers the lifetime JxlHipFrameDesc::dc_device asks for. The descriptor is checked on the host first (csrc/host/jxh_window_plan.h enum DcWindowRule: a non-empty
+ * window inside the frame, the apron as stated, positive steps, a precision byte for every DC group the apron touches,
+ * planes of at most 2^24 samples); a refused one makes no device call. */
+int jxlhip_dc_window(JxlHipContext* ctx, const JxlHipDcWindow* window);
+const float* jxlhip_dc_window_planes(JxlHipContext* ctx);
+/* Test entry: the same, and the planes copied to host_out ([3][win_ysize][win_xsize] floats). The context's buffer gets a
+ * kilobyte of room behind the planes and is filled with a sentinel first; JXLHIP_ERR_GUARD when the room was written to. */
+int jxlhip_debug_dc_window(JxlHipContext* ctx, const JxlHipDcWindow* window, float* host_out);
 
 /* ---- Canvas: the frames of a multi-frame codestream composed on the device (lib/jxl/blending.cc, alpha.cc,
  * render_pipeline/stage_blending.cc; dec_cache.cc:268-290 for where it sits: after the colour conversion, in the output

@@ -210,6 +210,27 @@ class Frame:
         """Test access: the spline dictionary as parsed and the draw cache built from it (None: no splines)."""
         return _frame_splines(lib().jxlamd_frame_splines, self._h)
 
+    def plan_window(self, box, channels=3, orientation=1):
+        """The window of a region decode (jxlamd_frame_plan_window; no device): the rectangle of whole 256 x 256 groups that
+        box = (x0, y0, xsize, ysize) of the oriented output image needs (None: the whole image), for an output of `channels`
+        channels on a context that undoes `orientation` (set_output_orientation). A dict: x0 / y0 / xsize / ysize (frame
+        pixels), gx0 / gy0 / gxs / gys (groups), box (the caller's box in the window image: bind this one), groups (the
+        frame's group number of every window group), groups_taken, groups_in_frame, reason (0: a true window; else
+        WINDOW_REASONS[reason] says why the window is the whole frame) and orientation. HipContext.upload_window takes it."""
+        L = lib()
+        L.jxlamd_frame_plan_window.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(Window)]
+        L.jxlamd_sizeof_window.restype = ctypes.c_size_t
+        assert L.jxlamd_sizeof_window() == ctypes.sizeof(Window)
+        w = Window()
+        w.orientation = int(orientation)
+        b = (ctypes.c_uint32 * 4)(*([0, 0, 0, 0] if box is None else [int(v) for v in box]))
+        _check(L.jxlamd_frame_plan_window(self._h, b, int(channels), ctypes.byref(w)), "jxlamd_frame_plan_window")
+        out = {name: int(getattr(w, name)) for name, _ in Window._fields_ if name != "box"}
+        out["box"] = tuple(int(v) for v in w.box)
+        per_row = (self.info["xsize"] + 255) // 256
+        out["groups"] = [(w.gy0 + i // w.gxs) * per_row + w.gx0 + i % w.gxs for i in range(w.gxs * w.gys)]
+        return out
+
     def close(self):
         if self._h:
             lib().jxlamd_frame_free(self._h)
@@ -323,6 +344,35 @@ def frame_dc_extent(data):
     return int(need.value)
 
 
+class Window(ctypes.Structure):  # JxlAmdWindow
+    _fields_ = [("orientation", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32), ("xsize", ctypes.c_uint32),
+                ("ysize", ctypes.c_uint32), ("gx0", ctypes.c_uint32), ("gy0", ctypes.c_uint32), ("gxs", ctypes.c_uint32),
+                ("gys", ctypes.c_uint32), ("box", ctypes.c_uint32 * 4), ("groups_taken", ctypes.c_uint32),
+                ("groups_in_frame", ctypes.c_uint32), ("reason", ctypes.c_uint32)]
+
+
+# enum WholeFrameReason of csrc/host/jxh_window_plan.h: why a frame's window is the whole frame (0: a true window)
+WINDOW_REASONS = ("windowed", "partial", "upsampling", "subsampling", "noise", "patches", "splines", "dc_frame", "alpha",
+                  "single_section", "one_group", "window_is_frame")
+
+
+class DcWindow(ctypes.Structure):  # JxlHipDcWindow
+    _fields_ = [("frame_xsize_blocks", ctypes.c_uint32), ("frame_ysize_blocks", ctypes.c_uint32),
+                ("win_x0", ctypes.c_uint32), ("win_y0", ctypes.c_uint32), ("win_xsize", ctypes.c_uint32), ("win_ysize", ctypes.c_uint32),
+                ("apron_x0", ctypes.c_uint32), ("apron_y0", ctypes.c_uint32), ("apron_xsize", ctypes.c_uint32), ("apron_ysize", ctypes.c_uint32),
+                ("apron", ctypes.c_void_p), ("dc_extra_precision", ctypes.c_void_p), ("num_dc_groups", ctypes.c_uint32),
+                ("dc_step", ctypes.c_float * 3), ("dc_cfl_x", ctypes.c_float), ("dc_cfl_b", ctypes.c_float), ("dc_smoothing", ctypes.c_uint32)]
+
+
+def dc_apron(window, frame_size):
+    """(x0, y0, xsize, ysize) in blocks: the window grown by one block on every side and clipped to the frame (PlanDcApron of
+    csrc/host/jxh_window_plan.h)."""
+    x0, y0, xs, ys = window
+    fx, fy = frame_size
+    ax0, ay0 = max(x0 - 1, 0), max(y0 - 1, 0)
+    return ax0, ay0, min(x0 + xs + 1, fx) - ax0, min(y0 + ys + 1, fy) - ay0
+
+
 def frame_is_modular(data):
     """Whether the codestream's first frame is Modular-coded (ModFrame, upload_modular) or VarDCT (Frame, upload)."""
     L = lib()
@@ -431,6 +481,44 @@ class HipContext:
         b0, b1 = band if band else (0, 0)
         _check(lib().jxlamd_frame_upload_band(frame._h, self._h, b0, b1), "jxlamd_frame_upload_band")
         self.frame_info = dict(frame.info)
+
+    def upload_window(self, frame, window):
+        """Region decode (jxlamd_frame_upload_window): uploads the window frame.plan_window made as a frame of its own. The
+        context then is a frame of the window's size: frame_info has its sizes and group count, errors() is indexed by window
+        group (window["groups"] maps back). A window with a reason set is upload(frame)."""
+        L = lib()
+        L.jxlamd_frame_upload_window.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Window)]
+        w = Window()
+        for name, _ in Window._fields_:
+            if name != "box":
+                setattr(w, name, int(window[name]))
+        w.box = (ctypes.c_uint32 * 4)(*window["box"])
+        _check(L.jxlamd_frame_upload_window(frame._h, self._h, ctypes.byref(w)), "jxlamd_frame_upload_window")
+        self.frame_info = dict(frame.info)
+        if not window["reason"]:
+            fi = self.frame_info
+            fi["xsize"], fi["ysize"] = window["xsize"], window["ysize"]
+            fi["out_xsize"], fi["out_ysize"] = window["xsize"], window["ysize"]
+            fi["xsize_blocks"], fi["ysize_blocks"] = (window["xsize"] + 7) // 8, (window["ysize"] + 7) // 8
+            fi["num_groups"] = window["groups_taken"]
+
+    def debug_dc_window(self, q, window, extra_precision, step, cfl_x, cfl_b, smoothing=True, apron=None):
+        """Test entry (jxlhip_debug_dc_window): k_dc_window alone on the coded integer planes q [3, ys, xs] of a frame with
+        the DC groups' precision shifts `extra_precision` (None: all 0), for window = (x0, y0, xsize, ysize) in blocks ->
+        float32 [3, ysize, xsize]. apron: the rectangle handed over instead of the planned one (for the refusals)."""
+        q = np.ascontiguousarray(q, np.int32)
+        _, fys, fxs = q.shape
+        x0, y0, xs, ys = window
+        ax0, ay0, axs, ays = apron if apron is not None else dc_apron(window, (fxs, fys))
+        cut = np.ascontiguousarray(q[:, ay0:ay0 + ays, ax0:ax0 + axs])
+        ep = None if extra_precision is None else np.ascontiguousarray(extra_precision, np.uint8)
+        d = DcWindow(fxs, fys, x0, y0, xs, ys, ax0, ay0, axs, ays, cut.ctypes.data, None if ep is None else ep.ctypes.data,
+                     0 if ep is None else ep.size, (ctypes.c_float * 3)(*step), cfl_x, cfl_b, 1 if smoothing else 0)
+        out = np.empty((3, ys, xs), np.float32)
+        L = lib()
+        L.jxlhip_debug_dc_window.argtypes = [ctypes.c_void_p, ctypes.POINTER(DcWindow), ctypes.c_void_p]
+        _check(L.jxlhip_debug_dc_window(self._h, ctypes.byref(d), out.ctypes.data), "jxlhip_debug_dc_window")
+        return out
 
     def upload_reduced(self, frame):
         """The frame's DC image as a reduced (1/8-scale) image: a Frame(data, reduced=True) or a whole Frame. Then

@@ -21,6 +21,13 @@ struct JxlAmdFrame {
 namespace jxlamd_internal {
 // jxlamd_last_error's text of the calling thread (it lives in jxl_api.cc).
 void SetLastError(const std::string& text);
+// The JxlHipFrameDesc of the whole frame (jxl_api.cc; the band fields stay 0). `hold` keeps what the descriptor points at
+// beside the frame's own arrays. 0, or 1 with the thread's error text set.
+struct FrameDescHold {
+  std::vector<JxlHipPassDesc> pd;
+  std::vector<float> ups_kernel;
+};
+int FillFrameDesc(const JxlAmdFrame* f, JxlHipFrameDesc* out, FrameDescHold* hold);
 }  // namespace jxlamd_internal
 
 #endif  // JXL_AMD_FRAME_H_

@@ -393,18 +393,19 @@ int jxlamd_frame_debug_swap_blocks(JxlAmdFrame* f, uint32_t i, uint32_t j) {
   return 0;
 }
 
-int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t group_row_begin, uint32_t group_row_end) {
-  g_last_error.clear();
-  if (!f || !ctx) {
-    g_last_error = "invalid argument";
-    return 1;
-  }
+}  // extern "C"
+// The descriptor of the whole frame, every field stated once for jxlamd_frame_upload_band and jxlamd_frame_upload_window
+// (jxl_api_window.cc). `hold` keeps what the descriptor points at beside the frame's own arrays; 0, or 1 with the thread's
+// error text.
+int jxlamd_internal::FillFrameDesc(const JxlAmdFrame* f, JxlHipFrameDesc* out, FrameDescHold* hold) {
   const jxh::FramePlan& P = f->plan;
   if (P.reduced) {
     g_last_error = "the frame was parsed for a reduced decode (jxlamd_frame_parse_reduced): jxlamd_frame_upload_reduced takes it";
     return 1;
   }
-  JxlHipFrameDesc d;
+  JxlHipFrameDesc& d = *out;
+  std::vector<JxlHipPassDesc>& pd = hold->pd;
+  std::vector<float>& ups_kernel = hold->ups_kernel;
   memset(&d, 0, sizeof(d));
   d.xsize = uint32_t(P.dim.xsize);
   d.ysize = uint32_t(P.dim.ysize);
@@ -419,7 +420,7 @@ int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t 
   d.section_size = P.section_size.data();
   d.group_absent = P.group_absent.empty() ? nullptr : P.group_absent.data();
   d.first_section_bit_offset = P.first_section_bit_offset;
-  std::vector<JxlHipPassDesc> pd(P.passes.size());
+  pd.assign(P.passes.size(), JxlHipPassDesc());
   for (size_t p = 0; p < P.passes.size(); p++) {
     const jxh::PassTables& T = P.passes[p];
     pd[p].log_alpha = uint32_t(T.log_alpha);
@@ -509,8 +510,6 @@ int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t 
   const bool linear = co.active ? co.linear : P.ih.linear_tf;
   d.linear_output = P.ih.xyb_encoded ? (linear ? 1 : 0) : (P.fh.ycbcr ? 2 : 3);
   d.color_target = P.ih.xyb_encoded && co.active && co.target.tf ? &co.target : nullptr;
-  d.band_group_row_begin = group_row_begin;
-  d.band_group_row_end = group_row_end;
   d.has_noise = P.has_noise ? 1 : 0;
   FillSplines(P.has_splines, P.splines, &d.splines);
   memset(&d.patches, 0, sizeof(d.patches));
@@ -533,7 +532,6 @@ int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t 
   // dec_frame.cc:160-168: the number of visible frames before this one, and of invisible ones since (none are accepted)
   d.noise_frame_index[0] = uint32_t(P.frame_index);
   d.noise_frame_index[1] = uint32_t(P.nonvisible_index);
-  std::vector<float> ups_kernel;
   if (P.fh.upsampling != 1) {
     UpsamplingKernels(P.fh.upsampling, P.ih, &ups_kernel);
     d.upsampling = P.fh.upsampling;
@@ -541,7 +539,22 @@ int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t 
     d.out_ysize = uint32_t(P.ih.ysize);
     d.upsampling_kernel = ups_kernel.data();
   }
-  int r = jxlhip_frame_upload(ctx, &d);  // (copies everything it keeps: `pd` and the other locals may go)
+  return 0;
+}
+extern "C" {
+
+int jxlamd_frame_upload_band(const JxlAmdFrame* f, JxlHipContext* ctx, uint32_t group_row_begin, uint32_t group_row_end) {
+  g_last_error.clear();
+  if (!f || !ctx) {
+    g_last_error = "invalid argument";
+    return 1;
+  }
+  JxlHipFrameDesc d;
+  jxlamd_internal::FrameDescHold hold;
+  if (jxlamd_internal::FillFrameDesc(f, &d, &hold)) return 1;
+  d.band_group_row_begin = group_row_begin;
+  d.band_group_row_end = group_row_end;
+  int r = jxlhip_frame_upload(ctx, &d);  // (copies everything it keeps: `hold` may go)
   if (r) g_last_error = "jxlhip_frame_upload failed (" + std::to_string(r) + ")";
   return r;
 }

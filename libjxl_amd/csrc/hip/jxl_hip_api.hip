@@ -24,6 +24,7 @@
 #include "../host/jxh_modular_launch_plan.h"
 #include "../host/jxh_modular_upload_plan.h"
 #include "../host/jxh_reduced_plan.h"
+#include "../host/jxh_window_plan.h"
 #include "../host/jxh_resample_plan.h"
 #include "../host/jxh_set_memo.h"
 #include "../host/jxh_tensor_out.h"
@@ -38,6 +39,7 @@
 #include "jxl_hip_dc.h"
 #include "jxl_hip_resample.h"
 #include "jxl_hip_reduced.h"
+#include "jxl_hip_dc_window.h"
 
 namespace reduced = jxlhip::reduced;
 namespace upload = jxlhip::upload;
@@ -417,6 +419,9 @@ struct JxlHipContext {
     uint32_t batch_tiles = 0;
   } red;
   Buf red_block, red_batch;
+  // jxlhip_dc_window: the apron's integers with the frame's precision bytes behind them (one staged copy), and the window's
+  // three float planes, which the window's frame upload takes as its dc_device (`dc` is then a view of dcw_out).
+  Buf dcw_in, dcw_out;
 };
 
 // JXLHIP_ENTROPY=1 (a test hook): no frame takes the lane-parallel k_entropy_lanes, every frame the wave-per-section
@@ -659,7 +664,7 @@ static std::vector<Buf*> AllBufs(JxlHipContext* c) {
                 &c->enc_rgb, &c->enc_planes[0], &c->enc_planes[1], &c->enc_planes[2], &c->enc_act, &c->enc_acs, &c->enc_qf, &c->enc_off, &c->enc_dc, &c->enc_coef, &c->enc_lut, &c->enc_dq, &c->enc_ytox, &c->enc_ytob, &c->ups_planes, &c->enc_aq_cells, &c->enc_aq_map, &c->enc_aq_mask, &c->enc_aq_in, &c->enc_mask1x1,
                 &c->est_planes, &c->est_qf, &c->est_mask, &c->est_ytox, &c->est_ytob, &c->est_dq, &c->est_cand, &c->est_index, &c->est_at, &c->est_out, &c->est_scaled,
                 &c->srch_mask, &c->srch_zero, &c->srch_cand, &c->srch_index, &c->srch_table, &c->walk_table, &c->walk_acs, &c->walk_entropy,
-                &c->rs_block, &c->rs_tmp, &c->rs_src, &c->rs_batch, &c->red_block, &c->red_batch, &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
+                &c->rs_block, &c->rs_tmp, &c->rs_src, &c->rs_batch, &c->red_block, &c->red_batch, &c->dcw_in, &c->dcw_out, &c->ent_counts, &c->ent_status, &c->ent_grp, &c->ent_tab, &c->ent_rec, &c->ent_fl, &c->ent_small, &c->ent_out, &c->ent_obase};
   for (auto& pb : c->pass_bufs)
     for (Buf* b : {&pb.ctx_map, &pb.alias, &pb.cfg, &pb.orders, &pb.ptable, &pb.poffset, &pb.alias_packed}) all.push_back(b);
   return all;
@@ -2795,6 +2800,75 @@ extern "C" int jxlhip_reduced_run_batch(JxlHipContext* const* ctxs, size_t n) {
 }
 extern "C" int jxlhip_reduced_run(JxlHipContext* c) { return jxlhip_reduced_run_batch(&c, 1); }
 
+// ------------------------------------------------------------------------------- DC image of a window (jxl_hip_dc_window.h)
+// The descriptor is checked on the host; then the apron and the precision bytes leave in one staged copy on the copy
+// stream, the kernel follows them there, and the call waits for both (the planes are read by launches on other streams).
+extern "C" int jxlhip_dc_window(JxlHipContext* c, const JxlHipDcWindow* d) {
+  namespace window = jxlhip::window;
+  if (!c || !d) return JXLHIP_ERR_INVALID_ARGUMENT;
+  int r = window::CheckDcWindow(*d);
+  if (r) return r;
+  // whatever still reads the planes of an earlier window (a transform launch) has to be finished
+  HIP_TRY(hipSetDevice(c->device));
+  if ((r = ApplyPendingWait(c))) return r;
+  if ((r = StageReset(c))) return r;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
+  const size_t q_bytes = size_t(d->apron_xsize) * d->apron_ysize * 12;
+  const size_t ep_bytes = d->dc_extra_precision ? size_t(d->num_dc_groups) : 0;
+  const size_t out_bytes = size_t(d->win_xsize) * d->win_ysize * 12;
+  if ((r = c->dcw_in.Ensure(q_bytes + ep_bytes))) return r;
+  if ((r = c->dcw_out.Ensure(out_bytes))) return r;
+  void* st = nullptr;
+  if ((r = StageAlloc(c, q_bytes + ep_bytes, &st))) return r;
+  memcpy(st, d->apron, q_bytes);
+  if (ep_bytes) memcpy(static_cast<uint8_t*>(st) + q_bytes, d->dc_extra_precision, ep_bytes);
+  jxlhip::DcWindowParams P;
+  memset(&P, 0, sizeof(P));
+  P.q = c->dcw_in.as<int32_t>();
+  P.ep = ep_bytes ? c->dcw_in.as<uint8_t>() + q_bytes : nullptr;
+  P.out = c->dcw_out.as<float>();
+  P.ax0 = int(d->apron_x0); P.ay0 = int(d->apron_y0); P.axs = int(d->apron_xsize); P.ays = int(d->apron_ysize);
+  P.wx0 = int(d->win_x0); P.wy0 = int(d->win_y0); P.wxs = int(d->win_xsize); P.wys = int(d->win_ysize);
+  P.fxs = int(d->frame_xsize_blocks); P.fys = int(d->frame_ysize_blocks);
+  P.xgroups = (d->frame_xsize_blocks + window::kDcGroupBlocks - 1) / window::kDcGroupBlocks;
+  P.smoothing = d->dc_smoothing ? 1 : 0;
+  for (int ch = 0; ch < 3; ch++) P.step[ch] = d->dc_step[ch];
+  P.cfl_x = d->dc_cfl_x;
+  P.cfl_b = d->dc_cfl_b;
+  hipStream_t cs = CopyStream(c->device);
+  if (!cs) cs = c->stream;
+  HIP_TRY(hipMemcpyAsync(c->dcw_in.p, st, q_bytes + ep_bytes, hipMemcpyHostToDevice, cs));
+  hipLaunchKernelGGL(jxlhip::k_dc_window, dim3(window::TilesX(d->win_xsize), window::TilesY(d->win_ysize)), dim3(256), 0, cs, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->stage.done, cs));
+  c->stage.recorded = true;
+  HIP_TRY(WaitEvent(c->stage.done));
+  return 0;
+}
+extern "C" const float* jxlhip_dc_window_planes(JxlHipContext* c) { return c ? c->dcw_out.as<float>() : nullptr; }
+extern "C" int jxlhip_debug_dc_window(JxlHipContext* c, const JxlHipDcWindow* d, float* host_out) {
+  if (!c || !d || !host_out) return JXLHIP_ERR_INVALID_ARGUMENT;
+  int r = jxlhip::window::CheckDcWindow(*d);
+  if (r) return r;
+  // the output buffer with a kilobyte of room behind the planes, all of it filled with a sentinel first
+  constexpr size_t kTail = 1024;
+  constexpr int kSentinel = 0x7B;
+  const size_t out_bytes = size_t(d->win_xsize) * d->win_ysize * 12;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((r = c->dcw_out.Ensure(out_bytes + kTail))) return r;
+  HIP_TRY(hipMemset(c->dcw_out.p, kSentinel, out_bytes + kTail));
+  HIP_TRY(hipDeviceSynchronize());
+  if ((r = jxlhip_dc_window(c, d))) return r;
+  uint8_t tail[kTail];
+  HIP_TRY(hipMemcpy(host_out, c->dcw_out.p, out_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tail, c->dcw_out.as<uint8_t>() + out_bytes, kTail, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < kTail; i++)
+    if (tail[i] != kSentinel) return JXLHIP_ERR_GUARD;
+  return 0;
+}
+
 extern "C" {
 
 int jxlhip_run_transform_batch(JxlHipContext* const* ctxs, size_t n) {
@@ -3190,8 +3264,7 @@ int jxlhip_debug_resample(JxlHipContext* c, const float* src, uint32_t xsize, ui
 int jxlhip_set_output_orientation(JxlHipContext* c, uint32_t orientation) {
   if (!c || orientation < 1 || orientation > 8) return JXLHIP_ERR_INVALID_ARGUMENT;
   // EXIF numbering -> mirror x (1) | mirror y (2) | transpose (4): stage_write.cc:441-458
-  static const uint8_t kBits[9] = {0, 0, 1, 3, 2, 4, 6, 7, 5};
-  c->out_orient = kBits[orientation];
+  c->out_orient = jxlhip::window::OrientBits(orientation);
   c->generation++;
   return 0;
 }

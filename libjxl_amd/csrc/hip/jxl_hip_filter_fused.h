@@ -21,6 +21,7 @@
 
 #include <type_traits>
 
+#include "../host/jxh_filter_halo.h"
 #include "jxl_hip_color.h"
 #include "jxl_hip_filter_abi.h"
 #include "jxl_hip_kernels.h"
@@ -46,9 +47,7 @@ struct FusedFilterParams {
 // the host's launch plan)
 constexpr int kFusedThreads = 512;  // 8 waves per tile: two resident tiles give every SIMD four waves to hide LDS latency
 constexpr int kFusedSigW = kFusedTW / 8 + 3, kFusedSigH = kFusedTH / 8 + 3;  // sigma blocks around a tile
-__host__ __device__ constexpr int FusedHalo(bool gab, int epf) {
-  return (gab ? 1 : 0) + (epf >= 3 ? 3 : 0) + (epf >= 1 ? 2 : 0) + (epf >= 2 ? 1 : 0);
-}
+// (FusedHalo(gab, epf), the pixels a tile reads around itself: ../host/jxh_filter_halo.h, shared with the host's window plan)
 __host__ __device__ constexpr size_t FusedLdsBytes(bool gab, int epf) {
   return (size_t(2) * 3 * (kFusedTW + 2 * FusedHalo(gab, epf)) * (kFusedTH + 2 * FusedHalo(gab, epf)) + kFusedSigW * kFusedSigH) *
          sizeof(float);

@@ -6,6 +6,10 @@ in the layout and type the consumer asked for, into memory the consumer owns. to
     crops = torch_io.decode_batch_to_tensor(datas, size=(224, 224), boxes=boxes)  # any sizes: crop + antialiased resize
     thumbs = torch_io.decode_batch_to_tensor(datas, size=(224, 224), reduce=8)    # from the 1/8-scale DC image: no AC decode
 
+A crop (size and box) of a VarDCT frame decodes only the 256 x 256 groups the box reads (region=True, the default: Frame.
+plan_window, HipContext.upload_window); the tensor is bit for bit the one region=False gives, which decodes the whole frame.
+One deviation: a damaged AC section in a group the box does not read goes unnoticed.
+
 Float types hold v * (1 / std[c]) + (-mean[c] / std[c]) of the decoder's float sample v in [0, 1] (scale and bias computed
 in float32, the product and the sum each rounded to float32, then to the type); uint8 holds the dithered 8-bit sample.
 The tensor's stream (torch.cuda.current_stream() unless given) is ordered before and behind the writes on the device:
@@ -81,6 +85,20 @@ def bind_resized(ctx, tensor, layout="CHW", box=None, mean=None, std=None, clamp
     ctx._bound_tensor = tensor  # keeps the memory alive while it is bound
 
 
+def _upload_crop(c, f, out, layout, box, mean, std, clamp, channels, region):
+    """The VarDCT upload of a crop: binds `out` as the resized output of `box` and uploads the frame; with `region` and a
+    box, only the window of groups the box needs (the box translated into the window image). Returns the frame's group
+    number of every group the context holds."""
+    if region and box is not None:
+        w = f.plan_window(box, channels)
+        bind_resized(c, out, layout, w["box"], mean, std, clamp)
+        c.upload_window(f, w)
+        return w["groups"]
+    bind_resized(c, out, layout, box, mean, std, clamp)
+    c.upload(f)
+    return list(range(f.info["num_groups"]))
+
+
 def _alloc(shape_chw, dtype, layout, device):
     c, h, w = shape_chw
     return torch.empty((c, h, w) if layout == "CHW" else (h, w, c), dtype=dtype, device="cuda:%d" % device)
@@ -129,12 +147,14 @@ def _decode_reduced(datas, outs, layout, mean, std, clamp, boxes, resized):
 
 
 def decode_to_tensor(data, dtype=torch.float16, layout="CHW", mean=None, std=None, clamp=False, channels=3, device=0, out=None,
-                     size=None, box=None, reduce=1):
+                     size=None, box=None, reduce=1, region=True):
     """One-shot: a VarDCT or Modular codestream's first frame -> a device tensor (allocated unless `out` is given).
     size = (height, width): the image, or box = (x0, y0, xsize, ysize) of it, is resized to that size on the device
     (bind_resized); an `out` given with it must have that size. Without `size` the tensor has the image's own size.
     reduce=8: from the frame's 1/8-scale DC image instead (VarDCT frames; `data` may be a prefix of frame_dc_extent(data)
     bytes): the tensor is (C, ceil(H / 8), ceil(W / 8)) without `size`, and `box` is in reduced-image coordinates.
+    region=True: with `size` and `box`, a VarDCT frame decodes only the groups the box reads (the same tensor, bit for bit;
+    a damaged section elsewhere in the frame is then not seen); region=False decodes the whole frame.
     Raises JxlAmdError on sections or streams the kernels flagged as corrupt."""
     if box is not None and size is None:
         raise ValueError("box needs size")
@@ -159,7 +179,8 @@ def decode_to_tensor(data, dtype=torch.float16, layout="CHW", mean=None, std=Non
                 out = _alloc((channels, int(size[0]), int(size[1])), dtype, layout, device)
             elif _image_size(out, layout) != (int(size[0]), int(size[1])):
                 raise ValueError("out is %r for size %r" % (tuple(out.shape), tuple(size)))
-            bind_resized(c, out, layout, box, mean, std, clamp)
+            if modular:
+                bind_resized(c, out, layout, box, mean, std, clamp)
         else:
             if out is None:
                 out = _alloc((channels, h, w), dtype, layout, device)
@@ -173,18 +194,22 @@ def decode_to_tensor(data, dtype=torch.float16, layout="CHW", mean=None, std=Non
             if r:
                 raise J.JxlAmdError("corrupt Modular streams: %r" % [(i, s) for i, s in enumerate(status) if s])
         else:
-            c.upload(f)
+            if size is not None:
+                groups = _upload_crop(c, f, out, layout, box, mean, std, clamp, channels, region)
+            else:
+                c.upload(f)
+                groups = list(range(f.info["num_groups"]))
             c.run_all()
             r, flags = c.errors()
-            if r:
-                raise J.JxlAmdError("corrupt AC sections: %r" % [(g, e) for g, e in enumerate(flags) if e])
+            if r:  # (frame group numbers: a window's groups are mapped back)
+                raise J.JxlAmdError("corrupt AC sections: %r" % [(groups[g], e) for g, e in enumerate(flags) if e])
         return out
     finally:
         c.close()
         f.close()
 
 
-def _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device, size, boxes):
+def _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device, size, boxes, region):
     """decode_batch_to_tensor with `size`: frames of any size, VarDCT and Modular mixed, each cropped to its box and resized
     into out[i]. The VarDCT contexts share the three batched stage launches, the Modular ones run_modular_batch; the resample
     passes are one launch pair per family."""
@@ -199,18 +224,19 @@ def _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device,
     elif tuple(out.shape) != (n, channels, hh, ww):
         raise ValueError("out is %r, size %r needs %r" % (tuple(out.shape), tuple(size), (n, channels, hh, ww)))
     modular = [J.frame_is_modular(d) for d in datas]
-    frames, ctxs = [], []
+    frames, ctxs, groups = [], [], []
     try:
         for d, m in zip(datas, modular):
             frames.append(J.ModFrame(d) if m else J.Frame(d))
         for i, f in enumerate(frames):
             c = J.HipContext(device)
             ctxs.append(c)
-            bind_resized(c, out[i], "CHW", boxes[i], mean, std, clamp)
             if modular[i]:
+                bind_resized(c, out[i], "CHW", boxes[i], mean, std, clamp)
                 c.upload_modular(f)
+                groups.append(None)
             else:
-                c.upload(f)
+                groups.append(_upload_crop(c, f, out[i], "CHW", boxes[i], mean, std, clamp, channels, region))
         var = [c for c, m in zip(ctxs, modular) if not m]
         mod = [c for c, m in zip(ctxs, modular) if m]
         if var:
@@ -227,7 +253,7 @@ def _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device,
             else:
                 r, flags = c.errors()
                 if r:
-                    raise J.JxlAmdError("frame %d: corrupt AC sections: %r" % (i, [(g, e) for g, e in enumerate(flags) if e]))
+                    raise J.JxlAmdError("frame %d: corrupt AC sections: %r" % (i, [(groups[i][g], e) for g, e in enumerate(flags) if e]))
         return out
     finally:
         for c in ctxs:
@@ -264,17 +290,18 @@ def _decode_batch_reduced(datas, out, dtype, mean, std, clamp, channels, device,
 
 
 def decode_batch_to_tensor(datas, out=None, dtype=torch.float16, mean=None, std=None, clamp=False, channels=3, device=0, size=None,
-                           boxes=None, reduce=1):
+                           boxes=None, reduce=1, region=True):
     """VarDCT frames of one size -> one (N, C, H, W) tensor: a context per frame, each bound to out[i], and one launch per
     stage for the whole set (run_entropy_batch / run_transform_batch / run_filter_color_batch). With size = (height, width)
     the frames may differ in size and kind (VarDCT, Modular); each is resized to that size, frame i cropped to boxes[i] first
     (a box (x0, y0, xsize, ysize) or None per frame). reduce=8: every frame's 1/8-scale DC image instead (VarDCT frames;
-    datas[i] may be a prefix of frame_dc_extent bytes; boxes in reduced-image coordinates), one launch for the set."""
+    datas[i] may be a prefix of frame_dc_extent bytes; boxes in reduced-image coordinates), one launch for the set.
+    region=True: with `size`, a VarDCT frame that has a box decodes only the groups the box reads, as in decode_to_tensor."""
     _check_reduce(reduce)
     if reduce == 8:
         return _decode_batch_reduced(datas, out, dtype, mean, std, clamp, channels, device, size, boxes)
     if size is not None:
-        return _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device, size, boxes)
+        return _decode_batch_resized(datas, out, dtype, mean, std, clamp, channels, device, size, boxes, region)
     if boxes is not None:
         raise ValueError("boxes needs size")
     frames = [J.Frame(d) for d in datas]
