@@ -701,6 +701,14 @@ class HipContext:
         self.frame_info = dict(mframe.info)
         self.frame_info["out_xsize"], self.frame_info["out_ysize"] = mframe.info["xsize"], mframe.info["ysize"]
 
+    def upload_modular_desc(self, desc, num_streams, xsize, ysize):
+        """jxlhip_modular_upload of a hand-made descriptor: `desc` is a ctypes structure laid out as JxlHipModFrameDesc
+        (include/jxl_amd_hip.h) whose arrays the caller keeps alive for the call."""
+        L = lib()
+        L.jxlhip_modular_upload.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.jxlhip_modular_upload(self._h, ctypes.byref(desc)), "jxlhip_modular_upload")
+        self.frame_info = dict(num_streams=int(num_streams), xsize=int(xsize), ysize=int(ysize), out_xsize=int(xsize), out_ysize=int(ysize))
+
     def run_modular(self):
         _check(lib().jxlhip_modular_run(self._h), "jxlhip_modular_run")
 
@@ -711,11 +719,13 @@ class HipContext:
         r = lib().jxlhip_modular_status(self._h, st, eb, n)
         return r, list(st)[:n], list(eb)[:n]
 
-    def modular_buffer(self, index):
-        need = self.frame_info["xsize"] * self.frame_info["ysize"]
-        out = np.empty(need, np.int32)
+    def modular_buffer(self, index, shape=None):
+        """Channel buffer `index` after the run; shape = (h, w) of a buffer that does not have the frame's size."""
+        h, w = shape if shape is not None else (self.frame_info["ysize"], self.frame_info["xsize"])
+        need = w * h
+        out = np.empty(max(need, 1), np.int32)
         _check(lib().jxlhip_modular_download_buffer(self._h, index, out.ctypes.data, need), "jxlhip_modular_download_buffer")
-        return out.reshape(self.frame_info["ysize"], self.frame_info["xsize"])
+        return out[:need].reshape(h, w)
 
     def pixels(self):
         """The interleaved result in the format of set_output_format (default RGB8)."""
